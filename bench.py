@@ -6,7 +6,16 @@ in HBM: packed quasi-mapping hit lists -> equivalence classes (start / addGroup 
 -> effective lengths -> EM (or VBEM) to convergence -> TPM / NumReads.  Read parsing and the
 quasi-mapper are third-party code outside the path and outside every timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|small]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|small] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given, and prints
+the result line.  --full adds, after the timed steps, everything else the benchmark measures: the step from host-pinned hit
+lists, the roofline (the sweep timed on its own + the committed PMC traffic), the bootstrap / Gibbs legs, the CPU baselines
+and the parity against the oracle, and at N > 1 the all-reduce and the other EM mode (--no-* switch single legs off).
+
+--dump-outputs DIR writes what the last timed step computed, as float64 .npy files: num_reads (estCount), tpm and
+effective_length per transcript, class_counts and class_label_lengths per equivalence class (canonical order).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 N = 1 : the configuration BASELINE.json's metric is quoted on ("... 200k-txp index"): configs[2], "cfg3" -- 400M
         paired-end fragments, 200k-transcript index, VBEM + empirical fragment-length correction; it fits one GPU
@@ -18,12 +27,13 @@ N > 1 : launched by torch.distributed.run, one rank per GPU.  STRONG scaling (BA
         with one exchange and the EM runs on the merged classes (sailfish_amd/distributed.py).  --weak gives every
         rank its own R reads instead (the job grows with N).
 
-Rank 0 prints ONE JSON line (metric, value, roofline, cpu_baseline ...).
+Rank 0 prints ONE JSON line (metric, value, ms_per_step, phase_ms ...; with --full also roofline, cpu_baseline ...).
 """
 import argparse
 import json
 import math
 import os
+import subprocess
 import sys
 import time
 
@@ -40,6 +50,7 @@ WORKLOADS = {
     "cfg3": (200_000, 4_000_000, 400_000_000, True, True),
 }
 HBM_PEAK_GBS = 8000.0   # MI355X spec (MI355X_MICROARCH.md): 8 TB/s HBM3E
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together
 
 
 def parse():
@@ -50,17 +61,57 @@ def parse():
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
     ap.add_argument("--em-mode", default="auto", choices=["auto", "replicated", "sharded"])
     ap.add_argument("--weak", action="store_true", help="N > 1: every rank gets its own R reads (weak scaling) instead of R/N")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-pinned", action="store_true", help="skip the leg that re-runs the step with the hit lists in pinned host memory")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs the headline figure does not need: host-pinned step, roofline, "
+                         "bootstrap / Gibbs, CPU baselines and parity, and at N > 1 the all-reduce and the other EM mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline / parity legs")
+    ap.add_argument("--no-host-pinned", action="store_true", help="--full: skip the leg that re-runs the step with the hit lists in pinned host memory")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
     ap.add_argument("--one-device", action="store_true", help="dry run: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--no-compare-em-modes", action="store_true",
-                    help="N > 1: skip the step in the OTHER EM mode (sharded <-> replicated) that is run and reported after the timed steps")
-    ap.add_argument("--no-sampling", action="store_true", help="N = 1: skip the bootstrap / Gibbs (BASELINE config 5) legs after the timed steps")
+                    help="--full, N > 1: skip the step in the OTHER EM mode (sharded <-> replicated) that is run and reported after the timed steps")
+    ap.add_argument("--no-sampling", action="store_true", help="--full, N = 1: skip the bootstrap / Gibbs (BASELINE config 5) legs after the timed steps")
     ap.add_argument("--gibbs-draws", type=int, default=1000)
     ap.add_argument("--bootstrap-draws", type=int, default=6)
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the baseline sample")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+def step_outputs(exp, quant, info):
+    """What a caller of the timed path receives from one step, copied to the host as float64 arrays: the per-transcript
+    estimates (NumReads = estCount, TPM, effective lengths) and the class table the EM ran on (counts and label lengths,
+    canonical order)."""
+    txps = exp.transcripts()
+    vec = quant.last_vec
+    rowptr = (vec.rowptr.to(torch.int64) & 0xFFFFFFFF)                # uint32 bits held in int32
+    out = {
+        "num_reads": txps.estCount,
+        "tpm": info["tpm"],
+        "effective_length": txps.EffectiveLength,
+        "class_counts": vec.counts,
+        "class_label_lengths": rowptr[1:] - rowptr[:-1],
+    }
+    return {k: v.detach().to("cpu", torch.float64).numpy() for k, v in out.items()}
+
+
+def dump_outputs(dirpath, arrays):
+    """DIR/<name>.npy for every array; when all of them together would exceed DUMP_LIMIT_BYTES, every array longer than its
+    share is cut to a fixed, seeded sample of its elements (positions sorted, the same for equal lengths)."""
+    os.makedirs(dirpath, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096) // 8 // max(len(arrays), 1)
+    total = sum(a.size for a in arrays.values()) * 8
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES - 4096 and a.size > share:
+            idx = np.sort(np.random.default_rng(20261016).choice(a.size, share, replace=False))
+            a = a[idx]
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline_full(vec, ref_len_np, ids_t, off_t, n_total, use_vbem, fl_counts):
@@ -194,9 +245,11 @@ def _relaunch_under_torchrun(a):
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush(); sys.stderr.flush()
-    os.execv(sys.executable, cmd)
+    rc = subprocess.call(cmd, env=env)               # a child process of its own (this one never opens the GPU)
+    sys.exit(rc if rc >= 0 else 128 - rc)            # killed by a signal: the shell's 128 + signal
 
 
 def main():
@@ -284,12 +337,16 @@ def main():
     total_reads = R_total * a.steps
     value = total_reads / dt
 
+    # ---- the last timed step's outputs, before any --full leg runs the step again
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step_outputs(exp, quant, info))
+
     # ---- the same step with the hit lists in HOST-PINNED memory (SURVEY 8d / BASELINE.md "Timed region": packed hit lists
     # resident in host-pinned memory -> ... -> TPM).  sfgpu_eq_add_batch_host streams the batch through two device staging
     # buffers (copy of chunk k + 1 on its own stream while chunk k is built), so the step costs its PCIe transfer plus
     # the build of the last chunk plus EM.  PCIe-inclusive: reported next to `value`, never as `value`.
     host_leg = None
-    if not a.no_host_pinned:
+    if a.full and not a.no_host_pinned:
         # every rank pins ITS shard (its own PCIe link); a rank that cannot (pinned allocation) must not leave the others in a
         # collective: the ok flag is agreed on first, then all ranks run the leg or none does
         h_ids = h_off = None
@@ -329,91 +386,92 @@ def main():
         del h_ids, h_off
     st = info["em_stats"]
     C, L = info["n_classes"], info["nnz"]
-
-    # ---- roofline of the dominant kernel, measured live with HIP events ------------------------
     # EM sweep: algorithmic bytes per launch, aux-weight-free variant:
     #   B_iter' = 4L + 8C + 48M   (+16M for VBEM's expTheta vector)
     b_iter = 4 * L + 8 * C + 48 * M + (16 * M if use_vbem else 0)
-    sweep_ms = quant.time_sweep(200)
     em_loop_ms_per_iter = st["loop_ms"] / max(st["iters"], 1)
-    # class build: B_read = 4*h + 4 (offset) + 16 (one slot probe) bytes per read
-    b_read = 4.0 * n_hits / R_local + 20.0
     build_ms = info["t_build_ms"]
     em_ms = info["t_em_ms"]
-    # HBM bytes per launch from the PMC passes committed under profiles/ (separate rocprofv3 runs of
-    # this same command; FETCH_SIZE x2 for the wide streaming loads of the sweep, raw for the random
-    # probes of the insert kernel -- see profiles/r1*_pmc_summary.md).  null when no profile matches.
-    traffic_em = traffic_em_iter = traffic_ins = traffic_src = None
-    try:
-        pmc_path = os.path.join(ROOT, "profiles", f"pmc_{a.workload}.json")
-        if not os.path.exists(pmc_path):
-            pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        pmc = json.load(open(pmc_path))
-        if pmc.get("workload") == a.workload and world == 1:
-            k = pmc["kernels"]
-            bytes_of = lambda e: ((2 if e.get("fetch_x2") else 1) * e["fetch_kib_per_launch"] + e["write_kib_per_launch"]) * 1024
-            # (kernel names carry their template arguments: k_sweep_lds<VB, GATHER>, k_part_route<RING>; the instance with the
-            #  most launches is the one the step ran)
-            pick = lambda prefix: max((v for n, v in k.items() if n == prefix or (n.startswith(prefix) and n[len(prefix)] in "<,>")),
-                                      key=lambda v: v.get("launches", 0), default=None)
-            # k_sweep_lds<VB, GATHER, FUSED>: the plain sweep (what time_sweep launches) and the fused iteration are different instances
-            vbs = "true" if use_vbem else "false"
-            plain = [v for n, v in k.items() if n.startswith(f"k_sweep_lds<{vbs}") and (n.count(",") == 1 or n.endswith(", false>"))]
-            fusedk = [v for n, v in k.items() if n.startswith(f"k_sweep_lds<{vbs}") and n.count(",") == 2 and n.endswith(", true>")]
-            if plain:
-                traffic_em = bytes_of(max(plain, key=lambda v: v.get("launches", 0)))
-            if fusedk:
-                traffic_em_iter = bytes_of(max(fusedk, key=lambda v: v.get("launches", 0)))
-            # the persistent loop (round 5): ONE launch holds all iterations -- its counters divided by the steps it ran (the iterations
-            # + the one sweep that runs for nothing before the stop is known)
-            persk = [v for n, v in k.items() if n.startswith(f"k_em_persist<{vbs}")]
-            if persk and st.get("persistent"):
-                traffic_em_iter = bytes_of(max(persk, key=lambda v: v.get("launches", 0))) / (st["iters"] + 1)
-            # class build = the partition kernels of one sub-batch (k_insert on the generic path)
-            parts = [v for v in (pick("k_part_route"), pick("k_part_insert")) if v] or [v for v in (pick("k_insert"),) if v]
-            if parts:
-                traffic_ins = sum(bytes_of(e) for e in parts)
-            # not re-measured by this run: it comes from the committed PMC passes of the same command
-            traffic_src = f"{os.path.relpath(pmc_path, ROOT)} ({pmc.get('source', '?')}; separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, " \
-                          f"FETCH x2 for 16-B-per-lane streaming kernels)"
-    except (OSError, ValueError, KeyError):
-        pass
-    n_ins = max(int(info["insert_launches"]), 1)
-    ins_ms = info["t_insert_ms"] / n_ins
-    # The EM is reported twice, and neither figure borrows from the other (round-3 review: B_iter' over the sweep kernel's time
-    # alone over-stated it):
-    #   roofline_em_iteration : the WHOLE iteration's algorithmic bytes B_iter' over the time one iteration takes in the loop as it
-    #                           runs (sweep + per-transcript update + what a chunk boundary costs) -- the figure to quote;
-    #   roofline_em_sweep     : the sweep kernel alone, with the bytes the SWEEP moves: labels 4 L + rowptr / count 8 C + the
-    #                           x vector it gathers from (8 M) + one partial sum per transcript it publishes (8 M); the other
-    #                           32 M (+ 16 M VBEM) of B_iter' are the update's.
-    b_sweep = 4 * L + 8 * C + 16 * M
     fused = bool(st.get("fused"))
-    roof_em = dict(bound="hbm", kernel="k_sweep_lds" + (" (the plain sweep, timed outside the loop: the loop itself runs it fused with the update)" if fused else ""), achieved=b_sweep / (sweep_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS,
-                   unit="GB/s", frac=b_sweep / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, traffic=traffic_em, traffic_source=traffic_src,
-                   bytes_per_launch=b_sweep, bytes_formula="4 L + 8 C + 16 M (sweep only: labels, rowptr + count, x gathered, partials published)",
-                   avg_launch_ms=sweep_ms, launches_per_step=st["iters"])
-    it_s = em_loop_ms_per_iter * 1e-3
-    persistent = bool(st.get("persistent"))
-    roof_em_iter = dict(bound="hbm", kernel=("one EM iteration inside the persistent loop (k_em_persist: ONE launch per optimize(); the device time of the launch / its iterations)"
-                                            if persistent else
-                                            "one EM iteration as the loop runs it (ONE kernel: the update of the iteration before at the head of the sweep; + chunk boundaries)"
-                                            if fused else "one EM iteration as the loop runs it (sweep + update + chunk boundaries)"),
-                        achieved=b_iter / it_s / 1e9, peak=HBM_PEAK_GBS, unit="GB/s", frac=b_iter / it_s / 1e9 / HBM_PEAK_GBS,
-                        traffic=(traffic_em_iter if fused else None), traffic_source=(traffic_src if fused else None),
-                        bytes_per_launch=b_iter, bytes_formula="B_iter' = 4 L + 8 C + 48 M (+ 16 M VBEM), SURVEY 8d aux-weight-free variant",
-                        avg_launch_ms=em_loop_ms_per_iter, launches_per_step=(1 if persistent else st["iters"]), iterations_per_step=st["iters"], persistent=persistent)
-    # class build: SURVEY 8d's B_read (ids + offset + one 16-byte slot probe) and, next to it, the COMPULSORY bytes alone
-    # (ids + offset: what any builder must read), so that the probe term cannot flatter the fraction
-    b_comp = 4.0 * n_hits / R_local + 4.0
-    roof_build = dict(bound="hbm", kernel=info.get("insert_kernels", "k_insert"), achieved=b_read * R_local / n_ins / (ins_ms * 1e-3) / 1e9,
-                      peak=HBM_PEAK_GBS, unit="GB/s",
-                      frac=b_read * R_local / n_ins / (ins_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, traffic=traffic_ins, traffic_source=traffic_src,
-                      bytes_per_launch=b_read * R_local / n_ins, avg_launch_ms=ins_ms, launches_per_step=n_ins,
-                      frac_compulsory_bytes=b_comp * R_local / n_ins / (ins_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                      compulsory_bytes_per_read=b_comp, bytes_per_read=b_read,
-                      frac_of_whole_phase=b_read * R_local / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-    dominant = roof_em if sweep_ms * st["iters"] >= info["t_insert_ms"] else roof_build
+
+    # ---- --full: roofline of the dominant kernel, measured live with HIP events ----------------
+    if a.full:
+        sweep_ms = quant.time_sweep(200)
+        # class build: B_read = 4*h + 4 (offset) + 16 (one slot probe) bytes per read
+        b_read = 4.0 * n_hits / R_local + 20.0
+        # HBM bytes per launch from the PMC passes committed under profiles/ (separate rocprofv3 runs of
+        # this same command; FETCH_SIZE x2 for the wide streaming loads of the sweep, raw for the random
+        # probes of the insert kernel -- see profiles/r1*_pmc_summary.md).  null when no profile matches.
+        traffic_em = traffic_em_iter = traffic_ins = traffic_src = None
+        try:
+            pmc_path = os.path.join(ROOT, "profiles", f"pmc_{a.workload}.json")
+            if not os.path.exists(pmc_path):
+                pmc_path = os.path.join(ROOT, "profiles", "pmc_latest.json")
+            pmc = json.load(open(pmc_path))
+            if pmc.get("workload") == a.workload and world == 1:
+                k = pmc["kernels"]
+                bytes_of = lambda e: ((2 if e.get("fetch_x2") else 1) * e["fetch_kib_per_launch"] + e["write_kib_per_launch"]) * 1024
+                # (kernel names carry their template arguments: k_sweep_lds<VB, GATHER>, k_part_route<RING>; the instance with the
+                #  most launches is the one the step ran)
+                pick = lambda prefix: max((v for n, v in k.items() if n == prefix or (n.startswith(prefix) and n[len(prefix)] in "<,>")),
+                                          key=lambda v: v.get("launches", 0), default=None)
+                # k_sweep_lds<VB, GATHER, FUSED>: the plain sweep (what time_sweep launches) and the fused iteration are different instances
+                vbs = "true" if use_vbem else "false"
+                plain = [v for n, v in k.items() if n.startswith(f"k_sweep_lds<{vbs}") and (n.count(",") == 1 or n.endswith(", false>"))]
+                fusedk = [v for n, v in k.items() if n.startswith(f"k_sweep_lds<{vbs}") and n.count(",") == 2 and n.endswith(", true>")]
+                if plain:
+                    traffic_em = bytes_of(max(plain, key=lambda v: v.get("launches", 0)))
+                if fusedk:
+                    traffic_em_iter = bytes_of(max(fusedk, key=lambda v: v.get("launches", 0)))
+                # the persistent loop (round 5): ONE launch holds all iterations -- its counters divided by the steps it ran (the iterations
+                # + the one sweep that runs for nothing before the stop is known)
+                persk = [v for n, v in k.items() if n.startswith(f"k_em_persist<{vbs}")]
+                if persk and st.get("persistent"):
+                    traffic_em_iter = bytes_of(max(persk, key=lambda v: v.get("launches", 0))) / (st["iters"] + 1)
+                # class build = the partition kernels of one sub-batch (k_insert on the generic path)
+                parts = [v for v in (pick("k_part_route"), pick("k_part_insert")) if v] or [v for v in (pick("k_insert"),) if v]
+                if parts:
+                    traffic_ins = sum(bytes_of(e) for e in parts)
+                # not re-measured by this run: it comes from the committed PMC passes of the same command
+                traffic_src = f"{os.path.relpath(pmc_path, ROOT)} ({pmc.get('source', '?')}; separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, " \
+                              f"FETCH x2 for 16-B-per-lane streaming kernels)"
+        except (OSError, ValueError, KeyError):
+            pass
+        n_ins = max(int(info["insert_launches"]), 1)
+        ins_ms = info["t_insert_ms"] / n_ins
+        # The EM is reported twice, and neither figure borrows from the other (round-3 review: B_iter' over the sweep kernel's time
+        # alone over-stated it):
+        #   roofline_em_iteration : the WHOLE iteration's algorithmic bytes B_iter' over the time one iteration takes in the loop as it
+        #                           runs (sweep + per-transcript update + what a chunk boundary costs) -- the figure to quote;
+        #   roofline_em_sweep     : the sweep kernel alone, with the bytes the SWEEP moves: labels 4 L + rowptr / count 8 C + the
+        #                           x vector it gathers from (8 M) + one partial sum per transcript it publishes (8 M); the other
+        #                           32 M (+ 16 M VBEM) of B_iter' are the update's.
+        b_sweep = 4 * L + 8 * C + 16 * M
+        roof_em = dict(bound="hbm", kernel="k_sweep_lds" + (" (the plain sweep, timed outside the loop: the loop itself runs it fused with the update)" if fused else ""), achieved=b_sweep / (sweep_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS,
+                       unit="GB/s", frac=b_sweep / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, traffic=traffic_em, traffic_source=traffic_src,
+                       bytes_per_launch=b_sweep, bytes_formula="4 L + 8 C + 16 M (sweep only: labels, rowptr + count, x gathered, partials published)",
+                       avg_launch_ms=sweep_ms, launches_per_step=st["iters"])
+        it_s = em_loop_ms_per_iter * 1e-3
+        persistent = bool(st.get("persistent"))
+        roof_em_iter = dict(bound="hbm", kernel=("one EM iteration inside the persistent loop (k_em_persist: ONE launch per optimize(); the device time of the launch / its iterations)"
+                                                if persistent else
+                                                "one EM iteration as the loop runs it (ONE kernel: the update of the iteration before at the head of the sweep; + chunk boundaries)"
+                                                if fused else "one EM iteration as the loop runs it (sweep + update + chunk boundaries)"),
+                            achieved=b_iter / it_s / 1e9, peak=HBM_PEAK_GBS, unit="GB/s", frac=b_iter / it_s / 1e9 / HBM_PEAK_GBS,
+                            traffic=(traffic_em_iter if fused else None), traffic_source=(traffic_src if fused else None),
+                            bytes_per_launch=b_iter, bytes_formula="B_iter' = 4 L + 8 C + 48 M (+ 16 M VBEM), SURVEY 8d aux-weight-free variant",
+                            avg_launch_ms=em_loop_ms_per_iter, launches_per_step=(1 if persistent else st["iters"]), iterations_per_step=st["iters"], persistent=persistent)
+        # class build: SURVEY 8d's B_read (ids + offset + one 16-byte slot probe) and, next to it, the COMPULSORY bytes alone
+        # (ids + offset: what any builder must read), so that the probe term cannot flatter the fraction
+        b_comp = 4.0 * n_hits / R_local + 4.0
+        roof_build = dict(bound="hbm", kernel=info.get("insert_kernels", "k_insert"), achieved=b_read * R_local / n_ins / (ins_ms * 1e-3) / 1e9,
+                          peak=HBM_PEAK_GBS, unit="GB/s",
+                          frac=b_read * R_local / n_ins / (ins_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, traffic=traffic_ins, traffic_source=traffic_src,
+                          bytes_per_launch=b_read * R_local / n_ins, avg_launch_ms=ins_ms, launches_per_step=n_ins,
+                          frac_compulsory_bytes=b_comp * R_local / n_ins / (ins_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          compulsory_bytes_per_read=b_comp, bytes_per_read=b_read,
+                          frac_of_whole_phase=b_read * R_local / (build_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+        dominant = roof_em if sweep_ms * st["iters"] >= info["t_insert_ms"] else roof_build
 
     out = {
         "metric": "reads quantified/sec, hit lists HBM-resident when the timed region starts (hit lists -> eq-classes -> EM to convergence "
@@ -434,8 +492,9 @@ def main():
         "phase_ms": {"class_build": build_ms, "insert_kernel": info["t_insert_ms"], "merge": info.get("t_merge_ms", 0.0),
                      "efflen": info["t_efflen_ms"], "em": em_ms, "tpm": info["t_tpm_ms"]},
         "class_build_reads_per_s": R_local / (build_ms * 1e-3),
-        "roofline": dominant, "roofline_em_iteration": roof_em_iter, "roofline_em_sweep": roof_em, "roofline_class_build": roof_build,
     }
+    if a.full:
+        out.update({"roofline": dominant, "roofline_em_iteration": roof_em_iter, "roofline_em_sweep": roof_em, "roofline_class_build": roof_build})
     if world == 1:
         # ---- what this N = 1 run implies for N = 2 / 4 / 8: a BUDGET made of this run's measured pieces plus
         #      stated constants, so that the first SCALE record of an 8-GPU node can be read against it.  Nothing here was run on > 1 GPU.
@@ -468,7 +527,7 @@ def main():
         out["ms_per_step_host_pinned"] = host_leg.get("ms_per_step")
         out["host_pinned"] = host_leg
 
-    # ---- N > 1 only, outside the timed region: what the EM-mode decision rests on, measured on THIS node (the sharded
+    # ---- N > 1 only, outside the timed region (--full): what the EM-mode decision rests on, measured on THIS node (the sharded
     # EM pays one all-reduce of M doubles per iteration; `auto` keeps the EM replicated while that costs more than a whole sweep)
     if dist:
         mg = {"em_mode_of_the_timed_steps": info["em_mode"]}
@@ -481,7 +540,12 @@ def main():
         except Exception as e:
             mg["rccl_ranks"] = None; mg["rccl_ranks_error"] = repr(e)
         mg["backend"] = a.backend; mg["one_device"] = bool(a.one_device); mg["world"] = world
+        if getattr(quant, "auto_measurement", None):
+            mg["auto_decision"] = quant.auto_measurement       # what `auto` measured on its first run (libsfgpu's own RCCL communicator)
+        mg["em_ms_of_the_timed_steps"] = em_ms
         try:
+            if not a.full:                        # the all-reduce and the step in the other EM mode are --full legs
+                raise StopIteration
             buf = torch.zeros(M, dtype=torch.float64, device=dev)
             for _ in range(10):
                 dist.all_reduce(buf)
@@ -493,9 +557,6 @@ def main():
             mg["allreduce_f64_M_us"] = (time.perf_counter() - t1) / 100 * 1e6
             mg["allreduce_bytes"] = M * 8
             mg["sweep_us_of_the_timed_problem"] = sweep_ms * 1e3
-            if getattr(quant, "auto_measurement", None):
-                mg["auto_decision"] = quant.auto_measurement       # what `auto` measured on its first run (libsfgpu's own RCCL communicator)
-            mg["em_ms_of_the_timed_steps"] = em_ms
             if a.no_compare_em_modes:
                 raise StopIteration
             other = "sharded" if info["em_mode"] == "replicated" else "replicated"
@@ -517,10 +578,10 @@ def main():
             mg["error"] = repr(e)
         out["multi_gpu"] = mg
 
-    # ---- N = 1 only, outside the timed region: the posterior-sampling paths over the job's converged classes.  BASELINE
+    # ---- --full, N = 1 only, outside the timed region: the posterior-sampling paths over the job's converged classes.  BASELINE
     # config 5 = CollapsedGibbsSampler, 1000 draws; the bootstrap is its sibling (doBootstrap).  SURVEY 8d's byte counts:
     #   Gibbs round, per sample and chain: B_round = 28 L + 8 C;   bootstrap draw: 8 C + iters x B_iter'
-    if world == 1 and not a.no_sampling:
+    if a.full and world == 1 and not a.no_sampling:
         samp = {}
         try:
             p = quant.problem
@@ -566,7 +627,7 @@ def main():
             samp["gibbs"] = dict(error=repr(e))
         out["sampling"] = samp
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cb = cpu_baseline(ref_len_np, ids, off, a.cpu_seconds, use_vbem)
         # CPU seconds for the full step = build at the sampled rate + EM iterations at the sampled
         # per-iteration cost scaled by nnz (the sweep is linear in nnz)

@@ -244,7 +244,7 @@ def test_bench_launches_its_own_ranks(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo", "--workload", "small",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-pinned", "--no-sampling"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host-pinned", "--no-sampling"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

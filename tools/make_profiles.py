@@ -2,7 +2,7 @@
 
 usage: python tools/make_profiles.py <stats_dir> <fetch_dir> <write_dir> <workload> <round-tag>
 
-  stats_dir : output of  rocprofv3 --kernel-trace --stats --output-format csv -d <stats_dir> -- python bench.py ...
+  stats_dir : output of  rocprofv3 --kernel-trace --stats --output-format csv -d <stats_dir> -- python bench.py --full ...
   fetch_dir : output of  rocprofv3 --pmc FETCH_SIZE --output-format csv -d <fetch_dir> -- (same command)
   write_dir : output of  rocprofv3 --pmc WRITE_SIZE --output-format csv -d <write_dir> -- (same command)
 

@@ -36,7 +36,8 @@ enum {
     SFGPU_ERR_ALPHA_SUM = 4, /* "total alpha weight was too small" -- :877-881 */
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
-    SFGPU_ERR_UNSUPPORTED = 7 /* reserved: an option of the reference this build does not implement (none at present) */
+    SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
+    SFGPU_ERR_FORMAT = 8     /* malformed input text (sfgpu_eq_add_text_host) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -118,6 +119,44 @@ SFGPU_API int sfgpu_eq_add_batch_device(sfgpu_eq* eq, const uint32_t* d_ids, con
  * different GPUs; same limits and synchronisation as sfgpu_eq_add_batch_device. */
 SFGPU_API int sfgpu_eq_add_weighted_device(sfgpu_eq* eq, const uint32_t* d_ids, const uint32_t* d_offsets,
                                  const uint64_t* d_counts, uint32_t n_groups);
+/* loadEquivClasses (src/SailfishQuantify.cpp:1444-1494, commented out in the reference; --readEqClasses :1114): the CLASS
+ * SECTION of an eq_classes.txt file -- the lines behind the header (M, C and the M names) that writeEquivCounts writes
+ * (src/GZipWriter.cpp:51-92) -- parsed on the device and folded into the builder.  Each line is
+ *     k \t id_1 \t ... \t id_k \t count \n
+ * Strict: fields separated by single tabs, decimal digits only, k >= 1, exactly k ids, every id < n_transcripts, count < 2^64,
+ * every line ends in '\n' except that the last line of the text may lack it.  Anything else (CR, spaces, an empty line or
+ * field, ...) is SFGPU_ERR_FORMAT.  A label is the key exactly as written (ordered, not sorted, not deduplicated) and is folded
+ * with upsert semantics through sfgpu_eq_add_weighted_device: equal labels add their counts, as insertGroup does (:82-88).
+ * Counts of 2^31 and above are read and summed as uint64; the EM refuses them later (sfgpu_problem::d_counts).
+ * The host text (pageable is fine) is staged through pinned memory in chunks of <= chunk_bytes bytes (0 = 32 MiB; otherwise
+ * 16 .. 2^30) that end at a '\n'; a line longer than a chunk is SFGPU_ERR_RANGE.  The copy of chunk c + 1 overlaps the parse
+ * of chunk c.  A chunk with an error folds nothing; chunks before it stay folded.  Synchronous; thread-safe like the other
+ * add calls.  On an error `out` names the first bad line (0-based within the class section) and the kind; the text is in
+ * sfgpu_last_error(). */
+enum {
+    SFGPU_EQTEXT_OK = 0,
+    SFGPU_EQTEXT_BAD_CHAR = 1,     /* a byte that is not a digit, '\t' or '\n' (a CR of CRLF line ends included) */
+    SFGPU_EQTEXT_EMPTY_FIELD = 2,  /* an empty line, or an empty field (two tabs in a row, a leading or trailing tab) */
+    SFGPU_EQTEXT_BAD_K = 3,        /* k is 0, or the line does not hold exactly k ids and a count */
+    SFGPU_EQTEXT_ID_RANGE = 4,     /* an id >= n_transcripts */
+    SFGPU_EQTEXT_COUNT_RANGE = 5,  /* a count >= 2^64 */
+    SFGPU_EQTEXT_LONG_LINE = 6     /* a line (with its '\n') longer than chunk_bytes */
+};
+typedef struct {
+    uint64_t n_lines;     /* class lines folded */
+    uint64_t n_ids;       /* label ids over those lines */
+    uint64_t sum_counts;  /* sum of their counts (modulo 2^64) */
+    uint64_t n_chunks;    /* chunks folded */
+    uint64_t err_line;    /* 0-based class line of the first error; UINT64_MAX without one */
+    int32_t err_kind;     /* SFGPU_EQTEXT_* */
+    int32_t pad_;
+    double stage_ms;      /* host: copies into the pinned staging buffers */
+    double h2d_ms;        /* device events around the staged copies */
+    double parse_ms;      /* device events around the parse kernels and scans */
+    double fold_ms;       /* host clock around the folds (sfgpu_eq_add_weighted_device) */
+} sfgpu_eqtext_result;
+SFGPU_API int sfgpu_eq_add_text_host(sfgpu_eq* eq, const char* h_text, uint64_t n_bytes, uint64_t n_transcripts,
+                                     uint64_t chunk_bytes, sfgpu_eqtext_result* out);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

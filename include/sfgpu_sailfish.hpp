@@ -9,6 +9,7 @@
 //   sailfish::gpu::ReadExperiment                 include/ReadExperiment.hpp:65-99, 236-257
 //   sailfish::gpu::CollapsedEMOptimizer           include/CollapsedEMOptimizer.hpp:20-35, src/CollapsedEMOptimizer.cpp:557-893
 //   sailfish::gpu::CollapsedGibbsSampler          include/CollapsedGibbsSampler.hpp:22-32, src/CollapsedGibbsSampler.cpp:187-291
+//   sailfish::gpu::loadEquivClasses               src/SailfishQuantify.cpp:1444-1494 (commented out there; --readEqClasses :1114)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -20,6 +21,8 @@
 
 #include <atomic>
 #include <cstdint>
+#include <fstream>
+#include <iterator>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -257,6 +260,54 @@ class ReadExperiment {
     std::vector<double> expectedSeqBias_ = std::vector<double>(4096, 1.0), expectedGC_ = std::vector<double>(101, 1.0);
     std::atomic<int64_t> numFwd_{0}, numRC_{0};
 };
+
+// ---- loadEquivClasses, src/SailfishQuantify.cpp:1444-1494 (commented out in the reference; --readEqClasses :1114) ------------
+// Reads the file writeEquivCounts writes (src/GZipWriter.cpp:51-92): M, C, the M names, then C lines "k \t id_1 .. id_k \t count".
+// The names must be readExp.transcripts()' names in order; the class section is parsed on the device and folded into the
+// builder with upsert semantics (sfgpu_eq_add_text_host: format, limits and error kinds in sfgpu.h).  Call it between the
+// builder's start() and finish(); several files fold into one table.  As the reference's loader, every count adds to the
+// observed and the mapped fragments.  Throws std::runtime_error naming the file and its 1-based line.
+inline void loadEquivClasses(const std::string& eqClassFile, ReadExperiment& readExp) {
+    std::ifstream in(eqClassFile, std::ios::binary);
+    if (!in) throw std::runtime_error(eqClassFile + ": cannot open");
+    const std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    size_t pos = 0;
+    uint64_t lineno = 0;
+    auto fail = [&](uint64_t line, const std::string& what) {
+        throw std::runtime_error(eqClassFile + ", line " + std::to_string(line) + ": " + what);
+    };
+    auto next_line = [&]() -> std::string {
+        ++lineno;
+        const size_t e = text.find('\n', pos);
+        if (e == std::string::npos) fail(lineno, "the file ends inside the header");
+        std::string s = text.substr(pos, e - pos);
+        pos = e + 1;
+        return s;
+    };
+    auto number = [&](const std::string& s) -> uint64_t {
+        if (s.empty() || s.size() > 19 || s.find_first_not_of("0123456789") != std::string::npos) fail(lineno, "expected a decimal integer");
+        return std::stoull(s);
+    };
+    auto& txps = readExp.transcripts();
+    const uint64_t M = number(next_line());
+    if (M != txps.size()) fail(lineno, "the header lists M=" + std::to_string(M) + " transcripts, expected " + std::to_string(txps.size()));
+    const uint64_t C = number(next_line());
+    for (uint64_t i = 0; i < M; ++i) {
+        const std::string name = next_line();
+        if (name != txps[i].RefName) fail(lineno, "transcript " + std::to_string(i) + " is named '" + name + "', expected '" + txps[i].RefName + "'");
+    }
+    sfgpu_eqtext_result r;
+    const int rc = sfgpu_eq_add_text_host(readExp.equivalenceClassBuilder().handle(), text.data() + pos, text.size() - pos, M, 0, &r);
+    if (rc != SFGPU_OK) {
+        if (r.err_line != UINT64_MAX) fail(2 + M + r.err_line + 1, sfgpu_last_error());
+        check(rc, "sfgpu_eq_add_text_host");
+    }
+    if (r.n_lines != C)
+        fail(2 + M + (r.n_lines < C ? r.n_lines : C) + 1, "the header announces C=" + std::to_string(C) + " classes, the file holds " +
+             std::to_string(r.n_lines));
+    readExp.numObservedFragmentsAtomic() += r.sum_counts;       // numObservedFragments += count; validHits += count (:1478-1479)
+    readExp.numMappedFragmentsAtomic() += r.sum_counts;
+}
 
 namespace detail {
 inline Logger* active_logger(Logger* set = nullptr, bool clear = false) {

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (imported first so libamdhip64.so.7 resolves to torc
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGPU_LIB_PATH", os.path.join(_HERE, "csrc", "libsfgpu.so"))   # override: kernel-tuning builds
 
-OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED = range(8)
+OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED, ERR_FORMAT = range(9)
 
 
 class SfgpuError(RuntimeError):
@@ -44,6 +44,15 @@ class EqStats(C.Structure):
     _fields_ = [("insert_ms", C.c_double), ("insert_launches", C.c_uint64), ("table_grows", C.c_uint64),
                 ("deferred_reads", C.c_uint64), ("table_slots", C.c_uint64),
                 ("hot_reads", C.c_uint64), ("spilled_reads", C.c_uint64), ("pipeline_drains", C.c_uint64)]
+
+
+class EqTextResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_ids", C.c_uint64), ("sum_counts", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("err_line", C.c_uint64), ("err_kind", C.c_int32), ("pad_", C.c_int32),
+                ("stage_ms", C.c_double), ("h2d_ms", C.c_double), ("parse_ms", C.c_double), ("fold_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
 _LOG_CB = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
@@ -109,6 +118,7 @@ _SIGS = {
     "sfgpu_eq_add_batch_host": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "sfgpu_eq_add_batch_device": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "sfgpu_eq_add_weighted_device": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
+    "sfgpu_eq_add_text_host": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EqTextResult)]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -114,6 +114,23 @@ class EquivalenceClassBuilder:
         torch.cuda.current_stream().synchronize()
         _lib.check(self._L.sfgpu_eq_add_weighted_device(self._h, _lib.ptr(ids_t), _lib.ptr(off_t), _lib.ptr(cnt_t), n))
 
+    def add_eq_file(self, path, names=None, chunk_bytes=0):
+        """loadEquivClasses (src/SailfishQuantify.cpp:1444-1494, commented out in the reference): fold the classes of one
+        eq_classes.txt file (writer.write_equiv_counts) with upsert semantics.  The class section is parsed on the device
+        (sailfish_amd.eqfile).  `names`, when given, must be what the file lists.  Returns the sfgpu_eqtext_result as a
+        dict (lines, ids, sum of counts, timings); a malformed file raises ValueError naming its 1-based line."""
+        from . import eqfile
+        return eqfile.fold_file(self, path, names=names, chunk_bytes=chunk_bytes)[1]
+
+    def _add_text(self, addr, n_bytes, n_transcripts, chunk_bytes, res):
+        """sfgpu_eq_add_text_host on host text at `addr`; returns the status (the caller words the error)."""
+        self._flush()
+        with torch.cuda.device(self.device):
+            if (torch.cuda.current_stream().cuda_stream or 0) != self._stream:
+                torch.cuda.current_stream().synchronize()   # the builder works on its creation stream
+            return self._L.sfgpu_eq_add_text_host(self._h, C.c_void_p(addr), int(n_bytes), int(n_transcripts), int(chunk_bytes),
+                                                  C.byref(res))
+
     def stats(self):
         st = _lib.EqStats()
         _lib.check(self._L.sfgpu_eq_get_stats(self._h, C.byref(st)))

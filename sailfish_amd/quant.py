@@ -94,21 +94,36 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
         exp.readBias()[:] = d_rb.cpu().numpy().view(np.uint32)
     if d_gc is not None:
         exp.observedGC()[:] = d_gc.cpu().numpy().view(np.uint32)
-    # quasiMapReads' tail: the fragment length distribution and the effective lengths (:937-991, :1035-1043)
-    if paired:
-        _efflen.set_effective_lengths(exp, sopt, fl_counts=fl.cpu().numpy().view(np.uint32), remaining_fl_ops=rem_fl)
+    # quasiMapReads' tail: the fragment length distribution and the effective lengths (:937-991, :1035-1043), then the rest
+    return _quantify_tail(exp, sopt, out_dir, start_time, fl_counts=fl.cpu().numpy().view(np.uint32) if paired else None,
+                          remaining_fl_ops=rem_fl, gene_map=gene_map, seed=seed)
+
+
+def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_ops, gene_map, seed, timings=None):
+    """Everything after the class table is finished (shared by quantify and quantify_eq_classes): effective lengths
+    (fl_counts None: the Gaussian prior, as a single-end run), [dumpEq], optimize with the bias recompute, quant.sf and aux/,
+    [Gibbs | bootstrap samples], [gene-level estimates].  `timings`, when a dict, receives the seconds of each phase."""
+    log = sopt.jointLog or (lambda lvl, msg: None)
+    clock = time.perf_counter
+    t0 = clock()
+    if fl_counts is not None:
+        _efflen.set_effective_lengths(exp, sopt, fl_counts=fl_counts, remaining_fl_ops=remaining_fl_ops)
     else:
         _efflen.set_effective_lengths(exp, sopt)
     if sopt.dumpEq:                                                          # :1331-1333
         _writer.write_equiv_counts(out_dir, exp, sopt)
+    t1 = clock()
     opt = CollapsedEMOptimizer()
     log(0, "Starting optimizer:\n")
     if not opt.optimize(exp, sopt, 0.01, 10000):                             # :1343-1350
         log(2, "Encountered error during optimization.\nThis should not happen.\nPlease file a bug report on GitHub.\n")
         return 1, exp
     log(0, "Finished optimizer")
+    exp.last_optimizer_stats = opt.last_stats
+    t2 = clock()
     _writer.write_abundances(out_dir, exp, sopt)                             # :1375
     _writer.write_meta(out_dir, exp, sopt, start_time)                       # :1377
+    t3 = clock()
     if sopt.numGibbsSamples > 0:                                             # :1379-1397
         w = _writer.BootstrapWriter(out_dir, sopt)
         ok = CollapsedGibbsSampler().sample(exp, sopt, w, sopt.numGibbsSamples, seed=seed)
@@ -121,9 +136,136 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
         w.close()
         if not ok:
             return 1, exp
+    t4 = clock()
     if gene_map is not None:                                                 # :1416-1426
         try:
             _genes.generate_gene_level_estimates(gene_map, out_dir)
         except ValueError as e:
             log(2, f"Error: [{e}] when trying to compute gene-level estimates. The gene-level file(s) may not exist")
+    if timings is not None:
+        timings.update(efflen_s=t1 - t0, optimize_s=t2 - t1, write_s=t3 - t2, samples_s=t4 - t3, genes_s=clock() - t4)
     return 0, exp
+
+
+def quantify_eq_classes(names, ref_len, eq_paths, out_dir, sopt: SailfishOpts = None, *, fld_counts=None, num_mapped=None,
+                        num_observed=None, observed_bias=None, observed_gc=None, num_fwd=None, num_rc=None, seq=None, seq_off=None,
+                        gene_map=None, cmd_options=None, seed=None, device="cuda"):
+    """Quantify from saved class tables (--readEqClasses, src/SailfishQuantify.cpp:1114 and loadEquivClasses :1444-1494,
+    both commented out in the reference): the classes of every file in `eq_paths` (eq_classes.txt as write_equiv_counts
+    writes it; several files -- lanes, runs -- fold into one table, equal labels adding their counts) are parsed on the device,
+    then the same tail as quantify() runs: effective lengths, [dumpEq], optimize, quant.sf, aux/, [bootstrap | Gibbs], [genes].
+
+    names / ref_len: the transcripts; every file must list exactly these names in this order.
+    fld_counts: the fragment-length counts of the run (maxFragLen entries); None selects the Gaussian prior, as a single-end run.
+    num_mapped / num_observed: default to the sum of the class counts (the loader's accounting).
+    observed_bias (4096) / observed_gc (101) and num_fwd / num_rc: what biasCorrect / gcBiasCorrect read; the class files do
+    not hold them, so they are required with those options (an all-ones vector is the untouched pseudo-count, never collected).
+    Returns (rc, ReadExperiment) like quantify(); exp.timings holds the seconds of each phase."""
+    sopt = sopt or SailfishOpts()
+    log = sopt.jointLog or (lambda lvl, msg: None)
+    dev = torch.device(device)
+    clock = time.perf_counter
+    t0 = clock()
+    if sopt.numGibbsSamples > 0 and sopt.numBootstraps > 0:                  # :1280-1286
+        log(2, "You cannot perform both Gibbs sampling and bootstrapping. Please choose one.")
+        return 1, None
+    if sopt.biasCorrect and sopt.gcBiasCorrect:                              # :1293-1297
+        log(2, "Enabling both sequence-specific and fragment GC bias correction simultaneously is not yet supported. "
+               "Please disable one of these options.")
+        return 1, None
+    for on, vec, n, what in ((sopt.biasCorrect, observed_bias, 4096, "observed_bias (biasCorrect)"),
+                             (sopt.gcBiasCorrect, observed_gc, 101, "observed_gc (gcBiasCorrect)")):
+        if not on:
+            continue
+        if vec is None:
+            raise ValueError(f"{what} is required: the class files do not hold the observed bias counts")
+        vec = np.asarray(vec)
+        if vec.shape != (n,):
+            raise ValueError(f"{what} must hold {n} counts, got shape {vec.shape}")
+        if np.all(vec == 1):
+            raise ValueError(f"{what} is all ones, the pseudo-count a run starts from: it was never collected "
+                             "(the original run did not use this bias correction)")
+    do_bias = sopt.biasCorrect or sopt.gcBiasCorrect
+    if do_bias:
+        if seq is None:
+            raise ValueError("bias correction needs the transcript sequences (seq, seq_off)")
+        if num_fwd is None or num_rc is None:
+            raise ValueError("bias correction needs num_fwd / num_rc, the strand split of the mapped fragments")
+    start_time = time.asctime()
+    write_cmd_info(out_dir, cmd_options)
+    exp = ReadExperiment(Transcripts(list(names), ref_len, device=dev), sopt)
+    if do_bias:
+        exp.setSequences(seq, seq_off)
+        if sopt.biasCorrect:
+            exp.readBias()[:] = np.asarray(observed_bias).astype(np.uint32)
+        if sopt.gcBiasCorrect:
+            exp.observedGC()[:] = np.asarray(observed_gc).astype(np.uint32)
+        exp.addNumFwd(num_fwd); exp.addNumRC(num_rc)
+    eq = exp.equivalenceClassBuilder()
+    eq.start()
+    t1 = clock()
+    from . import eqfile as _eqfile
+    _, exp.eqfile_results = _eqfile.fold_files(eq, eq_paths, names=exp.transcripts().RefName)
+    eq.finish()
+    t2 = clock()
+    exp.setNumMappedFragments(eq.total_reads if num_mapped is None else num_mapped)
+    exp.setNumObservedFragments(eq.total_reads if num_observed is None else num_observed)
+    exp.timings = dict(setup_s=t1 - t0, load_s=t2 - t1)
+    return _quantify_tail(exp, sopt, out_dir, start_time, fl_counts=fld_counts, remaining_fl_ops=0, gene_map=gene_map, seed=seed,
+                          timings=exp.timings)
+
+
+def fld_counts_for_requant(stored, sopt: SailfishOpts):
+    """The FLD argument of quantify_eq_classes that reproduces a finished run's effective lengths from its aux/fld.gz (the
+    stored counts themselves, writer.write_meta): counts equal, element for element, to efflen.normal_counts(sopt) mean the
+    run took the Gaussian-prior branch (single end, or too few unique pairs) -> None; any other counts are the empirical
+    distribution the run used -> those counts."""
+    stored = np.asarray(stored, dtype=np.int32)
+    prior = _efflen.normal_counts(sopt)
+    if stored.shape == prior.shape and np.array_equal(stored, prior):
+        return None
+    return stored.astype(np.uint32)
+
+
+def read_run(prev_dir, sopt: SailfishOpts = None):
+    """The inputs of a finished run, from its output directory: names and integer Length (quant.sf), the class file
+    (aux/eq_classes.txt), the stored FLD counts (aux/fld.gz), num_mapped / num_processed (aux/meta_info.json) and the observed
+    bias vectors (aux/observed_bias.gz, aux/observed_gc.gz)."""
+    import gzip
+    sopt = sopt or SailfishOpts()
+    aux = os.path.join(prev_dir, sopt.auxDir)
+    names, lengths = [], []
+    with open(os.path.join(prev_dir, "quant.sf")) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        if head[:3] != ["Name", "Length", "EffectiveLength"]:
+            raise ValueError(f"{os.path.join(prev_dir, 'quant.sf')}: not a quant.sf header: {head}")
+        for line in f:
+            row = line.rstrip("\n").split("\t")
+            names.append(row[0]); lengths.append(int(row[1]))
+    with open(os.path.join(aux, "meta_info.json")) as f:
+        meta = json.load(f)
+
+    def vec(name, dt):
+        with gzip.open(os.path.join(aux, name), "rb") as g:
+            return np.frombuffer(g.read(), dtype=dt).copy()
+    return dict(names=names, ref_len=np.asarray(lengths, np.uint32), eq_path=os.path.join(aux, "eq_classes.txt"),
+                fld=vec("fld.gz", np.int32), num_mapped=int(meta["num_mapped"]), num_processed=int(meta["num_processed"]),
+                observed_bias=vec("observed_bias.gz", np.int32), observed_gc=vec("observed_gc.gz", np.int32))
+
+
+def requantify(prev_dir, out_dir, sopt: SailfishOpts = None, *, seq=None, seq_off=None, num_fwd=None, num_rc=None, gene_map=None,
+               cmd_options=None, seed=None, device="cuda"):
+    """Quantify again from a finished run's output directory (written with dumpEq), without mapping: switch EM <-> VBEM, add
+    bootstraps or Gibbs draws, add a gene map.  Inputs come from read_run(prev_dir).  Effective lengths are recomputed (quant.sf
+    prints them with %g), and the FLD branch is the original run's: stored counts equal to efflen.normal_counts(sopt) element for
+    element -> the Gaussian prior, else the stored counts (fld_counts_for_requant).  sopt must carry the original maxFragLen
+    and prior mean / SD.  With biasCorrect / gcBiasCorrect the sequences and the strand split num_fwd / num_rc (not part of a
+    run's output) are required as well."""
+    sopt = sopt or SailfishOpts()
+    run = read_run(prev_dir, sopt)
+    return quantify_eq_classes(run["names"], run["ref_len"], [run["eq_path"]], out_dir, sopt,
+                               fld_counts=fld_counts_for_requant(run["fld"], sopt), num_mapped=run["num_mapped"],
+                               num_observed=run["num_processed"],
+                               observed_bias=run["observed_bias"] if sopt.biasCorrect else None,
+                               observed_gc=run["observed_gc"] if sopt.gcBiasCorrect else None, num_fwd=num_fwd, num_rc=num_rc,
+                               seq=seq, seq_off=seq_off, gene_map=gene_map, cmd_options=cmd_options, seed=seed, device=device)

@@ -1661,6 +1661,28 @@ using namespace sfgpu;
 
 static std::atomic<bool> g_allow_persist{true};      // sfgpu_em_allow_persistent: the process-wide switch (ranks that share a device turn the loop off)
 
+// The product's switches of the EM loop.  Read per call, never cached: tests flip them in-process.
+struct EmSwitches {
+    int fused = -1;              // SFGPU_EM_FUSED: -1 unset, 0, 1 (any other number counts as 1)
+    int persist = -1;            // SFGPU_EM_PERSIST: -1 unset, 0 off, 1; tests / dev: 2, 3, 4 (see ablate)
+    bool exact_norm = false;     // SFGPU_EM_EXACT_NORM set, to whatever value
+    int ablate = 0;              // what the persistent kernel is asked to leave out or delay
+};
+static EmSwitches em_read_switches() {
+    EmSwitches sw;
+    if (const char* e = getenv("SFGPU_EM_FUSED")) sw.fused = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("SFGPU_EM_PERSIST")) sw.persist = atoi(e);
+    sw.exact_norm = getenv("SFGPU_EM_EXACT_NORM") != nullptr;
+    // PERSIST=2 -> 1, dev: no tag checks (timing only); =4, tests: tile 0 starts late; =3, tests: a tile gives up in step 2 (the run
+    // is repeated with one kernel per iteration)
+    sw.ablate = sw.persist == 2 ? 1 : (sw.persist == 3 || sw.persist == 4) ? sw.persist : 0;
+    return sw;
+}
+
+// How an optimize() iterates: sweep + k_update per iteration, one fused kernel per iteration, or the whole loop as one launch
+// (which runs the fused iteration's arithmetic: whatever asks "fused?" means "not two_kernel").  em_choose_form decides.
+enum class EmForm { two_kernel, fused, persistent };
+
 struct sfgpu_em {
     hipStream_t user_stream = nullptr;
     hipStream_t stream = nullptr;          // own stream: graph capture is illegal on the null stream
@@ -1702,11 +1724,12 @@ struct sfgpu_em {
     uint32_t* unc = nullptr;                                // transcripts no window holds ([M] + count + the overlap tables' flags behind them)
     int fused_ok = -1;                                      // -1: not looked at yet; 0: this plan keeps the two-kernel iteration
     unsigned long long* dbg = nullptr;
-    bool fused = false;                                     // this optimize() runs fused launches
-    bool streamed = false;                                  // ... one by one, the host a few launches ahead of the device (no graph)
+    EmForm form = EmForm::two_kernel;                       // how this optimize() iterates
+    bool fused() const { return form != EmForm::two_kernel; }
+    bool streamed = false;                                  // the fused form's launches go out one by one, the host a few ahead of the device (no graph)
     uint32_t run_no = 0;                                    // tags the progress words of this optimize()
     uint32_t par = 0;                                       // parity of the next fused launch
-    bool graph_fused = false; bool graph_const_norm = true; double graph_log_norm = 0.0;      // (what the cached graph was built for)
+    EmForm graph_form = EmForm::two_kernel; bool graph_const_norm = true; double graph_log_norm = 0.0;      // (what the cached graph was built for)
     uint32_t null_cls = kTileNnz;                           // GATHER: class index of the transcript-major copy's padding = the largest class count of a tile
     // the PERSISTENT loop (em_persist.h): far-slot tables, the exchange buffer (control words + granule arrays), the plan's verdict
     uint32_t *esc_far = nullptr, *far_pos = nullptr, *far_xi = nullptr, *ft_list = nullptr; uint2* ftgt = nullptr;
@@ -1720,7 +1743,6 @@ struct sfgpu_em {
     uint32_t* pflags = nullptr;                             // device: [0] plan flags (!= 0: not eligible), [1] most far slots of a tile
     int persist_ok = -1;                                    // -1: not looked at yet; 0: this plan (or this device) does not run persistent
     uint32_t far_cap = 0, esc_ln = 0;                       // LDS of the persistent loop: far slots of a tile at most; far members of a tile kept on chip
-    bool persist = false;                                   // this optimize() runs as one launch
     bool no_persist = false;                                // set while several bootstrap lanes run (see sfgpu_bootstrap)
     int sharded_fused = 0;                                  // sfgpu_em_set_sharded_fused: the sharded loop runs one sweep kernel per iteration (every rank agreed)
     uint64_t* bs_prefix = nullptr; uint32_t* bs_base = nullptr;   // bootstrap: prefix sums / copy of the observed counts
@@ -1906,12 +1928,12 @@ static void em_stats_from_state(sfgpu_em* em, sfgpu_em_stats* s) {
     const EmState* h = em->h_state;
     uint32_t it = h->it_a;
     s->iters = it;
-    s->fused = em->fused ? 1u : 0u; s->persistent = em->persist ? 1u : 0u;
+    s->fused = em->fused() ? 1u : 0u; s->persistent = em->form == EmForm::persistent ? 1u : 0u;
     s->n_active = h->n_active;
     s->alpha_sum = h->alpha_sum;
     if (it == 0) { s->converged = 0; s->max_rel_diff = -DBL_MAX; return; }
     uint32_t par = (it - 1) & 1;
-    s->converged = em->fused ? (h->notconv3[(it - 1) % 3] == 0) : (h->notconv[par] == 0);
+    s->converged = em->fused() ? (h->notconv3[(it - 1) % 3] == 0) : (h->notconv[par] == 0);
     double m = -1.0;
     for (int i = 0; i < em->nb; ++i) { double v = em->h_blkmax[par * kMaxPartials + i]; if (v > m) m = v; }
     s->max_rel_diff = (m >= 0.0) ? m : -DBL_MAX;      // the reference starts from -DBL_MAX (:850)
@@ -1985,7 +2007,7 @@ static int em_renumber(sfgpu_em* em, const sfgpu_problem* prob, uint32_t L, uint
 // Leaves em->pflags on the device ([0] != 0: this plan does not run persistent; [1]: the most far slots a tile has); sfgpu_em_create
 // queues their read-back.  Nothing is waited for.
 static int em_persist_plan(sfgpu_em* em, uint32_t nt, uint64_t E, uint64_t P, const uint32_t* p_rowptr) {
-    const bool off = []() { const char* e = getenv("SFGPU_EM_PERSIST"); return e && atoi(e) == 0; }() || !g_allow_persist.load(std::memory_order_relaxed);
+    const bool off = em_read_switches().persist == 0 || !g_allow_persist.load(std::memory_order_relaxed);
     if (off || 2 * P * 16ull + 3 * E * 16ull >= (1ull << 31)) return SFGPU_OK;                  // (granules are addressed with 32-bit byte offsets)
     if (nt > 4096u) return SFGPU_OK;                            // (a plan of several rounds of tiles never runs persistent: no tables -- phase C's chunk array alone reserves 32 KB per tile)
     const uint64_t M = em->prob.M;
@@ -2399,8 +2421,8 @@ static int em_begin_on(sfgpu_em* em, const sfgpu_em_opts* opts, hipStream_t work
     int rc = em_fill_opts(em, opts);
     if (rc) return rc;
     em->cur = work;
-    em->fused = false; em->streamed = false;                 // (em_run decides)
-    em->const_norm = getenv("SFGPU_EM_EXACT_NORM") == nullptr;
+    em->form = EmForm::two_kernel; em->streamed = false;     // (em_run decides)
+    em->const_norm = !em_read_switches().exact_norm;
     em->vb_log_norm = digamma_pos((double)em->prob.M * kPriorAlpha + (double)em->prob.num_mapped);
     if (em->lenc_dirty) {
         hipLaunchKernelGGL(k_clamp_len, dim3(blocks_for(em->prob.M)), dim3(kEmBlock), 0, em->cur, em->prob.M, em->prob.d_len, em->lenc);
@@ -2515,11 +2537,11 @@ int sfgpu_em_poll(sfgpu_em* em, int* done, sfgpu_em_stats* stats) {
 // Two words, one per event: the word of chunk k is only rewritten by chunk k + 2, which is enqueued after the host has read
 // it -- every rank of a sharded run reads the same value at the same point of the loop, whatever its timing (a single word
 // could already hold the next chunk's state on one rank and not on the other: they would leave the loop at different chunks,
-// one of them inside an all-reduce).  The graph of em_run bakes its arguments and always posts into word 0: there a newer
+// one of them inside an all-reduce).  The graph of em_loop_chunked bakes its arguments and always posts into word 0: there a newer
 // value only means the end is seen a chunk earlier.
 static int em_enqueue_post(sfgpu_em* em, Launcher& L, int slot) {
     const EmState* st = em->d_state; uint32_t mn = em->opts.min_iter, mx = em->opts.max_iter; unsigned long long* m = em->h_mirror + 8 * slot;
-    int fused = em->fused ? 1 : 0;
+    int fused = em->fused() ? 1 : 0;
     void* args[] = {&st, &mn, &mx, &m, &fused};
     SF_HIP(L.launch(reinterpret_cast<const void*>(&k_post_state), dim3(1), dim3(1), args));
     return SFGPU_OK;
@@ -2545,7 +2567,7 @@ int sfgpu_em_finish(sfgpu_em* em, double* d_alpha_out, double* d_mass_out, sfgpu
     SF_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_mass, g, b, 0, em->cur, p.M, d_alpha_out, d_mass_out, em->partials, em->nb, em->d_state);
     SF_CHECK_LAUNCH();
-    if (em->fused) {
+    if (em->fused()) {
         hipLaunchKernelGGL(k_fused_max, dim3(2), dim3(kEmBlock), 0, em->cur, (uint64_t)em->n_tiles * (kSweepBlock / kWave), em->tmax, em->blkmax, em->nb);
         SF_CHECK_LAUNCH();
     }
@@ -2562,19 +2584,36 @@ int sfgpu_em_finish(sfgpu_em* em, double* d_alpha_out, double* d_mass_out, sfgpu
 
 sfgpu_stream sfgpu_em_stream(sfgpu_em* em) { return em ? reinterpret_cast<sfgpu_stream>(em->cur) : nullptr; }
 
+// "It seems that no transcripts are expressed" (:794-798): the error of every loop, with the statistics that show it
+static int em_no_active(const sfgpu_em_stats& st, sfgpu_em_stats* stats) {
+    set_error("It seems that no transcripts are expressed; something is likely wrong!");
+    if (stats) *stats = st;
+    return SFGPU_ERR_NO_ACTIVE;
+}
+
+// The structural half of em_choose_form (further down): does this plan have the fused kernel's tables at all, and may they be used?
+static bool em_can_fuse(const sfgpu_em* em, const EmSwitches& sw) {
+    return sw.fused != 0 && em->gather && em->partial_a && em->fused_ok != 0 && em->prob.C != 0;
+}
+// The plan's verdict on those tables (the classes are in canonical order): sfgpu_em_create queued its read-back behind them, this is
+// the one place that waits for it -- once per handle, and only when a form that needs the tables is about to be chosen.
+static int em_resolve_fused_ok(sfgpu_em* em) {
+    if (em->fused_ok >= 0) return SFGPU_OK;
+    SF_HIP(hipEventSynchronize(em->ev_plan));
+    em->fused_ok = (*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 2u) == 0u ? 1 : 0;
+    return SFGPU_OK;
+}
+
 // Can this handle run the sharded loop with one sweep kernel per iteration?  (its plan has the fused kernel's tables, the caller's
 // transcript order -- a plan with an order of its own indexes its vectors by position, which the other ranks' plans do not share --
 // and VBEM's normaliser is the run's constant.)  A multi-rank host asks every rank, takes the minimum (a collective of its own) and
 // tells every rank the answer with sfgpu_em_set_sharded_fused: all ranks must run the same form.
 int sfgpu_em_sharded_fused_ok(sfgpu_em* em) {
-    if (!em || !em->gather || !em->partial_a || em->inv || em->prob.C == 0) return 0;
-    if (const char* fe = getenv("SFGPU_EM_FUSED")) if (atoi(fe) == 0) return 0;
-    if (getenv("SFGPU_EM_EXACT_NORM") != nullptr) return 0;
-    if (em->fused_ok < 0) {
-        if (hipEventSynchronize(em->ev_plan) != hipSuccess) return 0;
-        em->fused_ok = ((*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 2u) == 0u && em->partial_a) ? 1 : 0;
-    }
-    return em->fused_ok == 1 ? 1 : 0;
+    const EmSwitches sw = em_read_switches();
+    if (!em || !em_can_fuse(em, sw)) return 0;
+    if (em->inv) return 0;               // (see above: the ranks share the caller's transcript order only)
+    if (sw.exact_norm) return 0;         // (EM too: every rank answers before it knows the run's options)
+    return em_resolve_fused_ok(em) == SFGPU_OK && em->fused_ok == 1 ? 1 : 0;
 }
 int sfgpu_em_set_sharded_fused(sfgpu_em* em, int on) {
     SF_REQUIRE(em, SFGPU_ERR_INVALID, "sfgpu_em_set_sharded_fused: null handle");
@@ -2600,11 +2639,7 @@ int sfgpu_em_optimize_sharded(sfgpu_em* em, const sfgpu_em_opts* opts, sfgpu_all
     int done = 0;
     sfgpu_em_stats st{};
     if ((rc = sfgpu_em_poll(em, &done, &st))) return rc;
-    if (st.n_active == 0) {                                                      // :794-798
-        set_error("It seems that no transcripts are expressed; something is likely wrong!");
-        if (stats) *stats = st;
-        return SFGPU_ERR_NO_ACTIVE;
-    }
+    if (st.n_active == 0) return em_no_active(st, stats);
     if (poll_every == 0) poll_every = 16;
     em->h_mirror[0] = em->h_mirror[8] = 0ull;
     if (em->sharded_fused && sfgpu_em_sharded_fused_ok(em) == 1) {
@@ -2614,7 +2649,7 @@ int sfgpu_em_optimize_sharded(sfgpu_em* em, const sfgpu_em_opts* opts, sfgpu_all
         // rotate through three buffers as in the fused loop (read L - 1's sum, add into L's, zero L + 1's); the stop test lags one
         // launch, and launches past the stop are no-ops whose all-reduce sums a vector nobody reads.  Every rank runs this form or
         // none does (sfgpu_em_set_sharded_fused after a collective agreement): the two forms notice the stop one iteration apart.
-        em->fused = true; em->par = 0;
+        em->form = EmForm::fused; em->par = 0;
         double* bufs[3] = {em->alpha_out, em->aout_b, em->aout_c};
         uint32_t L = 0;
         for (uint32_t k = 0; !done; ++k) {
@@ -2635,7 +2670,7 @@ int sfgpu_em_optimize_sharded(sfgpu_em* em, const sfgpu_em_opts* opts, sfgpu_all
     // (Iterations past the stop -- up to 2 poll_every of them -- still run their all-reduce.  What it sums then is all zeros: the last
     //  update zeroed alphaOut, and past the stop the sweep, k_fold and the update return at once, so nothing can grow; finish() and
     //  the statistics never read alphaOut.  The collective itself is the price of not having the host in the loop.)
-    for (uint32_t k = 0; !done; ++k) {                                           // (stop test pipelined as in em_run: every rank sees
+    for (uint32_t k = 0; !done; ++k) {                                           // (stop test pipelined as in em_loop_chunked: every rank sees
         for (uint32_t i = 0; i < poll_every; ++i) {                              //  the same state, iterations past the stop are no-ops)
             if ((rc = sfgpu_em_sweep(em)) || (rc = reduce()) || (rc = sfgpu_em_update(em))) return rc;
         }
@@ -2650,12 +2685,12 @@ static bool same_opts(const sfgpu_em_opts& a, const sfgpu_em_opts& b) {
            a.check_mode == b.check_mode && a.iters_per_launch == b.iters_per_launch;
 }
 
-constexpr uint32_t kPreLaunched = 8;      // iterations enqueued directly while the host builds the graph (em_run)
+constexpr uint32_t kPreLaunched = 8;      // iterations enqueued directly while the host builds the graph (em_loop_chunked)
 
 // `n` iterations as an executable graph (kernel arguments are baked, the iteration index and the stop
 // latch live in device memory)
 static bool em_graph_ready(const sfgpu_em* em, uint32_t n) {
-    return em->graph && same_opts(em->graph_opts, em->opts) && em->graph_iters == n && em->graph_fused == em->fused &&
+    return em->graph && same_opts(em->graph_opts, em->opts) && em->graph_iters == n && em->graph_form == em->form &&
            em->graph_const_norm == em->const_norm && em->graph_log_norm == em->vb_log_norm;      // (baked kernel arguments, like the bounds)
 }
 static int em_build_graph(sfgpu_em* em, uint32_t n) {
@@ -2667,7 +2702,7 @@ static int em_build_graph(sfgpu_em* em, uint32_t n) {
     const uint32_t par0 = em->par;                       // (fused: the graph starts on parity 0 and, n being even, ends on it)
     em->par = 0;
     for (uint32_t i = 0; i < n && rc == SFGPU_OK; ++i) {
-        if (em->fused) { rc = em_enqueue_fused(em, L, false); continue; }
+        if (em->fused()) { rc = em_enqueue_fused(em, L, false); continue; }
         rc = em_enqueue_sweep(em, L);
         if (rc == SFGPU_OK) rc = em_enqueue_update(em, true, L);
     }
@@ -2677,7 +2712,7 @@ static int em_build_graph(sfgpu_em* em, uint32_t n) {
     hipError_t ei = hipGraphInstantiate(&em->graph, L.graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(L.graph);
     SF_HIP(ei);
-    em->graph_opts = em->opts; em->graph_iters = n; em->graph_fused = em->fused;
+    em->graph_opts = em->opts; em->graph_iters = n; em->graph_form = em->form;
     em->graph_const_norm = em->const_norm; em->graph_log_norm = em->vb_log_norm;
     return SFGPU_OK;
 }
@@ -2775,305 +2810,178 @@ static int em_launch_persist(sfgpu_em* em, int ablate) {
     return SFGPU_OK;
 }
 
-// begin -> init -> iterate to the stop latch -> finish, on the handle's own stream
+// ---- which form an optimize() takes ----
+// The FUSED iteration: GATHER plans, EM or VBEM with the constant normaliser.  It pays when the tiles are large: its head adds ~3 us
+// of dependent round trips to every launch, which a co-resident block's phases hide when those are long, and saves k_update's
+// launch + one kernel boundary.  Measured (profiles/r4_em_notes.md): 18 000-nonzero tiles (cfg3) - 2.3 us (EM) / - 3.0 (VBEM) per
+// iteration, 12 900 - 3.1 / - 2.5, 5 300 (cfg2) + 1.25 / + 2.0.  So: fused from kFusedMinTileNnz nonzeros per tile up;
+// SFGPU_EM_FUSED=1 forces it wherever it can run, =0 keeps sweep + k_update (and with them rules out the persistent loop).
+// The PERSISTENT loop (em_persist.h; round 5): the whole loop as one launch, wherever the fused iteration could run and the plan fits
+// the chip in one round of blocks (whatever the tile size: it has no launch to amortise).  SFGPU_EM_PERSIST=0 keeps one kernel
+// per iteration (read when the plan is made too: no tables then); sfgpu_em_allow_persistent(0) and several bootstrap lanes
+// (no_persist) do the same.  A handle whose persistent launch gave up (persist_ok = 0) falls under the rule of the fused iteration.
+constexpr uint32_t kFusedMinTileNnz = 9000;
+
+// Could a run with these options be persistent, as far as can be told without waiting for the plan's verdicts?
+static bool em_may_persist(const sfgpu_em* em, const sfgpu_em_opts& o, const EmSwitches& sw) {
+    return em_can_fuse(em, sw) && (!o.use_vbem || !sw.exact_norm) && sw.persist != 0 && g_allow_persist.load(std::memory_order_relaxed) &&
+           o.max_iter >= 1u && o.max_iter < (1u << 24) - 2u && em->persist_ok != 0 && em->xbuf && !em->no_persist;
+}
+// The decision.  The verdicts are resolved lazily: fused_ok (a wait on the plan's event) only when one of the two forms is wanted,
+// persist_ok (em_persist_check: the same wait and hipFuncSetAttribute) only when the run would otherwise be persistent.
+static int em_choose_form(sfgpu_em* em, const sfgpu_em_opts& o, const EmSwitches& sw, EmForm* form) {
+    *form = EmForm::two_kernel;
+    if (!em_can_fuse(em, sw) || (o.use_vbem && sw.exact_norm)) return SFGPU_OK;
+    const bool fuse = sw.fused == 1 || em->tile_nnz >= kFusedMinTileNnz, persist = em_may_persist(em, o, sw);
+    if (!fuse && !persist) return SFGPU_OK;
+    const int rc = em_resolve_fused_ok(em);
+    if (rc || em->fused_ok != 1) return rc;
+    if (persist && em->persist_ok < 0) em_persist_check(em);
+    *form = (persist && em->persist_ok == 1) ? EmForm::persistent : fuse ? EmForm::fused : EmForm::two_kernel;
+    return SFGPU_OK;
+}
+
+#include "em_debug.h"
+
+// ---- the loops: every one enqueues iterations until the device's stop latch holds (iterations past it are no-ops) ----
+static int em_enqueue_iteration(sfgpu_em* em, bool first) {
+    if (em->fused()) return em_enqueue_fused(em, first);
+    int r = em_enqueue_sweep(em);
+    return r ? r : em_enqueue_update(em, true);
+}
+// one chunk: the cached graph (em_build_graph), or its iterations one by one
+static int em_enqueue_chunk(sfgpu_em* em, bool use_graph, uint32_t chunk) {
+    if (use_graph) { SF_HIP(hipGraphLaunch(em->graph, em->cur)); return SFGPU_OK; }
+    for (uint32_t i = 0; i < chunk; ++i) if (int rc = em_enqueue_iteration(em, false)) return rc;
+    return SFGPU_OK;
+}
+
+// The fused loop is STREAMED by default (SFGPU_EM_STREAMED=0: graph chunks as below): an iteration is one kernel of ~20 us and a
+// launch costs the host ~5, so the host simply stays eight launches ahead of the device (SFGPU_EM_AHEAD; 4 .. 20 measure alike).  Every launch writes "updates done |
+// ended" into a word of pinned host memory at its head; the host enqueues while it is less than kAhead launches ahead and
+// stops the moment the word says ended.  Against graph chunks of 32 iterations: no 14 us between graph launches (7 per cfg3
+// run), ~8 no-op launches past the stop instead of ~48, no graph to build: cfg3 22.5 -> 21.3 us per iteration, EM phase 5.5 -> 5.2 ms.
+static int em_loop_streamed(sfgpu_em* em) {
+    int rc;
+    static const uint32_t kAhead = []() { const char* e = SF_DEV_ENV("SFGPU_EM_AHEAD"); long v = e ? atol(e) : 0; return (uint32_t)(v >= 1 && v <= 256 ? v : 8); }();
+    volatile unsigned long long* mir = em->h_mirror;
+    *mir = 0ull;
+    ++em->run_no;                                         // (a word some launch of an earlier, failed run may still write is not this run's)
+    const unsigned long long tag = (1ull << 33) | ((unsigned long long)(em->run_no & 0xFFFFFu) << 34);
+    uint32_t launched = 0;
+    if ((rc = em_enqueue_iteration(em, true))) return rc;
+    ++launched;
+    // (the host follows the device through a word of pinned memory: a device that has stopped answering must not spin it for ever --
+    //  every few thousand polls the stream is asked how it is, and two minutes without progress end the run)
+    auto give_up = [&](const char* why) -> int {
+        (void)hipStreamSynchronize(em->cur);              // nothing of this run stays queued behind the error
+        em->in_optimize = false;
+        set_error("sfgpu_em_optimize: %s", why);
+        return SFGPU_ERR_HIP;
+    };
+    const auto t_start = std::chrono::steady_clock::now();
+    unsigned long long last_v = ~0ull; auto t_progress = t_start;
+    for (uint32_t spins = 0, polls = 0;; ++polls) {
+        const unsigned long long v = *mir;
+        if ((polls & 4095u) == 4095u) {
+            const hipError_t q = hipStreamQuery(em->cur);
+            if (q != hipSuccess && q != hipErrorNotReady) return give_up(hipGetErrorString(q));
+            const auto now = std::chrono::steady_clock::now();
+            if (v != last_v) { last_v = v; t_progress = now; }
+            else if (std::chrono::duration<double>(now - t_progress).count() > 120.0) return give_up("the EM loop made no progress for two minutes");
+        }
+        const bool any = (v >> 33) == (tag >> 33);
+        if (any && ((v >> 32) & 1ull)) return SFGPU_OK;   // a launch found the loop ended: everything behind it is a no-op
+        // launch n posts n - 1 updates done at its head; with `launched` enqueued, launched - 2 - posted wait behind the running one
+        const uint32_t posted = any ? (uint32_t)v : 0u;
+        const uint32_t queued = any ? (launched >= posted + 2u ? launched - posted - 2u : 0u) : launched;
+        if (queued < kAhead) { if ((rc = em_enqueue_iteration(em, false))) { (void)hipStreamSynchronize(em->cur); em->in_optimize = false; return rc; } ++launched; spins = 0; }
+        else if (++spins > 64u) { std::this_thread::yield(); spins = 0; }
+    }
+}
+
+// Chunks of iterations_per_launch iterations -- a graph, or (SFGPU_EM_NOGRAPH) direct launches -- with the pipelined stop test of
+// em_poll_start / em_poll_wait between them: the two-kernel form, and in variants builds the fused one with SFGPU_EM_STREAMED=0.
+static int em_loop_chunked(sfgpu_em* em) {
+    int rc, done = 0;
+    const bool use_graph = SF_DEV_ENV("SFGPU_EM_NOGRAPH") == nullptr;
+    uint32_t chunk = em->opts.iters_per_launch;
+    if (em->fused()) {
+        chunk += chunk & 1u;                                  // (a graph bakes the launches' parities)
+        // the first launch has nothing to update; a second one keeps the parity even for the graph
+        if ((rc = em_enqueue_iteration(em, true)) || (rc = em_enqueue_iteration(em, false))) return rc;
+    }
+    if (use_graph && !em_graph_ready(em, chunk)) {
+        // building the graph takes the host ~170 us: the first iterations go straight onto the stream and run meanwhile
+        // (iterations past the stop are no-ops, so it does not matter how many of them there are)
+        for (uint32_t i = 0; i < kPreLaunched; ++i) if ((rc = em_enqueue_iteration(em, false))) return rc;
+    }
+    if (use_graph && (rc = em_build_graph(em, chunk))) return rc;
+    em->h_mirror[0] = em->h_mirror[8] = 0ull;                // (nothing of an earlier run is in flight: finish() waited for it)
+    for (uint32_t k = 0; !done; ++k) {
+        if ((rc = em_enqueue_chunk(em, use_graph, chunk))) return rc;
+        if ((rc = em_poll_start(em, (int)(k & 1u), !use_graph))) return rc;
+        if (k > 0 && (rc = em_poll_wait(em, (int)((k - 1u) & 1u), use_graph, &done))) return rc;       // the chunk before this one
+    }
+    return SFGPU_OK;
+}
+
+// begin -> choose the form -> init -> the form's loop -> finish, on the handle's own stream.  A persistent launch that gave up is
+// repeated from its start: the handle's persist_ok is 0 by then, so the second choice is made without persistence.
 static int em_run(sfgpu_em* em, const sfgpu_em_opts* opts, double* d_alpha_out, double* d_mass_out,
                   sfgpu_em_stats* stats, bool quiet) {
     int rc;
     em->in_optimize = true;
     if ((rc = em_begin_on(em, opts, em->stream))) return rc;
-    // The fused iteration: GATHER plans, EM or VBEM with the constant normaliser.  It pays when the tiles are large: its head adds ~3 us
-    // of dependent round trips to every launch, which a co-resident block's phases hide when those are long, and saves k_update's
-    // launch + one kernel boundary.  Measured (profiles/r4_em_notes.md): 18 000-nonzero tiles (cfg3) - 2.3 us (EM) / - 3.0 (VBEM) per
-    // iteration, 12 900 - 3.1 / - 2.5, 5 300 (cfg2) + 1.25 / + 2.0.  So: fused from kFusedMinTileNnz nonzeros per tile up;
-    // SFGPU_EM_FUSED=1 forces it wherever it can run, =0 keeps sweep + k_update.
-    {
-        constexpr uint32_t kFusedMinTileNnz = 9000;
-        const char* fe = getenv("SFGPU_EM_FUSED");              // (read per run: tests switch it)
-        const bool fused_off = fe && atoi(fe) == 0, fused_forced = fe && atoi(fe) != 0;
-        em->fused = !fused_off && (fused_forced || em->tile_nnz >= kFusedMinTileNnz) && em->gather && em->fused_ok != 0 && em->prob.C != 0 &&
-                    (!em->opts.use_vbem || em->const_norm);
-    }
-    // The PERSISTENT loop (em_persist.h; round 5): the whole loop as one launch, wherever the fused iteration could run and the plan fits
-    // the chip in one round of blocks (whatever the tile size: it has no launch to amortise).  SFGPU_EM_PERSIST=0 keeps one kernel
-    // per iteration (read when the plan is made too: no tables then).
-    int persist_ablate = 0;
-    {
-        const char* fe = getenv("SFGPU_EM_FUSED"); const char* pe = getenv("SFGPU_EM_PERSIST");
-        const bool family = !(fe && atoi(fe) == 0) && !(pe && atoi(pe) == 0) && em->gather && em->fused_ok != 0 && em->prob.C != 0 &&
-                            g_allow_persist.load(std::memory_order_relaxed) && (!em->opts.use_vbem || em->const_norm) && em->opts.max_iter >= 1u && em->opts.max_iter < (1u << 24) - 2u && em->persist_ok != 0 && em->xbuf && !em->no_persist;
-        em->persist = family;
-        if (family) em->fused = true;
-        if (pe && atoi(pe) == 2) persist_ablate = 1;         // dev: no tag checks (timing only)
-        if (pe && atoi(pe) == 4) persist_ablate = 4;         // tests: tile 0 starts late
-        if (pe && atoi(pe) == 3) persist_ablate = 3;         // tests: a tile gives up in step 2 (the run is repeated with one kernel per iteration)
-    }
-    if (em->fused && em->fused_ok < 0) {
-        // the plan's verdict on the fused kernel's tables (sfgpu_em_create queued its read-back behind them; long done by now)
-        SF_HIP(hipEventSynchronize(em->ev_plan));
-        em->fused_ok = ((*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 2u) == 0u && em->partial_a) ? 1 : 0;
-        if (!em->fused_ok) em->fused = false;                // (the classes are not in canonical order)
-    }
-    if (em->persist && !em->fused) em->persist = false;
-    if (em->persist && em->persist_ok < 0) em_persist_check(em);
-    if (em->persist && em->persist_ok != 1) {
-        em->persist = false;
-        const char* fe = getenv("SFGPU_EM_FUSED");           // (back to the rule of the fused iteration)
-        em->fused = ((fe && atoi(fe) != 0) || em->tile_nnz >= 9000u);
-    }
+    const EmSwitches sw = em_read_switches();
+    if ((rc = em_choose_form(em, em->opts, sw, &em->form))) return rc;
+    const bool persistent = em->form == EmForm::persistent;
     std::unique_lock<std::mutex> persist_lock;
-    if (em->persist) { int dev = 0; (void)hipGetDevice(&dev); persist_lock = std::unique_lock<std::mutex>(g_persist_mu[dev & 15]); }
+    if (persistent) { int dev = 0; (void)hipGetDevice(&dev); persist_lock = std::unique_lock<std::mutex>(g_persist_mu[dev & 15]); }
     if ((rc = sfgpu_em_init_impl(em))) return rc;
-    if (em->fused && em->inv) {                               // alpha and effLen in the plan's order (the fused kernel's index space)
+    if (em->fused() && em->inv) {                             // alpha and effLen in the plan's order (the fused kernel's index space)
         const uint64_t M = em->prob.M;
         hipLaunchKernelGGL(k_gather_f64, dim3(blocks_for(M)), dim3(kEmBlock), 0, em->cur, M, em->alpha, em->inv, em->alphaP);
         hipLaunchKernelGGL(k_gather_f64, dim3(blocks_for(M)), dim3(kEmBlock), 0, em->cur, M, em->lenc, em->inv, em->lencP);
         SF_CHECK_LAUNCH();
     }
-    int done = 0;
     sfgpu_em_stats st{};
-    if (!em->fused) {
+    if (!em->fused()) {
+        int done = 0;
         if ((rc = sfgpu_em_poll(em, &done, &st))) return rc;
-        if (st.n_active == 0) {                                                      // :794-798
-            set_error("It seems that no transcripts are expressed; something is likely wrong!");
-            if (stats) *stats = st;
-            return SFGPU_ERR_NO_ACTIVE;
-        }
+        if (st.n_active == 0) return em_no_active(st, stats);
     }
     // (fused: no wait here -- the first launches go out behind init at once and the number of active transcripts is looked at when
     //  the loop has ended: a job without any runs minIter iterations over zeros before it reports so)
     if (!quiet) log_msg(0, "Optimizing over %llu equivalence classes", (unsigned long long)em->prob.C);   // :790
-    const bool use_graph = SF_DEV_ENV("SFGPU_EM_NOGRAPH") == nullptr;
-    uint32_t chunk = em->opts.iters_per_launch;
-    if (em->fused) {
-        chunk += chunk & 1u;                                  // (a graph bakes the launches' parities)
-        em->par = 0;
-    }
-#ifdef SFGPU_X_STAMP
-    if (!em->dbg) { SF_HIP(pool_malloc(&em->dbg, (size_t)em->n_tiles * 16 * 8)); }
-    SF_HIP(hipMemsetAsync(em->dbg, 0, (size_t)em->n_tiles * 16 * 8, em->cur));
-#endif
-    auto iteration = [&](bool first) -> int {
-        if (em->fused) return em_enqueue_fused(em, first);
-        int r = em_enqueue_sweep(em);
-        return r ? r : em_enqueue_update(em, true);
-    };
-    // The fused loop is STREAMED by default (SFGPU_EM_STREAMED=0: graph chunks as below): an iteration is one kernel of ~20 us and a
-    // launch costs the host ~5, so the host simply stays eight launches ahead of the device (SFGPU_EM_AHEAD; 4 .. 20 measure alike).  Every launch writes "updates done |
-    // ended" into a word of pinned host memory at its head; the host enqueues while it is less than kAhead launches ahead and
-    // stops the moment the word says ended.  Against graph chunks of 32 iterations: no 14 us between graph launches (7 per cfg3
-    // run), ~8 no-op launches past the stop instead of ~48, no graph to build: cfg3 22.5 -> 21.3 us per iteration, EM phase 5.5 -> 5.2 ms.
-    {
-        const char* se = SF_DEV_ENV("SFGPU_EM_STREAMED");
-        em->streamed = em->fused && !em->persist && !(se && atoi(se) == 0);
-    }
+    if (em->fused()) em->par = 0;
+    if ((rc = em_dbg_stamps_begin(em))) return rc;
+    const char* se = SF_DEV_ENV("SFGPU_EM_STREAMED");
+    em->streamed = em->form == EmForm::fused && !(se && atoi(se) == 0);
     SF_HIP(hipEventRecord(em->ev_a, em->cur));
-    if (em->persist) {
-        if ((rc = em_launch_persist(em, persist_ablate))) return rc;
-        done = 1;
-    } else if (em->streamed) {
-        static const uint32_t kAhead = []() { const char* e = SF_DEV_ENV("SFGPU_EM_AHEAD"); long v = e ? atol(e) : 0; return (uint32_t)(v >= 1 && v <= 256 ? v : 8); }();
-        volatile unsigned long long* mir = em->h_mirror;
-        *mir = 0ull;
-        ++em->run_no;                                         // (a word some launch of an earlier, failed run may still write is not this run's)
-        const unsigned long long tag = (1ull << 33) | ((unsigned long long)(em->run_no & 0xFFFFFu) << 34);
-        uint32_t launched = 0;
-        if ((rc = iteration(true))) return rc;
-        ++launched;
-        // (the host follows the device through a word of pinned memory: a device that has stopped answering must not spin it for ever --
-        //  every few thousand polls the stream is asked how it is, and two minutes without progress end the run)
-        auto give_up = [&](const char* why) -> int {
-            (void)hipStreamSynchronize(em->cur);              // nothing of this run stays queued behind the error
-            em->in_optimize = false;
-            set_error("sfgpu_em_optimize: %s", why);
-            return SFGPU_ERR_HIP;
-        };
-        const auto t_start = std::chrono::steady_clock::now();
-        unsigned long long last_v = ~0ull; auto t_progress = t_start;
-        for (uint32_t spins = 0, polls = 0;; ++polls) {
-            const unsigned long long v = *mir;
-            if ((polls & 4095u) == 4095u) {
-                const hipError_t q = hipStreamQuery(em->cur);
-                if (q != hipSuccess && q != hipErrorNotReady) return give_up(hipGetErrorString(q));
-                const auto now = std::chrono::steady_clock::now();
-                if (v != last_v) { last_v = v; t_progress = now; }
-                else if (std::chrono::duration<double>(now - t_progress).count() > 120.0) return give_up("the EM loop made no progress for two minutes");
-            }
-            const bool any = (v >> 33) == (tag >> 33);
-            if (any && ((v >> 32) & 1ull)) break;             // a launch found the loop ended: everything behind it is a no-op
-            // launch n posts n - 1 updates done at its head; with `launched` enqueued, launched - 2 - posted wait behind the running one
-            const uint32_t posted = any ? (uint32_t)v : 0u;
-            const uint32_t queued = any ? (launched >= posted + 2u ? launched - posted - 2u : 0u) : launched;
-            if (queued < kAhead) { if ((rc = iteration(false))) { (void)hipStreamSynchronize(em->cur); em->in_optimize = false; return rc; } ++launched; spins = 0; }
-            else if (++spins > 64u) { std::this_thread::yield(); spins = 0; }
-        }
-        done = 1;
-    } else {
-    if (em->fused) {
-        // the first launch has nothing to update; a second one keeps the parity even for the graph
-        if ((rc = iteration(true)) || (rc = iteration(false))) return rc;
-    }
-    if (use_graph && !em_graph_ready(em, chunk)) {
-        // building the graph takes the host ~170 us: the first iterations go straight onto the stream and run meanwhile
-        // (iterations past the stop are no-ops, so it does not matter how many of them there are)
-        for (uint32_t i = 0; i < kPreLaunched; ++i) if ((rc = iteration(false))) return rc;
-    }
-    if (use_graph && (rc = em_build_graph(em, chunk))) return rc;
-    em->h_mirror[0] = em->h_mirror[8] = 0ull;                // (nothing of an earlier run is in flight: finish() waited for it)
-    for (uint32_t k = 0; !done; ++k) {
-        if (use_graph) {
-            SF_HIP(hipGraphLaunch(em->graph, em->cur));
-        } else {
-            for (uint32_t i = 0; i < chunk; ++i) if ((rc = iteration(false))) return rc;
-        }
-        if ((rc = em_poll_start(em, (int)(k & 1u), !use_graph))) return rc;
-        if (k > 0 && (rc = em_poll_wait(em, (int)((k - 1u) & 1u), use_graph, &done))) return rc;       // the chunk before this one
-    }
-    }
+    rc = persistent ? em_launch_persist(em, sw.ablate) : em->streamed ? em_loop_streamed(em) : em_loop_chunked(em);
+    if (rc) return rc;
     SF_HIP(hipEventRecord(em->ev_b, em->cur));
-    if (em->fused && em->inv) {                               // back to the caller's order
+    if (em->fused() && em->inv) {                             // back to the caller's order
         hipLaunchKernelGGL(k_scatter_f64, dim3(blocks_for(em->prob.M)), dim3(kEmBlock), 0, em->cur, em->prob.M, em->alphaP, em->inv, em->alpha);
         SF_CHECK_LAUNCH();
     }
     rc = sfgpu_em_finish(em, d_alpha_out, d_mass_out, &st);
-    if (em->persist && *reinterpret_cast<const volatile uint32_t*>(em->h_plan + 7) != 0u) {
+    if (persistent && *reinterpret_cast<const volatile uint32_t*>(em->h_plan + 7) != 0u) {
         // a tile gave up waiting (its neighbours never became resident: the chip is shared with another process' kernels): this
         // handle goes back to one kernel per iteration, and the run is repeated from its start
         persist_lock.unlock();
         em->persist_ok = 0;
-        {
-            unsigned long long who[4] = {0, 0, 0, 0};
-            (void)hipMemcpy(who, em->xbuf + (size_t)(kCtlAbort + 1) * kCtlStride * 8, sizeof(who), hipMemcpyDeviceToHost);
-#ifdef SFGPU_P_PROGRESS
-            {
-                std::vector<unsigned long long> h(em->n_tiles);
-                (void)hipMemcpy(h.data(), em->dbg, h.size() * 8, hipMemcpyDeviceToHost);
-                std::string line;
-                for (uint32_t b = 0; b < em->n_tiles; ++b) { line += (char)('0' + (h[b] > 9 ? 9 : (int)h[b])); }
-                fprintf(stderr, "persist progress (step + 1 per tile, 0 = never ran): %s\n", line.c_str());
-                std::vector<unsigned long long> w(em->n_tiles);
-                (void)hipMemcpy(w.data(), em->dbg + em->n_tiles, w.size() * 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "persist waits at the give-up (tile: why * 1000 + step; tiles at steps < 2 only):");
-                for (uint32_t b = 0; b < em->n_tiles; ++b) if (h[b] < 3) fprintf(stderr, " %u:%llu", b, w[b]);
-                fprintf(stderr, "\n");
-                {   // when and where every block started (100 MHz clock): the late ones, and a histogram of the waits' reasons
-                    std::vector<unsigned long long> t0(em->n_tiles), hw(em->n_tiles);
-                    (void)hipMemcpy(t0.data(), em->dbg + 2 * em->n_tiles, t0.size() * 8, hipMemcpyDeviceToHost);
-                    (void)hipMemcpy(hw.data(), em->dbg + 3 * em->n_tiles, hw.size() * 8, hipMemcpyDeviceToHost);
-                    unsigned long long tmin = ~0ull; uint32_t never = 0;
-                    for (uint32_t b = 0; b < em->n_tiles; ++b) { if (!t0[b]) ++never; else tmin = std::min(tmin, t0[b]); }
-                    std::vector<uint32_t> ord(em->n_tiles);
-                    for (uint32_t b = 0; b < em->n_tiles; ++b) ord[b] = b;
-                    std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) { return t0[x] > t0[y]; });
-                    fprintf(stderr, "persist starts: %u blocks never started; the latest (tile: us after the first, xcc, hw_id):", never);
-                    for (uint32_t i = 0; i < 12 && i < em->n_tiles; ++i) { const uint32_t b = ord[i]; fprintf(stderr, " %u:%.1f,x%llu,%05llx", b, t0[b] ? (double)(t0[b] - tmin) * 0.01 : -1.0, hw[b] >> 32, hw[b] & 0xFFFFFull); }
-                    fprintf(stderr, "\n  why histogram (why * 1000 + step -> tiles):");
-                    std::map<unsigned long long, uint32_t> hist;
-                    for (uint32_t b = 0; b < em->n_tiles; ++b) ++hist[w[b]];
-                    for (auto& kv : hist) fprintf(stderr, " %llu->%u", kv.first, kv.second);
-                    fprintf(stderr, "\n  steps histogram (step + 1 -> tiles):");
-                    std::map<unsigned long long, uint32_t> hs;
-                    for (uint32_t b = 0; b < em->n_tiles; ++b) ++hs[h[b]];
-                    for (auto& kv : hs) fprintf(stderr, " %llu->%u", kv.first, kv.second);
-                    // the arrival counters as memory holds them now
-                    unsigned long long ctlw[4 * kShards];
-                    for (uint32_t k = 0; k < 4 * kShards; ++k) (void)hipMemcpy(&ctlw[k], em->xbuf + (size_t)(kCtlArrive + k) * kCtlStride * 8, 8, hipMemcpyDeviceToHost);
-                    fprintf(stderr, "\n  arrival counters [slot][shard] (low word):");
-                    for (uint32_t k = 0; k < 4 * kShards; ++k) fprintf(stderr, "%s%llu", (k % kShards) ? " " : " | ", ctlw[k] & 0xFFFFFFFFull);
-                    fprintf(stderr, "\n");
-                }
-                // the first stuck tile's view: what memory holds NOW where it polled (its neighbours' pieces, parity 1 = tags 1, 3, ...)
-                for (uint32_t b = 0; b < em->n_tiles; ++b) if (h[b] == 2 && w[b] / 1000 == 2) {
-                    TileDesc t; (void)hipMemcpy(&t, em->td + b, sizeof(t), hipMemcpyDeviceToHost);
-                    auto up2 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-                    const size_t o1 = up2((size_t)kCtlWords * 8 + 64 + sizeof(PersistCold)) + up2((size_t)(em->P ? em->P : 1) * 16);
-                    fprintf(stderr, "tile %u (lo %u span %u nb %u): tags in memory of its neighbours' first / last overlapping slots (parity 1):", b, t.lo, t.span, t.nb_n);
-                    for (uint32_t j2 = 0; j2 < t.nb_n && j2 < 6; ++j2) {
-                        const uint32_t lo2 = t.e[j2].x, sp2 = t.e[j2].y, off2 = t.e[j2].z;
-                        const uint32_t p0 = std::max(lo2, t.lo), p1 = std::min(lo2 + sp2, t.lo + t.span) - 1;
-                        uint32_t g0[4], g1[4];
-                        (void)hipMemcpy(g0, em->xbuf + o1 + (size_t)(off2 + (p0 - lo2)) * 16, 16, hipMemcpyDeviceToHost);
-                        (void)hipMemcpy(g1, em->xbuf + o1 + (size_t)(off2 + (p1 - lo2)) * 16, 16, hipMemcpyDeviceToHost);
-                        fprintf(stderr, " [tile %u: %u/%u .. %u/%u]", t.e[j2].w, g0[1], g0[3], g1[1], g1[3]);
-                    }
-                    fprintf(stderr, "\n");
-                    break;
-                }
-
-            }
-#endif
-            log_msg(1, "EM: the persistent loop gave up waiting for a tile (is the device shared?); running one kernel per iteration [tile %llu of %u, thread %llu, wait %llu, step %llu]",
-                    who[0] - 1ull, em->n_tiles, who[1], who[2], who[3]);
-        }
+        unsigned long long who[4] = {0, 0, 0, 0};
+        (void)hipMemcpy(who, em->xbuf + (size_t)(kCtlAbort + 1) * kCtlStride * 8, sizeof(who), hipMemcpyDeviceToHost);
+        em_dbg_persist_progress(em);
+        log_msg(1, "EM: the persistent loop gave up waiting for a tile (is the device shared?); running one kernel per iteration [tile %llu of %u, thread %llu, wait %llu, step %llu]",
+                who[0] - 1ull, em->n_tiles, who[1], who[2], who[3]);
         return em_run(em, opts, d_alpha_out, d_mass_out, stats, quiet);
     }
-    if (em->fused && st.n_active == 0) {                                             // :794-798 (see above)
-        set_error("It seems that no transcripts are expressed; something is likely wrong!");
-        if (stats) *stats = st;
-        return SFGPU_ERR_NO_ACTIVE;
-    }
-#ifdef SFGPU_P_STAMP
-    if (em->persist && em->dbg && st.iters > 2) {          // dev: where a persistent step goes, per tile (100 MHz clock)
-        std::vector<unsigned long long> h((size_t)em->n_tiles * 8);
-        (void)hipMemcpy(h.data(), em->dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        static const char* nm[7] = {"operands", "x+update", "barrier", "A", "B", "C", "D"};
-        const double steps = (double)st.iters + 1.0;
-        fprintf(stderr, "persist stamps (%s, %u tiles, %u steps; us per step and tile, mean / min / max over the tiles):", em->opts.use_vbem ? "VBEM" : "EM", em->n_tiles, st.iters + 1);
-        for (int k = 0; k < 7; ++k) {
-            double sum = 0, mn = 1e30, mx = 0;
-            for (uint32_t b = 0; b < em->n_tiles; ++b) { const double v = (double)h[b * 8 + k] * 0.01 / steps; sum += v; mn = std::min(mn, v); mx = std::max(mx, v); }
-            fprintf(stderr, " %s %.2f/%.2f/%.2f", nm[k], sum / em->n_tiles, mn, mx);
-        }
-        fprintf(stderr, "\n");
-        // the tiles that wait least for their operands set the pace: what are they made of?
-        std::vector<TileDesc> htd(em->n_tiles);
-        (void)hipMemcpy(htd.data(), em->td, htd.size() * sizeof(TileDesc), hipMemcpyDeviceToHost);
-        std::vector<uint32_t> order(em->n_tiles);
-        for (uint32_t b = 0; b < em->n_tiles; ++b) order[b] = b;
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h[x * 8] < h[y * 8]; });
-        std::vector<TilePack> htp(em->n_tiles);
-        (void)hipMemcpy(htp.data(), em->tp, htp.size() * sizeof(TilePack), hipMemcpyDeviceToHost);
-        double mean_nc = 0, mean_np = 0, mean_nm = 0, mean_ov = 0, mean_n[4] = {0, 0, 0, 0};
-        for (const TileDesc& t : htd) { mean_nc += t.nc; mean_np += t.np; mean_nm += t.nm; }
-        for (const TilePack& t : htp) { mean_ov += t.n_ov; mean_n[0] += t.n1; mean_n[1] += t.n2; mean_n[2] += t.n3; mean_n[3] += t.n4; }
-        fprintf(stderr, "  tile means: classes %.0f (records of 4 / 8 / 16 bytes / long: %.0f %.0f %.0f %.0f), pure chunks %.0f, mixed chunks %.0f, overflow chunks %.0f\n", mean_nc / em->n_tiles,
-                mean_n[0] / em->n_tiles, mean_n[1] / em->n_tiles, mean_n[2] / em->n_tiles, mean_n[3] / em->n_tiles, mean_np / em->n_tiles, mean_nm / em->n_tiles, mean_ov / em->n_tiles);
-        for (uint32_t i = 0; i < 6 && i < em->n_tiles; ++i) {
-            const uint32_t b = order[i]; const TileDesc& t = htd[b];
-            fprintf(stderr, "  tile %4u:", b);
-            for (int k = 0; k < 7; ++k) fprintf(stderr, " %s %.2f", nm[k], (double)h[b * 8 + k] * 0.01 / steps);
-            fprintf(stderr, " | span %u classes %u pure %u mixed %u overflow %u far members %u far slots %u neighbours %u\n", t.span, t.nc, t.np, t.nm, htp[b].n_ov, t.n_esc, t.nf, t.nb_n);
-        }
-    }
-#endif
-#ifdef SFGPU_X_STAMP
-    if (em->dbg) {                                          // dev: phase stamps of the last launch that ran (100 MHz clock)
-        std::vector<unsigned long long> h((size_t)em->n_tiles * 16);
-        (void)hipMemcpy(h.data(), em->dbg, h.size() * 8, hipMemcpyDeviceToHost);
-        unsigned long long t0min = ~0ull, tend = 0; double sum[16] = {0}; double ramp = 0; uint32_t n = 0;
-        for (uint32_t b = 0; b < em->n_tiles; ++b) if (h[b * 16] && h[b * 16 + 10]) { t0min = std::min(t0min, h[b * 16]); tend = std::max(tend, h[b * 16 + 10]); }
-        for (uint32_t b = 0; b < em->n_tiles; ++b) if (h[b * 16] && h[b * 16 + 10]) {
-            ++n; ramp += (double)(h[b * 16] - t0min);
-            for (int k = 1; k <= 10; ++k) sum[k] += h[b * 16 + k] ? (double)(h[b * 16 + k] - h[b * 16]) : 0.0;
-        }
-        fprintf(stderr, "stamps (%s, %u tiles; us after the tile's entry): entry %.2f after the first |", em->fused ? "fused" : "unfused", n, ramp / n * 0.01);
-        for (int k = 1; k <= 10; ++k) fprintf(stderr, " s%d %.2f", k, sum[k] / n * 0.01);
-        fprintf(stderr, " | first entry -> last end %.2f us\n", (double)(tend - t0min) * 0.01);
-        // the slowest tiles: duration of each phase for the five tiles with the latest end
-        std::vector<uint32_t> order;
-        for (uint32_t b = 0; b < em->n_tiles; ++b) if (h[b * 16] && h[b * 16 + 10]) order.push_back(b);
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return h[x * 16 + 10] - h[x * 16] > h[y * 16 + 10] - h[y * 16]; });
-        std::vector<TileDesc> htd(em->n_tiles);
-        (void)hipMemcpy(htd.data(), em->td, htd.size() * sizeof(TileDesc), hipMemcpyDeviceToHost);
-        for (size_t q = 0; q < order.size() && q < 5; ++q) {
-            const uint32_t b = order[q];
-            fprintf(stderr, "  slow tile %u (nc %u span %u n8 %u n_esc %u np %u nm %u nb %u; entry +%.2f):", b, htd[b].nc, htd[b].span, htd[b].n8, htd[b].n_esc, htd[b].np, htd[b].nm,
-                    htd[b].nb_n, (double)(h[b * 16] - t0min) * 0.01);
-            for (int k = 1; k <= 10; ++k) fprintf(stderr, " %.2f", h[b * 16 + k] ? (double)(h[b * 16 + k] - h[b * 16]) * 0.01 : 0.0);
-            fprintf(stderr, "\n");
-        }
-        if (order.size() > 5) { const uint32_t b = order[order.size() / 2]; fprintf(stderr, "  median tile %u: total %.2f\n", b, (double)(h[b * 16 + 10] - h[b * 16]) * 0.01); }
-    }
-#endif
+    if (em->fused() && st.n_active == 0) return em_no_active(st, stats);      // (see above)
+    em_dbg_persist_stamps(em, st.iters);
+    em_dbg_stamps_report(em);
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, em->ev_a, em->ev_b);
     st.loop_ms = ms;
@@ -3107,11 +3015,7 @@ static int em_run_bias(sfgpu_em* em, const sfgpu_em_opts* opts, sfgpu_bias* bias
     int done = 0;
     sfgpu_em_stats st{};
     if ((rc = sfgpu_em_poll(em, &done, &st))) return rc;
-    if (st.n_active == 0) {
-        set_error("It seems that no transcripts are expressed; something is likely wrong!");
-        if (stats) *stats = st;
-        return SFGPU_ERR_NO_ACTIVE;
-    }
+    if (st.n_active == 0) return em_no_active(st, stats);
     log_msg(0, "Optimizing over %llu equivalence classes", (unsigned long long)em->prob.C);
     const sfgpu_problem& p = em->prob;
     const bool use_graph = SF_DEV_ENV("SFGPU_EM_NOGRAPH") == nullptr;
@@ -3147,14 +3051,7 @@ static int em_run_bias(sfgpu_em* em, const sfgpu_em_opts* opts, sfgpu_bias* bias
         if (use_graph && (rc = em_build_graph(em, chunk))) return rc;
         done = 0;
         while (!done) {
-            if (use_graph) {
-                SF_HIP(hipGraphLaunch(em->graph, em->cur));
-            } else {
-                for (uint32_t i = 0; i < chunk; ++i) {
-                    if ((rc = em_enqueue_sweep(em))) return rc;
-                    if ((rc = em_enqueue_update(em, true))) return rc;
-                }
-            }
+            if ((rc = em_enqueue_chunk(em, use_graph, chunk))) return rc;      // (two-kernel iterations: the form em_begin_on leaves)
             if ((rc = em_poll_impl(em, &done, &st, false))) return rc;
         }
     }
@@ -3298,15 +3195,12 @@ int sfgpu_bootstrap(sfgpu_em* em, const sfgpu_em_opts* opts, uint32_t n_bootstra
     // 4.98 with three lanes of one kernel per iteration -- the persistent loop needs the chip to itself, see below); everywhere else
     // three lanes fill each other's kernel boundaries.  SFGPU_BS_LANES overrides.
     uint32_t n_lanes = 3;
-    {
-        const char* fe = getenv("SFGPU_EM_FUSED"); const char* pe = getenv("SFGPU_EM_PERSIST");
-        bool may = g_allow_persist.load(std::memory_order_relaxed) && !(fe && atoi(fe) == 0) && !(pe && atoi(pe) == 0) && em->gather && em->prob.C != 0 && em->xbuf && getenv("SFGPU_EM_EXACT_NORM") == nullptr &&
-                   o.max_iter >= 1u && o.max_iter < (1u << 24) - 2u && em->persist_ok != 0 && em->fused_ok != 0;
-        if (may && em->fused_ok < 0 && hipEventSynchronize(em->ev_plan) == hipSuccess)
-            em->fused_ok = ((*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 2u) == 0u && em->partial_a) ? 1 : 0;
-        if (may && em->fused_ok == 1 && em->persist_ok < 0) em_persist_check(em);
-        if (may && em->fused_ok == 1 && em->persist_ok == 1) n_lanes = 1;
-    }
+    const EmSwitches sw = em_read_switches();
+    EmForm form = EmForm::two_kernel;
+    // (no_persist is false here: this call sets it below, for the lanes it starts)
+    if (em_may_persist(em, o, sw) &&      // (no wait for the plan unless a replicate could be persistent)
+        !sw.exact_norm &&                 // (EM too, unlike em_choose_form: an exact-norm run keeps three lanes)
+        em_choose_form(em, o, sw, &form) == SFGPU_OK && form == EmForm::persistent) n_lanes = 1;
     if (const char* e = getenv("SFGPU_BS_LANES")) { long v = atol(e); if (v >= 1 && v <= 8) n_lanes = (uint32_t)v; }
     if (n_lanes > n_bootstraps) n_lanes = n_bootstraps ? n_bootstraps : 1;
     while (em->bs_clones.size() + 1 < n_lanes) {        // clones are kept with the handle for the next call

@@ -10,7 +10,8 @@ for spec in "$@"; do
   name="${spec%%:*}"; defs="${spec#*:}"
   hipcc $FLAGS $defs -c eqclass.hip -o variants/eqclass_$name.o
   hipcc $FLAGS -c core.hip -o variants/core_v.o           # (sfgpu_has_variants() answers 1)
-  hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libsfgpu_$name.so variants/core_v.o variants/eqclass_$name.o build/em.o build/misc.o build/primitives.o \
-        build/sampling.o build/gibbs.o build/filter.o build/bias.o build/merge.o build/mapper.o build/comm.o -Wl,-rpath,/opt/rocm/lib
+  # (every object the Makefile built, minus the two units compiled above)
+  hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libsfgpu_$name.so variants/core_v.o variants/eqclass_$name.o \
+        $(ls build/*.o | grep -v -e /core.o -e /eqclass.o) -Wl,-rpath,/opt/rocm/lib
   echo built $name "($defs)"
 done

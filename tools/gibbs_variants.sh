@@ -9,7 +9,8 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -munsafe-f
 for spec in "$@"; do
   name="${spec%%:*}"; defs="${spec#*:}"
   for f in gibbs sampling; do hipcc $FLAGS $defs -c $f.hip -o variants/${f}_$name.o; done
-  hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libsfgpu_$name.so build/core.o build/eqclass.o build/em.o build/misc.o build/primitives.o \
-        variants/sampling_$name.o variants/gibbs_$name.o build/filter.o build/bias.o build/merge.o build/mapper.o build/comm.o -Wl,-rpath,/opt/rocm/lib
+  # (every object the Makefile built, minus the two units compiled above)
+  hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libsfgpu_$name.so variants/sampling_$name.o variants/gibbs_$name.o \
+        $(ls build/*.o | grep -v -e /sampling.o -e /gibbs.o) -Wl,-rpath,/opt/rocm/lib
   echo built $name "($defs)"
 done

@@ -37,7 +37,8 @@ enum {
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8     /* malformed input text (sfgpu_eq_add_text_host) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host) */
+    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -157,6 +158,38 @@ typedef struct {
 } sfgpu_eqtext_result;
 SFGPU_API int sfgpu_eq_add_text_host(sfgpu_eq* eq, const char* h_text, uint64_t n_bytes, uint64_t n_transcripts,
                                      uint64_t chunk_bytes, sfgpu_eqtext_result* out);
+/* writeEquivCounts (src/GZipWriter.cpp:77-88), the other direction: the CLASS SECTION of an eq_classes.txt file formatted on the
+ * device from a class table in CSR form (the sfgpu_eq_export_device arrays, a table merged by sfgpu_eqvec_merge_disjoint, or
+ * one the caller assembled).  For each class, in the order given,
+ *     k \t id_1 \t ... \t id_k \t count \n
+ * decimal, no padding, no sign.  The header of the file (M, C and the M names) is the host's business, as in the reader.
+ * The arrays are formatted as they are: ids up to 2^32 - 1, counts up to 2^64 - 1 (20 digits), any k including 0
+ * ("0 \t count \n"); nothing is checked against a transcript count.  rowptr must start at 0 and never decrease (else
+ * SFGPU_ERR_INVALID); n_classes < 2^32 - 1 (SFGPU_ERR_RANGE).  The text may exceed 4 GB.
+ * The text is handed to `sink` in consecutive chunks, in order.  Each chunk is a whole number of lines (it ends in '\n'), is at
+ * most chunk_bytes long (0 = 32 MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID) and greedy: it holds as many whole lines as
+ * fit, so n_chunks is a function of the table and chunk_bytes alone.  h_bytes points into a pinned staging buffer of the
+ * library and is valid only during the call.  Chunk c + 1 is formatted and copied while the sink consumes chunk c (two staging
+ * buffers).  All line lengths are known before a byte is formatted: a line longer than chunk_bytes fails the call with
+ * SFGPU_ERR_RANGE before the first sink call (`out` holds the sizes).  A nonzero return of the sink ends the call with
+ * SFGPU_ERR_IO and no further sink call.  sink == NULL sizes the text only: `out` is filled, nothing is formatted or copied.
+ * n_classes == 0 is SFGPU_OK with zero bytes and no sink call.
+ * Synchronous; ordered behind whatever is queued on `stream`; independent calls may run from several threads.  Scratch on the
+ * device: 16 bytes per token (a table has n_ids + 2 n_classes tokens) and two chunk buffers. */
+typedef int (*sfgpu_text_sink)(const char* h_bytes, uint64_t n_bytes, void* user);   /* nonzero = stop */
+typedef struct {
+    uint64_t n_bytes;         /* bytes of the class section */
+    uint64_t n_lines;         /* = n_classes */
+    uint64_t n_ids;           /* label ids over those lines (rowptr[n_classes]) */
+    uint64_t n_chunks;        /* sink calls made */
+    uint64_t max_line_bytes;  /* longest line, with its '\n' */
+    double format_ms;         /* device events: sizing, scans, chunk plan, format kernels of all chunks */
+    double d2h_ms;            /* device events around the staged copies */
+    double sink_ms;           /* host clock inside the sink */
+} sfgpu_eqtext_write_result;
+SFGPU_API int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* d_ids, const uint64_t* d_counts,
+                                     uint64_t n_classes, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                     sfgpu_eqtext_write_result* out, sfgpu_stream stream);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

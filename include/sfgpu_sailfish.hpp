@@ -10,6 +10,7 @@
 //   sailfish::gpu::CollapsedEMOptimizer           include/CollapsedEMOptimizer.hpp:20-35, src/CollapsedEMOptimizer.cpp:557-893
 //   sailfish::gpu::CollapsedGibbsSampler          include/CollapsedGibbsSampler.hpp:22-32, src/CollapsedGibbsSampler.cpp:187-291
 //   sailfish::gpu::loadEquivClasses               src/SailfishQuantify.cpp:1444-1494 (commented out there; --readEqClasses :1114)
+//   sailfish::gpu::writeEquivCounts               src/GZipWriter.cpp:51-92 (the class lines are formatted on the device)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -142,7 +143,8 @@ class EquivalenceClassBuilder {
     }
 
     // :110-112  the classes on the host, canonical order (first id, hash, length, label) -- the reference's order is
-    // the cuckoo table's and changes from run to run.  Only writeEquivCounts needs this copy; optimize() does not.
+    // the cuckoo table's and changes from run to run.  For hosts that want the vector: optimize() and writeEquivCounts (below)
+    // work from the device table.
     std::vector<std::pair<const TranscriptGroup, TGValue>>& eqVec() {
         if (vec_.empty() && n_classes_) {
             std::vector<uint32_t> rowptr(n_classes_ + 1), ids(nnz_ ? nnz_ : 1);
@@ -307,6 +309,39 @@ inline void loadEquivClasses(const std::string& eqClassFile, ReadExperiment& rea
              std::to_string(r.n_lines));
     readExp.numObservedFragmentsAtomic() += r.sum_counts;       // numObservedFragments += count; validHits += count (:1478-1479)
     readExp.numMappedFragmentsAtomic() += r.sum_counts;
+}
+
+// ---- GZipWriter::writeEquivCounts, src/GZipWriter.cpp:51-92 ----------------------------------------------------------------
+// Writes the file loadEquivClasses reads: M, C and the names of readExp.transcripts() from the host, then the class lines of the
+// finished builder (call it after finish()), formatted on the device from the exported table (sfgpu_eqvec_write_text: format and
+// limits in sfgpu.h) and streamed into the file chunk by chunk -- no per-class vectors on the host (eqVec() is not called).
+// Classes are in the canonical order.  Throws std::runtime_error naming the file when it cannot be opened or written.
+inline bool writeEquivCounts(const std::string& eqClassFile, ReadExperiment& readExp) {
+    std::ofstream out(eqClassFile, std::ios::binary);
+    if (!out) throw std::runtime_error(eqClassFile + ": cannot open for writing");
+    auto& txps = readExp.transcripts();
+    auto& eq = readExp.equivalenceClassBuilder();
+    const uint64_t C = eq.numClasses();
+    out << txps.size() << '\n' << C << '\n';
+    for (const auto& t : txps) out << t.RefName << '\n';
+    if (C) {
+        DeviceBuf<uint32_t> rowptr(C + 1), ids(eq.numNonzeros());
+        DeviceBuf<uint64_t> counts(C);
+        check(sfgpu_eq_export_device(eq.handle(), rowptr.get(), ids.get(), counts.get(), nullptr), "sfgpu_eq_export_device");
+        check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize");        // the export runs on the builder's stream
+        auto sink = [](const char* bytes, uint64_t n, void* user) -> int {
+            std::ofstream& o = *static_cast<std::ofstream*>(user);
+            o.write(bytes, static_cast<std::streamsize>(n));
+            return o ? 0 : 1;
+        };
+        sfgpu_eqtext_write_result r;
+        const int rc = sfgpu_eqvec_write_text(rowptr.get(), ids.get(), counts.get(), C, 0, sink, &out, &r, nullptr);
+        if (rc == SFGPU_ERR_IO) throw std::runtime_error(eqClassFile + ": write failed");
+        check(rc, "sfgpu_eqvec_write_text");
+    }
+    out.close();
+    if (!out) throw std::runtime_error(eqClassFile + ": write failed");
+    return true;
 }
 
 namespace detail {

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (imported first so libamdhip64.so.7 resolves to torc
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGPU_LIB_PATH", os.path.join(_HERE, "csrc", "libsfgpu.so"))   # override: kernel-tuning builds
 
-OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED, ERR_FORMAT = range(9)
+OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED, ERR_FORMAT, ERR_IO = range(10)
 
 
 class SfgpuError(RuntimeError):
@@ -55,7 +55,16 @@ class EqTextResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class EqTextWriteResult(C.Structure):
+    _fields_ = [("n_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("n_ids", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("max_line_bytes", C.c_uint64), ("format_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _LOG_CB = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
+TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p)      # sfgpu_text_sink
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p)      # sfgpu_allreduce_fn
 SAMPLE_CB = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_uint64, C.c_void_p)
 GIBBS_CB = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_int32), C.c_uint64, C.c_void_p)
@@ -119,6 +128,7 @@ _SIGS = {
     "sfgpu_eq_add_batch_device": (C.c_int, [_P, _P, _P, C.c_uint32]),
     "sfgpu_eq_add_weighted_device": (C.c_int, [_P, _P, _P, _P, C.c_uint32]),
     "sfgpu_eq_add_text_host": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EqTextResult)]),
+    "sfgpu_eqvec_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P, C.POINTER(EqTextWriteResult), _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -1,0 +1,347 @@
+// eqtext_write.hip -- the class section of an eq_classes.txt file (GZipWriter::writeEquivCounts, src/GZipWriter.cpp:77-88)
+// formatted on the device from a CSR class table: sfgpu_eqvec_write_text, the mirror of eqtext.hip.
+//
+// Tokens in file order are k, the ids, the count of every class: class c starts at token rowptr[c] + 2 c and token t of the
+// table is followed by '\t', the count by '\n'.  All work is per token, so a label of 100 000 ids is as parallel as 100 000
+// one-id labels.
+//   sizing  k_tok_size: one lane per token finds its class (the class keys of a block's 256 tokens are staged in LDS) and
+//           writes digits + 1; an exclusive scan (primitives.h) gives every token its byte start, 64-bit over the table.
+//           k_tok_place: the start of every line, and for every 4 KB tile of the OUTPUT the token that holds its first byte.
+//           k_line_max: the longest line.  k_chunk_plan: the greedy chunk ends, by binary search of the line starts.
+//   format  k_format: one block per 4 KB tile of the output.  The tokens that overlap the tile are formatted into an LDS image
+//           of the tile (decfmt.h; a token is clipped to the tile), then every lane stores one aligned 16-byte group: global
+//           memory sees only full-width coalesced stores.  Tiles are aligned in the TABLE's byte offsets, so the per-tile
+//           token index is made once whatever the chunk size; a chunk's buffer starts at the tile that holds its first byte.
+// The formatted chunk c + 1 is produced and copied to its pinned buffer while the sink consumes chunk c.
+#include "common.h"
+#include "decfmt.h"
+#include "primitives.h"
+
+#include <chrono>
+#include <cstring>
+
+namespace sfgpu {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr uint32_t kTileBytes = 4096;                     // kBlock lanes x one 16-byte store
+constexpr int kTileShift = 12;
+constexpr uint64_t kDefaultChunk = 32ull << 20;           // the reader's limits (eqtext.hip)
+constexpr uint64_t kMaxChunk = 1ull << 30;
+constexpr uint64_t kMaxClasses = 0xffffffffull;           // a token's class index is kept in 32 bits
+constexpr int kMaxTokBytes = 21;                          // 20 digits and the separator
+
+inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+__device__ inline uint64_t class_key(const uint32_t* __restrict__ rowptr, uint64_t c) { return (uint64_t)rowptr[c] + 2 * c; }
+
+// the value of token t of class c: 0 -> k, 1 .. k -> the ids, k + 1 -> the count (is_count)
+__device__ inline uint64_t token_value(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids,
+                                       const uint64_t* __restrict__ counts, uint64_t t, uint32_t c, bool* is_count) {
+    const uint32_t r0 = rowptr[c], k = rowptr[c + 1] - r0;
+    const uint64_t j = t - ((uint64_t)r0 + 2ull * c);
+    *is_count = j == (uint64_t)k + 1;
+    if (j == 0) return k;
+    if (*is_count) return counts[c];
+    return ids[t - 2ull * c - 1];
+}
+
+// misc[0] |= 1 where rowptr decreases (the token layout would leave the arrays)
+__global__ void k_check_rowptr(const uint32_t* __restrict__ rowptr, uint64_t n_classes, unsigned long long* __restrict__ misc) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < n_classes && rowptr[c] > rowptr[c + 1]) atomicOr(&misc[0], 1ull);
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_tok_size(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, const uint64_t* __restrict__ counts,
+           uint64_t n_classes, uint64_t n_tok, uint32_t* __restrict__ tok_len, uint32_t* __restrict__ tok_class) {
+    __shared__ uint64_t keys[kBlock];
+    const uint64_t t0 = (uint64_t)blockIdx.x * kBlock, t = t0 + threadIdx.x;
+    // the class of the block's first token (the same search in every lane: its loads are uniform)
+    uint64_t lo = 0, hi = n_classes;                      // key(lo) <= t0 < key(hi), key(n_classes) = n_tok
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (class_key(rowptr, mid) <= t0) lo = mid; else hi = mid;
+    }
+    // a class holds >= 2 tokens: at most 128 classes begin behind t0 inside the block
+    const uint64_t cc = lo + threadIdx.x;
+    keys[threadIdx.x] = cc <= n_classes ? class_key(rowptr, cc) : ~0ull;
+    __syncthreads();
+    if (t >= n_tok) return;
+    uint32_t a = 0, b = kBlock;                           // keys[a] <= t < keys[b] (keys[kBlock] = infinity)
+    while (b - a > 1) {
+        const uint32_t mid = (a + b) / 2;
+        if (keys[mid] <= t) a = mid; else b = mid;
+    }
+    const uint32_t c = (uint32_t)(lo + a);
+    bool is_count;
+    const uint64_t v = token_value(rowptr, ids, counts, t, c, &is_count);
+    tok_len[t] = (uint32_t)dec_len_u64(v) + 1u;
+    tok_class[t] = c;
+}
+
+// line_start[c] = byte start of class c's first token (line_start[n_classes] = the total); tile_first[i] = the token that holds
+// byte i * kTileBytes (tile_first[number of tiles] = n_tok).  A token is shorter than a tile: it crosses at most one tile edge.
+__global__ void k_tok_place(const uint32_t* __restrict__ rowptr, uint64_t n_classes, uint64_t n_tok, const uint64_t* __restrict__ tok_start,
+                            const uint32_t* __restrict__ tok_class, uint64_t* __restrict__ line_start, uint64_t* __restrict__ tile_first) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tok) return;
+    const uint64_t s = tok_start[t], e = tok_start[t + 1];
+    const uint64_t ta = s >> kTileShift, tb = (e - 1) >> kTileShift;
+    if ((s & (kTileBytes - 1)) == 0) tile_first[ta] = t;
+    if (tb > ta) tile_first[tb] = t;
+    const uint32_t c = tok_class[t];
+    if (t == class_key(rowptr, c)) line_start[c] = s;
+    if (t == n_tok - 1) {
+        line_start[n_classes] = e;
+        tile_first[(e + kTileBytes - 1) >> kTileShift] = n_tok;
+    }
+}
+
+// a fixed grid strides over the classes: one atomic per wavefront of a few thousand, not of every 64 classes (they serialise on the address)
+constexpr unsigned kLineMaxBlocks = 1024;
+__global__ void k_line_max(const uint64_t* __restrict__ line_start, uint64_t n_classes, unsigned long long* __restrict__ misc) {
+    unsigned long long len = 0;
+    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_classes; c += (uint64_t)gridDim.x * blockDim.x) {
+        const unsigned long long l = line_start[c + 1] - line_start[c];
+        len = l > len ? l : len;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(len, o);
+        len = other > len ? other : len;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) atomicMax(&misc[1], len);
+}
+
+// greedy chunks, one thread: chunk i holds classes [plan[2 i - 2], plan[2 i]) and ends at byte plan[2 i + 1].  Every line fits
+// a chunk (checked by the host before the launch), so every chunk takes at least one line; misc[2] = number of chunks.
+__global__ void k_chunk_plan(const uint64_t* __restrict__ line_start, uint64_t n_classes, uint64_t chunk_bytes, uint64_t cap,
+                             uint64_t* __restrict__ plan, unsigned long long* __restrict__ misc) {
+    if (blockIdx.x || threadIdx.x) return;
+    uint64_t c = 0, n = 0;
+    while (c < n_classes && n < cap) {
+        const uint64_t limit = line_start[c] + chunk_bytes;
+        uint64_t lo = c + 1, hi = n_classes + 1;          // line_start[lo] <= limit < line_start[hi] (line_start[n_classes + 1] = infinity)
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (line_start[mid] <= limit) lo = mid; else hi = mid;
+        }
+        plan[2 * n] = lo; plan[2 * n + 1] = line_start[lo];
+        ++n;
+        c = lo;
+    }
+    misc[2] = n;
+}
+
+// one block per tile of the output; `out` is the chunk buffer, whose byte 0 is table byte out_base (a multiple of kTileBytes)
+__global__ void __launch_bounds__(kBlock)
+k_format(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, const uint64_t* __restrict__ counts,
+         const uint64_t* __restrict__ tok_start, const uint32_t* __restrict__ tok_class, const uint64_t* __restrict__ tile_first,
+         uint64_t n_tok, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
+    __shared__ uint4 tile4[kBlock];
+    char* tile = reinterpret_cast<char*>(tile4);
+    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
+    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);      // (the bytes behind the end of the table)
+    __syncthreads();
+    // tokens [t_lo, t_hi]: t_hi holds the first byte of the next tile (it may begin there: then nothing of it is in this tile)
+    const uint64_t t_lo = tile_first[ti];
+    uint64_t t_hi = tile_first[ti + 1];
+    if (t_hi >= n_tok) t_hi = n_tok - 1;
+    for (uint64_t t = t_lo + threadIdx.x; t <= t_hi; t += kBlock) {
+        const uint64_t s = tok_start[t];
+        const int nd = (int)(tok_start[t + 1] - s) - 1;
+        bool is_count;
+        const uint64_t v = token_value(rowptr, ids, counts, t, tok_class[t], &is_count);
+        const int64_t last = (int64_t)(s - base) + nd - 1;          // tile offset of the last digit (may lie before or behind the tile)
+        auto put = [&](int i, char ch) {
+            const int64_t p = last - i;
+            if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = ch;
+        };
+        if (v <= 0xffffffffull) dec_put_fixed_u32((uint32_t)v, nd, 0, put);
+        else dec_put_u64(v, put);
+        if (last + 1 >= 0 && last + 1 < (int64_t)kTileBytes) tile[last + 1] = is_count ? '\n' : '\t';
+    }
+    __syncthreads();
+    const uint64_t g = base + 16ull * threadIdx.x;
+    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct WriteScratch {
+    DevBuf<uint32_t> tok_len, tok_class;
+    DevBuf<uint64_t> tok_start, line_start, tile_first, plan;
+    DevBuf<uint4> out[2];
+    DevBuf<unsigned long long> misc;        // [0] rowptr not monotone, [1] longest line, [2] chunks planned
+};
+
+}  // namespace
+}  // namespace sfgpu
+
+using namespace sfgpu;
+
+extern "C" int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* d_ids, const uint64_t* d_counts, uint64_t n_classes,
+                                      uint64_t chunk_bytes, sfgpu_text_sink sink, void* user, sfgpu_eqtext_write_result* out,
+                                      sfgpu_stream stream) {
+    SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: null result");
+    memset(out, 0, sizeof(*out));
+    if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
+    SF_REQUIRE(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk, SFGPU_ERR_INVALID,
+               "sfgpu_eqvec_write_text: chunk_bytes must lie in [16, 2^30] (0 = default)");
+    if (n_classes == 0) return SFGPU_OK;
+    SF_REQUIRE(d_rowptr && d_counts, SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: null table");
+    SF_REQUIRE(n_classes < kMaxClasses, SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: n_classes must be below 2^32 - 1");
+
+    WriteScratch S;
+    hipStream_t st = nullptr, cs = nullptr;
+    char* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev_in = nullptr, ev_s[2] = {nullptr, nullptr};
+    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
+    unsigned long long* h_misc = nullptr;     // [0 .. 2] misc, [3] total bytes, [4] rowptr[0] and rowptr[n_classes]
+    uint64_t* h_plan = nullptr;
+    int rc = SFGPU_OK;
+
+    // every exit below goes through `done`: nothing may be released while a copy still writes the pinned buffers
+#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
+#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
+#define T_FAIL(code, msg) do { set_error("%s", msg); rc = (code); goto done; } while (0)
+    {
+        T_HIP(stream_acquire(&st));
+        T_HIP(stream_acquire(&cs));
+        T_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
+        for (auto& e : ev_s) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
+        T_HIP(pinned_malloc(&h_misc, 8 * sizeof(unsigned long long)));
+        // behind whatever the caller has queued on `stream`
+        T_HIP(hipEventRecord(ev_in, as_stream(stream)));
+        T_HIP(hipStreamWaitEvent(st, ev_in, 0));
+
+        T_TRY(S.misc.reserve(4, st, false));
+        T_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
+        uint32_t* h_ends = reinterpret_cast<uint32_t*>(&h_misc[4]);
+        T_HIP(hipMemcpyAsync(&h_ends[0], d_rowptr, 4, hipMemcpyDeviceToHost, st));
+        T_HIP(hipMemcpyAsync(&h_ends[1], d_rowptr + n_classes, 4, hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_check_rowptr, dim3(grid_of(n_classes)), dim3(kBlock), 0, st, d_rowptr, n_classes, S.misc.p);
+        T_HIP(hipGetLastError());
+        T_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        if (h_ends[0] != 0 || h_misc[0] != 0) T_FAIL(SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: rowptr must start at 0 and never decrease");
+        const uint64_t nnz = h_ends[1];
+        if (nnz && !d_ids) T_FAIL(SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: null ids");
+        const uint64_t n_tok = nnz + 2 * n_classes;
+        const uint64_t tile_cap = (n_tok * kMaxTokBytes >> kTileShift) + 2;
+
+        // ---- sizing: token lengths, byte starts, line starts, the tile index, the longest line
+        T_TRY(S.tok_len.reserve(n_tok + 1, st, false));
+        T_TRY(S.tok_class.reserve(n_tok, st, false));
+        T_TRY(S.tok_start.reserve(n_tok + 1, st, false));
+        T_TRY(S.line_start.reserve(n_classes + 1, st, false));
+        T_TRY(S.tile_first.reserve(tile_cap, st, false));
+        T_HIP(hipEventRecord(ev_s[0], st));
+        hipLaunchKernelGGL(k_tok_size, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, d_ids, d_counts, n_classes, n_tok,
+                           S.tok_len.p, S.tok_class.p);
+        T_HIP(hipGetLastError());
+        T_TRY(exclusive_scan_u32(S.tok_len.p, S.tok_start.p, n_tok, st, false));
+        hipLaunchKernelGGL(k_tok_place, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, n_classes, n_tok, S.tok_start.p,
+                           S.tok_class.p, S.line_start.p, S.tile_first.p);
+        T_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_line_max, dim3(grid_of(n_classes) < kLineMaxBlocks ? grid_of(n_classes) : kLineMaxBlocks), dim3(kBlock), 0, st, S.line_start.p, n_classes, S.misc.p);
+        T_HIP(hipGetLastError());
+        T_HIP(hipEventRecord(ev_s[1], st));
+        T_HIP(hipMemcpyAsync(&h_misc[1], S.misc.p + 1, 8, hipMemcpyDeviceToHost, st));
+        T_HIP(hipMemcpyAsync(&h_misc[3], S.tok_start.p + n_tok, 8, hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        {
+            float a = 0.f;
+            if (hipEventElapsedTime(&a, ev_s[0], ev_s[1]) == hipSuccess) out->format_ms += (double)a;
+        }
+        const uint64_t total = h_misc[3];
+        out->n_bytes = total; out->n_lines = n_classes; out->n_ids = nnz; out->max_line_bytes = h_misc[1];
+        if (!sink) goto done;
+        if (out->max_line_bytes > chunk_bytes) T_FAIL(SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: a line is longer than chunk_bytes");
+
+        // ---- the chunk plan: two consecutive greedy chunks hold more than chunk_bytes together
+        const uint64_t plan_cap = 2 * (total / chunk_bytes) + 2;
+        T_TRY(S.plan.reserve(2 * plan_cap, st, false));
+        T_HIP(pinned_malloc(&h_plan, 2 * plan_cap * sizeof(uint64_t)));
+        T_HIP(hipEventRecord(ev_s[0], st));
+        hipLaunchKernelGGL(k_chunk_plan, dim3(1), dim3(kWave), 0, st, S.line_start.p, n_classes, chunk_bytes, plan_cap, S.plan.p, S.misc.p);
+        T_HIP(hipGetLastError());
+        T_HIP(hipEventRecord(ev_s[1], st));
+        T_HIP(hipMemcpyAsync(&h_misc[2], S.misc.p + 2, 8, hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        const uint64_t n_chunks = h_misc[2];
+        T_HIP(hipMemcpyAsync(h_plan, S.plan.p, 2 * n_chunks * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        {
+            float a = 0.f;
+            if (hipEventElapsedTime(&a, ev_s[0], ev_s[1]) == hipSuccess) out->format_ms += (double)a;
+        }
+        if (n_chunks == 0 || h_plan[2 * n_chunks - 2] != n_classes || h_plan[2 * n_chunks - 1] != total)
+            T_FAIL(SFGPU_ERR_HIP, "sfgpu_eqvec_write_text: the chunk plan does not cover the table");
+
+        // ---- format + copy + sink, two buffers: chunk i + 1 is formatted and copied while the sink holds chunk i
+        const uint64_t stage_bytes = total < chunk_bytes ? total : chunk_bytes;
+        const uint64_t out_groups = (stage_bytes + 2 * kTileBytes) / 16 + 1;
+        for (int b = 0; b < 2 && (uint64_t)b < n_chunks; ++b) {
+            T_HIP(pinned_malloc(&pinned[b], stage_bytes));
+            T_TRY(S.out[b].reserve(out_groups, st, false));
+            T_HIP(hipEventCreateWithFlags(&ev_f0[b], hipEventDefault));
+            T_HIP(hipEventCreateWithFlags(&ev_f1[b], hipEventDefault));
+            T_HIP(hipEventCreateWithFlags(&ev_c0[b], hipEventDefault));
+            T_HIP(hipEventCreateWithFlags(&ev_c1[b], hipEventDefault));
+        }
+        auto chunk_begin = [&](uint64_t i) -> uint64_t { return i ? h_plan[2 * i - 1] : 0; };
+        // format on st into S.out[slot], then the copy on cs into pinned[slot]; the slot's previous chunk has left the sink, and
+        // its copy (which read S.out[slot]) was waited for before that
+        auto enqueue = [&](uint64_t i) -> int {
+            const int slot = (int)(i & 1);
+            const uint64_t b0 = chunk_begin(i), b1 = h_plan[2 * i + 1];
+            const uint64_t first_tile = b0 >> kTileShift, last_tile = (b1 - 1) >> kTileShift, out_base = first_tile << kTileShift;
+            SF_HIP(hipEventRecord(ev_f0[slot], st));
+            hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, st, d_rowptr, d_ids, d_counts,
+                               S.tok_start.p, S.tok_class.p, S.tile_first.p, n_tok, total, first_tile, out_base, S.out[slot].p);
+            SF_HIP(hipGetLastError());
+            SF_HIP(hipEventRecord(ev_f1[slot], st));
+            SF_HIP(hipStreamWaitEvent(cs, ev_f1[slot], 0));
+            SF_HIP(hipEventRecord(ev_c0[slot], cs));
+            SF_HIP(hipMemcpyAsync(pinned[slot], reinterpret_cast<const char*>(S.out[slot].p) + (b0 - out_base), b1 - b0, hipMemcpyDeviceToHost, cs));
+            SF_HIP(hipEventRecord(ev_c1[slot], cs));
+            return SFGPU_OK;
+        };
+        T_TRY(enqueue(0));
+        for (uint64_t i = 0; i < n_chunks; ++i) {
+            const int slot = (int)(i & 1);
+            if (i + 1 < n_chunks) T_TRY(enqueue(i + 1));
+            T_HIP(hipEventSynchronize(ev_c1[slot]));
+            {
+                float a = 0.f, b = 0.f;
+                if (hipEventElapsedTime(&a, ev_f0[slot], ev_f1[slot]) == hipSuccess) out->format_ms += (double)a;
+                if (hipEventElapsedTime(&b, ev_c0[slot], ev_c1[slot]) == hipSuccess) out->d2h_ms += (double)b;
+            }
+            const auto t0 = std::chrono::steady_clock::now();
+            const int stop = sink(pinned[slot], h_plan[2 * i + 1] - chunk_begin(i), user);
+            out->sink_ms += ms_since(t0);
+            out->n_chunks++;
+            if (stop) T_FAIL(SFGPU_ERR_IO, "sfgpu_eqvec_write_text: the sink refused a chunk");
+        }
+    }
+done:
+    if (cs) (void)hipStreamSynchronize(cs);
+    if (st) (void)hipStreamSynchronize(st);
+    for (int b = 0; b < 2; ++b) {
+        if (pinned[b]) pinned_free(pinned[b]);
+        for (hipEvent_t e : {ev_f0[b], ev_f1[b], ev_c0[b], ev_c1[b], ev_s[b]}) if (e) (void)hipEventDestroy(e);
+    }
+    if (ev_in) (void)hipEventDestroy(ev_in);
+    if (h_plan) pinned_free(h_plan);
+    if (h_misc) pinned_free(h_misc);
+    if (cs) stream_release(cs);
+    if (st) stream_release(st);
+    return rc;
+#undef T_HIP
+#undef T_TRY
+#undef T_FAIL
+}

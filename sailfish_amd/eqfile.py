@@ -6,11 +6,17 @@
 The header (M, C, the names) is read here on the host.  The class section is handed to the library by address (the file
 is mapped, not read into Python) and parsed on the device (sfgpu_eq_add_text_host); its classes are folded into a builder
 with upsert semantics, so several files (lanes, runs) fold into one table.  Every error names the file and the 1-based
-line of the file, header lines included."""
+line of the file, header lines included.
+
+The way out is the mirror: write_file writes the header here and hands the table's device arrays to the library, which formats
+the class section on the device (sfgpu_eqvec_write_text) and delivers it in whole-line chunks (write_classes); text_size only
+measures it.  format_text is the independent numpy restatement of the same bytes that tools and tests compare against."""
+import ctypes as C
 import mmap
 import os
 
 import numpy as np
+import torch
 
 from . import _lib
 
@@ -143,6 +149,65 @@ def fold_files(builder, paths, names=None, chunk_bytes=0):
     check_same_names(headers)
     results = [fold_file(builder, p, chunk_bytes=chunk_bytes)[1] for p in paths]
     return headers, results
+
+
+def _device_table(vec):
+    """(rowptr, ids, counts) device tensors of an EqVec or of such a triple; 32-bit rowptr / ids and 64-bit counts, as exported."""
+    rowptr, ids, counts = (vec.rowptr, vec.ids, vec.counts) if hasattr(vec, "rowptr") else vec
+    for t, sizes, what in ((rowptr, (4,), "rowptr"), (ids, (4,), "ids"), (counts, (8,), "counts")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and not t.is_floating_point() and t.element_size() in sizes):
+            raise TypeError(f"{what}: expected a device tensor of {sizes[0] * 8}-bit integers")
+    if rowptr.numel() != counts.numel() + 1:
+        raise ValueError(f"rowptr has {rowptr.numel()} entries for {counts.numel()} classes")
+    return rowptr.contiguous(), ids.contiguous(), counts.contiguous()
+
+
+def _write_text(vec, chunk_bytes, sink):
+    """sfgpu_eqvec_write_text on the table's device, behind torch's current stream; returns (status, result)."""
+    rowptr, ids, counts = _device_table(vec)
+    res = _lib.EqTextWriteResult()
+    with torch.cuda.device(rowptr.device):
+        rc = _lib.lib().sfgpu_eqvec_write_text(_lib.ptr(rowptr), _lib.ptr(ids), _lib.ptr(counts), counts.numel(), int(chunk_bytes),
+                                               sink, None, C.byref(res), _lib.current_stream_ptr())
+    return rc, res
+
+
+def text_size(vec):
+    """What the class section of `vec` (an EqVec, or (rowptr, ids, counts) device tensors) will measure, without formatting it:
+    the sfgpu_eqtext_write_result as a dict (n_bytes, n_lines, n_ids, max_line_bytes)."""
+    rc, res = _write_text(vec, 0, _lib.TEXT_SINK(0))
+    _lib.check(rc)
+    return res.as_dict()
+
+
+def write_classes(fileobj, vec, chunk_bytes=0):
+    """The class section of `vec` (an EqVec, or (rowptr, ids, counts) device tensors), formatted on the device
+    (sfgpu_eqvec_write_text), into the binary file object `fileobj`, chunk by chunk.  Returns the sfgpu_eqtext_write_result as
+    a dict.  An exception of fileobj.write stops the writer and is raised again here."""
+    raised = []
+
+    def sink(addr, n, _user):
+        try:                                   # nothing may unwind through the C frame
+            fileobj.write(memoryview((C.c_char * n).from_address(addr)))
+            return 0
+        except BaseException as e:             # noqa: BLE001  (re-raised below)
+            raised.append(e)
+            return 1
+
+    rc, res = _write_text(vec, chunk_bytes, _lib.TEXT_SINK(sink))
+    if raised:
+        raise raised[0]
+    _lib.check(rc)
+    return res.as_dict()
+
+
+def write_file(path, names, vec, chunk_bytes=0):
+    """eq_classes.txt for the table `vec` over the transcripts `names`: the header (M, C, the names) from the host, the class
+    section through write_classes.  The bytes are format_text's.  Returns write_classes' result."""
+    rowptr, _, counts = _device_table(vec)
+    with open(path, "wb") as f:
+        f.write(f"{len(names)}\n{counts.numel()}\n".encode() + "".join(n + "\n" for n in names).encode())
+        return write_classes(f, vec, chunk_bytes)
 
 
 def format_text(names, rowptr, ids, counts):

@@ -44,18 +44,12 @@ def write_abundances(path, readExp: ReadExperiment, sopt: SailfishOpts):
 
 
 def write_equiv_counts(path, readExp: ReadExperiment, sopt: SailfishOpts):
-    """writeEquivCounts (GZipWriter.cpp:51-92): aux/eq_classes.txt (canonical class order)."""
-    txps = readExp.transcripts()
-    rowptr, ids, counts, _ = readExp.equivalenceClassBuilder().eqVec().to_numpy()
+    """writeEquivCounts (GZipWriter.cpp:51-92): aux/eq_classes.txt (canonical class order).  The header is written here; the
+    class lines are formatted on the device from the builder's table (eqfile.write_file, sfgpu_eqvec_write_text)."""
+    from . import eqfile
     aux = os.path.join(path, sopt.auxDir)
     os.makedirs(aux, exist_ok=True)
-    with open(os.path.join(aux, "eq_classes.txt"), "w") as f:
-        f.write(f"{len(txps)}\n{len(counts)}\n")
-        for name in txps.RefName:
-            f.write(name + "\n")
-        for c in range(len(counts)):
-            lab = ids[rowptr[c]:rowptr[c + 1]]
-            f.write(f"{len(lab)}\t" + "".join(f"{t}\t" for t in lab) + f"{counts[c]}\n")
+    eqfile.write_file(os.path.join(aux, "eq_classes.txt"), readExp.transcripts().RefName, readExp.equivalenceClassBuilder().eqVec())
     return True
 
 

@@ -1,14 +1,17 @@
-"""Class-file reader at cfg3 size (sfgpu_eq_add_text_host; sailfish_amd/eqfile.py): writes an eq_classes.txt of the 400 M-read /
-200 k-transcript synthetic experiment and times the file read, the H2D copy, the parse kernels, the fold + finish, requantify end
-to end, and the host baseline (a per-line Python parse feeding insertGroups).
+"""Class-file reader and writer at cfg3 size (sfgpu_eq_add_text_host, sfgpu_eqvec_write_text; sailfish_amd/eqfile.py): writes an
+eq_classes.txt of the 400 M-read / 200 k-transcript synthetic experiment with the device writer and times the file read, the H2D
+copy, the parse kernels, the fold + finish, requantify end to end, and the host baseline (a per-line Python parse feeding
+insertGroups).  The write leg times eqfile.write_file (format kernels, D2H copies, the sink), the per-class Python loop the writer
+used before, the numpy format_text, and a plain pinned D2H copy of the same bytes.
 
 The table is the one the class build would make from cfg3's reads: pool labels (synth.label_pool, P = 4 M) drawn as
 synth.reads_from_pool draws them (min of two uniform picks) -- each label's count is a binomial of R reads instead of 400 M reads
-generated one by one -- folded through insertGroups and exported.  The file is written with eqfile.format_text; a small case
-checks first that its bytes are writer.write_equiv_counts'.
+generated one by one -- folded through insertGroups and exported.  The file is written with eqfile.write_file and compared once
+with eqfile.format_text; a small case checks first that format_text's bytes are writer.write_equiv_counts'.
 
-    python tools/eqfile_probe.py [--out DIR] [--reads 400000000] [--parse-only] [--no-host]
-Prints one JSON line.  --parse-only: write the file and fold it once (for rocprofv3 --kernel-trace --stats)."""
+    python tools/eqfile_probe.py [--out DIR] [--reads 400000000] [--parse-only] [--write] [--write-only] [--no-host]
+Prints one JSON line.  --write: the write leg alone, with its baselines.  --parse-only: write the file and fold it once;
+--write-only: write the file three times (both for rocprofv3 --kernel-trace --stats)."""
 import argparse
 import json
 import os
@@ -52,7 +55,53 @@ def cfg3_table(dev, M=200_000, P=4_000_000, R=400_000_000):
     eq.finish()
     rowptr, ids, counts, _ = eq.eqVec().to_numpy()
     ref_len = synth.transcript_lengths(M).numpy().view(np.uint32)
-    return [f"ENST{i:011d}" for i in range(M)], ref_len, (rowptr, ids, counts)
+    return [f"ENST{i:011d}" for i in range(M)], ref_len, (rowptr, ids, counts), eq.eqVec()
+
+
+def loop_write(path, names, rowptr, ids, counts):
+    """writer.write_equiv_counts as it was before the device writer: one Python iteration per class over a host copy"""
+    with open(path, "w") as f:
+        f.write(f"{len(names)}\n{len(counts)}\n")
+        for name in names:
+            f.write(name + "\n")
+        for c in range(len(counts)):
+            lab = ids[rowptr[c]:rowptr[c + 1]]
+            f.write(f"{len(lab)}\t" + "".join(f"{t}\t" for t in lab) + f"{counts[c]}\n")
+
+
+def write_leg(a, dev, path, names, vec, text, rec):
+    """eqfile.write_file against the loop, format_text (timed by the caller) and a plain pinned D2H copy of the class section"""
+    runs = []
+    for _ in range(4):                                       # the first run warms code objects, pools and the page cache
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        res = eqfile.write_file(path, names, vec)
+        runs.append(dict(res, write_file_s=time.perf_counter() - t))
+    assert open(path, "rb").read() == text
+    rec["writer"] = runs[1:]
+    rec["text_size"] = eqfile.text_size(vec)
+    n = runs[-1]["n_bytes"]
+    d = torch.zeros(n, dtype=torch.uint8, device=dev)
+    h = torch.empty(n, dtype=torch.uint8).pin_memory()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ds = []
+    for _ in range(4):
+        e0.record(); h.copy_(d, non_blocking=True); e1.record(); e1.synchronize()
+        ds.append(e0.elapsed_time(e1))
+    rec["pinned_d2h_ms"] = ds[1:]
+    t = time.perf_counter()
+    with open(path + ".copy", "wb") as f:
+        f.write(memoryview(h.numpy()))
+    rec["plain_file_write_s"] = time.perf_counter() - t
+    os.remove(path + ".copy")
+    del d, h
+    if not a.no_host:
+        rowptr, ids, counts, _ = vec.to_numpy()
+        t = time.perf_counter()
+        loop_write(path + ".loop", names, rowptr, ids, counts)
+        rec["python_loop_write_s"] = time.perf_counter() - t
+        assert open(path + ".loop", "rb").read() == text
+        os.remove(path + ".loop")
 
 
 def host_parse(text, header):
@@ -73,21 +122,32 @@ def main():
     ap.add_argument("--out", default="eqfile_probe_out")
     ap.add_argument("--reads", type=int, default=400_000_000)
     ap.add_argument("--parse-only", action="store_true")
+    ap.add_argument("--write", action="store_true")
+    ap.add_argument("--write-only", action="store_true")
     ap.add_argument("--no-host", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     os.makedirs(a.out, exist_ok=True)
     rec = {}
     check_writer_bytes(dev, os.path.join(a.out, "small"))
-    names, ref_len, (rowptr, ids, counts) = cfg3_table(dev, R=a.reads)
+    names, ref_len, (rowptr, ids, counts), vec = cfg3_table(dev, R=a.reads)
     path = os.path.join(a.out, "eq_classes.txt")
+    if a.write_only:
+        for _ in range(3):
+            res = eqfile.write_file(path, names, vec)
+        print(json.dumps(dict(classes=len(counts), ids=len(ids), **res)))
+        return
     t = time.perf_counter()
     text = eqfile.format_text(names, rowptr, ids, counts)
-    with open(path, "wb") as f:
-        f.write(text)
+    rec["format_text_s"] = time.perf_counter() - t
+    write_leg(a, dev, path, names, vec, text, rec)
     header = eqfile.read_header(path)
-    rec.update(classes=len(counts), ids=len(ids), file_bytes=len(text), class_section_bytes=len(text) - header.data_offset,
-               write_s=time.perf_counter() - t)
+    rec.update(classes=len(counts), ids=len(ids), file_bytes=len(text), class_section_bytes=len(text) - header.data_offset)
+    if a.write:
+        print(json.dumps(rec))
+        with open(os.path.join(a.out, "eqfile_probe_write.json"), "w") as f:
+            json.dump(rec, f, indent=1)
+        return
 
     def fold(chunk=0):
         eq = sf.EquivalenceClassBuilder(device=dev); eq.start()

@@ -38,7 +38,7 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host) */
-    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text) */
+    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_gz_*) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -190,6 +190,41 @@ typedef struct {
 SFGPU_API int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* d_ids, const uint64_t* d_counts,
                                      uint64_t n_classes, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                      sfgpu_eqtext_write_result* out, sfgpu_stream stream);
+/* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
+ * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
+ * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
+ * (RFC 1951) blocks come from HIP kernels (csrc/gzwrite.hip; the arithmetic is csrc/gzfmt.h).  The contract of the file is "one
+ * gzip member whose payload is the bytes written, in order"; the compressed bytes differ from zlib's.
+ *   open   emits the 10-byte header through `sink`.  chunk_bytes: the largest piece handed to the sink (0 = 32 MiB; otherwise
+ *          16 .. 2^30, else SFGPU_ERR_INVALID); pieces end anywhere, also inside a DEFLATE block.
+ *   write  n_bytes at d_src (any alignment; n_bytes == 0 is legal and emits nothing) are cut into independent 64 KB blocks, each
+ *          coded as one dynamic-Huffman block over literals and distance-1 run matches of length 3 .. 258 (the token class of
+ *          zlib's Z_RLE) and padded to a byte by an empty stored block -- or as stored blocks where that is not shorter: a block
+ *          never exceeds its payload by more than 10 bytes.  CRC-32 is computed on the device per block and combined on the
+ *          host (x^(8 n) mod P), also from one write to the next.  The output is a function of the bytes and of the way
+ *          they are split into writes, nothing else.  Compressed pieces are staged through two pinned buffers; the next batch
+ *          (64 MiB of payload) is encoded, and the next piece copied, while the sink holds a piece.  h_bytes is valid only
+ *          during the sink call.  Synchronous; ordered behind whatever is queued on `stream`; d_src may be reused on return.
+ *          A nonzero return of the sink ends the call with SFGPU_ERR_IO and no further sink call; the stream is then broken
+ *          (further writes: SFGPU_ERR_STATE) and close only releases it.
+ *   close  emits the final (empty stored) block, CRC-32 and ISIZE (total bytes modulo 2^32), fills *res (may be NULL) and frees
+ *          the handle, whatever it returns.  open + close gives a valid empty gzip file.
+ * A handle belongs to one thread at a time and to the device that was current at open.  Device scratch: ~200 MB for writes of
+ * 64 MiB and more. */
+typedef struct sfgpu_gz sfgpu_gz;
+typedef struct {
+    uint64_t n_bytes_in;        /* payload bytes written */
+    uint64_t n_bytes_out;       /* bytes accepted by the sink, header and trailer included */
+    uint64_t n_blocks;          /* 64 KB blocks coded */
+    uint64_t n_stored_blocks;   /* of those, laid out as stored blocks */
+    uint64_t n_chunks;          /* sink calls made, header and trailer included */
+    double encode_ms;           /* device events: encode, scan and compaction kernels of all batches */
+    double d2h_ms;              /* device events around the staged copies */
+    double sink_ms;             /* host clock inside the sink */
+} sfgpu_gz_result;
+SFGPU_API int sfgpu_gz_open(sfgpu_gz** out, sfgpu_text_sink sink, void* user, uint64_t chunk_bytes);
+SFGPU_API int sfgpu_gz_write_device(sfgpu_gz* z, const void* d_src, uint64_t n_bytes, sfgpu_stream stream);
+SFGPU_API int sfgpu_gz_close(sfgpu_gz* z, sfgpu_gz_result* res);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

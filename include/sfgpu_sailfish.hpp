@@ -11,6 +11,7 @@
 //   sailfish::gpu::CollapsedGibbsSampler          include/CollapsedGibbsSampler.hpp:22-32, src/CollapsedGibbsSampler.cpp:187-291
 //   sailfish::gpu::loadEquivClasses               src/SailfishQuantify.cpp:1444-1494 (commented out there; --readEqClasses :1114)
 //   sailfish::gpu::writeEquivCounts               src/GZipWriter.cpp:51-92 (the class lines are formatted on the device)
+//   sailfish::gpu::writeBootstraps                src/GZipWriter.cpp:249-285 (bootstraps.gz compressed on the device)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -341,6 +342,33 @@ inline bool writeEquivCounts(const std::string& eqClassFile, ReadExperiment& rea
     }
     out.close();
     if (!out) throw std::runtime_error(eqClassFile + ": write failed");
+    return true;
+}
+
+// ---- GZipWriter::writeBootstrap<T>, src/GZipWriter.cpp:249-285 ----------------------------------------------------------------
+// The reference appends every sample to one boost gzip stream on the host.  Here the samples stay where sfgpu_bootstrap /
+// sfgpu_gibbs_sample left them (d_out: n_samples x M elements of elem_bytes, rows in draw order) and are compressed on the device
+// (sfgpu_gz_*: one gzip member, payload = the raw little-endian samples); the file is what gzip readers expect of bootstraps.gz.
+// Throws std::runtime_error naming the file when it cannot be opened or written.
+inline bool writeBootstraps(const std::string& bsFile, const void* d_samples, uint64_t n_samples, uint64_t M, uint64_t elem_bytes) {
+    std::ofstream out(bsFile, std::ios::binary);
+    if (!out) throw std::runtime_error(bsFile + ": cannot open for writing");
+    auto sink = [](const char* bytes, uint64_t n, void* user) -> int {
+        std::ofstream& o = *static_cast<std::ofstream*>(user);
+        o.write(bytes, static_cast<std::streamsize>(n));
+        return o ? 0 : 1;
+    };
+    sfgpu_gz* z = nullptr;
+    int rc = sfgpu_gz_open(&z, sink, &out, 0);
+    if (rc == SFGPU_OK) {
+        const int rc_w = sfgpu_gz_write_device(z, d_samples, n_samples * M * elem_bytes, nullptr);
+        rc = sfgpu_gz_close(z, nullptr);              // frees the handle whatever happened
+        if (rc_w != SFGPU_OK) rc = rc_w;
+    }
+    if (rc == SFGPU_ERR_IO) throw std::runtime_error(bsFile + ": write failed");
+    check(rc, "sfgpu_gz_write_device");
+    out.close();
+    if (!out) throw std::runtime_error(bsFile + ": write failed");
     return true;
 }
 

@@ -125,15 +125,25 @@ def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_op
     _writer.write_meta(out_dir, exp, sopt, start_time)                       # :1377
     t3 = clock()
     if sopt.numGibbsSamples > 0:                                             # :1379-1397
+        # the draws stay on the device (no per-sample callback) and are compressed there: writer.BootstrapWriter.write_device
         w = _writer.BootstrapWriter(out_dir, sopt)
-        ok = CollapsedGibbsSampler().sample(exp, sopt, w, sopt.numGibbsSamples, seed=seed)
-        w.close()
+        gs = CollapsedGibbsSampler()
+        ok = gs.sample(exp, sopt, None, sopt.numGibbsSamples, seed=seed)
+        try:
+            if ok:
+                w.write_device(gs.last_samples)
+        finally:
+            w.close()
         if not ok:
             return 1, exp
     elif sopt.numBootstraps > 0:                                             # :1398-1413
         w = _writer.BootstrapWriter(out_dir, sopt)
-        ok = opt.gatherBootstraps(exp, sopt, w, 0.01, 10000, seed=seed)
-        w.close()
+        ok = opt.gatherBootstraps(exp, sopt, None, 0.01, 10000, seed=seed)
+        try:
+            if ok:
+                w.write_device(opt.last_bootstraps)
+        finally:
+            w.close()
         if not ok:
             return 1, exp
     t4 = clock()

@@ -101,15 +101,21 @@ def write_meta(path, readExp: ReadExperiment, sopt: SailfishOpts, start_time: st
 class BootstrapWriter:
     """writeBootstrap<T> (GZipWriter.cpp:249-285): every sample is appended as raw binary (float64 for
     bootstrap replicates, int32 for Gibbs samples) to aux/bootstrap/bootstraps.gz.  An instance is the callback
-    of EMProblem.bootstrap / gibbs_sample (the C ABI calls it one sample at a time, in draw order)."""
+    of EMProblem.bootstrap / gibbs_sample (the C ABI calls it one sample at a time, in draw order); it compresses on the host
+    (zlib level 6, one sample at a time).  write_device takes the samplers' n x M device matrix instead and produces the same
+    payload through the device encoder (gzfile.GzDeviceWriter).  One instance uses one of the two ways."""
+    ROWS_BYTES = 256 << 20          # write_device hands the matrix over in row slices of at most this many bytes
 
     def __init__(self, path, sopt: SailfishOpts, logger=None):
         self._dir = os.path.join(path, sopt.auxDir, "bootstrap")
         self._f = None
+        self._gz = None
         self._log = logger
         self.written = 0
 
     def __call__(self, abund):
+        if self._gz is not None:
+            raise RuntimeError("BootstrapWriter: samples were already written with write_device; one file takes one of the two ways")
         if self._f is None:
             os.makedirs(self._dir, exist_ok=True)
             self._f = gzip.open(os.path.join(self._dir, "bootstraps.gz"), "wb", compresslevel=6)
@@ -119,6 +125,28 @@ class BootstrapWriter:
             self._log(0, f"wrote {self.written} bootstraps")
         return True
 
+    def write_device(self, samples):
+        """`samples`: 2-D contiguous device tensor, one sample per row in draw order (float64 replicates, int32 Gibbs draws)."""
+        from . import gzfile
+        if self._f is not None:
+            raise RuntimeError("BootstrapWriter: samples were already written one by one; one file takes one of the two ways")
+        if not (isinstance(samples, torch.Tensor) and samples.is_cuda and samples.dim() == 2 and samples.is_contiguous()):
+            raise TypeError("write_device expects a contiguous 2-D device tensor, one sample per row")
+        if self._gz is None:
+            os.makedirs(self._dir, exist_ok=True)
+            self._gz = gzfile.GzDeviceWriter(os.path.join(self._dir, "bootstraps.gz"))
+        n, row_bytes = samples.shape[0], samples.shape[1] * samples.element_size()
+        step = max(1, self.ROWS_BYTES // max(row_bytes, 1))
+        for r0 in range(0, n, step):
+            self._gz.write(samples[r0:r0 + step])
+        self.written += n
+        if self._log:
+            self._log(0, f"wrote {self.written} bootstraps")
+        return True
+
     def close(self):
         if self._f is not None:
             self._f.close(); self._f = None
+        if self._gz is not None:
+            gz, self._gz = self._gz, None
+            self.last_result = gz.close()

@@ -38,7 +38,7 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host) */
-    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_gz_*) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -190,6 +190,40 @@ typedef struct {
 SFGPU_API int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* d_ids, const uint64_t* d_counts,
                                      uint64_t n_classes, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                      sfgpu_eqtext_write_result* out, sfgpu_stream stream);
+/* writeAbundances (src/GZipWriter.cpp:234-245): the ROW SECTION of a quant.sf file formatted on the device from the columns where
+ * they lie.  For each row, in the order given,
+ *     name \t Length \t %g(eff) \t %g(tpm) \t %g(num_reads) \n
+ * Length in decimal; the three doubles as printf("%g") prints them (the reference's cppformat "{}"): six significant digits,
+ * correctly rounded with ties to even on the exact binary value, fixed notation for decimal exponents -4 .. 5 and d.ddddde+XX
+ * otherwise, trailing zeros stripped; "inf" / "-inf", "nan" for a NaN of either sign, "-0" for -0.0.  The arithmetic is exact
+ * for every double (csrc/gfmt.h): 128-bit integers for 2^-56 <= |x| < 2^127, which covers what a quant.sf holds, and a slow
+ * multi-word path outside (n_slow counts its cells).  The header line of the file is the host's business.
+ * Row r's name is the bytes d_names[d_name_off[r] .. d_name_off[r + 1]): copied verbatim, never inspected, of any length including
+ * 0 (below 2^32 - 60, else SFGPU_ERR_RANGE).  d_name_off has n_rows + 1 entries, must start at 0 and never decrease (else
+ * SFGPU_ERR_INVALID); n_rows < 2^32 - 1 (SFGPU_ERR_RANGE).  All pointers are device pointers.  The text may exceed 4 GB.
+ * The text is handed to `sink` in consecutive chunks, in order.  Each chunk is a whole number of rows (it ends in '\n'), is at
+ * most chunk_bytes long (0 = 32 MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID) and greedy: it holds as many whole rows as
+ * fit, so n_chunks is a function of the table and chunk_bytes alone.  h_bytes points into a pinned staging buffer of the
+ * library and is valid only during the call.  Chunk c + 1 is formatted and copied while the sink consumes chunk c (two staging
+ * buffers).  All row lengths are known before a byte is formatted: a row longer than chunk_bytes fails the call with
+ * SFGPU_ERR_RANGE before the first sink call (`out` holds the sizes).  A nonzero return of the sink ends the call with
+ * SFGPU_ERR_IO and no further sink call.  sink == NULL sizes the text only: `out` is filled, nothing is formatted or copied.
+ * n_rows == 0 is SFGPU_OK with zero bytes and no sink call.
+ * Synchronous; ordered behind whatever is queued on `stream`; independent calls may run from several threads.  Scratch on the
+ * device: 24 bytes per row and two chunk buffers. */
+typedef struct {
+    uint64_t n_bytes;         /* bytes of the row section */
+    uint64_t n_rows;
+    uint64_t n_chunks;        /* sink calls made */
+    uint64_t max_row_bytes;   /* longest row, with its '\n' */
+    uint64_t n_slow;          /* cells that left the 128-bit window */
+    double format_ms;         /* device events: decode, sizing, scan, chunk plan, format kernels of all chunks */
+    double d2h_ms;            /* device events around the staged copies */
+    double sink_ms;           /* host clock inside the sink */
+} sfgpu_quant_write_result;
+SFGPU_API int sfgpu_quant_write_text(const char* d_names, const uint64_t* d_name_off, const uint32_t* d_length, const double* d_eff,
+                                     const double* d_tpm, const double* d_num_reads, uint64_t n_rows, uint64_t chunk_bytes,
+                                     sfgpu_text_sink sink, void* user, sfgpu_quant_write_result* out, sfgpu_stream stream);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

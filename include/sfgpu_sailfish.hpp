@@ -12,6 +12,7 @@
 //   sailfish::gpu::loadEquivClasses               src/SailfishQuantify.cpp:1444-1494 (commented out there; --readEqClasses :1114)
 //   sailfish::gpu::writeEquivCounts               src/GZipWriter.cpp:51-92 (the class lines are formatted on the device)
 //   sailfish::gpu::writeBootstraps                src/GZipWriter.cpp:249-285 (bootstraps.gz compressed on the device)
+//   sailfish::gpu::writeAbundances                src/GZipWriter.cpp:194-248 (the rows of quant.sf are formatted on the device)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -342,6 +343,50 @@ inline bool writeEquivCounts(const std::string& eqClassFile, ReadExperiment& rea
     }
     out.close();
     if (!out) throw std::runtime_error(eqClassFile + ": write failed");
+    return true;
+}
+
+// ---- GZipWriter::writeAbundances, src/GZipWriter.cpp:194-248 ------------------------------------------------------------------
+// quant.sf: the header line from the host, then one row per transcript of readExp -- Name, Length, EffectiveLength (the
+// reference length with sopt.noEffectiveLengthCorrection), TPM (sfgpu_tpm over estCount()) and NumReads (estCount()) -- formatted
+// on the device (sfgpu_quant_write_text: format and limits in sfgpu.h; the doubles print as the reference's "{}", printf %g) and
+// streamed into the file chunk by chunk.  Throws std::runtime_error naming the file when it cannot be opened or written.
+inline bool writeAbundances(const std::string& quantFile, ReadExperiment& readExp, const SailfishOpts& sopt) {
+    std::ofstream out(quantFile, std::ios::binary);
+    if (!out) throw std::runtime_error(quantFile + ": cannot open for writing");
+    out << "Name\tLength\tEffectiveLength\tTPM\tNumReads\n";
+    auto& txps = readExp.transcripts();
+    const uint64_t M = txps.size();
+    if (M) {
+        std::vector<char> names;
+        std::vector<uint64_t> off(M + 1, 0);
+        std::vector<uint32_t> len(M);
+        std::vector<double> eff(M), cnt(M);
+        for (uint64_t i = 0; i < M; ++i) {
+            names.insert(names.end(), txps[i].RefName.begin(), txps[i].RefName.end());
+            off[i + 1] = names.size();
+            len[i] = txps[i].RefLength;
+            eff[i] = sopt.noEffectiveLengthCorrection ? static_cast<double>(txps[i].RefLength) : txps[i].EffectiveLength;
+            cnt[i] = txps[i].estCount();
+        }
+        DeviceBuf<char> d_names(names);
+        DeviceBuf<uint64_t> d_off(off);
+        DeviceBuf<uint32_t> d_len(len);
+        DeviceBuf<double> d_eff(eff), d_cnt(cnt), d_tpm(M);
+        check(sfgpu_tpm(d_cnt.get(), d_eff.get(), M, static_cast<double>(readExp.numMappedFragments()), d_tpm.get(), nullptr), "sfgpu_tpm");
+        auto sink = [](const char* bytes, uint64_t n, void* user) -> int {
+            std::ofstream& o = *static_cast<std::ofstream*>(user);
+            o.write(bytes, static_cast<std::streamsize>(n));
+            return o ? 0 : 1;
+        };
+        sfgpu_quant_write_result r;
+        const int rc = sfgpu_quant_write_text(d_names.get(), d_off.get(), d_len.get(), d_eff.get(), d_tpm.get(), d_cnt.get(), M, 0, sink,
+                                              &out, &r, nullptr);
+        if (rc == SFGPU_ERR_IO) throw std::runtime_error(quantFile + ": write failed");
+        check(rc, "sfgpu_quant_write_text");
+    }
+    out.close();
+    if (!out) throw std::runtime_error(quantFile + ": write failed");
     return true;
 }
 

@@ -7,31 +7,31 @@
 //   sizing  k_tok_size: one lane per token finds its class (the class keys of a block's 256 tokens are staged in LDS) and
 //           writes digits + 1; an exclusive scan (primitives.h) gives every token its byte start, 64-bit over the table.
 //           k_tok_place: the start of every line, and for every 4 KB tile of the OUTPUT the token that holds its first byte.
-//           k_line_max: the longest line.  k_chunk_plan: the greedy chunk ends, by binary search of the line starts.
+//           textchunks.h: the longest line, and the greedy chunk ends by binary search of the line starts.
 //   format  k_format: one block per 4 KB tile of the output.  The tokens that overlap the tile are formatted into an LDS image
 //           of the tile (decfmt.h; a token is clipped to the tile), then every lane stores one aligned 16-byte group: global
 //           memory sees only full-width coalesced stores.  Tiles are aligned in the TABLE's byte offsets, so the per-tile
 //           token index is made once whatever the chunk size; a chunk's buffer starts at the tile that holds its first byte.
-// The formatted chunk c + 1 is produced and copied to its pinned buffer while the sink consumes chunk c.
+// The longest line, the chunk plan and the loop that hands the chunks to the sink (chunk c + 1 is produced and copied to its pinned
+// buffer while the sink consumes chunk c) are textchunks.h, shared with quant_write.hip.
 #include "common.h"
 #include "decfmt.h"
 #include "primitives.h"
+#include "textchunks.h"
 
-#include <chrono>
 #include <cstring>
 
 namespace sfgpu {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kTileBytes = 4096;                     // kBlock lanes x one 16-byte store
-constexpr int kTileShift = 12;
-constexpr uint64_t kDefaultChunk = 32ull << 20;           // the reader's limits (eqtext.hip)
-constexpr uint64_t kMaxChunk = 1ull << 30;
+using textchunks::kBlock;
+using textchunks::kTileBytes;
+using textchunks::kTileShift;
+using textchunks::kDefaultChunk;
+using textchunks::kMaxChunk;
+using textchunks::grid_of;
 constexpr uint64_t kMaxClasses = 0xffffffffull;           // a token's class index is kept in 32 bits
 constexpr int kMaxTokBytes = 21;                          // 20 digits and the separator
-
-inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 __device__ inline uint64_t class_key(const uint32_t* __restrict__ rowptr, uint64_t c) { return (uint64_t)rowptr[c] + 2 * c; }
 
@@ -98,42 +98,6 @@ __global__ void k_tok_place(const uint32_t* __restrict__ rowptr, uint64_t n_clas
     }
 }
 
-// a fixed grid strides over the classes: one atomic per wavefront of a few thousand, not of every 64 classes (they serialise on the address)
-constexpr unsigned kLineMaxBlocks = 1024;
-__global__ void k_line_max(const uint64_t* __restrict__ line_start, uint64_t n_classes, unsigned long long* __restrict__ misc) {
-    unsigned long long len = 0;
-    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_classes; c += (uint64_t)gridDim.x * blockDim.x) {
-        const unsigned long long l = line_start[c + 1] - line_start[c];
-        len = l > len ? l : len;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(len, o);
-        len = other > len ? other : len;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) atomicMax(&misc[1], len);
-}
-
-// greedy chunks, one thread: chunk i holds classes [plan[2 i - 2], plan[2 i]) and ends at byte plan[2 i + 1].  Every line fits
-// a chunk (checked by the host before the launch), so every chunk takes at least one line; misc[2] = number of chunks.
-__global__ void k_chunk_plan(const uint64_t* __restrict__ line_start, uint64_t n_classes, uint64_t chunk_bytes, uint64_t cap,
-                             uint64_t* __restrict__ plan, unsigned long long* __restrict__ misc) {
-    if (blockIdx.x || threadIdx.x) return;
-    uint64_t c = 0, n = 0;
-    while (c < n_classes && n < cap) {
-        const uint64_t limit = line_start[c] + chunk_bytes;
-        uint64_t lo = c + 1, hi = n_classes + 1;          // line_start[lo] <= limit < line_start[hi] (line_start[n_classes + 1] = infinity)
-        while (hi - lo > 1) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (line_start[mid] <= limit) lo = mid; else hi = mid;
-        }
-        plan[2 * n] = lo; plan[2 * n + 1] = line_start[lo];
-        ++n;
-        c = lo;
-    }
-    misc[2] = n;
-}
-
 // one block per tile of the output; `out` is the chunk buffer, whose byte 0 is table byte out_base (a multiple of kTileBytes)
 __global__ void __launch_bounds__(kBlock)
 k_format(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, const uint64_t* __restrict__ counts,
@@ -167,15 +131,10 @@ k_format(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, 
     if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 struct WriteScratch {
     DevBuf<uint32_t> tok_len, tok_class;
-    DevBuf<uint64_t> tok_start, line_start, tile_first, plan;
-    DevBuf<uint4> out[2];
-    DevBuf<unsigned long long> misc;        // [0] rowptr not monotone, [1] longest line, [2] chunks planned
+    DevBuf<uint64_t> tok_start, line_start, tile_first;
+    DevBuf<unsigned long long> misc;        // [0] rowptr not monotone, [1] longest line
 };
 
 }  // namespace
@@ -196,21 +155,17 @@ extern "C" int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* 
     SF_REQUIRE(n_classes < kMaxClasses, SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: n_classes must be below 2^32 - 1");
 
     WriteScratch S;
-    hipStream_t st = nullptr, cs = nullptr;
-    char* pinned[2] = {nullptr, nullptr};
+    hipStream_t st = nullptr;
     hipEvent_t ev_in = nullptr, ev_s[2] = {nullptr, nullptr};
-    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
-    unsigned long long* h_misc = nullptr;     // [0 .. 2] misc, [3] total bytes, [4] rowptr[0] and rowptr[n_classes]
-    uint64_t* h_plan = nullptr;
+    unsigned long long* h_misc = nullptr;     // [0 .. 1] misc, [3] total bytes, [4] rowptr[0] and rowptr[n_classes]
     int rc = SFGPU_OK;
 
-    // every exit below goes through `done`: nothing may be released while a copy still writes the pinned buffers
+    // every exit below goes through `done`
 #define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
 #define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
 #define T_FAIL(code, msg) do { set_error("%s", msg); rc = (code); goto done; } while (0)
     {
         T_HIP(stream_acquire(&st));
-        T_HIP(stream_acquire(&cs));
         T_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
         for (auto& e : ev_s) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
         T_HIP(pinned_malloc(&h_misc, 8 * sizeof(unsigned long long)));
@@ -247,8 +202,7 @@ extern "C" int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* 
         hipLaunchKernelGGL(k_tok_place, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, n_classes, n_tok, S.tok_start.p,
                            S.tok_class.p, S.line_start.p, S.tile_first.p);
         T_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_line_max, dim3(grid_of(n_classes) < kLineMaxBlocks ? grid_of(n_classes) : kLineMaxBlocks), dim3(kBlock), 0, st, S.line_start.p, n_classes, S.misc.p);
-        T_HIP(hipGetLastError());
+        T_TRY(textchunks::line_max(S.line_start.p, n_classes, S.misc.p + 1, st));
         T_HIP(hipEventRecord(ev_s[1], st));
         T_HIP(hipMemcpyAsync(&h_misc[1], S.misc.p + 1, 8, hipMemcpyDeviceToHost, st));
         T_HIP(hipMemcpyAsync(&h_misc[3], S.tok_start.p + n_tok, 8, hipMemcpyDeviceToHost, st));
@@ -262,83 +216,21 @@ extern "C" int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* 
         if (!sink) goto done;
         if (out->max_line_bytes > chunk_bytes) T_FAIL(SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: a line is longer than chunk_bytes");
 
-        // ---- the chunk plan: two consecutive greedy chunks hold more than chunk_bytes together
-        const uint64_t plan_cap = 2 * (total / chunk_bytes) + 2;
-        T_TRY(S.plan.reserve(2 * plan_cap, st, false));
-        T_HIP(pinned_malloc(&h_plan, 2 * plan_cap * sizeof(uint64_t)));
-        T_HIP(hipEventRecord(ev_s[0], st));
-        hipLaunchKernelGGL(k_chunk_plan, dim3(1), dim3(kWave), 0, st, S.line_start.p, n_classes, chunk_bytes, plan_cap, S.plan.p, S.misc.p);
-        T_HIP(hipGetLastError());
-        T_HIP(hipEventRecord(ev_s[1], st));
-        T_HIP(hipMemcpyAsync(&h_misc[2], S.misc.p + 2, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        const uint64_t n_chunks = h_misc[2];
-        T_HIP(hipMemcpyAsync(h_plan, S.plan.p, 2 * n_chunks * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, ev_s[0], ev_s[1]) == hipSuccess) out->format_ms += (double)a;
-        }
-        if (n_chunks == 0 || h_plan[2 * n_chunks - 2] != n_classes || h_plan[2 * n_chunks - 1] != total)
-            T_FAIL(SFGPU_ERR_HIP, "sfgpu_eqvec_write_text: the chunk plan does not cover the table");
-
-        // ---- format + copy + sink, two buffers: chunk i + 1 is formatted and copied while the sink holds chunk i
-        const uint64_t stage_bytes = total < chunk_bytes ? total : chunk_bytes;
-        const uint64_t out_groups = (stage_bytes + 2 * kTileBytes) / 16 + 1;
-        for (int b = 0; b < 2 && (uint64_t)b < n_chunks; ++b) {
-            T_HIP(pinned_malloc(&pinned[b], stage_bytes));
-            T_TRY(S.out[b].reserve(out_groups, st, false));
-            T_HIP(hipEventCreateWithFlags(&ev_f0[b], hipEventDefault));
-            T_HIP(hipEventCreateWithFlags(&ev_f1[b], hipEventDefault));
-            T_HIP(hipEventCreateWithFlags(&ev_c0[b], hipEventDefault));
-            T_HIP(hipEventCreateWithFlags(&ev_c1[b], hipEventDefault));
-        }
-        auto chunk_begin = [&](uint64_t i) -> uint64_t { return i ? h_plan[2 * i - 1] : 0; };
-        // format on st into S.out[slot], then the copy on cs into pinned[slot]; the slot's previous chunk has left the sink, and
-        // its copy (which read S.out[slot]) was waited for before that
-        auto enqueue = [&](uint64_t i) -> int {
-            const int slot = (int)(i & 1);
-            const uint64_t b0 = chunk_begin(i), b1 = h_plan[2 * i + 1];
-            const uint64_t first_tile = b0 >> kTileShift, last_tile = (b1 - 1) >> kTileShift, out_base = first_tile << kTileShift;
-            SF_HIP(hipEventRecord(ev_f0[slot], st));
-            hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, st, d_rowptr, d_ids, d_counts,
-                               S.tok_start.p, S.tok_class.p, S.tile_first.p, n_tok, total, first_tile, out_base, S.out[slot].p);
+        // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this table's tiles
+        textchunks::Stats ts;
+        rc = textchunks::deliver("sfgpu_eqvec_write_text", S.line_start.p, n_classes, total, chunk_bytes, sink, user, st, &ts,
+                                 [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
+            hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_rowptr, d_ids, d_counts,
+                               S.tok_start.p, S.tok_class.p, S.tile_first.p, n_tok, total, first_tile, out_base, buf);
             SF_HIP(hipGetLastError());
-            SF_HIP(hipEventRecord(ev_f1[slot], st));
-            SF_HIP(hipStreamWaitEvent(cs, ev_f1[slot], 0));
-            SF_HIP(hipEventRecord(ev_c0[slot], cs));
-            SF_HIP(hipMemcpyAsync(pinned[slot], reinterpret_cast<const char*>(S.out[slot].p) + (b0 - out_base), b1 - b0, hipMemcpyDeviceToHost, cs));
-            SF_HIP(hipEventRecord(ev_c1[slot], cs));
             return SFGPU_OK;
-        };
-        T_TRY(enqueue(0));
-        for (uint64_t i = 0; i < n_chunks; ++i) {
-            const int slot = (int)(i & 1);
-            if (i + 1 < n_chunks) T_TRY(enqueue(i + 1));
-            T_HIP(hipEventSynchronize(ev_c1[slot]));
-            {
-                float a = 0.f, b = 0.f;
-                if (hipEventElapsedTime(&a, ev_f0[slot], ev_f1[slot]) == hipSuccess) out->format_ms += (double)a;
-                if (hipEventElapsedTime(&b, ev_c0[slot], ev_c1[slot]) == hipSuccess) out->d2h_ms += (double)b;
-            }
-            const auto t0 = std::chrono::steady_clock::now();
-            const int stop = sink(pinned[slot], h_plan[2 * i + 1] - chunk_begin(i), user);
-            out->sink_ms += ms_since(t0);
-            out->n_chunks++;
-            if (stop) T_FAIL(SFGPU_ERR_IO, "sfgpu_eqvec_write_text: the sink refused a chunk");
-        }
+        });
+        out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
     }
 done:
-    if (cs) (void)hipStreamSynchronize(cs);
     if (st) (void)hipStreamSynchronize(st);
-    for (int b = 0; b < 2; ++b) {
-        if (pinned[b]) pinned_free(pinned[b]);
-        for (hipEvent_t e : {ev_f0[b], ev_f1[b], ev_c0[b], ev_c1[b], ev_s[b]}) if (e) (void)hipEventDestroy(e);
-    }
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (h_plan) pinned_free(h_plan);
+    for (hipEvent_t e : {ev_in, ev_s[0], ev_s[1]}) if (e) (void)hipEventDestroy(e);
     if (h_misc) pinned_free(h_misc);
-    if (cs) stream_release(cs);
     if (st) stream_release(st);
     return rc;
 #undef T_HIP

@@ -50,9 +50,20 @@ class Transcripts:
         self.estCount = torch.zeros(M, dtype=torch.float64, device=self.device)
         self.mass = torch.zeros(M, dtype=torch.float64, device=self.device)
         self.active = None
+        self._name_blob = None
 
     def __len__(self):
         return len(self.RefName)
+
+    def name_blob(self):
+        """(bytes, offsets) of the names on the device, as quantfile.write_rows takes them: the UTF-8 names back to back in
+        a uint8 tensor and the M + 1 byte offsets in an int64 tensor.  Built on first use; names do not change."""
+        if self._name_blob is None:
+            from . import quantfile
+            blob, off = quantfile.names_blob(self.RefName)
+            self._name_blob = (torch.from_numpy(np.frombuffer(blob, np.uint8).copy()).to(self.device),
+                               torch.from_numpy(off.view(np.int64).copy()).to(self.device))
+        return self._name_blob
 
     def ref_length_f64(self):
         return (self.RefLength.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)

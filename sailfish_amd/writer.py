@@ -28,18 +28,14 @@ def fmt_g(x):
 
 
 def write_abundances(path, readExp: ReadExperiment, sopt: SailfishOpts):
-    """writeAbundances (GZipWriter.cpp:194-248): Name, Length, EffectiveLength, TPM, NumReads."""
+    """writeAbundances (GZipWriter.cpp:194-248): Name, Length, EffectiveLength, TPM, NumReads.  The header line is written
+    here; the rows are formatted on the device from the columns where they lie (quantfile.write_file, sfgpu_quant_write_text).
+    The bytes are quantfile.format_rows', the per-row loop over fmt_g this function used to run."""
+    from . import quantfile
     txps = readExp.transcripts()
-    t, length = tpm(readExp, sopt)
-    t = t.cpu().numpy(); length = length.cpu().numpy()
-    cnt = txps.estCount.cpu().numpy()
-    ref = txps.RefLength.cpu().numpy().view(np.uint32)
+    t, length = tpm(readExp, sopt)          # (without the length correction `length` is the reference lengths as doubles)
     os.makedirs(path, exist_ok=True)
-    with open(os.path.join(path, "quant.sf"), "w") as f:
-        f.write("Name\tLength\tEffectiveLength\tTPM\tNumReads\n")
-        for i, name in enumerate(txps.RefName):
-            eff = fmt_g(float(ref[i])) if sopt.noEffectiveLengthCorrection else fmt_g(length[i])
-            f.write(f"{name}\t{int(ref[i])}\t{eff}\t{fmt_g(t[i])}\t{fmt_g(cnt[i])}\n")
+    quantfile.write_file(os.path.join(path, "quant.sf"), txps.name_blob(), txps.RefLength, length, t, txps.estCount)
     return True
 
 

@@ -38,7 +38,7 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host) */
-    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -224,6 +224,51 @@ typedef struct {
 SFGPU_API int sfgpu_quant_write_text(const char* d_names, const uint64_t* d_name_off, const uint32_t* d_length, const double* d_eff,
                                      const double* d_tpm, const double* d_num_reads, uint64_t n_rows, uint64_t chunk_bytes,
                                      sfgpu_text_sink sink, void* user, sfgpu_quant_write_result* out, sfgpu_stream stream);
+/* aggregateEstimatesToGeneLevel (src/SailfishUtils.cpp:929-1037), the `--geneMap` step: the rows of a quant.sf folded into genes
+ * on the device, from the columns where they lie (no file is read back).  Row r belongs to gene d_gene_of_row[r], an arbitrary
+ * id below n_gene_ids (else SFGPU_ERR_INVALID: found on the device and reported before any output is written); ids need not be
+ * dense, and a gene's rows may lie anywhere.  Output line g is the g-th gene in order of the genes' FIRST rows; d_gene_id_out[g]
+ * is its id and the four double columns hold
+ *     TPM, NumReads   the running sums of the gene's rows in row order, from 0.0
+ *     Length, EffectiveLength   sum of length_i * frac_i and eff_i * frac_i with frac_i = tpm_i / totalTPM, where totalTPM
+ *                     accumulates the RUNNING TPM sum after each row (the reference's quirk, kept) -- or frac_i = 1.0 / n when
+ *                     totalTPM > denorm_min does not hold (unexpressed genes, a NaN total)
+ * every gene one serial chain of IEEE additions in row order, one operation per operation of the reference and none fused
+ * (csrc/genefold.h), so the doubles are the host loop's bit for bit.  as_printed = 1 folds what the reference reads from the
+ * file: each of d_eff, d_tpm, d_num_reads first becomes the double strtod gives for its six-digit %g token (csrc/gfmt.h:
+ * gfmt_decode -> gfmt_value, exact for every double; n_slow counts the cells that left the fast windows, none for the values a
+ * quant.sf holds); as_printed = 0 folds the doubles as they are.  d_length is the integer Length column.
+ * The five outputs need room for min(n_rows, n_gene_ids) entries; *out->n_genes of them are written.  n_rows < 2^32 - 1
+ * (SFGPU_ERR_RANGE); n_rows == 0 is SFGPU_OK with zero genes.  All pointers are device pointers; the inputs are not modified.
+ * Parallelism is across genes (one lane folds one gene), so a single gene that holds every row is folded by one lane: 0.20 s for
+ * one gene of 1 000 000 rows on an MI355X (profiles/genes_probe.json); max_rows_per_gene reports the longest chain.
+ * Synchronous; ordered behind whatever is queued on `stream`; independent calls may run from several threads.  Scratch on the
+ * device: about 120 bytes per row. */
+typedef struct {
+    uint64_t n_rows;
+    uint64_t n_genes;            /* output lines */
+    uint64_t n_slow;             /* cells rounded through the multi-word paths (as_printed = 1) */
+    uint64_t max_rows_per_gene;  /* the longest serial chain */
+    double aggregate_ms;         /* device events from before the id check to after the fold: all kernels of the call and the two
+                                    host round trips between them (the id check, the number of genes) */
+} sfgpu_genes_result;
+SFGPU_API int sfgpu_genes_aggregate(const uint32_t* d_gene_of_row, const uint32_t* d_length, const double* d_eff, const double* d_tpm,
+                                    const double* d_num_reads, uint64_t n_rows, uint64_t n_gene_ids, int as_printed,
+                                    uint32_t* d_gene_id_out, double* d_length_out, double* d_eff_out, double* d_tpm_out,
+                                    double* d_num_reads_out, sfgpu_genes_result* out, sfgpu_stream stream);
+/* The ROW SECTION of a quant.genes.sf file (src/SailfishUtils.cpp:1018-1031) formatted on the device.  For each row, in order,
+ *     name \t %g(length) \t %g(eff) \t %g(tpm) \t %g(num_reads) \n
+ * all four numeric columns doubles (the outputs of sfgpu_genes_aggregate).  Row g's name is entry d_gene_id[g] of a name table of
+ * n_gene_ids names: the bytes d_names[d_name_off[i] .. d_name_off[i + 1]), i = d_gene_id[g]; an index that is not below
+ * n_gene_ids is SFGPU_ERR_INVALID.  d_name_off has n_gene_ids + 1 entries.  The comment and header lines of the file are the
+ * host's business.  In every other respect the contract is sfgpu_quant_write_text's (the same kernels, csrc/rowtext.h): names
+ * of any length copied verbatim, whole-row greedy chunks and the chunk_bytes rules, sink == NULL sizes only, a sink refusal is
+ * SFGPU_ERR_IO, a row longer than chunk_bytes is SFGPU_ERR_RANGE before the first sink call, n_rows == 0 is SFGPU_OK with no
+ * sink call; the result carries n_slow, max_row_bytes and the three times.  Scratch: 28 bytes per row and two chunk buffers. */
+SFGPU_API int sfgpu_genes_write_text(const char* d_names, const uint64_t* d_name_off, uint64_t n_gene_ids, const uint32_t* d_gene_id,
+                                     const double* d_length, const double* d_eff, const double* d_tpm, const double* d_num_reads,
+                                     uint64_t n_rows, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                     sfgpu_quant_write_result* out, sfgpu_stream stream);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

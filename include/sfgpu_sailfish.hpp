@@ -13,6 +13,7 @@
 //   sailfish::gpu::writeEquivCounts               src/GZipWriter.cpp:51-92 (the class lines are formatted on the device)
 //   sailfish::gpu::writeBootstraps                src/GZipWriter.cpp:249-285 (bootstraps.gz compressed on the device)
 //   sailfish::gpu::writeAbundances                src/GZipWriter.cpp:194-248 (the rows of quant.sf are formatted on the device)
+//   sailfish::gpu::aggregateEstimatesToGeneLevel  src/SailfishUtils.cpp:929-1037 (genes folded and formatted on the device)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -33,6 +34,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -346,6 +348,46 @@ inline bool writeEquivCounts(const std::string& eqClassFile, ReadExperiment& rea
     return true;
 }
 
+// ---- what writeAbundances and aggregateEstimatesToGeneLevel share ------------------------------------------------------------
+namespace detail {
+// the columns of quant.sf on the device, as writeAbundances writes them and aggregateEstimatesToGeneLevel folds them
+struct AbundanceColumns {
+    uint64_t M = 0;
+    DeviceBuf<char> names;
+    DeviceBuf<uint64_t> off;
+    DeviceBuf<uint32_t> len;
+    DeviceBuf<double> eff, cnt, tpm;
+    AbundanceColumns(ReadExperiment& readExp, const SailfishOpts& sopt) {
+        auto& txps = readExp.transcripts();
+        M = txps.size();
+        if (!M) return;
+        std::vector<char> h_names;
+        std::vector<uint64_t> h_off(M + 1, 0);
+        std::vector<uint32_t> h_len(M);
+        std::vector<double> h_eff(M), h_cnt(M);
+        for (uint64_t i = 0; i < M; ++i) {
+            h_names.insert(h_names.end(), txps[i].RefName.begin(), txps[i].RefName.end());
+            h_off[i + 1] = h_names.size();
+            h_len[i] = txps[i].RefLength;
+            h_eff[i] = sopt.noEffectiveLengthCorrection ? static_cast<double>(txps[i].RefLength) : txps[i].EffectiveLength;
+            h_cnt[i] = txps[i].estCount();
+        }
+        names.resize(h_names.size()); names.upload(h_names);
+        off.resize(M + 1); off.upload(h_off);
+        len.resize(M); len.upload(h_len);
+        eff.resize(M); eff.upload(h_eff);
+        cnt.resize(M); cnt.upload(h_cnt);
+        tpm.resize(M);
+        check(sfgpu_tpm(cnt.get(), eff.get(), M, static_cast<double>(readExp.numMappedFragments()), tpm.get(), nullptr), "sfgpu_tpm");
+    }
+};
+inline int ofstream_sink(const char* bytes, uint64_t n, void* user) {
+    std::ofstream& o = *static_cast<std::ofstream*>(user);
+    o.write(bytes, static_cast<std::streamsize>(n));
+    return o ? 0 : 1;
+}
+}  // namespace detail
+
 // ---- GZipWriter::writeAbundances, src/GZipWriter.cpp:194-248 ------------------------------------------------------------------
 // quant.sf: the header line from the host, then one row per transcript of readExp -- Name, Length, EffectiveLength (the
 // reference length with sopt.noEffectiveLengthCorrection), TPM (sfgpu_tpm over estCount()) and NumReads (estCount()) -- formatted
@@ -355,38 +397,65 @@ inline bool writeAbundances(const std::string& quantFile, ReadExperiment& readEx
     std::ofstream out(quantFile, std::ios::binary);
     if (!out) throw std::runtime_error(quantFile + ": cannot open for writing");
     out << "Name\tLength\tEffectiveLength\tTPM\tNumReads\n";
-    auto& txps = readExp.transcripts();
-    const uint64_t M = txps.size();
-    if (M) {
-        std::vector<char> names;
-        std::vector<uint64_t> off(M + 1, 0);
-        std::vector<uint32_t> len(M);
-        std::vector<double> eff(M), cnt(M);
-        for (uint64_t i = 0; i < M; ++i) {
-            names.insert(names.end(), txps[i].RefName.begin(), txps[i].RefName.end());
-            off[i + 1] = names.size();
-            len[i] = txps[i].RefLength;
-            eff[i] = sopt.noEffectiveLengthCorrection ? static_cast<double>(txps[i].RefLength) : txps[i].EffectiveLength;
-            cnt[i] = txps[i].estCount();
-        }
-        DeviceBuf<char> d_names(names);
-        DeviceBuf<uint64_t> d_off(off);
-        DeviceBuf<uint32_t> d_len(len);
-        DeviceBuf<double> d_eff(eff), d_cnt(cnt), d_tpm(M);
-        check(sfgpu_tpm(d_cnt.get(), d_eff.get(), M, static_cast<double>(readExp.numMappedFragments()), d_tpm.get(), nullptr), "sfgpu_tpm");
-        auto sink = [](const char* bytes, uint64_t n, void* user) -> int {
-            std::ofstream& o = *static_cast<std::ofstream*>(user);
-            o.write(bytes, static_cast<std::streamsize>(n));
-            return o ? 0 : 1;
-        };
+    detail::AbundanceColumns c(readExp, sopt);
+    if (c.M) {
         sfgpu_quant_write_result r;
-        const int rc = sfgpu_quant_write_text(d_names.get(), d_off.get(), d_len.get(), d_eff.get(), d_tpm.get(), d_cnt.get(), M, 0, sink,
-                                              &out, &r, nullptr);
+        const int rc = sfgpu_quant_write_text(c.names.get(), c.off.get(), c.len.get(), c.eff.get(), c.tpm.get(), c.cnt.get(), c.M, 0,
+                                              detail::ofstream_sink, &out, &r, nullptr);
         if (rc == SFGPU_ERR_IO) throw std::runtime_error(quantFile + ": write failed");
         check(rc, "sfgpu_quant_write_text");
     }
     out.close();
     if (!out) throw std::runtime_error(quantFile + ": write failed");
+    return true;
+}
+
+// ---- aggregateEstimatesToGeneLevel, src/SailfishUtils.cpp:929-1037 (the `--geneMap` step) ------------------------------------
+// quant.genes.sf at `genesFile` from the columns writeAbundances writes for readExp and sopt, without reading quant.sf back: the
+// header line of quant.sf from the host, then one row per gene -- Name, Length, EffectiveLength, TPM, NumReads, in order of each
+// gene's first transcript -- folded from the PRINTED values (six-digit %g tokens read back, as the reference reads them from the
+// file) and formatted on the device (sfgpu_genes_aggregate / sfgpu_genes_write_text: arithmetic, order and limits in sfgpu.h).
+// `geneName` maps a transcript name to its gene's name -- what TranscriptGeneMap::geneName is (lower_bound, no equality test;
+// past the last name a transcript is its own gene); gene identity is the name it returns.  Throws std::runtime_error naming the
+// file when it cannot be opened or written.
+template <typename GeneNameOf>
+inline bool aggregateEstimatesToGeneLevel(GeneNameOf&& geneName, ReadExperiment& readExp, const SailfishOpts& sopt, const std::string& genesFile) {
+    std::ofstream out(genesFile, std::ios::binary);
+    if (!out) throw std::runtime_error(genesFile + ": cannot open for writing");
+    out << "Name\tLength\tEffectiveLength\tTPM\tNumReads\n";
+    detail::AbundanceColumns c(readExp, sopt);
+    if (c.M) {
+        auto& txps = readExp.transcripts();
+        std::unordered_map<std::string, uint32_t> idOf;
+        std::vector<char> gNames;
+        std::vector<uint64_t> gOff(1, 0);
+        std::vector<uint32_t> geneOfRow(c.M);
+        for (uint64_t i = 0; i < c.M; ++i) {
+            const std::string g = geneName(txps[i].RefName);
+            auto it = idOf.find(g);
+            if (it == idOf.end()) {
+                it = idOf.emplace(g, static_cast<uint32_t>(idOf.size())).first;
+                gNames.insert(gNames.end(), g.begin(), g.end());
+                gOff.push_back(gNames.size());
+            }
+            geneOfRow[i] = it->second;
+        }
+        const uint64_t G = idOf.size();
+        DeviceBuf<uint32_t> dGeneOfRow(geneOfRow), dGeneId(G);
+        DeviceBuf<char> dNames(gNames);
+        DeviceBuf<uint64_t> dOff(gOff);
+        DeviceBuf<double> gLen(G), gEff(G), gTpm(G), gCnt(G);
+        sfgpu_genes_result ar;
+        check(sfgpu_genes_aggregate(dGeneOfRow.get(), c.len.get(), c.eff.get(), c.tpm.get(), c.cnt.get(), c.M, G, 1, dGeneId.get(), gLen.get(),
+                                    gEff.get(), gTpm.get(), gCnt.get(), &ar, nullptr), "sfgpu_genes_aggregate");
+        sfgpu_quant_write_result r;
+        const int rc = sfgpu_genes_write_text(dNames.get(), dOff.get(), G, dGeneId.get(), gLen.get(), gEff.get(), gTpm.get(), gCnt.get(),
+                                              ar.n_genes, 0, detail::ofstream_sink, &out, &r, nullptr);
+        if (rc == SFGPU_ERR_IO) throw std::runtime_error(genesFile + ": write failed");
+        check(rc, "sfgpu_genes_write_text");
+    }
+    out.close();
+    if (!out) throw std::runtime_error(genesFile + ": write failed");
     return true;
 }
 

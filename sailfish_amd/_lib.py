@@ -71,6 +71,14 @@ class QuantWriteResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GenesResult(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("n_genes", C.c_uint64), ("n_slow", C.c_uint64), ("max_rows_per_gene", C.c_uint64),
+                ("aggregate_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GzResult(C.Structure):
     _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("encode_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -146,6 +154,9 @@ _SIGS = {
     "sfgpu_eq_add_text_host": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EqTextResult)]),
     "sfgpu_eqvec_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P, C.POINTER(EqTextWriteResult), _P]),
     "sfgpu_quant_write_text": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P, C.POINTER(QuantWriteResult), _P]),
+    "sfgpu_genes_aggregate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, C.POINTER(GenesResult), _P]),
+    "sfgpu_genes_write_text": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
+                                         C.POINTER(QuantWriteResult), _P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),

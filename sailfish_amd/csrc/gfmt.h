@@ -10,6 +10,7 @@
 //                              gfmt_decode_fast / gfmt_decode_slow are its two halves, for callers that run them apart.
 //   gfmt_len(r)             -> bytes of the token
 //   gfmt_put(r, put)        -> the token through put(i, ch), the convention of decfmt.h: i = 0 is the LAST byte
+//   gfmt_value(r, &slow)    -> the double strtod reads back from that token (genes.hip folds printed values); at the end of the file
 //
 // With x = m 2^e (m < 2^53) and s = 5 - X the digits are D = round_half_even(m 2^e 10^s), an integer division.  X is estimated
 // from the bit length, and corrected by comparing the FLOOR of the quotient with 10^5 and 10^6 (not the rounded value: a binary
@@ -293,6 +294,124 @@ SF_GFMT_HD int gfmt_put(uint32_t r, Put put) {
     put(ne, X < 0 ? '-' : '+');
     put(ne + 1, 'e');
     return len;
+}
+
+// ---- the other direction: the double that strtod reads back from the token of a record (genes.hip folds printed values).
+// The token is D 10^k exactly, k = X - (digits(D) - 1), D < 10^6.
+//   gfmt_value_fast(r, &pending)  |k| <= 22: D and 10^|k| = 5^|k| 2^|k| are exact doubles, so one IEEE multiply or divide is
+//                                 the correctly rounded result; outside, *pending = true and gfmt_value_slow gives the value
+//   gfmt_value_slow(r)            any record, in the limbs above: the integer D 10^k rounded to 53 bits (k >= 0), or the
+//                                 quotient D 2^-e / 10^-k by compare and subtract with e chosen so that it has 53 bits -- fewer
+//                                 when e stops at -1074: denormals -- and the remainder deciding the tie (k < 0)
+SF_GFMT_HD double gfmt_from_bits(uint64_t bits) {
+    double x;
+    memcpy(&x, &bits, 8);
+    return x;
+}
+
+// zero / inf / nan records; false for a record with digits, whose D and k come back
+SF_GFMT_HD bool gfmt_value_split(uint32_t r, double* special, uint32_t* D, int* k) {
+    const uint64_t sign = (r & kGfmtSign) ? 1ull << 63 : 0ull;
+    if (r & kGfmtSpecial) {
+        const uint32_t kind = r & 3u;
+        *special = gfmt_from_bits(kind == kGfmtZero ? sign : kind == kGfmtInf ? (sign | 0x7ff0000000000000ull) : 0x7ff8000000000000ull);
+        return false;
+    }
+    *D = r & 0xfffffu;
+    *k = (int)((r >> 20) & 0x3ffu) - 512 - (dec_len_u32(*D) - 1);
+    return true;
+}
+
+SF_GFMT_HD double gfmt_value_fast(uint32_t r, bool* pending) {
+    double v;
+    uint32_t D;
+    int k;
+    *pending = false;
+    if (!gfmt_value_split(r, &v, &D, &k)) return v;
+    const int ak = k < 0 ? -k : k;
+    if (ak > 22) { *pending = true; return 0.0; }
+    uint64_t p5 = 1;
+    for (int i = 0; i < ak; ++i) p5 *= 5u;                         // 5^22 < 2^52
+    const double p10 = (double)p5 * (double)(1u << ak);           // exact: 10^22 has 52 significant bits
+    v = k < 0 ? (double)D / p10 : (double)D * p10;
+    return (r & kGfmtSign) ? -v : v;
+}
+
+SF_GFMT_HD int gfmt_big_bitlen(const uint32_t* a) {
+    for (int i = kGfmtLimbs - 1; i >= 0; --i)
+        if (a[i]) return 32 * i + gfmt_bitlen_u64(a[i]);
+    return 0;
+}
+
+SF_GFMT_SLOW double gfmt_value_slow(uint32_t r) {
+    double special;
+    uint32_t D;
+    int k;
+    if (!gfmt_value_split(r, &special, &D, &k)) return special;
+    const uint64_t sign = (r & kGfmtSign) ? 1ull << 63 : 0ull;
+    uint32_t num[kGfmtLimbs];
+    for (int i = 0; i < kGfmtLimbs; ++i) num[i] = 0;
+    num[0] = D;
+    uint64_t q;                                                   // the value is q 2^e2 before rounding, q < 2^53
+    int e2;
+    bool up;                                                      // round q up
+    if (k >= 0) {
+        gfmt_big_pow10(num, k);                                   // D 10^k < 2^20 10^308 < 2^1044
+        const int L = gfmt_big_bitlen(num);
+        e2 = L - 53;
+        if (e2 <= 0) {                                            // an integer below 2^53: exact
+            q = ((uint64_t)num[0] | ((uint64_t)num[1] << 32)) << -e2;
+            up = false;
+        } else {                                                  // bits e2 .. e2 + 52 lie in at most three limbs
+            const int w = e2 >> 5, b = e2 & 31;
+            const uint64_t lo = (uint64_t)num[w] | ((uint64_t)(w + 1 < kGfmtLimbs ? num[w + 1] : 0u) << 32);
+            const uint64_t hi = w + 2 < kGfmtLimbs ? num[w + 2] : 0u;
+            q = (b ? (lo >> b) | (hi << (64 - b)) : lo) & ((1ull << 53) - 1u);
+            const int hk = e2 - 1, hw = hk >> 5, hb = hk & 31;
+            const bool half = (num[hw] >> hb) & 1u;
+            bool sticky = (num[hw] & ((1u << hb) - 1u)) != 0;
+            for (int i = 0; i < hw; ++i) sticky = sticky || num[i] != 0;
+            up = half && (sticky || (q & 1u));
+        }
+    } else {
+        uint32_t den[kGfmtLimbs], t[kGfmtLimbs];
+        for (int i = 0; i < kGfmtLimbs; ++i) den[i] = 0;
+        den[0] = 1;
+        gfmt_big_pow10(den, -k);                                  // 10^329 < 2^1093
+        // D / den lies in (2^(bn - bd - 1), 2^(bn - bd + 1)): with e2 = bn - bd - 52 the quotient is below 2^53, and one more
+        // step of the division supplies the missing bit when it is below 2^52
+        e2 = gfmt_bitlen_u64(D) - gfmt_big_bitlen(den) - 52;
+        if (e2 < -1074) e2 = -1074;
+        gfmt_big_shl(num, -e2);                                   // below den 2^53 < 2^1146
+        for (int i = 0; i < kGfmtLimbs; ++i) t[i] = den[i];
+        gfmt_big_shl(t, 52);
+        q = 0;
+        for (int bit = 52; bit >= 0; --bit) {
+            if (gfmt_big_cmp(t, num) <= 0) { gfmt_big_sub(num, t); q |= 1ull << bit; }
+            gfmt_big_shr1(t);
+        }
+        gfmt_big_shl(num, 1);                                     // twice the remainder
+        if (q < (1ull << 52) && e2 > -1074) {
+            --e2;
+            q <<= 1;
+            if (gfmt_big_cmp(num, den) >= 0) { gfmt_big_sub(num, den); q |= 1u; }
+            gfmt_big_shl(num, 1);
+        }
+        const int c = gfmt_big_cmp(num, den);
+        up = c > 0 || (c == 0 && (q & 1u));
+    }
+    if (up) ++q;
+    if (q == (1ull << 53)) { q = 1ull << 52; ++e2; }
+    // q in [2^52, 2^53) is a normal number with biased exponent e2 + 1075; below 2^52 (only with e2 = -1074) a denormal, whose
+    // bits are q itself -- and q = 2^52 there is the smallest normal number by the same sum
+    const int be = e2 + 1075;
+    if (be >= 2047) return gfmt_from_bits(sign | 0x7ff0000000000000ull);
+    return gfmt_from_bits(sign | (q + ((uint64_t)(be - 1) << 52)));
+}
+
+SF_GFMT_HD double gfmt_value(uint32_t r, bool* slow) {
+    const double v = gfmt_value_fast(r, slow);
+    return *slow ? gfmt_value_slow(r) : v;
 }
 
 }  // namespace sfgpu

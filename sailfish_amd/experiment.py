@@ -30,6 +30,7 @@ class SailfishOpts:
     pdfSampFactor: int = 1              # --gcSpeedSamp
     dumpEq: bool = False
     auxDir: str = "aux"
+    txpAggregationKey: str = "gene_id"  # --txpAggregationKey (src/SailfishQuantify.cpp:1115): the GTF attribute genes are grouped by
     jointLog: Optional[object] = None   # callable(level:int, msg:str)
 
 

@@ -121,7 +121,10 @@ def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_op
     log(0, "Finished optimizer")
     exp.last_optimizer_stats = opt.last_stats
     t2 = clock()
-    _writer.write_abundances(out_dir, exp, sopt)                             # :1375
+    columns = _writer.abundance_columns(exp, sopt)
+    if gene_map is not None:                                                 # the gene step runs after the samplers: keep what was written
+        columns = columns[:2] + tuple(c.clone() for c in columns[2:])
+    _writer.write_abundances(out_dir, exp, sopt, columns=columns)            # :1375
     _writer.write_meta(out_dir, exp, sopt, start_time)                       # :1377
     t3 = clock()
     if sopt.numGibbsSamples > 0:                                             # :1379-1397
@@ -149,7 +152,11 @@ def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_op
     t4 = clock()
     if gene_map is not None:                                                 # :1416-1426
         try:
-            _genes.generate_gene_level_estimates(gene_map, out_dir)
+            # from the columns just written, on the device: quant.sf is not read back (genes.aggregate_columns).  Only what the
+            # reference catches here (std::invalid_argument: an unreadable map, :1419) is logged and passed over; a failure of the
+            # device path (_lib.SfgpuError, or a TypeError for columns that are not device tensors) is no map error and is raised,
+            # as every other device failure of this function is: there is no quiet fall-back to the host loop
+            _genes.generate_gene_level_estimates(gene_map, out_dir, agg_key=sopt.txpAggregationKey, columns=columns)
         except ValueError as e:
             log(2, f"Error: [{e}] when trying to compute gene-level estimates. The gene-level file(s) may not exist")
     if timings is not None:

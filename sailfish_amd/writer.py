@@ -27,15 +27,24 @@ def fmt_g(x):
     return "%g" % x
 
 
-def write_abundances(path, readExp: ReadExperiment, sopt: SailfishOpts):
-    """writeAbundances (GZipWriter.cpp:194-248): Name, Length, EffectiveLength, TPM, NumReads.  The header line is written
-    here; the rows are formatted on the device from the columns where they lie (quantfile.write_file, sfgpu_quant_write_text).
-    The bytes are quantfile.format_rows', the per-row loop over fmt_g this function used to run."""
-    from . import quantfile
+def abundance_columns(readExp: ReadExperiment, sopt: SailfishOpts):
+    """The columns of quant.sf where they lie: (names, Length, EffectiveLength, TPM, NumReads) -- the host list of names, the
+    32-bit integer device tensor of reference lengths and three float64 device tensors.  What write_abundances writes and what
+    the gene-level step (genes.aggregate_columns) folds."""
     txps = readExp.transcripts()
     t, length = tpm(readExp, sopt)          # (without the length correction `length` is the reference lengths as doubles)
+    return txps.RefName, txps.RefLength, length, t, txps.estCount
+
+
+def write_abundances(path, readExp: ReadExperiment, sopt: SailfishOpts, columns=None):
+    """writeAbundances (GZipWriter.cpp:194-248): Name, Length, EffectiveLength, TPM, NumReads.  The header line is written
+    here; the rows are formatted on the device from the columns where they lie (quantfile.write_file, sfgpu_quant_write_text).
+    The bytes are quantfile.format_rows', the per-row loop over fmt_g this function used to run.  `columns`: what
+    abundance_columns returned for this experiment, when the caller holds it already."""
+    from . import quantfile
+    _, ref_len, length, t, est = columns if columns is not None else abundance_columns(readExp, sopt)
     os.makedirs(path, exist_ok=True)
-    quantfile.write_file(os.path.join(path, "quant.sf"), txps.name_blob(), txps.RefLength, length, t, txps.estCount)
+    quantfile.write_file(os.path.join(path, "quant.sf"), readExp.transcripts().name_blob(), ref_len, length, t, est)
     return True
 
 

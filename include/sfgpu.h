@@ -454,6 +454,20 @@ SFGPU_API int sfgpu_em_set_bounds(sfgpu_em* em, uint32_t min_iter, uint32_t max_
  * it starts: processes or ranks that share a device call this with 0 (one kernel per iteration then; the same results).  Takes effect
  * for runs that begin afterwards; handles planned while it was 0 have no tables for the loop and keep one kernel per iteration. */
 SFGPU_API int sfgpu_em_allow_persistent(int on);
+/* Diagnostic, like sfgpu_xxh64_labels: the device arithmetic of VBEM's x_t = exp(psi(alpha_t) - c) / effLen_t (csrc/vbmath.h; :300-320)
+ * on its own, one lane per element, for the tests that hold every form to mpmath.  out[i] = form(d_a[i], d_c[i], d_len[i]); all pointers
+ * are device memory (a form reads only the arrays it names; the others may be NULL), n = 0 is fine, asynchronous on `stream`.  An unknown
+ * form returns SFGPU_ERR_INVALID and writes nothing.  The x forms are defined for a >= 0.01, len >= 1, c < 50 (what the loops hand them). */
+enum {
+    SFGPU_VB_DIGAMMA = 0,   /* digamma_pos(a) */
+    SFGPU_VB_X_PREPARE = 1, /* exp(digamma_pos(a) - c) / len: k_vb_prepare, the first x of every run and the two-kernel loop */
+    SFGPU_VB_X_LEAN = 2,    /* vb_x_lean: the fused sweep */
+    SFGPU_VB_X_FAST = 3,    /* vb_x_fast: one division, its own exp, constants in constant memory */
+    SFGPU_VB_X_HEAD = 4,    /* vb_x_head: the persistent loop (fast_rcp, literal constants) */
+    SFGPU_VB_RCP = 5        /* fast_rcp(len) */
+};
+SFGPU_API int sfgpu_vb_eval(int form, const double* d_a, const double* d_c, const double* d_len, uint64_t n, double* d_out,
+                            sfgpu_stream stream);
 SFGPU_API int sfgpu_em_rebase(sfgpu_em* em, const double* d_len);
 /* The sharded loop as ONE call (classes partitioned over the GPUs, alpha replicated, one SUM all-reduce of
  * alphaOut per iteration): `em` holds THIS rank's slice of the classes; `allreduce` must leave the element-wise sum over

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "primitives.h"
 #include "sampling.h"
+#include "vbmath.h"
 
 #include <atomic>
 #include <map>
@@ -80,140 +81,19 @@ __global__ void k_post_state(const EmState* st, uint32_t min_iter, uint32_t max_
     *mirror = (unsigned long long)it | ((unsigned long long)(stop ? 1u : 0u) << 32);
 }
 
-// psi(x), x > 0: the recurrence psi(x) = psi(x + 10) - sum_{k<10} 1/(x + k) for x < 10, then the asymptotic
-// series through B_14 (boost::math::digamma at :303, :314 in the reference; |err| ~ 1e-15).
-// The ten reciprocals are added as ONE fraction (pairwise n/d merges: every term is positive, so nothing
-// cancels) -- a single f64 division instead of up to ten dependent ones (a wavefront always holds some
-// low-abundance transcript, so the old loop ran all ten rounds for everybody).
-__host__ __device__ __forceinline__ double digamma_pos(double x) {
-    double r = 0.0;
-    if (x < 10.0) {
-        const double a0 = x, a1 = x + 1.0, a2 = x + 2.0, a3 = x + 3.0, a4 = x + 4.0,
-                     a5 = x + 5.0, a6 = x + 6.0, a7 = x + 7.0, a8 = x + 8.0, a9 = x + 9.0;
-        double n01 = a0 + a1, d01 = a0 * a1, n23 = a2 + a3, d23 = a2 * a3, n45 = a4 + a5, d45 = a4 * a5,
-               n67 = a6 + a7, d67 = a6 * a7, n89 = a8 + a9, d89 = a8 * a9;
-        const double n03 = n01 * d23 + n23 * d01, d03 = d01 * d23;
-        const double n47 = n45 * d67 + n67 * d45, d47 = d45 * d67;
-        const double n07 = n03 * d47 + n47 * d03, d07 = d03 * d47;
-        const double n09 = n07 * d89 + n89 * d07, d09 = d07 * d89;
-        r = -(n09 / d09);
-        x += 10.0;
-    }
-    double inv = 1.0 / x, inv2 = inv * inv;
-    double s = inv2 * (1.0 / 12.0 - inv2 * (1.0 / 120.0 - inv2 * (1.0 / 252.0 - inv2 * (1.0 / 240.0
-             - inv2 * (1.0 / 132.0 - inv2 * (691.0 / 32760.0 - inv2 * (1.0 / 12.0)))))));
-    return r + log(x) - 0.5 * inv - s;
-}
-
-// VBEM's x_t = exp(psi(a) - c) / effLen (:300-320) for the FUSED sweep, whose 64-register budget has no room for digamma_pos's
-// pairwise tree, a log and an exp.  Same recurrence and series as digamma_pos, but exp(log(y)) is y itself:
-//   exp(psi(a) - c) = y exp(-(1 / (2y) + s(y) + r + c)),   y = a (+ 10 below 10),   r = sum_{k<10} 1 / (a + k),
-// with r gathered as ONE fraction term by term (all terms positive: nothing cancels; ten numbers below 20 multiply to < 1e13).
-// One exp, no log, ~10 live doubles; agrees with exp(digamma_pos(a) - c) to a few ulp.
-__device__ __forceinline__ double vb_x_lean(double a, double c, double len) {
-    double y = a, q = c;
-    if (a < 10.0) {
-        double n = 1.0, d = a;
-#pragma unroll
-        for (int k = 1; k < 10; ++k) { const double t = a + (double)k; n = n * t + d; d = d * t; }
-        q += n / d;
-        y = a + 10.0;
-    }
-    const double inv = 1.0 / y, inv2 = inv * inv;
-    const double s = inv2 * (1.0 / 12.0 - inv2 * (1.0 / 120.0 - inv2 * (1.0 / 252.0 - inv2 * (1.0 / 240.0
-                   - inv2 * (1.0 / 132.0 - inv2 * (691.0 / 32760.0 - inv2 * (1.0 / 12.0)))))));
-    q += 0.5 * inv + s;
-    return y * exp(-q) / len;
-}
-
-// The same for the kernels that are short of registers AND of issue slots (the fused sweep, the persistent loop: every thread of a
-// window slot evaluates this once per iteration, ~9 wavefronts per tile on a dependent chain).  One division instead of three
-// (n / d, 1 / y and 1 / effLen share the reciprocal of d y effLen) and an exp of its own: k = rint(t log2 e), r = t - k ln 2 in two
-// pieces, the Taylor polynomial to r^13 (|r| <= ln 2 / 2: the remainder is below 4e-18), ldexp -- no special cases: the argument lies
-// in (-200, 0] (alpha >= the prior 0.01, c = psi(M prior + numMapped) < 50).  Its 15 constants sit in constant memory: as literals
-// the compiler keeps them in VGPR pairs across the persistent loop and spills them.  ~70 instructions against ~150; agrees with
-// exp(digamma_pos(a) - c) / len to ~1e-13 at alpha near the prior (the fraction of ten terms carries the rounding; the tests hold every loop to 1e-9).
-struct VbConsts { double l2e, ln2_hi, ln2_lo, c[12]; double s[7]; };
-__device__ __constant__ VbConsts kVb = {
-    1.4426950408889634074, 6.93147180369123816490e-01, 1.90821492927058770002e-10,
-    {1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0,
-     1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0, 0.5},
-    {1.0 / 12.0, 691.0 / 32760.0, 1.0 / 132.0, 1.0 / 240.0, 1.0 / 252.0, 1.0 / 120.0, 1.0 / 12.0}};
-__device__ __forceinline__ double vb_x_fast(double a, double c, double len) {
-    double y = a, n = 0.0, d = 1.0;
-    if (a < 10.0) {
-        n = 1.0; d = a;
-#pragma unroll
-        for (int k = 1; k < 10; ++k) { const double t = a + (double)k; n = fma(n, t, d); d = d * t; }
-        y = a + 10.0;
-    }
-    const double dy = d * y;
-    const double R = 1.0 / (dy * len);                                 // the one division
-    const double inv = (d * len) * R;                                  // 1 / y
-    const double rlen = dy * R;                                        // 1 / effLen
-    const double inv2 = inv * inv;
-    const VbConsts& K = kVb;
-    double s = fma(-inv2, K.s[0], K.s[1]);                              // inv2 (1/12 - inv2 (1/120 - inv2 (1/252 - inv2 (1/240 - inv2 (1/132 - inv2 (691/32760 - inv2 / 12))))))
-    s = fma(-inv2, s, K.s[2]); s = fma(-inv2, s, K.s[3]); s = fma(-inv2, s, K.s[4]); s = fma(-inv2, s, K.s[5]); s = fma(-inv2, s, K.s[6]);
-    s = s * inv2;
-    // t = -(c + n / d + 1 / (2 y) + s)   (n / d = n y effLen R)
-    const double t = -(c + fma(n * y, len * R, fma(0.5, inv, s)));
-    const double kf = rint(t * K.l2e);
-    double r = fma(-kf, K.ln2_hi, t);
-    r = fma(-kf, K.ln2_lo, r);
-    double p = K.c[0];
-#pragma unroll
-    for (int i = 1; i < 12; ++i) p = fma(p, r, K.c[i]);
-    p = fma(p, r, 1.0); p = fma(p, r, 1.0);
-    return ldexp(p * y, (int)kf) * rlen;
-}
-
-// The same arithmetic for the PERSISTENT loop's head (round 6).  There every tile is in the same phase at the same time (a tile needs its
-// neighbours' sums of the step before: lockstep), so the head's instructions are not hidden under another block's LDS phases and every
-// one of them is on the step's critical path -- and the constants of vb_x_fast arrived through 58 v_readlane per evaluation (22 doubles
-// loaded once, far more than the kernel's SGPRs hold: spilled into VGPR lanes).  Here a constant is two s_mov_b32 with literals right where
-// it is used (scalar ALU, no memory, no spill, never hoisted: the asm is volatile), and the two divisions are v_rcp_f64 + two Newton steps
-// (the operands are far from the denormals: a >= the prior, effLen >= 1) instead of the IEEE sequence.
-template <uint64_t B> __device__ __forceinline__ double kd_bits() {
-    uint32_t lo, hi;
-    asm volatile("s_mov_b32 %0, %1" : "=s"(lo) : "n"((uint32_t)B));
-    asm volatile("s_mov_b32 %0, %1" : "=s"(hi) : "n"((uint32_t)(B >> 32)));
-    return __hiloint2double((int)hi, (int)lo);
-}
-#define SF_KD(x) kd_bits<__builtin_bit_cast(uint64_t, (double)(x))>()
-__device__ __forceinline__ double fast_rcp(double x) {                 // 1 / x to ~1 ulp for normal x
-    double r = __builtin_amdgcn_rcp(x);
-    r = fma(fma(-x, r, 1.0), r, r);
-    r = fma(fma(-x, r, 1.0), r, r);
-    return r;
-}
-__device__ __forceinline__ double vb_x_head(double a, double c, double len) {
-    double y = a, n = 0.0, d = 1.0;
-    if (a < 10.0) {
-        n = 1.0; d = a;
-#pragma unroll
-        for (int k = 1; k < 10; ++k) { const double t = a + (double)k; n = fma(n, t, d); d = d * t; }
-        y = a + 10.0;
-    }
-    const double dy = d * y;
-    const double R = fast_rcp(dy * len);                               // the one reciprocal
-    const double inv = (d * len) * R;                                  // 1 / y
-    const double rlen = dy * R;                                        // 1 / effLen
-    const double inv2 = inv * inv;
-    double s = fma(-inv2, SF_KD(1.0 / 12.0), SF_KD(691.0 / 32760.0));   // inv2 (1/12 - inv2 (1/120 - inv2 (1/252 - inv2 (1/240 - inv2 (1/132 - inv2 (691/32760 - inv2 / 12))))))
-    s = fma(-inv2, s, SF_KD(1.0 / 132.0)); s = fma(-inv2, s, SF_KD(1.0 / 240.0)); s = fma(-inv2, s, SF_KD(1.0 / 252.0));
-    s = fma(-inv2, s, SF_KD(1.0 / 120.0)); s = fma(-inv2, s, SF_KD(1.0 / 12.0));
-    s = s * inv2;
-    const double t = -(c + fma(n * y, len * R, fma(0.5, inv, s)));      // -(c + n / d + 1 / (2 y) + s)   (n / d = n y effLen R)
-    const double kf = rint(t * SF_KD(1.4426950408889634074));
-    double r = fma(-kf, SF_KD(6.93147180369123816490e-01), t);
-    r = fma(-kf, SF_KD(1.90821492927058770002e-10), r);
-    double p = SF_KD(1.0 / 6227020800.0);
-    p = fma(p, r, SF_KD(1.0 / 479001600.0)); p = fma(p, r, SF_KD(1.0 / 39916800.0)); p = fma(p, r, SF_KD(1.0 / 3628800.0));
-    p = fma(p, r, SF_KD(1.0 / 362880.0)); p = fma(p, r, SF_KD(1.0 / 40320.0)); p = fma(p, r, SF_KD(1.0 / 5040.0)); p = fma(p, r, SF_KD(1.0 / 720.0));
-    p = fma(p, r, SF_KD(1.0 / 120.0)); p = fma(p, r, SF_KD(1.0 / 24.0)); p = fma(p, r, SF_KD(1.0 / 6.0)); p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0); p = fma(p, r, 1.0);
-    return ldexp(p * y, (int)kf) * rlen;
+// psi(x) and the forms of VBEM's x_t = exp(psi(alpha_t) - c) / effLen_t -- digamma_pos, vb_x_lean, vb_x_fast, vb_x_head, fast_rcp -- live in
+// vbmath.h (included above), which g++ compiles too: tests/test_vbmath_cpu.py and tests/test_gpu_vbmath.py hold every form to mpmath per evaluation.
+// sfgpu_vb_eval's kernel: one lane per element, the form fixed at compile time (each instance holds one form's code, as its caller does).
+template <int FORM> __global__ void k_vb_eval(const double* __restrict__ a, const double* __restrict__ c, const double* __restrict__ len,
+                                              uint64_t n, double* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kEmBlock + threadIdx.x;
+    if (i >= n) return;
+    if (FORM == SFGPU_VB_DIGAMMA) out[i] = digamma_pos(a[i]);
+    else if (FORM == SFGPU_VB_X_PREPARE) out[i] = exp(digamma_pos(a[i]) - c[i]) / len[i];
+    else if (FORM == SFGPU_VB_X_LEAN) out[i] = vb_x_lean(a[i], c[i], len[i]);
+    else if (FORM == SFGPU_VB_X_FAST) out[i] = vb_x_fast(a[i], c[i], len[i]);
+    else if (FORM == SFGPU_VB_X_HEAD) out[i] = vb_x_head(a[i], c[i], len[i]);
+    else out[i] = fast_rcp(len[i]);
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -2471,6 +2351,26 @@ int sfgpu_em_init(sfgpu_em* em) { return sfgpu_em_init_impl(em); }
 
 double* sfgpu_em_alpha(sfgpu_em* em) { return em ? em->alpha : nullptr; }
 double* sfgpu_em_lengths(sfgpu_em* em) { return em ? em->lenc : nullptr; }
+
+int sfgpu_vb_eval(int form, const double* d_a, const double* d_c, const double* d_len, uint64_t n, double* d_out, sfgpu_stream stream) {
+    if (form < SFGPU_VB_DIGAMMA || form > SFGPU_VB_RCP) { set_error("sfgpu_vb_eval: unknown form %d", form); return SFGPU_ERR_INVALID; }
+    SF_REQUIRE(n <= (1ull << 31), SFGPU_ERR_RANGE, "sfgpu_vb_eval: n exceeds 2^31");
+    if (n == 0) return SFGPU_OK;
+    const bool need_a = form != SFGPU_VB_RCP, need_c = form >= SFGPU_VB_X_PREPARE && form <= SFGPU_VB_X_HEAD, need_len = form != SFGPU_VB_DIGAMMA;
+    SF_REQUIRE(d_out && (!need_a || d_a) && (!need_c || d_c) && (!need_len || d_len), SFGPU_ERR_INVALID, "sfgpu_vb_eval: null pointer");
+    const dim3 g(blocks_for(n)), b(kEmBlock);
+    hipStream_t st = as_stream(stream);
+    switch (form) {
+    case SFGPU_VB_DIGAMMA:   hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_DIGAMMA>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    case SFGPU_VB_X_PREPARE: hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_X_PREPARE>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    case SFGPU_VB_X_LEAN:    hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_X_LEAN>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    case SFGPU_VB_X_FAST:    hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_X_FAST>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    case SFGPU_VB_X_HEAD:    hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_X_HEAD>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    default:                 hipLaunchKernelGGL(k_vb_eval<SFGPU_VB_RCP>, g, b, 0, st, d_a, d_c, d_len, n, d_out); break;
+    }
+    SF_CHECK_LAUNCH();
+    return SFGPU_OK;
+}
 
 int sfgpu_em_allow_persistent(int on) { g_allow_persist.store(on != 0, std::memory_order_relaxed); return SFGPU_OK; }
 

@@ -37,7 +37,7 @@ enum {
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host, sfgpu_reads_parse_host) */
     SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
 };
 
@@ -158,6 +158,58 @@ typedef struct {
 } sfgpu_eqtext_result;
 SFGPU_API int sfgpu_eq_add_text_host(sfgpu_eq* eq, const char* h_text, uint64_t n_bytes, uint64_t n_transcripts,
                                      uint64_t chunk_bytes, sfgpu_eqtext_result* out);
+/* FASTA / FASTQ records parsed on the device: a piece of a transcript or read file in, the packed bases and offsets that
+ * sfgpu_index_build and sfgpu_map_reads take out.  The C++ host of the reference keeps its own parsers; this
+ * entry point serves hosts that have none.  The rules live in sailfish_amd/csrc/readfmt.h, in short:
+ *   - h_text begins at a record start; its first byte fixes the format of the call ('>' FASTA, '@' FASTQ, else SFGPU_ERR_FORMAT
+ *     at record 0).  Lines end at '\n'; one '\r' before it is dropped.
+ *   - FASTQ: exactly four lines per record, the kind of a line is its index mod 4 (a quality line may begin with '@' or '+');
+ *     line 0 begins with '@', line 2 with '+', the quality is as long as the sequence.  No multi-line FASTQ.
+ *   - FASTA: a line that begins with '>' opens a record, all other lines up to the next one are its sequence (empty lines add
+ *     nothing, a record may be empty).
+ *   - bases are copied as they are (no case folding, N kept); the name is what follows '>' / '@' up to the first space or tab.
+ *   - final == 0: only complete records are seen (FASTQ: the '\n' of the fourth line is there; FASTA: the next '>' line has
+ *     begun).  final == 1: the last line may lack its '\n', an open FASTA record is complete, a FASTQ record with fewer than four
+ *     lines is SFGPU_READS_TRUNCATED; empty lines behind the last record are allowed.
+ * The call emits the longest prefix of the complete records that has at most max_reads records and at most cap_bases bases:
+ * d_bases[0 .. n_bases) (16-byte aligned, else SFGPU_ERR_INVALID), d_off[0 .. n_reads] (int64, d_off[0] = 0), and, unless
+ * d_name_span is NULL, (begin, length) of each name within h_text in d_name_span[2 r], [2 r + 1].  `consumed` is where the next
+ * call's text begins: the caller presents h_text + consumed again with more bytes appended (carry-over is the caller's).
+ * SFGPU_OK with n_reads == 0 and consumed == 0 on a text that is not final: no complete record yet, present more bytes.
+ * A first record with more than cap_bases bases is SFGPU_ERR_RANGE, as is n_bytes > 2^30.  A malformed record among the
+ * complete records of the text -- emitted or not -- is SFGPU_ERR_FORMAT: the smallest record wins, within it the first check
+ * that fails, and nothing is emitted.  n_bytes == 0, or a text of nothing but line ends, is SFGPU_OK with no records (consumed
+ * = n_bytes when final).
+ * The text (pageable is fine) goes through the library's pinned double buffer in sub-chunks; the copy of sub-chunk c + 1 runs
+ * while the newlines of sub-chunk c are counted; records are resolved over the whole text.  Synchronous, ordered behind the
+ * work already on `stream`, thread-safe like the other text calls, no CPU path. */
+enum {
+    SFGPU_READS_NONE = 0,
+    SFGPU_READS_FASTA = 1,
+    SFGPU_READS_FASTQ = 2
+};
+enum {
+    SFGPU_READS_OK = 0,
+    SFGPU_READS_BAD_START = 1,       /* a record does not begin with '@' (or the text with neither '>' nor '@') */
+    SFGPU_READS_MISSING_PLUS = 2,    /* the third line of a FASTQ record does not begin with '+' */
+    SFGPU_READS_LENGTH_MISMATCH = 3, /* quality and sequence of a FASTQ record differ in length */
+    SFGPU_READS_TRUNCATED = 4        /* final text: the last FASTQ record has fewer than four lines */
+};
+typedef struct {
+    uint64_t n_reads;      /* records emitted */
+    uint64_t n_bases;      /* their bases = d_off[n_reads] */
+    uint64_t consumed;     /* bytes of h_text through the end of the last emitted record, its line end included */
+    uint64_t n_lines;      /* lines of the text: its '\n' bytes, plus the last line of a final text */
+    uint64_t error_record; /* 0-based record of the first error within this call's text; UINT64_MAX without one */
+    uint64_t error_line;   /* ... and its 0-based line (TRUNCATED: the first line that is missing) */
+    int32_t format;        /* SFGPU_READS_FASTA / _FASTQ */
+    int32_t error_kind;    /* SFGPU_READS_* */
+    double ms_copy;        /* device events around the staged host-to-device copies */
+    double ms_kernels;     /* device events around the kernels and scans */
+} sfgpu_reads_result;
+SFGPU_API int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
+                                     uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                     sfgpu_stream stream);
 /* writeEquivCounts (src/GZipWriter.cpp:77-88), the other direction: the CLASS SECTION of an eq_classes.txt file formatted on the
  * device from a class table in CSR form (the sfgpu_eq_export_device arrays, a table merged by sfgpu_eqvec_merge_disjoint, or
  * one the caller assembled).  For each class, in the order given,

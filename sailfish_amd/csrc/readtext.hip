@@ -1,0 +1,370 @@
+// readtext.hip -- FASTA / FASTQ records parsed on the device: sfgpu_reads_parse_host.  What a record is, is decided by readfmt.h
+// (the same functions run serially in tests/readfile_harness.cpp); this file is the passes around them.
+//
+// The host text goes through two pinned buffers in sub-chunks of kSubBytes; the copy of sub-chunk c + 1 runs on the copy stream
+// while the '\n' bytes of sub-chunk c are counted.  A '\n' is appended behind the text, so the remainder (readfmt.h) is a line of
+// the device text like any other and L = the number of '\n' bytes on the device.  Then, over the whole text:
+//   k_reads_line_ends   scan of the counts -> where every line ends
+//   k_reads_lines       one lane per line: rf_line -> header flag, bases of the line, the FASTQ checks (atomic min over
+//                       (record << 8 | kind)) and the last non-empty line (atomic max)
+//   two scans           header flags -> the record of every line; bases per line -> where the line's bases go (dst)
+//   k_reads_rec_lines   the line that opens each record
+//   k_reads_cut         one lane: records the text holds, the error, the cut at max_reads / cap_bases (binary search), consumed
+//   k_reads_emit        one lane per record: d_off, the name span
+//   k_reads_compact     one block per 4 KB tile of the packed bases: each lane finds the line its 16 output bytes begin in by
+//                       binary search in dst, gathers them (one unaligned 16-byte read when they lie in one line, byte by byte
+//                       across line ends) and issues one 16-byte store
+#include "common.h"
+#include "primitives.h"
+#include "readfmt.h"
+
+namespace sfgpu {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr uint64_t kSubBytes = 4ull << 20;               // staged sub-chunk (a multiple of 16)
+constexpr uint32_t kTileBytes = 4096;                    // kBlock lanes x one 16-byte store
+
+inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+__device__ inline uint32_t nl_mask(const uint4 v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m |= (uint32_t)(((w[i >> 2] >> (8 * (i & 3))) & 0xffu) == '\n') << i;
+    return m;
+}
+
+__global__ void k_reads_count(const uint4* __restrict__ buf, uint64_t g0, uint64_t g1, uint32_t* __restrict__ nl_cnt) {
+    const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= g1) return;
+    nl_cnt[g] = __popc(nl_mask(buf[g]));
+}
+
+__global__ void k_reads_line_ends(const uint4* __restrict__ buf, uint64_t n_groups, const uint32_t* __restrict__ nl_scan,
+                                  uint32_t* __restrict__ line_end) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    uint32_t nl = nl_mask(buf[g]);
+    uint32_t at = nl_scan[g];
+    while (nl) {
+        const int i = __ffs(nl) - 1;
+        nl &= nl - 1;
+        line_end[at++] = (uint32_t)(g * 16 + i);
+    }
+}
+
+struct Bounds {
+    const uint32_t* line_end;
+    __device__ void operator()(uint32_t j, uint32_t* s, uint32_t* e) const { *s = j ? line_end[j - 1] + 1 : 0; *e = line_end[j]; }
+};
+struct Bytes {
+    const unsigned char* p;
+    __device__ unsigned char operator()(uint32_t i) const { return p[i]; }
+};
+
+// misc[0] = first error of the line checks, misc[1] = T (1 + the last non-empty usable line)
+__global__ void k_reads_lines(const unsigned char* __restrict__ bytes, int format, int final, uint32_t L, const uint32_t* __restrict__ line_end,
+                              uint32_t* __restrict__ hdr, uint32_t* __restrict__ seq, unsigned long long* __restrict__ misc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long t = 0;
+    if (i < L) {
+        const RfLine r = rf_line(format, final, i, L, Bytes{bytes}, Bounds{line_end});
+        hdr[i] = r.header;
+        seq[i] = r.seq;
+        if (r.error) atomicMin(&misc[0], ((unsigned long long)(i >> 2) << 8) | (unsigned long long)r.error);
+        if (r.len) t = (unsigned long long)i + 1;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(t, o);
+        t = other > t ? other : t;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0 && t) atomicMax(&misc[1], t);
+}
+
+// rec_line[r] = the line that opens record r; rec_line[H] = L
+__global__ void k_reads_rec_lines(uint32_t L, const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ hdr_scan,
+                                  uint32_t* __restrict__ rec_line) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > L) return;
+    if (i == L) { rec_line[hdr_scan[L]] = L; return; }
+    if (hdr[i]) rec_line[hdr_scan[i]] = i;
+}
+
+// res: [0] error, [1] records emitted, [2] their bases, [3] consumed, [4] records the text holds, [5] error line, [6] lines before the cut
+__global__ void k_reads_cut(int format, int final, uint32_t L, uint64_t n_bytes, uint64_t max_reads, uint64_t cap_bases,
+                            const uint32_t* __restrict__ line_end, const uint32_t* __restrict__ hdr_scan, const uint32_t* __restrict__ dst,
+                            const uint32_t* __restrict__ rec_line, const unsigned long long* __restrict__ misc,
+                            unsigned long long* __restrict__ res) {
+    if (blockIdx.x || threadIdx.x) return;
+    const RfCount c = rf_count_records(format, final, L, (uint32_t)misc[1], hdr_scan[L]);
+    const unsigned long long err = rf_final_error(misc[0], c);
+    res[0] = err; res[4] = c.records;
+    res[1] = res[2] = res[3] = res[5] = res[6] = 0;
+    if (err != kReadsNoError) { res[5] = rf_error_line(err, c); return; }
+    auto off_of = [&](uint32_t r) -> uint64_t { return dst[rec_line[r]]; };
+    const uint32_t R = rf_cut(c.records, max_reads, cap_bases, off_of);
+    const uint32_t rl = rec_line[R];
+    uint32_t s = 0, e = 0;
+    if (rl < L) Bounds{line_end}(rl, &s, &e);
+    res[1] = R; res[2] = off_of(R); res[3] = rf_consumed(final, R, c.records, n_bytes, s); res[6] = rl;
+}
+
+__global__ void k_reads_emit(const unsigned char* __restrict__ bytes, uint32_t R, const uint32_t* __restrict__ line_end,
+                             const uint32_t* __restrict__ dst, const uint32_t* __restrict__ rec_line, int64_t* __restrict__ d_off,
+                             uint64_t* __restrict__ d_name_span) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > R) return;
+    const uint32_t line = rec_line[r];
+    d_off[r] = (int64_t)dst[line];
+    if (r == R || !d_name_span) return;
+    uint32_t s, e;
+    Bounds{line_end}(line, &s, &e);
+    d_name_span[2 * (uint64_t)r] = (uint64_t)s + 1;
+    d_name_span[2 * (uint64_t)r + 1] = rf_name_len(Bytes{bytes}, s, rf_line_len(Bytes{bytes}, s, e));
+}
+
+// 16 bytes from byte p of the text (the buffer holds a whole group behind the last one that is read)
+__device__ inline uint4 load_unaligned16(const uint4* __restrict__ buf, uint32_t p) {
+    const uint4 a = buf[p >> 4], b = buf[(p >> 4) + 1];
+    const uint32_t t[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    const uint32_t ws = (p & 15u) >> 2, bs = (p & 3u) * 8;
+    uint32_t u[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) u[j] = ws == 0 ? t[j] : ws == 1 ? t[j + 1] : ws == 2 ? t[j + 2] : t[j + 3];
+    uint4 v;
+    v.x = __funnelshift_r(u[0], u[1], bs); v.y = __funnelshift_r(u[1], u[2], bs);
+    v.z = __funnelshift_r(u[2], u[3], bs); v.w = __funnelshift_r(u[3], u[4], bs);
+    return v;
+}
+
+// lines [0, Lc) carry the n_bases bases of the emitted records; dst[Lc] = n_bases
+__global__ void __launch_bounds__(kBlock) k_reads_compact(const uint4* __restrict__ buf, uint32_t Lc, uint32_t n_bases,
+                                                          const uint32_t* __restrict__ line_end, const uint32_t* __restrict__ dst,
+                                                          uint4* __restrict__ out) {
+    const uint32_t o = (blockIdx.x * (uint32_t)kBlock + threadIdx.x) * 16u;
+    if (o >= n_bases) return;
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(buf);
+    const uint32_t cnt = n_bases - o < 16u ? n_bases - o : 16u;
+    uint32_t lo = 0, hi = Lc;                                // dst[lo] <= o < dst[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (dst[mid] <= o) lo = mid; else hi = mid;
+    }
+    uint32_t i = lo;
+    uint32_t src = (i ? line_end[i - 1] + 1 : 0) + (o - dst[i]);
+    uint32_t avail = dst[i + 1] - o;
+    if (avail >= 16u) {                                      // (then cnt == 16)
+        out[o >> 4] = load_unaligned16(buf, src);
+        return;
+    }
+    uint32_t w[4] = {0, 0, 0, 0};
+    for (uint32_t k = 0; k < cnt;) {
+        if (avail == 0) {                                    // on to the next line that carries bases (there is one: k < cnt)
+            ++i;
+            src = line_end[i - 1] + 1;
+            avail = dst[i + 1] - dst[i];
+            continue;
+        }
+        const uint32_t take = avail < cnt - k ? avail : cnt - k;
+        for (uint32_t j = 0; j < take; ++j, ++k) {
+            const uint32_t b = bytes[src + j];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) if ((k >> 2) == (uint32_t)q) w[q] |= b << (8 * (k & 3u));
+        }
+        avail -= take;
+    }
+    if (cnt == 16u) { out[o >> 4] = make_uint4(w[0], w[1], w[2], w[3]); return; }
+    unsigned char* tail = reinterpret_cast<unsigned char*>(out) + o;
+    for (uint32_t k = 0; k < cnt; ++k) tail[k] = (unsigned char)(w[k >> 2] >> (8 * (k & 3u)));
+}
+
+const char* kind_text(int kind) {
+    switch (kind) {
+        case SFGPU_READS_BAD_START: return "the record does not begin with '@' (the text with neither '>' nor '@')";
+        case SFGPU_READS_MISSING_PLUS: return "the third line does not begin with '+'";
+        case SFGPU_READS_LENGTH_MISMATCH: return "quality and sequence differ in length";
+        case SFGPU_READS_TRUNCATED: return "the last record has fewer than four lines";
+        default: return "malformed";
+    }
+}
+
+struct ReadScratch {
+    DevBuf<uint4> text;
+    DevBuf<uint32_t> nl_cnt, nl_scan, line_end, hdr, seq, hdr_scan, dst, rec_line;
+    DevBuf<unsigned long long> misc;        // [0] first line error, [1] T, [2 .. 8] k_reads_cut's results
+};
+
+}  // namespace
+}  // namespace sfgpu
+
+using namespace sfgpu;
+
+extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
+                                      uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                      sfgpu_stream stream) {
+    SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null result");
+    memset(out, 0, sizeof(*out));
+    out->error_record = ~0ull; out->error_line = ~0ull;
+    SF_REQUIRE(n_bytes <= kReadsMaxBytes, SFGPU_ERR_RANGE, "sfgpu_reads_parse_host: more than 2^30 bytes in one call");
+    SF_REQUIRE(n_bytes == 0 || h_text, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null text");
+    SF_REQUIRE(d_off && (d_bases || cap_bases == 0), SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null output");
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_bases) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: d_bases must be 16-byte aligned");
+    final = final ? 1 : 0;
+    hipStream_t st = as_stream(stream);
+    SF_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
+    if (n_bytes == 0) { SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
+    const int format = rf_format_of((unsigned char)h_text[0]);
+    out->format = format;
+    if (format == SFGPU_READS_NONE) {
+        SF_HIP(hipStreamSynchronize(st));
+        if (rf_all_blank(h_text, n_bytes)) {
+            for (uint64_t p = 0; p < n_bytes; ++p) out->n_lines += h_text[p] == '\n';
+            out->n_lines += (uint64_t)final;
+            out->consumed = final ? n_bytes : 0;
+            return SFGPU_OK;
+        }
+        out->error_record = 0; out->error_line = 0; out->error_kind = SFGPU_READS_BAD_START;
+        set_error("reads text: record 0: %s", kind_text(SFGPU_READS_BAD_START));
+        return SFGPU_ERR_FORMAT;
+    }
+
+    // device text: the n_bytes, the appended '\n', zeros up to the group's end and one more group of zeros (load_unaligned16)
+    const uint64_t n1 = n_bytes + 1, n_groups = (n1 + 15) / 16;
+    const uint64_t n_sub = (n_bytes + kSubBytes - 1) / kSubBytes;
+    ReadScratch S;
+    hipStream_t cs = nullptr;
+    char* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
+    hipEvent_t ev_p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned long long* h_res = nullptr;
+    bool in_flight[2] = {false, false};
+    int rc = SFGPU_OK;
+    uint32_t L = 0;
+
+    // every exit below goes through `done`: nothing may be released while a copy still reads the pinned buffers
+#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
+#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
+    {
+        // a slot's times are read when the slot is taken again, and at the end
+        auto collect = [&](int slot) {
+            if (!in_flight[slot]) return;
+            (void)hipEventSynchronize(ev_c1[slot]);
+            float a = 0.f, b = 0.f;
+            if (hipEventElapsedTime(&a, ev_h2d[slot], ev_copied[slot]) == hipSuccess) out->ms_copy += (double)a;
+            if (hipEventElapsedTime(&b, ev_c0[slot], ev_c1[slot]) == hipSuccess) out->ms_kernels += (double)b;
+            in_flight[slot] = false;
+        };
+        T_HIP(stream_acquire(&cs));
+        for (int b = 0; b < 2 && (uint64_t)b < n_sub; ++b) {
+            T_HIP(pinned_malloc(&pinned[b], (n_bytes < kSubBytes ? n_bytes : kSubBytes) + 48));
+            for (hipEvent_t* e : {&ev_h2d[b], &ev_copied[b], &ev_c0[b], &ev_c1[b]}) T_HIP(hipEventCreateWithFlags(e, hipEventDefault));
+        }
+        for (auto& e : ev_p) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
+        T_HIP(pinned_malloc(&h_res, 8 * sizeof(unsigned long long)));
+        T_TRY(S.text.reserve(n_groups + 1, st, false));
+        T_TRY(S.nl_cnt.reserve(n_groups + 1, st, false));
+        T_TRY(S.nl_scan.reserve(n_groups + 1, st, false));
+        T_TRY(S.misc.reserve(16, st, false));
+        T_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
+        T_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
+        T_HIP(hipEventRecord(ev_p[0], st));
+        T_HIP(hipStreamWaitEvent(cs, ev_p[0], 0));          // the copies stay behind whatever `stream` held and behind the reservations
+
+        // ---- staged copy; the newlines of sub-chunk c are counted while sub-chunk c + 1 is copied
+        for (uint64_t c = 0; c < n_sub; ++c) {
+            const int slot = (int)(c & 1);
+            collect(slot);                                   // its previous copy has left the pinned buffer
+            const uint64_t p = c * kSubBytes, q = (c + 1 == n_sub) ? n_bytes : p + kSubBytes;
+            uint64_t m = q - p;
+            memcpy(pinned[slot], h_text + p, m);
+            if (c + 1 == n_sub) {
+                pinned[slot][m++] = '\n';
+                const uint64_t padded = ((m + 15) & ~15ull) + 16;
+                memset(pinned[slot] + m, 0, padded - m);
+                m = padded;
+            }
+            T_HIP(hipEventRecord(ev_h2d[slot], cs));
+            T_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.text.p) + p, pinned[slot], m, hipMemcpyHostToDevice, cs));
+            T_HIP(hipEventRecord(ev_copied[slot], cs));
+            const uint64_t g0 = p / 16, g1 = (c + 1 == n_sub) ? n_groups : q / 16;
+            T_HIP(hipStreamWaitEvent(st, ev_copied[slot], 0));
+            T_HIP(hipEventRecord(ev_c0[slot], st));
+            hipLaunchKernelGGL(k_reads_count, dim3(grid_of(g1 - g0)), dim3(kBlock), 0, st, S.text.p, g0, g1, S.nl_cnt.p);
+            T_HIP(hipGetLastError());
+            T_HIP(hipEventRecord(ev_c1[slot], st));
+            in_flight[slot] = true;
+        }
+
+        // ---- lines
+        T_HIP(hipEventRecord(ev_p[1], st));
+        T_TRY(exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st));
+        T_HIP(hipEventRecord(ev_p[2], st));
+        T_HIP(hipMemcpyAsync(&h_res[7], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        collect(0); collect(1);
+        L = (uint32_t)h_res[7];                               // >= 1: the appended '\n'
+        out->n_lines = (uint64_t)L - 1 + (uint64_t)final;
+        for (DevBuf<uint32_t>* b : {&S.line_end, &S.hdr, &S.seq, &S.hdr_scan, &S.dst, &S.rec_line}) T_TRY(b->reserve((uint64_t)L + 2, st, false));
+        T_HIP(hipEventRecord(ev_p[3], st));
+        hipLaunchKernelGGL(k_reads_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.text.p, n_groups, S.nl_scan.p, S.line_end.p);
+        T_HIP(hipGetLastError());
+        const unsigned char* d_bytes = reinterpret_cast<const unsigned char*>(S.text.p);
+        hipLaunchKernelGGL(k_reads_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, d_bytes, format, final, L, S.line_end.p, S.hdr.p, S.seq.p, S.misc.p);
+        T_HIP(hipGetLastError());
+        T_TRY(exclusive_scan_u32_u32(S.hdr.p, S.hdr_scan.p, L, st));
+        T_TRY(exclusive_scan_u32_u32(S.seq.p, S.dst.p, L, st));
+        hipLaunchKernelGGL(k_reads_rec_lines, dim3(grid_of((uint64_t)L + 1)), dim3(kBlock), 0, st, L, S.hdr.p, S.hdr_scan.p, S.rec_line.p);
+        T_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_reads_cut, dim3(1), dim3(kWave), 0, st, format, final, L, n_bytes, max_reads, cap_bases, S.line_end.p, S.hdr_scan.p,
+                           S.dst.p, S.rec_line.p, S.misc.p, S.misc.p + 2);
+        T_HIP(hipGetLastError());
+        T_HIP(hipEventRecord(ev_p[4], st));
+        T_HIP(hipMemcpyAsync(h_res, S.misc.p + 2, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        T_HIP(hipStreamSynchronize(st));
+        if (h_res[0] != kReadsNoError) {
+            out->error_record = h_res[0] >> 8; out->error_kind = (int32_t)(h_res[0] & 0xff); out->error_line = h_res[5];
+            set_error("reads text: record %llu (line %llu of this text): %s", (unsigned long long)out->error_record,
+                      (unsigned long long)out->error_line, kind_text(out->error_kind));
+            rc = SFGPU_ERR_FORMAT;
+        } else if (h_res[1] == 0 && h_res[4] > 0 && max_reads > 0) {
+            set_error("sfgpu_reads_parse_host: the first record alone has more than cap_bases = %llu bases", (unsigned long long)cap_bases);
+            rc = SFGPU_ERR_RANGE;
+        } else {
+            // ---- emission
+            const uint32_t R = (uint32_t)h_res[1], n_bases = (uint32_t)h_res[2], Lc = (uint32_t)h_res[6];
+            T_HIP(hipEventRecord(ev_p[5], st));
+            hipLaunchKernelGGL(k_reads_emit, dim3(grid_of((uint64_t)R + 1)), dim3(kBlock), 0, st, d_bytes, R, S.line_end.p, S.dst.p, S.rec_line.p,
+                               d_off, d_name_span);
+            T_HIP(hipGetLastError());
+            if (n_bases) {
+                hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, S.text.p, Lc, n_bases,
+                                   S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
+                T_HIP(hipGetLastError());
+            }
+            out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
+        }
+        T_HIP(hipEventRecord(ev_p[6], st));
+        T_HIP(hipStreamSynchronize(st));
+        {
+            float a = 0.f, b = 0.f, c = 0.f;
+            if (hipEventElapsedTime(&a, ev_p[1], ev_p[2]) == hipSuccess && hipEventElapsedTime(&b, ev_p[3], ev_p[4]) == hipSuccess)
+                out->ms_kernels += (double)a + (double)b;
+            if (rc == SFGPU_OK && hipEventElapsedTime(&c, ev_p[5], ev_p[6]) == hipSuccess) out->ms_kernels += (double)c;
+        }
+    }
+done:
+    if (cs) (void)hipStreamSynchronize(cs);
+    (void)hipStreamSynchronize(st);
+    for (int b = 0; b < 2; ++b) {
+        if (pinned[b]) pinned_free(pinned[b]);
+        for (hipEvent_t e : {ev_h2d[b], ev_copied[b], ev_c0[b], ev_c1[b]}) if (e) (void)hipEventDestroy(e);
+    }
+    for (auto& e : ev_p) if (e) (void)hipEventDestroy(e);
+    if (h_res) pinned_free(h_res);
+    if (cs) stream_release(cs);
+    return rc;
+#undef T_HIP
+#undef T_TRY
+}

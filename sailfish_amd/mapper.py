@@ -27,12 +27,16 @@ class QuasiIndex:
 
     def __init__(self, sequences, k=31, max_occ=1000, device="cuda", seeds=2, seed_len=None):
         """seed_len: None = the library's default (scan mode, seeds of min(19, k) bases, matches extended to maximal length);
-        0 = the end-seed contract (`seeds` exact k-mers per strand); 8 .. k = scan mode with seeds of that length"""
+        0 = the end-seed contract (`seeds` exact k-mers per strand); 8 .. k = scan mode with seeds of that length.
+        sequences: a list of str / bytes, or a (uint8 tensor, int64 offsets) pair already packed (readfile.read_transcripts)"""
         self.device = torch.device(device)
         self._L = _lib.lib()
-        seq, off = pack_sequences(sequences, self.device)
+        if isinstance(sequences, tuple):
+            seq, off = (t.to(self.device) for t in sequences)
+        else:
+            seq, off = pack_sequences(sequences, self.device)
         self.ref_len = (off[1:] - off[:-1]).to(torch.int32).contiguous()
-        self.M = len(sequences)
+        self.M = int(off.numel()) - 1
         self._keep = (seq.contiguous(), off[:-1].contiguous())
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -122,4 +126,51 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
         seq_kw = dict(seq=bytes(s.numpy().tobytes()), seq_off=o[:-1].numpy())
     rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     idx.close()
+    return rc, exp
+
+
+def _dollar_separated(bases, off):
+    """packed transcripts -> (the bytes with a '$' behind every transcript, where each begins): what the bias models take"""
+    b, o = bases.cpu().numpy(), off.cpu().numpy()
+    M, total = len(o) - 1, int(o[-1])
+    out = np.full(total + M, ord("$"), np.uint8)
+    out[np.arange(total) + np.repeat(np.arange(M), np.diff(o))] = b[:total]
+    return out.tobytes(), o[:-1] + np.arange(M)
+
+
+def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
+                   **kw):
+    """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
+    None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
+    batches are mapped and handed to quant.quantify as in quantify_reads.  -> (rc, experiment)"""
+    from . import quant
+    from .readfile import ReadFile, read_transcripts
+    names, (bases, off) = read_transcripts(transcripts_path, device)
+    idx = QuasiIndex((bases, off), k=k, device=device)
+
+    def batches():
+        f1 = ReadFile(reads1_path, device)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device)
+        try:
+            while True:
+                r1 = f1.read(batch_reads)
+                r2 = None if f2 is None else f2.read(batch_reads)
+                n = int(r1[1].numel()) - 1
+                if r2 is not None and int(r2[1].numel()) - 1 != n:
+                    raise ValueError(f"{reads1_path} and {reads2_path} do not hold the same number of records")
+                if n == 0:
+                    break
+                yield idx.map_reads(r1, r2)
+        finally:
+            f1.close()
+            if f2 is not None:
+                f2.close()
+    seq_kw = {}
+    if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
+        s, o = _dollar_separated(bases, off)
+        seq_kw = dict(seq=s, seq_off=o)
+    try:
+        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+    finally:
+        idx.close()
     return rc, exp

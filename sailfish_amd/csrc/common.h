@@ -1,6 +1,7 @@
 // common.h -- shared host-side plumbing of libsfgpu (error slot, HIP checks, logging).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -81,6 +82,74 @@ struct DevBuf {
         return SFGPU_OK;
     }
 };
+
+// What a file-facing call (eqtext.hip, readtext.hip, textchunks.h, ...) borrows for its duration: streams, events and pinned host
+// blocks.  None of them may go back while a copy can still touch a pinned block, so the scope waits for every stream before it
+// gives anything back.  The same holds for the call's device scratch, and that cannot be read off the type: declare the scope
+// AFTER the call's DevBufs, so that it is destroyed, and drains, BEFORE any scratch block returns to the pool (callers free only
+// after the work is synchronised, see pool_malloc).
+struct CallScope {
+    static constexpr int kMaxStreams = 2, kMaxEvents = 15, kMaxPinned = 4;      // the largest users: readtext.hip, textchunks.h
+    CallScope() = default;
+    CallScope(const CallScope&) = delete;
+    CallScope& operator=(const CallScope&) = delete;
+    ~CallScope() {
+        drain();
+        for (int i = 0; i < n_events; ++i) (void)hipEventDestroy(events[i]);
+        for (int i = 0; i < n_pinned; ++i) pinned_free(pinned[i]);
+        for (int i = n_streams; i-- > 0;) if (owned[i]) stream_release(streams[i]);
+    }
+    // a stream of the call's own: drained and released by the scope
+    hipError_t acquire(hipStream_t* s) {
+        if (n_streams == kMaxStreams) return hipErrorOutOfMemory;
+        const hipError_t e = stream_acquire(s);
+        if (e == hipSuccess) { streams[n_streams] = *s; owned[n_streams++] = true; }
+        return e;
+    }
+    // the caller's stream: only drained
+    hipError_t adopt(hipStream_t s) {
+        if (n_streams == kMaxStreams) return hipErrorOutOfMemory;
+        streams[n_streams] = s; owned[n_streams++] = false;
+        return hipSuccess;
+    }
+    hipError_t event(hipEvent_t* ev, unsigned flags = hipEventDefault) {
+        if (n_events == kMaxEvents) return hipErrorOutOfMemory;
+        const hipError_t e = hipEventCreateWithFlags(ev, flags);
+        if (e == hipSuccess) events[n_events++] = *ev;
+        return e;
+    }
+    template <typename T>
+    hipError_t pinned_block(T** p, size_t bytes) {
+        if (n_pinned == kMaxPinned) return hipErrorOutOfMemory;
+        const hipError_t e = pinned_malloc(p, bytes);
+        if (e == hipSuccess) pinned[n_pinned++] = *p;
+        return e;
+    }
+    // waits for every stream, the last one handed out first: every user takes its compute stream, then its copy stream, and the
+    // copy stream is drained before the compute stream
+    void drain() {
+        for (int i = n_streams; i-- > 0;) (void)hipStreamSynchronize(streams[i]);
+    }
+
+private:
+    hipStream_t streams[kMaxStreams];
+    bool owned[kMaxStreams];
+    hipEvent_t events[kMaxEvents];
+    void* pinned[kMaxPinned];
+    int n_streams = 0, n_events = 0, n_pinned = 0;
+};
+
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// *ms += the time from event a to event b; false, and *ms as it was, when the query fails
+inline bool add_elapsed(double* ms, hipEvent_t a, hipEvent_t b) {
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, a, b) != hipSuccess) return false;
+    *ms += (double)t;
+    return true;
+}
 
 // Tuning / experiment switches that lost their A/Bs (profiles/r*_notes.md name each) are read only by builds made with
 // -DSFGPU_VARIANTS (tools/*_variants.sh -> csrc/variants/libsfgpu_<name>.so): the product library neither reads them nor contains the

@@ -4,7 +4,7 @@
 // The host stages the text through a pinned buffer in chunks that end at a '\n' (the next chunk starts behind it); the copy
 // of chunk c + 1 runs while chunk c is parsed and folded.  A chunk is parsed in two passes over 16-byte groups:
 //   pass 1  k_text_count: '\n' and '\t' per group -> two exclusive scans (primitives.h) give every group its line and tab
-//           index; k_text_line_ends writes where each line ends.
+//           index; textlines.h's k_line_ends writes where each line ends.
 //   heads   k_text_line_head: one lane per line reads the leading k (the label length) and checks that the line holds
 //           exactly k + 2 fields; a scan of the k gives rowptr before a single id is parsed.
 //   pass 2  k_text_parse: one lane per group; every field that STARTS in the group is parsed by the lane that owns its
@@ -14,19 +14,18 @@
 // the builder's weighted upsert (sfgpu_eq_add_weighted_device): equal labels add their counts.
 #include "common.h"
 #include "primitives.h"
+#include "textlines.h"
 
-#include <chrono>
 #include <cstring>
 
 namespace sfgpu {
 namespace {
 
-constexpr int kTextBlock = 256;
+using textlines::grid_of;
+constexpr int kTextBlock = textlines::kBlock;
 constexpr uint64_t kTextDefaultChunk = 32ull << 20;      // bytes per staged chunk
 constexpr uint64_t kTextMaxChunk = 1ull << 30;           // lines and ids of one chunk stay far below the builder's u32 limits
 constexpr unsigned long long kNoError = ~0ull;
-
-inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kTextBlock - 1) / kTextBlock); }
 
 struct Masks {
     uint32_t nl, tab, digit;
@@ -62,19 +61,6 @@ __global__ void k_text_count(const uint4* __restrict__ buf, uint64_t n_groups, u
     const Masks m = group_masks(buf[g]);       // (the zero bytes behind the chunk count as neither)
     nl_cnt[g] = __popc(m.nl);
     tab_cnt[g] = __popc(m.tab);
-}
-
-__global__ void k_text_line_ends(const uint4* __restrict__ buf, uint64_t n_groups, const uint32_t* __restrict__ nl_scan,
-                                 uint32_t* __restrict__ line_end) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups) return;
-    uint32_t nl = group_masks(buf[g]).nl;
-    uint32_t at = nl_scan[g];
-    while (nl) {
-        const int i = __ffs(nl) - 1;
-        nl &= nl - 1;
-        line_end[at++] = (uint32_t)(g * 16 + i);
-    }
 }
 
 // one lane per line: k, the field count, and the tab index the line starts at
@@ -182,10 +168,6 @@ struct TextScratch {
     DevBuf<unsigned long long> misc;        // [0] first error, [1] sum of counts
 };
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 }  // namespace sfgpu
 
@@ -211,135 +193,101 @@ extern "C" int sfgpu_eq_add_text_host(sfgpu_eq* eq, const char* h_text, uint64_t
     };
 
     TextScratch S;
+    CallScope scope;        // after S: it drains both streams before S's blocks go back to the pool; nothing is released while a copy still reads the pinned buffers
     hipStream_t st = nullptr, cs = nullptr;
     char* pinned[2] = {nullptr, nullptr};
     hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_h2d[2] = {nullptr, nullptr}, ev_p[4] = {nullptr, nullptr, nullptr, nullptr};
     unsigned long long* h_misc = nullptr;
-    int rc = SFGPU_OK;
     uint64_t line_base = 0;
+    auto fail = [&](int code, uint64_t line, int kind) -> int {
+        out->err_line = line; out->err_kind = kind;
+        set_error("eq_classes text: class line %llu: %s", (unsigned long long)line, kind_text(kind));
+        return code;
+    };
 
-    // every exit below goes through `done`: nothing may be released while a copy still reads the pinned buffers
-#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
-#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
-    {
-        T_HIP(stream_acquire(&st));
-        T_HIP(stream_acquire(&cs));
-        const uint64_t stage_cap = chunk_bytes + 32;
-        for (int b = 0; b < 2; ++b) {
-            T_HIP(pinned_malloc(&pinned[b], stage_cap));
-            T_HIP(hipEventCreateWithFlags(&ev_copied[b], hipEventDefault));
-            T_HIP(hipEventCreateWithFlags(&ev_h2d[b], hipEventDefault));
-        }
-        for (auto& e : ev_p) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-        T_HIP(pinned_malloc(&h_misc, 4 * sizeof(unsigned long long)));
-        T_TRY(S.misc.reserve(2, st, false));
-
-        // host copy into pinned[slot] + its H2D on the copy stream; returns the staged size (a multiple of 16 is read by the kernels)
-        uint64_t staged[2] = {0, 0};
-        auto stage = [&](uint64_t pos, uint64_t end, int slot) -> int {
-            const auto t0 = std::chrono::steady_clock::now();
-            uint64_t n = end - pos;
-            memcpy(pinned[slot], h_text + pos, n);
-            if (h_text[end - 1] != '\n') pinned[slot][n++] = '\n';          // the final line may lack its newline
-            const uint64_t padded = (n + 15) & ~15ull;
-            memset(pinned[slot] + n, 0, padded + 16 - n);
-            out->stage_ms += ms_since(t0);
-            int r;
-            if ((r = S.bytes[slot].reserve(padded / 16 + 1, cs, false))) return r;
-            SF_HIP(hipEventRecord(ev_h2d[slot], cs));
-            SF_HIP(hipMemcpyAsync(S.bytes[slot].p, pinned[slot], padded + 16, hipMemcpyHostToDevice, cs));
-            SF_HIP(hipEventRecord(ev_copied[slot], cs));
-            staged[slot] = n;
-            return SFGPU_OK;
-        };
-
-        uint64_t pos = 0, end = chunk_end(0);
-        int slot = 0;
-        if (end == 0) { out->err_line = 0; out->err_kind = SFGPU_EQTEXT_LONG_LINE; rc = SFGPU_ERR_RANGE; goto fail; }
-        T_TRY(stage(pos, end, slot));
-        while (pos < n_bytes) {
-            const uint64_t n = staged[slot], n_groups = (n + 15) / 16;
-            T_HIP(hipStreamWaitEvent(st, ev_copied[slot], 0));
-            T_TRY(S.nl_cnt.reserve(n_groups + 1, st, false));
-            T_TRY(S.tab_cnt.reserve(n_groups + 1, st, false));
-            T_TRY(S.nl_scan.reserve(n_groups + 1, st, false));
-            T_TRY(S.tab_scan.reserve(n_groups + 1, st, false));
-            T_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
-            T_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
-            T_HIP(hipEventRecord(ev_p[0], st));
-            hipLaunchKernelGGL(k_text_count, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_groups, S.nl_cnt.p, S.tab_cnt.p);
-            T_HIP(hipGetLastError());
-            T_TRY(exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st));
-            T_TRY(exclusive_scan_u32_u32(S.tab_cnt.p, S.tab_scan.p, n_groups, st));
-            T_HIP(hipEventRecord(ev_p[1], st));
-            T_HIP(hipMemcpyAsync(&h_misc[2], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
-            // the next chunk is staged while this one is parsed (its buffers were freed by the previous chunk's synchronisations)
-            const uint64_t npos = end, nend = (npos < n_bytes) ? chunk_end(npos) : npos;
-            if (npos < n_bytes && nend != 0) T_TRY(stage(npos, nend, slot ^ 1));
-            T_HIP(hipStreamSynchronize(st));
-            const uint32_t n_lines = (uint32_t)h_misc[2];
-            T_TRY(S.line_end.reserve((uint64_t)n_lines + 1, st, false));
-            T_TRY(S.lens.reserve((uint64_t)n_lines + 1, st, false));
-            T_TRY(S.rowptr.reserve((uint64_t)n_lines + 1, st, false));
-            T_TRY(S.tab_base.reserve((uint64_t)n_lines + 1, st, false));
-            T_TRY(S.counts.reserve((uint64_t)n_lines + 1, st, false));
-            T_TRY(S.ids.reserve(n / 2 + 1, st, false));
-            T_HIP(hipEventRecord(ev_p[2], st));
-            hipLaunchKernelGGL(k_text_line_ends, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_groups, S.nl_scan.p, S.line_end.p);
-            T_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_text_line_head, dim3(grid_of(n_lines)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_lines, S.line_end.p,
-                               S.tab_scan.p, S.lens.p, S.tab_base.p, S.misc.p);
-            T_HIP(hipGetLastError());
-            T_TRY(exclusive_scan_u32_u32(S.lens.p, S.rowptr.p, n_lines, st));
-            hipLaunchKernelGGL(k_text_parse, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n, n_groups, S.nl_scan.p,
-                               S.tab_scan.p, S.rowptr.p, S.tab_base.p, n_transcripts, S.ids.p, S.counts.p, S.misc.p, S.misc.p + 1);
-            T_HIP(hipGetLastError());
-            T_HIP(hipEventRecord(ev_p[3], st));
-            T_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 16, hipMemcpyDeviceToHost, st));
-            T_HIP(hipMemcpyAsync(&h_misc[2], S.rowptr.p + n_lines, 4, hipMemcpyDeviceToHost, st));
-            T_HIP(hipStreamSynchronize(st));
-            {
-                float a = 0.f, b = 0.f, c = 0.f;
-                if (hipEventElapsedTime(&a, ev_p[0], ev_p[1]) == hipSuccess && hipEventElapsedTime(&b, ev_p[2], ev_p[3]) == hipSuccess)
-                    out->parse_ms += (double)a + (double)b;
-                if (hipEventElapsedTime(&c, ev_h2d[slot], ev_copied[slot]) == hipSuccess) out->h2d_ms += (double)c;
-            }
-            if (h_misc[0] != kNoError) {
-                out->err_line = line_base + (h_misc[0] >> 8);
-                out->err_kind = (int32_t)(h_misc[0] & 0xff);
-                rc = SFGPU_ERR_FORMAT;
-                goto fail;
-            }
-            const uint64_t n_ids = (uint32_t)h_misc[2];
-            {
-                const auto t0 = std::chrono::steady_clock::now();
-                T_TRY(sfgpu_eq_add_weighted_device(eq, S.ids.p, S.rowptr.p, S.counts.p, n_lines));     // returns after the fold has run
-                out->fold_ms += ms_since(t0);
-            }
-            out->n_lines += n_lines; out->n_ids += n_ids; out->sum_counts += h_misc[1]; out->n_chunks++;
-            line_base += n_lines;
-            if (npos < n_bytes && nend == 0) {
-                out->err_line = line_base; out->err_kind = SFGPU_EQTEXT_LONG_LINE; rc = SFGPU_ERR_RANGE; goto fail;
-            }
-            pos = npos; end = nend; slot ^= 1;
-        }
-        goto done;
-    }
-fail:
-    set_error("eq_classes text: class line %llu: %s", (unsigned long long)out->err_line, kind_text(out->err_kind));
-done:
-    if (cs) (void)hipStreamSynchronize(cs);
-    if (st) (void)hipStreamSynchronize(st);
+    SF_HIP(scope.acquire(&st));
+    SF_HIP(scope.acquire(&cs));
+    const uint64_t stage_cap = chunk_bytes + 32;
     for (int b = 0; b < 2; ++b) {
-        if (pinned[b]) pinned_free(pinned[b]);
-        if (ev_copied[b]) (void)hipEventDestroy(ev_copied[b]);
-        if (ev_h2d[b]) (void)hipEventDestroy(ev_h2d[b]);
+        SF_HIP(scope.pinned_block(&pinned[b], stage_cap));
+        SF_HIP(scope.event(&ev_copied[b]));
+        SF_HIP(scope.event(&ev_h2d[b]));
     }
-    for (auto& e : ev_p) if (e) (void)hipEventDestroy(e);
-    if (h_misc) pinned_free(h_misc);
-    if (cs) stream_release(cs);
-    if (st) stream_release(st);
-    return rc;
-#undef T_HIP
-#undef T_TRY
+    for (auto& e : ev_p) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_misc, 4 * sizeof(unsigned long long)));
+    if (int rc = S.misc.reserve(2, st, false)) return rc;
+
+    // host copy into pinned[slot] + its H2D on the copy stream; returns the staged size (a multiple of 16 is read by the kernels)
+    uint64_t staged[2] = {0, 0};
+    auto stage = [&](uint64_t pos, uint64_t end, int slot) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t n = end - pos;
+        memcpy(pinned[slot], h_text + pos, n);
+        if (h_text[end - 1] != '\n') pinned[slot][n++] = '\n';          // the final line may lack its newline
+        const uint64_t padded = (n + 15) & ~15ull;
+        memset(pinned[slot] + n, 0, padded + 16 - n);
+        out->stage_ms += ms_since(t0);
+        if (int rc = S.bytes[slot].reserve(padded / 16 + 1, cs, false)) return rc;
+        SF_HIP(hipEventRecord(ev_h2d[slot], cs));
+        SF_HIP(hipMemcpyAsync(S.bytes[slot].p, pinned[slot], padded + 16, hipMemcpyHostToDevice, cs));
+        SF_HIP(hipEventRecord(ev_copied[slot], cs));
+        staged[slot] = n;
+        return SFGPU_OK;
+    };
+
+    uint64_t pos = 0, end = chunk_end(0);
+    int slot = 0;
+    if (end == 0) return fail(SFGPU_ERR_RANGE, 0, SFGPU_EQTEXT_LONG_LINE);
+    if (int rc = stage(pos, end, slot)) return rc;
+    while (pos < n_bytes) {
+        const uint64_t n = staged[slot], n_groups = (n + 15) / 16;
+        SF_HIP(hipStreamWaitEvent(st, ev_copied[slot], 0));
+        for (DevBuf<uint32_t>* b : {&S.nl_cnt, &S.tab_cnt, &S.nl_scan, &S.tab_scan})
+            if (int rc = b->reserve(n_groups + 1, st, false)) return rc;
+        SF_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
+        SF_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
+        SF_HIP(hipEventRecord(ev_p[0], st));
+        hipLaunchKernelGGL(k_text_count, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_groups, S.nl_cnt.p, S.tab_cnt.p);
+        SF_HIP(hipGetLastError());
+        if (int rc = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return rc;
+        if (int rc = exclusive_scan_u32_u32(S.tab_cnt.p, S.tab_scan.p, n_groups, st)) return rc;
+        SF_HIP(hipEventRecord(ev_p[1], st));
+        SF_HIP(hipMemcpyAsync(&h_misc[2], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+        // the next chunk is staged while this one is parsed (its buffers were freed by the previous chunk's synchronisations)
+        const uint64_t npos = end, nend = (npos < n_bytes) ? chunk_end(npos) : npos;
+        if (npos < n_bytes && nend != 0) if (int rc = stage(npos, nend, slot ^ 1)) return rc;
+        SF_HIP(hipStreamSynchronize(st));
+        const uint32_t n_lines = (uint32_t)h_misc[2];
+        for (DevBuf<uint32_t>* b : {&S.line_end, &S.lens, &S.rowptr, &S.tab_base})
+            if (int rc = b->reserve((uint64_t)n_lines + 1, st, false)) return rc;
+        if (int rc = S.counts.reserve((uint64_t)n_lines + 1, st, false)) return rc;
+        if (int rc = S.ids.reserve(n / 2 + 1, st, false)) return rc;
+        SF_HIP(hipEventRecord(ev_p[2], st));
+        hipLaunchKernelGGL(textlines::k_line_ends, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_groups, S.nl_scan.p, S.line_end.p);
+        SF_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_text_line_head, dim3(grid_of(n_lines)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n_lines, S.line_end.p,
+                           S.tab_scan.p, S.lens.p, S.tab_base.p, S.misc.p);
+        SF_HIP(hipGetLastError());
+        if (int rc = exclusive_scan_u32_u32(S.lens.p, S.rowptr.p, n_lines, st)) return rc;
+        hipLaunchKernelGGL(k_text_parse, dim3(grid_of(n_groups)), dim3(kTextBlock), 0, st, S.bytes[slot].p, n, n_groups, S.nl_scan.p,
+                           S.tab_scan.p, S.rowptr.p, S.tab_base.p, n_transcripts, S.ids.p, S.counts.p, S.misc.p, S.misc.p + 1);
+        SF_HIP(hipGetLastError());
+        SF_HIP(hipEventRecord(ev_p[3], st));
+        SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 16, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipMemcpyAsync(&h_misc[2], S.rowptr.p + n_lines, 4, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipStreamSynchronize(st));
+        double parse = 0.0;                                   // both halves or neither
+        if (add_elapsed(&parse, ev_p[0], ev_p[1]) && add_elapsed(&parse, ev_p[2], ev_p[3])) out->parse_ms += parse;
+        add_elapsed(&out->h2d_ms, ev_h2d[slot], ev_copied[slot]);
+        if (h_misc[0] != kNoError) return fail(SFGPU_ERR_FORMAT, line_base + (h_misc[0] >> 8), (int)(h_misc[0] & 0xff));
+        const uint64_t n_ids = (uint32_t)h_misc[2];
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int rc = sfgpu_eq_add_weighted_device(eq, S.ids.p, S.rowptr.p, S.counts.p, n_lines)) return rc;     // returns after the fold has run
+        out->fold_ms += ms_since(t0);
+        out->n_lines += n_lines; out->n_ids += n_ids; out->sum_counts += h_misc[1]; out->n_chunks++;
+        line_base += n_lines;
+        if (npos < n_bytes && nend == 0) return fail(SFGPU_ERR_RANGE, line_base, SFGPU_EQTEXT_LONG_LINE);
+        pos = npos; end = nend; slot ^= 1;
+    }
+    return SFGPU_OK;
 }

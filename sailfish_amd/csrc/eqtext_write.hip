@@ -155,85 +155,67 @@ extern "C" int sfgpu_eqvec_write_text(const uint32_t* d_rowptr, const uint32_t* 
     SF_REQUIRE(n_classes < kMaxClasses, SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: n_classes must be below 2^32 - 1");
 
     WriteScratch S;
+    CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
     hipStream_t st = nullptr;
     hipEvent_t ev_in = nullptr, ev_s[2] = {nullptr, nullptr};
     unsigned long long* h_misc = nullptr;     // [0 .. 1] misc, [3] total bytes, [4] rowptr[0] and rowptr[n_classes]
-    int rc = SFGPU_OK;
+    SF_HIP(scope.acquire(&st));
+    SF_HIP(scope.event(&ev_in, hipEventDisableTiming));
+    for (auto& e : ev_s) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_misc, 8 * sizeof(unsigned long long)));
+    // behind whatever the caller has queued on `stream`
+    SF_HIP(hipEventRecord(ev_in, as_stream(stream)));
+    SF_HIP(hipStreamWaitEvent(st, ev_in, 0));
 
-    // every exit below goes through `done`
-#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
-#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
-#define T_FAIL(code, msg) do { set_error("%s", msg); rc = (code); goto done; } while (0)
-    {
-        T_HIP(stream_acquire(&st));
-        T_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        for (auto& e : ev_s) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-        T_HIP(pinned_malloc(&h_misc, 8 * sizeof(unsigned long long)));
-        // behind whatever the caller has queued on `stream`
-        T_HIP(hipEventRecord(ev_in, as_stream(stream)));
-        T_HIP(hipStreamWaitEvent(st, ev_in, 0));
+    if (int rc = S.misc.reserve(4, st, false)) return rc;
+    SF_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
+    uint32_t* h_ends = reinterpret_cast<uint32_t*>(&h_misc[4]);
+    SF_HIP(hipMemcpyAsync(&h_ends[0], d_rowptr, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_ends[1], d_rowptr + n_classes, 4, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_check_rowptr, dim3(grid_of(n_classes)), dim3(kBlock), 0, st, d_rowptr, n_classes, S.misc.p);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    SF_REQUIRE(h_ends[0] == 0 && h_misc[0] == 0, SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: rowptr must start at 0 and never decrease");
+    const uint64_t nnz = h_ends[1];
+    SF_REQUIRE(!nnz || d_ids, SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: null ids");
+    const uint64_t n_tok = nnz + 2 * n_classes;
+    const uint64_t tile_cap = (n_tok * kMaxTokBytes >> kTileShift) + 2;
 
-        T_TRY(S.misc.reserve(4, st, false));
-        T_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
-        uint32_t* h_ends = reinterpret_cast<uint32_t*>(&h_misc[4]);
-        T_HIP(hipMemcpyAsync(&h_ends[0], d_rowptr, 4, hipMemcpyDeviceToHost, st));
-        T_HIP(hipMemcpyAsync(&h_ends[1], d_rowptr + n_classes, 4, hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(k_check_rowptr, dim3(grid_of(n_classes)), dim3(kBlock), 0, st, d_rowptr, n_classes, S.misc.p);
-        T_HIP(hipGetLastError());
-        T_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        if (h_ends[0] != 0 || h_misc[0] != 0) T_FAIL(SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: rowptr must start at 0 and never decrease");
-        const uint64_t nnz = h_ends[1];
-        if (nnz && !d_ids) T_FAIL(SFGPU_ERR_INVALID, "sfgpu_eqvec_write_text: null ids");
-        const uint64_t n_tok = nnz + 2 * n_classes;
-        const uint64_t tile_cap = (n_tok * kMaxTokBytes >> kTileShift) + 2;
+    // ---- sizing: token lengths, byte starts, line starts, the tile index, the longest line
+    if (int rc = S.tok_len.reserve(n_tok + 1, st, false)) return rc;
+    if (int rc = S.tok_class.reserve(n_tok, st, false)) return rc;
+    if (int rc = S.tok_start.reserve(n_tok + 1, st, false)) return rc;
+    if (int rc = S.line_start.reserve(n_classes + 1, st, false)) return rc;
+    if (int rc = S.tile_first.reserve(tile_cap, st, false)) return rc;
+    SF_HIP(hipEventRecord(ev_s[0], st));
+    hipLaunchKernelGGL(k_tok_size, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, d_ids, d_counts, n_classes, n_tok,
+                       S.tok_len.p, S.tok_class.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = exclusive_scan_u32(S.tok_len.p, S.tok_start.p, n_tok, st, false)) return rc;
+    hipLaunchKernelGGL(k_tok_place, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, n_classes, n_tok, S.tok_start.p,
+                       S.tok_class.p, S.line_start.p, S.tile_first.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = textchunks::line_max(S.line_start.p, n_classes, S.misc.p + 1, st)) return rc;
+    SF_HIP(hipEventRecord(ev_s[1], st));
+    SF_HIP(hipMemcpyAsync(&h_misc[1], S.misc.p + 1, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_misc[3], S.tok_start.p + n_tok, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&out->format_ms, ev_s[0], ev_s[1]);
+    const uint64_t total = h_misc[3];
+    out->n_bytes = total; out->n_lines = n_classes; out->n_ids = nnz; out->max_line_bytes = h_misc[1];
+    if (!sink) return SFGPU_OK;
+    SF_REQUIRE(out->max_line_bytes <= chunk_bytes, SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: a line is longer than chunk_bytes");
 
-        // ---- sizing: token lengths, byte starts, line starts, the tile index, the longest line
-        T_TRY(S.tok_len.reserve(n_tok + 1, st, false));
-        T_TRY(S.tok_class.reserve(n_tok, st, false));
-        T_TRY(S.tok_start.reserve(n_tok + 1, st, false));
-        T_TRY(S.line_start.reserve(n_classes + 1, st, false));
-        T_TRY(S.tile_first.reserve(tile_cap, st, false));
-        T_HIP(hipEventRecord(ev_s[0], st));
-        hipLaunchKernelGGL(k_tok_size, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, d_ids, d_counts, n_classes, n_tok,
-                           S.tok_len.p, S.tok_class.p);
-        T_HIP(hipGetLastError());
-        T_TRY(exclusive_scan_u32(S.tok_len.p, S.tok_start.p, n_tok, st, false));
-        hipLaunchKernelGGL(k_tok_place, dim3(grid_of(n_tok)), dim3(kBlock), 0, st, d_rowptr, n_classes, n_tok, S.tok_start.p,
-                           S.tok_class.p, S.line_start.p, S.tile_first.p);
-        T_HIP(hipGetLastError());
-        T_TRY(textchunks::line_max(S.line_start.p, n_classes, S.misc.p + 1, st));
-        T_HIP(hipEventRecord(ev_s[1], st));
-        T_HIP(hipMemcpyAsync(&h_misc[1], S.misc.p + 1, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipMemcpyAsync(&h_misc[3], S.tok_start.p + n_tok, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, ev_s[0], ev_s[1]) == hipSuccess) out->format_ms += (double)a;
-        }
-        const uint64_t total = h_misc[3];
-        out->n_bytes = total; out->n_lines = n_classes; out->n_ids = nnz; out->max_line_bytes = h_misc[1];
-        if (!sink) goto done;
-        if (out->max_line_bytes > chunk_bytes) T_FAIL(SFGPU_ERR_RANGE, "sfgpu_eqvec_write_text: a line is longer than chunk_bytes");
-
-        // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this table's tiles
-        textchunks::Stats ts;
-        rc = textchunks::deliver("sfgpu_eqvec_write_text", S.line_start.p, n_classes, total, chunk_bytes, sink, user, st, &ts,
-                                 [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-            hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_rowptr, d_ids, d_counts,
-                               S.tok_start.p, S.tok_class.p, S.tile_first.p, n_tok, total, first_tile, out_base, buf);
-            SF_HIP(hipGetLastError());
-            return SFGPU_OK;
-        });
-        out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
-    }
-done:
-    if (st) (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : {ev_in, ev_s[0], ev_s[1]}) if (e) (void)hipEventDestroy(e);
-    if (h_misc) pinned_free(h_misc);
-    if (st) stream_release(st);
+    // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this table's tiles
+    textchunks::Stats ts;
+    const int rc = textchunks::deliver("sfgpu_eqvec_write_text", S.line_start.p, n_classes, total, chunk_bytes, sink, user, st, &ts,
+                                       [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
+        hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_rowptr, d_ids, d_counts,
+                           S.tok_start.p, S.tok_class.p, S.tile_first.p, n_tok, total, first_tile, out_base, buf);
+        SF_HIP(hipGetLastError());
+        return SFGPU_OK;
+    });
+    out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
     return rc;
-#undef T_HIP
-#undef T_TRY
-#undef T_FAIL
 }

@@ -173,99 +173,86 @@ extern "C" int sfgpu_genes_aggregate(const uint32_t* d_gene_of_row, const uint32
     SF_REQUIRE(n_gene_ids > 0 && n_gene_ids <= 0x100000000ull, SFGPU_ERR_INVALID, "sfgpu_genes_aggregate: n_gene_ids must lie in [1, 2^32] when there are rows");
 
     GeneScratch S;
+    CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
     hipStream_t st = nullptr;
     hipEvent_t ev_in = nullptr, ev_t[2] = {nullptr, nullptr};
     unsigned long long* h_misc = nullptr;     // [0 .. 2] misc, [3] groups
-    int rc = SFGPU_OK;
     const unsigned grid = grid_of(n_rows);
+    SF_HIP(scope.acquire(&st));
+    SF_HIP(scope.event(&ev_in, hipEventDisableTiming));
+    for (auto& e : ev_t) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_misc, 4 * sizeof(unsigned long long)));
+    // behind whatever the caller has queued on `stream`
+    SF_HIP(hipEventRecord(ev_in, as_stream(stream)));
+    SF_HIP(hipStreamWaitEvent(st, ev_in, 0));
 
-#define G_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
-#define G_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
-    {
-        G_HIP(stream_acquire(&st));
-        G_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        for (auto& e : ev_t) G_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-        G_HIP(pinned_malloc(&h_misc, 4 * sizeof(unsigned long long)));
-        // behind whatever the caller has queued on `stream`
-        G_HIP(hipEventRecord(ev_in, as_stream(stream)));
-        G_HIP(hipStreamWaitEvent(st, ev_in, 0));
-
-        G_TRY(S.misc.reserve(4, st, false));
-        if (as_printed) { G_TRY(S.val.reserve(3 * n_rows, st, false)); G_TRY(S.pend.reserve(3 * n_rows, st, false)); }
-        G_TRY(S.key_in.reserve(n_rows, st, false)); G_TRY(S.key_out.reserve(n_rows, st, false));
-        G_TRY(S.row_in.reserve(n_rows, st, false)); G_TRY(S.row_out.reserve(n_rows, st, false));
-        G_TRY(S.head.reserve(n_rows + 1, st, false)); G_TRY(S.grp.reserve(n_rows + 1, st, false));
-        G_TRY(S.opens.reserve(n_rows + 1, st, false)); G_TRY(S.line_of_row.reserve(n_rows + 1, st, false));
-        G_TRY(S.gstart.reserve(n_rows + 1, st, false));
-        G_TRY(S.g_length.reserve(n_rows, st, false)); G_TRY(S.g_col.reserve(3 * n_rows, st, false));
-
-        G_HIP(hipEventRecord(ev_t[0], st));
-        G_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(k_check_ids, dim3(grid), dim3(kBlock), 0, st, d_gene_of_row, n_rows, n_gene_ids, S.misc.p);
-        G_HIP(hipGetLastError());
-        G_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
-        G_HIP(hipStreamSynchronize(st));
-        if (h_misc[0]) { set_error("%s", "sfgpu_genes_aggregate: a gene id is not below n_gene_ids"); rc = SFGPU_ERR_INVALID; goto done; }
-
-        // ---- 1. round to printed
-        const double* eff = d_eff; const double* tpm = d_tpm; const double* num_reads = d_num_reads;
-        if (as_printed) {
-            const Cols3 cols = {{d_eff, d_tpm, d_num_reads}};
-            hipLaunchKernelGGL(k_round, dim3(grid, 3), dim3(kBlock), 0, st, cols, n_rows, S.val.p, S.pend.p, S.misc.p);
-            G_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_round_slow, dim3(grid, 3), dim3(kBlock), 0, st, cols, n_rows, S.val.p, S.pend.p);
-            G_HIP(hipGetLastError());
-            eff = S.val.p; tpm = S.val.p + n_rows; num_reads = S.val.p + 2 * n_rows;
-        }
-        // ---- 2. group: stable sort of (gene id, row)
-        int id_bits = 1;
-        while (id_bits < 32 && (n_gene_ids - 1) >> id_bits) ++id_bits;
-        hipLaunchKernelGGL(k_keys, dim3(grid), dim3(kBlock), 0, st, d_gene_of_row, n_rows, S.key_in.p, S.row_in.p);
-        G_HIP(hipGetLastError());
-        G_TRY(sort_pairs_u64_u32(S.key_in.p, S.key_out.p, S.row_in.p, S.row_out.p, n_rows, st, id_bits, false));
-        // ---- 3. group heads, group starts, the output line of every gene
-        G_HIP(hipMemsetAsync(S.opens.p, 0, (n_rows + 1) * sizeof(uint32_t), st));
-        G_HIP(hipMemsetAsync(S.head.p + n_rows, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(k_heads, dim3(grid), dim3(kBlock), 0, st, S.key_out.p, S.row_out.p, n_rows, S.head.p, S.opens.p);
-        G_HIP(hipGetLastError());
-        G_TRY(exclusive_scan_u32_u32(S.head.p, S.grp.p, n_rows, st));
-        G_TRY(exclusive_scan_u32_u32(S.opens.p, S.line_of_row.p, n_rows, st));
-        hipLaunchKernelGGL(k_group_starts, dim3(grid_of(n_rows + 1)), dim3(kBlock), 0, st, S.head.p, S.grp.p, n_rows, S.gstart.p);
-        G_HIP(hipGetLastError());
-        unsigned long long n_groups = 0;
-        {
-            uint32_t* h_groups = reinterpret_cast<uint32_t*>(&h_misc[3]);
-            G_HIP(hipMemcpyAsync(h_groups, S.grp.p + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            // ---- 4. gather (does not need the count)
-            hipLaunchKernelGGL(k_gather, dim3(grid), dim3(kBlock), 0, st, S.row_out.p, n_rows, d_length, eff, tpm, num_reads, S.g_length.p,
-                               S.g_col.p, S.g_col.p + n_rows, S.g_col.p + 2 * n_rows);
-            G_HIP(hipGetLastError());
-            G_HIP(hipStreamSynchronize(st));
-            n_groups = *h_groups;
-        }
-        if (n_groups == 0 || n_groups > n_rows || n_groups > n_gene_ids) { set_error("%s", "sfgpu_genes_aggregate: the grouping pass lost its count"); rc = SFGPU_ERR_HIP; goto done; }
-        // ---- 5. fold
-        hipLaunchKernelGGL(k_fold, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.gstart.p, (uint64_t)n_groups, S.key_out.p, S.row_out.p,
-                           S.line_of_row.p, S.g_length.p, S.g_col.p, S.g_col.p + n_rows, S.g_col.p + 2 * n_rows, d_gene_id_out, d_length_out,
-                           d_eff_out, d_tpm_out, d_num_reads_out, S.misc.p);
-        G_HIP(hipGetLastError());
-        G_HIP(hipEventRecord(ev_t[1], st));
-        G_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        G_HIP(hipStreamSynchronize(st));
-        {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, ev_t[0], ev_t[1]) == hipSuccess) out->aggregate_ms = (double)a;
-        }
-        out->n_rows = n_rows; out->n_genes = n_groups; out->n_slow = h_misc[1]; out->max_rows_per_gene = h_misc[2];
+    if (int rc = S.misc.reserve(4, st, false)) return rc;
+    if (as_printed) {
+        if (int rc = S.val.reserve(3 * n_rows, st, false)) return rc;
+        if (int rc = S.pend.reserve(3 * n_rows, st, false)) return rc;
     }
-done:
-    if (st) (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : {ev_in, ev_t[0], ev_t[1]}) if (e) (void)hipEventDestroy(e);
-    if (h_misc) pinned_free(h_misc);
-    if (st) stream_release(st);
-    return rc;
-#undef G_HIP
-#undef G_TRY
+    for (DevBuf<uint64_t>* b : {&S.key_in, &S.key_out}) if (int rc = b->reserve(n_rows, st, false)) return rc;
+    for (DevBuf<uint32_t>* b : {&S.row_in, &S.row_out}) if (int rc = b->reserve(n_rows, st, false)) return rc;
+    for (DevBuf<uint32_t>* b : {&S.head, &S.grp, &S.opens, &S.line_of_row, &S.gstart}) if (int rc = b->reserve(n_rows + 1, st, false)) return rc;
+    if (int rc = S.g_length.reserve(n_rows, st, false)) return rc;
+    if (int rc = S.g_col.reserve(3 * n_rows, st, false)) return rc;
+
+    SF_HIP(hipEventRecord(ev_t[0], st));
+    SF_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_check_ids, dim3(grid), dim3(kBlock), 0, st, d_gene_of_row, n_rows, n_gene_ids, S.misc.p);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    SF_REQUIRE(!h_misc[0], SFGPU_ERR_INVALID, "sfgpu_genes_aggregate: a gene id is not below n_gene_ids");
+
+    // ---- 1. round to printed
+    const double* eff = d_eff; const double* tpm = d_tpm; const double* num_reads = d_num_reads;
+    if (as_printed) {
+        const Cols3 cols = {{d_eff, d_tpm, d_num_reads}};
+        hipLaunchKernelGGL(k_round, dim3(grid, 3), dim3(kBlock), 0, st, cols, n_rows, S.val.p, S.pend.p, S.misc.p);
+        SF_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_round_slow, dim3(grid, 3), dim3(kBlock), 0, st, cols, n_rows, S.val.p, S.pend.p);
+        SF_HIP(hipGetLastError());
+        eff = S.val.p; tpm = S.val.p + n_rows; num_reads = S.val.p + 2 * n_rows;
+    }
+    // ---- 2. group: stable sort of (gene id, row)
+    int id_bits = 1;
+    while (id_bits < 32 && (n_gene_ids - 1) >> id_bits) ++id_bits;
+    hipLaunchKernelGGL(k_keys, dim3(grid), dim3(kBlock), 0, st, d_gene_of_row, n_rows, S.key_in.p, S.row_in.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = sort_pairs_u64_u32(S.key_in.p, S.key_out.p, S.row_in.p, S.row_out.p, n_rows, st, id_bits, false)) return rc;
+    // ---- 3. group heads, group starts, the output line of every gene
+    SF_HIP(hipMemsetAsync(S.opens.p, 0, (n_rows + 1) * sizeof(uint32_t), st));
+    SF_HIP(hipMemsetAsync(S.head.p + n_rows, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_heads, dim3(grid), dim3(kBlock), 0, st, S.key_out.p, S.row_out.p, n_rows, S.head.p, S.opens.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = exclusive_scan_u32_u32(S.head.p, S.grp.p, n_rows, st)) return rc;
+    if (int rc = exclusive_scan_u32_u32(S.opens.p, S.line_of_row.p, n_rows, st)) return rc;
+    hipLaunchKernelGGL(k_group_starts, dim3(grid_of(n_rows + 1)), dim3(kBlock), 0, st, S.head.p, S.grp.p, n_rows, S.gstart.p);
+    SF_HIP(hipGetLastError());
+    unsigned long long n_groups = 0;
+    {
+        uint32_t* h_groups = reinterpret_cast<uint32_t*>(&h_misc[3]);
+        SF_HIP(hipMemcpyAsync(h_groups, S.grp.p + n_rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        // ---- 4. gather (does not need the count)
+        hipLaunchKernelGGL(k_gather, dim3(grid), dim3(kBlock), 0, st, S.row_out.p, n_rows, d_length, eff, tpm, num_reads, S.g_length.p,
+                           S.g_col.p, S.g_col.p + n_rows, S.g_col.p + 2 * n_rows);
+        SF_HIP(hipGetLastError());
+        SF_HIP(hipStreamSynchronize(st));
+        n_groups = *h_groups;
+    }
+    SF_REQUIRE(n_groups > 0 && n_groups <= n_rows && n_groups <= n_gene_ids, SFGPU_ERR_HIP, "sfgpu_genes_aggregate: the grouping pass lost its count");
+    // ---- 5. fold
+    hipLaunchKernelGGL(k_fold, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.gstart.p, (uint64_t)n_groups, S.key_out.p, S.row_out.p,
+                       S.line_of_row.p, S.g_length.p, S.g_col.p, S.g_col.p + n_rows, S.g_col.p + 2 * n_rows, d_gene_id_out, d_length_out,
+                       d_eff_out, d_tpm_out, d_num_reads_out, S.misc.p);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipEventRecord(ev_t[1], st));
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&out->aggregate_ms, ev_t[0], ev_t[1]);
+    out->n_rows = n_rows; out->n_genes = n_groups; out->n_slow = h_misc[1]; out->max_rows_per_gene = h_misc[2];
+    return SFGPU_OK;
 }
 
 extern "C" int sfgpu_genes_write_text(const char* d_names, const uint64_t* d_name_off, uint64_t n_gene_ids, const uint32_t* d_gene_id,

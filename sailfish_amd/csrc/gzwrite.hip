@@ -23,7 +23,6 @@
 #include "gzfmt.h"
 #include "primitives.h"
 
-#include <chrono>
 #include <cstring>
 #include <new>
 
@@ -265,10 +264,6 @@ k_gz_compact(const uint8_t* __restrict__ slots, const uint64_t* __restrict__ blk
         dw[k] = head ? (sw[k] >> sh) | (sw[k + 1] << (32u - sh)) : sw[k];
 }
 
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 }  // namespace sfgpu
 
@@ -291,24 +286,14 @@ struct sfgpu_gz {
     DevBuf<uint32_t> blk_len, blk_meta;
     DevBuf<uint64_t> blk_off;
     DevBuf<uint8_t> out[2];
+    CallScope scope;                                    // streams, events, h_meta, h_total; last, so that it drains before the DevBufs go
+    ~sfgpu_gz() {
+        scope.drain();
+        for (char* p : pinned) if (p) pinned_free(p);   // the staging buffers grow between writes: not the scope's
+    }
 };
 
 namespace {
-
-void gz_free(sfgpu_gz* z) {
-    if (z->cs) (void)hipStreamSynchronize(z->cs);
-    if (z->st) (void)hipStreamSynchronize(z->st);
-    for (int b = 0; b < 2; ++b) {
-        if (z->pinned[b]) pinned_free(z->pinned[b]);
-        for (hipEvent_t e : {z->ev_c0[b], z->ev_c1[b]}) if (e) (void)hipEventDestroy(e);
-    }
-    for (hipEvent_t e : {z->ev_in, z->ev_e0, z->ev_e1}) if (e) (void)hipEventDestroy(e);
-    if (z->h_meta) pinned_free(z->h_meta);
-    if (z->h_total) pinned_free(z->h_total);
-    if (z->cs) stream_release(z->cs);
-    if (z->st) stream_release(z->st);
-    delete z;
-}
 
 int gz_sink(sfgpu_gz* z, const char* bytes, uint64_t n, const char* who) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -325,17 +310,12 @@ int gz_sink(sfgpu_gz* z, const char* bytes, uint64_t n, const char* who) {
 }
 
 int gz_open_impl(sfgpu_gz* z) {
-    SF_HIP(stream_acquire(&z->st));
-    SF_HIP(stream_acquire(&z->cs));
-    SF_HIP(hipEventCreateWithFlags(&z->ev_in, hipEventDisableTiming));
-    SF_HIP(hipEventCreateWithFlags(&z->ev_e0, hipEventDefault));
-    SF_HIP(hipEventCreateWithFlags(&z->ev_e1, hipEventDefault));
-    for (int b = 0; b < 2; ++b) {
-        SF_HIP(hipEventCreateWithFlags(&z->ev_c0[b], hipEventDefault));
-        SF_HIP(hipEventCreateWithFlags(&z->ev_c1[b], hipEventDefault));
-    }
-    SF_HIP(pinned_malloc(&z->h_meta, 2 * kBatchBlocks * sizeof(uint32_t)));
-    SF_HIP(pinned_malloc(&z->h_total, sizeof(uint64_t)));
+    SF_HIP(z->scope.acquire(&z->st));
+    SF_HIP(z->scope.acquire(&z->cs));
+    SF_HIP(z->scope.event(&z->ev_in, hipEventDisableTiming));
+    for (hipEvent_t* e : {&z->ev_e0, &z->ev_e1, &z->ev_c0[0], &z->ev_c1[0], &z->ev_c0[1], &z->ev_c1[1]}) SF_HIP(z->scope.event(e));
+    SF_HIP(z->scope.pinned_block(&z->h_meta, 2 * kBatchBlocks * sizeof(uint32_t)));
+    SF_HIP(z->scope.pinned_block(&z->h_total, sizeof(uint64_t)));
     uint8_t head[kGzHeaderBytes];
     gz_header(head);
     return gz_sink(z, reinterpret_cast<const char*>(head), kGzHeaderBytes, "sfgpu_gz_open");
@@ -399,10 +379,7 @@ int gz_write_impl(sfgpu_gz* z, const uint8_t* d_src, uint64_t n_bytes, sfgpu_str
     for (uint64_t i = 0; i < n_batches; ++i) {
         const uint32_t nb = batch_blocks(i);
         SF_HIP(hipStreamSynchronize(st));               // batch i is encoded, its sizes and CRCs are here
-        {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, z->ev_e0, z->ev_e1) == hipSuccess) z->res.encode_ms += (double)a;
-        }
+        add_elapsed(&z->res.encode_ms, z->ev_e0, z->ev_e1);
         const uint64_t total = *z->h_total;
         for (uint32_t b = 0; b < nb; ++b) {
             const uint64_t at = (i * kBatchBlocks + b) * (uint64_t)kGzBlockBytes;
@@ -419,10 +396,7 @@ int gz_write_impl(sfgpu_gz* z, const uint8_t* d_src, uint64_t n_bytes, sfgpu_str
             const uint64_t len = total - off < chunk ? total - off : chunk, next = off + len;
             if (next < total) if (int rc = copy_piece(pb ^ 1, d_out + next, total - next < chunk ? total - next : chunk)) return rc;
             SF_HIP(hipEventSynchronize(z->ev_c1[pb]));
-            {
-                float a = 0.f;
-                if (hipEventElapsedTime(&a, z->ev_c0[pb], z->ev_c1[pb]) == hipSuccess) z->res.d2h_ms += (double)a;
-            }
+            add_elapsed(&z->res.d2h_ms, z->ev_c0[pb], z->ev_c1[pb]);
             if (int rc = gz_sink(z, z->pinned[pb], len, "sfgpu_gz_write_device")) return rc;
             off = next; pb ^= 1;
         }
@@ -443,7 +417,7 @@ extern "C" int sfgpu_gz_open(sfgpu_gz** out, sfgpu_text_sink sink, void* user, u
     SF_REQUIRE(z, SFGPU_ERR_HIP, "sfgpu_gz_open: out of host memory");
     z->sink = sink; z->user = user; z->chunk_bytes = chunk_bytes;
     const int rc = gz_open_impl(z);
-    if (rc != SFGPU_OK) { gz_free(z); return rc; }
+    if (rc != SFGPU_OK) { delete z; return rc; }
     *out = z;
     return SFGPU_OK;
 }
@@ -456,8 +430,7 @@ extern "C" int sfgpu_gz_write_device(sfgpu_gz* z, const void* d_src, uint64_t n_
     const int rc = gz_write_impl(z, static_cast<const uint8_t*>(d_src), n_bytes, stream);
     if (rc != SFGPU_OK) {
         z->broken = true;                               // nothing may stay in flight behind a failed write
-        (void)hipStreamSynchronize(z->cs);
-        (void)hipStreamSynchronize(z->st);
+        z->scope.drain();
     }
     return rc;
 }
@@ -471,6 +444,6 @@ extern "C" int sfgpu_gz_close(sfgpu_gz* z, sfgpu_gz_result* res) {
         rc = gz_sink(z, reinterpret_cast<const char*>(tail), sizeof(tail), "sfgpu_gz_close");
     }
     if (res) *res = z->res;
-    gz_free(z);
+    delete z;
     return rc;
 }

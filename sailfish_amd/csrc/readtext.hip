@@ -4,7 +4,7 @@
 // The host text goes through two pinned buffers in sub-chunks of kSubBytes; the copy of sub-chunk c + 1 runs on the copy stream
 // while the '\n' bytes of sub-chunk c are counted.  A '\n' is appended behind the text, so the remainder (readfmt.h) is a line of
 // the device text like any other and L = the number of '\n' bytes on the device.  Then, over the whole text:
-//   k_reads_line_ends   scan of the counts -> where every line ends
+//   k_line_ends         scan of the counts -> where every line ends (textlines.h)
 //   k_reads_lines       one lane per line: rf_line -> header flag, bases of the line, the FASTQ checks (atomic min over
 //                       (record << 8 | kind)) and the last non-empty line (atomic max)
 //   two scans           header flags -> the record of every line; bases per line -> where the line's bases go (dst)
@@ -17,41 +17,21 @@
 #include "common.h"
 #include "primitives.h"
 #include "readfmt.h"
+#include "textlines.h"
 
 namespace sfgpu {
 namespace {
 
-constexpr int kBlock = 256;
+using textlines::kBlock;
+using textlines::grid_of;
+using textlines::nl_mask;
 constexpr uint64_t kSubBytes = 4ull << 20;               // staged sub-chunk (a multiple of 16)
 constexpr uint32_t kTileBytes = 4096;                    // kBlock lanes x one 16-byte store
-
-inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-
-__device__ inline uint32_t nl_mask(const uint4 v) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) m |= (uint32_t)(((w[i >> 2] >> (8 * (i & 3))) & 0xffu) == '\n') << i;
-    return m;
-}
 
 __global__ void k_reads_count(const uint4* __restrict__ buf, uint64_t g0, uint64_t g1, uint32_t* __restrict__ nl_cnt) {
     const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= g1) return;
     nl_cnt[g] = __popc(nl_mask(buf[g]));
-}
-
-__global__ void k_reads_line_ends(const uint4* __restrict__ buf, uint64_t n_groups, const uint32_t* __restrict__ nl_scan,
-                                  uint32_t* __restrict__ line_end) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups) return;
-    uint32_t nl = nl_mask(buf[g]);
-    uint32_t at = nl_scan[g];
-    while (nl) {
-        const int i = __ffs(nl) - 1;
-        nl &= nl - 1;
-        line_end[at++] = (uint32_t)(g * 16 + i);
-    }
 }
 
 struct Bounds {
@@ -234,137 +214,119 @@ extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int 
     const uint64_t n1 = n_bytes + 1, n_groups = (n1 + 15) / 16;
     const uint64_t n_sub = (n_bytes + kSubBytes - 1) / kSubBytes;
     ReadScratch S;
+    CallScope scope;        // after S: it drains both streams before S's blocks go back to the pool; nothing is released while a copy still reads the pinned buffers
     hipStream_t cs = nullptr;
     char* pinned[2] = {nullptr, nullptr};
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
     hipEvent_t ev_p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     unsigned long long* h_res = nullptr;
     bool in_flight[2] = {false, false};
+
+    // a slot's times are read when the slot is taken again, and at the end
+    auto collect = [&](int slot) {
+        if (!in_flight[slot]) return;
+        (void)hipEventSynchronize(ev_c1[slot]);
+        add_elapsed(&out->ms_copy, ev_h2d[slot], ev_copied[slot]);
+        add_elapsed(&out->ms_kernels, ev_c0[slot], ev_c1[slot]);
+        in_flight[slot] = false;
+    };
+    SF_HIP(scope.adopt(st));
+    SF_HIP(scope.acquire(&cs));
+    for (int b = 0; b < 2 && (uint64_t)b < n_sub; ++b) {
+        SF_HIP(scope.pinned_block(&pinned[b], (n_bytes < kSubBytes ? n_bytes : kSubBytes) + 48));
+        for (hipEvent_t* e : {&ev_h2d[b], &ev_copied[b], &ev_c0[b], &ev_c1[b]}) SF_HIP(scope.event(e));
+    }
+    for (auto& e : ev_p) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_res, 8 * sizeof(unsigned long long)));
+    if (int r = S.text.reserve(n_groups + 1, st, false)) return r;
+    if (int r = S.nl_cnt.reserve(n_groups + 1, st, false)) return r;
+    if (int r = S.nl_scan.reserve(n_groups + 1, st, false)) return r;
+    if (int r = S.misc.reserve(16, st, false)) return r;
+    SF_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
+    SF_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
+    SF_HIP(hipEventRecord(ev_p[0], st));
+    SF_HIP(hipStreamWaitEvent(cs, ev_p[0], 0));          // the copies stay behind whatever `stream` held and behind the reservations
+
+    // ---- staged copy; the newlines of sub-chunk c are counted while sub-chunk c + 1 is copied
+    for (uint64_t c = 0; c < n_sub; ++c) {
+        const int slot = (int)(c & 1);
+        collect(slot);                                   // its previous copy has left the pinned buffer
+        const uint64_t p = c * kSubBytes, q = (c + 1 == n_sub) ? n_bytes : p + kSubBytes;
+        uint64_t m = q - p;
+        memcpy(pinned[slot], h_text + p, m);
+        if (c + 1 == n_sub) {
+            pinned[slot][m++] = '\n';
+            const uint64_t padded = ((m + 15) & ~15ull) + 16;
+            memset(pinned[slot] + m, 0, padded - m);
+            m = padded;
+        }
+        SF_HIP(hipEventRecord(ev_h2d[slot], cs));
+        SF_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.text.p) + p, pinned[slot], m, hipMemcpyHostToDevice, cs));
+        SF_HIP(hipEventRecord(ev_copied[slot], cs));
+        const uint64_t g0 = p / 16, g1 = (c + 1 == n_sub) ? n_groups : q / 16;
+        SF_HIP(hipStreamWaitEvent(st, ev_copied[slot], 0));
+        SF_HIP(hipEventRecord(ev_c0[slot], st));
+        hipLaunchKernelGGL(k_reads_count, dim3(grid_of(g1 - g0)), dim3(kBlock), 0, st, S.text.p, g0, g1, S.nl_cnt.p);
+        SF_HIP(hipGetLastError());
+        SF_HIP(hipEventRecord(ev_c1[slot], st));
+        in_flight[slot] = true;
+    }
+
+    // ---- lines
+    SF_HIP(hipEventRecord(ev_p[1], st));
+    if (int r = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return r;
+    SF_HIP(hipEventRecord(ev_p[2], st));
+    SF_HIP(hipMemcpyAsync(&h_res[7], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    collect(0); collect(1);
+    const uint32_t L = (uint32_t)h_res[7];                // >= 1: the appended '\n'
+    out->n_lines = (uint64_t)L - 1 + (uint64_t)final;
+    for (DevBuf<uint32_t>* b : {&S.line_end, &S.hdr, &S.seq, &S.hdr_scan, &S.dst, &S.rec_line})
+        if (int r = b->reserve((uint64_t)L + 2, st, false)) return r;
+    SF_HIP(hipEventRecord(ev_p[3], st));
+    hipLaunchKernelGGL(textlines::k_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.text.p, n_groups, S.nl_scan.p, S.line_end.p);
+    SF_HIP(hipGetLastError());
+    const unsigned char* d_bytes = reinterpret_cast<const unsigned char*>(S.text.p);
+    hipLaunchKernelGGL(k_reads_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, d_bytes, format, final, L, S.line_end.p, S.hdr.p, S.seq.p, S.misc.p);
+    SF_HIP(hipGetLastError());
+    if (int r = exclusive_scan_u32_u32(S.hdr.p, S.hdr_scan.p, L, st)) return r;
+    if (int r = exclusive_scan_u32_u32(S.seq.p, S.dst.p, L, st)) return r;
+    hipLaunchKernelGGL(k_reads_rec_lines, dim3(grid_of((uint64_t)L + 1)), dim3(kBlock), 0, st, L, S.hdr.p, S.hdr_scan.p, S.rec_line.p);
+    SF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_reads_cut, dim3(1), dim3(kWave), 0, st, format, final, L, n_bytes, max_reads, cap_bases, S.line_end.p, S.hdr_scan.p,
+                       S.dst.p, S.rec_line.p, S.misc.p, S.misc.p + 2);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipEventRecord(ev_p[4], st));
+    SF_HIP(hipMemcpyAsync(h_res, S.misc.p + 2, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    // a format error and the cap_bases range error do not leave at once: the kernel times below are still reported
     int rc = SFGPU_OK;
-    uint32_t L = 0;
-
-    // every exit below goes through `done`: nothing may be released while a copy still reads the pinned buffers
-#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
-#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
-    {
-        // a slot's times are read when the slot is taken again, and at the end
-        auto collect = [&](int slot) {
-            if (!in_flight[slot]) return;
-            (void)hipEventSynchronize(ev_c1[slot]);
-            float a = 0.f, b = 0.f;
-            if (hipEventElapsedTime(&a, ev_h2d[slot], ev_copied[slot]) == hipSuccess) out->ms_copy += (double)a;
-            if (hipEventElapsedTime(&b, ev_c0[slot], ev_c1[slot]) == hipSuccess) out->ms_kernels += (double)b;
-            in_flight[slot] = false;
-        };
-        T_HIP(stream_acquire(&cs));
-        for (int b = 0; b < 2 && (uint64_t)b < n_sub; ++b) {
-            T_HIP(pinned_malloc(&pinned[b], (n_bytes < kSubBytes ? n_bytes : kSubBytes) + 48));
-            for (hipEvent_t* e : {&ev_h2d[b], &ev_copied[b], &ev_c0[b], &ev_c1[b]}) T_HIP(hipEventCreateWithFlags(e, hipEventDefault));
+    if (h_res[0] != kReadsNoError) {
+        out->error_record = h_res[0] >> 8; out->error_kind = (int32_t)(h_res[0] & 0xff); out->error_line = h_res[5];
+        set_error("reads text: record %llu (line %llu of this text): %s", (unsigned long long)out->error_record,
+                  (unsigned long long)out->error_line, kind_text(out->error_kind));
+        rc = SFGPU_ERR_FORMAT;
+    } else if (h_res[1] == 0 && h_res[4] > 0 && max_reads > 0) {
+        set_error("sfgpu_reads_parse_host: the first record alone has more than cap_bases = %llu bases", (unsigned long long)cap_bases);
+        rc = SFGPU_ERR_RANGE;
+    } else {
+        // ---- emission
+        const uint32_t R = (uint32_t)h_res[1], n_bases = (uint32_t)h_res[2], Lc = (uint32_t)h_res[6];
+        SF_HIP(hipEventRecord(ev_p[5], st));
+        hipLaunchKernelGGL(k_reads_emit, dim3(grid_of((uint64_t)R + 1)), dim3(kBlock), 0, st, d_bytes, R, S.line_end.p, S.dst.p, S.rec_line.p,
+                           d_off, d_name_span);
+        SF_HIP(hipGetLastError());
+        if (n_bases) {
+            hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, S.text.p, Lc, n_bases,
+                               S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
+            SF_HIP(hipGetLastError());
         }
-        for (auto& e : ev_p) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-        T_HIP(pinned_malloc(&h_res, 8 * sizeof(unsigned long long)));
-        T_TRY(S.text.reserve(n_groups + 1, st, false));
-        T_TRY(S.nl_cnt.reserve(n_groups + 1, st, false));
-        T_TRY(S.nl_scan.reserve(n_groups + 1, st, false));
-        T_TRY(S.misc.reserve(16, st, false));
-        T_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
-        T_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
-        T_HIP(hipEventRecord(ev_p[0], st));
-        T_HIP(hipStreamWaitEvent(cs, ev_p[0], 0));          // the copies stay behind whatever `stream` held and behind the reservations
-
-        // ---- staged copy; the newlines of sub-chunk c are counted while sub-chunk c + 1 is copied
-        for (uint64_t c = 0; c < n_sub; ++c) {
-            const int slot = (int)(c & 1);
-            collect(slot);                                   // its previous copy has left the pinned buffer
-            const uint64_t p = c * kSubBytes, q = (c + 1 == n_sub) ? n_bytes : p + kSubBytes;
-            uint64_t m = q - p;
-            memcpy(pinned[slot], h_text + p, m);
-            if (c + 1 == n_sub) {
-                pinned[slot][m++] = '\n';
-                const uint64_t padded = ((m + 15) & ~15ull) + 16;
-                memset(pinned[slot] + m, 0, padded - m);
-                m = padded;
-            }
-            T_HIP(hipEventRecord(ev_h2d[slot], cs));
-            T_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.text.p) + p, pinned[slot], m, hipMemcpyHostToDevice, cs));
-            T_HIP(hipEventRecord(ev_copied[slot], cs));
-            const uint64_t g0 = p / 16, g1 = (c + 1 == n_sub) ? n_groups : q / 16;
-            T_HIP(hipStreamWaitEvent(st, ev_copied[slot], 0));
-            T_HIP(hipEventRecord(ev_c0[slot], st));
-            hipLaunchKernelGGL(k_reads_count, dim3(grid_of(g1 - g0)), dim3(kBlock), 0, st, S.text.p, g0, g1, S.nl_cnt.p);
-            T_HIP(hipGetLastError());
-            T_HIP(hipEventRecord(ev_c1[slot], st));
-            in_flight[slot] = true;
-        }
-
-        // ---- lines
-        T_HIP(hipEventRecord(ev_p[1], st));
-        T_TRY(exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st));
-        T_HIP(hipEventRecord(ev_p[2], st));
-        T_HIP(hipMemcpyAsync(&h_res[7], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        collect(0); collect(1);
-        L = (uint32_t)h_res[7];                               // >= 1: the appended '\n'
-        out->n_lines = (uint64_t)L - 1 + (uint64_t)final;
-        for (DevBuf<uint32_t>* b : {&S.line_end, &S.hdr, &S.seq, &S.hdr_scan, &S.dst, &S.rec_line}) T_TRY(b->reserve((uint64_t)L + 2, st, false));
-        T_HIP(hipEventRecord(ev_p[3], st));
-        hipLaunchKernelGGL(k_reads_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.text.p, n_groups, S.nl_scan.p, S.line_end.p);
-        T_HIP(hipGetLastError());
-        const unsigned char* d_bytes = reinterpret_cast<const unsigned char*>(S.text.p);
-        hipLaunchKernelGGL(k_reads_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, d_bytes, format, final, L, S.line_end.p, S.hdr.p, S.seq.p, S.misc.p);
-        T_HIP(hipGetLastError());
-        T_TRY(exclusive_scan_u32_u32(S.hdr.p, S.hdr_scan.p, L, st));
-        T_TRY(exclusive_scan_u32_u32(S.seq.p, S.dst.p, L, st));
-        hipLaunchKernelGGL(k_reads_rec_lines, dim3(grid_of((uint64_t)L + 1)), dim3(kBlock), 0, st, L, S.hdr.p, S.hdr_scan.p, S.rec_line.p);
-        T_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_reads_cut, dim3(1), dim3(kWave), 0, st, format, final, L, n_bytes, max_reads, cap_bases, S.line_end.p, S.hdr_scan.p,
-                           S.dst.p, S.rec_line.p, S.misc.p, S.misc.p + 2);
-        T_HIP(hipGetLastError());
-        T_HIP(hipEventRecord(ev_p[4], st));
-        T_HIP(hipMemcpyAsync(h_res, S.misc.p + 2, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        if (h_res[0] != kReadsNoError) {
-            out->error_record = h_res[0] >> 8; out->error_kind = (int32_t)(h_res[0] & 0xff); out->error_line = h_res[5];
-            set_error("reads text: record %llu (line %llu of this text): %s", (unsigned long long)out->error_record,
-                      (unsigned long long)out->error_line, kind_text(out->error_kind));
-            rc = SFGPU_ERR_FORMAT;
-        } else if (h_res[1] == 0 && h_res[4] > 0 && max_reads > 0) {
-            set_error("sfgpu_reads_parse_host: the first record alone has more than cap_bases = %llu bases", (unsigned long long)cap_bases);
-            rc = SFGPU_ERR_RANGE;
-        } else {
-            // ---- emission
-            const uint32_t R = (uint32_t)h_res[1], n_bases = (uint32_t)h_res[2], Lc = (uint32_t)h_res[6];
-            T_HIP(hipEventRecord(ev_p[5], st));
-            hipLaunchKernelGGL(k_reads_emit, dim3(grid_of((uint64_t)R + 1)), dim3(kBlock), 0, st, d_bytes, R, S.line_end.p, S.dst.p, S.rec_line.p,
-                               d_off, d_name_span);
-            T_HIP(hipGetLastError());
-            if (n_bases) {
-                hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, S.text.p, Lc, n_bases,
-                                   S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
-                T_HIP(hipGetLastError());
-            }
-            out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
-        }
-        T_HIP(hipEventRecord(ev_p[6], st));
-        T_HIP(hipStreamSynchronize(st));
-        {
-            float a = 0.f, b = 0.f, c = 0.f;
-            if (hipEventElapsedTime(&a, ev_p[1], ev_p[2]) == hipSuccess && hipEventElapsedTime(&b, ev_p[3], ev_p[4]) == hipSuccess)
-                out->ms_kernels += (double)a + (double)b;
-            if (rc == SFGPU_OK && hipEventElapsedTime(&c, ev_p[5], ev_p[6]) == hipSuccess) out->ms_kernels += (double)c;
-        }
+        out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
     }
-done:
-    if (cs) (void)hipStreamSynchronize(cs);
-    (void)hipStreamSynchronize(st);
-    for (int b = 0; b < 2; ++b) {
-        if (pinned[b]) pinned_free(pinned[b]);
-        for (hipEvent_t e : {ev_h2d[b], ev_copied[b], ev_c0[b], ev_c1[b]}) if (e) (void)hipEventDestroy(e);
-    }
-    for (auto& e : ev_p) if (e) (void)hipEventDestroy(e);
-    if (h_res) pinned_free(h_res);
-    if (cs) stream_release(cs);
+    SF_HIP(hipEventRecord(ev_p[6], st));
+    SF_HIP(hipStreamSynchronize(st));
+    double lines = 0.0;                                   // both halves or neither
+    if (add_elapsed(&lines, ev_p[1], ev_p[2]) && add_elapsed(&lines, ev_p[3], ev_p[4])) out->ms_kernels += lines;
+    if (rc == SFGPU_OK) add_elapsed(&out->ms_kernels, ev_p[5], ev_p[6]);
     return rc;
-#undef T_HIP
-#undef T_TRY
 }

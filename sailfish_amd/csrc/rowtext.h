@@ -200,90 +200,73 @@ template <bool kGene>
 int write_rows(const char* who, const char* d_names, const uint64_t* d_name_off, uint64_t n_names, const uint32_t* d_first, Cols cols,
                uint64_t n_rows, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user, sfgpu_quant_write_result* out, sfgpu_stream stream) {
     Scratch S;
+    CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
     hipStream_t st = nullptr;
     hipEvent_t ev_in = nullptr, ev_s[2] = {nullptr, nullptr};
     unsigned long long* h_misc = nullptr;     // [0 .. 3] misc, [4] total bytes, [5] name_off[0], [6] name_off[n_names]
-    int rc = SFGPU_OK;
     constexpr int kCols = n_cols<kGene>();
+    auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
+    SF_HIP(scope.acquire(&st));
+    SF_HIP(scope.event(&ev_in, hipEventDisableTiming));
+    for (auto& e : ev_s) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_misc, 8 * sizeof(unsigned long long)));
+    // behind whatever the caller has queued on `stream`
+    SF_HIP(hipEventRecord(ev_in, as_stream(stream)));
+    SF_HIP(hipStreamWaitEvent(st, ev_in, 0));
 
-    // every exit below goes through `done`
-#define T_HIP(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); rc = SFGPU_ERR_HIP; goto done; } } while (0)
-#define T_TRY(expr) do { if ((rc = (expr)) != SFGPU_OK) goto done; } while (0)
-#define T_FAIL(code, msg) do { set_error("%s: %s", who, msg); rc = (code); goto done; } while (0)
-    {
-        T_HIP(stream_acquire(&st));
-        T_HIP(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-        for (auto& e : ev_s) T_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-        T_HIP(pinned_malloc(&h_misc, 8 * sizeof(unsigned long long)));
-        // behind whatever the caller has queued on `stream`
-        T_HIP(hipEventRecord(ev_in, as_stream(stream)));
-        T_HIP(hipStreamWaitEvent(st, ev_in, 0));
-
-        T_TRY(S.misc.reserve(4, st, false));
-        T_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
-        T_HIP(hipMemcpyAsync(&h_misc[5], d_name_off, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipMemcpyAsync(&h_misc[6], d_name_off + n_names, 8, hipMemcpyDeviceToHost, st));
-        if (n_names) {
-            hipLaunchKernelGGL(k_check_off<kGene>, dim3(grid_of(n_names)), dim3(kBlock), 0, st, d_name_off, n_names, S.misc.p);
-            T_HIP(hipGetLastError());
-        }
-        if (kGene) {
-            hipLaunchKernelGGL(k_check_name_index, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_first, n_rows, n_names, S.misc.p);
-            T_HIP(hipGetLastError());
-        }
-        T_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        if (h_misc[5] != 0 || (h_misc[0] & 1)) T_FAIL(SFGPU_ERR_INVALID, "name_off must start at 0 and never decrease");
-        if (h_misc[0] & 2) T_FAIL(SFGPU_ERR_RANGE, "a name is longer than 2^32 - 60 bytes");
-        if (h_misc[0] & 4) T_FAIL(SFGPU_ERR_INVALID, "a row's name index is not below the number of names");
-        if (h_misc[6] && !d_names) T_FAIL(SFGPU_ERR_INVALID, "null names");
-
-        // ---- sizing: the decoded cells, row lengths, row starts, the longest row
-        T_TRY(S.rec.reserve(kCols * n_rows, st, false));
-        T_TRY(S.row_len.reserve(n_rows + 1, st, false));
-        T_TRY(S.row_start.reserve(n_rows + 1, st, false));
-        T_HIP(hipEventRecord(ev_s[0], st));
-        hipLaunchKernelGGL(k_decode, dim3(grid_of(n_rows), kCols), dim3(kBlock), 0, st, cols, n_rows, S.rec.p, S.misc.p);
-        T_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_decode_slow, dim3(grid_of(n_rows), kCols), dim3(kBlock), 0, st, cols, n_rows, S.rec.p);
-        T_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_row_size<kGene>, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_name_off, d_first, S.rec.p, n_rows, S.row_len.p);
-        T_HIP(hipGetLastError());
-        T_TRY(exclusive_scan_u32(S.row_len.p, S.row_start.p, n_rows, st, false));
-        T_TRY(textchunks::line_max(S.row_start.p, n_rows, S.misc.p + 1, st));
-        T_HIP(hipEventRecord(ev_s[1], st));
-        T_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        T_HIP(hipMemcpyAsync(&h_misc[4], S.row_start.p + n_rows, 8, hipMemcpyDeviceToHost, st));
-        T_HIP(hipStreamSynchronize(st));
-        {
-            float a = 0.f;
-            if (hipEventElapsedTime(&a, ev_s[0], ev_s[1]) == hipSuccess) out->format_ms += (double)a;
-        }
-        const uint64_t total = h_misc[4];
-        out->n_bytes = total; out->n_rows = n_rows; out->max_row_bytes = h_misc[1]; out->n_slow = h_misc[3];
-        if (!sink) goto done;
-        if (out->max_row_bytes > chunk_bytes) T_FAIL(SFGPU_ERR_RANGE, "a row is longer than chunk_bytes");
-
-        // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this table's tiles
-        textchunks::Stats ts;
-        rc = textchunks::deliver(who, S.row_start.p, n_rows, total, chunk_bytes, sink, user, st, &ts,
-                                 [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-            hipLaunchKernelGGL(k_format<kGene>, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_names, d_name_off, d_first,
-                               S.rec.p, S.row_start.p, n_rows, total, first_tile, out_base, buf);
-            SF_HIP(hipGetLastError());
-            return SFGPU_OK;
-        });
-        out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
+    if (int rc = S.misc.reserve(4, st, false)) return rc;
+    SF_HIP(hipMemsetAsync(S.misc.p, 0, 4 * sizeof(unsigned long long), st));
+    SF_HIP(hipMemcpyAsync(&h_misc[5], d_name_off, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_misc[6], d_name_off + n_names, 8, hipMemcpyDeviceToHost, st));
+    if (n_names) {
+        hipLaunchKernelGGL(k_check_off<kGene>, dim3(grid_of(n_names)), dim3(kBlock), 0, st, d_name_off, n_names, S.misc.p);
+        SF_HIP(hipGetLastError());
     }
-done:
-    if (st) (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : {ev_in, ev_s[0], ev_s[1]}) if (e) (void)hipEventDestroy(e);
-    if (h_misc) pinned_free(h_misc);
-    if (st) stream_release(st);
+    if (kGene) {
+        hipLaunchKernelGGL(k_check_name_index, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_first, n_rows, n_names, S.misc.p);
+        SF_HIP(hipGetLastError());
+    }
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    if (h_misc[5] != 0 || (h_misc[0] & 1)) return fail(SFGPU_ERR_INVALID, "name_off must start at 0 and never decrease");
+    if (h_misc[0] & 2) return fail(SFGPU_ERR_RANGE, "a name is longer than 2^32 - 60 bytes");
+    if (h_misc[0] & 4) return fail(SFGPU_ERR_INVALID, "a row's name index is not below the number of names");
+    if (h_misc[6] && !d_names) return fail(SFGPU_ERR_INVALID, "null names");
+
+    // ---- sizing: the decoded cells, row lengths, row starts, the longest row
+    if (int rc = S.rec.reserve(kCols * n_rows, st, false)) return rc;
+    if (int rc = S.row_len.reserve(n_rows + 1, st, false)) return rc;
+    if (int rc = S.row_start.reserve(n_rows + 1, st, false)) return rc;
+    SF_HIP(hipEventRecord(ev_s[0], st));
+    hipLaunchKernelGGL(k_decode, dim3(grid_of(n_rows), kCols), dim3(kBlock), 0, st, cols, n_rows, S.rec.p, S.misc.p);
+    SF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_decode_slow, dim3(grid_of(n_rows), kCols), dim3(kBlock), 0, st, cols, n_rows, S.rec.p);
+    SF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_row_size<kGene>, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_name_off, d_first, S.rec.p, n_rows, S.row_len.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = exclusive_scan_u32(S.row_len.p, S.row_start.p, n_rows, st, false)) return rc;
+    if (int rc = textchunks::line_max(S.row_start.p, n_rows, S.misc.p + 1, st)) return rc;
+    SF_HIP(hipEventRecord(ev_s[1], st));
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_misc[4], S.row_start.p + n_rows, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&out->format_ms, ev_s[0], ev_s[1]);
+    const uint64_t total = h_misc[4];
+    out->n_bytes = total; out->n_rows = n_rows; out->max_row_bytes = h_misc[1]; out->n_slow = h_misc[3];
+    if (!sink) return SFGPU_OK;
+    if (out->max_row_bytes > chunk_bytes) return fail(SFGPU_ERR_RANGE, "a row is longer than chunk_bytes");
+
+    // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this table's tiles
+    textchunks::Stats ts;
+    const int rc = textchunks::deliver(who, S.row_start.p, n_rows, total, chunk_bytes, sink, user, st, &ts,
+                                       [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
+        hipLaunchKernelGGL(k_format<kGene>, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_names, d_name_off, d_first,
+                           S.rec.p, S.row_start.p, n_rows, total, first_tile, out_base, buf);
+        SF_HIP(hipGetLastError());
+        return SFGPU_OK;
+    });
+    out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
     return rc;
-#undef T_HIP
-#undef T_TRY
-#undef T_FAIL
 }
 
 }  // namespace rowtext

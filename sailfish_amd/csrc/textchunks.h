@@ -6,8 +6,6 @@
 #pragma once
 #include "common.h"
 
-#include <chrono>
-
 namespace sfgpu {
 namespace textchunks {
 
@@ -68,28 +66,13 @@ struct Stats {                             // added to, never reset: the caller'
     double format_ms = 0.0, d2h_ms = 0.0, sink_ms = 0.0;
 };
 
-// everything the loop owns; released only after both streams have drained (a copy may still write the pinned buffers)
+// everything the loop owns; the scope comes last, so that it is destroyed first and both streams have drained before a block
+// goes back (a copy may still write the pinned buffers)
 struct Pipe {
-    hipStream_t st = nullptr, cs = nullptr;
-    char* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev_p[2] = {nullptr, nullptr};
-    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
-    uint64_t* h_plan = nullptr;
-    unsigned long long* h_n = nullptr;
     DevBuf<uint64_t> plan;
     DevBuf<unsigned long long> n;
     DevBuf<uint4> out[2];
-    ~Pipe() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        if (st) (void)hipStreamSynchronize(st);
-        for (int b = 0; b < 2; ++b) {
-            if (pinned[b]) pinned_free(pinned[b]);
-            for (hipEvent_t e : {ev_p[b], ev_f0[b], ev_f1[b], ev_c0[b], ev_c1[b]}) if (e) (void)hipEventDestroy(e);
-        }
-        if (h_plan) pinned_free(h_plan);
-        if (h_n) pinned_free(h_n);
-        if (cs) stream_release(cs);
-    }
+    CallScope scope;
 };
 
 // Plans the chunks of a text of `total` bytes in n_lines lines (every line at most chunk_bytes long: the caller has checked) and
@@ -100,45 +83,44 @@ template <typename FormatTiles>
 int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uint64_t total, uint64_t chunk_bytes, sfgpu_text_sink sink,
             void* user, hipStream_t st, Stats* stats, FormatTiles format_tiles) {
     Pipe P;
-    P.st = st;
-#define TC_FAIL(code, what) do { set_error("%s: %s", who, what); return (code); } while (0)
-#define TC_TRY(expr) do { const int _rc = (expr); if (_rc != SFGPU_OK) return _rc; } while (0)
-    SF_HIP(stream_acquire(&P.cs));
-    for (auto& e : P.ev_p) SF_HIP(hipEventCreateWithFlags(&e, hipEventDefault));
-    SF_HIP(pinned_malloc(&P.h_n, sizeof(unsigned long long)));
+    hipStream_t cs = nullptr;
+    char* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev_p[2] = {nullptr, nullptr};
+    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
+    uint64_t* h_plan = nullptr;
+    unsigned long long* h_n = nullptr;
+    SF_HIP(P.scope.adopt(st));
+    SF_HIP(P.scope.acquire(&cs));
+    for (auto& e : ev_p) SF_HIP(P.scope.event(&e));
+    SF_HIP(P.scope.pinned_block(&h_n, sizeof(unsigned long long)));
 
     // ---- the chunk plan: two consecutive greedy chunks hold more than chunk_bytes together
     const uint64_t plan_cap = 2 * (total / chunk_bytes) + 2;
-    TC_TRY(P.plan.reserve(2 * plan_cap, st, false));
-    TC_TRY(P.n.reserve(1, st, false));
-    SF_HIP(pinned_malloc(&P.h_plan, 2 * plan_cap * sizeof(uint64_t)));
-    SF_HIP(hipEventRecord(P.ev_p[0], st));
+    if (int rc = P.plan.reserve(2 * plan_cap, st, false)) return rc;
+    if (int rc = P.n.reserve(1, st, false)) return rc;
+    SF_HIP(P.scope.pinned_block(&h_plan, 2 * plan_cap * sizeof(uint64_t)));
+    SF_HIP(hipEventRecord(ev_p[0], st));
     hipLaunchKernelGGL(k_chunk_plan, dim3(1), dim3(kWave), 0, st, d_line_start, n_lines, chunk_bytes, plan_cap, P.plan.p, P.n.p);
     SF_HIP(hipGetLastError());
-    SF_HIP(hipEventRecord(P.ev_p[1], st));
-    SF_HIP(hipMemcpyAsync(P.h_n, P.n.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipEventRecord(ev_p[1], st));
+    SF_HIP(hipMemcpyAsync(h_n, P.n.p, 8, hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
-    const uint64_t n_chunks = *P.h_n;
-    uint64_t* h_plan = P.h_plan;
+    const uint64_t n_chunks = *h_n;
     SF_HIP(hipMemcpyAsync(h_plan, P.plan.p, 2 * n_chunks * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
-    {
-        float a = 0.f;
-        if (hipEventElapsedTime(&a, P.ev_p[0], P.ev_p[1]) == hipSuccess) stats->format_ms += (double)a;
+    add_elapsed(&stats->format_ms, ev_p[0], ev_p[1]);
+    if (n_chunks == 0 || h_plan[2 * n_chunks - 2] != n_lines || h_plan[2 * n_chunks - 1] != total) {
+        set_error("%s: the chunk plan does not cover the table", who);
+        return SFGPU_ERR_HIP;
     }
-    if (n_chunks == 0 || h_plan[2 * n_chunks - 2] != n_lines || h_plan[2 * n_chunks - 1] != total)
-        TC_FAIL(SFGPU_ERR_HIP, "the chunk plan does not cover the table");
 
     // ---- format + copy + sink, two buffers: chunk i + 1 is formatted and copied while the sink holds chunk i
     const uint64_t stage_bytes = total < chunk_bytes ? total : chunk_bytes;
     const uint64_t out_groups = (stage_bytes + 2 * kTileBytes) / 16 + 1;
     for (int b = 0; b < 2 && (uint64_t)b < n_chunks; ++b) {
-        SF_HIP(pinned_malloc(&P.pinned[b], stage_bytes));
-        TC_TRY(P.out[b].reserve(out_groups, st, false));
-        SF_HIP(hipEventCreateWithFlags(&P.ev_f0[b], hipEventDefault));
-        SF_HIP(hipEventCreateWithFlags(&P.ev_f1[b], hipEventDefault));
-        SF_HIP(hipEventCreateWithFlags(&P.ev_c0[b], hipEventDefault));
-        SF_HIP(hipEventCreateWithFlags(&P.ev_c1[b], hipEventDefault));
+        SF_HIP(P.scope.pinned_block(&pinned[b], stage_bytes));
+        if (int rc = P.out[b].reserve(out_groups, st, false)) return rc;
+        for (hipEvent_t* e : {&ev_f0[b], &ev_f1[b], &ev_c0[b], &ev_c1[b]}) SF_HIP(P.scope.event(e));
     }
     auto chunk_begin = [&](uint64_t i) -> uint64_t { return i ? h_plan[2 * i - 1] : 0; };
     // format on st into out[slot], then the copy on cs into pinned[slot]; the slot's previous chunk has left the sink, and
@@ -147,34 +129,32 @@ int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uin
         const int slot = (int)(i & 1);
         const uint64_t b0 = chunk_begin(i), b1 = h_plan[2 * i + 1];
         const uint64_t first_tile = b0 >> kTileShift, last_tile = (b1 - 1) >> kTileShift, out_base = first_tile << kTileShift;
-        SF_HIP(hipEventRecord(P.ev_f0[slot], st));
-        TC_TRY(format_tiles(first_tile, last_tile, out_base, P.out[slot].p, st));
-        SF_HIP(hipEventRecord(P.ev_f1[slot], st));
-        SF_HIP(hipStreamWaitEvent(P.cs, P.ev_f1[slot], 0));
-        SF_HIP(hipEventRecord(P.ev_c0[slot], P.cs));
-        SF_HIP(hipMemcpyAsync(P.pinned[slot], reinterpret_cast<const char*>(P.out[slot].p) + (b0 - out_base), b1 - b0, hipMemcpyDeviceToHost, P.cs));
-        SF_HIP(hipEventRecord(P.ev_c1[slot], P.cs));
+        SF_HIP(hipEventRecord(ev_f0[slot], st));
+        if (int rc = format_tiles(first_tile, last_tile, out_base, P.out[slot].p, st)) return rc;
+        SF_HIP(hipEventRecord(ev_f1[slot], st));
+        SF_HIP(hipStreamWaitEvent(cs, ev_f1[slot], 0));
+        SF_HIP(hipEventRecord(ev_c0[slot], cs));
+        SF_HIP(hipMemcpyAsync(pinned[slot], reinterpret_cast<const char*>(P.out[slot].p) + (b0 - out_base), b1 - b0, hipMemcpyDeviceToHost, cs));
+        SF_HIP(hipEventRecord(ev_c1[slot], cs));
         return SFGPU_OK;
     };
-    TC_TRY(enqueue(0));
+    if (int rc = enqueue(0)) return rc;
     for (uint64_t i = 0; i < n_chunks; ++i) {
         const int slot = (int)(i & 1);
-        if (i + 1 < n_chunks) TC_TRY(enqueue(i + 1));
-        SF_HIP(hipEventSynchronize(P.ev_c1[slot]));
-        {
-            float a = 0.f, b = 0.f;
-            if (hipEventElapsedTime(&a, P.ev_f0[slot], P.ev_f1[slot]) == hipSuccess) stats->format_ms += (double)a;
-            if (hipEventElapsedTime(&b, P.ev_c0[slot], P.ev_c1[slot]) == hipSuccess) stats->d2h_ms += (double)b;
-        }
+        if (i + 1 < n_chunks) if (int rc = enqueue(i + 1)) return rc;
+        SF_HIP(hipEventSynchronize(ev_c1[slot]));
+        add_elapsed(&stats->format_ms, ev_f0[slot], ev_f1[slot]);
+        add_elapsed(&stats->d2h_ms, ev_c0[slot], ev_c1[slot]);
         const auto t0 = std::chrono::steady_clock::now();
-        const int stop = sink(P.pinned[slot], h_plan[2 * i + 1] - chunk_begin(i), user);
-        stats->sink_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const int stop = sink(pinned[slot], h_plan[2 * i + 1] - chunk_begin(i), user);
+        stats->sink_ms += ms_since(t0);
         stats->n_chunks++;
-        if (stop) TC_FAIL(SFGPU_ERR_IO, "the sink refused a chunk");
+        if (stop) {
+            set_error("%s: the sink refused a chunk", who);
+            return SFGPU_ERR_IO;
+        }
     }
     return SFGPU_OK;
-#undef TC_FAIL
-#undef TC_TRY
 }
 
 }  // namespace textchunks

@@ -87,7 +87,7 @@ def test_parse_parity_at_scale(built, gpu, tmp_path):
 @pytest.mark.gpu
 def test_chunk_edges(built, gpu, tmp_path):
     """a few-KB chunk: lines straddle every chunk boundary; a label as long as a chunk still parses; one longer is refused"""
-    from sailfish_amd import eqfile
+    from sailfish_amd import _lib, eqfile
     rng = np.random.default_rng(12)
     M = 5000
     rowptr, ids, counts = _random_classes(rng, 20_000, M, long_label=700)     # ~3.5 KB line
@@ -102,6 +102,16 @@ def test_chunk_edges(built, gpu, tmp_path):
     with pytest.raises(ValueError) as e:
         _fold(str(p), names, gpu, chunk_bytes=2048)
     assert "longer than the chunk size" in str(e.value) and f"line {2 + M + 20_000 // 2 + 1}:" in str(e.value), str(e.value)
+    # the first class line is the long one: refused before anything is staged
+    q = tmp_path / "first.txt"
+    q.write_bytes(eqfile.format_text(names, np.array([0, 700]), ids[:700], counts[:1]))
+    with pytest.raises(ValueError) as e:
+        _fold(str(q), names, gpu, chunk_bytes=2048)
+    assert "longer than the chunk size" in str(e.value) and f"line {2 + M + 1}:" in str(e.value), str(e.value)
+    # a builder that has been finished refuses the fold of the first chunk, while the second is on its way to the device
+    with pytest.raises(_lib.SfgpuError) as e:
+        eq.add_eq_file(str(p), names=names, chunk_bytes=4096)
+    assert e.value.code == _lib.ERR_STATE
 
 
 def _hit_batches(rng, rl, R, paired, n_batches=3):

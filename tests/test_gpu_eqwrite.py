@@ -179,6 +179,12 @@ def test_chunk_edges(built, gpu):
     for bad in (15, 2 ** 30 + 1):
         rc, res, chunks = _collect(dev, bad)
         assert rc == _lib.ERR_INVALID and chunks == []
+    # a row pointer that decreases, one that does not start at 0, ids announced by the row pointer and a null id array
+    rowptr, ids, counts = dev
+    down = rowptr.clone(); down[200] = down[199] - 1
+    for bad in ((down, ids, counts), (rowptr + 1, ids, counts), (rowptr, None, counts)):
+        rc, res, chunks = _collect(bad, 4096)
+        assert rc == _lib.ERR_INVALID and chunks == []
     rc, _, chunks = _collect(dev, 2 ** 30)
     assert rc == _lib.OK and b"".join(chunks) == want
 

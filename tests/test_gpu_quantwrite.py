@@ -312,6 +312,8 @@ def test_name_offsets_are_checked(built, gpu):
     bad = off.clone(); bad[0] = 1
     rc, _, chunks = _collect(((blob, bad),) + d[1:])
     assert rc == _lib.ERR_INVALID and chunks == []
+    rc, _, chunks = _collect(((blob[:0], off),) + d[1:])          # offsets that announce name bytes, and a null blob
+    assert rc == _lib.ERR_INVALID and chunks == []
     rc, _, chunks = _collect(((blob, off),) + d[1:])
     assert rc == _lib.OK and b"".join(chunks) == _want(cols)
 

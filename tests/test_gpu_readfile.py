@@ -146,6 +146,25 @@ def test_errors_name_the_first_bad_record(gpu, harness):
     assert r["rc"] == ERR_FORMAT and r["error"] == (TRUNCATED, 700, 4 * 700 + 2) and r["seqs"] == []
 
 
+@pytest.mark.gpu
+def test_error_behind_reused_staging_slots(gpu, harness):
+    """a text of three staged sub-chunks (4 MiB each: the first pinned slot is collected and taken again) whose last sub-chunk
+    holds a record without its '+'; the same text unbroken parses whole"""
+    rng = np.random.default_rng(6)
+    rec, seq, name = fastq_text(rng, 1, lens=[1001])
+    reps = (8 << 20) // len(rec) + 3                      # the last record lies wholly behind byte 8 MiB
+    text = rec * reps
+    assert 8 << 20 < len(text) - len(rec) and len(text) < (8 << 20) + (1 << 16)
+    lines = text.split(b"\n")
+    bad_line = 4 * (reps - 1) + 2
+    assert lines[bad_line] == b"+" + name[0]
+    lines[bad_line] = b""
+    r = check(gpu, harness, b"\n".join(lines), 1)
+    assert r["rc"] == ERR_FORMAT and r["error"] == (MISSING_PLUS, reps - 1, bad_line) and r["seqs"] == [] and r["consumed"] == 0
+    r = check(gpu, harness, text, 1)
+    assert r["rc"] == OK and r["seqs"] == seq * reps and r["names"] == name * reps and r["consumed"] == len(text)
+
+
 def _texts_for_carry():
     rng = np.random.default_rng(8)
     yield fastq_text(rng, 40, lens=[0, 1, 15, 16, 17, 31, 33, 300, 150, 70] * 4)

@@ -37,7 +37,7 @@ enum {
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8,    /* malformed input text (sfgpu_eq_add_text_host, sfgpu_reads_parse_host) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host) */
     SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
 };
 
@@ -210,6 +210,55 @@ typedef struct {
 SFGPU_API int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
                                      uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
                                      sfgpu_stream stream);
+/* The same parse of a text that already lies in device memory (what sfgpu_bgzf_inflate_host wrote): nothing is staged and
+ * ms_copy is 0.  d_text is 16-byte aligned and has room for cap_text >= round16(n_bytes + 1) + 16 bytes (else SFGPU_ERR_INVALID):
+ * the call itself writes the '\n' and the zero padding behind the n_bytes of text, the text is otherwise not modified.  The
+ * format is taken from the first byte (a one-byte copy back), a text of nothing but line ends is found by a reduction on the
+ * device; every output and every result field is what sfgpu_reads_parse_host gives for the same bytes, name spans included
+ * (they index d_text). */
+SFGPU_API int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads,
+                                       uint8_t* d_bases, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span,
+                                       sfgpu_reads_result* out, sfgpu_stream stream);
+/* Blocked gzip (BGZF: what bgzip and the Illumina converters write) inflated on the device, one wavefront per member.  The
+ * rules live in sailfish_amd/csrc/bgzfmt.h: a member is a gzip member with a 'B','C' extra subfield that holds its size, at
+ * most 64 KB of payload, and no match that reaches before its first byte.
+ * h_src[0 .. n_bytes) begins at a member.  The host reads the headers and trailers only and builds the member directory
+ * (offset, size, offset of the payload = exclusive sum of the ISIZEs); the compressed bytes go through the library's pinned
+ * double buffer in sub-chunks and the members of a sub-chunk are inflated while the next one is copied.  The call takes the
+ * whole members in file order whose payloads fit in cap_bytes and writes them back to back to d_dst[0 .. n_bytes_out)
+ * (any alignment: the caller may inflate behind a text it keeps); `consumed` is where the next call's input begins.  With final != 0 a trailing
+ * partial member is SFGPU_BGZF_TRUNCATED, otherwise it is left for the next call.  d_dst == NULL sizes only: the directory is
+ * built and `out` filled (n_members, consumed, n_bytes_out for the given cap_bytes), nothing is copied or inflated.
+ * A member that fails a check is SFGPU_ERR_FORMAT with the first such member in file order and the first failed check in
+ * stream order within it; d_dst is then unspecified.  No wave writes outside its member's [out_off, out_off + ISIZE).
+ * n_bytes > 2^30 is SFGPU_ERR_RANGE.  Synchronous, ordered behind the work already on `stream`, no CPU path. */
+enum {
+    SFGPU_BGZF_OK = 0,
+    SFGPU_BGZF_BAD_HEADER = 1,       /* not gzip / no BC subfield / BSIZE too small for header and trailer or not where the stream ends / ISIZE > 65536 */
+    SFGPU_BGZF_TRUNCATED = 2,        /* the body ends before the end-of-block code of the final block; final: the input ends inside a member */
+    SFGPU_BGZF_BAD_BLOCK_TYPE = 3,   /* BTYPE 3 */
+    SFGPU_BGZF_STORED_LEN = 4,       /* LEN != ~NLEN */
+    SFGPU_BGZF_BAD_CODE_LENGTHS = 5, /* a code-length set that zlib's inflate_table rejects, HLIT > 286, HDIST > 30, a bad repeat, no code for 256 */
+    SFGPU_BGZF_BAD_SYMBOL = 6,       /* length symbol 286 / 287, distance symbol 30 / 31, or a code word nobody assigned */
+    SFGPU_BGZF_DISTANCE_TOO_FAR = 7, /* a match reaches before the member's first byte */
+    SFGPU_BGZF_SIZE_MISMATCH = 8,    /* the payload is not ISIZE bytes */
+    SFGPU_BGZF_CRC_MISMATCH = 9
+};
+typedef struct {
+    uint64_t n_members;        /* whole members taken */
+    uint64_t consumed;         /* bytes of h_src through the last of them */
+    uint64_t n_bytes_out;      /* their payload = the sum of their ISIZEs */
+    uint64_t n_stored_blocks;  /* DEFLATE blocks by type, over all members */
+    uint64_t n_fixed_blocks;
+    uint64_t n_dynamic_blocks;
+    uint64_t error_member;     /* 0-based first bad member of h_src in file order; UINT64_MAX without one */
+    int32_t error_kind;        /* SFGPU_BGZF_* */
+    int32_t pad_;
+    double ms_copy;            /* device events around the staged host-to-device copies */
+    double ms_kernels;         /* device events around the inflate kernels */
+} sfgpu_bgzf_result;
+SFGPU_API int sfgpu_bgzf_inflate_host(const void* h_src, uint64_t n_bytes, int final, uint8_t* d_dst, uint64_t cap_bytes,
+                                      sfgpu_bgzf_result* out, sfgpu_stream stream);
 /* writeEquivCounts (src/GZipWriter.cpp:77-88), the other direction: the CLASS SECTION of an eq_classes.txt file formatted on the
  * device from a class table in CSR form (the sfgpu_eq_export_device arrays, a table merged by sfgpu_eqvec_merge_disjoint, or
  * one the caller assembled).  For each class, in the order given,

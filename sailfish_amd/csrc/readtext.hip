@@ -1,5 +1,7 @@
-// readtext.hip -- FASTA / FASTQ records parsed on the device: sfgpu_reads_parse_host.  What a record is, is decided by readfmt.h
-// (the same functions run serially in tests/readfile_harness.cpp); this file is the passes around them.
+// readtext.hip -- FASTA / FASTQ records parsed on the device: sfgpu_reads_parse_host, and sfgpu_reads_parse_device for a text that
+// is in device memory already (what bgzf_read.hip inflated).  What a record is, is decided by readfmt.h (the same functions run
+// serially in tests/readfile_harness.cpp); this file is the passes around them.  The two entries differ in how the text and the
+// newline counts of its 16-byte groups get there; from the scan of the counts on they are one function, parse_counted.
 //
 // The host text goes through two pinned buffers in sub-chunks of kSubBytes; the copy of sub-chunk c + 1 runs on the copy stream
 // while the '\n' bytes of sub-chunk c are counted.  A '\n' is appended behind the text, so the remainder (readfmt.h) is a line of
@@ -32,6 +34,23 @@ __global__ void k_reads_count(const uint4* __restrict__ buf, uint64_t g0, uint64
     const uint64_t g = g0 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= g1) return;
     nl_cnt[g] = __popc(nl_mask(buf[g]));
+}
+
+// cnt[0] += bytes that are neither '\n' nor '\r', cnt[1] += '\n' bytes (rf_all_blank and the line count of a text without records)
+__global__ void k_reads_blank(const unsigned char* __restrict__ bytes, uint64_t n, unsigned long long* __restrict__ cnt) {
+    const uint64_t p0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16u;
+    unsigned long long other = 0, nl = 0;
+    for (uint64_t p = p0; p < n && p < p0 + 16u; ++p) {
+        const unsigned char b = bytes[p];
+        nl += b == '\n';
+        other += b != '\n' && b != '\r';
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) { other += __shfl_xor(other, o); nl += __shfl_xor(nl, o); }
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+        if (other) atomicAdd(&cnt[0], other);
+        if (nl) atomicAdd(&cnt[1], nl);
+    }
 }
 
 struct Bounds {
@@ -176,6 +195,73 @@ struct ReadScratch {
     DevBuf<unsigned long long> misc;        // [0] first line error, [1] T, [2 .. 8] k_reads_cut's results
 };
 
+// Everything behind the newline counts, for both entries: text = the n_bytes, the appended '\n', zeros up to the end of its 16-byte
+// group and one more group of zeros; S.nl_cnt holds the count of every group (work queued on st); S.misc is initialised.
+// after_counts() runs behind the first wait for st (the host entry reads the times of its staged copies there).
+template <typename AfterCounts>
+int parse_counted(ReadScratch& S, const uint4* text, uint64_t n_bytes, int format, int final, uint64_t max_reads, uint8_t* d_bases,
+                  uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out, hipStream_t st, hipEvent_t* ev_p,
+                  unsigned long long* h_res, AfterCounts after_counts) {
+    const uint64_t n_groups = (n_bytes + 1 + 15) / 16;
+    // ---- lines
+    SF_HIP(hipEventRecord(ev_p[1], st));
+    if (int r = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return r;
+    SF_HIP(hipEventRecord(ev_p[2], st));
+    SF_HIP(hipMemcpyAsync(&h_res[7], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    after_counts();
+    const uint32_t L = (uint32_t)h_res[7];                // >= 1: the appended '\n'
+    out->n_lines = (uint64_t)L - 1 + (uint64_t)final;
+    for (DevBuf<uint32_t>* b : {&S.line_end, &S.hdr, &S.seq, &S.hdr_scan, &S.dst, &S.rec_line})
+        if (int r = b->reserve((uint64_t)L + 2, st, false)) return r;
+    SF_HIP(hipEventRecord(ev_p[3], st));
+    hipLaunchKernelGGL(textlines::k_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, S.nl_scan.p, S.line_end.p);
+    SF_HIP(hipGetLastError());
+    const unsigned char* d_bytes = reinterpret_cast<const unsigned char*>(text);
+    hipLaunchKernelGGL(k_reads_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, d_bytes, format, final, L, S.line_end.p, S.hdr.p, S.seq.p, S.misc.p);
+    SF_HIP(hipGetLastError());
+    if (int r = exclusive_scan_u32_u32(S.hdr.p, S.hdr_scan.p, L, st)) return r;
+    if (int r = exclusive_scan_u32_u32(S.seq.p, S.dst.p, L, st)) return r;
+    hipLaunchKernelGGL(k_reads_rec_lines, dim3(grid_of((uint64_t)L + 1)), dim3(kBlock), 0, st, L, S.hdr.p, S.hdr_scan.p, S.rec_line.p);
+    SF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_reads_cut, dim3(1), dim3(kWave), 0, st, format, final, L, n_bytes, max_reads, cap_bases, S.line_end.p, S.hdr_scan.p,
+                       S.dst.p, S.rec_line.p, S.misc.p, S.misc.p + 2);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipEventRecord(ev_p[4], st));
+    SF_HIP(hipMemcpyAsync(h_res, S.misc.p + 2, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    // a format error and the cap_bases range error do not leave at once: the kernel times below are still reported
+    int rc = SFGPU_OK;
+    if (h_res[0] != kReadsNoError) {
+        out->error_record = h_res[0] >> 8; out->error_kind = (int32_t)(h_res[0] & 0xff); out->error_line = h_res[5];
+        set_error("reads text: record %llu (line %llu of this text): %s", (unsigned long long)out->error_record,
+                  (unsigned long long)out->error_line, kind_text(out->error_kind));
+        rc = SFGPU_ERR_FORMAT;
+    } else if (h_res[1] == 0 && h_res[4] > 0 && max_reads > 0) {
+        set_error("sfgpu_reads_parse_host: the first record alone has more than cap_bases = %llu bases", (unsigned long long)cap_bases);
+        rc = SFGPU_ERR_RANGE;
+    } else {
+        // ---- emission
+        const uint32_t R = (uint32_t)h_res[1], n_bases = (uint32_t)h_res[2], Lc = (uint32_t)h_res[6];
+        SF_HIP(hipEventRecord(ev_p[5], st));
+        hipLaunchKernelGGL(k_reads_emit, dim3(grid_of((uint64_t)R + 1)), dim3(kBlock), 0, st, d_bytes, R, S.line_end.p, S.dst.p, S.rec_line.p,
+                           d_off, d_name_span);
+        SF_HIP(hipGetLastError());
+        if (n_bases) {
+            hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, text, Lc, n_bases,
+                               S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
+            SF_HIP(hipGetLastError());
+        }
+        out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
+    }
+    SF_HIP(hipEventRecord(ev_p[6], st));
+    SF_HIP(hipStreamSynchronize(st));
+    double lines = 0.0;                                   // both halves or neither
+    if (add_elapsed(&lines, ev_p[1], ev_p[2]) && add_elapsed(&lines, ev_p[3], ev_p[4])) out->ms_kernels += lines;
+    if (rc == SFGPU_OK) add_elapsed(&out->ms_kernels, ev_p[5], ev_p[6]);
+    return rc;
+}
+
 }  // namespace
 }  // namespace sfgpu
 
@@ -272,61 +358,71 @@ extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int 
         in_flight[slot] = true;
     }
 
-    // ---- lines
-    SF_HIP(hipEventRecord(ev_p[1], st));
-    if (int r = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return r;
-    SF_HIP(hipEventRecord(ev_p[2], st));
-    SF_HIP(hipMemcpyAsync(&h_res[7], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+    return parse_counted(S, S.text.p, n_bytes, format, final, max_reads, d_bases, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
+                         [&]() { collect(0); collect(1); });
+}
+
+extern "C" int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads, uint8_t* d_bases,
+                                        uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                        sfgpu_stream stream) {
+    SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null result");
+    memset(out, 0, sizeof(*out));
+    out->error_record = ~0ull; out->error_line = ~0ull;
+    SF_REQUIRE(n_bytes <= kReadsMaxBytes, SFGPU_ERR_RANGE, "sfgpu_reads_parse_device: more than 2^30 bytes in one call");
+    SF_REQUIRE(n_bytes == 0 || d_text, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null text");
+    SF_REQUIRE(d_off && (d_bases || cap_bases == 0), SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null output");
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_bases) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: d_bases must be 16-byte aligned");
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_text) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: d_text must be 16-byte aligned");
+    const uint64_t n1 = n_bytes + 1, n_groups = (n1 + 15) / 16, padded = 16 * n_groups + 16;
+    SF_REQUIRE(n_bytes == 0 || cap_text >= padded, SFGPU_ERR_INVALID,
+               "sfgpu_reads_parse_device: cap_text must hold the text, its '\\n', the rest of that 16-byte group and one group more");
+    final = final ? 1 : 0;
+    hipStream_t st = as_stream(stream);
+    SF_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
+    if (n_bytes == 0) { SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
+
+    ReadScratch S;          // S.text stays empty: the text is the caller's
+    CallScope scope;        // after S, as in sfgpu_reads_parse_host
+    hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr;
+    hipEvent_t ev_p[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    unsigned long long* h_res = nullptr;                 // [0 .. 8) parse_counted's, [8] the first byte, [8 .. 10) the blank counts
+    SF_HIP(scope.adopt(st));
+    SF_HIP(scope.event(&ev_c0));
+    SF_HIP(scope.event(&ev_c1));
+    for (auto& e : ev_p) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_res, 10 * sizeof(unsigned long long)));
+    h_res[8] = 0;
+    SF_HIP(hipMemcpyAsync(&h_res[8], d_text, 1, hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
-    collect(0); collect(1);
-    const uint32_t L = (uint32_t)h_res[7];                // >= 1: the appended '\n'
-    out->n_lines = (uint64_t)L - 1 + (uint64_t)final;
-    for (DevBuf<uint32_t>* b : {&S.line_end, &S.hdr, &S.seq, &S.hdr_scan, &S.dst, &S.rec_line})
-        if (int r = b->reserve((uint64_t)L + 2, st, false)) return r;
-    SF_HIP(hipEventRecord(ev_p[3], st));
-    hipLaunchKernelGGL(textlines::k_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, S.text.p, n_groups, S.nl_scan.p, S.line_end.p);
-    SF_HIP(hipGetLastError());
-    const unsigned char* d_bytes = reinterpret_cast<const unsigned char*>(S.text.p);
-    hipLaunchKernelGGL(k_reads_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, d_bytes, format, final, L, S.line_end.p, S.hdr.p, S.seq.p, S.misc.p);
-    SF_HIP(hipGetLastError());
-    if (int r = exclusive_scan_u32_u32(S.hdr.p, S.hdr_scan.p, L, st)) return r;
-    if (int r = exclusive_scan_u32_u32(S.seq.p, S.dst.p, L, st)) return r;
-    hipLaunchKernelGGL(k_reads_rec_lines, dim3(grid_of((uint64_t)L + 1)), dim3(kBlock), 0, st, L, S.hdr.p, S.hdr_scan.p, S.rec_line.p);
-    SF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_reads_cut, dim3(1), dim3(kWave), 0, st, format, final, L, n_bytes, max_reads, cap_bases, S.line_end.p, S.hdr_scan.p,
-                       S.dst.p, S.rec_line.p, S.misc.p, S.misc.p + 2);
-    SF_HIP(hipGetLastError());
-    SF_HIP(hipEventRecord(ev_p[4], st));
-    SF_HIP(hipMemcpyAsync(h_res, S.misc.p + 2, 7 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    // a format error and the cap_bases range error do not leave at once: the kernel times below are still reported
-    int rc = SFGPU_OK;
-    if (h_res[0] != kReadsNoError) {
-        out->error_record = h_res[0] >> 8; out->error_kind = (int32_t)(h_res[0] & 0xff); out->error_line = h_res[5];
-        set_error("reads text: record %llu (line %llu of this text): %s", (unsigned long long)out->error_record,
-                  (unsigned long long)out->error_line, kind_text(out->error_kind));
-        rc = SFGPU_ERR_FORMAT;
-    } else if (h_res[1] == 0 && h_res[4] > 0 && max_reads > 0) {
-        set_error("sfgpu_reads_parse_host: the first record alone has more than cap_bases = %llu bases", (unsigned long long)cap_bases);
-        rc = SFGPU_ERR_RANGE;
-    } else {
-        // ---- emission
-        const uint32_t R = (uint32_t)h_res[1], n_bases = (uint32_t)h_res[2], Lc = (uint32_t)h_res[6];
-        SF_HIP(hipEventRecord(ev_p[5], st));
-        hipLaunchKernelGGL(k_reads_emit, dim3(grid_of((uint64_t)R + 1)), dim3(kBlock), 0, st, d_bytes, R, S.line_end.p, S.dst.p, S.rec_line.p,
-                           d_off, d_name_span);
+    const int format = rf_format_of((unsigned char)(h_res[8] & 0xffu));
+    out->format = format;
+    if (int r = S.misc.reserve(16, st, false)) return r;
+    if (format == SFGPU_READS_NONE) {
+        SF_HIP(hipMemsetAsync(S.misc.p, 0, 16, st));
+        hipLaunchKernelGGL(k_reads_blank, dim3(grid_of((n_bytes + 15) / 16)), dim3(kBlock), 0, st, d_text, n_bytes, S.misc.p);
         SF_HIP(hipGetLastError());
-        if (n_bases) {
-            hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, S.text.p, Lc, n_bases,
-                               S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
-            SF_HIP(hipGetLastError());
+        SF_HIP(hipMemcpyAsync(&h_res[8], S.misc.p, 16, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipStreamSynchronize(st));
+        if (h_res[8] == 0) {
+            out->n_lines = h_res[9] + (uint64_t)final;
+            out->consumed = final ? n_bytes : 0;
+            return SFGPU_OK;
         }
-        out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
+        out->error_record = 0; out->error_line = 0; out->error_kind = SFGPU_READS_BAD_START;
+        set_error("reads text: record 0: %s", kind_text(SFGPU_READS_BAD_START));
+        return SFGPU_ERR_FORMAT;
     }
-    SF_HIP(hipEventRecord(ev_p[6], st));
-    SF_HIP(hipStreamSynchronize(st));
-    double lines = 0.0;                                   // both halves or neither
-    if (add_elapsed(&lines, ev_p[1], ev_p[2]) && add_elapsed(&lines, ev_p[3], ev_p[4])) out->ms_kernels += lines;
-    if (rc == SFGPU_OK) add_elapsed(&out->ms_kernels, ev_p[5], ev_p[6]);
-    return rc;
+    SF_HIP(hipMemsetAsync(d_text + n_bytes, '\n', 1, st));
+    SF_HIP(hipMemsetAsync(d_text + n1, 0, padded - n1, st));
+    if (int r = S.nl_cnt.reserve(n_groups + 1, st, false)) return r;
+    if (int r = S.nl_scan.reserve(n_groups + 1, st, false)) return r;
+    SF_HIP(hipMemsetAsync(S.misc.p, 0xff, 8, st));
+    SF_HIP(hipMemsetAsync(S.misc.p + 1, 0, 8, st));
+    const uint4* text = reinterpret_cast<const uint4*>(d_text);
+    SF_HIP(hipEventRecord(ev_c0, st));
+    hipLaunchKernelGGL(k_reads_count, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, (uint64_t)0, n_groups, S.nl_cnt.p);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipEventRecord(ev_c1, st));
+    return parse_counted(S, text, n_bytes, format, final, max_reads, d_bases, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
+                         [&]() { add_elapsed(&out->ms_kernels, ev_c0, ev_c1); });
 }

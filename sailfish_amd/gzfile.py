@@ -1,9 +1,13 @@
 """gzip files written from device memory -- GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285) without the host
 compressor: the raw bytes of device tensors become one gzip member whose DEFLATE blocks are produced on the device
 (sfgpu_gz_open / sfgpu_gz_write_device / sfgpu_gz_close, sailfish_amd/csrc/gzwrite.hip).  Any gzip reader inflates the file to
-the bytes written, in order; the compressed bytes are not zlib's."""
+the bytes written, in order; the compressed bytes are not zlib's.
+
+`write_bgzf` is the host-side writer of the blocked form (BGZF) that `readfile.ReadFile` inflates on the device."""
 import ctypes as C
 import os
+import struct
+import zlib
 
 import torch
 
@@ -86,3 +90,37 @@ class GzDeviceWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")      # the empty member that ends a BGZF file
+
+
+def bgzf_member(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
+    """one BGZF member: gzip header with the 'BC' subfield (BSIZE = member bytes - 1), raw DEFLATE of `payload`, CRC-32, ISIZE"""
+    if len(payload) > 65536:
+        raise ValueError("a BGZF member holds at most 65536 bytes")
+    z = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    body = z.compress(payload) + z.flush()
+    total = 18 + len(body) + 8
+    if total > 65536:
+        raise ValueError(f"the member would be {total} bytes: lower member_bytes (65280 always fits)")
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", total - 1) + body
+            + struct.pack("<II", zlib.crc32(payload), len(payload)))
+
+
+def write_bgzf(path_or_file, data, level=6, member_bytes=65280, strategy=zlib.Z_DEFAULT_STRATEGY):
+    """`data` (bytes-like) as a BGZF file: members of member_bytes payload bytes each, deflated by zlib on the host, and the
+    28-byte EOF member.  Any gzip reader inflates it to `data`.  Returns the number of bytes written."""
+    if not 1 <= member_bytes <= 65536:
+        raise ValueError("member_bytes must be 1 .. 65536")
+    own = isinstance(path_or_file, (str, bytes, os.PathLike))
+    f = open(path_or_file, "wb") if own else path_or_file
+    try:
+        view, n = memoryview(data).cast("B"), 0
+        for a in range(0, len(view), member_bytes):
+            n += f.write(bgzf_member(bytes(view[a:a + member_bytes]), level, strategy))
+        n += f.write(BGZF_EOF)
+    finally:
+        if own:
+            f.close()
+    return n

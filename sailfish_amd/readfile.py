@@ -5,8 +5,11 @@
 as the `(uint8 bases, int64 offsets)` pairs that `QuasiIndex` and `QuasiIndex.map_reads` take.  Nothing is parsed on the host:
 the host reads the file, the device finds the records.
 
-A gzip file (detected by its magic bytes) is inflated on the host with Python's `gzip` module and fed through the same path;
-that path is bound by the host's inflate, not by the device."""
+A gzip file is detected by its magic bytes.  The blocked form (BGZF: what bgzip and the Illumina converters write, and
+`gzfile.write_bgzf`) is inflated on the device, one wavefront per member (sfgpu_bgzf_inflate_host, csrc/bgzf_read.hip), and parsed
+where it lands (sfgpu_reads_parse_device): the host reads the compressed file and hops over the member sizes, nothing else.
+Any other gzip file is one serial bit stream; it is inflated on the host with Python's `gzip` module and fed through the
+plain-text path, which is then bound by the host's inflate."""
 import ctypes as C
 import gzip
 
@@ -16,6 +19,9 @@ import torch
 from . import _lib
 
 MAX_TEXT = 1 << 30            # one parse call (sfgpu_reads_parse_host)
+BGZF_KINDS = {1: "not a BGZF member header", 2: "the member ends before its last block does", 3: "block type 3",
+              4: "a stored block's LEN and NLEN disagree", 5: "invalid code lengths", 6: "invalid literal/length or distance code",
+              7: "a match reaches before the member's first byte", 8: "the payload is not ISIZE bytes", 9: "CRC-32 mismatch"}
 KINDS = {1: "a record does not begin with '@' (or the file with neither '>' nor '@')",
          2: "the third line of the record does not begin with '+'",
          3: "quality and sequence differ in length",
@@ -79,26 +85,152 @@ class BlockCarry:
         return None
 
 
+def bgzf_member_bytes(head):
+    """bytes of the gzip member whose header begins `head` when it carries the BGZF 'BC' subfield (BSIZE + 1), else None"""
+    if len(head) < 18 or head[:3] != b"\x1f\x8b\x08" or not head[3] & 4:
+        return None
+    xlen = head[10] | head[11] << 8
+    p, end = 12, min(12 + xlen, len(head))
+    while p + 4 <= end:
+        slen = head[p + 2] | head[p + 3] << 8
+        if head[p:p + 2] == b"BC" and slen == 2 and p + 6 <= end:
+            return (head[p + 4] | head[p + 5] << 8) + 1
+        p += 4 + slen
+    return None
+
+
+class DeviceInflate:
+    """The carry-over around the device inflater and the device parser: compressed blocks in, the members that do not end in a block
+    in front of the next one; the inflated text stays in one device buffer, the parser's unconsumed tail is moved to its front
+    (device to device) and the next members are inflated behind it.  next() is BlockCarry.next for this path."""
+
+    def __init__(self, owner, stream, block_bytes):
+        self.o, self.stream, self.block_bytes = owner, stream, int(block_bytes)
+        self.cbuf = np.empty(max(self.block_bytes, 1 << 16), np.uint8)     # compressed bytes read and not inflated: cbuf[:chi]
+        self.chi = 0
+        self.file_off = 0                     # where cbuf[0] lies in the file
+        self.members = 0                      # members inflated so far
+        self.eof = False
+        self.text = None                      # device buffer; text[lo:hi] = inflated and not consumed
+        self.lo = self.hi = 0
+        self.records = 0
+        self.starved = True
+
+    def _read(self, want):
+        if want > self.cbuf.size:
+            grown = np.empty(max(want, 2 * self.cbuf.size), np.uint8)
+            grown[: self.chi] = self.cbuf[: self.chi]
+            self.cbuf = grown
+        while not self.eof and self.chi < want:
+            got = self.stream.readinto(memoryview(self.cbuf)[self.chi:want])
+            if not got:
+                self.eof = True
+            else:
+                self.chi += got
+
+    def _inflate_error(self, res):
+        m, off = int(res.error_member), self.file_off
+        for _ in range(m):                    # hop to the bad member for its offset (the error path only)
+            off += bgzf_member_bytes(bytes(self.cbuf[off - self.file_off:off - self.file_off + 65536]))
+        raise ValueError(f"{self.o.path}: gzip member {self.members + m} (byte {off} of the file) does not inflate: "
+                         f"{BGZF_KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
+
+    def _more(self):
+        """inflate the next block behind the unconsumed text; False at the end of the file"""
+        o, L = self.o, self.o._L
+        want = self.block_bytes
+        while True:
+            self._read(max(want, self.chi + 1) if self.chi >= want else want)
+            if self.chi == 0 and self.eof:
+                return False
+            tail = self.hi - self.lo
+            room = MAX_TEXT - 64 - tail
+            res = _lib.BgzfResult()
+            rc = L.sfgpu_bgzf_inflate_host(_lib.ptr(self.cbuf), self.chi, int(self.eof), None, room, C.byref(res), None)      # sizes only
+            if rc == _lib.ERR_FORMAT and res.n_members == 0:
+                self._inflate_error(res)
+            if res.n_members:
+                break
+            if self.eof:
+                return False
+            if self.chi >= MAX_TEXT:
+                raise ValueError(f"{o.path}: gzip member {self.members} does not end within 1 GiB")
+            want = max(want, self.chi) * 2
+        need = ((tail + int(res.n_bytes_out) + 1 + 15) & ~15) + 16       # what the parser asks for behind the text
+        with torch.cuda.device(o.device):
+            if self.text is None or self.text.numel() < need:
+                grown = torch.empty(max(need, 0 if self.text is None else 2 * self.text.numel()), dtype=torch.uint8, device=o.device)
+                if tail:
+                    grown[:tail] = self.text[self.lo:self.hi]
+                self.text = grown
+            elif self.lo and tail:
+                self.text[:tail] = self.text[self.lo:self.hi].clone()
+            self.lo, self.hi = 0, tail
+            res = _lib.BgzfResult()
+            rc = L.sfgpu_bgzf_inflate_host(_lib.ptr(self.cbuf), self.chi, int(self.eof), _lib.ptr(self.text[tail:]), room, C.byref(res),
+                                           _lib.current_stream_ptr())
+        if rc == _lib.ERR_FORMAT:
+            self._inflate_error(res)
+        _lib.check(rc)
+        n_out = int(res.n_bytes_out)
+        self.hi = tail + n_out
+        used = int(res.consumed)
+        self.cbuf[: self.chi - used] = self.cbuf[used:self.chi].copy()
+        self.chi -= used
+        self.file_off += used
+        self.members += int(res.n_members)
+        for k, v in (("ms_inflate", res.ms_kernels), ("ms_copy", res.ms_copy), ("bytes_compressed", used), ("members", int(res.n_members))):
+            o.stats[k] += v
+        return True
+
+    def next(self, max_reads):
+        while max_reads > 0:
+            if self.starved or self.hi == self.lo:
+                more = self._more()
+                self.starved = False
+                if not more and self.hi == self.lo:
+                    return None
+            final = self.eof and self.chi == 0
+            res = self.o._parse_device(self.text, self.lo, self.hi, final, max_reads, self.records)
+            if res.n_reads or final:
+                self.lo += res.consumed
+                self.records += res.n_reads
+                return res if res.n_reads else None
+            if self.hi - self.lo >= MAX_TEXT - (1 << 17):
+                raise ValueError(f"{self.o.path}: record {self.records} does not end within 1 GiB")
+            self.starved = True
+        return None
+
+
 class ReadFile:
     """A FASTA / FASTQ file (plain or gzip) read through the device parser.
 
     read(max_reads) -> (bases: uint8 device tensor, offsets: int64 device tensor [n + 1]) holding exactly max_reads records unless
     the file ends first (n == 0 at the end).  With names=True the record names (bytes) of the last read() are in `last_names`.
-    The gzip path inflates on the host and is bound by it."""
+    `inflate` says where a gzip file is inflated: "auto" takes the device for a BGZF file (its first member carries the 'BC'
+    subfield) and the host for any other gzip file, "host" forces Python's gzip; the attribute `inflate` is "device", "host" or
+    None (a plain file).  block_bytes counts bytes of the file as it is stored: compressed ones on the device path."""
 
-    def __init__(self, path, device="cuda", block_bytes=32 << 20, names=False):
+    def __init__(self, path, device="cuda", block_bytes=32 << 20, names=False, inflate="auto"):
+        if inflate not in ("auto", "host"):
+            raise ValueError("inflate must be 'auto' or 'host'")
         self.path = str(path)
         self.device = torch.device(device)
         self._L = _lib.lib()
         with open(self.path, "rb") as f:
-            magic = f.read(2)
-        self.gzipped = magic == b"\x1f\x8b"
-        self._f = gzip.open(self.path, "rb") if self.gzipped else open(self.path, "rb", buffering=0)
-        self._carry = BlockCarry(self._f, block_bytes, self.path)
+            head = f.read(4096)
+        self.gzipped = head[:2] == b"\x1f\x8b"
+        self.inflate = None if not self.gzipped else "device" if inflate == "auto" and bgzf_member_bytes(head) else "host"
         self._names = bool(names)
         self.last_names = []
         self.format = 0
-        self.stats = dict(calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0)
+        self.stats = dict(calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0, ms_inflate=0.0, bytes_compressed=0, members=0)
+        if self.inflate == "device":
+            self._f = open(self.path, "rb", buffering=0)
+            self._carry = DeviceInflate(self, self._f, block_bytes)
+        else:
+            self._f = gzip.open(self.path, "rb") if self.gzipped else open(self.path, "rb", buffering=0)
+            self._carry = BlockCarry(self._f, block_bytes, self.path)
 
     def _parse(self, text, final, max_reads):
         n = int(text.size)
@@ -127,10 +259,46 @@ class ReadFile:
             off = off.clone()
         return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names))
 
+    def _parse_device(self, text, lo, hi, final, max_reads, records):
+        """_parse for text[lo:hi] of a device buffer (lo is a multiple of 16 or the text is moved there first by the caller)"""
+        n = hi - lo
+        max_reads = int(min(max_reads, n // 2 + 1))
+        with torch.cuda.device(self.device):
+            if lo % 16:                                         # the parser wants its text at a 16-byte boundary
+                text[:n] = text[lo:hi].clone()
+                self._carry.lo, self._carry.hi, lo, hi = 0, n, 0, n
+            bases = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
+            off = torch.empty(max_reads + 1, dtype=torch.int64, device=self.device)
+            span = torch.empty(2 * max_reads, dtype=torch.int64, device=self.device) if self._names else None
+            res = _lib.ReadsResult()
+            view = text[lo:]
+            rc = self._L.sfgpu_reads_parse_device(_lib.ptr(view), n, view.numel(), int(final), max_reads, _lib.ptr(bases), n, _lib.ptr(off),
+                                                  _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
+        if rc == _lib.ERR_FORMAT:
+            raise ValueError(f"{self.path}: record {records + res.error_record} is malformed: "
+                             f"{KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
+        _lib.check(rc)
+        self.format = res.format or self.format
+        for k, v in (("calls", 1), ("bytes_parsed", n), ("ms_kernels", res.ms_kernels)):
+            self.stats[k] += v
+        names = None
+        if self._names and res.n_reads:                         # the bytes of the spans only come back
+            sp = span[: 2 * res.n_reads].view(-1, 2)
+            lens = sp[:, 1]
+            ends = torch.cumsum(lens, 0)
+            idx = torch.arange(int(ends[-1]), device=self.device) + torch.repeat_interleave(sp[:, 0] - (ends - lens), lens)
+            raw = view[idx].cpu().numpy().tobytes()
+            cuts = np.concatenate([[0], ends.cpu().numpy()]).tolist()
+            names = [raw[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        off = off[: res.n_reads + 1]
+        if 2 * off.numel() < max_reads:
+            off = off.clone()
+        return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names))
+
     def read(self, max_reads):
         parts, left = [], int(max_reads)
         while left > 0:
-            res = self._carry.next(self._parse, left)
+            res = self._carry.next(left) if self.inflate == "device" else self._carry.next(self._parse, left)
             if res is None:
                 break
             parts.append(res.payload)

@@ -37,7 +37,7 @@ enum {
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*) */
     SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
 };
 
@@ -259,6 +259,62 @@ typedef struct {
 } sfgpu_bgzf_result;
 SFGPU_API int sfgpu_bgzf_inflate_host(const void* h_src, uint64_t n_bytes, int final, uint8_t* d_dst, uint64_t cap_bytes,
                                       sfgpu_bgzf_result* out, sfgpu_stream stream);
+/* ORDINARY gzip (gzip, pigz, fastq-dump --gzip: one serial DEFLATE stream per member, of any length) inflated on the device,
+ * chunk by chunk.  The rules live in sailfish_amd/csrc/gzrdfmt.h.  The call's compressed bytes are cut into spans of chunk_bytes;
+ * in every span but the first a FINDER looks for the first bit position at which the decoder accepts a dynamic block header
+ * (a candidate; it may be false: there is no body check).  PASS A decodes from the known position and from every candidate, one
+ * wavefront each, into a ring of 32768 sixteen-bit symbols in which a match that reaches before the chunk copies "byte i of my
+ * predecessor's window"; a chunk stops where a block boundary is a candidate, behind a final block, or where the input ends.
+ * The CHAIN follows end = next start from the known position: the chunks it reaches are the call's chunks, every other candidate
+ * in front of its end is a false start whose work is discarded.  PROPAGATION resolves each chunk's window from its
+ * predecessor's, PASS B decodes every chain chunk again with that window as preset dictionary and writes bytes at the chunk's
+ * exact offset, and the chunks' CRC-32s are combined in order.  Behind a final block CRC-32 and ISIZE are compared and the call
+ * ends (member_end = 1); the next call starts the next member, so a file of many small members costs one call per member.
+ * Zero bytes behind a member are padding.
+ *
+ * A handle carries the stream's state from call to call: the last 32 KB emitted, the bit within the first unconsumed byte at
+ * which the next block begins, the running CRC-32 and length.  sfgpu_gzrd_open: chunk_bytes = 0 takes the default (16384);
+ * values below 64 are SFGPU_ERR_RANGE.
+ * sfgpu_gzrd_plan_host: h_src[0 .. n_bytes) begins at the byte that holds the handle's bit position (n_bytes <= 2^30 and at
+ * most 65536 spans, i.e. n_bytes <= 65536 * chunk_bytes, else SFGPU_ERR_RANGE).  The handle keeps device scratch for the emit:
+ * the compressed bytes, 64 KB of ring per span (4 x the compressed bytes at the default chunk_bytes, 4 GiB at the most) and
+ * 32 KB of resolved window per chain chunk; it grows to the largest call and goes back with sfgpu_gzrd_close.  It parses a member header when the handle is at one, stages the bytes, runs the finder, pass A, the chain
+ * and the propagation, and fills `res` without writing any payload: the chain's longest prefix whose output fits cap_bytes.
+ * need_cap != 0 says that not even the first chunk fits (its size).  n_chunks == 0 without an error and without need_cap says
+ * that no block ends within these bytes: call again with more (`consumed` bytes, padding in front of a header, may be dropped).
+ * A plan may be replaced by another plan; nothing advances until the emit.
+ * sfgpu_gzrd_emit: pass B for the planned chunks into d_dst[0 .. n_bytes_out) (any alignment), then the trailer checks; the
+ * handle advances and `res` is the plan's result with ms_emit and the final error_kind.
+ * Errors are SFGPU_ERR_FORMAT with error_kind (SFGPU_BGZF_*; BAD_HEADER here: not a gzip member header, CM != 8 or a reserved
+ * flag; TRUNCATED: with final != 0 the input ends inside a member) and error_offset, the byte of h_src at which the failing
+ * chunk (or header) starts.  An error of the plan ends the chain in front of the failing chunk; the emit that follows writes
+ * the chunks in front of it and returns the first error in stream order (DISTANCE_TOO_FAR shows in pass B only).  After an
+ * error the handle is to be closed.  Both calls are synchronous and ordered behind the work already on `stream`; no CPU path. */
+typedef struct sfgpu_gzrd sfgpu_gzrd;
+typedef struct {
+    uint64_t consumed;         /* whole bytes of h_src the caller may drop after the emit */
+    uint64_t n_bytes_out;      /* payload of the planned chunks */
+    uint64_t n_chunks;         /* chunks of the chain taken */
+    uint64_t n_candidates;     /* spans in which the finder accepted a header */
+    uint64_t n_false_starts;   /* candidates in front of the chain's end that the chain did not reach */
+    uint64_t n_stored_blocks;  /* DEFLATE blocks by type in the planned chunks */
+    uint64_t n_fixed_blocks;
+    uint64_t n_dynamic_blocks;
+    uint64_t need_cap;         /* the first chunk's payload when even that does not fit cap_bytes, else 0 */
+    uint64_t error_offset;     /* UINT64_MAX without an error */
+    int32_t member_end;        /* the planned chunks end a member */
+    int32_t error_kind;        /* SFGPU_BGZF_* */
+    double ms_copy;            /* device events around: the staged host-to-device copies, */
+    double ms_find;            /* the finder, */
+    double ms_decode;          /* pass A, */
+    double ms_propagate;       /* the window propagation, */
+    double ms_emit;            /* pass B */
+} sfgpu_gzrd_result;
+SFGPU_API int sfgpu_gzrd_open(sfgpu_gzrd** out, uint32_t chunk_bytes);
+SFGPU_API int sfgpu_gzrd_plan_host(sfgpu_gzrd* z, const void* h_src, uint64_t n_bytes, int final, uint64_t cap_bytes,
+                                   sfgpu_gzrd_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_gzrd_emit(sfgpu_gzrd* z, uint8_t* d_dst, sfgpu_gzrd_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_gzrd_close(sfgpu_gzrd* z);
 /* writeEquivCounts (src/GZipWriter.cpp:77-88), the other direction: the CLASS SECTION of an eq_classes.txt file formatted on the
  * device from a class table in CSR form (the sfgpu_eq_export_device arrays, a table merged by sfgpu_eqvec_merge_disjoint, or
  * one the caller assembled).  For each class, in the order given,

@@ -73,6 +73,17 @@ class BgzfResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class GzrdResult(C.Structure):
+    _fields_ = [("consumed", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_chunks", C.c_uint64), ("n_candidates", C.c_uint64),
+                ("n_false_starts", C.c_uint64), ("n_stored_blocks", C.c_uint64), ("n_fixed_blocks", C.c_uint64),
+                ("n_dynamic_blocks", C.c_uint64), ("need_cap", C.c_uint64), ("error_offset", C.c_uint64), ("member_end", C.c_int32),
+                ("error_kind", C.c_int32), ("ms_copy", C.c_double), ("ms_find", C.c_double), ("ms_decode", C.c_double),
+                ("ms_propagate", C.c_double), ("ms_emit", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class EqTextWriteResult(C.Structure):
     _fields_ = [("n_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("n_ids", C.c_uint64), ("n_chunks", C.c_uint64),
                 ("max_line_bytes", C.c_uint64), ("format_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -173,6 +184,10 @@ _SIGS = {
     "sfgpu_reads_parse_host": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_reads_parse_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_bgzf_inflate_host": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_uint64, C.POINTER(BgzfResult), _P]),
+    "sfgpu_gzrd_open": (C.c_int, [C.POINTER(_P), C.c_uint32]),
+    "sfgpu_gzrd_plan_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(GzrdResult), _P]),
+    "sfgpu_gzrd_emit": (C.c_int, [_P, _P, C.POINTER(GzrdResult), _P]),
+    "sfgpu_gzrd_close": (C.c_int, [_P]),
     "sfgpu_eqvec_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P, C.POINTER(EqTextWriteResult), _P]),
     "sfgpu_quant_write_text": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P, C.POINTER(QuantWriteResult), _P]),
     "sfgpu_genes_aggregate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, C.POINTER(GenesResult), _P]),

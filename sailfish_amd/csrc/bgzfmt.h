@@ -14,6 +14,10 @@
 //   bgz_finish         the checks behind the last block, in stream order
 //   bgz_inflate_member all of it serially
 //
+// gzrdfmt.h (ordinary gzip, chunk by chunk) has a SIBLING of bgz_inflate_body: gzr_dyn_header + gzr_decode_chunk run the same
+// statements with 64-bit output positions, a stop rule at block boundaries and a preset window.  A fix to the decode or to what
+// zlib accepts belongs in both.
+//
 // ERRORS (SFGPU_BGZF_*, include/sfgpu.h).  The first failed check in stream order is the member's error.  Where zlib and the
 // wording of RFC 1951 differ, zlib decides:
 //   - an incomplete code is BAD_CODE_LENGTHS, except that a literal/length or distance code of ONE code of one bit is accepted

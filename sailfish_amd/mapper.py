@@ -139,18 +139,19 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   **kw):
+                   inflate="auto", **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
-    batches are mapped and handed to quant.quantify as in quantify_reads.  -> (rc, experiment)"""
+    batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
+    -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, read_transcripts
-    names, (bases, off) = read_transcripts(transcripts_path, device)
+    names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
 
     def batches():
-        f1 = ReadFile(reads1_path, device)
-        f2 = None if reads2_path is None else ReadFile(reads2_path, device)
+        f1 = ReadFile(reads1_path, device, inflate=inflate)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device, inflate=inflate)
         try:
             while True:
                 r1 = f1.read(batch_reads)

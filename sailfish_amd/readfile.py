@@ -8,8 +8,10 @@ the host reads the file, the device finds the records.
 A gzip file is detected by its magic bytes.  The blocked form (BGZF: what bgzip and the Illumina converters write, and
 `gzfile.write_bgzf`) is inflated on the device, one wavefront per member (sfgpu_bgzf_inflate_host, csrc/bgzf_read.hip), and parsed
 where it lands (sfgpu_reads_parse_device): the host reads the compressed file and hops over the member sizes, nothing else.
-Any other gzip file is one serial bit stream; it is inflated on the host with Python's `gzip` module and fed through the
-plain-text path, which is then bound by the host's inflate."""
+Any other gzip file is one serial bit stream per member.  By default it is inflated on the host with Python's `gzip` module and
+fed through the plain-text path, which is then bound by the host's inflate; with inflate="device" it is inflated on the device
+chunk by chunk (sfgpu_gzrd_*, csrc/gz_read.hip: block starts are found speculatively, the chunks are decoded twice, the gzip
+trailer's CRC-32 says whether the result is right) and parsed where it lands, like a BGZF file."""
 import ctypes as C
 import gzip
 
@@ -22,6 +24,7 @@ MAX_TEXT = 1 << 30            # one parse call (sfgpu_reads_parse_host)
 BGZF_KINDS = {1: "not a BGZF member header", 2: "the member ends before its last block does", 3: "block type 3",
               4: "a stored block's LEN and NLEN disagree", 5: "invalid code lengths", 6: "invalid literal/length or distance code",
               7: "a match reaches before the member's first byte", 8: "the payload is not ISIZE bytes", 9: "CRC-32 mismatch"}
+GZ_KINDS = {**BGZF_KINDS, 1: "not a gzip member header", 2: "the file ends inside a member"}
 KINDS = {1: "a record does not begin with '@' (or the file with neither '>' nor '@')",
          2: "the third line of the record does not begin with '+'",
          3: "quality and sequence differ in length",
@@ -99,10 +102,11 @@ def bgzf_member_bytes(head):
     return None
 
 
-class DeviceInflate:
-    """The carry-over around the device inflater and the device parser: compressed blocks in, the members that do not end in a block
-    in front of the next one; the inflated text stays in one device buffer, the parser's unconsumed tail is moved to its front
-    (device to device) and the next members are inflated behind it.  next() is BlockCarry.next for this path."""
+class DeviceCarry:
+    """The carry-over around a device inflater and the device parser: compressed blocks in, the compressed bytes the inflater has
+    not consumed in front of the next block; the inflated text stays in one device buffer, the parser's unconsumed tail is moved to
+    its front (device to device) and the next text is inflated behind it.  next() is BlockCarry.next for this path; _more() is
+    the inflater's."""
 
     def __init__(self, owner, stream, block_bytes):
         self.o, self.stream, self.block_bytes = owner, stream, int(block_bytes)
@@ -127,6 +131,50 @@ class DeviceInflate:
                 self.eof = True
             else:
                 self.chi += got
+
+    def _place(self, n_out):
+        """room for n_out bytes behind the unconsumed text, which moves to the front of the (possibly grown) buffer -> its length"""
+        o, tail = self.o, self.hi - self.lo
+        need = ((tail + n_out + 1 + 15) & ~15) + 16       # what the parser asks for behind the text
+        if self.text is None or self.text.numel() < need:
+            grown = torch.empty(max(need, 0 if self.text is None else 2 * self.text.numel()), dtype=torch.uint8, device=o.device)
+            if tail:
+                grown[:tail] = self.text[self.lo:self.hi]
+            self.text = grown
+        elif self.lo and tail:
+            self.text[:tail] = self.text[self.lo:self.hi].clone()
+        self.lo, self.hi = 0, tail
+        return tail
+
+    def _drop(self, used):
+        self.cbuf[: self.chi - used] = self.cbuf[used:self.chi].copy()
+        self.chi -= used
+        self.file_off += used
+
+    def close(self):
+        pass
+
+    def next(self, max_reads):
+        while max_reads > 0:
+            if self.starved or self.hi == self.lo:
+                more = self._more()
+                self.starved = False
+                if not more and self.hi == self.lo:
+                    return None
+            final = self.eof and self.chi == 0
+            res = self.o._parse_device(self.text, self.lo, self.hi, final, max_reads, self.records)
+            if res.n_reads or final:
+                self.lo += res.consumed
+                self.records += res.n_reads
+                return res if res.n_reads else None
+            if self.hi - self.lo >= MAX_TEXT - (1 << 17):
+                raise ValueError(f"{self.o.path}: record {self.records} does not end within 1 GiB")
+            self.starved = True
+        return None
+
+
+class DeviceInflate(DeviceCarry):
+    """DeviceCarry for a BGZF file: the members that do not end in a block wait in front of the next one"""
 
     def _inflate_error(self, res):
         m, off = int(res.error_member), self.file_off
@@ -156,16 +204,8 @@ class DeviceInflate:
             if self.chi >= MAX_TEXT:
                 raise ValueError(f"{o.path}: gzip member {self.members} does not end within 1 GiB")
             want = max(want, self.chi) * 2
-        need = ((tail + int(res.n_bytes_out) + 1 + 15) & ~15) + 16       # what the parser asks for behind the text
         with torch.cuda.device(o.device):
-            if self.text is None or self.text.numel() < need:
-                grown = torch.empty(max(need, 0 if self.text is None else 2 * self.text.numel()), dtype=torch.uint8, device=o.device)
-                if tail:
-                    grown[:tail] = self.text[self.lo:self.hi]
-                self.text = grown
-            elif self.lo and tail:
-                self.text[:tail] = self.text[self.lo:self.hi].clone()
-            self.lo, self.hi = 0, tail
+            tail = self._place(int(res.n_bytes_out))
             res = _lib.BgzfResult()
             rc = L.sfgpu_bgzf_inflate_host(_lib.ptr(self.cbuf), self.chi, int(self.eof), _lib.ptr(self.text[tail:]), room, C.byref(res),
                                            _lib.current_stream_ptr())
@@ -175,31 +215,87 @@ class DeviceInflate:
         n_out = int(res.n_bytes_out)
         self.hi = tail + n_out
         used = int(res.consumed)
-        self.cbuf[: self.chi - used] = self.cbuf[used:self.chi].copy()
-        self.chi -= used
-        self.file_off += used
+        self._drop(used)
         self.members += int(res.n_members)
         for k, v in (("ms_inflate", res.ms_kernels), ("ms_copy", res.ms_copy), ("bytes_compressed", used), ("members", int(res.n_members))):
             o.stats[k] += v
         return True
 
-    def next(self, max_reads):
-        while max_reads > 0:
-            if self.starved or self.hi == self.lo:
-                more = self._more()
-                self.starved = False
-                if not more and self.hi == self.lo:
-                    return None
-            final = self.eof and self.chi == 0
-            res = self.o._parse_device(self.text, self.lo, self.hi, final, max_reads, self.records)
-            if res.n_reads or final:
-                self.lo += res.consumed
-                self.records += res.n_reads
-                return res if res.n_reads else None
-            if self.hi - self.lo >= MAX_TEXT - (1 << 17):
-                raise ValueError(f"{self.o.path}: record {self.records} does not end within 1 GiB")
-            self.starved = True
-        return None
+
+class DeviceGunzip(DeviceCarry):
+    """DeviceCarry for an ordinary gzip file: plan (finder, pass A, chain, propagation: sizes only) -> room in the text buffer ->
+    emit (pass B) behind the unconsumed text.  One call ends with a member at the latest, so a file of many small members costs
+    a call per member."""
+
+    def __init__(self, owner, stream, block_bytes, chunk_bytes=0):
+        super().__init__(owner, stream, block_bytes)
+        self.z = C.c_void_p()
+        self.failed = None                    # the error a plan found behind chunks that were still good (file offset in error_offset)
+        with torch.cuda.device(owner.device):
+            _lib.check(owner._L.sfgpu_gzrd_open(C.byref(self.z), chunk_bytes))
+
+    def close(self):
+        if self.z:
+            self.o._L.sfgpu_gzrd_close(self.z); self.z = C.c_void_p()
+
+    def _inflate_error(self, res):
+        at = int(res.error_offset) if res is self.failed else self.file_off + int(res.error_offset)
+        raise ValueError(f"{self.o.path}: gzip member {self.members} (byte {at} of the file) does not "
+                         f"inflate: {GZ_KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
+
+    def _more(self):
+        """inflate the next chunks behind the unconsumed text; False at the end of the file"""
+        o, L = self.o, self.o._L
+        if self.failed is not None:
+            self._inflate_error(self.failed)
+        want = self.block_bytes
+        with torch.cuda.device(o.device):
+            while True:
+                self._read(max(want, self.chi + 1) if self.chi >= want else want)
+                room = MAX_TEXT - 64 - (self.hi - self.lo)
+                res = _lib.GzrdResult()
+                rc = L.sfgpu_gzrd_plan_host(self.z, _lib.ptr(self.cbuf), self.chi, int(self.eof), room, C.byref(res), _lib.current_stream_ptr())
+                if rc == _lib.ERR_FORMAT and res.n_chunks == 0:
+                    self._inflate_error(res)
+                if rc != _lib.ERR_FORMAT:              # (an error behind good chunks: they are emitted first, see below)
+                    _lib.check(rc)
+                for k, v in (("ms_copy", res.ms_copy), ("ms_find", res.ms_find), ("ms_decode", res.ms_decode), ("ms_inflate", res.ms_decode),
+                             ("ms_propagate", res.ms_propagate)):
+                    o.stats[k] += v
+                if res.n_chunks:
+                    break
+                if res.need_cap:
+                    raise ValueError(f"{o.path}: one chunk of gzip member {self.members} holds {int(res.need_cap)} bytes: more than a call takes")
+                if res.consumed:                           # padding between members
+                    self._drop(int(res.consumed)); o.stats["bytes_compressed"] += int(res.consumed)
+                    continue
+                if self.eof:
+                    return False
+                if self.chi >= MAX_TEXT:
+                    raise ValueError(f"{o.path}: a block of gzip member {self.members} does not end within 1 GiB")
+                want = min(max(want, self.chi) * 2, MAX_TEXT)
+            tail = self._place(int(res.n_bytes_out))
+            planned = (res.error_kind, int(res.error_offset))
+            rc = L.sfgpu_gzrd_emit(self.z, _lib.ptr(self.text[tail:]), C.byref(res), _lib.current_stream_ptr())
+        if rc == _lib.ERR_FORMAT:
+            # Which error is it?  The emit returns the plan's own (kind, offset) only when every chunk in front of it decoded in
+            # pass B: an error of pass B names an earlier chunk (another offset), and a trailer check cannot coincide with a plan
+            # error, because the chain then ends in front of the final block.  Anything else means the text is not to be trusted.
+            if (res.error_kind, int(res.error_offset)) != planned or not planned[0]:
+                self._inflate_error(res)
+            # the plan's error lies behind these chunks: their records are delivered, the next call raises (as the BGZF path does)
+            self.failed = _lib.GzrdResult.from_buffer_copy(res)
+            self.failed.error_offset = self.file_off + int(res.error_offset)
+        else:
+            _lib.check(rc)
+        self.hi = tail + int(res.n_bytes_out)
+        used = int(res.consumed)
+        self._drop(used)
+        self.members += int(res.member_end)
+        for k, v in (("ms_emit", res.ms_emit), ("ms_inflate", res.ms_emit), ("bytes_compressed", used), ("members", int(res.member_end)), ("chunks", int(res.n_chunks)),
+                     ("candidates", int(res.n_candidates)), ("false_starts", int(res.n_false_starts))):
+            o.stats[k] += v
+        return True
 
 
 class ReadFile:
@@ -208,26 +304,31 @@ class ReadFile:
     read(max_reads) -> (bases: uint8 device tensor, offsets: int64 device tensor [n + 1]) holding exactly max_reads records unless
     the file ends first (n == 0 at the end).  With names=True the record names (bytes) of the last read() are in `last_names`.
     `inflate` says where a gzip file is inflated: "auto" takes the device for a BGZF file (its first member carries the 'BC'
-    subfield) and the host for any other gzip file, "host" forces Python's gzip; the attribute `inflate` is "device", "host" or
-    None (a plain file).  block_bytes counts bytes of the file as it is stored: compressed ones on the device path."""
+    subfield) and the host for any other gzip file, "host" forces Python's gzip, "device" takes the device for every gzip file
+    (a BGZF file member by member, any other chunk by chunk: DeviceGunzip); the attribute `inflate` is "device", "host" or None (a
+    plain file).  block_bytes counts bytes of the file as it is stored: compressed ones on the device path.  `stats` counts, for
+    an ordinary gzip file on the device, the chunks decoded, the block starts the finder accepted (candidates) and those of them
+    that the chain did not reach (false_starts); ms_inflate is there ms_decode (pass A) + ms_emit (pass B)."""
 
     def __init__(self, path, device="cuda", block_bytes=32 << 20, names=False, inflate="auto"):
-        if inflate not in ("auto", "host"):
-            raise ValueError("inflate must be 'auto' or 'host'")
+        if inflate not in ("auto", "host", "device"):
+            raise ValueError("inflate must be 'auto', 'host' or 'device'")
         self.path = str(path)
         self.device = torch.device(device)
         self._L = _lib.lib()
         with open(self.path, "rb") as f:
             head = f.read(4096)
         self.gzipped = head[:2] == b"\x1f\x8b"
-        self.inflate = None if not self.gzipped else "device" if inflate == "auto" and bgzf_member_bytes(head) else "host"
+        bgzf = self.gzipped and bgzf_member_bytes(head) is not None
+        self.inflate = None if not self.gzipped else "device" if inflate == "device" or (inflate == "auto" and bgzf) else "host"
         self._names = bool(names)
         self.last_names = []
         self.format = 0
-        self.stats = dict(calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0, ms_inflate=0.0, bytes_compressed=0, members=0)
+        self.stats = dict(calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0, ms_inflate=0.0, bytes_compressed=0, members=0,
+                          chunks=0, candidates=0, false_starts=0, ms_find=0.0, ms_decode=0.0, ms_propagate=0.0, ms_emit=0.0)
         if self.inflate == "device":
             self._f = open(self.path, "rb", buffering=0)
-            self._carry = DeviceInflate(self, self._f, block_bytes)
+            self._carry = (DeviceInflate if bgzf else DeviceGunzip)(self, self._f, block_bytes)
         else:
             self._f = gzip.open(self.path, "rb") if self.gzipped else open(self.path, "rb", buffering=0)
             self._carry = BlockCarry(self._f, block_bytes, self.path)
@@ -318,6 +419,8 @@ class ReadFile:
     def close(self):
         if self._f is not None:
             self._f.close(); self._f = None
+            if self.inflate == "device":
+                self._carry.close()
 
     def __enter__(self):
         return self
@@ -326,10 +429,10 @@ class ReadFile:
         self.close()
 
 
-def read_transcripts(path, device="cuda", block_bytes=32 << 20):
+def read_transcripts(path, device="cuda", block_bytes=32 << 20, inflate="auto"):
     """a transcript FASTA (or FASTQ) whole -> (names: list of str, (bases, offsets) on the device); the names are sliced on the
     host from the name spans the parser reports"""
-    with ReadFile(path, device, block_bytes, names=True) as rf:
+    with ReadFile(path, device, block_bytes, names=True, inflate=inflate) as rf:
         bases, off = rf.read(1 << 62)
         names = [nm.decode("utf-8", "replace") for nm in rf.last_names]
     if off.numel() <= 1:

@@ -4,11 +4,14 @@ level 6, and plain.
   bgzf_device   ReadFile(bgzf): the device inflater (sfgpu_bgzf_inflate_host) and the parse of the device text
   bgzf_host     ReadFile(bgzf, inflate="host"): Python's gzip on one host thread, then the plain-text path -- what a .gz file cost
                 before the device inflater
-  gzip_host     ReadFile(ordinary gzip): the same host path, the only one such a file has
+  gzip_host     ReadFile(ordinary gzip): the same host path, what inflate="auto" chooses for such a file
+  gzip_device   ReadFile(ordinary gzip, inflate="device"): the chunked device inflater (sfgpu_gzrd_*: finder, two decode passes,
+                window propagation) and the parse of the device text
   plain         ReadFile(plain text): the floor of every compressed path
-and, beside the four, bgzf_device_one_block: the device path with block_bytes = the file's size, so that all members are in one
-launch (the inflate kernel is bound by the decode latency of one member, so its rate grows with the members in flight).
-The four results are compared (bases and offsets, equal) BEFORE any time is reported.  *_s are host wall time
+and, beside them, bgzf_device_one_block and gzip_device_one_block: the device paths with block_bytes = the file's size, so that all
+members (chunks) are in one launch (the inflate kernels are bound by the decode latency of one member or chunk, so their rate
+grows with the number in flight).
+The results are compared (bases and offsets, equal) BEFORE any time is reported.  *_s are host wall time
 (time.perf_counter) around open .. read(all) .. torch.cuda.synchronize(); ms_* are the library's device events summed over the
 calls of a file.  The first run of each path warms code objects, pools and the page cache and is dropped; the other --repeats
 are all reported, with their medians.
@@ -49,7 +52,7 @@ def run(path, dev, repeats, **kw):
         print(f"# {os.path.basename(path)} {kw} {rows[-1]['wall_s']:.3f} s", file=sys.stderr, flush=True)
     runs = rows[1:]
     out = dict(file_bytes=os.path.getsize(path), runs=runs, wall_s_median=statistics.median(r["wall_s"] for r in runs))
-    for k in ("ms_inflate", "ms_copy", "ms_kernels"):
+    for k in ("ms_inflate", "ms_copy", "ms_kernels", "ms_find", "ms_decode", "ms_propagate", "ms_emit", "chunks", "candidates", "false_starts"):
         out[k + "_median"] = statistics.median(r[k] for r in runs)
     return out, result
 
@@ -85,8 +88,11 @@ def main():
         rec["plain"], results["plain"] = run(plain, dev, a.repeats)
         rec["bgzf_host"], results["bgzf_host"] = run(bgzf, dev, a.repeats, inflate="host")
         rec["gzip_host"], results["gzip_host"] = run(gz, dev, a.repeats)
+        rec["gzip_device"], results["gzip_device"] = run(gz, dev, a.repeats, inflate="device")
+        rec["gzip_device_one_block"], results["gzip_device_one_block"] = run(gz, dev, a.repeats, inflate="device", block_bytes=os.path.getsize(gz))
     assert rec["bgzf_device"]["runs"][0]["inflate"] == "device" and rec["bgzf_host"]["runs"][0]["inflate"] == "host"
     assert rec["gzip_host"]["runs"][0]["inflate"] == "host" and rec["plain"]["runs"][0]["inflate"] is None
+    assert rec["gzip_device"]["runs"][0]["inflate"] == "device" and rec["gzip_device"]["runs"][0]["chunks"] > 1
     for k, (b, o) in results.items():               # equal before any figure counts
         assert torch.equal(b, results["plain"][0]) and torch.equal(o, results["plain"][1]), f"{k} differs from the plain file's result"
     rec["records"] = int(results["plain"][1].numel()) - 1
@@ -96,6 +102,11 @@ def main():
     rec["device_over_plain"] = d["wall_s_median"] / p["wall_s_median"]
     rec["inflate_output_GB_per_s"] = rec["text_bytes"] / (d["ms_inflate_median"] * 1e-3) / 1e9
     rec["inflate_output_GB_per_s_one_block"] = rec["text_bytes"] / (rec["bgzf_device_one_block"]["ms_inflate_median"] * 1e-3) / 1e9
+    g, gh = rec["gzip_device"], rec["gzip_host"]
+    rec["gzip_device_faster_than_host"] = g["wall_s_median"] < gh["wall_s_median"]
+    rec["gzip_host_over_device"] = gh["wall_s_median"] / g["wall_s_median"]
+    rec["gzip_host_over_device_one_block"] = gh["wall_s_median"] / rec["gzip_device_one_block"]["wall_s_median"]
+    rec["gzip_device_over_bgzf_device"] = g["wall_s_median"] / d["wall_s_median"]
     print(json.dumps(rec))
     with open(os.path.join(a.out, "readgz_probe.json"), "w") as f:
         json.dump(rec, f, indent=1)

@@ -426,6 +426,80 @@ SFGPU_API int sfgpu_genes_write_text(const char* d_names, const uint64_t* d_name
                                      const double* d_length, const double* d_eff, const double* d_tpm, const double* d_num_reads,
                                      uint64_t n_rows, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                      sfgpu_quant_write_result* out, sfgpu_stream stream);
+/* readTranscriptToGeneMap / transcriptGeneMapFromGTF (src/SailfishUtils.cpp:322-507) and TranscriptGeneMap::findTranscriptID: the
+ * `--geneMap` file read on the device and joined to the transcript names there.  What the two forms of the file say is stated
+ * once, serially, in csrc/gtffmt.h (the rules of genes.TranscriptGeneMap.from_gtf / .from_file); the kernels are csrc/genemap.hip.
+ * A map is built from many text blocks, so it is a handle:
+ *   open     kind = SFGPU_GMAP_GTF (records of 9 tab-separated columns; key[0 .. key_len) names the attribute that groups
+ *            transcripts, any bytes, "gene_id" in the reference's default) or SFGPU_GMAP_TSV (`transcript gene` token pairs; the
+ *            key is ignored and may be NULL).
+ *   add_text_host / _device   the conventions of sfgpu_reads_parse_host / _device: the text begins at a line start, whole lines
+ *            are consumed (`consumed` = one past the last '\n'; with final != 0 everything, a last line without '\n' included) and
+ *            the caller carries the tail in front of the next block.  n_bytes <= 2^30 (SFGPU_ERR_RANGE); a text without any '\n'
+ *            that is not final is SFGPU_ERR_RANGE with consumed = 0 (a line longer than the block: present more).  The device form
+ *            wants d_text 16-byte aligned with cap_text >= round16(n_bytes + 1) + 16 bytes (else SFGPU_ERR_INVALID) and writes into
+ *            that slack.  The names of the records are compacted into storage of the handle: the text is not needed after the call.
+ *            needs_host != 0 (SFGPU_GMAP_HOST_* bits) says that the consumed text holds something the device rules do not parse --
+ *            a byte >= 0x80, a NUL, a '\r' not followed by '\n', a name longer than 256 bytes; nothing of that text is stored then,
+ *            the handle stays flagged and finish reports the same bits: the caller reads the file with the host reader.
+ *   finish   sorts the transcripts bytewise (stable, so a GTF transcript takes the value of its first record in file order that
+ *            carries the key, and equal names of a two-column map keep file order), removes the duplicate ids of a GTF, numbers
+ *            the genes by first appearance (GTF: in sorted transcript order; two-column: in file order) and builds the tables.
+ *            More than 2^32 - 1 records is SFGPU_ERR_RANGE (raised by the add call that passes it).
+ *   export   copies the tables to the caller's device arrays: d_tnames / d_tname_off[n_transcripts + 1] the sorted transcript
+ *            names back to back, d_t2g[n_transcripts], d_gnames / d_gname_off[n_genes + 1] the gene names in id order (the layout
+ *            sfgpu_genes_write_text takes).  Any pointer may be NULL.
+ *   lookup   findTranscriptID for every row: lower_bound (bytewise, a prefix first) of the row's name d_names[d_name_off[r] ..
+ *            d_name_off[r + 1]) in the sorted transcript names, with NO equality test; d_gene_of_row[r] = t2g[position], or
+ *            0xFFFFFFFF past the last name (such rows are counted in *n_past: the transcript is "its own gene").
+ *   from_host   a finished handle from tables the host reader built (what the caller does with a needs_host file): names back to
+ *            back with n + 1 offsets each (host arrays; t2g[i] < n_genes, the transcript names sorted bytewise, else
+ *            SFGPU_ERR_INVALID), so that lookup and export serve either kind of map.
+ * export and lookup before finish, add after it, and finish on a flagged handle are SFGPU_ERR_STATE.  All calls are synchronous and
+ * ordered behind the work already on `stream`; one handle is used from one thread at a time.  No CPU path. */
+typedef struct sfgpu_gmap sfgpu_gmap;
+enum {
+    SFGPU_GMAP_GTF = 0,
+    SFGPU_GMAP_TSV = 1
+};
+enum {
+    SFGPU_GMAP_HOST_HIGH_BYTE = 1,
+    SFGPU_GMAP_HOST_NUL = 2,
+    SFGPU_GMAP_HOST_LONE_CR = 4,
+    SFGPU_GMAP_HOST_LONG_NAME = 8
+};
+typedef struct {
+    uint64_t n_lines;      /* lines consumed by this call */
+    uint64_t n_records;    /* GTF: records (lines with a transcript_id) stored; two-column: tokens stored */
+    uint64_t consumed;     /* bytes of the text the caller may drop */
+    uint32_t needs_host;   /* SFGPU_GMAP_HOST_* bits */
+    uint32_t pad_;
+    double ms_copy;        /* device events around the staged host-to-device copies (0 for the device form) */
+    double ms_kernels;     /* device events around the kernels and scans of the call */
+} sfgpu_gmap_add_result;
+typedef struct {
+    uint64_t n_records;       /* GTF records / two-column pairs the map is built from */
+    uint64_t n_transcripts;
+    uint64_t n_genes;
+    uint64_t tname_bytes;     /* sizes of the two name blobs */
+    uint64_t gname_bytes;
+    uint32_t needs_host;
+    uint32_t sort_rounds;     /* 8-byte refinement rounds of the transcript sort */
+    double ms_kernels;
+} sfgpu_gmap_result;
+SFGPU_API int sfgpu_gmap_open(sfgpu_gmap** out, int kind, const char* key, uint32_t key_len);
+SFGPU_API int sfgpu_gmap_from_host(sfgpu_gmap** out, const char* h_tnames, const uint64_t* h_tname_off, const uint32_t* h_t2g,
+                                   uint64_t n_transcripts, const char* h_gnames, const uint64_t* h_gname_off, uint64_t n_genes);
+SFGPU_API int sfgpu_gmap_add_text_host(sfgpu_gmap* m, const char* h_text, uint64_t n_bytes, int final, sfgpu_gmap_add_result* res,
+                                       sfgpu_stream stream);
+SFGPU_API int sfgpu_gmap_add_text_device(sfgpu_gmap* m, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final,
+                                         sfgpu_gmap_add_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_gmap_finish(sfgpu_gmap* m, sfgpu_gmap_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_gmap_export(sfgpu_gmap* m, char* d_tnames, uint64_t* d_tname_off, uint32_t* d_t2g, char* d_gnames,
+                                uint64_t* d_gname_off, sfgpu_stream stream);
+SFGPU_API int sfgpu_gmap_lookup(sfgpu_gmap* m, const char* d_names, const uint64_t* d_name_off, uint64_t n_rows,
+                                uint32_t* d_gene_of_row, uint64_t* n_past, sfgpu_stream stream);
+SFGPU_API int sfgpu_gmap_close(sfgpu_gmap* m);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

@@ -14,6 +14,7 @@
 //   sailfish::gpu::writeBootstraps                src/GZipWriter.cpp:249-285 (bootstraps.gz compressed on the device)
 //   sailfish::gpu::writeAbundances                src/GZipWriter.cpp:194-248 (the rows of quant.sf are formatted on the device)
 //   sailfish::gpu::aggregateEstimatesToGeneLevel  src/SailfishUtils.cpp:929-1037 (genes folded and formatted on the device)
+//   sailfish::gpu::readTranscriptToGeneMap        src/SailfishUtils.cpp:322-507 (the --geneMap file read, sorted and joined on the device)
 //
 // Header only; needs sfgpu.h, the HIP runtime API (hipMalloc / hipMemcpy for the caller-owned buffers the ABI takes)
 // and C++14.  No Boost, TBB, spdlog or Eigen: the logger is a std::function<void(int level, const std::string&)>.
@@ -457,6 +458,116 @@ inline bool aggregateEstimatesToGeneLevel(GeneNameOf&& geneName, ReadExperiment&
     out.close();
     if (!out) throw std::runtime_error(genesFile + ": write failed");
     return true;
+}
+
+// ---- TranscriptGeneMap read and joined on the device (sfgpu_gmap_*) ----------------------------------------------------------
+// The map of a --geneMap file as a device handle: sorted transcript names, t2g and gene names (include/TranscriptGeneMap.hpp),
+// built by readTranscriptToGeneMap below.
+class DeviceGeneMap {
+  public:
+    DeviceGeneMap(int kind, const std::string& key) { check(sfgpu_gmap_open(&h_, kind, key.data(), static_cast<uint32_t>(key.size())), "sfgpu_gmap_open"); }
+    DeviceGeneMap(const DeviceGeneMap&) = delete;
+    DeviceGeneMap& operator=(const DeviceGeneMap&) = delete;
+    ~DeviceGeneMap() { (void)sfgpu_gmap_close(h_); }
+    sfgpu_gmap* get() const { return h_; }
+    uint64_t numTranscripts() const { return info.n_transcripts; }
+    uint64_t numGenes() const { return info.n_genes; }
+    sfgpu_gmap_result info = sfgpu_gmap_result();      // filled by finish
+  private:
+    sfgpu_gmap* h_ = nullptr;
+};
+
+// readTranscriptToGeneMap / transcriptGeneMapFromGTF (src/SailfishUtils.cpp:322-507): a file whose extension is .gtf is read as GTF
+// (`key` names the attribute that groups transcripts), anything else as `transcript gene` pairs.  The file goes to the device
+// block by block (sfgpu_gmap_add_text_host; the unconsumed tail of a block is carried in front of the next) and is parsed,
+// sorted and numbered there.  Throws std::runtime_error when the file cannot be read, or holds what the device rules do not
+// parse (a non-ASCII byte, a NUL, a lone '\r', a name longer than 256 bytes: sfgpu.h) -- this adaptor has no host reader.
+// A gzip-compressed map is not inflated here (the Python side does that): its bytes are flagged and refused like any other
+// non-text.  blockBytes is cut to the 2^30 bytes one call takes.
+inline std::unique_ptr<DeviceGeneMap> readTranscriptToGeneMap(const std::string& path, const std::string& key = "gene_id",
+                                                              size_t blockBytes = size_t(32) << 20) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error(path + ": cannot open the gene map");
+    const bool gtf = path.size() >= 4 && path.compare(path.size() - 4, 4, ".gtf") == 0;
+    std::unique_ptr<DeviceGeneMap> m(new DeviceGeneMap(gtf ? SFGPU_GMAP_GTF : SFGPU_GMAP_TSV, key));
+    if (blockBytes > (size_t(1) << 29)) blockBytes = size_t(1) << 29;      // a block and the tail in front of it: one call takes 2^30 bytes
+    std::vector<char> buf;
+    bool eof = false;
+    while (!eof) {
+        const size_t had = buf.size();
+        buf.resize(had + (blockBytes ? blockBytes : 1));
+        in.read(buf.data() + had, static_cast<std::streamsize>(buf.size() - had));
+        buf.resize(had + static_cast<size_t>(in.gcount()));
+        eof = in.eof();
+        if (in.bad()) throw std::runtime_error(path + ": read failed");
+        sfgpu_gmap_add_result r;
+        const int rc = sfgpu_gmap_add_text_host(m->get(), buf.data(), buf.size(), eof ? 1 : 0, &r, nullptr);
+        if (rc == SFGPU_ERR_RANGE && r.consumed == 0 && !eof && buf.size() < (size_t(1) << 30)) continue;      // no line ends yet: read on
+        check(rc, "sfgpu_gmap_add_text_host");
+        if (r.needs_host) throw std::runtime_error(path + ": the gene map holds bytes the device reader does not parse");
+        buf.erase(buf.begin(), buf.begin() + static_cast<std::ptrdiff_t>(r.consumed));
+    }
+    check(sfgpu_gmap_finish(m->get(), &m->info, nullptr), "sfgpu_gmap_finish");
+    return m;
+}
+
+// aggregateEstimatesToGeneLevel with the map on the device: the transcript names of readExp are joined to it there
+// (sfgpu_gmap_lookup: TranscriptGeneMap::findTranscriptID, lower_bound with no equality test) and the gene names are written from
+// the map's own table.  Only when a transcript sorts past the map's last name -- it is then its own gene, keyed by its name --
+// are the ids of those rows resolved on the host.  The file is the one the functor form writes with tgm.geneName.
+inline bool aggregateEstimatesToGeneLevel(const DeviceGeneMap& tgm, ReadExperiment& readExp, const SailfishOpts& sopt, const std::string& genesFile) {
+    std::ofstream out(genesFile, std::ios::binary);
+    if (!out) throw std::runtime_error(genesFile + ": cannot open for writing");
+    out << "Name\tLength\tEffectiveLength\tTPM\tNumReads\n";
+    detail::AbundanceColumns c(readExp, sopt);
+    if (c.M) {
+        uint64_t G = tgm.numGenes(), nPast = 0;
+        DeviceBuf<uint32_t> dGeneOfRow(c.M);
+        check(sfgpu_gmap_lookup(tgm.get(), c.names.get(), c.off.get(), c.M, dGeneOfRow.get(), &nPast, nullptr), "sfgpu_gmap_lookup");
+        DeviceBuf<char> dNames(static_cast<size_t>(tgm.info.gname_bytes));
+        DeviceBuf<uint64_t> dOff(static_cast<size_t>(G + 1));
+        check(sfgpu_gmap_export(tgm.get(), nullptr, nullptr, nullptr, dNames.get(), dOff.get(), nullptr), "sfgpu_gmap_export");
+        if (nPast) {
+            std::vector<char> gNames = dNames.download();
+            std::vector<uint64_t> gOff = dOff.download();
+            std::vector<uint32_t> geneOfRow = dGeneOfRow.download();
+            std::unordered_map<std::string, uint32_t> idOf;
+            for (uint64_t g = 0; g < G; ++g) idOf.emplace(std::string(gNames.data() + gOff[g], gNames.data() + gOff[g + 1]), static_cast<uint32_t>(g));
+            auto& txps = readExp.transcripts();
+            for (uint64_t i = 0; i < c.M; ++i) {
+                if (geneOfRow[i] != 0xFFFFFFFFu) continue;
+                const std::string& g = txps[i].RefName;
+                auto it = idOf.find(g);
+                if (it == idOf.end()) {
+                    it = idOf.emplace(g, static_cast<uint32_t>(gOff.size() - 1)).first;
+                    gNames.insert(gNames.end(), g.begin(), g.end());
+                    gOff.push_back(gNames.size());
+                }
+                geneOfRow[i] = it->second;
+            }
+            G = gOff.size() - 1;
+            dGeneOfRow.upload(geneOfRow);
+            dNames.resize(gNames.size()); dNames.upload(gNames);
+            dOff.resize(gOff.size()); dOff.upload(gOff);
+        }
+        const size_t cap = static_cast<size_t>(G < c.M ? G : c.M);
+        DeviceBuf<uint32_t> dGeneId(cap);
+        DeviceBuf<double> gLen(cap), gEff(cap), gTpm(cap), gCnt(cap);
+        sfgpu_genes_result ar;
+        check(sfgpu_genes_aggregate(dGeneOfRow.get(), c.len.get(), c.eff.get(), c.tpm.get(), c.cnt.get(), c.M, G, 1, dGeneId.get(), gLen.get(),
+                                    gEff.get(), gTpm.get(), gCnt.get(), &ar, nullptr), "sfgpu_genes_aggregate");
+        sfgpu_quant_write_result r;
+        const int rc = sfgpu_genes_write_text(dNames.get(), dOff.get(), G, dGeneId.get(), gLen.get(), gEff.get(), gTpm.get(), gCnt.get(),
+                                              ar.n_genes, 0, detail::ofstream_sink, &out, &r, nullptr);
+        if (rc == SFGPU_ERR_IO) throw std::runtime_error(genesFile + ": write failed");
+        check(rc, "sfgpu_genes_write_text");
+    }
+    out.close();
+    if (!out) throw std::runtime_error(genesFile + ": write failed");
+    return true;
+}
+inline bool aggregateEstimatesToGeneLevel(DeviceGeneMap& tgm, ReadExperiment& readExp, const SailfishOpts& sopt, const std::string& genesFile) {
+    return aggregateEstimatesToGeneLevel(static_cast<const DeviceGeneMap&>(tgm), readExp, sopt, genesFile);
 }
 
 // ---- GZipWriter::writeBootstrap<T>, src/GZipWriter.cpp:249-285 ----------------------------------------------------------------

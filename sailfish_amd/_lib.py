@@ -108,6 +108,22 @@ class GenesResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GmapAddResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("consumed", C.c_uint64), ("needs_host", C.c_uint32),
+                ("pad_", C.c_uint32), ("ms_copy", C.c_double), ("ms_kernels", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
+class GmapResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_transcripts", C.c_uint64), ("n_genes", C.c_uint64), ("tname_bytes", C.c_uint64),
+                ("gname_bytes", C.c_uint64), ("needs_host", C.c_uint32), ("sort_rounds", C.c_uint32), ("ms_kernels", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class GzResult(C.Structure):
     _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("encode_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -193,6 +209,14 @@ _SIGS = {
     "sfgpu_genes_aggregate": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, _P, _P, _P, _P, C.POINTER(GenesResult), _P]),
     "sfgpu_genes_write_text": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
                                          C.POINTER(QuantWriteResult), _P]),
+    "sfgpu_gmap_open": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_uint32]),
+    "sfgpu_gmap_from_host": (C.c_int, [C.POINTER(_P), _P, _P, _P, C.c_uint64, _P, _P, C.c_uint64]),
+    "sfgpu_gmap_add_text_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.POINTER(GmapAddResult), _P]),
+    "sfgpu_gmap_add_text_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(GmapAddResult), _P]),
+    "sfgpu_gmap_finish": (C.c_int, [_P, C.POINTER(GmapResult), _P]),
+    "sfgpu_gmap_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "sfgpu_gmap_lookup": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P]),
+    "sfgpu_gmap_close": (C.c_int, [_P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),

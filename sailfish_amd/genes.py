@@ -6,8 +6,10 @@ aggregateEstimatesToGeneLevel (src/SailfishUtils.cpp:929-1037) and generateGeneL
 aggregate_estimates_to_gene_level is the host restatement: it reads the PRINTED quant.sf back (so the 6-significant-digit
 values), row by row.  aggregate_columns is the product path of `quantify(..., gene_map=...)`: the same file from the columns
 where they lie on the device (sfgpu_genes_aggregate rounds them to their printed values, folds the genes with the function
-of csrc/genefold.h and sfgpu_genes_write_text formats the rows), byte for byte; only the name lookup (vectorised,
-TranscriptGeneMap.gene_ids_of) and the comment lines stay on the host.  The arithmetic is restated literally,
+of csrc/genefold.h and sfgpu_genes_write_text formats the rows), byte for byte.  With a DeviceGeneMap -- the map file read on
+the device (sfgpu_gmap_*, csrc/genemap.hip; the rules of the two readers below restated in csrc/gtffmt.h) -- the names are
+joined there as well (sfgpu_gmap_lookup) and only the comment lines stay on the host; with a TranscriptGeneMap the name lookup
+(vectorised, TranscriptGeneMap.gene_ids_of) is host work.  The arithmetic is restated literally,
 including two quirks a drop-in must keep:
   * totalTPM accumulates the RUNNING gene sum (`totalTPM += expVals[tpmIdx]` after the add, :1004-1009), so the
     TPM-weighted gene lengths are weighted by tpm_i / (sum of prefix sums), not by tpm_i / sum;
@@ -21,7 +23,10 @@ the grouping key is gene_id, gene_name, or any attribute named by `agg_key`; tra
 numbered by first appearance in that order.  Parity unpinned for this reader (no reference vector exists for it)."""
 import bisect
 import ctypes as C
+import gzip
 import os
+import tempfile
+import time
 
 import numpy as np
 
@@ -148,6 +153,283 @@ class TranscriptGeneMap:
         return ids.astype(np.uint32), table
 
 
+HOST_REASONS = {1: "a byte >= 0x80", 2: "a NUL byte", 4: "a '\\r' that is not followed by '\\n'", 8: "a name longer than 256 bytes"}
+
+
+class _TimedReader:
+    """readinto of a binary stream, with the seconds it took"""
+
+    def __init__(self, f):
+        self.f, self.seconds = f, 0.0
+
+    def readinto(self, b):
+        t0 = time.perf_counter()
+        n = self.f.readinto(b)
+        self.seconds += time.perf_counter() - t0
+        return n
+
+
+class DeviceGeneMap:
+    """A --geneMap file as tables on the device: the sorted transcript names, t2g and the gene names of the TranscriptGeneMap that
+    from_gtf / from_file give for the same file (to_host() returns exactly that), built without a per-line host loop
+    (sfgpu_gmap_add_text_host / _device, sfgpu_gmap_finish) and joined to transcript names without host strings (lookup).
+
+    from_path: an extension .gtf selects the GTF rules, anything else the two-column rules (generate_gene_level_estimates' rule); a
+    gzip file is detected by its magic bytes and the rules are then chosen from the extension under a trailing .gz.  The file is
+    read in blocks of block_bytes (at least 64; bytes of the file as stored) and the unconsumed tail is carried by the carriers of
+    `readfile`: BlockCarry for a plain file and for a gzip file inflated by Python's gzip, DeviceInflate / DeviceGunzip for one
+    inflated on the device, with this class's parse callback in place of ReadFile's.  `inflate` is ReadFile's: "auto" takes the
+    device for a BGZF file and the host for any other gzip file.
+    A file that holds what the device rules do not parse (csrc/gtffmt.h: a non-ASCII byte, a NUL, a lone CR, a name longer than
+    256 bytes) is read by the host reader and uploaded (sfgpu_gmap_from_host): stats["reader"] is "host" and stats["reason"] says
+    why; otherwise stats["reader"] is "device".  stats also holds the seconds spent reading the file (read_s), the device times
+    of the calls (ms_copy, ms_kernels, ms_finish), calls, bytes, lines, records, sort_rounds."""
+
+    MIN_BLOCK = 64
+
+    def __init__(self, handle, device, is_gtf, stats):
+        self._h, self.device, self.is_gtf, self.stats = handle, device, is_gtf, stats
+        self._host = self._tables = None
+
+    # ---- reading
+    @classmethod
+    def from_path(cls, path, agg_key="gene_id", device="cuda", block_bytes=32 << 20, inflate="auto"):
+        import torch
+
+        from . import _lib, readfile
+        if inflate not in ("auto", "host", "device"):
+            raise ValueError("inflate must be 'auto', 'host' or 'device'")
+        if int(block_bytes) < cls.MIN_BLOCK:
+            raise ValueError(f"block_bytes must be at least {cls.MIN_BLOCK}")
+        path = str(path)
+        device = torch.device(device)
+        with open(path, "rb") as f:
+            head = f.read(4096)
+        gzipped = head[:2] == b"\x1f\x8b"
+        stem = path[:-3] if gzipped and path.endswith(".gz") else path
+        is_gtf = os.path.splitext(stem)[1] == ".gtf"
+        bgzf = gzipped and readfile.bgzf_member_bytes(head) is not None
+        where = None if not gzipped else "device" if inflate == "device" or (inflate == "auto" and bgzf) else "host"
+        L = _lib.lib()
+        key = agg_key.encode("utf-8")
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(L.sfgpu_gmap_open(C.byref(h), 0 if is_gtf else 1, key, len(key)))
+        reader = _GmapReader(L, h, device, path)
+        try:
+            if where == "device":
+                f = open(path, "rb", buffering=0)
+                timed = _TimedReader(f)
+                carry = (readfile.DeviceInflate if bgzf else readfile.DeviceGunzip)(reader, timed, block_bytes)
+                reader._carry = carry
+                try:
+                    while carry.next(1 << 62) is not None:
+                        pass
+                except _NeedsHost:
+                    pass
+                finally:
+                    carry.close(); f.close()
+            else:
+                f = gzip.open(path, "rb") if gzipped else open(path, "rb", buffering=0)
+                timed = _TimedReader(f)
+                carry = readfile.BlockCarry(timed, block_bytes, path)
+                try:
+                    while carry.next(reader.parse_host, 1 << 62) is not None:
+                        pass
+                except _NeedsHost:
+                    pass
+                finally:
+                    f.close()
+            stats = reader.stats
+            stats.update(read_s=timed.seconds, inflate=where)
+            if reader.needs_host:
+                with torch.cuda.device(device):
+                    L.sfgpu_gmap_close(h)
+                h = None
+                return cls._from_host_reader(path, is_gtf, agg_key, gzipped, device, stats, reader.needs_host)
+            res = _lib.GmapResult()
+            with torch.cuda.device(device):
+                _lib.check(L.sfgpu_gmap_finish(h, C.byref(res), _lib.current_stream_ptr()))
+            stats.update(reader="device", reason=None, ms_finish=res.ms_kernels, sort_rounds=int(res.sort_rounds), n_records=int(res.n_records))
+            out = cls(h, device, is_gtf, stats)
+            out._sizes = (int(res.n_transcripts), int(res.n_genes), int(res.tname_bytes), int(res.gname_bytes))
+            h = None
+            return out
+        finally:
+            if h is not None:
+                with torch.cuda.device(device):
+                    L.sfgpu_gmap_close(h)
+
+    @classmethod
+    def _from_host_reader(cls, path, is_gtf, agg_key, gzipped, device, stats, flags):
+        tmp = None
+        try:
+            if gzipped:                                                   # the host readers open plain files
+                with gzip.open(path, "rb") as f, tempfile.NamedTemporaryFile(suffix=".gtf" if is_gtf else ".tsv", delete=False) as out:
+                    tmp = out.name
+                    out.write(f.read())
+            src = tmp or path
+            tgm = TranscriptGeneMap.from_gtf(src, agg_key) if is_gtf else TranscriptGeneMap.from_file(src)
+        finally:
+            if tmp:
+                os.unlink(tmp)
+        out = cls.from_host_map(tgm, device)
+        out.is_gtf = is_gtf
+        out.stats = dict(stats, reader="host", reason="; ".join(v for k, v in HOST_REASONS.items() if flags & k))
+        return out
+
+    @classmethod
+    def from_host_map(cls, tgm, device="cuda"):
+        """the tables of a TranscriptGeneMap uploaded (sfgpu_gmap_from_host); to_host() returns `tgm` itself"""
+        import torch
+
+        from . import _lib, quantfile
+        device = torch.device(device)
+        tb, to = quantfile.names_blob(tgm.transcript_names)
+        gb, go = quantfile.names_blob(tgm.gene_names)
+        t2g = np.ascontiguousarray(tgm.t2g, dtype=np.uint32)
+        h = C.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().sfgpu_gmap_from_host(C.byref(h), tb, _lib.ptr(to), _lib.ptr(t2g), len(tgm.transcript_names), gb, _lib.ptr(go),
+                                                       len(tgm.gene_names)))
+        out = cls(h, device, None, dict(reader="host", reason=None))
+        out._sizes = (len(tgm.transcript_names), len(tgm.gene_names), len(tb), len(gb))
+        out._host = tgm
+        return out
+
+    # ---- the tables
+    def num_transcripts(self): return self._sizes[0]
+    def num_genes(self): return self._sizes[1]
+
+    def tables(self):
+        """(tnames uint8, tname_off int64 [T + 1], t2g int32 holding uint32 bits [T], gnames uint8, gname_off int64 [G + 1]) on the
+        device, copied out of the handle once"""
+        import torch
+
+        from . import _lib
+        if self._h is None:
+            raise ValueError("the gene map is closed")
+        if self._tables is None:
+            T, G, tb, gb = self._sizes
+            mk = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=self.device)
+            tn, to, t2g, gn, go = mk(tb, torch.uint8), mk(T + 1, torch.int64), mk(T, torch.int32), mk(gb, torch.uint8), mk(G + 1, torch.int64)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.lib().sfgpu_gmap_export(self._h, _lib.ptr(tn), _lib.ptr(to), _lib.ptr(t2g), _lib.ptr(gn), _lib.ptr(go),
+                                                        _lib.current_stream_ptr()))
+            self._tables = (tn[:tb], to, t2g[:T], gn[:gb], go)
+        return self._tables
+
+    def gene_table(self):
+        """the gene names as the (blob, offsets) pair write_gene_rows takes"""
+        t = self.tables()
+        return t[3], t[4]
+
+    def to_host(self):
+        """the TranscriptGeneMap of the same file"""
+        if self._host is None:
+            tn, to, t2g, gn, go = (x.cpu().numpy() for x in self.tables())
+            cut = lambda blob, off: [blob[a:b].tobytes().decode("utf-8") for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+            m = TranscriptGeneMap.__new__(TranscriptGeneMap)
+            m.transcript_names, m.gene_names = cut(tn, to), cut(gn, go)
+            m.t2g = t2g.view(np.uint32).astype(np.int64).tolist()
+            self._host = m
+        return self._host
+
+    def lookup(self, names):
+        """findTranscriptID for every row name.  `names`: the (uint8 blob, 64-bit offsets) pair of device tensors that
+        Transcripts.name_blob() returns.  -> (gene_of_row: int32 device tensor holding uint32 bits, n_past): lower_bound with no
+        equality test; the n_past rows past the last name hold 0xFFFFFFFF."""
+        import torch
+
+        from . import _lib
+        if self._h is None:
+            raise ValueError("the gene map is closed")
+        blob, off = names
+        n = off.numel() - 1
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        n_past = C.c_uint64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().sfgpu_gmap_lookup(self._h, _lib.ptr(blob.contiguous()) if blob.numel() else None, _lib.ptr(off.contiguous()), n,
+                                                    _lib.ptr(out), C.byref(n_past), _lib.current_stream_ptr()))
+        return out[:n], int(n_past.value)
+
+    def close(self):
+        if self._h is not None:
+            import torch
+
+            from . import _lib
+            with torch.cuda.device(self.device):
+                _lib.lib().sfgpu_gmap_close(self._h)
+            self._h = self._tables = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class _NeedsHost(Exception):
+    """raised out of the block loop by the first call that reports needs_host: nothing more of the file is read for the device"""
+
+
+class _GmapReader:
+    """what the carriers of `readfile` drive: the parse callbacks over one sfgpu_gmap handle (and the attributes DeviceCarry reads
+    from its owner)"""
+
+    def __init__(self, L, handle, device, path):
+        self._L, self._h, self.device, self.path = L, handle, device, path
+        self._carry = None
+        self.needs_host = 0
+        self.stats = dict(calls=0, bytes_parsed=0, n_lines=0, ms_copy=0.0, ms_kernels=0.0, ms_inflate=0.0, bytes_compressed=0, members=0,
+                          chunks=0, candidates=0, false_starts=0, ms_find=0.0, ms_decode=0.0, ms_propagate=0.0, ms_emit=0.0)
+
+    def _done(self, rc, res, n):
+        from . import _lib, readfile
+        if rc == _lib.ERR_RANGE and res.consumed == 0 and n <= readfile.MAX_TEXT:
+            return readfile.Parsed(0, 0)                                   # no line ends in this text: the carrier presents more
+        _lib.check(rc)
+        self.needs_host |= int(res.needs_host)
+        for k, v in (("calls", 1), ("bytes_parsed", int(res.consumed)), ("n_lines", int(res.n_lines)), ("ms_copy", res.ms_copy),
+                     ("ms_kernels", res.ms_kernels)):
+            self.stats[k] += v
+        if self.needs_host:
+            raise _NeedsHost()                                             # the host reader takes the whole file: read no further
+        return readfile.Parsed(int(res.n_lines), int(res.consumed))
+
+    def parse_host(self, text, final, _max_reads):
+        import torch
+
+        from . import _lib
+        res = _lib.GmapAddResult()
+        with torch.cuda.device(self.device):
+            rc = self._L.sfgpu_gmap_add_text_host(self._h, _lib.ptr(text), int(text.size), int(final), C.byref(res), _lib.current_stream_ptr())
+        return self._done(rc, res, int(text.size))
+
+    def _parse_device(self, text, lo, hi, final, _max_reads, _records):
+        import torch
+
+        from . import _lib
+        n = hi - lo
+        res = _lib.GmapAddResult()
+        with torch.cuda.device(self.device):
+            if lo % 16:                                                    # the parser wants its text at a 16-byte boundary
+                text[:n] = text[lo:hi].clone()
+                self._carry.lo, self._carry.hi, lo, hi = 0, n, 0, n
+            view = text[lo:]
+            rc = self._L.sfgpu_gmap_add_text_device(self._h, _lib.ptr(view), n, view.numel(), int(final), C.byref(res), _lib.current_stream_ptr())
+        out = self._done(rc, res, n)
+        if out.n_reads and not final:
+            self._carry.starved = True                                     # what is left holds no line end: inflate before the next call
+        return out
+
+
 def aggregate_estimates_to_gene_level(tgm: TranscriptGeneMap, quant_path: str) -> str:
     """aggregateEstimatesToGeneLevel (:929-1037): writes <quant_path minus extension>.genes.sf, returns its path."""
     comments, gene_exps, header = [], {}, True
@@ -260,7 +542,28 @@ def write_gene_rows(fileobj, table, gene_id, length, eff, tpm, num_reads, chunk_
 QUANT_HEADER = "Name\tLength\tEffectiveLength\tTPM\tNumReads"
 
 
-def aggregate_columns(tgm: TranscriptGeneMap, names, length, eff, tpm, num_reads, out_path: str, comments=(QUANT_HEADER,),
+def _names_of_blob(names):
+    """the host list of a (blob, offsets) pair of device tensors"""
+    blob, off = (x.cpu().numpy() for x in names)
+    return [blob[a:b].tobytes().decode("utf-8") for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+def _device_gene_ids(dmap, names, device):
+    """(gene id of every row as a device tensor, gene table, number of ids) through a DeviceGeneMap"""
+    if isinstance(names, tuple):
+        pair = names
+    else:
+        from . import quantfile
+        b, o = quantfile.names_blob(names)
+        pair = (_to_device(np.frombuffer(b, np.uint8), np.uint8, device), _to_device(o, np.int64, device))
+    ids, n_past = dmap.lookup(pair)
+    if n_past == 0:
+        return ids, dmap.gene_table(), dmap.num_genes()
+    host_ids, table = dmap.to_host().gene_ids_of(names if not isinstance(names, tuple) else _names_of_blob(names))
+    return _to_device(host_ids, np.int32, device), table, len(table)
+
+
+def aggregate_columns(tgm, names, length, eff, tpm, num_reads, out_path: str, comments=(QUANT_HEADER,),
                       as_printed=True, chunk_bytes=0):
     """quant.genes.sf at `out_path` from the columns of quant.sf where they lie, without reading the file back: the bytes
     aggregate_estimates_to_gene_level writes from the quant.sf that quantfile.write_file writes from the same columns.
@@ -268,12 +571,21 @@ def aggregate_columns(tgm: TranscriptGeneMap, names, length, eff, tpm, num_reads
     32-bit integer device tensor; eff / tpm / num_reads: float64 device tensors.  `comments`: the lines the host function
     would copy from quant.sf, its header line included.  The names are looked up and factorised to ids on the host (gene_ids_of),
     the genes are folded and the rows formatted on the device; the comment lines are written here.
+    With a DeviceGeneMap the names are joined on the device (sfgpu_gmap_lookup); `names` is then best the (blob, offsets) pair of
+    Transcripts.name_blob() (a host list is uploaded), and while no row lies past the map's last name -- the usual case -- no
+    string touches the host: the gene table handed to the row writer is the map's device pair.  Rows past the last name are
+    "their own gene", keyed by name as the host dict is: the ids are then resolved by gene_ids_of on the map's to_host().
     Returns {"aggregate": sfgpu_genes_result, "write": sfgpu_quant_write_result} as dicts."""
-    ids, table = tgm.gene_ids_of(names)
-    if len(ids) != eff.numel():
-        raise ValueError(f"{len(ids)} names for {eff.numel()} rows")
-    d_ids = _to_device(ids, np.int32, eff.device)
-    gid, g_len, g_eff, g_tpm, g_nr, agg = aggregate_device(d_ids, len(table), length, eff, tpm, num_reads, as_printed=as_printed)
+    if isinstance(tgm, DeviceGeneMap):
+        d_ids, table, n_ids = _device_gene_ids(tgm, names, eff.device)
+    else:
+        if isinstance(names, tuple):
+            names = _names_of_blob(names)
+        ids, table = tgm.gene_ids_of(names)
+        d_ids, n_ids = _to_device(ids, np.int32, eff.device), len(table)
+    if d_ids.numel() != eff.numel():
+        raise ValueError(f"{d_ids.numel()} names for {eff.numel()} rows")
+    gid, g_len, g_eff, g_tpm, g_nr, agg = aggregate_device(d_ids, n_ids, length, eff, tpm, num_reads, as_printed=as_printed)
     with open(out_path, "wb") as f:
         for c in comments:
             f.write(c.encode("utf-8") + b"\n")
@@ -284,16 +596,19 @@ def aggregate_columns(tgm: TranscriptGeneMap, names, length, eff, tpm, num_reads
 def generate_gene_level_estimates(gene_map_path: str, est_dir: str, agg_key: str = "gene_id", columns=None) -> str:
     """generateGeneLevelEstimates (:1039-1088): a map whose extension is .gtf is read as GTF, anything else as the
     two-column format.  `columns`, when given, is (names, length, eff, tpm, num_reads) as aggregate_columns takes them --
-    the columns the caller has just written to <est_dir>/quant.sf: the genes are then folded on the device from those
-    (aggregate_columns) instead of from the file read back, with the same bytes in quant.genes.sf."""
+    the columns the caller has just written to <est_dir>/quant.sf: the map is then read on the device (DeviceGeneMap.from_path,
+    which also takes a gzip-compressed map) and the genes are folded there from those columns (aggregate_columns) instead of
+    from the file read back, with the same bytes in quant.genes.sf."""
+    if columns is not None:
+        dmap = DeviceGeneMap.from_path(gene_map_path, agg_key, device=columns[2].device)          # the map is read and joined on the device
+        out_path = os.path.join(est_dir, "quant.genes.sf")
+        with dmap:
+            aggregate_columns(dmap, *columns, out_path)
+        return out_path
     if os.path.splitext(gene_map_path)[1] == ".gtf":
         tgm = TranscriptGeneMap.from_gtf(gene_map_path, agg_key)
     else:
         tgm = TranscriptGeneMap.from_file(gene_map_path)
-    if columns is not None:
-        out_path = os.path.join(est_dir, "quant.genes.sf")
-        aggregate_columns(tgm, *columns, out_path)
-        return out_path
     est = os.path.join(est_dir, "quant.sf")
     if not os.path.exists(est):
         raise ValueError(f"Attempting to compute gene-level esimtates, but could not \nfind isoform-level file {est}")

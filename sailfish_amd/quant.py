@@ -156,7 +156,9 @@ def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_op
             # reference catches here (std::invalid_argument: an unreadable map, :1419) is logged and passed over; a failure of the
             # device path (_lib.SfgpuError, or a TypeError for columns that are not device tensors) is no map error and is raised,
             # as every other device failure of this function is: there is no quiet fall-back to the host loop
-            _genes.generate_gene_level_estimates(gene_map, out_dir, agg_key=sopt.txpAggregationKey, columns=columns)
+            # (the names go as the device pair quant.sf was written from: the join with the map happens on the device too)
+            _genes.generate_gene_level_estimates(gene_map, out_dir, agg_key=sopt.txpAggregationKey,
+                                                 columns=(exp.transcripts().name_blob(),) + tuple(columns[1:]))
         except ValueError as e:
             log(2, f"Error: [{e}] when trying to compute gene-level estimates. The gene-level file(s) may not exist")
     if timings is not None:

@@ -38,7 +38,8 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*) */
-    SFGPU_ERR_IO = 9         /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -500,6 +501,58 @@ SFGPU_API int sfgpu_gmap_export(sfgpu_gmap* m, char* d_tnames, uint64_t* d_tname
 SFGPU_API int sfgpu_gmap_lookup(sfgpu_gmap* m, const char* d_names, const uint64_t* d_name_off, uint64_t n_rows,
                                 uint32_t* d_gene_of_row, uint64_t* n_past, sfgpu_stream stream);
 SFGPU_API int sfgpu_gmap_close(sfgpu_gmap* m);
+/* A mapper's SAM text (what `rapmap quasimap -o`, bowtie2 or bwa write against a transcriptome) turned into the sfgpu_hit records and
+ * read offsets that sfgpu_filter_hits and sfgpu_sample_bias take, on the device.  What a SAM file says to this library is stated once,
+ * serially, in csrc/samfmt.h (the rules of samfile.read_sam_host: fields, flags, CIGAR, groups, pairs, order); the kernels are
+ * csrc/samtext.hip.  In short: lines with byte-equal QNAME that follow each other are one fragment (name-grouped files, as mappers
+ * write them; nothing is stripped from a name); '@' lines are counted and skipped; 0x4 / 0x800 lines yield no record; a mapped 0x40
+ * line directly followed by a mapped 0x80 line on the same transcript is a PAIRED_END_PAIRED record (frag_len = max end - min start,
+ * TLEN is not read), a fragment with a pair yields only its pairs, otherwise its mapped lines are orphans (left run, right run) or,
+ * single end, status-0 records; each run ascending in tid, ties in file order.  pos = POS - 1 - the leading soft clip.
+ *   open     d_names / d_name_off[M + 1]: the transcript names in index order, back to back (device arrays, copied into the handle);
+ *            RNAME is looked up in an XXH64 table of them with a byte compare behind every hash match.  A name that occurs twice is
+ *            SFGPU_ERR_INVALID.  paired != 0: the paired-end rules.  M < 2^32 - 1.
+ *   parse_host / _device   the conventions of sfgpu_gmap_add_text_host / _device: the text begins at a line start, n_bytes <= 2^30
+ *            (SFGPU_ERR_RANGE), the device form wants d_text 16-byte aligned with cap_text >= round16(n_bytes + 1) + 16 bytes (else
+ *            SFGPU_ERR_INVALID) and writes into that slack; with final != 0 a last line without '\n' is read as if it had one.  The
+ *            last fragment of a text that is not final is held back (the next line may carry its name): `consumed` ends in front of
+ *            its first line, and consumed == 0 with n_reads == 0 means "present more".  Output: d_hits[0 .. n_hits), d_off[0 ..
+ *            n_reads] (uint32, d_off[0] = 0 in every call).  n_hits > cap_hits or n_reads > cap_reads is SFGPU_ERR_CAPACITY with
+ *            need_hits / need_reads set and nothing written: call again with room (d_off holds cap_reads + 1 entries).  A malformed
+ *            line among the lines the call looked at (held back or not) is SFGPU_ERR_FORMAT: `bad` is the SFGPU_SAM_BAD_* bit of the
+ *            first rule the LOWEST such line breaks (in the order of the bits), bad_line its index in this text; nothing is written.
+ * All calls are synchronous and ordered behind the work already on `stream`; one handle is used from one thread at a time.  No CPU path. */
+typedef struct sfgpu_sam sfgpu_sam;
+struct sfgpu_hit;          /* (defined with sfgpu_filter_hits below) */
+enum {
+    SFGPU_SAM_BAD_FIELDS = 1,   /* fewer than 11 tab-separated fields (an empty line included) */
+    SFGPU_SAM_BAD_NUMBER = 2,   /* FLAG is not 1-5 digits <= 65535; POS of a mapped line is not 1-10 digits in 1 .. 2^31 - 1 */
+    SFGPU_SAM_BAD_FLAG = 4,     /* paired call: 0x1 missing, or not exactly one of 0x40 / 0x80; single-end call: 0x1 set */
+    SFGPU_SAM_BAD_RNAME = 8,    /* a mapped line names no transcript of the handle */
+    SFGPU_SAM_BAD_CIGAR = 16,   /* neither '*' nor a run of (1-9 digits, one of MIDNSHP=X) */
+    SFGPU_SAM_BAD_LENGTH = 32   /* the read is longer than 65535 bases, or SEQ and CIGAR disagree about its length */
+};
+typedef struct {
+    uint64_t n_lines;      /* lines consumed by this call, header lines included */
+    uint64_t n_header;     /* '@' lines among them */
+    uint64_t n_reads;      /* fragments (groups) emitted */
+    uint64_t n_hits;       /* records emitted */
+    uint64_t n_pairs;      /* PAIRED_END_PAIRED records among them */
+    uint64_t consumed;     /* bytes of the text the caller may drop */
+    uint64_t need_hits;    /* SFGPU_ERR_CAPACITY: the sizes the call needs */
+    uint64_t need_reads;
+    uint64_t bad_line;     /* SFGPU_ERR_FORMAT: the lowest malformed line (0-based, in this text) */
+    uint32_t bad;          /* ... and its SFGPU_SAM_BAD_* bit */
+    uint32_t pad_;
+    double ms_copy;        /* device events around the staged host-to-device copies (0 for the device form) */
+    double ms_kernels;     /* device events around the kernels, scans and the sort of the call */
+} sfgpu_sam_result;
+SFGPU_API int sfgpu_sam_open(sfgpu_sam** out, const char* d_names, const uint64_t* d_name_off, uint64_t M, int paired, sfgpu_stream stream);
+SFGPU_API int sfgpu_sam_parse_host(sfgpu_sam* s, const char* h_text, uint64_t n_bytes, int final, struct sfgpu_hit* d_hits, uint64_t cap_hits,
+                                   uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_sam_parse_device(sfgpu_sam* s, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, struct sfgpu_hit* d_hits,
+                                     uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_sam_close(sfgpu_sam* s);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

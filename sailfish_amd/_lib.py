@@ -11,7 +11,7 @@ import torch  # noqa: F401  (imported first so libamdhip64.so.7 resolves to torc
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SFGPU_LIB_PATH", os.path.join(_HERE, "csrc", "libsfgpu.so"))   # override: kernel-tuning builds
 
-OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED, ERR_FORMAT, ERR_IO = range(10)
+OK, ERR_INVALID, ERR_HIP, ERR_NO_ACTIVE, ERR_ALPHA_SUM, ERR_RANGE, ERR_STATE, ERR_UNSUPPORTED, ERR_FORMAT, ERR_IO, ERR_CAPACITY = range(11)
 
 
 class SfgpuError(RuntimeError):
@@ -124,6 +124,15 @@ class GmapResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SamResult(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_header", C.c_uint64), ("n_reads", C.c_uint64), ("n_hits", C.c_uint64), ("n_pairs", C.c_uint64),
+                ("consumed", C.c_uint64), ("need_hits", C.c_uint64), ("need_reads", C.c_uint64), ("bad_line", C.c_uint64), ("bad", C.c_uint32),
+                ("pad_", C.c_uint32), ("ms_copy", C.c_double), ("ms_kernels", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class GzResult(C.Structure):
     _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("encode_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -217,6 +226,10 @@ _SIGS = {
     "sfgpu_gmap_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "sfgpu_gmap_lookup": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(C.c_uint64), _P]),
     "sfgpu_gmap_close": (C.c_int, [_P]),
+    "sfgpu_sam_open": (C.c_int, [C.POINTER(_P), _P, _P, C.c_uint64, C.c_int, _P]),
+    "sfgpu_sam_parse_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
+    "sfgpu_sam_parse_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
+    "sfgpu_sam_close": (C.c_int, [_P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),

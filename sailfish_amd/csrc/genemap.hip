@@ -26,6 +26,7 @@
 #include "common.h"
 #include "gtffmt.h"
 #include "primitives.h"
+#include "textlines.h"
 
 namespace sfgpu {
 namespace {
@@ -43,21 +44,8 @@ struct Bytes {
     __device__ unsigned char operator()(uint64_t i) const { return p[i]; }
 };
 
-// bit i = byte i of the group is c
-__device__ inline uint32_t eq_mask(const uint4 v, unsigned char c) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) m |= (uint32_t)(((w[i >> 2] >> (8 * (i & 3))) & 0xffu) == c) << i;
-    return m;
-}
-
-// bit i = byte p0 + i lies in [s, e)
-__device__ inline uint32_t range_mask(uint64_t p0, uint64_t s, uint64_t e) {
-    if (p0 >= e || p0 + 16 <= s) return 0;
-    const uint32_t lo = s > p0 ? (uint32_t)(s - p0) : 0, hi = e - p0 >= 16 ? 16u : (uint32_t)(e - p0);
-    return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-}
+using textlines::eq_mask;
+using textlines::range_mask;
 
 __device__ inline bool word_has_zero(uint32_t w) { return ((w - 0x01010101u) & ~w & 0x80808080u) != 0; }
 
@@ -699,20 +687,6 @@ extern "C" int sfgpu_gmap_add_text_host(sfgpu_gmap* m, const char* h_text, uint6
     return rc;
 }
 
-// the byte behind the last '\n' below n (0: none)
-static __global__ void k_gmap_last_nl(const unsigned char* __restrict__ bytes, uint64_t n, unsigned long long* __restrict__ last) {
-    const uint64_t p0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16u;
-    unsigned long long best = 0;
-    for (uint64_t p = p0; p < n && p < p0 + 16u; ++p)
-        if (bytes[p] == '\n') best = p + 1;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(best, o);
-        best = other > best ? other : best;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0 && best) atomicMax(last, best);
-}
-
 extern "C" int sfgpu_gmap_add_text_device(sfgpu_gmap* m, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final,
                                           sfgpu_gmap_add_result* res, sfgpu_stream stream) {
     SF_REQUIRE(m && res, SFGPU_ERR_INVALID, "sfgpu_gmap_add_text_device: null handle or result");
@@ -738,7 +712,7 @@ extern "C" int sfgpu_gmap_add_text_device(sfgpu_gmap* m, uint8_t* d_text, uint64
     if (int r = last.reserve(1, st, false)) return r;
     SF_HIP(hipEventRecord(ev_k0, st));
     SF_HIP(hipMemsetAsync(last.p, 0, 8, st));
-    hipLaunchKernelGGL(k_gmap_last_nl, dim3(grid_of((n_bytes + 15) / 16)), dim3(kBlock), 0, st, d_text, n_bytes, last.p);
+    hipLaunchKernelGGL(textlines::k_last_nl, dim3(grid_of((n_bytes + 15) / 16)), dim3(kBlock), 0, st, d_text, n_bytes, last.p);
     SF_CHECK_LAUNCH();
     unsigned long long* h_last = reinterpret_cast<unsigned long long*>(&h[6]);
     SF_HIP(hipMemcpyAsync(h_last, last.p, 8, hipMemcpyDeviceToHost, st));

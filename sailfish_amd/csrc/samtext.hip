@@ -1,0 +1,578 @@
+// samtext.hip -- a mapper's SAM text turned into sfgpu_hit records and read offsets on the device: sfgpu_sam_*.  What a line says,
+// which lines pair and what record they make is decided by samfmt.h (the same functions run serially in tests/sam_harness.cpp);
+// this file is the passes around them.  No pass walks a line: the cost of a call depends on its bytes and its lines, not on how
+// long a line or how large a group is.
+//
+// The text (whole lines) lies on the device as 16-byte groups.
+//   k_sam_count        per group: its '\n' and its '\t' bytes
+//   scans, k_sam_line_ends   where line j ends, and how many tabs stand in front of it
+//   k_sam_tabs         per group: the tab at p is tab number (tabs in front of p) - (tabs in front of its line) of line (newlines in
+//                      front of p); the first ten of a line are stored.  SEQ's length is a difference of two of them, so nobody
+//                      reads SEQ or QUAL.
+//   k_sam_lines        one lane per line: samfmt.h's sam_parse_line over FLAG, RNAME, POS and CIGAR; RNAME is looked up in the
+//                      handle's table (XXH64 of the name, linear probing, a byte compare behind every hash match).  The lowest
+//                      malformed line is a 64-bit min (one atomic per wavefront that holds one).
+//   scan, k_sam_compact   the non-header lines ("records of the text"), in order
+//   k_sam_heads        record k begins a group when its QNAME differs from record k - 1's; a scan of the heads numbers the groups;
+//                      the last head is where a text that is not final is cut
+//   k_sam_pairs        pair heads are a neighbour test (sam_pairs_with); "this group has a pair" is a plain store of 1 by every pair
+//                      head into the group's flag: the segmented OR without a segment walk
+//   k_sam_survive, scan, k_sam_keys   the lines that yield a record, compacted; d_off[group] = the survivors in front of its head;
+//                      key = (group, right orphan, tid)
+//   sort_pairs_u64_u32 (stable: ties stay in file order), k_sam_write   the records, sam_pair_hit / sam_single_hit
+#include "common.h"
+#include "primitives.h"
+#include "samfmt.h"
+#include "textlines.h"
+#include "xxh64_device.h"
+
+namespace sfgpu {
+namespace {
+
+using textlines::eq_mask;
+using textlines::range_mask;
+
+constexpr int kBlock = 256;
+inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+constexpr uint64_t kSubBytes = 4ull << 20;               // staged sub-chunk (a multiple of 16)
+constexpr uint64_t kMaxBytes = 1ull << 30;               // one parse call
+constexpr unsigned long long kNoBad = ~0ull;
+
+struct Bytes {
+    const unsigned char* p;
+    __device__ unsigned char operator()(uint32_t i) const { return p[i]; }
+};
+
+// ---- the name table -------------------------------------------------------------------------------------------------------
+
+// XXH64 over the name's bytes as little-endian words, the last one zero-padded (a hash only: equality is the byte compare)
+__device__ inline uint64_t name_hash(const unsigned char* q, uint32_t n) {
+    return xxh64_words([q, n](uint32_t i) {
+        uint32_t w = 0;
+        for (uint32_t b = 0; b < 4 && 4 * i + b < n; ++b) w |= (uint32_t)q[4 * i + b] << (8 * b);
+        return w;
+    }, (n + 3) / 4);
+}
+
+struct NameTable {
+    const unsigned char* blob;
+    const uint64_t* off;          // [M + 1]
+    const uint32_t* slot;         // [mask + 1]: 0 = empty, else the name's index + 1
+    uint32_t mask;
+    __device__ bool is(uint32_t t, const unsigned char* q, uint32_t n) const {
+        if (off[t + 1] - off[t] != n) return false;
+        const unsigned char* a = blob + off[t];
+        for (uint32_t i = 0; i < n; ++i)
+            if (a[i] != q[i]) return false;
+        return true;
+    }
+    __device__ uint32_t find(const unsigned char* q, uint32_t n) const {
+        uint32_t at = (uint32_t)name_hash(q, n) & mask;
+        for (uint32_t probe = 0; probe <= mask; ++probe, at = (at + 1) & mask) {
+            const uint32_t v = slot[at];
+            if (v == 0) return kSamNone;
+            if (is(v - 1, q, n)) return v - 1;
+        }
+        return kSamNone;
+    }
+};
+
+// every name into the table; *flag |= 1: a name occurs twice, 2: the offsets decrease or a name has 2^32 bytes or more
+__global__ void k_sam_table(const unsigned char* __restrict__ blob, const uint64_t* __restrict__ off, uint32_t M, uint32_t* __restrict__ slot,
+                            uint32_t mask, uint32_t* __restrict__ flag) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= M) return;
+    if (off[t + 1] < off[t] || off[t + 1] - off[t] > 0xfffffffeull) { atomicOr(flag, 2u); return; }
+    const unsigned char* q = blob + off[t];
+    const uint32_t n = (uint32_t)(off[t + 1] - off[t]);
+    const NameTable T{blob, off, slot, mask};
+    uint32_t at = (uint32_t)name_hash(q, n) & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe, at = (at + 1) & mask) {
+        const uint32_t old = atomicCAS(&slot[at], 0u, t + 1);
+        if (old == 0) return;
+        if (T.is(old - 1, q, n)) { atomicOr(flag, 1u); return; }
+    }
+}
+
+// ---- lines and tabs -------------------------------------------------------------------------------------------------------
+
+__global__ void k_sam_count(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, uint32_t* __restrict__ nl_cnt,
+                            uint32_t* __restrict__ tab_cnt) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    const uint4 v = buf[g];
+    const uint32_t in = range_mask(g * 16, 0, n_text);
+    nl_cnt[g] = __popc(eq_mask(v, '\n') & in);
+    tab_cnt[g] = __popc(eq_mask(v, '\t') & in);
+}
+
+// line_end[j] = the '\n' that ends line j; line_tab0[j] = the tabs in front of line j
+__global__ void k_sam_line_ends(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, const uint32_t* __restrict__ nl_scan,
+                                const uint32_t* __restrict__ tab_scan, uint32_t* __restrict__ line_end, uint32_t* __restrict__ line_tab0) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    const uint4 v = buf[g];
+    const uint32_t in = range_mask(g * 16, 0, n_text);
+    uint32_t nl = eq_mask(v, '\n') & in;
+    const uint32_t tabs = eq_mask(v, '\t') & in;
+    uint32_t at = nl_scan[g];
+    const uint32_t t0 = tab_scan[g];
+    if (g == 0) line_tab0[0] = 0;
+    while (nl) {
+        const int i = __ffs(nl) - 1;
+        nl &= nl - 1;
+        line_end[at] = (uint32_t)(g * 16 + i);
+        line_tab0[at + 1] = t0 + __popc(tabs & ((1u << i) - 1u));
+        ++at;
+    }
+}
+
+// tab_pos[ord * L + j] = the ord-th tab of line j, ord < kSamTabs (the array is preset to kSamNone)
+__global__ void k_sam_tabs(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, const uint32_t* __restrict__ nl_scan,
+                           const uint32_t* __restrict__ tab_scan, const uint32_t* __restrict__ line_tab0, uint32_t L,
+                           uint32_t* __restrict__ tab_pos) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    const uint4 v = buf[g];
+    const uint32_t in = range_mask(g * 16, 0, n_text);
+    const uint32_t tabs = eq_mask(v, '\t') & in;
+    if (!tabs) return;
+    const uint32_t nl = eq_mask(v, '\n') & in;
+    const uint32_t j0 = nl_scan[g];
+    uint32_t t = tab_scan[g];
+    for (uint32_t w = tabs; w; w &= w - 1, ++t) {
+        const int i = __ffs(w) - 1;
+        const uint32_t j = j0 + __popc(nl & ((1u << i) - 1u));
+        if (j >= L) return;                               // (the text ends in a '\n': no tab stands behind the last line)
+        const uint32_t ord = t - line_tab0[j];
+        if (ord < kSamTabs) tab_pos[(uint64_t)ord * L + j] = (uint32_t)(g * 16 + i);
+    }
+}
+
+// what k_sam_lines keeps of a line: read_len | mapped << 16 | fwd << 17 | side << 18
+__device__ inline uint32_t pack_line(const SamLine& l) {
+    return (uint32_t)l.read_len | (uint32_t)l.mapped << 16 | (uint32_t)l.fwd << 17 | (uint32_t)l.side << 18;
+}
+struct Lines {
+    const uint32_t* info;
+    const uint32_t* tid;
+    const int32_t* pos;
+    __device__ SamLine operator()(uint32_t j) const {
+        const uint32_t w = info[j];
+        SamLine l = {0, 0, tid[j], pos[j], (uint16_t)(w & 0xffffu), 0, (uint8_t)((w >> 16) & 1u), (uint8_t)((w >> 18) & 3u), (uint8_t)((w >> 17) & 1u)};
+        return l;
+    }
+};
+
+// One lane per line.  No lane leaves before the shuffles.
+__global__ void __launch_bounds__(kBlock) k_sam_lines(const unsigned char* __restrict__ bytes, uint32_t L, const uint32_t* __restrict__ line_end,
+                                                      const uint32_t* __restrict__ tab_pos, int paired, NameTable T, uint32_t* __restrict__ info,
+                                                      uint32_t* __restrict__ tid, int32_t* __restrict__ pos, uint32_t* __restrict__ isrec,
+                                                      unsigned long long* __restrict__ first_bad) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long key = kNoBad;
+    if (j < L) {
+        const Bytes get{bytes};
+        const uint32_t s = j ? line_end[j - 1] + 1 : 0;
+        const uint32_t e = sam_line_end(get, s, line_end[j]);
+        uint32_t tab[kSamTabs];
+#pragma unroll
+        for (uint32_t o = 0; o < kSamTabs; ++o) tab[o] = tab_pos[(uint64_t)o * L + j];
+        const SamLine l = sam_parse_line(get, s, e, tab, paired != 0, [&](uint32_t a, uint32_t n) { return T.find(bytes + a, n); });
+        info[j] = pack_line(l); tid[j] = l.tid; pos[j] = l.pos; isrec[j] = l.header ? 0u : 1u;
+        if (l.bad) key = ((unsigned long long)j << 8) | l.bad;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other < key ? other : key;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0 && key != kNoBad) atomicMin(first_bad, key);
+}
+
+__global__ void k_sam_compact(uint32_t L, const uint32_t* __restrict__ isrec, const uint32_t* __restrict__ rec_scan, uint32_t* __restrict__ rec_line) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < L && isrec[j]) rec_line[rec_scan[j]] = j;
+}
+
+// ---- groups, pairs, records -----------------------------------------------------------------------------------------------
+
+// head[k] = record k's QNAME differs from record k - 1's
+__global__ void k_sam_heads(const unsigned char* __restrict__ bytes, uint32_t K, const uint32_t* __restrict__ rec_line,
+                            const uint32_t* __restrict__ line_end, const uint32_t* __restrict__ tab_pos, uint32_t* __restrict__ head) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    if (k == 0) { head[0] = 1; return; }
+    const uint32_t j = rec_line[k], i = rec_line[k - 1];
+    const uint32_t sj = line_end[j - 1] + 1, si = i ? line_end[i - 1] + 1 : 0;        // (j > i >= 0; tab 0 of a record exists)
+    const uint32_t n = tab_pos[j] - sj;
+    bool same = tab_pos[i] - si == n;
+    for (uint32_t b = 0; same && b < n; ++b) same = bytes[sj + b] == bytes[si + b];
+    head[k] = same ? 0u : 1u;
+}
+
+// the last head: cut[0] = its record, cut[1] = its line, cut[2] = where that line begins
+__global__ void k_sam_cut(uint32_t K, const uint32_t* __restrict__ head, const uint32_t* __restrict__ head_scan, const uint32_t* __restrict__ rec_line,
+                          const uint32_t* __restrict__ line_end, uint32_t* __restrict__ cut) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K || !head[k] || head_scan[k] + 1 != head_scan[K]) return;
+    const uint32_t j = rec_line[k];
+    cut[0] = k; cut[1] = j; cut[2] = j ? line_end[j - 1] + 1 : 0;
+}
+
+__device__ inline uint32_t group_of(const uint32_t* head, const uint32_t* head_scan, uint32_t k) { return head_scan[k] + head[k] - 1u; }
+
+// records below Kc: pair_head[k], has_pair[group] (preset to 0)
+__global__ void k_sam_pairs(uint32_t Kc, const uint32_t* __restrict__ rec_line, const uint32_t* __restrict__ head, const uint32_t* __restrict__ head_scan,
+                            Lines lines, uint32_t* __restrict__ pair_head, uint32_t* __restrict__ has_pair) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Kc) return;
+    const bool ph = k + 1 < Kc && !head[k + 1] && sam_pairs_with(lines(rec_line[k]), lines(rec_line[k + 1]));
+    pair_head[k] = ph ? 1u : 0u;
+    if (ph) has_pair[group_of(head, head_scan, k)] = 1u;
+}
+
+// surv[k] = record k yields a record (K entries, 0 from Kc on); *n_pairs += the pair heads.  No lane leaves before the ballot.
+__global__ void __launch_bounds__(kBlock) k_sam_survive(uint32_t K, uint32_t Kc, const uint32_t* __restrict__ rec_line, const uint32_t* __restrict__ head,
+                                                        const uint32_t* __restrict__ head_scan, Lines lines, const uint32_t* __restrict__ pair_head,
+                                                        const uint32_t* __restrict__ has_pair, uint32_t* __restrict__ surv,
+                                                        unsigned long long* __restrict__ n_pairs) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    bool pair = false;
+    if (k < K) {
+        bool s = false;
+        if (k < Kc) {
+            pair = pair_head[k] != 0;
+            s = has_pair[group_of(head, head_scan, k)] ? pair : lines(rec_line[k]).mapped != 0;
+        }
+        surv[k] = s ? 1u : 0u;
+    }
+    const unsigned long long b = __ballot(pair);
+    if ((threadIdx.x & (kWave - 1)) == 0 && b) atomicAdd(n_pairs, (unsigned long long)__popcll(b));
+}
+
+// off[group] = the survivors in front of its head; the survivors' sort keys, their values = the record
+__global__ void k_sam_keys(uint32_t Kc, const uint32_t* __restrict__ rec_line, const uint32_t* __restrict__ head, const uint32_t* __restrict__ head_scan,
+                           Lines lines, const uint32_t* __restrict__ surv, const uint32_t* __restrict__ surv_scan, uint32_t* __restrict__ off,
+                           uint64_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Kc) return;
+    const uint32_t g = group_of(head, head_scan, k), at = surv_scan[k];
+    if (head[k]) off[g] = at;
+    if (!surv[k]) return;
+    const SamLine l = lines(rec_line[k]);
+    key[at] = sam_sort_key(g, l.side == 2, l.tid);        // (a pair head is a left mate)
+    val[at] = k;
+}
+
+__global__ void k_sam_write(uint32_t n_hits, const uint32_t* __restrict__ order, const uint32_t* __restrict__ rec_line,
+                            const uint32_t* __restrict__ pair_head, Lines lines, sfgpu_hit* __restrict__ hits) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_hits) return;
+    const uint32_t k = order[i];
+    const SamLine a = lines(rec_line[k]);
+    hits[i] = pair_head[k] ? sam_pair_hit(a, lines(rec_line[k + 1])) : sam_single_hit(a);
+}
+
+struct Scratch {
+    DevBuf<uint4> text;
+    DevBuf<uint32_t> nl_cnt, nl_scan, tab_cnt, tab_scan, line_end, line_tab0, tab_pos, info, tid, isrec, rec_scan, rec_line, head, head_scan,
+        pair_head, has_pair, surv, surv_scan, val, val2, cut;
+    DevBuf<int32_t> pos;
+    DevBuf<uint64_t> key, key2;
+    DevBuf<unsigned long long> word;              // [0] the lowest malformed line, [1] the pairs
+};
+
+}  // namespace
+}  // namespace sfgpu
+
+using namespace sfgpu;
+
+struct sfgpu_sam {
+    bool paired = false;
+    uint64_t M = 0;
+    uint32_t mask = 0;
+    DevBuf<unsigned char> blob;
+    DevBuf<uint64_t> off;
+    DevBuf<uint32_t> slot;
+};
+
+namespace {
+
+// The text on the device: [0, n_text) ends in a '\n' (whole lines); `used` of its bytes are the caller's (n_text - used = 1 when
+// the '\n' of the last line was supplied).  h: 8 pinned 64-bit words.
+int parse_device_text(sfgpu_sam* m, Scratch& S, const uint4* text, uint64_t n_text, uint64_t used, bool final, sfgpu_hit* d_hits,
+                      uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, hipStream_t st, uint64_t* h) {
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(text);
+    const uint64_t n_groups = (n_text + 15) / 16;
+    uint32_t* h32 = reinterpret_cast<uint32_t*>(h);
+    for (DevBuf<uint32_t>* b : {&S.nl_cnt, &S.nl_scan, &S.tab_cnt, &S.tab_scan}) if (int r = b->reserve(n_groups + 2, st, false)) return r;
+    if (int r = S.word.reserve(2, st, false)) return r;
+    if (int r = S.cut.reserve(4, st, false)) return r;
+    hipLaunchKernelGGL(k_sam_count, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_cnt.p, S.tab_cnt.p);
+    SF_CHECK_LAUNCH();
+    if (int r = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return r;
+    if (int r = exclusive_scan_u32_u32(S.tab_cnt.p, S.tab_scan.p, n_groups, st)) return r;
+    SF_HIP(hipMemcpyAsync(&h32[0], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    const uint32_t L = h32[0];
+    if (L == 0) return SFGPU_OK;
+
+    // ---- the lines
+    for (DevBuf<uint32_t>* b : {&S.line_end, &S.line_tab0, &S.info, &S.tid, &S.isrec, &S.rec_scan}) if (int r = b->reserve((uint64_t)L + 2, st, false)) return r;
+    if (int r = S.pos.reserve((uint64_t)L + 2, st, false)) return r;
+    if (int r = S.tab_pos.reserve((uint64_t)kSamTabs * L, st, false)) return r;
+    SF_HIP(hipMemsetAsync(S.tab_pos.p, 0xff, (uint64_t)kSamTabs * L * 4, st));
+    SF_HIP(hipMemsetAsync(S.word.p, 0xff, 8, st));
+    SF_HIP(hipMemsetAsync(S.word.p + 1, 0, 8, st));
+    hipLaunchKernelGGL(k_sam_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_scan.p, S.tab_scan.p, S.line_end.p,
+                       S.line_tab0.p);
+    SF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sam_tabs, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_scan.p, S.tab_scan.p, S.line_tab0.p, L,
+                       S.tab_pos.p);
+    SF_CHECK_LAUNCH();
+    const NameTable T{m->blob.p, m->off.p, m->slot.p, m->mask};
+    hipLaunchKernelGGL(k_sam_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, bytes, L, S.line_end.p, S.tab_pos.p, m->paired ? 1 : 0, T, S.info.p, S.tid.p,
+                       S.pos.p, S.isrec.p, S.word.p);
+    SF_CHECK_LAUNCH();
+    if (int r = exclusive_scan_u32_u32(S.isrec.p, S.rec_scan.p, L, st)) return r;
+    SF_HIP(hipMemcpyAsync(&h[1], S.word.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h32[0], S.rec_scan.p + L, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    if (h[1] != kNoBad) {
+        res->bad = (uint32_t)(h[1] & 0xffu);
+        res->bad_line = h[1] >> 8;
+        set_error("sfgpu_sam_parse: line %llu of the text is malformed (SFGPU_SAM_BAD_* %u)", (unsigned long long)res->bad_line, res->bad);
+        return SFGPU_ERR_FORMAT;
+    }
+    const uint32_t K = h32[0];
+    if (K == 0) {                                         // header lines only
+        res->n_lines = res->n_header = L;
+        res->consumed = used;
+        return SFGPU_OK;
+    }
+
+    // ---- the groups
+    for (DevBuf<uint32_t>* b : {&S.rec_line, &S.head, &S.head_scan, &S.pair_head, &S.has_pair, &S.surv, &S.surv_scan})
+        if (int r = b->reserve((uint64_t)K + 2, st, false)) return r;
+    hipLaunchKernelGGL(k_sam_compact, dim3(grid_of(L)), dim3(kBlock), 0, st, L, S.isrec.p, S.rec_scan.p, S.rec_line.p);
+    SF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_sam_heads, dim3(grid_of(K)), dim3(kBlock), 0, st, bytes, K, S.rec_line.p, S.line_end.p, S.tab_pos.p, S.head.p);
+    SF_CHECK_LAUNCH();
+    if (int r = exclusive_scan_u32_u32(S.head.p, S.head_scan.p, K, st)) return r;
+    hipLaunchKernelGGL(k_sam_cut, dim3(grid_of(K)), dim3(kBlock), 0, st, K, S.head.p, S.head_scan.p, S.rec_line.p, S.line_end.p, S.cut.p);
+    SF_CHECK_LAUNCH();
+    SF_HIP(hipMemcpyAsync(&h32[0], S.head_scan.p + K, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h32[1], S.cut.p, 12, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    const uint32_t n_groups_seen = h32[0];
+    const uint32_t Kc = final ? K : h32[1], n_reads = final ? n_groups_seen : n_groups_seen - 1;
+    const uint64_t n_lines = final ? L : h32[2], consumed = final ? used : h32[3];
+    if (n_reads == 0) {                                   // one group, held back: the header lines in front of it may go
+        res->n_lines = res->n_header = n_lines;
+        res->consumed = consumed;
+        return SFGPU_OK;
+    }
+
+    // ---- the records
+    const Lines lines{S.info.p, S.tid.p, S.pos.p};
+    SF_HIP(hipMemsetAsync(S.has_pair.p, 0, (uint64_t)n_reads * 4, st));
+    if (m->paired) {
+        hipLaunchKernelGGL(k_sam_pairs, dim3(grid_of(Kc)), dim3(kBlock), 0, st, Kc, S.rec_line.p, S.head.p, S.head_scan.p, lines, S.pair_head.p,
+                           S.has_pair.p);
+        SF_CHECK_LAUNCH();
+    } else {
+        SF_HIP(hipMemsetAsync(S.pair_head.p, 0, (uint64_t)Kc * 4, st));
+    }
+    hipLaunchKernelGGL(k_sam_survive, dim3(grid_of(K)), dim3(kBlock), 0, st, K, Kc, S.rec_line.p, S.head.p, S.head_scan.p, lines, S.pair_head.p,
+                       S.has_pair.p, S.surv.p, S.word.p + 1);
+    SF_CHECK_LAUNCH();
+    if (int r = exclusive_scan_u32_u32(S.surv.p, S.surv_scan.p, K, st)) return r;
+    SF_HIP(hipMemcpyAsync(&h32[0], S.surv_scan.p + K, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h[1], S.word.p + 1, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    const uint32_t n_hits = h32[0];
+    if (n_hits > cap_hits || n_reads > cap_reads) {
+        res->need_hits = n_hits; res->need_reads = n_reads;
+        set_error("sfgpu_sam_parse: %u records in %u reads do not fit cap_hits = %llu, cap_reads = %llu", n_hits, n_reads,
+                  (unsigned long long)cap_hits, (unsigned long long)cap_reads);
+        return SFGPU_ERR_CAPACITY;
+    }
+    for (DevBuf<uint64_t>* b : {&S.key, &S.key2}) if (int r = b->reserve((uint64_t)n_hits + 2, st, false)) return r;
+    for (DevBuf<uint32_t>* b : {&S.val, &S.val2}) if (int r = b->reserve((uint64_t)n_hits + 2, st, false)) return r;
+    hipLaunchKernelGGL(k_sam_keys, dim3(grid_of(Kc)), dim3(kBlock), 0, st, Kc, S.rec_line.p, S.head.p, S.head_scan.p, lines, S.surv.p, S.surv_scan.p, d_off,
+                       S.key.p, S.val.p);
+    SF_CHECK_LAUNCH();
+    SF_HIP(hipMemcpyAsync(d_off + n_reads, S.surv_scan.p + K, 4, hipMemcpyDeviceToDevice, st));
+    if (n_hits) {
+        int group_bits = 1;
+        while (group_bits < 31 && (1u << group_bits) < n_reads) ++group_bits;
+        if (int r = sort_pairs_u64_u32(S.key.p, S.key2.p, S.val.p, S.val2.p, n_hits, st, 33 + group_bits, false)) return r;
+        hipLaunchKernelGGL(k_sam_write, dim3(grid_of(n_hits)), dim3(kBlock), 0, st, n_hits, S.val2.p, S.rec_line.p, S.pair_head.p, lines, d_hits);
+        SF_CHECK_LAUNCH();
+    }
+    SF_HIP(hipStreamSynchronize(st));
+    res->n_lines = n_lines; res->n_header = n_lines - Kc; res->n_reads = n_reads; res->n_hits = n_hits; res->n_pairs = h[1];
+    res->consumed = consumed;
+    return SFGPU_OK;
+}
+
+int check_parse_args(const char* who, sfgpu_sam* m, const void* text, uint64_t n_bytes, sfgpu_hit* d_hits, uint64_t cap_hits, uint32_t* d_off,
+                     sfgpu_sam_result* res) {
+    if (!m || !res) { set_error("%s: null handle or result", who); return SFGPU_ERR_INVALID; }
+    memset(res, 0, sizeof(*res));
+    if (n_bytes > kMaxBytes) { set_error("%s: more than 2^30 bytes in one call", who); return SFGPU_ERR_RANGE; }
+    if ((n_bytes && !text) || !d_off || (cap_hits && !d_hits)) { set_error("%s: null array", who); return SFGPU_ERR_INVALID; }
+    return SFGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int sfgpu_sam_open(sfgpu_sam** out, const char* d_names, const uint64_t* d_name_off, uint64_t M, int paired, sfgpu_stream stream) {
+    SF_REQUIRE(out && d_name_off, SFGPU_ERR_INVALID, "sfgpu_sam_open: null handle or offsets");
+    SF_REQUIRE(M < 0xffffffffull - 1, SFGPU_ERR_RANGE, "sfgpu_sam_open: 2^32 - 1 names or more");
+    hipStream_t st = as_stream(stream);
+    sfgpu_sam* m = new sfgpu_sam;
+    m->paired = paired != 0;
+    m->M = M;
+    uint64_t size = 64;
+    while (size < 2 * M) size *= 2;
+    m->mask = (uint32_t)(size - 1);
+    DevBuf<uint32_t> flag;
+    auto build = [&]() -> int {
+        CallScope scope;
+        uint64_t* h = nullptr;
+        SF_HIP(scope.adopt(st));
+        SF_HIP(scope.pinned_block(&h, 2 * sizeof(uint64_t)));
+        if (int r = m->off.reserve(M + 1, st, false)) return r;
+        if (int r = m->slot.reserve(size, st, false)) return r;
+        if (int r = flag.reserve(1, st, false)) return r;
+        SF_HIP(hipMemcpyAsync(m->off.p, d_name_off, (M + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+        SF_HIP(hipMemcpyAsync(&h[0], d_name_off + M, 8, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipMemcpyAsync(&h[1], d_name_off, 8, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipStreamSynchronize(st));
+        const uint64_t n_bytes = h[0];
+        SF_REQUIRE(h[1] == 0 && (d_names || n_bytes == 0), SFGPU_ERR_INVALID, "sfgpu_sam_open: offsets must start at 0 over non-null names");
+        if (int r = m->blob.reserve(n_bytes + 1, st, false)) return r;
+        if (n_bytes) SF_HIP(hipMemcpyAsync(m->blob.p, d_names, n_bytes, hipMemcpyDeviceToDevice, st));
+        SF_HIP(hipMemsetAsync(m->slot.p, 0, size * 4, st));
+        SF_HIP(hipMemsetAsync(flag.p, 0, 4, st));
+        if (M) {
+            hipLaunchKernelGGL(k_sam_table, dim3(grid_of(M)), dim3(kBlock), 0, st, m->blob.p, m->off.p, (uint32_t)M, m->slot.p, m->mask, flag.p);
+            SF_CHECK_LAUNCH();
+        }
+        uint32_t* h32 = reinterpret_cast<uint32_t*>(h);
+        SF_HIP(hipMemcpyAsync(h32, flag.p, 4, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipStreamSynchronize(st));
+        SF_REQUIRE(!(h32[0] & 2u), SFGPU_ERR_INVALID, "sfgpu_sam_open: the name offsets decrease");
+        SF_REQUIRE(!(h32[0] & 1u), SFGPU_ERR_INVALID, "sfgpu_sam_open: a transcript name occurs twice");
+        return SFGPU_OK;
+    };
+    const int rc = build();
+    if (rc != SFGPU_OK) { (void)hipStreamSynchronize(st); delete m; return rc; }
+    *out = m;
+    return SFGPU_OK;
+}
+
+extern "C" int sfgpu_sam_close(sfgpu_sam* m) {
+    if (!m) return SFGPU_OK;
+    (void)hipDeviceSynchronize();
+    delete m;
+    return SFGPU_OK;
+}
+
+extern "C" int sfgpu_sam_parse_host(sfgpu_sam* m, const char* h_text, uint64_t n_bytes, int final, sfgpu_hit* d_hits, uint64_t cap_hits,
+                                    uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream) {
+    if (int r = check_parse_args("sfgpu_sam_parse_host", m, h_text, n_bytes, d_hits, cap_hits, d_off, res)) return r;
+    hipStream_t st = as_stream(stream);
+    SF_HIP(hipMemsetAsync(d_off, 0, 4, st));
+    uint64_t used = n_bytes;
+    if (!final) while (used && h_text[used - 1] != '\n') --used;
+    if (used == 0) { SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
+    const bool append = h_text[used - 1] != '\n';            // (final only)
+    const uint64_t n_text = used + (append ? 1 : 0), n_groups = (n_text + 15) / 16, n_sub = (used + kSubBytes - 1) / kSubBytes;
+
+    Scratch S;
+    CallScope scope;        // after S: it drains both streams before S's blocks go back to the pool
+    hipStream_t cs = nullptr;
+    char* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev_slot[2] = {nullptr, nullptr}, ev_c0 = nullptr, ev_c1 = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
+    uint64_t* h = nullptr;
+    SF_HIP(scope.adopt(st));
+    SF_HIP(scope.acquire(&cs));
+    for (int b = 0; b < 2 && (uint64_t)b < n_sub; ++b) {
+        SF_HIP(scope.pinned_block(&pinned[b], (used < kSubBytes ? used : kSubBytes) + 48));
+        SF_HIP(scope.event(&ev_slot[b]));
+    }
+    for (hipEvent_t* e : {&ev_c0, &ev_c1, &ev_k0, &ev_k1}) SF_HIP(scope.event(e));
+    SF_HIP(scope.pinned_block(&h, 8 * sizeof(uint64_t)));
+    if (int r = S.text.reserve(n_groups + 1, st, false)) return r;
+    SF_HIP(hipEventRecord(ev_k0, st));
+    SF_HIP(hipStreamWaitEvent(cs, ev_k0, 0));                // the copies stay behind whatever `stream` held and behind the reservation
+    SF_HIP(hipEventRecord(ev_c0, cs));
+    for (uint64_t c = 0; c < n_sub; ++c) {
+        const int slot = (int)(c & 1);
+        if (c >= 2) SF_HIP(hipEventSynchronize(ev_slot[slot]));      // its previous copy has left the pinned buffer
+        const uint64_t p = c * kSubBytes, q = (c + 1 == n_sub) ? used : p + kSubBytes;
+        uint64_t n = q - p;
+        memcpy(pinned[slot], h_text + p, n);
+        if (c + 1 == n_sub) {
+            if (append) pinned[slot][n++] = '\n';
+            const uint64_t padded = (n + 15) & ~15ull;
+            memset(pinned[slot] + n, 0, padded - n);
+            n = padded;
+        }
+        SF_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.text.p) + p, pinned[slot], n, hipMemcpyHostToDevice, cs));
+        SF_HIP(hipEventRecord(ev_slot[slot], cs));
+    }
+    SF_HIP(hipEventRecord(ev_c1, cs));
+    SF_HIP(hipStreamWaitEvent(st, ev_c1, 0));
+    SF_HIP(hipEventRecord(ev_k0, st));
+    const int rc = parse_device_text(m, S, S.text.p, n_text, used, final != 0, d_hits, cap_hits, d_off, cap_reads, res, st, h);
+    SF_HIP(hipEventRecord(ev_k1, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&res->ms_copy, ev_c0, ev_c1);
+    add_elapsed(&res->ms_kernels, ev_k0, ev_k1);
+    return rc;
+}
+
+extern "C" int sfgpu_sam_parse_device(sfgpu_sam* m, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, sfgpu_hit* d_hits,
+                                      uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream) {
+    if (int r = check_parse_args("sfgpu_sam_parse_device", m, d_text, n_bytes, d_hits, cap_hits, d_off, res)) return r;
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_text) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_sam_parse_device: d_text must be 16-byte aligned");
+    SF_REQUIRE(n_bytes == 0 || cap_text >= ((n_bytes + 1 + 15) & ~15ull) + 16, SFGPU_ERR_INVALID,
+               "sfgpu_sam_parse_device: cap_text must hold the text, a '\\n', the rest of that 16-byte group and one group more");
+    hipStream_t st = as_stream(stream);
+    SF_HIP(hipMemsetAsync(d_off, 0, 4, st));
+    if (n_bytes == 0) { SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
+    Scratch S;
+    DevBuf<unsigned long long> last;
+    CallScope scope;        // after the scratch, as in sfgpu_sam_parse_host
+    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
+    uint64_t* h = nullptr;
+    SF_HIP(scope.adopt(st));
+    SF_HIP(scope.event(&ev_k0));
+    SF_HIP(scope.event(&ev_k1));
+    SF_HIP(scope.pinned_block(&h, 8 * sizeof(uint64_t)));
+    if (int r = last.reserve(1, st, false)) return r;
+    SF_HIP(hipEventRecord(ev_k0, st));
+    SF_HIP(hipMemsetAsync(last.p, 0, 8, st));
+    hipLaunchKernelGGL(textlines::k_last_nl, dim3(grid_of((n_bytes + 15) / 16)), dim3(kBlock), 0, st, d_text, n_bytes, last.p);
+    SF_CHECK_LAUNCH();
+    SF_HIP(hipMemcpyAsync(&h[7], last.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    const uint64_t used = final ? n_bytes : h[7];
+    int rc = SFGPU_OK;
+    if (used) {
+        uint64_t n_text = used;
+        if (final && h[7] != n_bytes) {                      // the last line lacks its '\n': it goes into the slack
+            SF_HIP(hipMemsetAsync(d_text + n_bytes, '\n', 1, st));
+            n_text = n_bytes + 1;
+        }
+        rc = parse_device_text(m, S, reinterpret_cast<const uint4*>(d_text), n_text, used, final != 0, d_hits, cap_hits, d_off, cap_reads, res, st, h);
+    }
+    SF_HIP(hipEventRecord(ev_k1, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&res->ms_kernels, ev_k0, ev_k1);
+    return rc;
+}

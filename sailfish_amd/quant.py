@@ -99,6 +99,37 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
                           remaining_fl_ops=rem_fl, gene_map=gene_map, seed=seed)
 
 
+def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, transcripts_path=None, device="cuda", block_bytes=32 << 20,
+                 inflate="auto", **kw):
+    """`sailfish quant` from a mapper's SAM file on (RapMap's `quasimap -o`, bowtie2, bwa against the transcriptome; plain, BGZF or
+    gzip; grouped by read name): the names and lengths come from the @SQ lines, the alignment lines are turned into hit records
+    on the device (samfile.SamFile) and handed to quantify batch by batch.  transcripts_path: the transcript FASTA, required with
+    biasCorrect / gcBiasCorrect (read with readfile.read_transcripts; its names and lengths must equal the header's, in order).
+    -> (rc, experiment)"""
+    from . import samfile
+    sopt = sopt or SailfishOpts()
+    fmt = _hits.LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(lib_format)
+    names, lengths = samfile.read_header(sam_path)
+    if not names:
+        raise ValueError(f"{sam_path}: no @SQ lines in the header")
+    seq_kw = {}
+    if sopt.biasCorrect or sopt.gcBiasCorrect:
+        if transcripts_path is None:
+            raise ValueError("bias correction needs the transcript sequences (transcripts_path)")
+        from .mapper import _dollar_separated
+        from .readfile import read_transcripts
+        t_names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
+        if t_names != names or np.diff(off.cpu().numpy()).tolist() != lengths:
+            raise ValueError(f"{transcripts_path}: the names and lengths of the transcripts are not those of the @SQ lines of {sam_path}")
+        s, o = _dollar_separated(bases, off)
+        seq_kw = dict(seq=s, seq_off=o)
+    batches = samfile.SamFile(sam_path, device, fmt[0] == 1, names=names, block_bytes=block_bytes, inflate=inflate)
+    try:
+        return quantify(names, np.array(lengths, np.uint32), batches, lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+    finally:
+        batches.close()
+
+
 def _quantify_tail(exp, sopt, out_dir, start_time, *, fl_counts, remaining_fl_ops, gene_map, seed, timings=None):
     """Everything after the class table is finished (shared by quantify and quantify_eq_classes): effective lengths
     (fl_counts None: the Gaussian prior, as a single-end run), [dumpEq], optimize with the bias recompute, quant.sf and aux/,

@@ -553,6 +553,36 @@ SFGPU_API int sfgpu_sam_parse_host(sfgpu_sam* s, const char* h_text, uint64_t n_
 SFGPU_API int sfgpu_sam_parse_device(sfgpu_sam* s, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, struct sfgpu_hit* d_hits,
                                      uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_sam_close(sfgpu_sam* s);
+/* The same records from a mapper's BAM file (`samtools view -b` of what the mapper wrote; grouped by read name).  The caller hands over
+ * the INFLATED stream (what sfgpu_bgzf_inflate_host wrote, or gzip on the host) in consecutive texts; what it says is stated once,
+ * serially, in csrc/bamfmt.h (the rules of samfile.read_bam_host), the kernels are csrc/bamtext.hip.  It is the SAM rule set with the
+ * text syntax taken away, with the same SFGPU_SAM_BAD_* bits: FIELDS is a block_size below 32 or below what l_read_name, n_cigar_op
+ * and l_seq need, an empty name or one without its NUL, or a final text that ends inside a record; NUMBER a mapped record whose pos is
+ * outside 0 .. 2^31 - 2; RNAME a refID outside the header's references or a reference that is no name of the handle; CIGAR an op
+ * code above 8; FLAG and LENGTH as in SAM (l_seq == 0 is SEQ '*', n_cigar_op == 0 is CIGAR '*').  Groups, pairs and the record
+ * order are SAM's.  A record's start is known only from the block_size in front of it: that chain is resolved exactly and in
+ * parallel (exit pointers per tile of the text by pointer doubling in LDS, then supertiles), never guessed.
+ *   open     d_names / d_name_off[M + 1] as in sfgpu_sam_open (the same table); d_ref_names / d_ref_off[n_ref + 1]: the header's
+ *            reference names in refID order, back to back (device arrays); they are joined to the names on the device, a reference
+ *            that is no transcript of the run makes the records on it BAD_RNAME.  header_bytes: the length of the binary header
+ *            ("BAM\1" .. the last l_ref) in the inflated stream.
+ *   parse_host / _device   the argument lists, limits, alignment and slack of sfgpu_sam_parse_host / _device.  The text of a call
+ *            begins at stream offset = the sum of the `consumed` values this handle has returned; the call skips
+ *            max(0, header_bytes - that sum) bytes itself, so a header larger than a text needs no special call.  A record that the
+ *            text does not hold whole, and everything behind it, is not looked at unless final != 0.  The last group of a text
+ *            that is not final is held back, and such a call that emits no group consumes nothing (consumed == 0, n_reads == 0:
+ *            "present more").  In the result n_lines counts the alignment records consumed, n_header is 0, bad_line is the 0-based
+ *            index of the lowest malformed record among the records of this text.  SFGPU_ERR_CAPACITY and SFGPU_ERR_FORMAT as
+ *            in sfgpu_sam_parse_*: nothing is written and nothing consumed.
+ * All calls are synchronous and ordered behind the work already on `stream`; one handle is used from one thread at a time.  No CPU path. */
+typedef struct sfgpu_bam sfgpu_bam;
+SFGPU_API int sfgpu_bam_open(sfgpu_bam** out, const char* d_names, const uint64_t* d_name_off, uint64_t M, const char* d_ref_names,
+                             const uint64_t* d_ref_off, uint64_t n_ref, uint64_t header_bytes, int paired, sfgpu_stream stream);
+SFGPU_API int sfgpu_bam_parse_host(sfgpu_bam* b, const char* h_text, uint64_t n_bytes, int final, struct sfgpu_hit* d_hits, uint64_t cap_hits,
+                                   uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_bam_parse_device(sfgpu_bam* b, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, struct sfgpu_hit* d_hits,
+                                     uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_bam_close(sfgpu_bam* b);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

@@ -230,6 +230,10 @@ _SIGS = {
     "sfgpu_sam_parse_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_sam_parse_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_sam_close": (C.c_int, [_P]),
+    "sfgpu_bam_open": (C.c_int, [C.POINTER(_P), _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint64, C.c_int, _P]),
+    "sfgpu_bam_parse_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
+    "sfgpu_bam_parse_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
+    "sfgpu_bam_close": (C.c_int, [_P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),

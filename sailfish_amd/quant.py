@@ -103,7 +103,9 @@ def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, tr
                  inflate="auto", **kw):
     """`sailfish quant` from a mapper's SAM file on (RapMap's `quasimap -o`, bowtie2, bwa against the transcriptome; plain, BGZF or
     gzip; grouped by read name): the names and lengths come from the @SQ lines, the alignment lines are turned into hit records
-    on the device (samfile.SamFile) and handed to quantify batch by batch.  transcripts_path: the transcript FASTA, required with
+    on the device (samfile.SamFile) and handed to quantify batch by batch.  `sam_path` may as well be the BAM file that
+    `samtools view -b` made of that output (name-grouped, not position-sorted): the names and lengths then come from its binary
+    reference list, and its record stream is parsed on the device behind the BGZF inflate.  transcripts_path: the transcript FASTA, required with
     biasCorrect / gcBiasCorrect (read with readfile.read_transcripts; its names and lengths must equal the header's, in order).
     -> (rc, experiment)"""
     from . import samfile

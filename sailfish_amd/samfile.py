@@ -7,10 +7,16 @@ BGZF and -- with inflate="device" -- ordinary gzip inflated on the device and pa
 The header is: `read_header` reads the @SQ lines with Python, they are a thousandth of a real file.
 
 The file must be grouped by read name, as mappers write it (all lines of a fragment follow each other); a position-sorted file
-is not.  `write_sam` is the way back: hit records as SAM text, for the device mapper's output and for tests."""
+is not.  `write_sam` is the way back: hit records as SAM text, for the device mapper's output and for tests.
+
+BAM (what `samtools view -b` makes of the same alignments) is read too: a BGZF file whose first member inflates to "BAM\1".  What
+its record stream says is csrc/bamfmt.h, `read_bam_host` is the contract, the device side is csrc/bamtext.hip behind
+sfgpu_bam_parse_host / _device, and `SamFile` picks the format by itself (`SamFile.format`).  `sam_to_bam`, `bam_to_sam` and
+`write_bam` are host-side converters, for tests and for the way back."""
 import ctypes as C
 import gzip
 import re
+import struct
 
 import numpy as np
 
@@ -23,6 +29,14 @@ KINDS = {BAD_FIELDS: "fewer than 11 tab-separated fields",
          BAD_RNAME: "RNAME is not one of the transcript names",
          BAD_CIGAR: "CIGAR is neither '*' nor a run of (1-9 digits, one of MIDNSHP=X)",
          BAD_LENGTH: "the read is longer than 65535 bases, or SEQ and CIGAR disagree about its length"}
+BAM_KINDS = {BAD_FIELDS: "block_size is below 32 or below what l_read_name, n_cigar_op and l_seq need, the name is empty or lacks its NUL, "
+                         "or the file ends inside the record",
+             BAD_NUMBER: "pos of a mapped record is not in 0 .. 2^31 - 2",
+             BAD_FLAG: KINDS[BAD_FLAG],
+             BAD_RNAME: "refID of a mapped record is not in 0 .. n_ref - 1, or its reference is not one of the transcript names",
+             BAD_CIGAR: "a CIGAR op code above 8",
+             BAD_LENGTH: "the read is longer than 65535 bases, or l_seq and the CIGAR disagree about its length"}
+BAM_MAGIC = b"BAM\x01"
 _CIGAR = re.compile(rb"(?:[0-9]{1,9}[MIDNSHP=X])+")
 _CIGAR_OP = re.compile(rb"([0-9]+)([MIDNSHP=X])")
 _LEAD = re.compile(rb"(?:[0-9]+H)*((?:[0-9]+S)*)")
@@ -32,6 +46,22 @@ def _malformed(path, line, kind):
     return ValueError(f"{path}: line {line} is malformed: {KINDS[kind]} (kind {kind})")
 
 
+def _malformed_bam(path, record, kind):
+    return ValueError(f"{path}: record {record} is malformed: {BAM_KINDS[kind]} (kind {kind})")
+
+
+def is_bam(path):
+    """a gzip (BGZF, as a rule) file whose first bytes inflate to the BAM magic"""
+    with open(path, "rb") as f:
+        if f.read(2) != b"\x1f\x8b":
+            return False
+    try:
+        with gzip.open(path, "rb") as f:
+            return f.read(4) == BAM_MAGIC
+    except (OSError, EOFError):
+        return False
+
+
 def _open_text(path):
     with open(path, "rb") as f:
         gz = f.read(2) == b"\x1f\x8b"
@@ -39,7 +69,10 @@ def _open_text(path):
 
 
 def read_header(path):
-    """(names, lengths) of the @SQ lines (SN:, LN:) in front of the first alignment line, in file order; plain or gzip"""
+    """(names, lengths) of the @SQ lines (SN:, LN:) in front of the first alignment line, in file order; plain or gzip.  Of a BAM
+    file: its binary reference list (read_bam_header)."""
+    if is_bam(path):
+        return read_bam_header(path)[:2]
     names, lengths = [], []
     with _open_text(path) as f:
         for n, line in enumerate(f, 1):
@@ -141,6 +174,275 @@ def read_sam_host(data, names, paired, path="<sam>", counts=None):
     return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
 
 
+# ---- the BAM contract -------------------------------------------------------------------------------------------------------
+
+def _bam_header(data):
+    """the header of an inflated BAM stream -> (names, lengths, header_bytes, text), or None when `data` ends inside it"""
+    if len(data) < 4:
+        return None
+    if data[:4] != BAM_MAGIC:
+        raise ValueError("not a BAM stream: it does not begin with 'BAM\\1'")
+    if len(data) < 12:
+        return None
+    p = 8 + struct.unpack_from("<I", data, 4)[0]
+    if len(data) < p + 4:
+        return None
+    text, n_ref = bytes(data[8:p]), struct.unpack_from("<I", data, p)[0]
+    p += 4
+    names, lengths = [], []
+    for _ in range(n_ref):
+        if len(data) < p + 4:
+            return None
+        l_name = struct.unpack_from("<I", data, p)[0]
+        if len(data) < p + 4 + l_name + 4:
+            return None
+        if l_name == 0:
+            raise ValueError("a BAM reference without a name")
+        names.append(bytes(data[p + 4:p + 4 + l_name - 1]).decode("utf-8", "surrogateescape"))
+        lengths.append(struct.unpack_from("<I", data, p + 4 + l_name)[0])
+        p += 4 + l_name + 4
+    return names, lengths, p, text
+
+
+def read_bam_header(path):
+    """(names, lengths, header_bytes, text) of a BAM file: the reference list in file order, the length of the binary header in
+    the inflated stream, and the SAM header text it carries.  Members are inflated on the host (zlib, through gzip) until the
+    header is whole: it is a thousandth of the file, like the @SQ lines."""
+    with gzip.open(path, "rb") as f:
+        data, want = b"", 1 << 16
+        while True:
+            more = f.read(want - len(data))
+            data += more
+            try:
+                head = _bam_header(data)
+            except ValueError as e:
+                raise ValueError(f"{path}: {e}") from None
+            if head is not None:
+                return head
+            if not more:
+                raise ValueError(f"{path}: the file ends inside the BAM header")
+            want *= 2
+
+
+def _parse_record(data, p, ref_tid, paired):
+    """the record at p, whole in data -> (kind, None) or (0, (qname, mapped, side, tid, pos, read_len, fwd)): csrc/bamfmt.h"""
+    block_size, ref, pos, l_name, _mapq, _bin, n_cigar, flag, l_seq = struct.unpack_from("<iiiBBHHHI", data, p)
+    if block_size < 32 + l_name + 4 * n_cigar + (l_seq + 1) // 2 + l_seq or l_name == 0 or data[p + 36 + l_name - 1] != 0:
+        return BAD_FIELDS, None
+    qname, bad = bytes(data[p + 36:p + 36 + l_name - 1]), 0
+    first, second = bool(flag & 0x40), bool(flag & 0x80)
+    if (not flag & 0x1 or first == second) if paired else flag & 0x1:
+        bad |= BAD_FLAG
+    side = (1 if first else 2) if paired else 0
+    if flag & (0x4 | 0x800):
+        return bad, (qname, False, side, 0, 0, 0, not flag & 0x10)
+    if not 0 <= pos <= 2 ** 31 - 2:
+        bad |= BAD_NUMBER
+    tid = ref_tid[ref] if 0 <= ref < len(ref_tid) else None
+    if tid is None:
+        bad |= BAD_RNAME
+    ops = [(w >> 4, w & 15) for w in struct.unpack_from("<%dI" % n_cigar, data, p + 36 + l_name)]
+    read_len = lead = 0
+    if any(op > 8 for _, op in ops):
+        bad |= BAD_CIGAR
+    else:
+        qlen = sum(n for n, op in ops if op in (0, 1, 4, 7, 8))            # M I S = X
+        k = 0
+        while k < len(ops) and ops[k][1] == 5:                             # the leading H ...
+            k += 1
+        while k < len(ops) and ops[k][1] == 4:                             # ... and the S behind them
+            lead += ops[k][0]
+            k += 1
+        read_len = l_seq if l_seq else qlen
+        if read_len > 65535 or (l_seq and n_cigar and l_seq != qlen):
+            bad |= BAD_LENGTH
+    if bad:
+        return bad & -bad, None
+    return 0, (qname, True, side, tid, pos - lead, read_len, not flag & 0x10)
+
+
+def read_bam_host(data, names, paired, path="<bam>", counts=None):
+    """The rules for BAM, on the host, written to be read: `data` (bytes: a whole inflated BAM stream, header included) -> what
+    read_sam_host returns.  The record chain is walked from the header's end; a record whose block_size is below 32, or that the
+    stream ends in, is BAD_FIELDS.  Raises the ValueError SamFile raises (lowest malformed record, 1-based; first broken rule).
+    `counts` receives lines (= records) / header (0) / reads / hits / pairs."""
+    data = bytes(data)
+    head = _bam_header(data)
+    if head is None:
+        raise ValueError(f"{path}: the file ends inside the BAM header")
+    refs, _, p, _ = head
+    tid_of = {nm: i for i, nm in enumerate(_name_bytes(names))}
+    ref_tid = [tid_of.get(r) for r in _name_bytes(refs)]
+    groups, n = [], 0
+    while p < len(data):
+        n += 1
+        if len(data) - p < 4:
+            raise _malformed_bam(path, n, BAD_FIELDS)
+        block_size = struct.unpack_from("<i", data, p)[0]
+        if block_size < 32 or p + 4 + block_size > len(data):
+            raise _malformed_bam(path, n, BAD_FIELDS)
+        kind, rec = _parse_record(data, p, ref_tid, paired)
+        if kind:
+            raise _malformed_bam(path, n, kind)
+        if groups and groups[-1][-1][0] == rec[0]:
+            groups[-1].append(rec)
+        else:
+            groups.append([rec])
+        p += 4 + block_size
+    recs, off = [], [0]
+    for g in groups:
+        recs.extend(_group_records(g, paired))
+        off.append(len(recs))
+    if counts is not None:
+        counts.update(lines=n, header=0, reads=len(groups), hits=len(recs), pairs=sum(r[8] == 3 for r in recs))
+    return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
+
+
+# ---- SAM text <-> BAM stream (host) ------------------------------------------------------------------------------------------
+
+_OPS = b"MIDNSHP=X"
+_BASES = b"=ACMGRSVTWYHKDBN"
+_BASE_CODE = {c: i for i, c in enumerate(_BASES)}
+_TAG_INT = {b"c": "<b", b"C": "<B", b"s": "<h", b"S": "<H", b"i": "<i", b"I": "<I"}
+
+
+def _reg2bin(beg, end):
+    """the SAM specification's bin of the zero-based half-open interval [beg, end)"""
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def sam_to_bam(text):
+    """SAM text -> the uncompressed BAM stream of the same alignments.  The references are the @SQ lines, every '@' line goes into
+    the header text; bin is the specification's reg2bin, SEQ is 4-bit packed, QUAL '*' becomes 0xFF bytes.  Optional fields of the
+    types A, i, f and Z are converted; any other, a QNAME above 254 bytes, or a line the SAM rules reject is a ValueError."""
+    lines = bytes(text).split(b"\n")
+    if lines[-1] == b"":
+        lines.pop()
+    lines = [l[:-1] if l.endswith(b"\r") else l for l in lines]
+    head = [l for l in lines if l.startswith(b"@")]
+    refs = []
+    for l in head:
+        if l.startswith(b"@SQ\t"):
+            tags = {x[:2]: x[3:] for x in l.split(b"\t")[1:] if x[2:3] == b":"}
+            if b"SN" not in tags or not tags.get(b"LN", b"").isdigit():
+                raise ValueError("an @SQ line without SN: and a numeric LN:")
+            refs.append((tags[b"SN"], int(tags[b"LN"])))
+    tid_of = {nm: i for i, (nm, _) in enumerate(refs)}
+    htext = b"".join(l + b"\n" for l in head)
+    out = [BAM_MAGIC, struct.pack("<I", len(htext)), htext, struct.pack("<I", len(refs))]
+    out += [struct.pack("<I", len(nm) + 1) + nm + b"\0" + struct.pack("<I", ln) for nm, ln in refs]
+    for n, l in enumerate(lines, 1):
+        if l.startswith(b"@"):
+            continue
+        f = l.split(b"\t")
+        flag = int(f[1]) if len(f) > 1 and f[1].isdigit() and len(f[1]) <= 5 else 0
+        kind, _ = _parse_line(l, tid_of, bool(flag & 0x1))
+        if kind:
+            raise ValueError(f"line {n} is malformed: {KINDS[kind]} (kind {kind})")
+        qname, rname, cigar, rnext, seq, qual = f[0], f[2], f[5], f[6], f[9], f[10]
+        if not 1 <= len(qname) <= 254:
+            raise ValueError(f"line {n}: a QNAME of {len(qname)} bytes does not fit BAM")
+        try:
+            pos, mapq, pnext, tlen = int(f[3]) - 1, int(f[4]), int(f[7]) - 1, int(f[8])
+            ref = -1 if rname == b"*" else tid_of[rname]
+            nref = -1 if rnext == b"*" else ref if rnext == b"=" else tid_of[rnext]
+        except (ValueError, KeyError):
+            raise ValueError(f"line {n}: POS, MAPQ, PNEXT or TLEN is no number, or RNAME / RNEXT is no @SQ name") from None
+        ops = [] if cigar == b"*" else [(int(c), _OPS.index(op)) for c, op in _CIGAR_OP.findall(cigar)]
+        if cigar != b"*" and (not _CIGAR.fullmatch(cigar) or len(ops) > 65535 or any(c >= 1 << 28 for c, _ in ops)):
+            raise ValueError(f"line {n}: the CIGAR does not fit BAM")
+        ref_len = sum(c for c, op in ops if op in (0, 2, 3, 7, 8))
+        bases = b"" if seq == b"*" else seq
+        if qual != b"*" and len(qual) != len(bases):
+            raise ValueError(f"line {n}: SEQ and QUAL differ in length")
+        packed = bytearray((len(bases) + 1) // 2)
+        for i, c in enumerate(bases.upper()):
+            packed[i >> 1] |= _BASE_CODE.get(c, 15) << (0 if i & 1 else 4)
+        tags = []
+        for t in f[11:]:
+            if len(t) < 5 or t[2:3] != b":" or t[4:5] != b":" or t[3:4] not in b"AifZ":
+                raise ValueError(f"line {n}: the optional field {t!r} is not of type A, i, f or Z")
+            ty, v = t[3:4], t[5:]
+            try:
+                if ty == b"A" and len(v) == 1:
+                    tags.append(t[:2] + b"A" + v)
+                elif ty == b"i":
+                    x = int(v)
+                    code = next(c for c, (lo, hi) in ((b"c", (-128, 127)), (b"C", (0, 255)), (b"s", (-32768, 32767)), (b"S", (0, 65535)),
+                                                      (b"i", (-2 ** 31, 2 ** 31 - 1)), (b"I", (0, 2 ** 32 - 1))) if lo <= x <= hi)
+                    tags.append(t[:2] + code + struct.pack(_TAG_INT[code], x))
+                elif ty == b"f":
+                    tags.append(t[:2] + b"f" + struct.pack("<f", float(v)))
+                elif ty == b"Z":
+                    tags.append(t[:2] + b"Z" + v + b"\0")
+                else:
+                    raise ValueError
+            except (ValueError, StopIteration):
+                raise ValueError(f"line {n}: the optional field {t!r} is ill-formed") from None
+        body = b"".join([struct.pack("<iiBBHHHIiii", ref, pos, len(qname) + 1, mapq & 255,
+                                     _reg2bin(pos, pos + max(ref_len, 1)) if pos >= 0 else 4680, len(ops), flag, len(bases), nref, pnext, tlen),
+                         qname, b"\0", struct.pack("<%dI" % len(ops), *[c << 4 | op for c, op in ops]), bytes(packed),
+                         b"\xff" * len(bases) if qual == b"*" else bytes(q - 33 for q in qual)] + tags)
+        out += [struct.pack("<i", len(body)), body]
+    return b"".join(out)
+
+
+def _tag_text(data, p, end):
+    """the optional fields in data[p:end] as SAM text fields"""
+    out = []
+    while p < end:
+        tag, ty = bytes(data[p:p + 2]), bytes(data[p + 2:p + 3])
+        p += 3
+        if ty == b"A":
+            out.append(tag + b":A:" + bytes(data[p:p + 1])); p += 1
+        elif ty in _TAG_INT:
+            out.append(tag + b":i:%d" % struct.unpack_from(_TAG_INT[ty], data, p)[0]); p += struct.calcsize(_TAG_INT[ty])
+        elif ty == b"f":
+            out.append(tag + b":f:" + repr(struct.unpack_from("<f", data, p)[0]).encode()); p += 4
+        elif ty in (b"Z", b"H"):
+            e = data.index(b"\0", p)
+            out.append(tag + b":" + ty + b":" + bytes(data[p:e])); p = e + 1
+        elif ty == b"B":
+            sub, count = bytes(data[p:p + 1]), struct.unpack_from("<I", data, p + 1)[0]
+            fmt = "<f" if sub == b"f" else _TAG_INT[sub]
+            vals = struct.unpack_from("<%d%s" % (count, fmt[1]), data, p + 5)
+            out.append(tag + b":B:" + sub + b"".join(b",%s" % repr(v).encode() for v in vals)); p += 5 + count * struct.calcsize(fmt)
+        else:
+            raise ValueError(f"an optional field of the unknown type {ty!r}")
+    return out
+
+
+def bam_to_sam(data):
+    """an inflated BAM stream -> SAM text (host): the header text, then one line per record"""
+    data = bytes(data)
+    head = _bam_header(data)
+    if head is None:
+        raise ValueError("the stream ends inside the BAM header")
+    refs, _, p, text = head
+    refs = _name_bytes(refs)
+    out = [text if not text or text.endswith(b"\n") else text + b"\n"]
+    while p < len(data):
+        block_size, ref, pos, l_name, mapq, _bin, n_cigar, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiiBBHHHIiii", data, p)
+        end = p + 4 + block_size
+        if block_size < 32 or end > len(data):
+            raise ValueError(f"the record at byte {p} of the stream is broken")
+        q = p + 36
+        qname = data[q:q + l_name - 1]; q += l_name
+        cigar = b"".join(b"%d%c" % (w >> 4, _OPS[w & 15]) for w in struct.unpack_from("<%dI" % n_cigar, data, q)) or b"*"; q += 4 * n_cigar
+        seq = bytes(_BASES[data[q + (i >> 1)] >> (0 if i & 1 else 4) & 15] for i in range(l_seq)) or b"*"; q += (l_seq + 1) // 2
+        qual = b"*" if l_seq == 0 or data[q] == 0xff else bytes(x + 33 for x in data[q:q + l_seq]); q += l_seq
+        rname = refs[ref] if ref >= 0 else b"*"
+        rnext = b"*" if nref < 0 else b"=" if nref == ref else refs[nref]
+        out.append(b"\t".join([qname, b"%d" % flag, rname, b"%d" % (pos + 1), b"%d" % mapq, cigar, rnext, b"%d" % (npos + 1), b"%d" % tlen, seq, qual]
+                              + _tag_text(data, q, end)) + b"\n")
+        p = end
+    return b"".join(out)
+
+
 # ---- the way back ---------------------------------------------------------------------------------------------------------
 
 def _aligned(pos, length, what):
@@ -152,13 +454,8 @@ def _aligned(pos, length, what):
     return 1, b"%dS%dM" % (-pos, length + pos)
 
 
-def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False):
-    """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
-    line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
-    a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
-    `seqs` gives, per read, the bases (single end) or a (mate 1, mate 2) pair, written as given.  `read_names`: per read, default
-    r<index>.  The library is taken as paired when any record is, or, without records, when seqs holds pairs.  bgzf=True writes
-    blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan."""
+def _sam_text(names, ref_len, hits, offsets, read_names, seqs):
+    """the text write_sam writes"""
     hits = np.asarray(hits).view(HIT_DTYPE).reshape(-1)
     off = np.asarray(offsets).astype(np.int64)
     paired = bool((hits["mate_status"] != 0).any()) if len(hits) else bool(seqs and isinstance(seqs[0], tuple))
@@ -188,7 +485,17 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
                                    s1 if status == 1 else s2))
             else:
                 out.append(line % (q, sec | (0 if fwd else 0x10), nm[tid], p1, c1, b"*", 0, 0, s1))
-    data = b"".join(out)
+    return b"".join(out)
+
+
+def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False):
+    """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
+    line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
+    a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
+    `seqs` gives, per read, the bases (single end) or a (mate 1, mate 2) pair, written as given.  `read_names`: per read, default
+    r<index>.  The library is taken as paired when any record is, or, without records, when seqs holds pairs.  bgzf=True writes
+    blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan."""
+    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs)
     if bgzf:
         from . import gzfile
         gzfile.write_bgzf(path, data)
@@ -197,16 +504,28 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
             f.write(data)
 
 
+def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280):
+    """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
+    members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf)."""
+    from . import gzfile
+    gzfile.write_bgzf(path, sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs)), member_bytes=member_bytes)
+
+
 # ---- the device reader ----------------------------------------------------------------------------------------------------
 
 class SamFile:
-    """A SAM file (plain, BGZF or gzip) read through the device parser: iterating yields (hits: uint8 device tensor [n_hits * 24] of
+    """A SAM file (plain, BGZF or gzip) or a BAM file read through the device parser: iterating yields (hits: uint8 device tensor [n_hits * 24] of
     HIT_DTYPE records, offsets: int32 device tensor [n_reads + 1], starting at 0 in every batch), one batch per block of the file.
 
     `names`: the transcript names in index order; default: the file's @SQ lines (read_header).  `paired`: the library's rules
     (csrc/samfmt.h).  `inflate` and block_bytes as readfile.ReadFile takes them.  `stats` counts lines, header lines, reads, hits,
     pairs and blocks (parse calls that emitted a batch or ended the file) and sums the device times.  A malformed line raises
-    ValueError naming the path, the 1-based line number in the file and the kind; the batch that holds it is not emitted."""
+    ValueError naming the path, the 1-based line number in the file and the kind; the batch that holds it is not emitted.
+
+    `format` says what the file is: "sam" or "bam" (a gzip file whose first bytes inflate to "BAM\1").  A BAM file goes through
+    readfile.DeviceInflate and sfgpu_bam_parse_device (inflate "auto" or "device") or gzip, BlockCarry and sfgpu_bam_parse_host
+    ("host", and whenever the gzip file is not BGZF); its reference list is the default for `names`, `lines` counts its alignment
+    records (`header_lines` stays 0) and a malformed record is named by its 1-based number among them (BAM_KINDS)."""
 
     def __init__(self, path, device="cuda", paired=True, names=None, block_bytes=32 << 20, inflate="auto"):
         import torch
@@ -215,7 +534,11 @@ class SamFile:
         if inflate not in ("auto", "host", "device"):
             raise ValueError("inflate must be 'auto', 'host' or 'device'")
         self.path, self.device, self.paired = str(path), torch.device(device), bool(paired)
-        if names is None:
+        self.format = "bam" if is_bam(self.path) else "sam"
+        if self.format == "bam":
+            refs, _, header_bytes, _ = read_bam_header(self.path)
+            names = refs if names is None else names
+        elif names is None:
             names, _ = read_header(self.path)
             if not names:
                 raise ValueError(f"{self.path}: no @SQ lines: give the transcript names (names=)")
@@ -225,17 +548,26 @@ class SamFile:
         gzipped = head[:2] == b"\x1f\x8b"
         bgzf = gzipped and readfile.bgzf_member_bytes(head) is not None
         self.inflate = None if not gzipped else "device" if inflate == "device" or (inflate == "auto" and bgzf) else "host"
+        if self.format == "bam" and not bgzf:
+            self.inflate = "host"
         self.stats = dict(lines=0, header_lines=0, reads=0, hits=0, pairs=0, blocks=0, calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0,
                           ms_inflate=0.0, bytes_compressed=0, members=0, chunks=0, candidates=0, false_starts=0, ms_find=0.0, ms_decode=0.0,
                           ms_propagate=0.0, ms_emit=0.0)
-        nb = _name_bytes(names)
-        blob = np.frombuffer(b"".join(nb), np.uint8)
-        off = np.concatenate([[0], np.cumsum([len(x) for x in nb], dtype=np.int64)]).astype(np.int64)
-        d_blob = torch.from_numpy(blob.copy()).to(self.device) if blob.size else None
-        d_off = torch.from_numpy(off).to(self.device)
+        def on_device(items):
+            nb = _name_bytes(items)
+            blob = np.frombuffer(b"".join(nb), np.uint8)
+            off = np.concatenate([[0], np.cumsum([len(x) for x in nb], dtype=np.int64)]).astype(np.int64)
+            return torch.from_numpy(blob.copy()).to(self.device) if blob.size else None, torch.from_numpy(off).to(self.device), len(nb)
+
+        d_blob, d_off, n_names = on_device(names)
         self._h = C.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self._L.sfgpu_sam_open(C.byref(self._h), _lib.ptr(d_blob), _lib.ptr(d_off), len(nb), int(self.paired), _lib.current_stream_ptr())
+            if self.format == "bam":
+                d_rblob, d_roff, n_ref = on_device(refs)
+                rc = self._L.sfgpu_bam_open(C.byref(self._h), _lib.ptr(d_blob), _lib.ptr(d_off), n_names, _lib.ptr(d_rblob), _lib.ptr(d_roff), n_ref,
+                                            header_bytes, int(self.paired), _lib.current_stream_ptr())
+            else:
+                rc = self._L.sfgpu_sam_open(C.byref(self._h), _lib.ptr(d_blob), _lib.ptr(d_off), n_names, int(self.paired), _lib.current_stream_ptr())
         if rc == _lib.ERR_INVALID:
             raise ValueError(f"{self.path}: {self._L.sfgpu_last_error().decode('utf-8', 'replace')}")
         _lib.check(rc)
@@ -251,7 +583,8 @@ class SamFile:
         import torch
 
         from . import _lib, readfile
-        cap_reads = n // 11 + 1                            # a read has a line, a line ten tabs and (but for the last) a '\n'
+        # a read has a line, a line ten tabs and (but for the last) a '\n'; a BAM record has 36 bytes or more
+        cap_reads = n // 36 + 1 if self.format == "bam" else n // 11 + 1
         cap_hits = n // 64 + 1024                          # a guess: the call says what it needs
         off = torch.empty(cap_reads + 1, dtype=torch.int32, device=self.device)
         res = _lib.SamResult()
@@ -263,7 +596,7 @@ class SamFile:
                     break
                 cap_hits = int(res.need_hits)
         if rc == _lib.ERR_FORMAT and res.bad:
-            raise _malformed(self.path, self.stats["lines"] + int(res.bad_line) + 1, int(res.bad))
+            raise (_malformed_bam if self.format == "bam" else _malformed)(self.path, self.stats["lines"] + int(res.bad_line) + 1, int(res.bad))
         _lib.check(rc)
         st = self.stats
         st["calls"] += 1; st["ms_copy"] += res.ms_copy; st["ms_kernels"] += res.ms_kernels
@@ -277,7 +610,8 @@ class SamFile:
     def _parse_host(self, text, final, _max_reads):
         from . import _lib
         n = int(text.size)
-        return self._call(n, final, lambda hits, ch, off, cr, res: self._L.sfgpu_sam_parse_host(
+        parse = self._L.sfgpu_bam_parse_host if self.format == "bam" else self._L.sfgpu_sam_parse_host
+        return self._call(n, final, lambda hits, ch, off, cr, res: parse(
             self._h, _lib.ptr(text), n, int(final), _lib.ptr(hits), ch, _lib.ptr(off), cr, C.byref(res), _lib.current_stream_ptr()))
 
     def _parse_device(self, text, lo, hi, final, _max_reads, _records):
@@ -287,7 +621,8 @@ class SamFile:
             text[:n] = text[lo:hi].clone()
             self._carry.lo, self._carry.hi, lo, hi = 0, n, 0, n
         view = text[lo:]
-        out = self._call(n, final, lambda hits, ch, off, cr, res: self._L.sfgpu_sam_parse_device(
+        parse = self._L.sfgpu_bam_parse_device if self.format == "bam" else self._L.sfgpu_sam_parse_device
+        out = self._call(n, final, lambda hits, ch, off, cr, res: parse(
             self._h, _lib.ptr(view), n, view.numel(), int(final), _lib.ptr(hits), ch, _lib.ptr(off), cr, C.byref(res), _lib.current_stream_ptr()))
         if out.n_reads and not final:
             self._carry.starved = True                     # what is left is one group that has not ended: inflate before the next call
@@ -309,7 +644,7 @@ class SamFile:
         if self._h is not None:
             import torch
             with torch.cuda.device(self.device):
-                self._L.sfgpu_sam_close(self._h)
+                (self._L.sfgpu_bam_close if self.format == "bam" else self._L.sfgpu_sam_close)(self._h)
             self._h = None
             self._f.close()
             if self.inflate == "device":

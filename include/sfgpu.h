@@ -38,7 +38,7 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*) */
-    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_gz_*) */
     SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*) */
 };
 
@@ -583,6 +583,48 @@ SFGPU_API int sfgpu_bam_parse_host(sfgpu_bam* b, const char* h_text, uint64_t n_
 SFGPU_API int sfgpu_bam_parse_device(sfgpu_bam* b, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, struct sfgpu_hit* d_hits,
                                      uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bam_close(sfgpu_bam* b);
+/* The other direction (what `rapmap quasimap -o` offers): the ALIGNMENT LINES of a SAM file formatted on the device from one batch of
+ * hit records in CSR form, as sfgpu_map_reads and sfgpu_sam_parse_* leave it.  What the lines say is stated once, serially, in
+ * csrc/samwfmt.h (the bytes of samfile._sam_text); the kernels are csrc/samtext_write.hip.  In short, per read in order: a pair
+ * record (mate_status 3) gives its 0x40 and its 0x80 line, any other record one line (orphans with 0x8, single-end records
+ * without 0x1), 0x100 from the read's second record on; a read without records gives 77 / 141 (paired != 0) or one 4 line.
+ * MAPQ 255, CIGAR <len>M or <clip>S<rest>M, QUAL '*'; SEQ is written as given, also on 0x10 lines.  The @HD / @SQ header is the
+ * host's business.
+ *   d_hits / d_hit_offsets[n_reads + 1]   the batch (uint32 offsets, starting at 0, never decreasing, else SFGPU_ERR_INVALID).
+ *   d_ref_names / d_ref_name_off[n_refs + 1]   the transcript names back to back, uint64 offsets (quantfile.names_blob).
+ *   d_qnames / d_qname_off[n_reads + 1]   the read names, likewise; d_qname_off == NULL: read r is named r<read_index_base + r>.
+ *   d_seq1 / d_seq1_off[n_reads + 1]   the bases of mate 1 (of the reads, single end) back to back with int64 offsets, as
+ *            sfgpu_reads_parse_* and sfgpu_map_reads take them; d_seq1_off == NULL: SEQ is '*'.  d_seq2 / d_seq2_off: mate 2, read
+ *            only when paired != 0.  Names and bases are copied verbatim, never inspected, of any length including 0.
+ * A record with pos < 0 and -pos >= read_len (no base on the transcript; for a pair record either mate), or with tid >= n_refs,
+ * cannot be written: the call returns SFGPU_ERR_INVALID before any sink call, error_read / error_record name the lowest such
+ * (read, record) of the batch and error_kind says which rule (1 position, 2 tid; the position first where one record breaks both).
+ * The text is handed to `sink` as sfgpu_quant_write_text hands over its rows: consecutive chunks of at most chunk_bytes (0 = 32
+ * MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID), greedy, each a whole number of UNITS -- a unit is what one record or one
+ * record-less read produces, so the two lines of a pair are never split -- from a pinned staging buffer that is valid only during
+ * the call, chunk c + 1 formatted and copied while the sink consumes chunk c.  A unit longer than chunk_bytes is SFGPU_ERR_RANGE
+ * before the first sink call (`out` holds the sizes); a nonzero return of the sink ends the call with SFGPU_ERR_IO and no further
+ * sink call; sink == NULL sizes (and checks) only; n_reads == 0 is SFGPU_OK with zero bytes and no sink call.
+ * Synchronous; ordered behind whatever is queued on `stream`; independent calls may run from several threads.  Scratch on the
+ * device: 8 bytes per read, 16 bytes per unit and two chunk buffers. */
+typedef struct {
+    uint64_t n_bytes;         /* bytes of the alignment lines */
+    uint64_t n_lines;
+    uint64_t n_chunks;        /* sink calls made */
+    uint64_t max_unit_bytes;  /* longest unit, with its '\n's */
+    uint64_t error_read;      /* SFGPU_ERR_INVALID with error_kind != 0: the lowest (read, record) that cannot be written */
+    uint64_t error_record;
+    uint32_t error_kind;      /* 0 none, 1 no base on the transcript, 2 tid >= n_refs */
+    uint32_t pad_;
+    double format_ms;         /* device events: checks, sizing, scans, chunk plan, format kernels of all chunks */
+    double d2h_ms;            /* device events around the staged copies */
+    double sink_ms;           /* host clock inside the sink */
+} sfgpu_samwrite_result;
+SFGPU_API int sfgpu_sam_write_text(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                   const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                   const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                   const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                   void* user, sfgpu_samwrite_result* out, sfgpu_stream stream);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE

@@ -133,6 +133,15 @@ class SamResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class SamWriteResult(C.Structure):
+    _fields_ = [("n_bytes", C.c_uint64), ("n_lines", C.c_uint64), ("n_chunks", C.c_uint64), ("max_unit_bytes", C.c_uint64),
+                ("error_read", C.c_uint64), ("error_record", C.c_uint64), ("error_kind", C.c_uint32), ("pad_", C.c_uint32),
+                ("format_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class GzResult(C.Structure):
     _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("encode_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -234,6 +243,8 @@ _SIGS = {
     "sfgpu_bam_parse_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_bam_parse_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_bam_close": (C.c_int, [_P]),
+    "sfgpu_sam_write_text": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
+                                       C.POINTER(SamWriteResult), _P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),

@@ -1,0 +1,359 @@
+// samtext_write.hip -- the mapper's hit records as SAM alignment lines, formatted on the device from the CSR batch where it
+// lies: sfgpu_sam_write_text, the mirror of samtext.hip.  WHAT a line says is samwfmt.h (the bytes of samfile._sam_text); this
+// file finds where every line lies and writes it.
+//
+// A UNIT is what one hit record (one line, or the two lines of a pair record) or one read without records (its 4 line, or its
+// 77 / 141 lines) produces.  Units are numbered in file order: the unit of hit h of read r is h + e(r), that of a record-less
+// read r is hit_off[r] + e(r), with e(r) = the record-less reads in front of r.  No unit is empty, chunks end between units.
+//   sizing  k_read_flags marks the record-less reads (and checks the offsets); an exclusive scan gives e.  k_record_size: one
+//           lane per hit record finds its read in the CSR offsets (binary search), checks the record (samw_check: the lowest
+//           offender of either kind wins an atomicMin) and writes the bytes of its unit; k_empty_size: one lane per read writes
+//           the bytes of its record-less unit.  An exclusive scan (primitives.h) gives every unit its 64-bit byte start.
+//           textchunks.h: the longest unit and the greedy chunk ends.
+//   format  k_format: one block per 4 KB tile of the output.  The units that overlap the tile are found by binary search of the
+//           unit starts (a unit may span many tiles: SEQ is of any length).  One lane per line writes the numeric parts, the
+//           default QNAME and every name or SEQ of at most kShortCopy bytes into an LDS image of the tile, clipped to the tile;
+//           longer names and SEQs are queued as copy jobs, clipped to the tile, and copied a byte per lane and step, the block's
+//           wavefronts taking the jobs in turn.  Then every lane stores one aligned 16-byte group: global memory sees only
+//           full-width coalesced stores.  Name and SEQ bytes are copied, never inspected.
+// The chunks are planned and handed to the sink by textchunks.h, the loop of eqtext_write.hip and rowtext.h.
+#include "common.h"
+#include "decfmt.h"
+#include "primitives.h"
+#include "samwfmt.h"
+#include "textchunks.h"
+
+#include <cstring>
+
+namespace sfgpu {
+namespace {
+
+using textchunks::kBlock;
+using textchunks::kTileBytes;
+using textchunks::kTileShift;
+using textchunks::kDefaultChunk;
+using textchunks::kMaxChunk;
+using textchunks::grid_of;
+
+constexpr uint32_t kShortCopy = 48;                       // longer names and SEQs are copied by whole wavefronts
+// copy jobs are longer than kShortCopy and disjoint in the text: so many can touch one tile
+constexpr uint32_t kJobCap = kTileBytes / (kShortCopy + 1) + 3;
+constexpr unsigned long long kNoError = ~0ull;
+
+enum : unsigned long long { kBadOffsets = 1, kTooLong = 2, kNullBytes = 4 };
+// misc: [0] flags, [1] longest unit, [2] lowest (read << 32 | record) that breaks the position rule, [3] ... whose tid is no
+// reference, [4] lines
+constexpr int kMisc = 5;
+
+// offsets off[0 .. n] of `bytes`: kBadOffsets where they decrease (or are negative), kNullBytes where bytes are named but absent
+template <typename Off>
+__global__ void k_check_off(const void* __restrict__ bytes, const Off* __restrict__ off, uint64_t n, unsigned long long* __restrict__ misc) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Off a = off[i], b = off[i + 1];
+    if (a > b || a < (Off)0) atomicOr(&misc[0], kBadOffsets);
+    else if (b > a && !bytes) atomicOr(&misc[0], kNullBytes);
+}
+
+// empty[r] = 1 for a read without records; the CSR offsets start at 0 and never decrease
+__global__ void k_read_flags(const uint32_t* __restrict__ hit_off, uint32_t n_reads, uint32_t* __restrict__ empty,
+                             unsigned long long* __restrict__ misc) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t a = hit_off[r], b = hit_off[r + 1];
+    if (a > b || (r == 0 && a != 0)) atomicOr(&misc[0], kBadOffsets);
+    empty[r] = a == b;
+}
+
+__device__ inline void count_lines(uint32_t n, unsigned long long* __restrict__ misc) {
+    unsigned long long v = n;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & (kWave - 1)) == 0 && v) atomicAdd(&misc[4], v);
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before, uint32_t* __restrict__ unit_len,
+              uint32_t* __restrict__ unit_read, unsigned long long* __restrict__ misc) {
+    const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t lines = 0;
+    if (h < n_hits) {
+        uint64_t lo = 0, hi = a.n_reads;                  // hit_off[lo] <= h < hit_off[hi]: the last such lo is the read that holds h
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (a.hit_off[mid] <= h) lo = mid; else hi = mid;
+        }
+        const uint64_t r = lo, rank = h - a.hit_off[r], u = h + e_before[r];
+        const sfgpu_hit rec = a.hits[h];
+        uint64_t len = 0;
+        if (const int kind = samw_check(rec, a.n_refs)) atomicMin(&misc[kind == SAMW_BAD_POS ? 2 : 3], (unsigned long long)(r << 32 | rank));
+        else len = samw_unit_len(a, r, &rec, rank);
+        if (len > 0xffffffffull) { atomicOr(&misc[0], kTooLong); len = 0; }
+        unit_len[u] = (uint32_t)len;
+        unit_read[u] = (uint32_t)r;
+        lines = samw_record_lines(rec);
+    }
+    count_lines(lines, misc);
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_empty_size(SamwArgs a, const uint32_t* __restrict__ e_before, uint32_t* __restrict__ unit_len, uint32_t* __restrict__ unit_read,
+             unsigned long long* __restrict__ misc) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t lines = 0;
+    if (r < a.n_reads && a.hit_off[r] == a.hit_off[r + 1]) {
+        const uint64_t u = (uint64_t)a.hit_off[r] + e_before[r];
+        uint64_t len = samw_unit_len(a, r, nullptr, 0);
+        if (len > 0xffffffffull) { atomicOr(&misc[0], kTooLong); len = 0; }
+        unit_len[u] = (uint32_t)len;
+        unit_read[u] = (uint32_t)r;
+        lines = samw_empty_lines(a.paired != 0);
+    }
+    count_lines(lines, misc);
+}
+
+// the unit that holds byte x of the text (x < unit_start[n_units]); units are never empty, so the starts increase strictly
+__device__ inline uint64_t unit_of(const uint64_t* __restrict__ unit_start, uint64_t n_units, uint64_t x) {
+    uint64_t lo = 0, hi = n_units;                        // unit_start[lo] <= x < unit_start[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (unit_start[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+struct CopyJob {
+    const char* src;        // the first byte that lies in the tile
+    uint32_t at, n;         // tile offset and bytes
+};
+
+// one block per tile of the output; `out` is the chunk buffer, whose byte 0 is text byte out_base (a multiple of kTileBytes)
+__global__ void __launch_bounds__(kBlock)
+k_format(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
+         uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
+    __shared__ uint4 tile4[kBlock];
+    __shared__ CopyJob jobs[kJobCap];
+    __shared__ uint32_t n_jobs;
+    char* tile = reinterpret_cast<char*>(tile4);
+    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
+    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);      // (the bytes behind the end of the text)
+    if (threadIdx.x == 0) n_jobs = 0;
+    __syncthreads();
+    const uint64_t end = base + kTileBytes < n_bytes ? base + kTileBytes : n_bytes;      // base < n_bytes: the grid ends with the chunk
+    const uint64_t u_lo = unit_of(unit_start, n_units, base), u_hi = unit_of(unit_start, n_units, end - 1);
+    auto put_at = [&](int64_t p, char ch) {               // tile offset p, which may lie before or behind the tile
+        if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = ch;
+    };
+    // bytes src[0 .. n) to text offset s: by this lane when short, else queued for the wavefronts (the part inside the tile)
+    auto copy = [&](const char* src, uint64_t s, uint64_t n) {
+        if (n <= kShortCopy) {
+            const int64_t p0 = (int64_t)(s - base);
+            for (uint32_t i = 0; i < (uint32_t)n; ++i) put_at(p0 + i, src[i]);
+            return;
+        }
+        const uint64_t lo = s > base ? s : base, hi = s + n < end ? s + n : end;
+        if (lo >= hi) return;
+        const uint32_t k = atomicAdd(&n_jobs, 1u);
+        if (k < kJobCap) jobs[k] = CopyJob{src + (lo - s), (uint32_t)(lo - base), (uint32_t)(hi - lo)};
+    };
+    // two line slots per unit: a unit's second line is absent unless it is a pair record or a record-less paired read
+    for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
+        const uint64_t u = u_lo + (slot >> 1);
+        const uint32_t which = (uint32_t)(slot & 1);
+        const uint64_t r = unit_read[u];
+        const uint32_t h0 = a.hit_off[r];
+        const bool empty = h0 == a.hit_off[r + 1];
+        sfgpu_hit rec = {};
+        uint64_t rank = 0;
+        if (!empty) {
+            const uint64_t h = u - e_before[r];
+            rec = a.hits[h];
+            rank = h - h0;
+        }
+        if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
+        const uint32_t tid = empty ? 0u : rec.tid;
+        uint64_t s = unit_start[u];
+        if (which) s += samw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_record_line(rec, rank, 0), r, tid);
+        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_record_line(rec, rank, which);
+        if (s >= end || s + samw_line_len(a, l, r, tid) <= base) continue;
+        // QNAME
+        if (a.qname_off) {
+            const uint64_t o = a.qname_off[r], n = a.qname_off[r + 1] - o;
+            copy(a.qnames + o, s, n);
+            s += n;
+        } else {
+            const int64_t p0 = (int64_t)(s - base);
+            samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { put_at(p0 + i, ch); });
+            s += samw_default_qname_len(a.read_index_base + r);
+        }
+        {   // \t FLAG \t
+            const int64_t p0 = (int64_t)(s - base);
+            samw_put_head(l, [&](int i, char ch) { put_at(p0 + i, ch); });
+            s += samw_head_len(l);
+        }
+        // RNAME
+        if (l.mapped) {
+            const uint64_t o = a.ref_name_off[tid], n = a.ref_name_off[tid + 1] - o;
+            copy(a.ref_names + o, s, n);
+            s += n;
+        } else {
+            put_at((int64_t)(s - base), '*');
+            s += 1;
+        }
+        {   // \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
+            const int64_t p0 = (int64_t)(s - base);
+            samw_put_mid(l, [&](int i, char ch) { put_at(p0 + i, ch); });
+            s += samw_mid_len(l);
+        }
+        // SEQ
+        const uint8_t* seq;
+        uint64_t sl;
+        if (samw_seq(a, l, r, &seq, &sl)) copy(reinterpret_cast<const char*>(seq), s, sl);
+        else put_at((int64_t)(s - base), '*');
+        s += sl;
+        const int64_t p0 = (int64_t)(s - base);
+        put_at(p0, '\t'); put_at(p0 + 1, '*'); put_at(p0 + 2, '\n');
+    }
+    __syncthreads();
+    // the long names and SEQs: the wavefronts take the jobs in turn, a byte per lane and step
+    const uint32_t nj = n_jobs < kJobCap ? n_jobs : kJobCap;
+    const uint32_t wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
+    for (uint32_t k = wave; k < nj; k += kBlock / kWave) {
+        const CopyJob j = jobs[k];
+        for (uint32_t i = lane; i < j.n; i += kWave) tile[j.at + i] = j.src[i];
+    }
+    __syncthreads();
+    const uint64_t g = base + 16ull * threadIdx.x;
+    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+}
+
+struct Scratch {
+    DevBuf<uint32_t> empty, e_before, unit_len, unit_read;
+    DevBuf<uint64_t> unit_start;
+    DevBuf<unsigned long long> misc;
+};
+
+}  // namespace
+}  // namespace sfgpu
+
+using namespace sfgpu;
+
+extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                    void* user, sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    const char* who = "sfgpu_sam_write_text";
+    SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null result");
+    memset(out, 0, sizeof(*out));
+    if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
+    SF_REQUIRE(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk, SFGPU_ERR_INVALID,
+               "sfgpu_sam_write_text: chunk_bytes must lie in [16, 2^30] (0 = default)");
+    if (n_reads == 0) return SFGPU_OK;
+    SF_REQUIRE(d_hit_offsets, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null hit offsets");
+    SF_REQUIRE(d_ref_name_off || n_refs == 0, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null reference name offsets");
+    SF_REQUIRE(!d_qnames || d_qname_off, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: read names without their offsets");
+    SF_REQUIRE((!d_seq1 || d_seq1_off) && (!d_seq2 || d_seq2_off), SFGPU_ERR_INVALID, "sfgpu_sam_write_text: bases without their offsets");
+    SF_REQUIRE(n_reads < 0xffffffffu, SFGPU_ERR_RANGE, "sfgpu_sam_write_text: n_reads must be below 2^32 - 1");
+    SamwArgs a = {d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                  d_seq1, d_seq1_off, paired ? d_seq2 : nullptr, paired ? d_seq2_off : nullptr, read_index_base};
+
+    Scratch S;
+    CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
+    hipStream_t st = nullptr;
+    hipEvent_t ev_in = nullptr, ev_a[2] = {nullptr, nullptr}, ev_s[2] = {nullptr, nullptr};
+    unsigned long long* h_misc = nullptr;     // [0 .. kMisc) misc, [5] total bytes; uint32 view of [6]: n_hits, record-less reads
+    auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
+    SF_HIP(scope.acquire(&st));
+    SF_HIP(scope.event(&ev_in, hipEventDisableTiming));
+    for (auto& e : ev_a) SF_HIP(scope.event(&e));
+    for (auto& e : ev_s) SF_HIP(scope.event(&e));
+    SF_HIP(scope.pinned_block(&h_misc, 8 * sizeof(unsigned long long)));
+    // behind whatever the caller has queued on `stream`
+    SF_HIP(hipEventRecord(ev_in, as_stream(stream)));
+    SF_HIP(hipStreamWaitEvent(st, ev_in, 0));
+
+    // ---- the arrays' shape: offsets that never decrease, the record-less reads, the number of units
+    if (int rc = S.misc.reserve(kMisc, st, false)) return rc;
+    if (int rc = S.empty.reserve((uint64_t)n_reads + 1, st, false)) return rc;
+    if (int rc = S.e_before.reserve((uint64_t)n_reads + 1, st, false)) return rc;
+    SF_HIP(hipMemsetAsync(S.misc.p, 0, kMisc * sizeof(unsigned long long), st));
+    SF_HIP(hipMemsetAsync(S.misc.p + 2, 0xff, 2 * sizeof(unsigned long long), st));
+    SF_HIP(hipEventRecord(ev_a[0], st));
+    hipLaunchKernelGGL(k_read_flags, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, d_hit_offsets, n_reads, S.empty.p, S.misc.p);
+    SF_HIP(hipGetLastError());
+    if (n_refs) {
+        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(n_refs)), dim3(kBlock), 0, st, (const void*)d_ref_names, d_ref_name_off,
+                           (uint64_t)n_refs, S.misc.p);
+        SF_HIP(hipGetLastError());
+    }
+    if (d_qname_off) {
+        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, (const void*)d_qnames, d_qname_off,
+                           (uint64_t)n_reads, S.misc.p);
+        SF_HIP(hipGetLastError());
+    }
+    for (int m = 0; m < 2; ++m) {
+        const int64_t* off = m ? a.seq2_off : a.seq1_off;
+        if (!off) continue;
+        hipLaunchKernelGGL(k_check_off<int64_t>, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, (const void*)(m ? a.seq2 : a.seq1), off,
+                           (uint64_t)n_reads, S.misc.p);
+        SF_HIP(hipGetLastError());
+    }
+    if (int rc = exclusive_scan_u32_u32(S.empty.p, S.e_before.p, n_reads, st)) return rc;
+    SF_HIP(hipEventRecord(ev_a[1], st));
+    uint32_t* h_counts = reinterpret_cast<uint32_t*>(&h_misc[6]);
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_counts[0], d_hit_offsets + n_reads, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_counts[1], S.e_before.p + n_reads, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&out->format_ms, ev_a[0], ev_a[1]);
+    if (h_misc[0] & kBadOffsets) return fail(SFGPU_ERR_INVALID, "an offset array decreases, or the hit offsets do not start at 0");
+    if (h_misc[0] & kNullBytes) return fail(SFGPU_ERR_INVALID, "offsets name bytes of a null array");
+    const uint64_t n_hits = h_counts[0], n_units = n_hits + h_counts[1];
+    if (n_hits && !d_hits) return fail(SFGPU_ERR_INVALID, "null hits");
+
+    // ---- sizing and validation: unit lengths, unit starts, the longest unit, the lowest record that cannot be written
+    if (int rc = S.unit_len.reserve(n_units + 1, st, false)) return rc;
+    if (int rc = S.unit_read.reserve(n_units, st, false)) return rc;
+    if (int rc = S.unit_start.reserve(n_units + 1, st, false)) return rc;
+    SF_HIP(hipEventRecord(ev_s[0], st));
+    if (n_hits) {
+        hipLaunchKernelGGL(k_record_size, dim3(grid_of(n_hits)), dim3(kBlock), 0, st, a, n_hits, S.e_before.p, S.unit_len.p, S.unit_read.p,
+                           S.misc.p);
+        SF_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_empty_size, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, a, S.e_before.p, S.unit_len.p, S.unit_read.p, S.misc.p);
+    SF_HIP(hipGetLastError());
+    if (int rc = exclusive_scan_u32(S.unit_len.p, S.unit_start.p, n_units, st, false)) return rc;
+    if (int rc = textchunks::line_max(S.unit_start.p, n_units, S.misc.p + 1, st)) return rc;
+    SF_HIP(hipEventRecord(ev_s[1], st));
+    SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, kMisc * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_misc[5], S.unit_start.p + n_units, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    add_elapsed(&out->format_ms, ev_s[0], ev_s[1]);
+    if (h_misc[2] != kNoError || h_misc[3] != kNoError) {
+        const bool by_pos = h_misc[2] <= h_misc[3];       // (one record breaking both rules reports the position, as samw_check does)
+        const unsigned long long key = by_pos ? h_misc[2] : h_misc[3];
+        out->error_read = key >> 32; out->error_record = key & 0xffffffffull; out->error_kind = by_pos ? SAMW_BAD_POS : SAMW_BAD_TID;
+        set_error("%s: read %llu, record %llu: %s", who, (unsigned long long)out->error_read, (unsigned long long)out->error_record,
+                  by_pos ? "the read has no base on the transcript: SAM cannot say that" : "the transcript id is not below n_refs");
+        return SFGPU_ERR_INVALID;
+    }
+    if (h_misc[0] & kTooLong) return fail(SFGPU_ERR_RANGE, "a unit is longer than 2^32 - 1 bytes");
+    const uint64_t total = h_misc[5];
+    out->n_bytes = total; out->n_lines = h_misc[4]; out->max_unit_bytes = h_misc[1];
+    if (!sink) return SFGPU_OK;
+    if (out->max_unit_bytes > chunk_bytes) return fail(SFGPU_ERR_RANGE, "a unit (a line, or the two lines of a pair) is longer than chunk_bytes");
+
+    // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this text's tiles
+    textchunks::Stats ts;
+    const int rc = textchunks::deliver(who, S.unit_start.p, n_units, total, chunk_bytes, sink, user, st, &ts,
+                                       [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
+        hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
+                           S.unit_start.p, n_units, total, first_tile, out_base, buf);
+        SF_HIP(hipGetLastError());
+        return SFGPU_OK;
+    });
+    out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
+    return rc;
+}

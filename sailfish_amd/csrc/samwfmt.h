@@ -1,0 +1,267 @@
+// samwfmt.h -- the SAM lines this library writes for its hit records, stated once: the alignment lines of samfile._sam_text (the
+// text samfile.write_sam writes), byte for byte, for `paired` given explicitly.  Plain C++, host and device, serial:
+// samtext_write.hip runs the same functions inside its kernels (WHERE a line lies in the output and which lines a tile holds is
+// found in parallel there; WHAT a line says is decided here), and tests/samwrite_harness.cpp runs them alone (samw_serial below).
+//
+// A line is   QNAME \t FLAG \t RNAME \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t SEQ \t * \n
+// and a UNIT is what one hit record or one read without records produces; units follow each other in read order, a read's
+// records in their order.
+//   pair record (mate_status 3): two lines.  FLAG 0x1|0x2|0x40|sec|(fwd ? 0 : 0x10)|(mate_fwd ? 0 : 0x20), then the mirrored 0x80
+//          line (0x10 from mate_fwd, 0x20 from fwd); RNEXT '='; PNEXT the other line's POS; TLEN +frag_len on the first line iff
+//          pos <= mate_pos, negated on the second; SEQ of mate 1, then of mate 2.
+//   orphan (any other nonzero mate_status): one line.  FLAG 0x1|0x8|0x40 (status 1, SEQ of mate 1) or 0x1|0x8|0x80 (SEQ of
+//          mate 2), |sec|(fwd ? 0 : 0x10); RNEXT '*', PNEXT 0, TLEN 0.
+//   single-end record (mate_status 0): one line.  FLAG sec|(fwd ? 0 : 0x10); RNEXT '*', PNEXT 0, TLEN 0; SEQ of mate 1.
+//   sec = 0x100 from the read's second record on.
+//   read without a record: paired, the lines 77 and 141 (SEQ of mate 1, of mate 2); single end, one line 4.  RNAME '*', POS 0,
+//          CIGAR '*', RNEXT '*', PNEXT 0, TLEN 0.
+//   POS and CIGAR of a read of len bases at pos: pos >= 0 gives pos + 1 and <len>M; pos < 0 gives 1 and <-pos>S<len + pos>M, and
+//          -pos >= len is an error (no base lies on the transcript: SAM cannot say that), as is tid >= n_refs.
+//   MAPQ is 255, QUAL '*'.  QNAME is the caller's bytes, or r<global read index> when none are given; SEQ is the caller's bytes, or
+//   '*' when none are given; RNAME is the transcript's name.  These bytes are copied, never inspected.
+// The SEQ of a 0x10 line is written as given, NOT reverse-complemented: that is the contract of _sam_text as it stands, and the
+// reader (samfmt.h) takes only SEQ's length.
+#pragma once
+#include <cstdint>
+
+#include "../../include/sfgpu.h"
+#include "decfmt.h"
+
+#if defined(__HIPCC__)
+#define SAMW_HD __host__ __device__ __forceinline__
+#else
+#define SAMW_HD inline
+#endif
+
+namespace sfgpu {
+
+constexpr uint32_t kSamwTail = 3;                 // \t * \n behind SEQ
+// (the head \t FLAG \t is at most 5 bytes: the largest FLAG is 0x1b3 = 435; the middle \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
+// at most 54: 65535S65535M, -4294967295)
+enum { SAMW_OK = 0, SAMW_BAD_POS = 1, SAMW_BAD_TID = 2 };
+
+// what one line says, names and SEQ apart
+struct SamwLine {
+    int64_t tlen;
+    uint32_t flag, pos, pnext;
+    uint32_t clip, match;        // CIGAR <clip>S<match>M (clip = 0: <match>M); unmapped: '*'
+    uint8_t mapped;              // RNAME is the name of the record's tid; else '*'
+    uint8_t rnext;               // '=' or '*'
+    uint8_t mate2;               // SEQ is mate 2's
+};
+
+SAMW_HD uint32_t samw_record_lines(const sfgpu_hit& h) { return h.mate_status == 3 ? 2u : 1u; }
+SAMW_HD uint32_t samw_empty_lines(bool paired) { return paired ? 2u : 1u; }
+
+// _aligned's rule for one mate
+SAMW_HD bool samw_pos_ok(int32_t pos, uint32_t len) { return pos >= 0 || -(int64_t)pos < (int64_t)len; }
+
+// 0, or the first rule the record breaks (the position rule before the transcript id, as _sam_text meets them)
+SAMW_HD int samw_check(const sfgpu_hit& h, uint32_t n_refs) {
+    if (!samw_pos_ok(h.pos, h.read_len)) return SAMW_BAD_POS;
+    if (h.mate_status == 3 && !samw_pos_ok(h.mate_pos, h.mate_len)) return SAMW_BAD_POS;
+    if (h.tid >= n_refs) return SAMW_BAD_TID;
+    return SAMW_OK;
+}
+
+SAMW_HD void samw_aligned(int32_t pos, uint32_t len, uint32_t* p, uint32_t* clip, uint32_t* match) {
+    if (pos >= 0) { *p = (uint32_t)pos + 1u; *clip = 0; *match = len; }
+    else { *p = 1; *clip = (uint32_t)(-(int64_t)pos); *match = (uint32_t)((int64_t)len + pos); }
+}
+
+// line `which` (0, or 1 for the second line of a pair record) of a checked record that is number `rank` among its read's
+SAMW_HD SamwLine samw_record_line(const sfgpu_hit& h, uint64_t rank, uint32_t which) {
+    SamwLine l;
+    const uint32_t sec = rank ? 0x100u : 0u, st = h.mate_status;
+    uint32_t p1, c1, m1;
+    samw_aligned(h.pos, h.read_len, &p1, &c1, &m1);
+    l.mapped = 1;
+    if (st == 3) {
+        uint32_t p2, c2, m2;
+        samw_aligned(h.mate_pos, h.mate_len, &p2, &c2, &m2);
+        const int64_t tlen = h.pos <= h.mate_pos ? (int64_t)h.frag_len : -(int64_t)h.frag_len;
+        const uint32_t r1 = h.fwd ? 0u : 1u, r2 = h.mate_fwd ? 0u : 1u;
+        l.rnext = '=';
+        if (which == 0) {
+            l.flag = 0x1u | 0x2u | 0x40u | sec | (r1 ? 0x10u : 0u) | (r2 ? 0x20u : 0u);
+            l.pos = p1; l.clip = c1; l.match = m1; l.pnext = p2; l.tlen = tlen; l.mate2 = 0;
+        } else {
+            l.flag = 0x1u | 0x2u | 0x80u | sec | (r2 ? 0x10u : 0u) | (r1 ? 0x20u : 0u);
+            l.pos = p2; l.clip = c2; l.match = m2; l.pnext = p1; l.tlen = -tlen; l.mate2 = 1;
+        }
+        return l;
+    }
+    l.pos = p1; l.clip = c1; l.match = m1; l.rnext = '*'; l.pnext = 0; l.tlen = 0;
+    l.flag = sec | (h.fwd ? 0u : 0x10u);
+    l.mate2 = 0;
+    if (st) {
+        l.flag |= 0x1u | 0x8u | (st == 1 ? 0x40u : 0x80u);
+        l.mate2 = st != 1;
+    }
+    return l;
+}
+
+// line `which` of a read without records
+SAMW_HD SamwLine samw_empty_line(bool paired, uint32_t which) {
+    SamwLine l;
+    l.flag = paired ? (which ? 141u : 77u) : 4u;
+    l.pos = 0; l.clip = 0; l.match = 0; l.pnext = 0; l.tlen = 0;
+    l.mapped = 0; l.rnext = '*'; l.mate2 = (uint8_t)(paired && which);
+    return l;
+}
+
+// QNAME when the caller gives none: r<index>
+SAMW_HD uint32_t samw_default_qname_len(uint64_t index) { return 1u + (uint32_t)dec_len_u64(index); }
+template <typename Put>
+SAMW_HD void samw_put_default_qname(uint64_t index, Put put) {          // put(i, ch): byte i of the name
+    const int nd = dec_len_u64(index);
+    put(0, 'r');
+    dec_put_u64(index, [&](int i, char ch) { put(nd - i, ch); });
+}
+
+// the head: \t FLAG \t, between QNAME and RNAME
+SAMW_HD uint32_t samw_head_len(const SamwLine& l) { return 2u + (uint32_t)dec_len_u32(l.flag); }
+template <typename Put>
+SAMW_HD void samw_put_head(const SamwLine& l, Put put) {
+    const int nd = dec_len_u32(l.flag);
+    put(0, '\t');
+    dec_put_fixed_u32(l.flag, nd, 0, [&](int i, char ch) { put(nd - i, ch); });
+    put(nd + 1, '\t');
+}
+
+SAMW_HD uint32_t samw_cigar_len(const SamwLine& l) {
+    if (!l.mapped) return 1;
+    return (l.clip ? (uint32_t)dec_len_u32(l.clip) + 1u : 0u) + (uint32_t)dec_len_u32(l.match) + 1u;
+}
+
+// the middle: \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t, between RNAME and SEQ
+SAMW_HD uint32_t samw_mid_len(const SamwLine& l) {
+    const uint32_t t = (uint32_t)(l.tlen < 0 ? -l.tlen : l.tlen);        // |TLEN| is a frag_len: it fits 32 bits
+    return 1u + (uint32_t)dec_len_u32(l.pos) + 5u + samw_cigar_len(l) + 3u + (uint32_t)dec_len_u32(l.pnext) + 1u + (l.tlen < 0 ? 1u : 0u) +
+           (uint32_t)dec_len_u32(t) + 1u;
+}
+template <typename Put>
+SAMW_HD void samw_put_mid(const SamwLine& l, Put put) {
+    int p = 0;
+    auto num = [&](uint32_t v) {                  // the digits of v at p .. p + nd - 1
+        const int nd = dec_len_u32(v), last = p + nd - 1;
+        dec_put_fixed_u32(v, nd, 0, [&](int i, char ch) { put(last - i, ch); });
+        p += nd;
+    };
+    put(p++, '\t'); num(l.pos);
+    put(p++, '\t'); put(p++, '2'); put(p++, '5'); put(p++, '5'); put(p++, '\t');
+    if (!l.mapped) put(p++, '*');
+    else {
+        if (l.clip) { num(l.clip); put(p++, 'S'); }
+        num(l.match); put(p++, 'M');
+    }
+    put(p++, '\t'); put(p++, (char)l.rnext); put(p++, '\t'); num(l.pnext); put(p++, '\t');
+    if (l.tlen < 0) put(p++, '-');
+    num((uint32_t)(l.tlen < 0 ? -l.tlen : l.tlen));
+    put(p++, '\t');
+}
+
+// ---- the arrays of one write call, and the serial statement over them ---------------------------------------------------------
+// What sfgpu_sam_write_text takes (include/sfgpu.h): names and SEQ as bytes back to back with n + 1 offsets; qname_off == nullptr
+// stands for r<read_index_base + r>, seq1_off / seq2_off == nullptr for '*'.
+struct SamwArgs {
+    const sfgpu_hit* hits;
+    const uint32_t* hit_off;
+    uint32_t n_reads;
+    int paired;
+    const char* ref_names;
+    const uint64_t* ref_name_off;
+    uint32_t n_refs;
+    const char* qnames;
+    const uint64_t* qname_off;
+    const uint8_t* seq1;
+    const int64_t* seq1_off;
+    const uint8_t* seq2;
+    const int64_t* seq2_off;
+    uint64_t read_index_base;
+};
+
+SAMW_HD uint64_t samw_qname_len(const SamwArgs& a, uint64_t r) {
+    return a.qname_off ? a.qname_off[r + 1] - a.qname_off[r] : (uint64_t)samw_default_qname_len(a.read_index_base + r);
+}
+SAMW_HD uint64_t samw_rname_len(const SamwArgs& a, const SamwLine& l, uint32_t tid) {
+    return l.mapped ? a.ref_name_off[tid + 1] - a.ref_name_off[tid] : 1u;
+}
+// SEQ of the line of read r: false and 1 byte for '*', else the bases (a null pointer only with *len == 0)
+SAMW_HD bool samw_seq(const SamwArgs& a, const SamwLine& l, uint64_t r, const uint8_t** seq, uint64_t* len) {
+    const uint8_t* s = l.mate2 ? a.seq2 : a.seq1;
+    const int64_t* o = l.mate2 ? a.seq2_off : a.seq1_off;
+    *seq = nullptr; *len = 1;
+    if (!o) return false;
+    *len = (uint64_t)(o[r + 1] - o[r]);
+    if (*len) *seq = s + o[r];
+    return true;
+}
+SAMW_HD uint64_t samw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t tid) {
+    const uint8_t* seq;
+    uint64_t sl;
+    (void)samw_seq(a, l, r, &seq, &sl);
+    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + kSamwTail;
+}
+// the bytes of unit (read r, record h of rank `rank`; h == nullptr: the read has no record)
+SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+    const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
+    uint64_t len = 0;
+    for (uint32_t w = 0; w < n; ++w) len += samw_line_len(a, h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
+    return len;
+}
+
+#if !defined(__HIPCC__)
+// The whole text, serially (host only; the judge of the kernels is still _sam_text).  Pass 1 sizes and checks: returns 0 and the
+// sizes, or the kind of the lowest (read, record) that breaks a rule.  Pass 2 (out != nullptr, room for *n_bytes) writes.
+struct SamwSerial {
+    uint64_t n_bytes = 0, n_lines = 0, n_units = 0, max_unit_bytes = 0, error_read = 0, error_record = 0;
+    int error_kind = 0;
+};
+
+inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
+    *res = SamwSerial();
+    for (uint64_t r = 0; r < a.n_reads; ++r)
+        for (uint64_t h = a.hit_off[r]; h < a.hit_off[r + 1]; ++h)
+            if (int kind = samw_check(a.hits[h], a.n_refs)) {
+                res->error_read = r; res->error_record = h - a.hit_off[r]; res->error_kind = kind;
+                return kind;
+            }
+    uint64_t at = 0;
+    auto line = [&](const SamwLine& l, uint64_t r, uint32_t tid) {
+        const uint64_t len = samw_line_len(a, l, r, tid);
+        if (out) {
+            char* p = out + at;
+            if (a.qname_off) for (uint64_t i = a.qname_off[r]; i < a.qname_off[r + 1]; ++i) *p++ = a.qnames[i];
+            else { samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { p[i] = ch; }); p += samw_default_qname_len(a.read_index_base + r); }
+            samw_put_head(l, [&](int i, char ch) { p[i] = ch; }); p += samw_head_len(l);
+            if (l.mapped) for (uint64_t i = a.ref_name_off[tid]; i < a.ref_name_off[tid + 1]; ++i) *p++ = a.ref_names[i];
+            else *p++ = '*';
+            samw_put_mid(l, [&](int i, char ch) { p[i] = ch; }); p += samw_mid_len(l);
+            const uint8_t* s;
+            uint64_t sl;
+            if (samw_seq(a, l, r, &s, &sl)) for (uint64_t i = 0; i < sl; ++i) *p++ = (char)s[i];
+            else *p++ = '*';
+            *p++ = '\t'; *p++ = '*'; *p++ = '\n';
+        }
+        at += len;
+        res->n_lines++;
+    };
+    auto unit = [&](uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+        const uint64_t before = at;
+        const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
+        for (uint32_t w = 0; w < n; ++w) line(h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
+        res->n_units++;
+        if (at - before > res->max_unit_bytes) res->max_unit_bytes = at - before;
+    };
+    for (uint64_t r = 0; r < a.n_reads; ++r) {
+        const uint64_t h0 = a.hit_off[r], h1 = a.hit_off[r + 1];
+        if (h0 == h1) unit(r, nullptr, 0);
+        for (uint64_t u = h0; u < h1; ++u) unit(r, a.hits + u, u - h0);
+    }
+    res->n_bytes = at;
+    return 0;
+}
+#endif
+
+}  // namespace sfgpu

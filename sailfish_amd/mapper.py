@@ -108,23 +108,45 @@ def hits_to_numpy(hits, offsets):
     return hits.cpu().numpy().view(HIT_DTYPE), offsets.cpu().numpy().view(np.uint32)
 
 
-def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda", **kw):
+def _mappings_writer(write_mappings, names, idx, paired):
+    """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
+    if write_mappings is None:
+        return None
+    from .samfile import SamDeviceWriter
+    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired)
+
+
+def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
+                   write_mappings=None, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
-    and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  -> (rc, experiment)"""
+    and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
+    binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
+    is quantified: QNAME r<index of the read>, SEQ the read's bases; the estimates do not depend on it.  -> (rc, experiment)"""
     from . import quant
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
+    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None)
 
     def batches():
         for a in range(0, n, batch_reads):
             b = min(n, a + batch_reads)
-            h, o = idx.map_reads(reads1[a:b], None if reads2 is None else reads2[a:b])
+            r1, r2 = reads1[a:b], None if reads2 is None else reads2[a:b]
+            if sam is not None:                              # the bases are wanted on the device beyond the mapper's call
+                r1 = tuple(t.to(idx.device) for t in pack_sequences(r1))
+                r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
+            h, o = idx.map_reads(r1, r2)
+            if sam is not None:
+                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2))
             yield h, o
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
         s, o = pack_sequences([x + "$" if isinstance(x, str) else bytes(x) + b"$" for x in sequences])
         seq_kw = dict(seq=bytes(s.numpy().tobytes()), seq_off=o[:-1].numpy())
-    rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+    try:
+        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+    finally:
+        if sam is not None:
+            sam.close()
     idx.close()
     return rc, exp
 
@@ -139,18 +161,20 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", **kw):
+                   inflate="auto", write_mappings=None, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
-    -> (rc, experiment)"""
+    write_mappings as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names are
+    sliced and packed on the host: ReadFile(names=True)).  -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, read_transcripts
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
+    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None)
 
     def batches():
-        f1 = ReadFile(reads1_path, device, inflate=inflate)
+        f1 = ReadFile(reads1_path, device, names=sam is not None, inflate=inflate)
         f2 = None if reads2_path is None else ReadFile(reads2_path, device, inflate=inflate)
         try:
             while True:
@@ -161,7 +185,10 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                     raise ValueError(f"{reads1_path} and {reads2_path} do not hold the same number of records")
                 if n == 0:
                     break
-                yield idx.map_reads(r1, r2)
+                h, o = idx.map_reads(r1, r2)
+                if sam is not None:
+                    sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2))
+                yield h, o
         finally:
             f1.close()
             if f2 is not None:
@@ -173,5 +200,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     try:
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     finally:
+        if sam is not None:
+            sam.close()
         idx.close()
     return rc, exp

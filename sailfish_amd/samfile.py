@@ -7,7 +7,8 @@ BGZF and -- with inflate="device" -- ordinary gzip inflated on the device and pa
 The header is: `read_header` reads the @SQ lines with Python, they are a thousandth of a real file.
 
 The file must be grouped by read name, as mappers write it (all lines of a fragment follow each other); a position-sorted file
-is not.  `write_sam` is the way back: hit records as SAM text, for the device mapper's output and for tests.
+is not.  `write_sam` is the way back: hit records as SAM text, the host statement (`_sam_text`); `SamDeviceWriter` writes the same
+file from the device mapper's batches where they lie (sfgpu_sam_write_text, csrc/samtext_write.hip, rules in csrc/samwfmt.h).
 
 BAM (what `samtools view -b` makes of the same alignments) is read too: a BGZF file whose first member inflates to "BAM\1".  What
 its record stream says is csrc/bamfmt.h, `read_bam_host` is the contract, the device side is csrc/bamtext.hip behind
@@ -509,6 +510,129 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf)."""
     from . import gzfile
     gzfile.write_bgzf(path, sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs)), member_bytes=member_bytes)
+
+
+# ---- the way back, on the device ------------------------------------------------------------------------------------------
+
+WRITE_KINDS = {1: "the read has no base on the transcript: SAM cannot say that", 2: "the transcript index is not below the number of names"}
+
+
+def sam_header(names, ref_len):
+    """the @HD and @SQ lines _sam_text begins with"""
+    return b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(_name_bytes(names), ref_len))
+
+
+class SamDeviceWriter:
+    """The SAM file write_sam writes, formatted on the device from the mapper's batches where they lie (sfgpu_sam_write_text,
+    csrc/samtext_write.hip; what a line says is csrc/samwfmt.h, and `_sam_text` is the statement it is judged by).
+
+    `path_or_file`: a path, or a binary file object (left open by close()).  `names`, `ref_len`: the transcripts in index order;
+    the constructor writes the @HD / @SQ lines from the host.  `paired`: the library (decides what a read without records gives).
+    `write(hits, offsets)` takes one batch as QuasiIndex.map_reads and SamFile return it (uint8 device tensor of HIT_DTYPE records,
+    int32 device tensor [reads + 1]) and appends its lines, in whole-unit chunks of chunk_bytes (0: the library's 32 MiB).
+      read_names  a (uint8 bytes, 64-bit offsets [reads + 1]) pair of device tensors, or a list of names (packed with
+                  quantfile.names_blob and uploaded); default r<index>, the index counted over all batches written so far.
+      seqs        the (bases, int64 offsets) device pair of readfile.ReadFile.read / mapper.pack_sequences, or (paired) a pair of such
+                  pairs; default '*'.  Bases are written as given, also on 0x10 lines.
+    A record SAM cannot express (WRITE_KINDS) raises ValueError naming the lowest such read -- counted over all batches, as
+    write_sam counts it -- and record; nothing of that batch is written.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times."""
+
+    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0):
+        from . import _lib, quantfile
+        self._L = _lib.lib()
+        self.paired, self.chunk_bytes = bool(paired), int(chunk_bytes)
+        self._names = quantfile.names_blob(_name_bytes(names))
+        self._n_refs = len(self._names[1]) - 1
+        self._d_names = None                               # uploaded to the device of the first batch
+        self._own = not hasattr(path_or_file, "write")
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        self.n_reads = 0                                   # the running read index
+        self.stats = dict(reads=0, hits=0, lines=0, bytes=0, chunks=0, batches=0, ms_format=0.0, ms_copy=0.0, ms_sink=0.0)
+        head = sam_header(names, ref_len)
+        self._f.write(head)
+        self.stats["header_bytes"] = len(head)
+
+    @staticmethod
+    def _blob(pair, dev):
+        """(bytes, 64-bit offsets), host (bytes / numpy) or device tensors -> contiguous (uint8, int64) tensors on dev"""
+        import torch
+        b, o = pair
+        if not isinstance(b, torch.Tensor):
+            b = torch.from_numpy(np.frombuffer(bytes(b), np.uint8).copy())
+        if not isinstance(o, torch.Tensor):
+            o = torch.from_numpy(np.ascontiguousarray(o).view(np.int64).copy())
+        if b.element_size() != 1 or o.is_floating_point() or o.element_size() != 8:
+            raise TypeError("expected (bytes, 64-bit integer offsets)")
+        return b.to(dev).contiguous(), o.to(dev).contiguous()
+
+    def write(self, hits, offsets, *, read_names=None, seqs=None):
+        import torch
+
+        from . import _lib, quantfile
+        if self._f is None:
+            raise ValueError("the SAM writer is closed")
+        dev = hits.device
+        d_hits, d_off = hits.contiguous(), offsets.contiguous()
+        n = int(d_off.numel()) - 1
+        if self._d_names is None or self._d_names[0].device != dev:
+            b, o = self._names
+            self._d_names = self._blob((b, o), dev)
+        q = (None, None)
+        if read_names is not None:
+            pair = read_names if isinstance(read_names, tuple) else quantfile.names_blob(_name_bytes(read_names))
+            q = self._blob(pair, dev)
+            if q[1].numel() != n + 1:
+                raise ValueError(f"{q[1].numel() - 1} read names for {n} reads")
+        s = [(None, None), (None, None)]
+        if seqs is not None:
+            mates = seqs if isinstance(seqs[0], (tuple, list)) else (seqs,)
+            if len(mates) != (2 if self.paired else 1):
+                raise ValueError("seqs: one (bases, offsets) pair for a single-end library, a pair of them for a paired one")
+            for m, pair in enumerate(mates):
+                s[m] = self._blob(pair, dev)
+                if s[m][1].numel() != n + 1:
+                    raise ValueError(f"bases of {s[m][1].numel() - 1} reads for {n} reads")
+        raised = []
+
+        def sink(addr, nb, _user):
+            try:                                   # nothing may unwind through the C frame
+                self._f.write(memoryview((C.c_char * nb).from_address(addr)))
+                return 0
+            except BaseException as e:             # noqa: BLE001  (re-raised below)
+                raised.append(e)
+                return 1
+
+        res = _lib.SamWriteResult()
+        p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
+        with torch.cuda.device(dev):
+            rc = self._L.sfgpu_sam_write_text(p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]),
+                                              self._n_refs, p(q[0]), p(q[1]), p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads,
+                                              self.chunk_bytes, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
+        if raised:
+            raise raised[0]
+        if rc == _lib.ERR_INVALID and res.error_kind:
+            raise ValueError(f"read {self.n_reads + int(res.error_read)}, record {int(res.error_record)}: {WRITE_KINDS[int(res.error_kind)]}")
+        _lib.check(rc)
+        self.n_reads += n
+        st = self.stats
+        for k, v in (("reads", n), ("hits", d_hits.numel() // 24), ("lines", res.n_lines), ("bytes", res.n_bytes), ("chunks", res.n_chunks), ("batches", 1)):
+            st[k] += int(v)
+        st["ms_format"] += res.format_ms; st["ms_copy"] += res.d2h_ms; st["ms_sink"] += res.sink_ms
+        return res.as_dict()
+
+    def close(self):
+        if self._f is not None:
+            if self._own:
+                self._f.close()
+            else:
+                self._f.flush()
+            self._f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- the device reader ----------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ enum {
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
     SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*) */
-    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_gz_*) */
+    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_gz_*, sfgpu_bgzw_*) */
     SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*) */
 };
 
@@ -660,6 +660,62 @@ typedef struct {
 SFGPU_API int sfgpu_gz_open(sfgpu_gz** out, sfgpu_text_sink sink, void* user, uint64_t chunk_bytes);
 SFGPU_API int sfgpu_gz_write_device(sfgpu_gz* z, const void* d_src, uint64_t n_bytes, sfgpu_stream stream);
 SFGPU_API int sfgpu_gz_close(sfgpu_gz* z, sfgpu_gz_result* res);
+/* Blocked gzip (BGZF, the container of BAM and of bgzip'ed text: what samtools, IGV and htslib read) from device memory.  The
+ * file is "BGZF members whose payloads are the bytes written, in order, and the 28-byte EOF member"; any gzip reader inflates it,
+ * and sfgpu_bgzf_inflate_host reads it back on the device.  What a member says is stated once, serially, in csrc/bgzwfmt.h; the
+ * kernels are csrc/bgzf_write.hip.  Unlike sfgpu_gz_* the DEFLATE blocks carry real (length, distance) matches: alignment files
+ * repeat names, bases and columns a few hundred bytes apart, which the run matches of sfgpu_gz_* cannot say.
+ *   open   emits nothing.  chunk_bytes: the largest piece handed to the sink (0 = 32 MiB; otherwise 16 .. 2^30, else
+ *          SFGPU_ERR_INVALID); pieces end anywhere, also inside a member.
+ *   write  n_bytes at d_src (any alignment; n_bytes == 0 is legal and emits nothing) are cut into members of 32 768 payload
+ *          bytes, the write's last member short.  A member is the 18-byte BGZF header with BSIZE, ONE final DEFLATE block, CRC-32
+ *          and ISIZE, all written by the kernel.  The block is dynamic-Huffman over literals and matches of length 3 .. 258 at
+ *          distance 1 .. 32 768 within the member (the parse: a 4-byte hash per position against the greatest earlier position of
+ *          the same bucket in 256-position steps, distance 1 and the previous distance as second candidates, greedy, restarted at
+ *          every 64-byte slice), or one stored block where that is not shorter: a member never exceeds its payload by more than
+ *          31 bytes.  The output is a function of the bytes and of the way they are split into writes, nothing else.  Staging,
+ *          overlap, the sink's rights and SFGPU_ERR_IO / SFGPU_ERR_STATE are those of sfgpu_gz_write_device.
+ *   close  emits the EOF member, fills *res (may be NULL) and frees the handle, whatever it returns.  open + close gives the
+ *          28-byte empty BGZF file.
+ * A handle belongs to one thread at a time and to the device that was current at open.  Device scratch: ~200 MB for writes of
+ * 64 MiB and more. */
+typedef struct sfgpu_bgzw sfgpu_bgzw;
+typedef struct {
+    uint64_t n_bytes_in;        /* payload bytes written */
+    uint64_t n_bytes_out;       /* bytes accepted by the sink, the EOF member included */
+    uint64_t n_members;         /* members coded, the EOF member not counted */
+    uint64_t n_stored_members;  /* of those, laid out as a stored block */
+    uint64_t n_matches;         /* tokens of the coded members, summed by the kernel */
+    uint64_t n_literals;
+    uint64_t n_chunks;          /* sink calls made */
+    double encode_ms;           /* device events: encode, scan and compaction kernels of all batches */
+    double d2h_ms;              /* device events around the staged copies */
+    double sink_ms;             /* host clock inside the sink */
+} sfgpu_bgzw_result;
+SFGPU_API int sfgpu_bgzw_open(sfgpu_bgzw** out, sfgpu_text_sink sink, void* user, uint64_t chunk_bytes);
+SFGPU_API int sfgpu_bgzw_write_device(sfgpu_bgzw* z, const void* d_src, uint64_t n_bytes, sfgpu_stream stream);
+SFGPU_API int sfgpu_bgzw_close(sfgpu_bgzw* z, sfgpu_bgzw_result* res);
+/* sfgpu_sam_write_text into a BGZF file: the same batch, the same checks and the same bytes, but the chunks never visit the host
+ * uncompressed -- every chunk of at most chunk_bytes (0 = 32 MiB) is formatted into a device buffer and handed to `z`
+ * (sfgpu_bgzw_write_device) where it lies, chunk c + 1 formatted while chunk c is encoded, copied and sunk.  `z` copies and sinks
+ * what it writes; its result (sfgpu_bgzw_close) holds the compressed bytes, the encode, copy and sink times.  format:
+ * SFGPU_SAMW_TEXT, the alignment lines of sfgpu_sam_write_text (a "sam.gz" file when the caller has written the @HD / @SQ lines
+ * through the same handle).  In `out`, n_bytes counts the uncompressed bytes, n_chunks the chunks handed to `z`; d2h_ms and sink_ms
+ * stay 0.  A batch that cannot be written fails before anything reaches `z` (error_kind etc. as in sfgpu_sam_write_text); a failure
+ * of `z` (SFGPU_ERR_IO: its sink refused) ends the call and leaves `z` broken.  n_reads == 0 writes nothing.
+ * SFGPU_SAMW_BAM writes the same lines as BAM records (a BAM file when the caller has written the magic, the header text and the
+ * reference list through the same handle): what samfile.sam_to_bam makes of the text, stated in csrc/bamwfmt.h -- mapq 255, the
+ * specification's bin, CIGAR words S and M, SEQ 4-bit packed through =ACMGRSVTWYHKDBN after upper-casing (anything else 15), QUAL
+ * 0xff, no SEQ given: l_seq 0.  A unit is then the one or two records of a hit record or record-less read, n_lines counts records,
+ * and three more rules fail a batch, after kinds 1 and 2 where one record breaks several (a record-less read counts as record 0):
+ * error_kind 3 a read name not of 1 .. 254 bytes; 4 bases given whose number differs from the record's read length, or more than
+ * 65 535 of them; 5 an alignment that ends beyond 2^29. */
+enum { SFGPU_SAMW_TEXT = 0, SFGPU_SAMW_BAM = 1 };
+SFGPU_API int sfgpu_sam_write_bgzf(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                   const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                   const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                   const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                   sfgpu_samwrite_result* out, sfgpu_stream stream);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

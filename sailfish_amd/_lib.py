@@ -150,6 +150,15 @@ class GzResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BgzwResult(C.Structure):
+    _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_members", C.c_uint64), ("n_stored_members", C.c_uint64),
+                ("n_matches", C.c_uint64), ("n_literals", C.c_uint64), ("n_chunks", C.c_uint64), ("encode_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _LOG_CB = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
 TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p)      # sfgpu_text_sink
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p)      # sfgpu_allreduce_fn
@@ -248,6 +257,11 @@ _SIGS = {
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
+    "sfgpu_bgzw_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
+    "sfgpu_bgzw_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
+    "sfgpu_bgzw_close": (C.c_int, [_P, C.POINTER(BgzwResult)]),
+    "sfgpu_sam_write_bgzf": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
+                                       C.POINTER(SamWriteResult), _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

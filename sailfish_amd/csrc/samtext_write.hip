@@ -17,10 +17,17 @@
 //           wavefronts taking the jobs in turn.  Then every lane stores one aligned 16-byte group: global memory sees only
 //           full-width coalesced stores.  Name and SEQ bytes are copied, never inspected.
 // The chunks are planned and handed to the sink by textchunks.h, the loop of eqtext_write.hip and rowtext.h.
+//
+// sfgpu_sam_write_bgzf hands the chunks to the BGZF encoder (bgzf_write.hip) on the device instead, and with SFGPU_SAMW_BAM the
+// lines are BAM records (WHAT a record says is bamwfmt.h): the same units, scan, tiles and chunks; the sizing kernels take the
+// record sizes and bamwfmt.h's three further checks (template argument BAM), and k_format_bam builds a tile of records -- the
+// fixed 36 bytes, NUL and CIGAR words by the line's lane, names copied, SEQ packed two bases a byte and QUAL filled with 0xff by
+// whole wavefronts where they are longer than kShortCopy bytes of output.
 #include "common.h"
 #include "decfmt.h"
 #include "primitives.h"
 #include "samwfmt.h"
+#include "bamwfmt.h"
 #include "textchunks.h"
 
 #include <cstring>
@@ -36,14 +43,18 @@ using textchunks::kMaxChunk;
 using textchunks::grid_of;
 
 constexpr uint32_t kShortCopy = 48;                       // longer names and SEQs are copied by whole wavefronts
-// copy jobs are longer than kShortCopy and disjoint in the text: so many can touch one tile
+// copy jobs are longer than kShortCopy and disjoint in the text: so many can touch one tile.  The same bound holds for the three
+// kinds of runs of a BAM record (name, packed SEQ, QUAL): a run is queued only when it is longer than kShortCopy bytes OF OUTPUT,
+// and the runs of all records are disjoint ranges of the output, so at most kTileBytes / (kShortCopy + 1) lie whole in a tile
+// and two more are cut by its ends.  The `k < kJobCap` tests below can therefore not drop a job.
 constexpr uint32_t kJobCap = kTileBytes / (kShortCopy + 1) + 3;
 constexpr unsigned long long kNoError = ~0ull;
 
 enum : unsigned long long { kBadOffsets = 1, kTooLong = 2, kNullBytes = 4 };
 // misc: [0] flags, [1] longest unit, [2] lowest (read << 32 | record) that breaks the position rule, [3] ... whose tid is no
-// reference, [4] lines
-constexpr int kMisc = 5;
+// reference, [4] lines, [5 .. 7] the lowest (read << 32 | record) that breaks bamwfmt.h's rules 3 .. 5 (BAM records only)
+constexpr int kMisc = 8;
+__device__ inline int misc_of_kind(int kind) { return kind <= SAMW_BAD_TID ? 1 + kind : 2 + kind; }
 
 // offsets off[0 .. n] of `bytes`: kBadOffsets where they decrease (or are negative), kNullBytes where bytes are named but absent
 template <typename Off>
@@ -72,6 +83,8 @@ __device__ inline void count_lines(uint32_t n, unsigned long long* __restrict__ 
     if ((threadIdx.x & (kWave - 1)) == 0 && v) atomicAdd(&misc[4], v);
 }
 
+// BAM: the units are bamwfmt.h's records (one per line) with its checks behind samwfmt.h's, else the text's lines
+template <bool BAM>
 __global__ void __launch_bounds__(kBlock)
 k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before, uint32_t* __restrict__ unit_len,
               uint32_t* __restrict__ unit_read, unsigned long long* __restrict__ misc) {
@@ -86,8 +99,9 @@ k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before
         const uint64_t r = lo, rank = h - a.hit_off[r], u = h + e_before[r];
         const sfgpu_hit rec = a.hits[h];
         uint64_t len = 0;
-        if (const int kind = samw_check(rec, a.n_refs)) atomicMin(&misc[kind == SAMW_BAD_POS ? 2 : 3], (unsigned long long)(r << 32 | rank));
-        else len = samw_unit_len(a, r, &rec, rank);
+        if (const int kind = BAM ? bamw_check(a, r, &rec, rank) : samw_check(rec, a.n_refs))
+            atomicMin(&misc[misc_of_kind(kind)], (unsigned long long)(r << 32 | rank));
+        else len = BAM ? bamw_unit_len(a, r, &rec, rank) : samw_unit_len(a, r, &rec, rank);
         if (len > 0xffffffffull) { atomicOr(&misc[0], kTooLong); len = 0; }
         unit_len[u] = (uint32_t)len;
         unit_read[u] = (uint32_t)r;
@@ -96,6 +110,7 @@ k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before
     count_lines(lines, misc);
 }
 
+template <bool BAM>
 __global__ void __launch_bounds__(kBlock)
 k_empty_size(SamwArgs a, const uint32_t* __restrict__ e_before, uint32_t* __restrict__ unit_len, uint32_t* __restrict__ unit_read,
              unsigned long long* __restrict__ misc) {
@@ -103,7 +118,9 @@ k_empty_size(SamwArgs a, const uint32_t* __restrict__ e_before, uint32_t* __rest
     uint32_t lines = 0;
     if (r < a.n_reads && a.hit_off[r] == a.hit_off[r + 1]) {
         const uint64_t u = (uint64_t)a.hit_off[r] + e_before[r];
-        uint64_t len = samw_unit_len(a, r, nullptr, 0);
+        uint64_t len = 0;
+        if (const int kind = BAM ? bamw_check(a, r, nullptr, 0) : 0) atomicMin(&misc[misc_of_kind(kind)], (unsigned long long)(r << 32));
+        else len = BAM ? bamw_unit_len(a, r, nullptr, 0) : samw_unit_len(a, r, nullptr, 0);
         if (len > 0xffffffffull) { atomicOr(&misc[0], kTooLong); len = 0; }
         unit_len[u] = (uint32_t)len;
         unit_read[u] = (uint32_t)r;
@@ -227,6 +244,106 @@ k_format(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __re
     if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
 }
 
+// ---- BAM records (bamwfmt.h): the same tiles, units and scan; a unit's lines are records
+struct BamJob {
+    const uint8_t* src;     // kCopy: the first byte that lies in the tile; kPack: the base of the first packed byte that does
+    uint32_t at, n;         // tile offset and bytes
+    uint32_t kind, left;    // kPack: the bases from src on
+};
+enum : uint32_t { kCopy = 0, kPack = 1, kFill = 2 };
+
+// k_format for BAM records.  One lane per record writes the 36 fixed bytes, the NUL, the CIGAR words, the default QNAME and
+// every name, packed SEQ or QUAL run of at most kShortCopy bytes; longer ones are queued, clipped to the tile, and done by the
+// wavefronts in turn, a byte per lane and step: a name copied, a packed byte made from its two bases, a QUAL byte set to 0xff.
+__global__ void __launch_bounds__(kBlock)
+k_format_bam(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
+             uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
+    __shared__ uint4 tile4[kBlock];
+    __shared__ BamJob jobs[kJobCap];
+    __shared__ uint32_t n_jobs;
+    uint8_t* tile = reinterpret_cast<uint8_t*>(tile4);
+    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
+    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    if (threadIdx.x == 0) n_jobs = 0;
+    __syncthreads();
+    const uint64_t end = base + kTileBytes < n_bytes ? base + kTileBytes : n_bytes;
+    const uint64_t u_lo = unit_of(unit_start, n_units, base), u_hi = unit_of(unit_start, n_units, end - 1);
+    auto put_at = [&](int64_t p, uint8_t b) {
+        if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = b;
+    };
+    // output bytes [s, s + n) of `kind` from src (kPack: n packed bytes of n_bases bases)
+    auto run = [&](uint32_t kind, const uint8_t* src, uint64_t s, uint64_t n, uint64_t n_bases) {
+        if (n <= kShortCopy) {
+            const int64_t p0 = (int64_t)(s - base);
+            for (uint32_t i = 0; i < (uint32_t)n; ++i)
+                put_at(p0 + i, kind == kCopy ? src[i] : kind == kPack ? bamw_packed_byte(src, n_bases, i) : (uint8_t)0xff);
+            return;
+        }
+        const uint64_t lo = s > base ? s : base, hi = s + n < end ? s + n : end;
+        if (lo >= hi) return;
+        const uint32_t k = atomicAdd(&n_jobs, 1u);
+        if (k >= kJobCap) return;
+        const uint64_t skip = lo - s;
+        jobs[k] = BamJob{kind == kCopy ? src + skip : kind == kPack ? src + 2 * skip : nullptr, (uint32_t)(lo - base), (uint32_t)(hi - lo), kind,
+                         kind == kPack ? (uint32_t)(n_bases - 2 * skip) : 0u};
+    };
+    for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
+        const uint64_t u = u_lo + (slot >> 1);
+        const uint32_t which = (uint32_t)(slot & 1);
+        const uint64_t r = unit_read[u];
+        const uint32_t h0 = a.hit_off[r];
+        const bool empty = h0 == a.hit_off[r + 1];
+        sfgpu_hit rec = {};
+        uint64_t rank = 0;
+        if (!empty) {
+            const uint64_t h = u - e_before[r];
+            rec = a.hits[h];
+            rank = h - h0;
+        }
+        if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
+        const uint32_t tid = empty ? 0u : rec.tid;
+        uint64_t s = unit_start[u];
+        if (which) s += bamw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_record_line(rec, rank, 0), r);
+        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_record_line(rec, rank, which);
+        const uint64_t len = bamw_line_len(a, l, r), qn = samw_qname_len(a, r);
+        if (s >= end || s + len <= base) continue;
+        const uint8_t* seq;
+        const uint64_t n_bases = bamw_l_seq(a, l, r, &seq);
+        {
+            const int64_t p0 = (int64_t)(s - base);
+            bamw_put_fixed(l, tid, len, qn, n_bases, [&](int i, uint8_t b) { put_at(p0 + i, b); });
+            s += kBamwFixed;
+        }
+        if (a.qname_off) run(kCopy, reinterpret_cast<const uint8_t*>(a.qnames) + a.qname_off[r], s, qn, 0);
+        else {
+            const int64_t p0 = (int64_t)(s - base);
+            samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { put_at(p0 + i, (uint8_t)ch); });
+        }
+        s += qn;
+        put_at((int64_t)(s - base), 0);
+        s += 1;
+        {
+            const int64_t p0 = (int64_t)(s - base);
+            bamw_put_cigar(l, [&](int i, uint8_t b) { put_at(p0 + i, b); });
+            s += 4 * bamw_cigar_ops(l);
+        }
+        run(kPack, seq, s, (n_bases + 1) / 2, n_bases);
+        s += (n_bases + 1) / 2;
+        run(kFill, nullptr, s, n_bases, 0);
+    }
+    __syncthreads();
+    const uint32_t nj = n_jobs < kJobCap ? n_jobs : kJobCap;
+    const uint32_t wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
+    for (uint32_t k = wave; k < nj; k += kBlock / kWave) {
+        const BamJob j = jobs[k];
+        for (uint32_t i = lane; i < j.n; i += kWave)
+            tile[j.at + i] = j.kind == kCopy ? j.src[i] : j.kind == kPack ? bamw_packed_byte(j.src, j.left, i) : (uint8_t)0xff;
+    }
+    __syncthreads();
+    const uint64_t g = base + 16ull * threadIdx.x;
+    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+}
+
 struct Scratch {
     DevBuf<uint32_t> empty, e_before, unit_len, unit_read;
     DevBuf<uint64_t> unit_start;
@@ -238,23 +355,26 @@ struct Scratch {
 
 using namespace sfgpu;
 
-extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                    void* user, sfgpu_samwrite_result* out, sfgpu_stream stream) {
-    const char* who = "sfgpu_sam_write_text";
-    SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null result");
+namespace {
+
+// sfgpu_sam_write_text (sink) and sfgpu_sam_write_bgzf (z; format SFGPU_SAMW_TEXT or SFGPU_SAMW_BAM): everything up to the chunk
+// loop is the same but for the kernels that size and check a unit
+int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired, const char* d_ref_names,
+              const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames, const uint64_t* d_qname_off, const uint8_t* d_seq1,
+              const int64_t* d_seq1_off, const uint8_t* d_seq2, const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes,
+              sfgpu_text_sink sink, void* user, sfgpu_bgzw* z, int format, sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    const bool bam = format == SFGPU_SAMW_BAM;
+    auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
+    if (!out) return fail(SFGPU_ERR_INVALID, "null result");
     memset(out, 0, sizeof(*out));
     if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
-    SF_REQUIRE(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk, SFGPU_ERR_INVALID,
-               "sfgpu_sam_write_text: chunk_bytes must lie in [16, 2^30] (0 = default)");
+    if (!(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk)) return fail(SFGPU_ERR_INVALID, "chunk_bytes must lie in [16, 2^30] (0 = default)");
     if (n_reads == 0) return SFGPU_OK;
-    SF_REQUIRE(d_hit_offsets, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null hit offsets");
-    SF_REQUIRE(d_ref_name_off || n_refs == 0, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null reference name offsets");
-    SF_REQUIRE(!d_qnames || d_qname_off, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: read names without their offsets");
-    SF_REQUIRE((!d_seq1 || d_seq1_off) && (!d_seq2 || d_seq2_off), SFGPU_ERR_INVALID, "sfgpu_sam_write_text: bases without their offsets");
-    SF_REQUIRE(n_reads < 0xffffffffu, SFGPU_ERR_RANGE, "sfgpu_sam_write_text: n_reads must be below 2^32 - 1");
+    if (!d_hit_offsets) return fail(SFGPU_ERR_INVALID, "null hit offsets");
+    if (!(d_ref_name_off || n_refs == 0)) return fail(SFGPU_ERR_INVALID, "null reference name offsets");
+    if (!(!d_qnames || d_qname_off)) return fail(SFGPU_ERR_INVALID, "read names without their offsets");
+    if (!((!d_seq1 || d_seq1_off) && (!d_seq2 || d_seq2_off))) return fail(SFGPU_ERR_INVALID, "bases without their offsets");
+    if (!(n_reads < 0xffffffffu)) return fail(SFGPU_ERR_RANGE, "n_reads must be below 2^32 - 1");
     SamwArgs a = {d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
                   d_seq1, d_seq1_off, paired ? d_seq2 : nullptr, paired ? d_seq2_off : nullptr, read_index_base};
 
@@ -262,13 +382,12 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
     CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
     hipStream_t st = nullptr;
     hipEvent_t ev_in = nullptr, ev_a[2] = {nullptr, nullptr}, ev_s[2] = {nullptr, nullptr};
-    unsigned long long* h_misc = nullptr;     // [0 .. kMisc) misc, [5] total bytes; uint32 view of [6]: n_hits, record-less reads
-    auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
+    unsigned long long* h_misc = nullptr;     // [0 .. kMisc) misc, [kMisc] total bytes; uint32 view of [kMisc + 1]: n_hits, record-less reads
     SF_HIP(scope.acquire(&st));
     SF_HIP(scope.event(&ev_in, hipEventDisableTiming));
     for (auto& e : ev_a) SF_HIP(scope.event(&e));
     for (auto& e : ev_s) SF_HIP(scope.event(&e));
-    SF_HIP(scope.pinned_block(&h_misc, 8 * sizeof(unsigned long long)));
+    SF_HIP(scope.pinned_block(&h_misc, (kMisc + 2) * sizeof(unsigned long long)));
     // behind whatever the caller has queued on `stream`
     SF_HIP(hipEventRecord(ev_in, as_stream(stream)));
     SF_HIP(hipStreamWaitEvent(st, ev_in, 0));
@@ -279,6 +398,7 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
     if (int rc = S.e_before.reserve((uint64_t)n_reads + 1, st, false)) return rc;
     SF_HIP(hipMemsetAsync(S.misc.p, 0, kMisc * sizeof(unsigned long long), st));
     SF_HIP(hipMemsetAsync(S.misc.p + 2, 0xff, 2 * sizeof(unsigned long long), st));
+    SF_HIP(hipMemsetAsync(S.misc.p + 5, 0xff, 3 * sizeof(unsigned long long), st));
     SF_HIP(hipEventRecord(ev_a[0], st));
     hipLaunchKernelGGL(k_read_flags, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, d_hit_offsets, n_reads, S.empty.p, S.misc.p);
     SF_HIP(hipGetLastError());
@@ -301,7 +421,7 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
     }
     if (int rc = exclusive_scan_u32_u32(S.empty.p, S.e_before.p, n_reads, st)) return rc;
     SF_HIP(hipEventRecord(ev_a[1], st));
-    uint32_t* h_counts = reinterpret_cast<uint32_t*>(&h_misc[6]);
+    uint32_t* h_counts = reinterpret_cast<uint32_t*>(&h_misc[kMisc + 1]);
     SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(&h_counts[0], d_hit_offsets + n_reads, 4, hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(&h_counts[1], S.e_before.p + n_reads, 4, hipMemcpyDeviceToHost, st));
@@ -318,42 +438,77 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
     if (int rc = S.unit_start.reserve(n_units + 1, st, false)) return rc;
     SF_HIP(hipEventRecord(ev_s[0], st));
     if (n_hits) {
-        hipLaunchKernelGGL(k_record_size, dim3(grid_of(n_hits)), dim3(kBlock), 0, st, a, n_hits, S.e_before.p, S.unit_len.p, S.unit_read.p,
+        hipLaunchKernelGGL(bam ? k_record_size<true> : k_record_size<false>, dim3(grid_of(n_hits)), dim3(kBlock), 0, st, a, n_hits, S.e_before.p, S.unit_len.p, S.unit_read.p,
                            S.misc.p);
         SF_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_empty_size, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, a, S.e_before.p, S.unit_len.p, S.unit_read.p, S.misc.p);
+    hipLaunchKernelGGL(bam ? k_empty_size<true> : k_empty_size<false>, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, a, S.e_before.p, S.unit_len.p, S.unit_read.p, S.misc.p);
     SF_HIP(hipGetLastError());
     if (int rc = exclusive_scan_u32(S.unit_len.p, S.unit_start.p, n_units, st, false)) return rc;
     if (int rc = textchunks::line_max(S.unit_start.p, n_units, S.misc.p + 1, st)) return rc;
     SF_HIP(hipEventRecord(ev_s[1], st));
     SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, kMisc * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    SF_HIP(hipMemcpyAsync(&h_misc[5], S.unit_start.p + n_units, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_misc[kMisc], S.unit_start.p + n_units, 8, hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
     add_elapsed(&out->format_ms, ev_s[0], ev_s[1]);
-    if (h_misc[2] != kNoError || h_misc[3] != kNoError) {
-        const bool by_pos = h_misc[2] <= h_misc[3];       // (one record breaking both rules reports the position, as samw_check does)
-        const unsigned long long key = by_pos ? h_misc[2] : h_misc[3];
-        out->error_read = key >> 32; out->error_record = key & 0xffffffffull; out->error_kind = by_pos ? SAMW_BAD_POS : SAMW_BAD_TID;
-        set_error("%s: read %llu, record %llu: %s", who, (unsigned long long)out->error_read, (unsigned long long)out->error_record,
-                  by_pos ? "the read has no base on the transcript: SAM cannot say that" : "the transcript id is not below n_refs");
-        return SFGPU_ERR_INVALID;
+    {   // the lowest (read, record) of any kind; one record breaking several rules reports the first, as samw_check / bamw_check do
+        static const char* const kWhat[] = {"", "the read has no base on the transcript: SAM cannot say that", "the transcript id is not below n_refs",
+                                            "the read name is not of 1 .. 254 bytes: BAM cannot say that",
+                                            "the bases given differ in number from the read length, or are more than 65535",
+                                            "the alignment ends beyond 2^29"};
+        static const int kSlot[] = {0, 2, 3, 5, 6, 7};
+        int kind = 0;
+        for (int k = 1; k <= BAMW_BAD_END; ++k)
+            if (h_misc[kSlot[k]] != kNoError && (!kind || h_misc[kSlot[k]] < h_misc[kSlot[kind]])) kind = k;
+        if (kind) {
+            const unsigned long long key = h_misc[kSlot[kind]];
+            out->error_read = key >> 32; out->error_record = key & 0xffffffffull; out->error_kind = (uint32_t)kind;
+            set_error("%s: read %llu, record %llu: %s", who, (unsigned long long)out->error_read, (unsigned long long)out->error_record, kWhat[kind]);
+            return SFGPU_ERR_INVALID;
+        }
     }
     if (h_misc[0] & kTooLong) return fail(SFGPU_ERR_RANGE, "a unit is longer than 2^32 - 1 bytes");
-    const uint64_t total = h_misc[5];
+    const uint64_t total = h_misc[kMisc];
     out->n_bytes = total; out->n_lines = h_misc[4]; out->max_unit_bytes = h_misc[1];
-    if (!sink) return SFGPU_OK;
+    if (!sink && !z) return SFGPU_OK;
     if (out->max_unit_bytes > chunk_bytes) return fail(SFGPU_ERR_RANGE, "a unit (a line, or the two lines of a pair) is longer than chunk_bytes");
 
     // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this text's tiles
     textchunks::Stats ts;
-    const int rc = textchunks::deliver(who, S.unit_start.p, n_units, total, chunk_bytes, sink, user, st, &ts,
-                                       [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-        hipLaunchKernelGGL(k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
-                           S.unit_start.p, n_units, total, first_tile, out_base, buf);
+    auto format_tiles = [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
+        hipLaunchKernelGGL(bam ? k_format_bam : k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p,
+                           S.unit_read.p, S.unit_start.p, n_units, total, first_tile, out_base, buf);
         SF_HIP(hipGetLastError());
         return SFGPU_OK;
-    });
+    };
+    // the compressed formats: the chunk's device bytes go to the BGZF encoder, which copies and sinks what IT writes
+    const int rc = z ? textchunks::deliver_device(who, S.unit_start.p, n_units, total, chunk_bytes, st, &ts,
+                                                  [&](const uint8_t* d_bytes, uint64_t n, hipStream_t ready) -> int {
+                                                      return sfgpu_bgzw_write_device(z, d_bytes, n, reinterpret_cast<sfgpu_stream>(ready));
+                                                  }, format_tiles)
+                     : textchunks::deliver(who, S.unit_start.p, n_units, total, chunk_bytes, sink, user, st, &ts, format_tiles);
     out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
     return rc;
+}
+
+}  // namespace
+
+extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                    void* user, sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    return sam_write("sfgpu_sam_write_text", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, nullptr, SFGPU_SAMW_TEXT, out, stream);
+}
+
+extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                    sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
+    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
+    return sam_write("sfgpu_sam_write_bgzf", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, read_index_base, chunk_bytes, nullptr, nullptr, z, format, out, stream);
 }

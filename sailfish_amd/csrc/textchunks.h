@@ -3,6 +3,8 @@
 // 64-bit byte start of every line on the device (line_start[n_lines] = the total) and a step "format tiles [a, b] of the text
 // into this buffer"; tiles are kTileBytes of the OUTPUT, aligned in the text's byte offsets, and a chunk's buffer starts at the
 // tile that holds its first byte.  Chunk c + 1 is formatted and copied to its pinned buffer while the sink consumes chunk c.
+// deliver_device is the second consumer: the chunk's bytes stay on the device and go to a function (the BGZF encoder of
+// samtext_write.hip's compressed formats) while chunk c + 1 is formatted.
 #pragma once
 #include "common.h"
 
@@ -75,26 +77,16 @@ struct Pipe {
     CallScope scope;
 };
 
-// Plans the chunks of a text of `total` bytes in n_lines lines (every line at most chunk_bytes long: the caller has checked) and
-// hands them to `sink` in order.  format_tiles(first_tile, last_tile, out_base, out, st) enqueues on st the kernels that write
-// tiles first_tile .. last_tile into `out`, whose byte 0 is text byte out_base = first_tile * kTileBytes, and returns a status.
-// `who` names the entry point in error messages.  st is the caller's stream (the sizing pass ran on it); it is drained on return.
-template <typename FormatTiles>
-int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uint64_t total, uint64_t chunk_bytes, sfgpu_text_sink sink,
-            void* user, hipStream_t st, Stats* stats, FormatTiles format_tiles) {
-    Pipe P;
-    hipStream_t cs = nullptr;
-    char* pinned[2] = {nullptr, nullptr};
+// The chunk plan of a text of `total` bytes in n_lines lines (every line at most chunk_bytes long: the caller has checked), on st:
+// *h_plan (pinned, the scope's) holds per chunk its line end and its byte end.  Two consecutive greedy chunks hold more than
+// chunk_bytes together, which bounds their number.
+inline int plan_chunks(const char* who, Pipe& P, const uint64_t* d_line_start, uint64_t n_lines, uint64_t total, uint64_t chunk_bytes,
+                       hipStream_t st, Stats* stats, uint64_t** h_plan_out, uint64_t* n_chunks_out) {
     hipEvent_t ev_p[2] = {nullptr, nullptr};
-    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
     uint64_t* h_plan = nullptr;
     unsigned long long* h_n = nullptr;
-    SF_HIP(P.scope.adopt(st));
-    SF_HIP(P.scope.acquire(&cs));
     for (auto& e : ev_p) SF_HIP(P.scope.event(&e));
     SF_HIP(P.scope.pinned_block(&h_n, sizeof(unsigned long long)));
-
-    // ---- the chunk plan: two consecutive greedy chunks hold more than chunk_bytes together
     const uint64_t plan_cap = 2 * (total / chunk_bytes) + 2;
     if (int rc = P.plan.reserve(2 * plan_cap, st, false)) return rc;
     if (int rc = P.n.reserve(1, st, false)) return rc;
@@ -113,6 +105,26 @@ int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uin
         set_error("%s: the chunk plan does not cover the table", who);
         return SFGPU_ERR_HIP;
     }
+    *h_plan_out = h_plan; *n_chunks_out = n_chunks;
+    return SFGPU_OK;
+}
+
+// Plans the chunks of a text of `total` bytes in n_lines lines (every line at most chunk_bytes long: the caller has checked) and
+// hands them to `sink` in order.  format_tiles(first_tile, last_tile, out_base, out, st) enqueues on st the kernels that write
+// tiles first_tile .. last_tile into `out`, whose byte 0 is text byte out_base = first_tile * kTileBytes, and returns a status.
+// `who` names the entry point in error messages.  st is the caller's stream (the sizing pass ran on it); it is drained on return.
+template <typename FormatTiles>
+int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uint64_t total, uint64_t chunk_bytes, sfgpu_text_sink sink,
+            void* user, hipStream_t st, Stats* stats, FormatTiles format_tiles) {
+    Pipe P;
+    hipStream_t cs = nullptr;
+    char* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr}, ev_c0[2] = {nullptr, nullptr}, ev_c1[2] = {nullptr, nullptr};
+    uint64_t* h_plan = nullptr;
+    uint64_t n_chunks = 0;
+    SF_HIP(P.scope.adopt(st));
+    SF_HIP(P.scope.acquire(&cs));
+    if (int rc = plan_chunks(who, P, d_line_start, n_lines, total, chunk_bytes, st, stats, &h_plan, &n_chunks)) return rc;
 
     // ---- format + copy + sink, two buffers: chunk i + 1 is formatted and copied while the sink holds chunk i
     const uint64_t stage_bytes = total < chunk_bytes ? total : chunk_bytes;
@@ -153,6 +165,52 @@ int deliver(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uin
             set_error("%s: the sink refused a chunk", who);
             return SFGPU_ERR_IO;
         }
+    }
+    return SFGPU_OK;
+}
+
+// The same plan and the same tiles, but the chunk stays on the device: consume(d_bytes, n_bytes, ready) is called per chunk in
+// order with a stream `ready` behind which the chunk's bytes are complete; it returns a status when it is done with the bytes
+// (synchronous, as a sink is).  Chunk i + 1 is formatted on st meanwhile.
+template <typename Consume, typename FormatTiles>
+int deliver_device(const char* who, const uint64_t* d_line_start, uint64_t n_lines, uint64_t total, uint64_t chunk_bytes, hipStream_t st,
+                   Stats* stats, Consume consume, FormatTiles format_tiles) {
+    Pipe P;
+    hipStream_t ready = nullptr;
+    hipEvent_t ev_f0[2] = {nullptr, nullptr}, ev_f1[2] = {nullptr, nullptr};
+    uint64_t* h_plan = nullptr;
+    uint64_t n_chunks = 0;
+    SF_HIP(P.scope.adopt(st));
+    SF_HIP(P.scope.acquire(&ready));
+    if (int rc = plan_chunks(who, P, d_line_start, n_lines, total, chunk_bytes, st, stats, &h_plan, &n_chunks)) return rc;
+    const uint64_t stage_bytes = total < chunk_bytes ? total : chunk_bytes;
+    const uint64_t out_groups = (stage_bytes + 2 * kTileBytes) / 16 + 1;
+    for (int b = 0; b < 2 && (uint64_t)b < n_chunks; ++b) {
+        if (int rc = P.out[b].reserve(out_groups, st, false)) return rc;
+        for (hipEvent_t* e : {&ev_f0[b], &ev_f1[b]}) SF_HIP(P.scope.event(e));
+    }
+    auto chunk_begin = [&](uint64_t i) -> uint64_t { return i ? h_plan[2 * i - 1] : 0; };
+    auto out_base = [&](uint64_t i) -> uint64_t { return (chunk_begin(i) >> kTileShift) << kTileShift; };
+    // format on st into out[slot]: the slot's previous chunk has been consumed
+    auto enqueue = [&](uint64_t i) -> int {
+        const int slot = (int)(i & 1);
+        const uint64_t b0 = chunk_begin(i), b1 = h_plan[2 * i + 1];
+        SF_HIP(hipEventRecord(ev_f0[slot], st));
+        if (int rc = format_tiles(b0 >> kTileShift, (b1 - 1) >> kTileShift, out_base(i), P.out[slot].p, st)) return rc;
+        SF_HIP(hipEventRecord(ev_f1[slot], st));
+        return SFGPU_OK;
+    };
+    if (int rc = enqueue(0)) return rc;
+    for (uint64_t i = 0; i < n_chunks; ++i) {
+        const int slot = (int)(i & 1);
+        SF_HIP(hipStreamWaitEvent(ready, ev_f1[slot], 0));      // before chunk i + 1 is queued: the consumer waits for chunk i alone
+        if (i + 1 < n_chunks) if (int rc = enqueue(i + 1)) return rc;
+        const uint64_t b0 = chunk_begin(i);
+        const int rc = consume(reinterpret_cast<const uint8_t*>(P.out[slot].p) + (b0 - out_base(i)), h_plan[2 * i + 1] - b0, ready);
+        if (rc != SFGPU_OK) return rc;                          // (a consumer that failed may not have waited for the chunk)
+        SF_HIP(hipEventSynchronize(ev_f1[slot]));               // the consumer has waited behind it: this returns at once
+        add_elapsed(&stats->format_ms, ev_f0[slot], ev_f1[slot]);
+        stats->n_chunks++;
     }
     return SFGPU_OK;
 }

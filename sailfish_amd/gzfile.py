@@ -3,7 +3,9 @@ compressor: the raw bytes of device tensors become one gzip member whose DEFLATE
 (sfgpu_gz_open / sfgpu_gz_write_device / sfgpu_gz_close, sailfish_amd/csrc/gzwrite.hip).  Any gzip reader inflates the file to
 the bytes written, in order; the compressed bytes are not zlib's.
 
-`write_bgzf` is the host-side writer of the blocked form (BGZF) that `readfile.ReadFile` inflates on the device."""
+`BgzfDeviceWriter` is its twin for the blocked form (BGZF: the container of BAM, what samtools and IGV read), whose members carry
+real (length, distance) matches (sfgpu_bgzw_*, sailfish_amd/csrc/bgzf_write.hip); `write_bgzf` is the host-side writer of that
+form, which `readfile.ReadFile` and `samfile.SamFile` inflate on the device."""
 import ctypes as C
 import os
 import struct
@@ -77,6 +79,90 @@ class GzDeviceWriter:
             h, self._h = self._h, None
             with torch.cuda.device(self._device):
                 rc = _lib.lib().sfgpu_gz_close(h, C.byref(res))
+            self.result = res.as_dict()
+            self._check(rc)
+        finally:
+            if self._own:
+                self._f.close()
+        return self.result
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class BgzfDeviceWriter:
+    """BgzfDeviceWriter(path or binary file object, chunk_bytes=0): the twin of GzDeviceWriter for a BGZF file (sfgpu_bgzw_open /
+    sfgpu_bgzw_write_device / sfgpu_bgzw_close).  write(tensor) appends the raw bytes of a contiguous device tensor as members of
+    32 768 payload bytes (the write's last one short), close() writes the EOF member and returns the sfgpu_bgzw_result as a dict
+    (also kept as .result and .stats); usable as a context manager.  The stream is opened by the first write, on that tensor's
+    device (by close, on the current device, for an empty file).  An exception of the file object's write stops the stream and is
+    raised again by the call that met it.  The file is a function of the bytes and of the way they are split into writes."""
+
+    def __init__(self, fileobj_or_path, chunk_bytes=0):
+        self._own = isinstance(fileobj_or_path, (str, bytes, os.PathLike))
+        self._f = open(fileobj_or_path, "wb") if self._own else fileobj_or_path
+        self._chunk = int(chunk_bytes)
+        self._h = None
+        self._closed = False
+        self._raised = []
+        self.result = None
+
+        def sink(addr, n, _user):
+            try:                                   # nothing may unwind through the C frame
+                self._f.write(memoryview((C.c_char * n).from_address(addr)))
+                return 0
+            except BaseException as e:             # noqa: BLE001  (re-raised by _check)
+                self._raised.append(e)
+                return 1
+        self._sink = _lib.TEXT_SINK(sink)          # alive as long as the handle
+
+    @property
+    def stats(self):
+        return self.result
+
+    def _check(self, rc):
+        if self._raised:
+            raise self._raised.pop(0)
+        _lib.check(rc)
+
+    def _open(self, device):
+        if self._h is None:
+            h = C.c_void_p()
+            with torch.cuda.device(device):
+                rc = _lib.lib().sfgpu_bgzw_open(C.byref(h), self._sink, None, self._chunk)
+            self._check(rc)
+            self._h, self._device = h, device
+
+    def write(self, tensor):
+        if self._closed:
+            raise ValueError("write to a closed BgzfDeviceWriter")
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda):
+            raise TypeError("BgzfDeviceWriter.write expects a device tensor")
+        if not tensor.is_contiguous():
+            raise ValueError("BgzfDeviceWriter.write expects a contiguous tensor")
+        self._open(tensor.device)
+        if tensor.device != self._device:
+            raise ValueError(f"the stream was opened on {self._device}, the tensor lies on {tensor.device}")
+        n = tensor.numel() * tensor.element_size()
+        with torch.cuda.device(self._device):
+            rc = _lib.lib().sfgpu_bgzw_write_device(self._h, _lib.ptr(tensor), n, _lib.current_stream_ptr())
+        self._check(rc)
+        return n
+
+    def close(self):
+        if self._closed:
+            return self.result
+        self._closed = True
+        try:
+            self._open(torch.device("cuda", torch.cuda.current_device()))
+            res = _lib.BgzwResult()
+            h, self._h = self._h, None
+            with torch.cuda.device(self._device):
+                rc = _lib.lib().sfgpu_bgzw_close(h, C.byref(res))
             self.result = res.as_dict()
             self._check(rc)
         finally:

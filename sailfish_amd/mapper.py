@@ -108,24 +108,27 @@ def hits_to_numpy(hits, offsets):
     return hits.cpu().numpy().view(HIT_DTYPE), offsets.cpu().numpy().view(np.uint32)
 
 
-def _mappings_writer(write_mappings, names, idx, paired):
+def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam"):
     """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
     if write_mappings is None:
         return None
     from .samfile import SamDeviceWriter
-    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired)
+    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format)
 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   write_mappings=None, **kw):
+                   write_mappings=None, mappings_format="sam", **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
-    is quantified: QNAME r<index of the read>, SEQ the read's bases; the estimates do not depend on it.  -> (rc, experiment)"""
+    is quantified: QNAME r<index of the read>, SEQ the read's bases; the estimates do not depend on it.  mappings_format is
+    SamDeviceWriter's `format` ("sam"; "sam.gz" for the text, "bam" for BAM records, in BGZF members encoded on the device); it is never
+    inferred from the path.
+    -> (rc, experiment)"""
     from . import quant
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
-    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None)
+    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format)
 
     def batches():
         for a in range(0, n, batch_reads):
@@ -161,17 +164,17 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", write_mappings=None, **kw):
+                   inflate="auto", write_mappings=None, mappings_format="sam", **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
-    write_mappings as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names are
+    write_mappings and mappings_format as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names are
     sliced and packed on the host: ReadFile(names=True)).  -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, read_transcripts
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
-    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None)
+    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format)
 
     def batches():
         f1 = ReadFile(reads1_path, device, names=sam is not None, inflate=inflate)

@@ -514,7 +514,14 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
 
 # ---- the way back, on the device ------------------------------------------------------------------------------------------
 
+# SamDeviceWriter(format=): plain text; the same text in BGZF members encoded on the device; BAM records, likewise
+WRITE_FORMATS = ("sam", "sam.gz", "bam")
+_SAMW_FORMAT = {"sam.gz": 0, "bam": 1}                     # SFGPU_SAMW_TEXT, SFGPU_SAMW_BAM (include/sfgpu.h)
 WRITE_KINDS = {1: "the read has no base on the transcript: SAM cannot say that", 2: "the transcript index is not below the number of names"}
+# what format="bam" adds (csrc/bamwfmt.h), behind WRITE_KINDS where one record breaks several
+BAM_WRITE_KINDS = {3: "the read name is not of 1 .. 254 bytes: BAM cannot say that",
+                   4: "the bases given differ in number from the record's read length, or are more than 65535: BAM cannot say that",
+                   5: "the alignment ends beyond 2^29: BAM cannot say that"}
 
 
 def sam_header(names, ref_len):
@@ -535,12 +542,20 @@ class SamDeviceWriter:
       seqs        the (bases, int64 offsets) device pair of readfile.ReadFile.read / mapper.pack_sequences, or (paired) a pair of such
                   pairs; default '*'.  Bases are written as given, also on 0x10 lines.
     A record SAM cannot express (WRITE_KINDS) raises ValueError naming the lowest such read -- counted over all batches, as
-    write_sam counts it -- and record; nothing of that batch is written.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times."""
+    write_sam counts it -- and record; nothing of that batch is written.
+    `format`: "sam" (the default) writes the text as it is.  "sam.gz" writes the same text, @HD / @SQ lines included, as a BGZF
+    file whose members are encoded on the device (gzfile.BgzfDeviceWriter; csrc/bgzf_write.hip): the formatted chunks go from
+    the formatter to the encoder on the device, only compressed bytes are copied; close() writes the EOF member and adds
+    bytes_out, members, stored_members, matches, literals, ms_encode and chunks_out to `stats`.  "bam" writes the BAM file
+    write_bam writes (sam_to_bam of the same text: magic, header text, reference list, one record per line; csrc/bamwfmt.h) through
+    the same encoder; BAM_WRITE_KINDS are then errors too, a read without records counting as record 0.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times."""
 
-    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0):
+    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam"):
         from . import _lib, quantfile
+        if format not in WRITE_FORMATS:
+            raise ValueError(f"format must be one of {WRITE_FORMATS}, not {format!r}")
         self._L = _lib.lib()
-        self.paired, self.chunk_bytes = bool(paired), int(chunk_bytes)
+        self.paired, self.chunk_bytes, self.format = bool(paired), int(chunk_bytes), format
         self._names = quantfile.names_blob(_name_bytes(names))
         self._n_refs = len(self._names[1]) - 1
         self._d_names = None                               # uploaded to the device of the first batch
@@ -549,8 +564,21 @@ class SamDeviceWriter:
         self.n_reads = 0                                   # the running read index
         self.stats = dict(reads=0, hits=0, lines=0, bytes=0, chunks=0, batches=0, ms_format=0.0, ms_copy=0.0, ms_sink=0.0)
         head = sam_header(names, ref_len)
-        self._f.write(head)
+        if format == "bam":
+            head = sam_to_bam(head)                        # magic, header text and reference list
         self.stats["header_bytes"] = len(head)
+        self._z = None
+        if format == "sam":
+            self._f.write(head)
+        else:                                              # the header goes through the encoder as the first write, once the device is known
+            from . import gzfile
+            self._z, self._head = gzfile.BgzfDeviceWriter(self._f, chunk_bytes=self.chunk_bytes), head
+
+    def _write_head(self, dev):
+        import torch
+        if self._head is not None:
+            head, self._head = self._head, None
+            self._z.write(torch.from_numpy(np.frombuffer(head, np.uint8).copy()).to(dev))
 
     @staticmethod
     def _blob(pair, dev):
@@ -604,14 +632,20 @@ class SamDeviceWriter:
 
         res = _lib.SamWriteResult()
         p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
+        batch = (p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs, p(q[0]), p(q[1]),
+                 p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads, self.chunk_bytes)
         with torch.cuda.device(dev):
-            rc = self._L.sfgpu_sam_write_text(p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]),
-                                              self._n_refs, p(q[0]), p(q[1]), p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads,
-                                              self.chunk_bytes, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
-        if raised:
-            raise raised[0]
+            if self._z is None:
+                rc = self._L.sfgpu_sam_write_text(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
+            else:
+                self._write_head(dev)
+                rc = self._L.sfgpu_sam_write_bgzf(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr())
+        sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
+        if sunk:
+            raise sunk.pop(0)
         if rc == _lib.ERR_INVALID and res.error_kind:
-            raise ValueError(f"read {self.n_reads + int(res.error_read)}, record {int(res.error_record)}: {WRITE_KINDS[int(res.error_kind)]}")
+            what = {**WRITE_KINDS, **BAM_WRITE_KINDS}[int(res.error_kind)]
+            raise ValueError(f"read {self.n_reads + int(res.error_read)}, record {int(res.error_record)}: {what}")
         _lib.check(rc)
         self.n_reads += n
         st = self.stats
@@ -621,12 +655,27 @@ class SamDeviceWriter:
         return res.as_dict()
 
     def close(self):
-        if self._f is not None:
+        if self._f is None:
+            return
+        try:
+            if self._z is not None:
+                try:
+                    if not self._z._raised and self._z._h is None:
+                        import torch
+                        self._write_head(torch.device("cuda", torch.cuda.current_device()))
+                    res = self._z.close()              # the EOF member
+                finally:
+                    self._z = None
+                for k, v in (("bytes_out", res["n_bytes_out"]), ("members", res["n_members"]), ("stored_members", res["n_stored_members"]),
+                             ("matches", res["n_matches"]), ("literals", res["n_literals"]), ("ms_encode", res["encode_ms"])):
+                    self.stats[k] = v
+                self.stats["ms_copy"] += res["d2h_ms"]; self.stats["ms_sink"] += res["sink_ms"]; self.stats["chunks_out"] = res["n_chunks"]
+        finally:                                       # the file is released also when the encoder's close raises
+            f, self._f = self._f, None
             if self._own:
-                self._f.close()
+                f.close()
             else:
-                self._f.flush()
-            self._f = None
+                f.flush()
 
     def __enter__(self):
         return self

@@ -631,7 +631,8 @@ SFGPU_API int sfgpu_sam_write_text(const struct sfgpu_hit* d_hits, const uint32_
  * (RFC 1951) blocks come from HIP kernels (csrc/gzwrite.hip; the arithmetic is csrc/gzfmt.h).  The contract of the file is "one
  * gzip member whose payload is the bytes written, in order"; the compressed bytes differ from zlib's.
  *   open   emits the 10-byte header through `sink`.  chunk_bytes: the largest piece handed to the sink (0 = 32 MiB; otherwise
- *          16 .. 2^30, else SFGPU_ERR_INVALID); pieces end anywhere, also inside a DEFLATE block.
+ *          16 .. 2^30, else SFGPU_ERR_INVALID); pieces end anywhere, also inside a DEFLATE block.  Takes the handle's streams and
+ *          8 KB of device memory for the per-block CRCs (SFGPU_ERR_HIP where it cannot), also for a handle that never writes.
  *   write  n_bytes at d_src (any alignment; n_bytes == 0 is legal and emits nothing) are cut into independent 64 KB blocks, each
  *          coded as one dynamic-Huffman block over literals and distance-1 run matches of length 3 .. 258 (the token class of
  *          zlib's Z_RLE) and padded to a byte by an empty stored block -- or as stored blocks where that is not shorter: a block

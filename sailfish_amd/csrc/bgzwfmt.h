@@ -115,34 +115,13 @@ SF_GZ_HD void bgzw_eof_member(uint8_t* out) {
     for (uint32_t i = 20; i < kBgzwEofBytes; ++i) out[i] = 0;
 }
 
-// The header of the FINAL dynamic block for the literal/length lengths `lens` and the distance lengths `dlens`, written from
-// bit pos0 through or32.  Returns its length in bits.  `w` is the caller's scratch.
+// The header of the FINAL dynamic block for the literal/length lengths `lens` and the distance lengths `dlens` (trailing zeros
+// above symbol 0 are not sent), written from bit pos0 through or32: gzfmt.h's writer.  Returns its length in bits.
 template <typename Or32>
 SF_GZ_HD uint32_t bgzw_write_block_header(const uint8_t* lens, const uint8_t* dlens, GzClWork* w, uint64_t pos0, Or32 or32) {
-    uint32_t* cl_freq = w->cl_freq; uint32_t* cl_code = w->cl_code; uint8_t* cl_lens = w->cl_lens;
-    int n_lit = kGzLitSyms, n_dist = kBgzwDistSyms;
-    while (n_lit > 257 && lens[n_lit - 1] == 0) --n_lit;
+    int n_dist = kBgzwDistSyms;
     while (n_dist > 1 && dlens[n_dist - 1] == 0) --n_dist;
-    const int n_seq = n_lit + n_dist;
-    auto seq = [&](int i) -> int { return i < n_lit ? (int)lens[i] : (int)dlens[i - n_lit]; };
-    for (int s = 0; s < kGzClSyms; ++s) cl_freq[s] = 0;
-    gz_cl_rle(seq, n_seq, [&](int sym, int, uint32_t) { ++cl_freq[sym]; });
-    huff_lengths_serial(cl_freq, kGzClSyms, kGzMaxClBits, cl_lens, w->order, w->parent, w->node_freq, w->count);
-    for (int s = 0; s < kGzClSyms; ++s) cl_code[s] = huff_code_rev(cl_lens, kGzClSyms, s);
-    int n_cl = kGzClSyms;
-    while (n_cl > 4 && cl_lens[gz_cl_order(n_cl - 1)] == 0) --n_cl;
-    uint64_t pos = pos0;
-    auto put = [&](uint32_t v, int nb) { gz_put_bits(or32, pos, v, nb); pos += (uint32_t)nb; };
-    put(1u, 1);                                          // BFINAL
-    put(2u, 2);                                          // BTYPE = dynamic
-    put((uint32_t)(n_lit - 257), 5);
-    put((uint32_t)(n_dist - 1), 5);
-    put((uint32_t)(n_cl - 4), 4);
-    for (int i = 0; i < n_cl; ++i) put(cl_lens[gz_cl_order(i)], 3);
-    gz_cl_rle(seq, n_seq, [&](int sym, int eb, uint32_t ev) {
-        put(cl_code[sym] | (ev << cl_lens[sym]), cl_lens[sym] + eb);
-    });
-    return (uint32_t)(pos - pos0);
+    return gz_write_dyn_header(1u, pos0, lens, [&](int i) { return dlens[i]; }, n_dist, w, or32);
 }
 
 // bits of one token under the two codes

@@ -14,7 +14,8 @@
 //   huff_*           length-limited code lengths from a histogram: order by (frequency, symbol), two-queue merge, leaf depths,
 //                    depth counts forced to the limit by Kraft arithmetic, lengths handed out by rank; canonical codes
 //   gz_cl_rle        the code-length sequence of a block header in symbols 0 .. 18 (16 / 17 / 18 are the repeats)
-//   gz_write_block_header / gz_header / gz_trailer / gz_stored_*   the framing
+//   gz_write_dyn_header / gz_write_block_header / gz_header / gz_trailer / gz_stored_*   the framing (the dynamic block header is
+//                    bgzwfmt.h's as well)
 //   gz_encode_block_serial   all of it driven by a plain loop: the host encoder that the device stream is compared with
 // Steps that the kernel runs one lane per item (rank, depth, length of rank, canonical code) are functions of one item here, so
 // that the serial driver and the kernel call the same code.
@@ -321,38 +322,45 @@ SF_GZ_HD int gz_cl_order(int i) {
     return order[i];
 }
 
-// The header of a non-final dynamic block for the literal/length lengths `lens` (the distance code is always symbols 0 and 1 at
-// one bit each: distance 1 is symbol 0), written from bit 0 through or32.  Returns its length in bits.  `w` is the caller's scratch.
+// The header of a dynamic block with the given BFINAL bit, for the literal/length lengths `lens` (trailing zeros above symbol
+// 256 are not sent) and the n_dist distance lengths dist_len(0 .. n_dist - 1) exactly as the caller counts them, written from bit
+// pos0 through or32.  Returns its length in bits.  `w` is the caller's scratch.
 struct GzClWork {
     uint32_t cl_freq[kGzClSyms], cl_code[kGzClSyms], node_freq[2 * kGzClSyms], count[kGzMaxClBits + 1];
     uint16_t order[kGzClSyms], parent[2 * kGzClSyms];
     uint8_t cl_lens[kGzClSyms];
 };
-template <typename Or32>
-SF_GZ_HD uint32_t gz_write_block_header(const uint8_t* lens, GzClWork* w, Or32 or32) {
+template <typename DistLen, typename Or32>
+SF_GZ_HD uint32_t gz_write_dyn_header(uint32_t bfinal, uint64_t pos0, const uint8_t* lens, DistLen dist_len, int n_dist, GzClWork* w, Or32 or32) {
     uint32_t* cl_freq = w->cl_freq; uint32_t* cl_code = w->cl_code; uint8_t* cl_lens = w->cl_lens;
     int n_lit = kGzLitSyms;
     while (n_lit > 257 && lens[n_lit - 1] == 0) --n_lit;
-    const int n_seq = n_lit + kGzDistSyms;
-    auto seq = [&](int i) -> int { return i < n_lit ? (int)lens[i] : 1; };
+    const int n_seq = n_lit + n_dist;
+    auto seq = [&](int i) -> int { return i < n_lit ? (int)lens[i] : (int)dist_len(i - n_lit); };
     for (int s = 0; s < kGzClSyms; ++s) cl_freq[s] = 0;
     gz_cl_rle(seq, n_seq, [&](int sym, int, uint32_t) { ++cl_freq[sym]; });
     huff_lengths_serial(cl_freq, kGzClSyms, kGzMaxClBits, cl_lens, w->order, w->parent, w->node_freq, w->count);
     for (int s = 0; s < kGzClSyms; ++s) cl_code[s] = huff_code_rev(cl_lens, kGzClSyms, s);
     int n_cl = kGzClSyms;
     while (n_cl > 4 && cl_lens[gz_cl_order(n_cl - 1)] == 0) --n_cl;
-    uint64_t pos = 0;
+    uint64_t pos = pos0;
     auto put = [&](uint32_t v, int nb) { gz_put_bits(or32, pos, v, nb); pos += (uint32_t)nb; };
-    put(0u, 1);                                          // BFINAL
+    put(bfinal, 1);
     put(2u, 2);                                          // BTYPE = dynamic
     put((uint32_t)(n_lit - 257), 5);
-    put((uint32_t)(kGzDistSyms - 1), 5);
+    put((uint32_t)(n_dist - 1), 5);
     put((uint32_t)(n_cl - 4), 4);
     for (int i = 0; i < n_cl; ++i) put(cl_lens[gz_cl_order(i)], 3);
     gz_cl_rle(seq, n_seq, [&](int sym, int eb, uint32_t ev) {
         put(cl_code[sym] | (ev << cl_lens[sym]), cl_lens[sym] + eb);
     });
-    return (uint32_t)pos;
+    return (uint32_t)(pos - pos0);
+}
+// this stream's blocks: not final, from bit 0; the distance code is always symbols 0 and 1 at one bit each (distance 1 is
+// symbol 0), and both are sent: the count is not trimmed
+template <typename Or32>
+SF_GZ_HD uint32_t gz_write_block_header(const uint8_t* lens, GzClWork* w, Or32 or32) {
+    return gz_write_dyn_header(0u, 0ull, lens, [](int) { return 1; }, kGzDistSyms, w, or32);
 }
 
 // bits of one token under the lengths `lens` / its code word (literal: the byte; match: length code, extra bits, the 1-bit

@@ -1,6 +1,6 @@
-// slotcompact.h -- the last step of the BGZF encoder (bgzf_write.hip): every workgroup has left its member in a slot of
-// kSlotBytes at a 16-byte boundary, a scan of the member lengths gives the byte offsets, and this kernel moves the slots there
-// (the scheme of gzwrite.hip's k_gz_compact, for any slot size).  Members end on byte boundaries, so no bit is touched.
+// slotcompact.h -- the last device step of the slot writers (slotpipe.h; gzwrite.hip's blocks, bgzf_write.hip's members): every
+// workgroup has left its bytes in a slot of kSlotBytes at a 16-byte boundary, a scan of the lengths gives the byte offsets, and
+// this kernel moves the slots there.  Blocks and members end on byte boundaries, so no bit is touched.
 #pragma once
 #include <cstdint>
 

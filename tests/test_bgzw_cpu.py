@@ -4,6 +4,7 @@ inflater (bgzfmt.h through tests/bgzf_harness.cpp): every member the serial enco
 pay, carries the matches the parse is stated to find, and alignment files come out below zlib's Z_RLE.  No GPU."""
 import ctypes as C
 import gzip
+import json
 import os
 import re
 import struct
@@ -175,12 +176,15 @@ def test_every_member_is_valid(harness, inflater):
             assert st["stored"] == (1 if 0 < len(data) % P < 32 else 0) and len(file) < len(data) // 8 + 200, name      # a tiny last member
 
 
+def several_writes_case(P):
+    return bamwrite_corpus.stream(True, "sam", 300)[:3 * P + 1000], (1, P - 1, 0, P + 1, 7)
+
+
 def test_empty_file_and_several_writes(harness, inflater):
     P = harness.P
     file, st = harness.encode(b"")
     assert file == EOF and st["members"] == 0
-    data = bamwrite_corpus.stream(True, "sam", 300)[:3 * P + 1000]
-    writes = (1, P - 1, 0, P + 1, 7)
+    data, writes = several_writes_case(P)
     file, st = harness.encode(data, writes)
     check_file(file, data, P, writes, inflater)
     assert st["members"] == 1 + 1 + 0 + 2 + 1 + 2 and file != harness.encode(data)[0]
@@ -231,17 +235,27 @@ def _repeat_at(P, dist):
     return bytes(buf), at
 
 
-def test_every_distance_symbol(harness):
-    """the lowest and highest distance of every distance symbol that fits a member: the token at the repeat is a match at exactly
-    that distance.  A repeat across the member cut is not a match: the next member starts afresh."""
-    P = harness.P
+def symbol_distances(P):
+    """the lowest and highest distance of every distance symbol that fits a member"""
     dists, d = [], 1
     for sym in range(30):
         eb = max(0, sym // 2 - 1)
         dists += [d, d + (1 << eb) - 1]; d += 1 << eb
     # the greatest distance is P - 4, not P - 3: the parse finds a repeat through its 4-byte hash, so the last position that can
     # start one is P - 4, and its farthest source is position 0
-    dists = sorted({min(x, P - 4) for x in dists})
+    return sorted({min(x, P - 4) for x in dists})
+
+
+def member_cut_case(P):
+    block = np.random.default_rng(33).integers(0, 256, P, dtype=np.uint8).tobytes()
+    return block, block + block[-50:]
+
+
+def test_every_distance_symbol(harness):
+    """the lowest and highest distance of every distance symbol that fits a member: the token at the repeat is a match at exactly
+    that distance.  A repeat across the member cut is not a match: the next member starts afresh."""
+    P = harness.P
+    dists = symbol_distances(P)
     assert dists[:12] == [1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 16] and dists[-2:] == [24577, P - 4]
     seen = set()
     for dist in dists:
@@ -254,11 +268,17 @@ def test_every_distance_symbol(harness):
         check_file(file, data, P)
         assert st["stored"] == 0 and st["matches"] >= 1
     assert seen == set(range(30))
-    rng = np.random.default_rng(33)
-    block = rng.integers(0, 256, P, dtype=np.uint8).tobytes()
-    file, st = harness.encode(block + block[-50:])
-    check_file(file, block + block[-50:], P)
+    block, twice = member_cut_case(P)
+    file, st = harness.encode(twice)
+    check_file(file, twice, P)
     assert st["stored"] == 2 and all(l == 1 for _, l, _ in harness.tokens(block[-50:]))
+
+
+def planted_cases():
+    """a repeat of every length 3 .. 258 at a slice start and across a slice end"""
+    rng = np.random.default_rng(34)
+    return {f"len{length}@{at}": _planted(rng, at + length + 9, at, STEP + 11, length)
+            for length in range(3, 259) for at in (2 * STEP, 2 * STEP + SLICE - 3)}
 
 
 def test_every_match_length(harness):
@@ -267,16 +287,13 @@ def test_every_match_length(harness):
     parse: a match ends at the end of its 64-byte slice, so that one lane owns one slice; the planted repeats of those
     lengths are coded as several matches, and gz_len_symbol's upper half is exercised by gzfmt.h's own tests only."""
     P = harness.P
-    rng = np.random.default_rng(34)
     lengths = set()
-    for length in range(3, 259):
-        for at in (2 * STEP, 2 * STEP + SLICE - 3):
-            data = _planted(rng, at + length + 9, at, STEP + 11, length)
-            toks = harness.tokens(data)
-            assert all(p // SLICE == (p + l - 1) // SLICE for p, l, _ in toks)
-            lengths |= {l for _, l, _ in toks if l > 1}
-            file, _ = harness.encode(data)
-            check_file(file, data, P)
+    for data in planted_cases().values():
+        toks = harness.tokens(data)
+        assert all(p // SLICE == (p + l - 1) // SLICE for p, l, _ in toks)
+        lengths |= {l for _, l, _ in toks if l > 1}
+        file, _ = harness.encode(data)
+        check_file(file, data, P)
     assert lengths == set(range(3, SLICE + 1))         # nothing above SLICE: see the docstring
 
 
@@ -302,3 +319,30 @@ def test_size_against_zlib(harness, inflater, paired, kind):
           f"{st['matches']} matches, {st['literals']} literals; zlib Z_RLE {rle}, level 1 {l1}, level 6 {l6}; "
           f"ratio to level 1 {len(file) / l1:.3f}, to level 6 {len(file) / l6:.3f}, to Z_RLE {len(file) / rle:.3f}")
     assert len(file) < rle
+
+
+def digest_sets(P):
+    """name -> (payload, write cuts), or a list of them digested as one: every input the tests above hand to the serial encoder"""
+    sets = {f"inputs/{k}": (v, ()) for k, v in inputs(P).items()}
+    sets["empty"] = (b"", ())
+    data, writes = several_writes_case(P)
+    sets["several_writes"] = (data, writes)
+    sets["several_writes/one_write"] = (data, ())
+    sets["every_distance_symbol"] = [(_repeat_at(P, d)[0], ()) for d in symbol_distances(P)]
+    sets["member_cut"] = (member_cut_case(P)[1], ())
+    sets["every_match_length"] = [(v, ()) for v in planted_cases().values()]
+    for paired, kind in ((True, "sam"), (True, "bam"), (False, "sam"), (False, "bam")):
+        sets[f"corpus/{'paired' if paired else 'single'}.{kind}"] = (bamwrite_corpus.stream(paired, kind), ())
+    return sets
+
+
+def test_serial_file_digests(harness):
+    """the serial encoder still writes the files it wrote when tests/golden/deflate_writer_digests.json was recorded: zlib accepts
+    any valid file, this pins the bytes that tests/test_gpu_bgzw.py compares the device with"""
+    from test_gzwrite_cpu import DIGESTS, stream_digests
+    with open(DIGESTS) as f:
+        want = json.load(f)["bgzf"]
+    got = stream_digests(lambda data, writes: harness.encode(data, writes)[0], digest_sets(harness.P))
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name

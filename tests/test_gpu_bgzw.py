@@ -170,3 +170,37 @@ def test_a_write_of_more_than_one_batch(built, gpu):
     ms = members(file)
     assert len(ms) - 1 == res["n_members"] == -(-n // 32768) > 2048 and res["n_bytes_in"] == n and res["n_bytes_out"] == len(file)
     assert all(len(payload) == 32768 for _, payload in ms[:-2]) and len(ms[-2][1]) == n % 32768
+
+
+def test_gzip_and_bgzf_handles_interleaved(built, gpu, harness, tmp_path):
+    """a gzip handle and a BGZF handle open at once, their writes alternating: both run through the one driver (slotpipe.h), and
+    neither sees the other's buffers, counters or chunk size.  Two writes of 200 000 bytes each (four 64 KB gzip blocks, seven
+    BGZF members with a short last one), the second from a source one byte off alignment; one handle with 4096-byte chunks, which
+    end inside blocks, the other with the default; both ways round.  Each file is its serial encoder's, cut for cut."""
+    import test_gzwrite_cpu as G
+    from sailfish_amd import _lib
+    L = _lib.lib()
+    n = 200_000
+    data = bamwrite_corpus.stream(True, "sam")[:2 * n]
+    srcs = [_dev(data[:n], gpu), _dev(data[n:], gpu, shift=1)]
+    gz_exe = G.build_harness(tmp_path)
+    want = {"gz": G.host_encode(gz_exe, tmp_path, data, writes=(n,))[0], "bgzw": harness.encode(data, (n,))[0]}
+    for chunk in ({"gz": 4096, "bgzw": 0}, {"gz": 0, "bgzw": 4096}):
+        chunks = {"gz": [], "bgzw": []}
+        sinks = {k: _lib.TEXT_SINK(lambda addr, m, _user, k=k: chunks[k].append(bytes((C.c_char * m).from_address(addr))) or 0) for k in chunks}
+        hs = {"gz": C.c_void_p(), "bgzw": C.c_void_p()}
+        assert L.sfgpu_gz_open(C.byref(hs["gz"]), sinks["gz"], None, chunk["gz"]) == _lib.OK
+        assert L.sfgpu_bgzw_open(C.byref(hs["bgzw"]), sinks["bgzw"], None, chunk["bgzw"]) == _lib.OK
+        for t in srcs:
+            assert L.sfgpu_gz_write_device(hs["gz"], _lib.ptr(t), t.numel(), _lib.current_stream_ptr()) == _lib.OK
+            assert L.sfgpu_bgzw_write_device(hs["bgzw"], _lib.ptr(t), t.numel(), _lib.current_stream_ptr()) == _lib.OK
+        res = {"gz": _lib.GzResult(), "bgzw": _lib.BgzwResult()}
+        assert L.sfgpu_gz_close(hs["gz"], C.byref(res["gz"])) == _lib.OK
+        assert L.sfgpu_bgzw_close(hs["bgzw"], C.byref(res["bgzw"])) == _lib.OK
+        for k in chunks:
+            got, r = b"".join(chunks[k]), res[k].as_dict()
+            assert got == want[k], k
+            assert (r["n_bytes_in"], r["n_bytes_out"], r["n_chunks"]) == (2 * n, len(want[k]), len(chunks[k])), k
+            assert max(len(c) for c in chunks[k]) <= (chunk[k] or 1 << 25)
+            assert (len(chunks[k]) > 10) == (chunk[k] == 4096)
+        assert res["gz"].as_dict()["n_blocks"] == 8 and res["bgzw"].as_dict()["n_members"] == 14

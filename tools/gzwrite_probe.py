@@ -10,7 +10,8 @@ zlib level 6 on a slice.  The host path is timed on --host-gibbs / --host-boot s
 it is one sample at a time, so its time is linear in the number of samples.
 
     python tools/gzwrite_probe.py [--out DIR] [--gibbs N] [--boot N] [--reads R] [--encode-only]
-Prints one JSON line.  --encode-only: three device writes of the Gibbs matrix and nothing else (for rocprofv3 --kernel-trace --stats)."""
+Prints one JSON line.  --encode-only: three device writes of the Gibbs matrix and nothing else (for rocprofv3 --kernel-trace --stats,
+and for an A/B of two builds: the line holds every write's result)."""
 import argparse
 import gzip
 import json
@@ -112,9 +113,11 @@ def main():
 
     if a.encode_only:
         mat, _ = sample("gibbs", a.gibbs, None)
+        writes = []
         for _ in range(3):
             w = sf.writer.BootstrapWriter(os.path.join(a.out, "enc"), sopt); w.write_device(mat); w.close()
-        print(json.dumps(w.last_result))
+            writes.append(w.last_result)
+        print(json.dumps(dict(bytes=mat.numel() * mat.element_size(), writes=writes)))
         return
     for kind, n, n_host in (("gibbs", a.gibbs, a.host_gibbs), ("boot", a.boot, a.host_boot)):
         sample(kind, min(n, 8), None)                                   # warm-up

@@ -220,6 +220,17 @@ SFGPU_API int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int f
 SFGPU_API int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads,
                                        uint8_t* d_bases, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span,
                                        sfgpu_reads_result* out, sfgpu_stream stream);
+/* The two parses with the qualities kept: d_qual (16-byte aligned, room for cap_bases bytes; NULL: exactly the calls above).  For a
+ * FASTQ text the qualities of the emitted records are written so that record r's are d_qual[d_off[r] .. d_off[r + 1]) -- the bytes
+ * of line 4r + 3 without its line end or the '\r' of a CRLF end, as many as the record has bases.  For a FASTA text d_qual is not
+ * written.  Everything else -- the cut at max_reads / cap_bases, consumed, the errors, "a call that reports an error emits
+ * nothing" -- is what the call without d_qual gives for the same bytes. */
+SFGPU_API int sfgpu_reads_parse_host_q(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
+                                       uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                       sfgpu_stream stream);
+SFGPU_API int sfgpu_reads_parse_device_q(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads,
+                                         uint8_t* d_bases, uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span,
+                                         sfgpu_reads_result* out, sfgpu_stream stream);
 /* Blocked gzip (BGZF: what bgzip and the Illumina converters write) inflated on the device, one wavefront per member.  The
  * rules live in sailfish_amd/csrc/bgzfmt.h: a member is a gzip member with a 'B','C' extra subfield that holds its size, at
  * most 64 KB of payload, and no match that reaches before its first byte.
@@ -588,8 +599,8 @@ SFGPU_API int sfgpu_bam_close(sfgpu_bam* b);
  * csrc/samwfmt.h (the bytes of samfile._sam_text); the kernels are csrc/samtext_write.hip.  In short, per read in order: a pair
  * record (mate_status 3) gives its 0x40 and its 0x80 line, any other record one line (orphans with 0x8, single-end records
  * without 0x1), 0x100 from the read's second record on; a read without records gives 77 / 141 (paired != 0) or one 4 line.
- * MAPQ 255, CIGAR <len>M or <clip>S<rest>M, QUAL '*'; SEQ is written as given, also on 0x10 lines.  The @HD / @SQ header is the
- * host's business.
+ * MAPQ 255, CIGAR <len>M or <clip>S<rest>M, QUAL '*'; SEQ is written as given, also on 0x10 lines (sfgpu_sam_write_text_q below
+ * writes the qualities and puts 0x10 lines on the reference's strand).  The @HD / @SQ header is the host's business.
  *   d_hits / d_hit_offsets[n_reads + 1]   the batch (uint32 offsets, starting at 0, never decreasing, else SFGPU_ERR_INVALID).
  *   d_ref_names / d_ref_name_off[n_refs + 1]   the transcript names back to back, uint64 offsets (quantfile.names_blob).
  *   d_qnames / d_qname_off[n_reads + 1]   the read names, likewise; d_qname_off == NULL: read r is named r<read_index_base + r>.
@@ -614,7 +625,7 @@ typedef struct {
     uint64_t max_unit_bytes;  /* longest unit, with its '\n's */
     uint64_t error_read;      /* SFGPU_ERR_INVALID with error_kind != 0: the lowest (read, record) that cannot be written */
     uint64_t error_record;
-    uint32_t error_kind;      /* 0 none, 1 no base on the transcript, 2 tid >= n_refs */
+    uint32_t error_kind;      /* 0 none, 1 no base on the transcript, 2 tid >= n_refs, 3 .. 5 sfgpu_sam_write_bgzf's, 6 a quality byte outside '!' .. '~' */
     uint32_t pad_;
     double format_ms;         /* device events: checks, sizing, scans, chunk plan, format kernels of all chunks */
     double d2h_ms;            /* device events around the staged copies */
@@ -625,6 +636,24 @@ SFGPU_API int sfgpu_sam_write_text(const struct sfgpu_hit* d_hits, const uint32_
                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
                                    void* user, sfgpu_samwrite_result* out, sfgpu_stream stream);
+/* sfgpu_sam_write_text with qualities and orientation; sfgpu_sam_write_text is this call with NULL, NULL, 0.
+ *   d_qual1 / d_qual2   the qualities of mate 1 / mate 2 (d_qual2 read only when paired != 0): bytes back to back that share the
+ *            mate's base offsets, so quality r is d_qual1[d_seq1_off[r] .. d_seq1_off[r + 1]).  NULL: QUAL is '*'.  Qualities of a
+ *            mate whose bases are not given (d_seq?_off == NULL) are SFGPU_ERR_INVALID.  QUAL is those bytes on every line that
+ *            carries the mate's SEQ, 0x100 lines and the lines of record-less reads included; a read of 0 bases has an empty QUAL.
+ *            (A 1-base read whose quality byte is '*' reads as "no qualities": the format's ambiguity, written as it is.)
+ *   oriented != 0   a line whose FLAG has 0x10 stores SEQ and QUAL on the reference's strand, as the SAM specification has it: SEQ
+ *            reverse-complemented (A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, either case kept, every other byte as it is),
+ *            QUAL reversed.  Lines without 0x10, every line of a record-less read among them, are as given.
+ * error_kind 6: a quality byte outside '!' .. '~' (33 .. 126) -- a tab or a newline would break the text.  The batch fails like
+ * kinds 1 and 2, before any sink call; the lowest read that holds such a byte is reported as (read, record 0) and merged with
+ * the other kinds by the lowest (read, record), then the lowest kind. */
+SFGPU_API int sfgpu_sam_write_text_q(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
+                                     const uint8_t* d_qual2, int oriented);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
@@ -717,6 +746,16 @@ SFGPU_API int sfgpu_sam_write_bgzf(const struct sfgpu_hit* d_hits, const uint32_
                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                    sfgpu_samwrite_result* out, sfgpu_stream stream);
+/* sfgpu_sam_write_bgzf with the qualities and the orientation of sfgpu_sam_write_text_q, error_kind 6 included; sfgpu_sam_write_bgzf
+ * is this call with NULL, NULL, 0.  SFGPU_SAMW_BAM: QUAL is the quality bytes - 33 (0xff without qualities); on a 0x10 record of an
+ * oriented file the bases are complemented and packed from the last to the first, the qualities reversed: the record
+ * samfile.sam_to_bam makes of the oriented text. */
+SFGPU_API int sfgpu_sam_write_bgzf_q(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
+                                     int oriented);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

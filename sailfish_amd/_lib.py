@@ -226,6 +226,8 @@ _SIGS = {
     "sfgpu_eq_add_text_host": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(EqTextResult)]),
     "sfgpu_reads_parse_host": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_reads_parse_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
+    "sfgpu_reads_parse_host_q": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
+    "sfgpu_reads_parse_device_q": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_bgzf_inflate_host": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_uint64, C.POINTER(BgzfResult), _P]),
     "sfgpu_gzrd_open": (C.c_int, [C.POINTER(_P), C.c_uint32]),
     "sfgpu_gzrd_plan_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(GzrdResult), _P]),
@@ -254,6 +256,8 @@ _SIGS = {
     "sfgpu_bam_close": (C.c_int, [_P]),
     "sfgpu_sam_write_text": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
                                        C.POINTER(SamWriteResult), _P]),
+    "sfgpu_sam_write_text_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
+                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -262,6 +266,8 @@ _SIGS = {
     "sfgpu_bgzw_close": (C.c_int, [_P, C.POINTER(BgzwResult)]),
     "sfgpu_sam_write_bgzf": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
                                        C.POINTER(SamWriteResult), _P]),
+    "sfgpu_sam_write_bgzf_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
+                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

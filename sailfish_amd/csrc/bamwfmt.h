@@ -9,7 +9,10 @@
 //   uint8 l_read_name (QNAME and its NUL)    uint8 mapq 255             uint16 bin     uint16 n_cigar_op   uint16 flag
 //   uint32 l_seq                             int32 next_refID (own tid for '=', else -1)   int32 next_pos (PNEXT - 1)   int32 tlen
 //   QNAME NUL | n_cigar_op words len << 4 | op (S = 4 then M = 0; a line without clip has the M word alone, an unmapped line none)
-//   | SEQ, 4 bits a base, the high nibble first, through =ACMGRSVTWYHKDBN after upper-casing, anything else 15 | l_seq bytes 0xff.
+//   | SEQ, 4 bits a base, the high nibble first, through =ACMGRSVTWYHKDBN after upper-casing, anything else 15
+//   | QUAL, l_seq bytes: 0xff without qualities, else the quality bytes - 33.
+// A record is what sam_to_bam makes of samwfmt.h's line: on a line that samwfmt.h puts on the reference's strand (samw_reversed) the
+// bases are taken from the last to the first and complemented (samw_comp) before they are packed, the qualities are reversed.
 // bin is the specification's reg2bin(pos, pos + max(match, 1)), 4680 when pos < 0.  SEQ '*' (no bases given) is l_seq 0.  TLEN is
 // a frag_len below 2^31 (a larger one is written modulo 2^32; sam_to_bam cannot pack it at all).
 // What BAM cannot say fails the batch like samwfmt.h's kinds 1 and 2, after them where one record breaks several:
@@ -52,6 +55,12 @@ SAMW_HD uint32_t bamw_base_code(uint8_t c) {
 // byte i of the packed SEQ of n bases
 SAMW_HD uint8_t bamw_packed_byte(const uint8_t* seq, uint64_t n, uint64_t i) {
     const uint32_t hi = bamw_base_code(seq[2 * i]), lo = 2 * i + 1 < n ? bamw_base_code(seq[2 * i + 1]) : 0u;
+    return (uint8_t)(hi << 4 | lo);
+}
+
+// byte i of the packed SEQ of the reverse complement of n bases: bases n - 1 - 2i and n - 2 - 2i, low nibble 0 past the start
+SAMW_HD uint8_t bamw_packed_byte_rev(const uint8_t* seq, uint64_t n, uint64_t i) {
+    const uint32_t hi = bamw_base_code(samw_comp(seq[n - 1 - 2 * i])), lo = 2 * i + 1 < n ? bamw_base_code(samw_comp(seq[n - 2 - 2 * i])) : 0u;
     return (uint8_t)(hi << 4 | lo);
 }
 
@@ -130,14 +139,15 @@ SAMW_HD void bamw_put_cigar(const SamwLine& l, Put put) {
 // (read, record) that breaks a rule (a read without records counts as record 0).  Pass 2 (out != nullptr) writes.
 inline int bamw_serial(const SamwArgs& a, uint8_t* out, SamwSerial* res) {
     *res = SamwSerial();
-    for (uint64_t r = 0; r < a.n_reads; ++r) {
+    for (uint64_t r = 0; r < a.n_reads && !res->error_kind; ++r) {
         const uint64_t h0 = a.hit_off[r], h1 = a.hit_off[r + 1];
         for (uint64_t h = h0; h < h1 || (h == h0 && h0 == h1); ++h)
             if (int kind = bamw_check(a, r, h0 == h1 ? nullptr : a.hits + h, h - h0)) {
                 res->error_read = r; res->error_record = h - h0; res->error_kind = kind;
-                return kind;
+                break;
             }
     }
+    if (int kind = samw_merge_qual(a, res)) return kind;
     uint64_t at = 0;
     auto line = [&](const SamwLine& l, uint64_t r, uint32_t tid) {
         const uint64_t len = bamw_line_len(a, l, r), qn = samw_qname_len(a, r);
@@ -150,8 +160,12 @@ inline int bamw_serial(const SamwArgs& a, uint8_t* out, SamwSerial* res) {
             else { samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { p[i] = (uint8_t)ch; }); p += qn; }
             *p++ = 0;
             bamw_put_cigar(l, [&](int i, uint8_t b) { p[i] = b; }); p += 4 * bamw_cigar_ops(l);
-            for (uint64_t i = 0; i < (n + 1) / 2; ++i) *p++ = bamw_packed_byte(s, n, i);
-            for (uint64_t i = 0; i < n; ++i) *p++ = 0xff;
+            const bool rev = samw_reversed(a, l);
+            for (uint64_t i = 0; i < (n + 1) / 2; ++i) *p++ = rev ? bamw_packed_byte_rev(s, n, i) : bamw_packed_byte(s, n, i);
+            const uint8_t* q;
+            uint64_t ql;
+            const bool given = samw_qual(a, l, r, &q, &ql);
+            for (uint64_t i = 0; i < n; ++i) *p++ = given ? (uint8_t)((rev ? q[n - 1 - i] : q[i]) - 33u) : (uint8_t)0xff;
         }
         at += len;
         res->n_lines++;

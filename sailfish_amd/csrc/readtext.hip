@@ -15,7 +15,9 @@
 //   k_reads_emit        one lane per record: d_off, the name span
 //   k_reads_compact     one block per 4 KB tile of the packed bases: each lane finds the line its 16 output bytes begin in by
 //                       binary search in dst, gathers them (one unaligned 16-byte read when they lie in one line, byte by byte
-//                       across line ends) and issues one 16-byte store
+//                       across line ends) and issues one 16-byte store.  The qualities of a FASTQ text (the _q entries) are a
+//                       second run of the same kernel with the line selector 2: a record's quality line lies two lines behind
+//                       its sequence line and is of the same length (readfmt.h checks that), so dst says where its bytes go
 #include "common.h"
 #include "primitives.h"
 #include "readfmt.h"
@@ -138,7 +140,9 @@ __device__ inline uint4 load_unaligned16(const uint4* __restrict__ buf, uint32_t
     return v;
 }
 
-// lines [0, Lc) carry the n_bases bases of the emitted records; dst[Lc] = n_bases
+// lines [0, Lc) carry the n_bases bases of the emitted records; dst[Lc] = n_bases.  SEL = 0 gathers the bases; SEL = 2 (FASTQ)
+// the bytes of the line two behind each line that carries bases: the qualities, to the same places
+template <uint32_t SEL>
 __global__ void __launch_bounds__(kBlock) k_reads_compact(const uint4* __restrict__ buf, uint32_t Lc, uint32_t n_bases,
                                                           const uint32_t* __restrict__ line_end, const uint32_t* __restrict__ dst,
                                                           uint4* __restrict__ out) {
@@ -152,7 +156,7 @@ __global__ void __launch_bounds__(kBlock) k_reads_compact(const uint4* __restric
         if (dst[mid] <= o) lo = mid; else hi = mid;
     }
     uint32_t i = lo;
-    uint32_t src = (i ? line_end[i - 1] + 1 : 0) + (o - dst[i]);
+    uint32_t src = (i + SEL ? line_end[i + SEL - 1] + 1 : 0) + (o - dst[i]);
     uint32_t avail = dst[i + 1] - o;
     if (avail >= 16u) {                                      // (then cnt == 16)
         out[o >> 4] = load_unaligned16(buf, src);
@@ -162,7 +166,7 @@ __global__ void __launch_bounds__(kBlock) k_reads_compact(const uint4* __restric
     for (uint32_t k = 0; k < cnt;) {
         if (avail == 0) {                                    // on to the next line that carries bases (there is one: k < cnt)
             ++i;
-            src = line_end[i - 1] + 1;
+            src = line_end[i + SEL - 1] + 1;
             avail = dst[i + 1] - dst[i];
             continue;
         }
@@ -200,7 +204,7 @@ struct ReadScratch {
 // after_counts() runs behind the first wait for st (the host entry reads the times of its staged copies there).
 template <typename AfterCounts>
 int parse_counted(ReadScratch& S, const uint4* text, uint64_t n_bytes, int format, int final, uint64_t max_reads, uint8_t* d_bases,
-                  uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out, hipStream_t st, hipEvent_t* ev_p,
+                  uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out, hipStream_t st, hipEvent_t* ev_p,
                   unsigned long long* h_res, AfterCounts after_counts) {
     const uint64_t n_groups = (n_bytes + 1 + 15) / 16;
     // ---- lines
@@ -248,9 +252,14 @@ int parse_counted(ReadScratch& S, const uint4* text, uint64_t n_bytes, int forma
                            d_off, d_name_span);
         SF_HIP(hipGetLastError());
         if (n_bases) {
-            hipLaunchKernelGGL(k_reads_compact, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, text, Lc, n_bases,
+            hipLaunchKernelGGL(k_reads_compact<0>, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, text, Lc, n_bases,
                                S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_bases));
             SF_HIP(hipGetLastError());
+            if (d_qual && format == SFGPU_READS_FASTQ) {
+                hipLaunchKernelGGL(k_reads_compact<2>, dim3((n_bases + kTileBytes - 1) / kTileBytes), dim3(kBlock), 0, st, text, Lc, n_bases,
+                                   S.line_end.p, S.dst.p, reinterpret_cast<uint4*>(d_qual));
+                SF_HIP(hipGetLastError());
+            }
         }
         out->n_reads = R; out->n_bases = n_bases; out->consumed = h_res[3];
     }
@@ -270,6 +279,12 @@ using namespace sfgpu;
 extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
                                       uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
                                       sfgpu_stream stream) {
+    return sfgpu_reads_parse_host_q(h_text, n_bytes, final, max_reads, d_bases, nullptr, cap_bases, d_off, d_name_span, out, stream);
+}
+
+extern "C" int sfgpu_reads_parse_host_q(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
+                                        uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                        sfgpu_stream stream) {
     SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null result");
     memset(out, 0, sizeof(*out));
     out->error_record = ~0ull; out->error_line = ~0ull;
@@ -277,6 +292,7 @@ extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int 
     SF_REQUIRE(n_bytes == 0 || h_text, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null text");
     SF_REQUIRE(d_off && (d_bases || cap_bases == 0), SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: null output");
     SF_REQUIRE((reinterpret_cast<uintptr_t>(d_bases) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: d_bases must be 16-byte aligned");
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_qual) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_host: d_qual must be 16-byte aligned");
     final = final ? 1 : 0;
     hipStream_t st = as_stream(stream);
     SF_HIP(hipMemsetAsync(d_off, 0, sizeof(int64_t), st));
@@ -358,13 +374,19 @@ extern "C" int sfgpu_reads_parse_host(const char* h_text, uint64_t n_bytes, int 
         in_flight[slot] = true;
     }
 
-    return parse_counted(S, S.text.p, n_bytes, format, final, max_reads, d_bases, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
+    return parse_counted(S, S.text.p, n_bytes, format, final, max_reads, d_bases, d_qual, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
                          [&]() { collect(0); collect(1); });
 }
 
 extern "C" int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads, uint8_t* d_bases,
                                         uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
                                         sfgpu_stream stream) {
+    return sfgpu_reads_parse_device_q(d_text, n_bytes, cap_text, final, max_reads, d_bases, nullptr, cap_bases, d_off, d_name_span, out, stream);
+}
+
+extern "C" int sfgpu_reads_parse_device_q(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads, uint8_t* d_bases,
+                                          uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, sfgpu_reads_result* out,
+                                          sfgpu_stream stream) {
     SF_REQUIRE(out, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null result");
     memset(out, 0, sizeof(*out));
     out->error_record = ~0ull; out->error_line = ~0ull;
@@ -372,6 +394,7 @@ extern "C" int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint6
     SF_REQUIRE(n_bytes == 0 || d_text, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null text");
     SF_REQUIRE(d_off && (d_bases || cap_bases == 0), SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: null output");
     SF_REQUIRE((reinterpret_cast<uintptr_t>(d_bases) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: d_bases must be 16-byte aligned");
+    SF_REQUIRE((reinterpret_cast<uintptr_t>(d_qual) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: d_qual must be 16-byte aligned");
     SF_REQUIRE((reinterpret_cast<uintptr_t>(d_text) & 15u) == 0, SFGPU_ERR_INVALID, "sfgpu_reads_parse_device: d_text must be 16-byte aligned");
     const uint64_t n1 = n_bytes + 1, n_groups = (n1 + 15) / 16, padded = 16 * n_groups + 16;
     SF_REQUIRE(n_bytes == 0 || cap_text >= padded, SFGPU_ERR_INVALID,
@@ -423,6 +446,6 @@ extern "C" int sfgpu_reads_parse_device(uint8_t* d_text, uint64_t n_bytes, uint6
     hipLaunchKernelGGL(k_reads_count, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, (uint64_t)0, n_groups, S.nl_cnt.p);
     SF_HIP(hipGetLastError());
     SF_HIP(hipEventRecord(ev_c1, st));
-    return parse_counted(S, text, n_bytes, format, final, max_reads, d_bases, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
+    return parse_counted(S, text, n_bytes, format, final, max_reads, d_bases, d_qual, cap_bases, d_off, d_name_span, out, st, ev_p, h_res,
                          [&]() { add_elapsed(&out->ms_kernels, ev_c0, ev_c1); });
 }

@@ -3,7 +3,7 @@
 // samtext_write.hip runs the same functions inside its kernels (WHERE a line lies in the output and which lines a tile holds is
 // found in parallel there; WHAT a line says is decided here), and tests/samwrite_harness.cpp runs them alone (samw_serial below).
 //
-// A line is   QNAME \t FLAG \t RNAME \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t SEQ \t * \n
+// A line is   QNAME \t FLAG \t RNAME \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t SEQ \t QUAL \n
 // and a UNIT is what one hit record or one read without records produces; units follow each other in read order, a read's
 // records in their order.
 //   pair record (mate_status 3): two lines.  FLAG 0x1|0x2|0x40|sec|(fwd ? 0 : 0x10)|(mate_fwd ? 0 : 0x20), then the mirrored 0x80
@@ -17,10 +17,18 @@
 //          CIGAR '*', RNEXT '*', PNEXT 0, TLEN 0.
 //   POS and CIGAR of a read of len bases at pos: pos >= 0 gives pos + 1 and <len>M; pos < 0 gives 1 and <-pos>S<len + pos>M, and
 //          -pos >= len is an error (no base lies on the transcript: SAM cannot say that), as is tid >= n_refs.
-//   MAPQ is 255, QUAL '*'.  QNAME is the caller's bytes, or r<global read index> when none are given; SEQ is the caller's bytes, or
-//   '*' when none are given; RNAME is the transcript's name.  These bytes are copied, never inspected.
-// The SEQ of a 0x10 line is written as given, NOT reverse-complemented: that is the contract of _sam_text as it stands, and the
-// reader (samfmt.h) takes only SEQ's length.
+//   MAPQ is 255.  QNAME is the caller's bytes, or r<global read index> when none are given; SEQ is the caller's bytes, or '*' when
+//   none are given; RNAME is the transcript's name.  Names are copied, never inspected.
+//   QUAL is '*' unless the mate's qualities are given (qual1 / qual2: bytes back to back that share the mate's base offsets, so
+//          they can only be given with the bases): then it is those bytes, on every line that carries the mate's SEQ (0x100 lines and
+//          the 77 / 141 / 4 lines too); a read of 0 bases has an empty QUAL as it has an empty SEQ.  Every quality byte must lie in
+//          '!' .. '~' (a tab or a newline would break the text; BAM stores byte - 33): a read that holds another one fails the batch
+//          as (read, record 0) of kind SAMW_BAD_QUAL, merged with the other kinds by lowest (read, record), then lowest kind.  One
+//          quality byte '*' of a 1-base read reads as "no qualities": the format's ambiguity, written as it is.
+//   Orientation: with `oriented` == 0 SEQ and QUAL are written as given on every line (the reader, samfmt.h, takes only SEQ's
+//          length).  With `oriented` != 0 a line whose FLAG has 0x10 stores them on the reference's strand, as the SAM
+//          specification has it: SEQ reverse-complemented (samw_comp, byte by byte), QUAL reversed.  Lines without 0x10 -- every
+//          line of a read without records among them -- are as given.
 #pragma once
 #include <cstdint>
 
@@ -35,10 +43,27 @@
 
 namespace sfgpu {
 
-constexpr uint32_t kSamwTail = 3;                 // \t * \n behind SEQ
+constexpr uint32_t kSamwTail = 2;                 // \t and \n around QUAL
 // (the head \t FLAG \t is at most 5 bytes: the largest FLAG is 0x1b3 = 435; the middle \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
 // at most 54: 65535S65535M, -4294967295)
-enum { SAMW_OK = 0, SAMW_BAD_POS = 1, SAMW_BAD_TID = 2 };
+enum { SAMW_OK = 0, SAMW_BAD_POS = 1, SAMW_BAD_TID = 2, SAMW_BAD_QUAL = 6 };     // (3 .. 5 are bamwfmt.h's)
+
+// the complement of a base: A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, in either case (kept); S, W, N and every other byte as it is
+SAMW_HD uint8_t samw_comp(uint8_t c) {
+    const uint8_t low = (c >= 'a' && c <= 'z') ? 0x20 : 0;
+    uint8_t v;
+    switch ((uint8_t)(c - low)) {
+        case 'A': v = 'T'; break;  case 'T': v = 'A'; break;  case 'U': v = 'A'; break;
+        case 'C': v = 'G'; break;  case 'G': v = 'C'; break;
+        case 'R': v = 'Y'; break;  case 'Y': v = 'R'; break;
+        case 'K': v = 'M'; break;  case 'M': v = 'K'; break;
+        case 'B': v = 'V'; break;  case 'V': v = 'B'; break;
+        case 'D': v = 'H'; break;  case 'H': v = 'D'; break;
+        default: return c;
+    }
+    return (uint8_t)(v + low);
+}
+SAMW_HD bool samw_qual_ok(uint8_t q) { return q >= 33 && q <= 126; }
 
 // what one line says, names and SEQ apart
 struct SamwLine {
@@ -163,7 +188,9 @@ SAMW_HD void samw_put_mid(const SamwLine& l, Put put) {
 
 // ---- the arrays of one write call, and the serial statement over them ---------------------------------------------------------
 // What sfgpu_sam_write_text takes (include/sfgpu.h): names and SEQ as bytes back to back with n + 1 offsets; qname_off == nullptr
-// stands for r<read_index_base + r>, seq1_off / seq2_off == nullptr for '*'.
+// stands for r<read_index_base + r>, seq1_off / seq2_off == nullptr for '*'.  qual1 / qual2 (sfgpu_sam_write_text_q): the mate's
+// qualities at its base offsets, nullptr for '*'; oriented: 0x10 lines on the reference's strand.  (Appended with defaults: the
+// callers of the entries without them brace-initialise the rest.)
 struct SamwArgs {
     const sfgpu_hit* hits;
     const uint32_t* hit_off;
@@ -179,6 +206,9 @@ struct SamwArgs {
     const uint8_t* seq2;
     const int64_t* seq2_off;
     uint64_t read_index_base;
+    const uint8_t* qual1 = nullptr;
+    const uint8_t* qual2 = nullptr;
+    int oriented = 0;
 };
 
 SAMW_HD uint64_t samw_qname_len(const SamwArgs& a, uint64_t r) {
@@ -197,11 +227,24 @@ SAMW_HD bool samw_seq(const SamwArgs& a, const SamwLine& l, uint64_t r, const ui
     if (*len) *seq = s + o[r];
     return true;
 }
+// QUAL of the line of read r: false and 1 byte for '*', else the qualities, as many as the bases
+SAMW_HD bool samw_qual(const SamwArgs& a, const SamwLine& l, uint64_t r, const uint8_t** qual, uint64_t* len) {
+    const uint8_t* q = l.mate2 ? a.qual2 : a.qual1;
+    const int64_t* o = l.mate2 ? a.seq2_off : a.seq1_off;
+    *qual = nullptr; *len = 1;
+    if (!q || !o) return false;
+    *len = (uint64_t)(o[r + 1] - o[r]);
+    *qual = q + o[r];
+    return true;
+}
+// SEQ and QUAL of the line go on the reference's strand
+SAMW_HD bool samw_reversed(const SamwArgs& a, const SamwLine& l) { return a.oriented != 0 && (l.flag & 0x10u) != 0; }
 SAMW_HD uint64_t samw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t tid) {
-    const uint8_t* seq;
-    uint64_t sl;
-    (void)samw_seq(a, l, r, &seq, &sl);
-    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + kSamwTail;
+    const uint8_t* p;
+    uint64_t sl, ql;
+    (void)samw_seq(a, l, r, &p, &sl);
+    (void)samw_qual(a, l, r, &p, &ql);
+    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail;
 }
 // the bytes of unit (read r, record h of rank `rank`; h == nullptr: the read has no record)
 SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
@@ -219,14 +262,42 @@ struct SamwSerial {
     int error_kind = 0;
 };
 
+// the lowest read with a quality byte outside '!' .. '~' (one flat pass over each mate's bytes; every read is written at least
+// once), or n_reads
+inline uint64_t samw_bad_qual_read(const SamwArgs& a) {
+    uint64_t worst = a.n_reads;
+    for (int m = 0; m < 2; ++m) {
+        const uint8_t* q = m ? a.qual2 : a.qual1;
+        const int64_t* o = m ? a.seq2_off : a.seq1_off;
+        if (!q || !o) continue;
+        for (int64_t i = o[0]; i < o[a.n_reads]; ++i)
+            if (!samw_qual_ok(q[i])) {
+                uint64_t r = 0;
+                while (o[r + 1] <= i) ++r;
+                if (r < worst) worst = r;
+                break;
+            }
+    }
+    return worst;
+}
+// the error of the records (kind 0: none) merged with the quality rule: lowest (read, record), then lowest kind
+inline int samw_merge_qual(const SamwArgs& a, SamwSerial* res) {
+    const uint64_t r = samw_bad_qual_read(a);
+    if (r < a.n_reads && (!res->error_kind || r < res->error_read || (r == res->error_read && res->error_record > 0))) {
+        res->error_read = r; res->error_record = 0; res->error_kind = SAMW_BAD_QUAL;
+    }
+    return res->error_kind;
+}
+
 inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
     *res = SamwSerial();
-    for (uint64_t r = 0; r < a.n_reads; ++r)
+    for (uint64_t r = 0; r < a.n_reads && !res->error_kind; ++r)
         for (uint64_t h = a.hit_off[r]; h < a.hit_off[r + 1]; ++h)
             if (int kind = samw_check(a.hits[h], a.n_refs)) {
                 res->error_read = r; res->error_record = h - a.hit_off[r]; res->error_kind = kind;
-                return kind;
+                break;
             }
+    if (int kind = samw_merge_qual(a, res)) return kind;
     uint64_t at = 0;
     auto line = [&](const SamwLine& l, uint64_t r, uint32_t tid) {
         const uint64_t len = samw_line_len(a, l, r, tid);
@@ -240,9 +311,13 @@ inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
             samw_put_mid(l, [&](int i, char ch) { p[i] = ch; }); p += samw_mid_len(l);
             const uint8_t* s;
             uint64_t sl;
-            if (samw_seq(a, l, r, &s, &sl)) for (uint64_t i = 0; i < sl; ++i) *p++ = (char)s[i];
+            const bool rev = samw_reversed(a, l);
+            if (samw_seq(a, l, r, &s, &sl)) for (uint64_t i = 0; i < sl; ++i) *p++ = (char)(rev ? samw_comp(s[sl - 1 - i]) : s[i]);
             else *p++ = '*';
-            *p++ = '\t'; *p++ = '*'; *p++ = '\n';
+            *p++ = '\t';
+            if (samw_qual(a, l, r, &s, &sl)) for (uint64_t i = 0; i < sl; ++i) *p++ = (char)(rev ? s[sl - 1 - i] : s[i]);
+            else *p++ = '*';
+            *p++ = '\n';
         }
         at += len;
         res->n_lines++;

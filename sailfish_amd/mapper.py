@@ -108,38 +108,43 @@ def hits_to_numpy(hits, offsets):
     return hits.cpu().numpy().view(HIT_DTYPE), offsets.cpu().numpy().view(np.uint32)
 
 
-def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam"):
+def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", oriented=False):
     """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
     if write_mappings is None:
         return None
     from .samfile import SamDeviceWriter
-    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format)
+    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format, oriented=oriented)
 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   write_mappings=None, mappings_format="sam", **kw):
+                   write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
     is quantified: QNAME r<index of the read>, SEQ the read's bases; the estimates do not depend on it.  mappings_format is
     SamDeviceWriter's `format` ("sam"; "sam.gz" for the text, "bam" for BAM records, in BGZF members encoded on the device); it is never
-    inferred from the path.
+    inferred from the path.  quals1 / quals2: the reads' qualities (lists like reads1 / reads2, of as many bytes a read as it has
+    bases), written as QUAL; default '*'.  mappings_oriented=True puts the lines with 0x10 on the transcript's strand, as the SAM
+    specification stores them (SEQ reverse-complemented, QUAL reversed): the file other tools expect.
     -> (rc, experiment)"""
     from . import quant
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
-    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format)
+    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented)
 
     def batches():
         for a in range(0, n, batch_reads):
             b = min(n, a + batch_reads)
             r1, r2 = reads1[a:b], None if reads2 is None else reads2[a:b]
+            q1 = q2 = None
             if sam is not None:                              # the bases are wanted on the device beyond the mapper's call
                 r1 = tuple(t.to(idx.device) for t in pack_sequences(r1))
                 r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
+                q1 = None if quals1 is None else pack_sequences(quals1[a:b])[0].to(idx.device)
+                q2 = None if quals2 is None or r2 is None else pack_sequences(quals2[a:b])[0].to(idx.device)
             h, o = idx.map_reads(r1, r2)
             if sam is not None:
-                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2))
+                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
             yield h, o
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
@@ -164,21 +169,24 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", write_mappings=None, mappings_format="sam", **kw):
+                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
     write_mappings and mappings_format as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names are
-    sliced and packed on the host: ReadFile(names=True)).  -> (rc, experiment)"""
+    sliced and packed on the host: ReadFile(names=True)).  mappings_oriented=True writes the file other tools expect: the read files are
+    opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
+    reverse-complemented and QUAL reversed.  -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, read_transcripts
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
-    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format)
+    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented)
+    keep = sam is not None and bool(mappings_oriented)
 
     def batches():
-        f1 = ReadFile(reads1_path, device, names=sam is not None, inflate=inflate)
-        f2 = None if reads2_path is None else ReadFile(reads2_path, device, inflate=inflate)
+        f1 = ReadFile(reads1_path, device, names=sam is not None, inflate=inflate, quals=keep)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device, inflate=inflate, quals=keep)
         try:
             while True:
                 r1 = f1.read(batch_reads)
@@ -190,7 +198,9 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                     break
                 h, o = idx.map_reads(r1, r2)
                 if sam is not None:
-                    sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2))
+                    q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals
+                    sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
+                              quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
                 yield h, o
         finally:
             f1.close()

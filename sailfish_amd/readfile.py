@@ -303,6 +303,8 @@ class ReadFile:
 
     read(max_reads) -> (bases: uint8 device tensor, offsets: int64 device tensor [n + 1]) holding exactly max_reads records unless
     the file ends first (n == 0 at the end).  With names=True the record names (bytes) of the last read() are in `last_names`.
+    With quals=True the qualities of the last read() are in `last_quals`: a uint8 device tensor that shares the bases' offsets
+    (record r's are last_quals[offsets[r]:offsets[r + 1]], the bytes of its quality line), or None for a FASTA file.
     `inflate` says where a gzip file is inflated: "auto" takes the device for a BGZF file (its first member carries the 'BC'
     subfield) and the host for any other gzip file, "host" forces Python's gzip, "device" takes the device for every gzip file
     (a BGZF file member by member, any other chunk by chunk: DeviceGunzip); the attribute `inflate` is "device", "host" or None (a
@@ -310,7 +312,7 @@ class ReadFile:
     an ordinary gzip file on the device, the chunks decoded, the block starts the finder accepted (candidates) and those of them
     that the chain did not reach (false_starts); ms_inflate is there ms_decode (pass A) + ms_emit (pass B)."""
 
-    def __init__(self, path, device="cuda", block_bytes=32 << 20, names=False, inflate="auto"):
+    def __init__(self, path, device="cuda", block_bytes=32 << 20, names=False, inflate="auto", quals=False):
         if inflate not in ("auto", "host", "device"):
             raise ValueError("inflate must be 'auto', 'host' or 'device'")
         self.path = str(path)
@@ -323,6 +325,8 @@ class ReadFile:
         self.inflate = None if not self.gzipped else "device" if inflate == "device" or (inflate == "auto" and bgzf) else "host"
         self._names = bool(names)
         self.last_names = []
+        self._quals = bool(quals)
+        self.last_quals = None
         self.format = 0
         self.stats = dict(calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0, ms_inflate=0.0, bytes_compressed=0, members=0,
                           chunks=0, candidates=0, false_starts=0, ms_find=0.0, ms_decode=0.0, ms_propagate=0.0, ms_emit=0.0)
@@ -339,10 +343,11 @@ class ReadFile:
         bases = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
         off = torch.empty(max_reads + 1, dtype=torch.int64, device=self.device)
         span = torch.empty(2 * max_reads, dtype=torch.int64, device=self.device) if self._names else None
+        qual = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device) if self._quals else None
         res = _lib.ReadsResult()
         with torch.cuda.device(self.device):
-            rc = self._L.sfgpu_reads_parse_host(_lib.ptr(text), n, int(final), max_reads, _lib.ptr(bases), n, _lib.ptr(off), _lib.ptr(span),
-                                                C.byref(res), _lib.current_stream_ptr())
+            rc = self._L.sfgpu_reads_parse_host_q(_lib.ptr(text), n, int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n, _lib.ptr(off),
+                                                  _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
         if rc == _lib.ERR_FORMAT:
             raise ValueError(f"{self.path}: record {self._carry.records + res.error_record} is malformed: "
                              f"{KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
@@ -358,7 +363,7 @@ class ReadFile:
         off = off[: res.n_reads + 1]
         if 2 * off.numel() < max_reads:                        # a batch must not pin an array sized for the records that might have been
             off = off.clone()
-        return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names))
+        return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names, qual[: res.n_bases] if self._kept(res, qual) else None))
 
     def _parse_device(self, text, lo, hi, final, max_reads, records):
         """_parse for text[lo:hi] of a device buffer (lo is a multiple of 16 or the text is moved there first by the caller)"""
@@ -371,10 +376,11 @@ class ReadFile:
             bases = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
             off = torch.empty(max_reads + 1, dtype=torch.int64, device=self.device)
             span = torch.empty(2 * max_reads, dtype=torch.int64, device=self.device) if self._names else None
+            qual = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device) if self._quals else None
             res = _lib.ReadsResult()
             view = text[lo:]
-            rc = self._L.sfgpu_reads_parse_device(_lib.ptr(view), n, view.numel(), int(final), max_reads, _lib.ptr(bases), n, _lib.ptr(off),
-                                                  _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
+            rc = self._L.sfgpu_reads_parse_device_q(_lib.ptr(view), n, view.numel(), int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n,
+                                                    _lib.ptr(off), _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
         if rc == _lib.ERR_FORMAT:
             raise ValueError(f"{self.path}: record {records + res.error_record} is malformed: "
                              f"{KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
@@ -394,7 +400,12 @@ class ReadFile:
         off = off[: res.n_reads + 1]
         if 2 * off.numel() < max_reads:
             off = off.clone()
-        return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names))
+        return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names, qual[: res.n_bases] if self._kept(res, qual) else None))
+
+    @staticmethod
+    def _kept(res, qual):
+        """the parse wrote the qualities: they were asked for and the text is FASTQ"""
+        return qual is not None and res.format == 2            # SFGPU_READS_FASTQ
 
     def read(self, max_reads):
         parts, left = [], int(max_reads)
@@ -405,13 +416,15 @@ class ReadFile:
             parts.append(res.payload)
             left -= res.n_reads
         self.last_names = [nm for p in parts for nm in (p[2] or [])]
+        kept = [p[3] for p in parts if p[3] is not None]
+        self.last_quals = (kept[0] if len(kept) == 1 else torch.cat(kept)) if kept and len(kept) == len(parts) else None
         if not parts:
             return torch.zeros(1, dtype=torch.uint8, device=self.device), torch.zeros(1, dtype=torch.int64, device=self.device)
         if len(parts) == 1:
             return parts[0][0], parts[0][1]
         acc = parts[0][1][-1]                                  # the rebasing stays on the device
         offs = [parts[0][1]]
-        for b, o, _ in parts[1:]:
+        for b, o, _, _ in parts[1:]:
             offs.append(o[1:] + acc)
             acc = acc + o[-1]
         return torch.cat([p[0] for p in parts]), torch.cat(offs)

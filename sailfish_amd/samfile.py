@@ -455,48 +455,86 @@ def _aligned(pos, length, what):
     return 1, b"%dS%dM" % (-pos, length + pos)
 
 
-def _sam_text(names, ref_len, hits, offsets, read_names, seqs):
-    """the text write_sam writes"""
+# the complement of csrc/samwfmt.h's samw_comp: the bytes named change, in either case; S, W, N and every other byte stay
+_COMP = bytes.maketrans(b"ACGTURYKMBDHVacgturykmbdhv", b"TGCAAYRMKVHDBtgcaayrmkvhdb")
+
+
+def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False):
+    """the text write_sam writes.  quals: per read the quality bytes (single end) or a (mate 1, mate 2) pair, a mate's None for
+    "not given" (QUAL '*'); they go with the mate's SEQ on every line.  oriented: a line with 0x10 carries SEQ reverse-complemented
+    and QUAL reversed.  The rules are stated in csrc/samwfmt.h."""
+    if quals is not None and seqs is None:
+        raise ValueError("qualities of reads whose bases are not given")
     hits = np.asarray(hits).view(HIT_DTYPE).reshape(-1)
     off = np.asarray(offsets).astype(np.int64)
     paired = bool((hits["mate_status"] != 0).any()) if len(hits) else bool(seqs and isinstance(seqs[0], tuple))
     nm = _name_bytes(names)
     out = [b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n"]
     out += [b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(nm, ref_len)]
-    line = b"%s\t%d\t%s\t%d\t255\t%s\t%s\t%d\t%d\t%s\t*\n"
+    fmt = b"%s\t%d\t%s\t%d\t255\t%s\t%s\t%d\t%d\t%s\t%s\n"
+
+    def line(q, flag, rname, p, cigar, rnext, pnext, tlen, sq):
+        """sq: the mate's (SEQ, QUAL or None)"""
+        s, ql = sq
+        if ql is None:
+            ql = b"*"
+        if oriented and flag & 0x10:
+            s, ql = (s if s == b"*" and seqs is None else s.translate(_COMP)[::-1]), (ql if sq[1] is None else ql[::-1])
+        return fmt % (q, flag, rname, p, cigar, rnext, pnext, tlen, s, ql)
+
+    def check_quals(r, mates):
+        """QUAL_WRITE_KINDS 6, reported as record 0 of the read: behind a record 0 that breaks another rule, in front of any later record"""
+        for _, ql in mates:
+            if ql is not None and any(not 33 <= c <= 126 for c in ql):
+                raise ValueError(f"read {r}, record 0: {QUAL_WRITE_KINDS[6]}")
+
     for r in range(len(off) - 1):
         q = _name_bytes([read_names[r]])[0] if read_names is not None else b"r%d" % r
         s = seqs[r] if seqs is not None else (b"*", b"*") if paired else b"*"
         s1, s2 = s if paired else (s, None)
+        k = quals[r] if quals is not None else (None, None) if paired else None
+        k1, k2 = k if paired else (k, None)
+        for sq, ql in ((s1, k1), (s2, k2)):
+            if ql is not None and len(ql) != len(sq):
+                raise ValueError(f"read {r}: {len(ql)} qualities for {len(sq)} bases")
+        s1, s2 = (s1, k1), (s2, k2)
         recs = hits[off[r]:off[r + 1]].tolist()
         if not recs:
-            out.append(line % (q, 77, b"*", 0, b"*", b"*", 0, 0, s1) + line % (q, 141, b"*", 0, b"*", b"*", 0, 0, s2) if paired
-                       else line % (q, 4, b"*", 0, b"*", b"*", 0, 0, s1))
+            check_quals(r, (s1, s2))
+            out.append(line(q, 77, b"*", 0, b"*", b"*", 0, 0, s1) + line(q, 141, b"*", 0, b"*", b"*", 0, 0, s2) if paired
+                       else line(q, 4, b"*", 0, b"*", b"*", 0, 0, s1))
         for i, (tid, pos, mpos, frag, rlen, mlen, fwd, mfwd, status, _) in enumerate(recs):
             sec = 0x100 if i else 0
             what = f"read {r}, record {i}"
             p1, c1 = _aligned(pos, rlen, what)
             if status == 3:
                 p2, c2 = _aligned(mpos, mlen, what)
+            rname = nm[tid]
+            if i == 0:
+                check_quals(r, (s1, s2))
+            if status == 3:
                 tlen = frag if pos <= mpos else -frag
-                out.append(line % (q, 0x1 | 0x2 | 0x40 | sec | (0 if fwd else 0x10) | (0 if mfwd else 0x20), nm[tid], p1, c1, b"=", p2, tlen, s1))
-                out.append(line % (q, 0x1 | 0x2 | 0x80 | sec | (0 if mfwd else 0x10) | (0 if fwd else 0x20), nm[tid], p2, c2, b"=", p1, -tlen, s2))
+                out.append(line(q, 0x1 | 0x2 | 0x40 | sec | (0 if fwd else 0x10) | (0 if mfwd else 0x20), rname, p1, c1, b"=", p2, tlen, s1))
+                out.append(line(q, 0x1 | 0x2 | 0x80 | sec | (0 if mfwd else 0x10) | (0 if fwd else 0x20), rname, p2, c2, b"=", p1, -tlen, s2))
             elif status:
-                out.append(line % (q, 0x1 | 0x8 | (0x40 if status == 1 else 0x80) | sec | (0 if fwd else 0x10), nm[tid], p1, c1, b"*", 0, 0,
-                                   s1 if status == 1 else s2))
+                out.append(line(q, 0x1 | 0x8 | (0x40 if status == 1 else 0x80) | sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0,
+                                s1 if status == 1 else s2))
             else:
-                out.append(line % (q, sec | (0 if fwd else 0x10), nm[tid], p1, c1, b"*", 0, 0, s1))
+                out.append(line(q, sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0, s1))
     return b"".join(out)
 
 
-def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False):
+def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False):
     """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
     line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
     a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
-    `seqs` gives, per read, the bases (single end) or a (mate 1, mate 2) pair, written as given.  `read_names`: per read, default
+    `seqs` gives, per read, the bases (single end) or a (mate 1, mate 2) pair; QUAL is '*' unless `quals` gives the qualities the
+    same way (a mate's None: not given).  Both are written as given unless `oriented`: then a line with 0x10 carries SEQ
+    reverse-complemented and QUAL reversed, as the SAM specification stores them.  A quality byte outside '!' .. '~' is a ValueError
+    (QUAL_WRITE_KINDS); a 1-base read whose quality is '*' reads as "no qualities", the format's ambiguity.  `read_names`: per read, default
     r<index>.  The library is taken as paired when any record is, or, without records, when seqs holds pairs.  bgzf=True writes
     blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan."""
-    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs)
+    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented)
     if bgzf:
         from . import gzfile
         gzfile.write_bgzf(path, data)
@@ -505,11 +543,12 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
             f.write(data)
 
 
-def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280):
+def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False):
     """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
     members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf)."""
     from . import gzfile
-    gzfile.write_bgzf(path, sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs)), member_bytes=member_bytes)
+    gzfile.write_bgzf(path, sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented)),
+                      member_bytes=member_bytes)
 
 
 # ---- the way back, on the device ------------------------------------------------------------------------------------------
@@ -518,6 +557,8 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
 WRITE_FORMATS = ("sam", "sam.gz", "bam")
 _SAMW_FORMAT = {"sam.gz": 0, "bam": 1}                     # SFGPU_SAMW_TEXT, SFGPU_SAMW_BAM (include/sfgpu.h)
 WRITE_KINDS = {1: "the read has no base on the transcript: SAM cannot say that", 2: "the transcript index is not below the number of names"}
+# what qualities add (quals=; csrc/samwfmt.h), in either format: reported as record 0 of the lowest read that holds such a byte
+QUAL_WRITE_KINDS = {6: "a quality byte is not in '!' .. '~': SAM cannot say that"}
 # what format="bam" adds (csrc/bamwfmt.h), behind WRITE_KINDS where one record breaks several
 BAM_WRITE_KINDS = {3: "the read name is not of 1 .. 254 bytes: BAM cannot say that",
                    4: "the bases given differ in number from the record's read length, or are more than 65535: BAM cannot say that",
@@ -540,7 +581,11 @@ class SamDeviceWriter:
       read_names  a (uint8 bytes, 64-bit offsets [reads + 1]) pair of device tensors, or a list of names (packed with
                   quantfile.names_blob and uploaded); default r<index>, the index counted over all batches written so far.
       seqs        the (bases, int64 offsets) device pair of readfile.ReadFile.read / mapper.pack_sequences, or (paired) a pair of such
-                  pairs; default '*'.  Bases are written as given, also on 0x10 lines.
+                  pairs; default '*'.
+      quals       the qualities that go with `seqs`: a device uint8 tensor that shares the bases' offsets (readfile.ReadFile's
+                  last_quals), or (paired) a pair of them, either member None; default QUAL '*'.
+    Bases and qualities are written as given, also on 0x10 lines, unless `oriented=True`: then a 0x10 line carries SEQ
+    reverse-complemented and QUAL reversed (the SAM specification's orientation, what other tools expect).
     A record SAM cannot express (WRITE_KINDS) raises ValueError naming the lowest such read -- counted over all batches, as
     write_sam counts it -- and record; nothing of that batch is written.
     `format`: "sam" (the default) writes the text as it is.  "sam.gz" writes the same text, @HD / @SQ lines included, as a BGZF
@@ -550,12 +595,12 @@ class SamDeviceWriter:
     write_bam writes (sam_to_bam of the same text: magic, header text, reference list, one record per line; csrc/bamwfmt.h) through
     the same encoder; BAM_WRITE_KINDS are then errors too, a read without records counting as record 0.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times."""
 
-    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam"):
+    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False):
         from . import _lib, quantfile
         if format not in WRITE_FORMATS:
             raise ValueError(f"format must be one of {WRITE_FORMATS}, not {format!r}")
         self._L = _lib.lib()
-        self.paired, self.chunk_bytes, self.format = bool(paired), int(chunk_bytes), format
+        self.paired, self.chunk_bytes, self.format, self.oriented = bool(paired), int(chunk_bytes), format, bool(oriented)
         self._names = quantfile.names_blob(_name_bytes(names))
         self._n_refs = len(self._names[1]) - 1
         self._d_names = None                               # uploaded to the device of the first batch
@@ -593,7 +638,7 @@ class SamDeviceWriter:
             raise TypeError("expected (bytes, 64-bit integer offsets)")
         return b.to(dev).contiguous(), o.to(dev).contiguous()
 
-    def write(self, hits, offsets, *, read_names=None, seqs=None):
+    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None):
         import torch
 
         from . import _lib, quantfile
@@ -620,6 +665,24 @@ class SamDeviceWriter:
                 s[m] = self._blob(pair, dev)
                 if s[m][1].numel() != n + 1:
                     raise ValueError(f"bases of {s[m][1].numel() - 1} reads for {n} reads")
+        ql = [None, None]
+        if quals is not None:
+            mates = tuple(quals) if isinstance(quals, (tuple, list)) else (quals,)
+            if len(mates) != (2 if self.paired else 1):
+                raise ValueError("quals: one tensor of quality bytes for a single-end library, a pair of them (either may be None) for a paired one")
+            for m, t in enumerate(mates):
+                if t is None:
+                    continue
+                if s[m][1] is None:
+                    raise ValueError("qualities of a mate whose bases are not given")
+                if not isinstance(t, torch.Tensor):
+                    t = torch.from_numpy(np.frombuffer(bytes(t), np.uint8).copy())
+                if t.element_size() != 1:
+                    raise TypeError("quals: expected quality bytes")
+                t = t.to(dev).contiguous().reshape(-1)
+                if t.numel() != s[m][0].numel():
+                    raise ValueError(f"{t.numel()} quality bytes for {s[m][0].numel()} bases")
+                ql[m] = t if t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)     # no base at all: still "given"
         raised = []
 
         def sink(addr, nb, _user):
@@ -634,17 +697,18 @@ class SamDeviceWriter:
         p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
         batch = (p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs, p(q[0]), p(q[1]),
                  p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads, self.chunk_bytes)
+        extra = (None if ql[0] is None else _lib.ptr(ql[0]), None if ql[1] is None else _lib.ptr(ql[1]), int(self.oriented))
         with torch.cuda.device(dev):
             if self._z is None:
-                rc = self._L.sfgpu_sam_write_text(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
+                rc = self._L.sfgpu_sam_write_text_q(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra)
             else:
                 self._write_head(dev)
-                rc = self._L.sfgpu_sam_write_bgzf(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr())
+                rc = self._L.sfgpu_sam_write_bgzf_q(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra)
         sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
         if sunk:
             raise sunk.pop(0)
         if rc == _lib.ERR_INVALID and res.error_kind:
-            what = {**WRITE_KINDS, **BAM_WRITE_KINDS}[int(res.error_kind)]
+            what = {**WRITE_KINDS, **BAM_WRITE_KINDS, **QUAL_WRITE_KINDS}[int(res.error_kind)]
             raise ValueError(f"read {self.n_reads + int(res.error_read)}, record {int(res.error_record)}: {what}")
         _lib.check(rc)
         self.n_reads += n

@@ -9,7 +9,14 @@ Clocks: *_write_s are host wall time (time.perf_counter) around the whole writer
 ms_format / ms_encode / ms_copy are device events and ms_sink the host clock inside the sink, from the writer's stats.  The first
 run of each leg warms code objects, pools and the page cache and is dropped; the other five are all reported, with their median.
 
-    python tools/bamwrite_probe.py [--out DIR] [--json FILE] [--reads 100000] [--repeats 5] [--write-only]
+--oriented runs a second leg instead of the one above: the same batch with qualities of every base and oriented=True (the lines
+with 0x10 carry SEQ reverse-complemented and QUAL reversed), "sam.gz" and "bam" beside the plain oriented text.  The inflated
+"sam.gz" is compared with the plain oriented text (which tools/samwrite_probe.py --oriented compares with write_sam), the "bam"
+writer with write_bam(quals=, oriented=True) on the first 2 000 reads; then five writes of each after a warm-up, with a plain
+pinned copy of as many bytes as the formatter hands to the encoder.  The record goes to profiles/bamqual_probe.json unless --json
+says otherwise.
+
+    python tools/bamwrite_probe.py [--out DIR] [--json FILE] [--reads 100000] [--repeats 5] [--write-only] [--oriented]
 Prints one JSON line and writes FILE (default profiles/bamwrite_probe.json).  --write-only: three "sam.gz" and three "bam" writes, nothing else
 (for rocprofv3 --kernel-trace --stats)."""
 import argparse
@@ -41,6 +48,67 @@ def zlib_file_bytes(data, level):
     return n
 
 
+def oriented_leg(a, dev, names, ref_len, hits, off, b1, b2, d_batch, up, rng):
+    d_hits, d_off, d_seqs = d_batch
+    L = a.read_len
+    q1, q2 = (rng.integers(33, 127, a.reads * L).astype(np.uint8) for _ in range(2))
+    d_quals = (up(q1), up(q2))
+    path = {fmt: os.path.join(a.out, "oriented." + fmt) for fmt in ("sam", "sam.gz", "bam")}
+
+    def device_write(fmt):
+        with samfile.SamDeviceWriter(path[fmt], names, ref_len, True, format=fmt, oriented=True) as w:
+            w.write(d_hits, d_off, seqs=d_seqs, quals=d_quals)
+        return dict(w.stats)
+
+    for fmt in path:
+        device_write(fmt)
+    text = open(path["sam"], "rb").read()
+    assert gzip.decompress(open(path["sam.gz"], "rb").read()) == text, "the compressed oriented file does not inflate to the plain one"
+    stream = gzip.decompress(open(path["bam"], "rb").read())
+    n = min(2000, a.reads)                                 # the host writer packs base by base in Python: a prefix of the batch
+    sub = os.path.join(a.out, "oriented.sub.bam")
+    with samfile.SamDeviceWriter(sub, names, ref_len, True, format="bam", oriented=True) as w:
+        w.write(d_hits[:24 * int(off[n])], d_off[:n + 1], seqs=tuple((b[:n * L], o[:n + 1]) for b, o in d_seqs), quals=tuple(q[:n * L] for q in d_quals))
+    cut = lambda x: [(x[0][i * L:(i + 1) * L].tobytes(), x[1][i * L:(i + 1) * L].tobytes()) for i in range(n)]  # noqa: E731
+    samfile.write_bam(sub + ".host", names, ref_len, hits[:int(off[n])], off[:n + 1], seqs=cut((b1, b2)), quals=cut((q1, q2)), oriented=True)
+    assert gzip.decompress(open(sub, "rb").read()) == gzip.decompress(open(sub + ".host", "rb").read()), "the oriented device BAM writer and write_bam disagree"
+    legs = {}
+    for fmt in path:
+        runs = []
+        for _ in range(a.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = device_write(fmt)
+            runs.append(dict(st, write_s=time.perf_counter() - t0))
+        legs[fmt] = runs
+    med = statistics.median
+    rec = dict(reads=a.reads, hits=int(len(hits)), text_bytes=len(text), bam_stream_bytes=len(stream), device=torch.cuda.get_device_name(0),
+               file_bytes={fmt: os.path.getsize(p) for fmt, p in path.items()}, writer=legs)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for fmt, n_in in (("sam", len(text)), ("sam.gz", len(text)), ("bam", len(stream))):
+        runs = legs[fmt]
+        rec[fmt + "_median"] = dict(write_s=med(r["write_s"] for r in runs), ms_format=med(r["ms_format"] for r in runs),
+                                    ms_copy=med(r["ms_copy"] for r in runs), ms_sink=med(r["ms_sink"] for r in runs))
+        if fmt != "sam":
+            rec[fmt + "_median"]["ms_encode"] = med(r["ms_encode"] for r in runs)
+        src = torch.empty(n_in, dtype=torch.uint8, device=dev).random_(0, 255)
+        dst = torch.empty(n_in, dtype=torch.uint8).pin_memory()
+        copies = []
+        for i in range(a.repeats + 1):
+            ev[0].record()
+            dst.copy_(src, non_blocking=True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if i:
+                copies.append(ev[0].elapsed_time(ev[1]))
+        rec[fmt + "_median"]["plain_copy_ms_of_formatted_bytes"] = med(copies)
+    print(json.dumps(rec))
+    out = a.json if a.json != os.path.join(ROOT, "profiles", "bamwrite_probe.json") else os.path.join(ROOT, "profiles", "bamqual_probe.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="bamwrite_probe_out")
@@ -50,6 +118,7 @@ def main():
     ap.add_argument("--refs", type=int, default=30_000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--write-only", action="store_true")
+    ap.add_argument("--oriented", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     os.makedirs(a.out, exist_ok=True)
@@ -67,6 +136,9 @@ def main():
             w.write(d_hits, d_off, seqs=d_seqs)
         return dict(w.stats)
 
+    if a.oriented:
+        oriented_leg(a, dev, names, ref_len, hits, off, b1, b2, (d_hits, d_off, d_seqs), up, rng)
+        return
     if a.write_only:
         for fmt in ("sam.gz", "bam"):
             for _ in range(3):

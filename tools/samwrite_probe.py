@@ -9,7 +9,13 @@ torch.cuda.synchronize(); format_ms / d2h_ms are device events and sink_ms the h
 plain_copy_ms is device events around one copy into a pinned buffer.  The first run of each leg warms code objects, pools and the
 page cache and is dropped; the other five are all reported, with their median.
 
-    python tools/samwrite_probe.py [--out DIR] [--json FILE] [--reads 100000] [--repeats 5] [--write-only]
+--oriented adds a second leg on the same batch: qualities of every base and SamDeviceWriter(oriented=True), so that the lines
+with 0x10 (half the records) carry SEQ reverse-complemented and QUAL reversed.  Its file is compared with
+write_sam(quals=, oriented=True) once, then written five times after a warm-up; the record gains `oriented` (its runs, medians
+and a plain pinned copy of as many bytes as ITS text has).  --skip-host leaves the host loop's timing out (a quick A/B of the
+device legs).
+
+    python tools/samwrite_probe.py [--out DIR] [--json FILE] [--reads 100000] [--repeats 5] [--write-only] [--oriented] [--skip-host]
 Prints one JSON line and writes FILE (default profiles/samwrite_probe.json).  --write-only: three device writes, nothing else
 (for rocprofv3 --kernel-trace --stats)."""
 import argparse
@@ -59,6 +65,8 @@ def main():
     ap.add_argument("--refs", type=int, default=30_000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--write-only", action="store_true")
+    ap.add_argument("--oriented", action="store_true")
+    ap.add_argument("--skip-host", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     os.makedirs(a.out, exist_ok=True)
@@ -92,29 +100,67 @@ def main():
         t0 = time.perf_counter()
         st = device_write()
         runs.append(dict(st, device_write_s=time.perf_counter() - t0))
-    for _ in range(a.repeats):
+    for _ in range(0 if a.skip_host else a.repeats):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         samfile.write_sam(path + ".host", names, ref_len, hits, off, seqs=seqs)
         loops.append(time.perf_counter() - t0)
     os.remove(path + ".host")
     n_bytes = runs[0]["bytes"]
-    src = torch.empty(n_bytes, dtype=torch.uint8, device=dev).random_(0, 255)
-    dst = torch.empty(n_bytes, dtype=torch.uint8).pin_memory()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for i in range(a.repeats + 1):
-        ev[0].record()
-        dst.copy_(src, non_blocking=True)
-        ev[1].record()
-        torch.cuda.synchronize()
-        if i:
-            copies.append(ev[0].elapsed_time(ev[1]))
+
+    def plain_copies(n):
+        src = torch.empty(n, dtype=torch.uint8, device=dev).random_(0, 255)
+        dst = torch.empty(n, dtype=torch.uint8).pin_memory()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        out = []
+        for i in range(a.repeats + 1):
+            ev[0].record()
+            dst.copy_(src, non_blocking=True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if i:
+                out.append(ev[0].elapsed_time(ev[1]))
+        return out
+
+    copies = plain_copies(n_bytes)
     med = statistics.median
+    oriented = None
+    if a.oriented:
+        q1, q2 = (rng.integers(33, 127, a.reads * a.read_len).astype(np.uint8) for _ in range(2))
+        d_quals = (up(q1), up(q2))
+        qpath = os.path.join(a.out, "mappings.oriented.sam")
+
+        def oriented_write():
+            with samfile.SamDeviceWriter(qpath, names, ref_len, True, oriented=True) as w:
+                w.write(d_hits, d_off, seqs=d_seqs, quals=d_quals)
+                return dict(w.stats)
+
+        oriented_write()
+        L = a.read_len
+        samfile.write_sam(qpath + ".host", names, ref_len, hits, off, seqs=seqs, oriented=True,
+                          quals=[(q1[i * L:(i + 1) * L].tobytes(), q2[i * L:(i + 1) * L].tobytes()) for i in range(a.reads)])
+        assert open(qpath + ".host", "rb").read() == open(qpath, "rb").read(), "the oriented device writer and write_sam disagree"
+        os.remove(qpath + ".host")
+        qruns = []
+        for _ in range(a.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = oriented_write()
+            qruns.append(dict(st, device_write_s=time.perf_counter() - t0))
+        qcopies = plain_copies(qruns[0]["bytes"])
+        with open(qpath, "rb") as f:
+            reversed_lines = sum(1 for l in f if not l.startswith(b"@") and int(l.split(b"\t", 2)[1]) & 0x10)
+        oriented = dict(text_bytes=qruns[0]["bytes"], reversed_lines=reversed_lines, writer=qruns, plain_copy_ms=qcopies,
+                        device_write_s_median=med(r["device_write_s"] for r in qruns), format_ms_median=med(r["ms_format"] for r in qruns),
+                        d2h_ms_median=med(r["ms_copy"] for r in qruns), sink_ms_median=med(r["ms_sink"] for r in qruns),
+                        plain_copy_ms_median=med(qcopies))
     rec = dict(reads=a.reads, hits=int(len(hits)), lines=runs[0]["lines"], file_bytes=len(text), text_bytes=n_bytes, device=torch.cuda.get_device_name(0),
                writer=runs, host_write_s=loops, plain_copy_ms=copies,
                device_write_s_median=med(r["device_write_s"] for r in runs), format_ms_median=med(r["ms_format"] for r in runs),
                d2h_ms_median=med(r["ms_copy"] for r in runs), sink_ms_median=med(r["ms_sink"] for r in runs),
-               host_write_s_median=med(loops), plain_copy_ms_median=med(copies))
+               host_write_s_median=med(loops) if loops else None, plain_copy_ms_median=med(copies))
+    if oriented is not None:
+        rec["oriented"] = oriented
     print(json.dumps(rec))
     os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
     with open(a.json, "w") as f:

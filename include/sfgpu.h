@@ -231,6 +231,32 @@ SFGPU_API int sfgpu_reads_parse_host_q(const char* h_text, uint64_t n_bytes, int
 SFGPU_API int sfgpu_reads_parse_device_q(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads,
                                          uint8_t* d_bases, uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span,
                                          sfgpu_reads_result* out, sfgpu_stream stream);
+/* The two parses with the read names delivered on the device as well: d_names == NULL gives exactly the _q calls above (which are
+ * these calls with NULLs).  Otherwise the names of the EMITTED records -- those in front of the max_reads / cap_bases cut -- are
+ * written back to back to d_names[0 .. *n_name_bytes) and d_name_off[r] (64-bit, room for max_reads + 1 entries) is the exclusive
+ * sum of their lengths: record r's name is d_names[d_name_off[r] .. d_name_off[r + 1]), d_name_off[0] = 0 and d_name_off[n_reads] =
+ * *n_name_bytes (n_name_bytes may be NULL).  This is the (bytes, 64-bit offsets) pair sfgpu_sam_write_text and sfgpu_bam_write take
+ * as read names.  A name is what d_name_span describes (up to the first space or tab, never the '\r' of a CRLF end, possibly
+ * empty); spans and blob may be asked for together and agree.  d_names must be 16-byte aligned and cap_names a multiple of 16
+ * (else SFGPU_ERR_INVALID): the call may write zeros up to the end of the blob's last 16-byte group.  Names that need more than
+ * cap_names bytes are SFGPU_ERR_RANGE, and like every error that call emits nothing (n_reads == 0, consumed == 0); cap_names >=
+ * n_bytes rounded up to 16 is always enough.  Everything else is what the _q call gives for the same bytes.  With names the call
+ * waits for the device once more (the blob's size decides the range error and the gather's grid). */
+SFGPU_API int sfgpu_reads_parse_host_n(const char* h_text, uint64_t n_bytes, int final, uint64_t max_reads, uint8_t* d_bases,
+                                       uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span, uint8_t* d_names,
+                                       uint64_t cap_names, uint64_t* d_name_off, uint64_t* n_name_bytes, sfgpu_reads_result* out,
+                                       sfgpu_stream stream);
+SFGPU_API int sfgpu_reads_parse_device_n(uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, uint64_t max_reads,
+                                         uint8_t* d_bases, uint8_t* d_qual, uint64_t cap_bases, int64_t* d_off, uint64_t* d_name_span,
+                                         uint8_t* d_names, uint64_t cap_names, uint64_t* d_name_off, uint64_t* n_name_bytes,
+                                         sfgpu_reads_result* out, sfgpu_stream stream);
+/* Do the mate files of a paired library run in step?  Two name blobs of n_reads names each (as the calls above write them; any
+ * alignment) are compared read by read under the stem rule of sailfish_amd/csrc/readfmt.h: a trailing "/1" or "/2" is dropped
+ * from either name, whichever digit it is, and the rest must be equal in length and bytes (x/1 ~ x/2 ~ x; x/3 is not x).
+ * *first_mismatch (host) = the lowest read whose names disagree, UINT64_MAX when all agree (and for n_reads == 0).  Synchronous,
+ * ordered behind the work already on `stream`. */
+SFGPU_API int sfgpu_reads_names_match(const uint8_t* d_names1, const uint64_t* d_off1, const uint8_t* d_names2, const uint64_t* d_off2,
+                                      uint64_t n_reads, uint64_t* first_mismatch, sfgpu_stream stream);
 /* Blocked gzip (BGZF: what bgzip and the Illumina converters write) inflated on the device, one wavefront per member.  The
  * rules live in sailfish_amd/csrc/bgzfmt.h: a member is a gzip member with a 'B','C' extra subfield that holds its size, at
  * most 64 KB of payload, and no match that reaches before its first byte.

@@ -228,6 +228,11 @@ _SIGS = {
     "sfgpu_reads_parse_device": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_reads_parse_host_q": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
     "sfgpu_reads_parse_device_q": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, C.POINTER(ReadsResult), _P]),
+    "sfgpu_reads_parse_host_n": (C.c_int, [_P, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P,
+                                           C.POINTER(C.c_uint64), C.POINTER(ReadsResult), _P]),
+    "sfgpu_reads_parse_device_n": (C.c_int, [_P, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P,
+                                             C.POINTER(C.c_uint64), C.POINTER(ReadsResult), _P]),
+    "sfgpu_reads_names_match": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P]),
     "sfgpu_bgzf_inflate_host": (C.c_int, [_P, C.c_uint64, C.c_int, _P, C.c_uint64, C.POINTER(BgzfResult), _P]),
     "sfgpu_gzrd_open": (C.c_int, [C.POINTER(_P), C.c_uint32]),
     "sfgpu_gzrd_plan_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(GzrdResult), _P]),

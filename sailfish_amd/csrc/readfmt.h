@@ -92,6 +92,37 @@ SF_READFMT_HD uint32_t rf_name_len(Byte byte, uint32_t s, uint32_t len) {
     return k - 1;
 }
 
+// NAME BLOB.  The names of the records a call emits (those in front of the max_reads / cap_bases cut, not all the text holds) lie
+// back to back: name_off[r] = the sum of the name lengths of the records before r (name_off[0] = 0), name_off[R] = the bytes of the
+// blob.  A name may be empty.  rf_blob_record says whose byte the blob's byte o is: the r < R with name_off[r] <= o < name_off[r + 1]
+// (there is one for every o < name_off[R]; records with empty names own no byte).
+template <typename Off>
+SF_READFMT_HD uint32_t rf_blob_record(uint32_t R, uint32_t o, Off name_off) {
+    uint32_t lo = 0, hi = R;                                 // name_off(lo) <= o < name_off(hi)
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (name_off(mid) <= o) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// MATES.  The stem of a name of len bytes at s: the name without a trailing "/1" or "/2" (the mark some tools put on the mates of a
+// pair), whichever of the two digits it is; any other name is its own stem.  Two mates AGREE iff their stems are of equal length
+// and equal bytes: x/1 ~ x/2 ~ x, while x/3 is not x.
+template <typename Byte>
+SF_READFMT_HD uint64_t rf_mate_stem_len(Byte byte, uint64_t s, uint64_t len) {
+    return (len >= 2 && byte(s + len - 2) == '/' && (byte(s + len - 1) == '1' || byte(s + len - 1) == '2')) ? len - 2 : len;
+}
+
+template <typename Byte1, typename Byte2>
+SF_READFMT_HD bool rf_mates_agree(Byte1 byte1, uint64_t s1, uint64_t len1, Byte2 byte2, uint64_t s2, uint64_t len2) {
+    const uint64_t m = rf_mate_stem_len(byte1, s1, len1);
+    if (m != rf_mate_stem_len(byte2, s2, len2)) return false;
+    for (uint64_t k = 0; k < m; ++k)
+        if (byte1(s1 + k) != byte2(s2 + k)) return false;
+    return true;
+}
+
 struct RfCount {
     uint32_t records;     // records the text holds
     uint32_t truncated;   // FASTQ, final: the last of them lacks lines

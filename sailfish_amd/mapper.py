@@ -169,24 +169,29 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, **kw):
+                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
-    write_mappings and mappings_format as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names are
-    sliced and packed on the host: ReadFile(names=True)).  mappings_oriented=True writes the file other tools expect: the read files are
+    write_mappings and mappings_format as in quantify_reads; QNAME is the record's name in the mate 1 file up to its first space or tab (the names
+    stay on the device from the parser to the writer: ReadFile(names="device")).  check_mate_names=True compares the names of the two
+    mates of every read on the device (readfile.mate_names_match: equal but for a trailing /1 or /2) and raises ValueError at the first
+    read where the files are out of step, naming the record counted from the start of the files and both names
+    (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
     reverse-complemented and QUAL reversed.  -> (rc, experiment)"""
     from . import quant
-    from .readfile import ReadFile, read_transcripts
+    from .readfile import ReadFile, mate_names_match, read_transcripts
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented)
     keep = sam is not None and bool(mappings_oriented)
 
     def batches():
-        f1 = ReadFile(reads1_path, device, names=sam is not None, inflate=inflate, quals=keep)
-        f2 = None if reads2_path is None else ReadFile(reads2_path, device, inflate=inflate, quals=keep)
+        check = bool(check_mate_names) and reads2_path is not None
+        f1 = ReadFile(reads1_path, device, names="device" if sam is not None or check else False, inflate=inflate, quals=keep)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device, names="device" if check else False, inflate=inflate, quals=keep)
+        done = 0                                              # records of the batches before this one
         try:
             while True:
                 r1 = f1.read(batch_reads)
@@ -196,6 +201,13 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                     raise ValueError(f"{reads1_path} and {reads2_path} do not hold the same number of records")
                 if n == 0:
                     break
+                if check:
+                    bad = mate_names_match(f1.last_names, f2.last_names)
+                    if bad is not None:                       # only these two names are copied back
+                        nm1, nm2 = (bytes(b[int(o[bad]):int(o[bad + 1])].cpu().numpy()) for b, o in (f1.last_names, f2.last_names))
+                        raise ValueError(f"{reads1_path} and {reads2_path} are out of step at record {done + bad}: "
+                                         f"{nm1.decode('utf-8', 'replace')!r} against {nm2.decode('utf-8', 'replace')!r}")
+                done += n
                 h, o = idx.map_reads(r1, r2)
                 if sam is not None:
                     q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals

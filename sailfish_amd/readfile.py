@@ -302,7 +302,11 @@ class ReadFile:
     """A FASTA / FASTQ file (plain or gzip) read through the device parser.
 
     read(max_reads) -> (bases: uint8 device tensor, offsets: int64 device tensor [n + 1]) holding exactly max_reads records unless
-    the file ends first (n == 0 at the end).  With names=True the record names (bytes) of the last read() are in `last_names`.
+    the file ends first (n == 0 at the end).  With names=True the record names (bytes) of the last read() are in `last_names`,
+    sliced on the host from the name spans the parser reports.  With names="device" they stay where the parser left them:
+    `last_names` is then the (uint8 device tensor, int64 device tensor [n + 1]) pair of the names back to back and their offsets
+    (sfgpu_reads_parse_*_n), the form SamDeviceWriter.write(read_names=) and mate_names_match take; nothing is copied back and no
+    Python runs per record (no reads: an empty tensor and one zero).
     With quals=True the qualities of the last read() are in `last_quals`: a uint8 device tensor that shares the bases' offsets
     (record r's are last_quals[offsets[r]:offsets[r + 1]], the bytes of its quality line), or None for a FASTA file.
     `inflate` says where a gzip file is inflated: "auto" takes the device for a BGZF file (its first member carries the 'BC'
@@ -323,8 +327,11 @@ class ReadFile:
         self.gzipped = head[:2] == b"\x1f\x8b"
         bgzf = self.gzipped and bgzf_member_bytes(head) is not None
         self.inflate = None if not self.gzipped else "device" if inflate == "device" or (inflate == "auto" and bgzf) else "host"
-        self._names = bool(names)
-        self.last_names = []
+        if isinstance(names, str) and names != "device":
+            raise ValueError("names must be True, False or 'device'")
+        self._names_dev = isinstance(names, str)        # the device blob
+        self._names = bool(names) and not self._names_dev      # the host list
+        self.last_names = self._no_names() if self._names_dev else []
         self._quals = bool(quals)
         self.last_quals = None
         self.format = 0
@@ -344,10 +351,12 @@ class ReadFile:
         off = torch.empty(max_reads + 1, dtype=torch.int64, device=self.device)
         span = torch.empty(2 * max_reads, dtype=torch.int64, device=self.device) if self._names else None
         qual = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device) if self._quals else None
+        blob, blob_off, cap_names, n_name = self._name_room(n, max_reads)
         res = _lib.ReadsResult()
         with torch.cuda.device(self.device):
-            rc = self._L.sfgpu_reads_parse_host_q(_lib.ptr(text), n, int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n, _lib.ptr(off),
-                                                  _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
+            rc = self._L.sfgpu_reads_parse_host_n(_lib.ptr(text), n, int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n, _lib.ptr(off),
+                                                  _lib.ptr(span), _lib.ptr(blob), cap_names, _lib.ptr(blob_off), C.byref(n_name), C.byref(res),
+                                                  _lib.current_stream_ptr())
         if rc == _lib.ERR_FORMAT:
             raise ValueError(f"{self.path}: record {self._carry.records + res.error_record} is malformed: "
                              f"{KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
@@ -360,6 +369,8 @@ class ReadFile:
             sp = span[: 2 * res.n_reads].cpu().numpy().reshape(-1, 2)
             raw = text.tobytes()
             names = [raw[b:b + l] for b, l in sp.tolist()]
+        elif self._names_dev:
+            names = self._name_pair(blob, blob_off, int(n_name.value), int(res.n_reads), max_reads)
         off = off[: res.n_reads + 1]
         if 2 * off.numel() < max_reads:                        # a batch must not pin an array sized for the records that might have been
             off = off.clone()
@@ -377,10 +388,12 @@ class ReadFile:
             off = torch.empty(max_reads + 1, dtype=torch.int64, device=self.device)
             span = torch.empty(2 * max_reads, dtype=torch.int64, device=self.device) if self._names else None
             qual = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device) if self._quals else None
+            blob, blob_off, cap_names, n_name = self._name_room(n, max_reads)
             res = _lib.ReadsResult()
             view = text[lo:]
-            rc = self._L.sfgpu_reads_parse_device_q(_lib.ptr(view), n, view.numel(), int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n,
-                                                    _lib.ptr(off), _lib.ptr(span), C.byref(res), _lib.current_stream_ptr())
+            rc = self._L.sfgpu_reads_parse_device_n(_lib.ptr(view), n, view.numel(), int(final), max_reads, _lib.ptr(bases), _lib.ptr(qual), n,
+                                                    _lib.ptr(off), _lib.ptr(span), _lib.ptr(blob), cap_names, _lib.ptr(blob_off), C.byref(n_name),
+                                                    C.byref(res), _lib.current_stream_ptr())
         if rc == _lib.ERR_FORMAT:
             raise ValueError(f"{self.path}: record {records + res.error_record} is malformed: "
                              f"{KINDS.get(res.error_kind, 'malformed')} (kind {res.error_kind})")
@@ -397,10 +410,33 @@ class ReadFile:
             raw = view[idx].cpu().numpy().tobytes()
             cuts = np.concatenate([[0], ends.cpu().numpy()]).tolist()
             names = [raw[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        elif self._names_dev:
+            names = self._name_pair(blob, blob_off, int(n_name.value), int(res.n_reads), max_reads)
         off = off[: res.n_reads + 1]
         if 2 * off.numel() < max_reads:
             off = off.clone()
         return Parsed(int(res.n_reads), int(res.consumed), (bases[: res.n_bases], off, names, qual[: res.n_bases] if self._kept(res, qual) else None))
+
+    def _no_names(self):
+        return torch.zeros(0, dtype=torch.uint8, device=self.device), torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _name_room(self, n, max_reads):
+        """what a parse call of n bytes needs for its name blob -> (blob, offsets, cap_names, n_name_bytes); Nones and 0 without one"""
+        if not self._names_dev:
+            return None, None, 0, C.c_uint64(0)
+        cap = max((n + 15) & ~15, 16)                        # the names of a text are never more than its bytes
+        return (torch.empty(cap, dtype=torch.uint8, device=self.device), torch.empty(max_reads + 1, dtype=torch.int64, device=self.device),
+                cap, C.c_uint64(0))
+
+    @staticmethod
+    def _name_pair(blob, blob_off, n_name, n_reads, max_reads):
+        """the pair of one parse call; like the offsets of the bases, it must not pin arrays sized for what might have been"""
+        b, o = blob[:n_name], blob_off[: n_reads + 1]
+        if 2 * n_name < blob.numel():
+            b = b.clone()
+        if 2 * o.numel() < max_reads:
+            o = o.clone()
+        return b, o
 
     @staticmethod
     def _kept(res, qual):
@@ -415,7 +451,18 @@ class ReadFile:
                 break
             parts.append(res.payload)
             left -= res.n_reads
-        self.last_names = [nm for p in parts for nm in (p[2] or [])]
+        if self._names_dev:
+            pairs = [p[2] for p in parts]
+            if len(pairs) <= 1:
+                self.last_names = pairs[0] if pairs else self._no_names()
+            else:                                              # rebased on the device, as the bases are below
+                acc, offs = pairs[0][1][-1], [pairs[0][1]]
+                for _, o in pairs[1:]:
+                    offs.append(o[1:] + acc)
+                    acc = acc + o[-1]
+                self.last_names = torch.cat([b for b, _ in pairs]), torch.cat(offs)
+        else:
+            self.last_names = [nm for p in parts for nm in (p[2] or [])]
         kept = [p[3] for p in parts if p[3] is not None]
         self.last_quals = (kept[0] if len(kept) == 1 else torch.cat(kept)) if kept and len(kept) == len(parts) else None
         if not parts:
@@ -440,6 +487,33 @@ class ReadFile:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def mate_stem(name):
+    """the name without a trailing b"/1" or b"/2" (whichever digit it is), any other name whole: what the names of two mates have
+    to share.  The Python statement of csrc/readfmt.h's rf_mate_stem_len."""
+    name = bytes(name)
+    return name[:-2] if len(name) >= 2 and name[-2:] in (b"/1", b"/2") else name
+
+
+def mate_names_match(pair1, pair2):
+    """Do two batches of read names run in step?  pair1, pair2: (uint8 device tensor, int64 device tensor [n + 1]) as
+    ReadFile(names="device") leaves them in `last_names`.  -> None when every read's two names have the same mate_stem, else the
+    lowest read whose names disagree.  Compared on the device (sfgpu_reads_names_match); one integer comes back.  The offsets are
+    trusted as the parser's are (never decreasing, the last one within the bytes): only shapes and types are looked at here."""
+    (b1, o1), (b2, o2) = pair1, pair2
+    n = int(o1.numel()) - 1
+    if int(o2.numel()) - 1 != n or n < 0:
+        raise ValueError(f"{n} names against {int(o2.numel()) - 1}")
+    for b, o in ((b1, o1), (b2, o2)):
+        if b.dtype != torch.uint8 or o.dtype != torch.int64 or not b.is_cuda or o.device != b.device or b.device != b1.device:
+            raise TypeError("expected (uint8, int64) tensors on one device")
+    b1, o1, b2, o2 = (t.contiguous() for t in (b1, o1, b2, o2))
+    first = C.c_uint64(0)
+    with torch.cuda.device(b1.device):
+        _lib.check(_lib.lib().sfgpu_reads_names_match(_lib.ptr(b1), _lib.ptr(o1), _lib.ptr(b2), _lib.ptr(o2), n, C.byref(first),
+                                                      _lib.current_stream_ptr()))
+    return None if first.value == 2 ** 64 - 1 else int(first.value)
 
 
 def read_transcripts(path, device="cuda", block_bytes=32 << 20, inflate="auto"):

@@ -35,11 +35,11 @@ enum {
                                 src/CollapsedEMOptimizer.cpp:794-798 */
     SFGPU_ERR_ALPHA_SUM = 4, /* "total alpha weight was too small" -- :877-881 */
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
-    SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish) */
+    SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish, sfgpu_samc_emit before sfgpu_samc_finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*, sfgpu_sam_parse_*, sfgpu_bam_parse_*, sfgpu_sam_collect_*, sfgpu_bam_collect_*) */
     SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_gz_*, sfgpu_bgzw_*) */
-    SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*) */
+    SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*, sfgpu_bam_parse_*, sfgpu_samc_emit) */
 };
 
 typedef void* sfgpu_stream;          /* hipStream_t */
@@ -567,7 +567,9 @@ enum {
     SFGPU_SAM_BAD_FLAG = 4,     /* paired call: 0x1 missing, or not exactly one of 0x40 / 0x80; single-end call: 0x1 set */
     SFGPU_SAM_BAD_RNAME = 8,    /* a mapped line names no transcript of the handle */
     SFGPU_SAM_BAD_CIGAR = 16,   /* neither '*' nor a run of (1-9 digits, one of MIDNSHP=X) */
-    SFGPU_SAM_BAD_LENGTH = 32   /* the read is longer than 65535 bases, or SEQ and CIGAR disagree about its length */
+    SFGPU_SAM_BAD_LENGTH = 32,  /* the read is longer than 65535 bases, or SEQ and CIGAR disagree about its length */
+    SFGPU_SAM_BAD_QNAME = 64    /* sfgpu_sam_collect_* only: QNAME is longer than 254 bytes; in a paired call PNEXT of a mapped line
+                                   that is not 1-10 digits in 0 .. 2^31 - 1 is BAD_NUMBER there */
 };
 typedef struct {
     uint64_t n_lines;      /* lines consumed by this call, header lines included */
@@ -620,6 +622,63 @@ SFGPU_API int sfgpu_bam_parse_host(sfgpu_bam* b, const char* h_text, uint64_t n_
 SFGPU_API int sfgpu_bam_parse_device(sfgpu_bam* b, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final, struct sfgpu_hit* d_hits,
                                      uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bam_close(sfgpu_bam* b);
+/* The COLLATED reading of the same files: for a SAM or BAM file whose lines stand in any order -- a position-sorted file, what
+ * `samtools sort` leaves -- where sfgpu_sam_parse_* / sfgpu_bam_parse_* would see every line as a fragment of its own.  The alignment
+ * lines of the WHOLE file are collected on the device as fixed-size line records plus their names; after the last text they are
+ * grouped by QNAME exactly (a string sort over the name bytes: equal ranks are byte-equal names, nothing is hashed), paired through
+ * their mate fields, and emitted in slices as the (d_hits, d_off) batches the name-grouped readers give.  The rules are stated
+ * once, serially, in csrc/samcfmt.h (those of samfile.read_sam_collated_host / read_bam_collated_host); the kernels are
+ * csrc/samcollate.hip, behind the line front ends of the name-grouped readers (csrc/samfront.h, csrc/bamfront.h).  In short: ALL
+ * non-header lines with byte-equal QNAME are one fragment, numbered by their first lines, lines in file order inside; in a paired
+ * call a mapped line also has RNEXT and PNEXT read and NAMES A MATE iff FLAG lacks 0x8, RNEXT is "=" or its RNAME, and PNEXT >= 1 (BAM:
+ * next_refID == refID, next_pos >= 0); lines a (0x40) and b (0x80) of a fragment pair when both are mapped on one transcript, both
+ * name a mate, a.PNEXT == b.POS and b.PNEXT == a.POS (the written POS); among lines with one (transcript, POS of mate 1, POS of
+ * mate 2) the i-th 0x40 line in file order pairs with the i-th 0x80 line.  What a fragment yields and the record order are
+ * sfgpu_sam_parse_*'s.
+ *   samc_open   an empty collection; paired != 0: the paired-end rules.
+ *   sam_collect_host / _device, bam_collect_host / _device   one text of the file, through the parser handle `s` / `b` that holds the
+ *            transcript names (its `paired` must be the collection's, else SFGPU_ERR_INVALID).  The text conventions are those of
+ *            sfgpu_sam_parse_* / sfgpu_bam_parse_*: alignment, slack, n_bytes <= 2^30, `final`, the BAM header skipped through the
+ *            handle's stream position.  Nothing is held back: `consumed` ends behind the last complete line or record, consumed == 0
+ *            means "present more".  Per non-header line 32 bytes and the QNAME's bytes are appended (the arrays grow by doubling);
+ *            the result's n_lines / n_header count the lines consumed, n_reads, n_hits and n_pairs stay 0.  A malformed line is
+ *            SFGPU_ERR_FORMAT with bad / bad_line as in sfgpu_sam_parse_* (lowest line, first rule; SFGPU_SAM_BAD_QNAME is the last
+ *            rule), and nothing of that call is appended.  2^32 - 1 lines or more in one collection is SFGPU_ERR_RANGE.
+ *   samc_finish   groups, orders and pairs: rank refinement over the names in rounds of 8 bytes (sort_rounds of them, at most 32),
+ *            one stable sort by (first line of the fragment, file order), two by (fragment, transcript, POS of mate 1, POS of mate
+ *            2, side) over the lines that name a mate.  `info` says what the collection holds; state_bytes is the device memory the
+ *            handle keeps from here on.
+ *   samc_emit   the fragments [first_read, first_read + n_reads) of the collection: d_hits[0 .. n_hits), d_off[0 .. n_reads] (uint32,
+ *            d_off[0] = 0 in every call); the result's n_reads, n_hits, n_pairs and ms_kernels are the slice's.  n_hits > cap_hits is
+ *            SFGPU_ERR_CAPACITY with need_hits set and nothing written; a slice that reaches beyond the collection's fragments is
+ *            SFGPU_ERR_RANGE.
+ * collect after finish, finish twice, and emit before finish are SFGPU_ERR_STATE.  All calls are synchronous and ordered behind the
+ * work already on `stream`; one handle is used from one thread at a time.  No CPU path. */
+typedef struct sfgpu_samc sfgpu_samc;
+typedef struct {
+    uint64_t n_lines;      /* alignment lines collected (header lines are not) */
+    uint64_t n_reads;      /* fragments */
+    uint64_t n_hits;       /* records all fragments yield */
+    uint64_t n_pairs;      /* PAIRED_END_PAIRED records among them */
+    uint64_t state_bytes;  /* device memory held by the handle */
+    uint32_t sort_rounds;  /* rounds of the name sort */
+    uint32_t pad_;
+    double ms_collect;     /* device events around the kernels of all collect calls */
+    double ms_finish;      /* ... and of finish */
+} sfgpu_samc_info;
+SFGPU_API int sfgpu_samc_open(sfgpu_samc** out, int paired, sfgpu_stream stream);
+SFGPU_API int sfgpu_sam_collect_host(sfgpu_sam* s, sfgpu_samc* c, const char* h_text, uint64_t n_bytes, int final, sfgpu_sam_result* res,
+                                     sfgpu_stream stream);
+SFGPU_API int sfgpu_sam_collect_device(sfgpu_sam* s, sfgpu_samc* c, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final,
+                                       sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_bam_collect_host(sfgpu_bam* b, sfgpu_samc* c, const char* h_text, uint64_t n_bytes, int final, sfgpu_sam_result* res,
+                                     sfgpu_stream stream);
+SFGPU_API int sfgpu_bam_collect_device(sfgpu_bam* b, sfgpu_samc* c, uint8_t* d_text, uint64_t n_bytes, uint64_t cap_text, int final,
+                                       sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_samc_finish(sfgpu_samc* c, sfgpu_samc_info* info, sfgpu_stream stream);
+SFGPU_API int sfgpu_samc_emit(sfgpu_samc* c, uint64_t first_read, uint64_t n_reads, struct sfgpu_hit* d_hits, uint64_t cap_hits, uint32_t* d_off,
+                              sfgpu_sam_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_samc_close(sfgpu_samc* c);
 /* The other direction (what `rapmap quasimap -o` offers): the ALIGNMENT LINES of a SAM file formatted on the device from one batch of
  * hit records in CSR form, as sfgpu_map_reads and sfgpu_sam_parse_* leave it.  What the lines say is stated once, serially, in
  * csrc/samwfmt.h (the bytes of samfile._sam_text); the kernels are csrc/samtext_write.hip.  In short, per read in order: a pair

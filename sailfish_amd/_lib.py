@@ -124,6 +124,14 @@ class GmapResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SamcInfo(C.Structure):
+    _fields_ = [("n_lines", C.c_uint64), ("n_reads", C.c_uint64), ("n_hits", C.c_uint64), ("n_pairs", C.c_uint64), ("state_bytes", C.c_uint64),
+                ("sort_rounds", C.c_uint32), ("pad_", C.c_uint32), ("ms_collect", C.c_double), ("ms_finish", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class SamResult(C.Structure):
     _fields_ = [("n_lines", C.c_uint64), ("n_header", C.c_uint64), ("n_reads", C.c_uint64), ("n_hits", C.c_uint64), ("n_pairs", C.c_uint64),
                 ("consumed", C.c_uint64), ("need_hits", C.c_uint64), ("need_reads", C.c_uint64), ("bad_line", C.c_uint64), ("bad", C.c_uint32),
@@ -259,6 +267,14 @@ _SIGS = {
     "sfgpu_bam_parse_host": (C.c_int, [_P, _P, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_bam_parse_device": (C.c_int, [_P, _P, C.c_uint64, C.c_uint64, C.c_int, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(SamResult), _P]),
     "sfgpu_bam_close": (C.c_int, [_P]),
+    "sfgpu_samc_open": (C.c_int, [C.POINTER(_P), C.c_int, _P]),
+    "sfgpu_sam_collect_host": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(SamResult), _P]),
+    "sfgpu_sam_collect_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(SamResult), _P]),
+    "sfgpu_bam_collect_host": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, C.POINTER(SamResult), _P]),
+    "sfgpu_bam_collect_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(SamResult), _P]),
+    "sfgpu_samc_finish": (C.c_int, [_P, C.POINTER(SamcInfo), _P]),
+    "sfgpu_samc_emit": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(SamResult), _P]),
+    "sfgpu_samc_close": (C.c_int, [_P]),
     "sfgpu_sam_write_text": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
                                        C.POINTER(SamWriteResult), _P]),
     "sfgpu_sam_write_text_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,

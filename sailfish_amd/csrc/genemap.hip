@@ -15,7 +15,7 @@
 //                     own group were loaded by the same wavefront in the same step: they come from the L1, no LDS stage is kept.
 //   k_tsv_tokens      two-column form: one lane per group walks the tokens that start in it
 //   scans, k_gmap_append   the names of the records, compacted into the handle's blob (one lane per name)
-// finish: the string sort is rank refinement in rounds of 8 bytes (rank_strings): the key of a round is the next 8 bytes of each
+// finish: the string sort is rank refinement in rounds of 8 bytes (rank_strings, ranksort.h): the key of a round is the next 8 bytes of each
 // name, big-endian and zero-padded (no NUL in a name, so a prefix sorts first); two stable sort_pairs_u64_u32 passes, by key and
 // then by the current run, order the names by (run, key), and a new run starts wherever either changes.  The first order is file
 // order and every pass is stable, so inside a run of equal names the records stay in file order: "the first record that carries
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "gtffmt.h"
 #include "primitives.h"
+#include "ranksort.h"
 #include "textlines.h"
 
 namespace sfgpu {
@@ -219,7 +220,7 @@ __global__ void k_gmap_append(const unsigned char* __restrict__ bytes, uint64_t 
     off[k + 1] = base + scan[k + 1];
 }
 
-// ---- the string sort ------------------------------------------------------------------------------------------------------
+// ---- the string sort (ranksort.h) ------------------------------------------------------------------------------------------
 
 // the names of the handle: name 2 * rec + which of record rec = sel[item] (sel == null: the item itself); kNone: the empty name
 struct Names {
@@ -233,93 +234,23 @@ struct Names {
         const uint64_t k = 2 * (uint64_t)rec + which;
         *s = off[k]; *n = off[k + 1] - off[k];
     }
-};
-
-__global__ void k_rank_init(uint32_t n, uint32_t* __restrict__ perm, uint32_t* __restrict__ run, uint32_t* __restrict__ iota) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    perm[j] = j; run[j] = 0; iota[j] = j;
-}
-
-__global__ void k_rank_keys(Names nm, uint32_t n, const uint32_t* __restrict__ perm, uint32_t round, uint64_t* __restrict__ key) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    uint64_t s, len, k = 0;
-    nm.span(perm[j], &s, &len);
-    const uint64_t at = 8ull * round;
-    for (uint32_t i = 0; i < 8; ++i) k = (k << 8) | (at + i < len ? nm.blob[s + at + i] : 0u);
-    key[j] = k;
-}
-
-__global__ void k_rank_runs_of(uint32_t n, const uint32_t* __restrict__ run, const uint32_t* __restrict__ idx2, uint64_t* __restrict__ rk) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) rk[j] = run[idx2[j]];
-}
-
-// the new order: position j holds what stood at idx2[idx3[j]]; a run begins where the old run or the key changes
-__global__ void k_rank_apply(uint32_t n, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ idx2, const uint32_t* __restrict__ idx3,
-                             const uint64_t* __restrict__ key2, const uint64_t* __restrict__ rk2, uint32_t* __restrict__ perm_out,
-                             uint32_t* __restrict__ head) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    perm_out[j] = perm[idx2[idx3[j]]];
-    head[j] = (j == 0 || rk2[j] != rk2[j - 1] || key2[idx3[j]] != key2[idx3[j - 1]]) ? 1u : 0u;
-}
-
-// run[j] from the scan of the heads; *more = 1 when a run of several names holds one with bytes behind this round
-__global__ void k_rank_runs(Names nm, uint32_t n, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ head_scan, uint32_t round,
-                            uint32_t* __restrict__ run, uint32_t* __restrict__ more) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const uint32_t mine = head_scan[j + 1] - 1;
-    run[j] = mine;
-    const bool shared = (j > 0 && head_scan[j] - 1 == mine) || (j + 1 < n && head_scan[j + 2] - 1 == mine);
-    if (!shared) return;
-    uint64_t s, len;
-    nm.span(perm[j], &s, &len);
-    if (len > 8ull * (round + 1)) *more = 1;
-}
-
-struct RankScratch {
-    DevBuf<uint64_t> key, key2, rk, rk2;
-    DevBuf<uint32_t> iota, idx2, idx3, perm2, head, head_scan, more;
-};
-
-// perm[j] = the item at sorted position j (bytewise, a prefix first, equal names in item order); run[j] = the number of distinct
-// names in front of position j's; *n_runs distinct names
-int rank_strings(Names nm, uint32_t n, RankScratch& R, DevBuf<uint32_t>& perm, DevBuf<uint32_t>& run, uint32_t* n_runs, uint32_t* rounds,
-                 uint32_t* h_pair, hipStream_t st) {
-    *n_runs = 0;
-    if (n == 0) return SFGPU_OK;
-    for (DevBuf<uint64_t>* b : {&R.key, &R.key2, &R.rk, &R.rk2}) if (int r = b->reserve((uint64_t)n + 2, st, false)) return r;
-    for (DevBuf<uint32_t>* b : {&R.iota, &R.idx2, &R.idx3, &R.perm2, &R.head, &R.head_scan, &perm, &run})
-        if (int r = b->reserve((uint64_t)n + 3, st, false)) return r;
-    if (int r = R.more.reserve(2, st, false)) return r;
-    hipLaunchKernelGGL(k_rank_init, dim3(grid_of(n)), dim3(kBlock), 0, st, n, perm.p, run.p, R.iota.p);
-    SF_CHECK_LAUNCH();
-    for (uint32_t round = 0;; ++round) {
-        hipLaunchKernelGGL(k_rank_keys, dim3(grid_of(n)), dim3(kBlock), 0, st, nm, n, perm.p, round, R.key.p);
-        SF_CHECK_LAUNCH();
-        if (int r = sort_pairs_u64_u32(R.key.p, R.key2.p, R.iota.p, R.idx2.p, n, st, 64, false)) return r;
-        hipLaunchKernelGGL(k_rank_runs_of, dim3(grid_of(n)), dim3(kBlock), 0, st, n, run.p, R.idx2.p, R.rk.p);
-        SF_CHECK_LAUNCH();
-        if (int r = sort_pairs_u64_u32(R.rk.p, R.rk2.p, R.iota.p, R.idx3.p, n, st, 32, false)) return r;
-        hipLaunchKernelGGL(k_rank_apply, dim3(grid_of(n)), dim3(kBlock), 0, st, n, perm.p, R.idx2.p, R.idx3.p, R.key2.p, R.rk2.p, R.perm2.p, R.head.p);
-        SF_CHECK_LAUNCH();
-        if (int r = exclusive_scan_u32_u32(R.head.p, R.head_scan.p, n, st)) return r;
-        SF_HIP(hipMemsetAsync(R.more.p, 0, 4, st));
-        hipLaunchKernelGGL(k_rank_runs, dim3(grid_of(n)), dim3(kBlock), 0, st, nm, n, R.perm2.p, R.head_scan.p, round, run.p, R.more.p);
-        SF_CHECK_LAUNCH();
-        SF_HIP(hipMemcpyAsync(perm.p, R.perm2.p, (uint64_t)n * 4, hipMemcpyDeviceToDevice, st));
-        SF_HIP(hipMemcpyAsync(&h_pair[0], R.more.p, 4, hipMemcpyDeviceToHost, st));
-        SF_HIP(hipMemcpyAsync(&h_pair[1], R.head_scan.p + n, 4, hipMemcpyDeviceToHost, st));
-        SF_HIP(hipStreamSynchronize(st));
-        if (rounds) ++*rounds;
-        if (!h_pair[0]) break;
+    // ranksort.h's view of the names
+    __device__ uint64_t key(uint32_t item, uint32_t round) const {
+        uint64_t s, len, k = 0;
+        span(item, &s, &len);
+        const uint64_t at = 8ull * round;
+        for (uint32_t i = 0; i < 8; ++i) k = (k << 8) | (at + i < len ? blob[s + at + i] : 0u);
+        return k;
     }
-    *n_runs = h_pair[1];
-    return SFGPU_OK;
-}
+    __device__ uint64_t bytes(uint32_t item) const {
+        uint64_t s, len;
+        span(item, &s, &len);
+        return len;
+    }
+};
+
+using ranksort::RankScratch;
+using ranksort::rank_strings;
 
 // ---- finish ---------------------------------------------------------------------------------------------------------------
 

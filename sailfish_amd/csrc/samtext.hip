@@ -3,16 +3,9 @@
 // this file is the passes around them.  No pass walks a line: the cost of a call depends on its bytes and its lines, not on how
 // long a line or how large a group is.
 //
-// The text (whole lines) lies on the device as 16-byte groups.
-//   k_sam_count        per group: its '\n' and its '\t' bytes
-//   scans, k_sam_line_ends   where line j ends, and how many tabs stand in front of it
-//   k_sam_tabs         per group: the tab at p is tab number (tabs in front of p) - (tabs in front of its line) of line (newlines in
-//                      front of p); the first ten of a line are stored.  SEQ's length is a difference of two of them, so nobody
-//                      reads SEQ or QUAL.
-//   k_sam_lines        one lane per line: samfmt.h's sam_parse_line over FLAG, RNAME, POS and CIGAR; RNAME is looked up in the
-//                      handle's table (XXH64 of the name, linear probing, a byte compare behind every hash match).  The lowest
-//                      malformed line is a 64-bit min (one atomic per wavefront that holds one).
-//   scan, k_sam_compact   the non-header lines ("records of the text"), in order
+// The text (whole lines) lies on the device as 16-byte groups.  The line front end -- k_sam_count, k_sam_line_ends, k_sam_tabs,
+// k_sam_lines, k_sam_compact: where the lines and their tabs are and what each line says -- is samfront.h (the collated reading of
+// samcollate.hip runs it too).  Then
 //   k_sam_heads        record k begins a group when its QNAME differs from record k - 1's; a scan of the heads numbers the groups;
 //                      the last head is where a text that is not final is cut
 //   k_sam_pairs        pair heads are a neighbour test (sam_pairs_with); "this group has a pair" is a plain store of 1 by every pair
@@ -20,30 +13,22 @@
 //   k_sam_survive, scan, k_sam_keys   the lines that yield a record, compacted; d_off[group] = the survivors in front of its head;
 //                      key = (group, right orphan, tid)
 //   sort_pairs_u64_u32 (stable: ties stay in file order), k_sam_write   the records, sam_pair_hit / sam_single_hit
-// Everything from k_sam_pairs on lies in samback.h: bamtext.hip runs the same kernels behind its own front end.
+// Everything from k_sam_pairs on lies in samback.h: bamtext.hip runs the same kernels behind its own front end.  The host text is
+// staged by textstage.h.
 #include "common.h"
 #include "primitives.h"
 #include "samback.h"
 #include "samfmt.h"
+#include "samfront.h"
 #include "textlines.h"
+#include "textstage.h"
 #include "xxh64_device.h"
 
 namespace sfgpu {
 namespace {
 
-using textlines::eq_mask;
-using textlines::range_mask;
 using namespace samback;
-
-inline unsigned grid_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
-constexpr uint64_t kSubBytes = 4ull << 20;               // staged sub-chunk (a multiple of 16)
-constexpr uint64_t kMaxBytes = 1ull << 30;               // one parse call
-constexpr unsigned long long kNoBad = ~0ull;
-
-struct Bytes {
-    const unsigned char* p;
-    __device__ unsigned char operator()(uint32_t i) const { return p[i]; }
-};
+using namespace samfront;
 
 // ---- the name table -------------------------------------------------------------------------------------------------------
 
@@ -62,92 +47,6 @@ __global__ void k_sam_table(const unsigned char* __restrict__ blob, const uint64
         if (old == 0) return;
         if (T.is(old - 1, q, n)) { atomicOr(flag, 1u); return; }
     }
-}
-
-// ---- lines and tabs -------------------------------------------------------------------------------------------------------
-
-__global__ void k_sam_count(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, uint32_t* __restrict__ nl_cnt,
-                            uint32_t* __restrict__ tab_cnt) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups) return;
-    const uint4 v = buf[g];
-    const uint32_t in = range_mask(g * 16, 0, n_text);
-    nl_cnt[g] = __popc(eq_mask(v, '\n') & in);
-    tab_cnt[g] = __popc(eq_mask(v, '\t') & in);
-}
-
-// line_end[j] = the '\n' that ends line j; line_tab0[j] = the tabs in front of line j
-__global__ void k_sam_line_ends(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, const uint32_t* __restrict__ nl_scan,
-                                const uint32_t* __restrict__ tab_scan, uint32_t* __restrict__ line_end, uint32_t* __restrict__ line_tab0) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups) return;
-    const uint4 v = buf[g];
-    const uint32_t in = range_mask(g * 16, 0, n_text);
-    uint32_t nl = eq_mask(v, '\n') & in;
-    const uint32_t tabs = eq_mask(v, '\t') & in;
-    uint32_t at = nl_scan[g];
-    const uint32_t t0 = tab_scan[g];
-    if (g == 0) line_tab0[0] = 0;
-    while (nl) {
-        const int i = __ffs(nl) - 1;
-        nl &= nl - 1;
-        line_end[at] = (uint32_t)(g * 16 + i);
-        line_tab0[at + 1] = t0 + __popc(tabs & ((1u << i) - 1u));
-        ++at;
-    }
-}
-
-// tab_pos[ord * L + j] = the ord-th tab of line j, ord < kSamTabs (the array is preset to kSamNone)
-__global__ void k_sam_tabs(const uint4* __restrict__ buf, uint64_t n_groups, uint64_t n_text, const uint32_t* __restrict__ nl_scan,
-                           const uint32_t* __restrict__ tab_scan, const uint32_t* __restrict__ line_tab0, uint32_t L,
-                           uint32_t* __restrict__ tab_pos) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_groups) return;
-    const uint4 v = buf[g];
-    const uint32_t in = range_mask(g * 16, 0, n_text);
-    const uint32_t tabs = eq_mask(v, '\t') & in;
-    if (!tabs) return;
-    const uint32_t nl = eq_mask(v, '\n') & in;
-    const uint32_t j0 = nl_scan[g];
-    uint32_t t = tab_scan[g];
-    for (uint32_t w = tabs; w; w &= w - 1, ++t) {
-        const int i = __ffs(w) - 1;
-        const uint32_t j = j0 + __popc(nl & ((1u << i) - 1u));
-        if (j >= L) return;                               // (the text ends in a '\n': no tab stands behind the last line)
-        const uint32_t ord = t - line_tab0[j];
-        if (ord < kSamTabs) tab_pos[(uint64_t)ord * L + j] = (uint32_t)(g * 16 + i);
-    }
-}
-
-// One lane per line.  No lane leaves before the shuffles.
-__global__ void __launch_bounds__(kBlock) k_sam_lines(const unsigned char* __restrict__ bytes, uint32_t L, const uint32_t* __restrict__ line_end,
-                                                      const uint32_t* __restrict__ tab_pos, int paired, NameTable T, uint32_t* __restrict__ info,
-                                                      uint32_t* __restrict__ tid, int32_t* __restrict__ pos, uint32_t* __restrict__ isrec,
-                                                      unsigned long long* __restrict__ first_bad) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long key = kNoBad;
-    if (j < L) {
-        const Bytes get{bytes};
-        const uint32_t s = j ? line_end[j - 1] + 1 : 0;
-        const uint32_t e = sam_line_end(get, s, line_end[j]);
-        uint32_t tab[kSamTabs];
-#pragma unroll
-        for (uint32_t o = 0; o < kSamTabs; ++o) tab[o] = tab_pos[(uint64_t)o * L + j];
-        const SamLine l = sam_parse_line(get, s, e, tab, paired != 0, [&](uint32_t a, uint32_t n) { return T.find(bytes + a, n); });
-        info[j] = pack_line(l); tid[j] = l.tid; pos[j] = l.pos; isrec[j] = l.header ? 0u : 1u;
-        if (l.bad) key = ((unsigned long long)j << 8) | l.bad;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o);
-        key = other < key ? other : key;
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0 && key != kNoBad) atomicMin(first_bad, key);
-}
-
-__global__ void k_sam_compact(uint32_t L, const uint32_t* __restrict__ isrec, const uint32_t* __restrict__ rec_scan, uint32_t* __restrict__ rec_line) {
-    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < L && isrec[j]) rec_line[rec_scan[j]] = j;
 }
 
 // ---- groups, pairs, records -----------------------------------------------------------------------------------------------
@@ -175,13 +74,10 @@ __global__ void k_sam_cut(uint32_t K, const uint32_t* __restrict__ head, const u
     cut[0] = k; cut[1] = j; cut[2] = j ? line_end[j - 1] + 1 : 0;
 }
 
-struct Scratch {
+struct Scratch : Front {                          // (word[1]: the pairs)
     DevBuf<uint4> text;
-    DevBuf<uint32_t> nl_cnt, nl_scan, tab_cnt, tab_scan, line_end, line_tab0, tab_pos, info, tid, isrec, rec_scan, rec_line, head, head_scan,
-        pair_head, has_pair, surv, surv_scan, val, val2, cut;
-    DevBuf<int32_t> pos;
+    DevBuf<uint32_t> rec_line, head, head_scan, pair_head, has_pair, surv, surv_scan, val, val2, cut;
     DevBuf<uint64_t> key, key2;
-    DevBuf<unsigned long long> word;              // [0] the lowest malformed line, [1] the pairs
 };
 
 }  // namespace
@@ -196,37 +92,13 @@ namespace {
 int parse_device_text(sfgpu_sam* m, Scratch& S, const uint4* text, uint64_t n_text, uint64_t used, bool final, sfgpu_hit* d_hits,
                       uint64_t cap_hits, uint32_t* d_off, uint64_t cap_reads, sfgpu_sam_result* res, hipStream_t st, uint64_t* h) {
     const unsigned char* bytes = reinterpret_cast<const unsigned char*>(text);
-    const uint64_t n_groups = (n_text + 15) / 16;
     uint32_t* h32 = reinterpret_cast<uint32_t*>(h);
-    for (DevBuf<uint32_t>* b : {&S.nl_cnt, &S.nl_scan, &S.tab_cnt, &S.tab_scan}) if (int r = b->reserve(n_groups + 2, st, false)) return r;
-    if (int r = S.word.reserve(2, st, false)) return r;
     if (int r = S.cut.reserve(4, st, false)) return r;
-    hipLaunchKernelGGL(k_sam_count, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_cnt.p, S.tab_cnt.p);
-    SF_CHECK_LAUNCH();
-    if (int r = exclusive_scan_u32_u32(S.nl_cnt.p, S.nl_scan.p, n_groups, st)) return r;
-    if (int r = exclusive_scan_u32_u32(S.tab_cnt.p, S.tab_scan.p, n_groups, st)) return r;
-    SF_HIP(hipMemcpyAsync(&h32[0], S.nl_scan.p + n_groups, 4, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    const uint32_t L = h32[0];
+    uint32_t L = 0;
+    if (int r = sam_front_lines(m, S, text, n_text, st, h32, &L)) return r;
     if (L == 0) return SFGPU_OK;
 
     // ---- the lines
-    for (DevBuf<uint32_t>* b : {&S.line_end, &S.line_tab0, &S.info, &S.tid, &S.isrec, &S.rec_scan}) if (int r = b->reserve((uint64_t)L + 2, st, false)) return r;
-    if (int r = S.pos.reserve((uint64_t)L + 2, st, false)) return r;
-    if (int r = S.tab_pos.reserve((uint64_t)kSamTabs * L, st, false)) return r;
-    SF_HIP(hipMemsetAsync(S.tab_pos.p, 0xff, (uint64_t)kSamTabs * L * 4, st));
-    SF_HIP(hipMemsetAsync(S.word.p, 0xff, 8, st));
-    SF_HIP(hipMemsetAsync(S.word.p + 1, 0, 8, st));
-    hipLaunchKernelGGL(k_sam_line_ends, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_scan.p, S.tab_scan.p, S.line_end.p,
-                       S.line_tab0.p);
-    SF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_sam_tabs, dim3(grid_of(n_groups)), dim3(kBlock), 0, st, text, n_groups, n_text, S.nl_scan.p, S.tab_scan.p, S.line_tab0.p, L,
-                       S.tab_pos.p);
-    SF_CHECK_LAUNCH();
-    const NameTable T{m->blob.p, m->off.p, m->slot.p, m->mask};
-    hipLaunchKernelGGL(k_sam_lines, dim3(grid_of(L)), dim3(kBlock), 0, st, bytes, L, S.line_end.p, S.tab_pos.p, m->paired ? 1 : 0, T, S.info.p, S.tid.p,
-                       S.pos.p, S.isrec.p, S.word.p);
-    SF_CHECK_LAUNCH();
     if (int r = exclusive_scan_u32_u32(S.isrec.p, S.rec_scan.p, L, st)) return r;
     SF_HIP(hipMemcpyAsync(&h[1], S.word.p, 8, hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(&h32[0], S.rec_scan.p + L, 4, hipMemcpyDeviceToHost, st));
@@ -382,49 +254,17 @@ extern "C" int sfgpu_sam_parse_host(sfgpu_sam* m, const char* h_text, uint64_t n
     if (!final) while (used && h_text[used - 1] != '\n') --used;
     if (used == 0) { SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
     const bool append = h_text[used - 1] != '\n';            // (final only)
-    const uint64_t n_text = used + (append ? 1 : 0), n_groups = (n_text + 15) / 16, n_sub = (used + kSubBytes - 1) / kSubBytes;
+    const uint64_t n_text = used + (append ? 1 : 0);
 
     Scratch S;
     CallScope scope;        // after S: it drains both streams before S's blocks go back to the pool
-    hipStream_t cs = nullptr;
-    char* pinned[2] = {nullptr, nullptr};
-    hipEvent_t ev_slot[2] = {nullptr, nullptr}, ev_c0 = nullptr, ev_c1 = nullptr, ev_k0 = nullptr, ev_k1 = nullptr;
-    uint64_t* h = nullptr;
-    SF_HIP(scope.adopt(st));
-    SF_HIP(scope.acquire(&cs));
-    for (int b = 0; b < 2 && (uint64_t)b < n_sub; ++b) {
-        SF_HIP(scope.pinned_block(&pinned[b], (used < kSubBytes ? used : kSubBytes) + 48));
-        SF_HIP(scope.event(&ev_slot[b]));
-    }
-    for (hipEvent_t* e : {&ev_c0, &ev_c1, &ev_k0, &ev_k1}) SF_HIP(scope.event(e));
-    SF_HIP(scope.pinned_block(&h, 8 * sizeof(uint64_t)));
-    if (int r = S.text.reserve(n_groups + 1, st, false)) return r;
-    SF_HIP(hipEventRecord(ev_k0, st));
-    SF_HIP(hipStreamWaitEvent(cs, ev_k0, 0));                // the copies stay behind whatever `stream` held and behind the reservation
-    SF_HIP(hipEventRecord(ev_c0, cs));
-    for (uint64_t c = 0; c < n_sub; ++c) {
-        const int slot = (int)(c & 1);
-        if (c >= 2) SF_HIP(hipEventSynchronize(ev_slot[slot]));      // its previous copy has left the pinned buffer
-        const uint64_t p = c * kSubBytes, q = (c + 1 == n_sub) ? used : p + kSubBytes;
-        uint64_t n = q - p;
-        memcpy(pinned[slot], h_text + p, n);
-        if (c + 1 == n_sub) {
-            if (append) pinned[slot][n++] = '\n';
-            const uint64_t padded = (n + 15) & ~15ull;
-            memset(pinned[slot] + n, 0, padded - n);
-            n = padded;
-        }
-        SF_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.text.p) + p, pinned[slot], n, hipMemcpyHostToDevice, cs));
-        SF_HIP(hipEventRecord(ev_slot[slot], cs));
-    }
-    SF_HIP(hipEventRecord(ev_c1, cs));
-    SF_HIP(hipStreamWaitEvent(st, ev_c1, 0));
-    SF_HIP(hipEventRecord(ev_k0, st));
-    const int rc = parse_device_text(m, S, S.text.p, n_text, used, final != 0, d_hits, cap_hits, d_off, cap_reads, res, st, h);
-    SF_HIP(hipEventRecord(ev_k1, st));
+    HostStage H;
+    if (int r = stage_host_text(scope, H, S.text, h_text, used, append, st)) return r;
+    const int rc = parse_device_text(m, S, S.text.p, n_text, used, final != 0, d_hits, cap_hits, d_off, cap_reads, res, st, H.h);
+    SF_HIP(hipEventRecord(H.ev_k1, st));
     SF_HIP(hipStreamSynchronize(st));
-    add_elapsed(&res->ms_copy, ev_c0, ev_c1);
-    add_elapsed(&res->ms_kernels, ev_k0, ev_k1);
+    add_elapsed(&res->ms_copy, H.ev_c0, H.ev_c1);
+    add_elapsed(&res->ms_kernels, H.ev_k0, H.ev_k1);
     return rc;
 }
 

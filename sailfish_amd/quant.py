@@ -100,13 +100,18 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
 
 
 def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, transcripts_path=None, device="cuda", block_bytes=32 << 20,
-                 inflate="auto", **kw):
+                 inflate="auto", collate=False, **kw):
     """`sailfish quant` from a mapper's SAM file on (RapMap's `quasimap -o`, bowtie2, bwa against the transcriptome; plain, BGZF or
     gzip; grouped by read name): the names and lengths come from the @SQ lines, the alignment lines are turned into hit records
     on the device (samfile.SamFile) and handed to quantify batch by batch.  `sam_path` may as well be the BAM file that
     `samtools view -b` made of that output (name-grouped, not position-sorted): the names and lengths then come from its binary
     reference list, and its record stream is parsed on the device behind the BGZF inflate.  transcripts_path: the transcript FASTA, required with
     biasCorrect / gcBiasCorrect (read with readfile.read_transcripts; its names and lengths must equal the header's, in order).
+    collate: False, True or "auto", handed to samfile.SamFile: True reads a file whose lines stand in any order (a position-sorted
+    SAM or BAM file, what `samtools sort` leaves) by collecting it on the device, grouping the lines by QNAME exactly and pairing
+    them through their mate fields; "auto" does so iff the header says SO:coordinate.  The fragments then arrive in the order of
+    their first lines, and the fragment-length sample (numFragSamples) is taken from the fragments that appear first, as always: in
+    a position-sorted file those are the fragments of the first transcripts, not a sample of the whole library.
     -> (rc, experiment)"""
     from . import samfile
     sopt = sopt or SailfishOpts()
@@ -125,7 +130,7 @@ def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, tr
             raise ValueError(f"{transcripts_path}: the names and lengths of the transcripts are not those of the @SQ lines of {sam_path}")
         s, o = _dollar_separated(bases, off)
         seq_kw = dict(seq=s, seq_off=o)
-    batches = samfile.SamFile(sam_path, device, fmt[0] == 1, names=names, block_bytes=block_bytes, inflate=inflate)
+    batches = samfile.SamFile(sam_path, device, fmt[0] == 1, names=names, block_bytes=block_bytes, inflate=inflate, collate=collate)
     try:
         return quantify(names, np.array(lengths, np.uint32), batches, lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     finally:

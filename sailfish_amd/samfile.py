@@ -6,8 +6,10 @@ BGZF and -- with inflate="device" -- ordinary gzip inflated on the device and pa
 `(hits, offsets)` batches that `hits.filter_hits` and `quant.quantify` take.  Nothing of the alignment lines is parsed on the host.
 The header is: `read_header` reads the @SQ lines with Python, they are a thousandth of a real file.
 
-The file must be grouped by read name, as mappers write it (all lines of a fragment follow each other); a position-sorted file
-is not.  `write_sam` is the way back: hit records as SAM text, the host statement (`_sam_text`); `SamDeviceWriter` writes the same
+The file must be grouped by read name, as mappers write it (all lines of a fragment follow each other), unless it is read with
+`collate=True`: then the lines may stand in any order -- a position-sorted file, what `samtools sort` leaves -- and the whole file
+is collected on the device, grouped by QNAME exactly and paired through the mate fields (csrc/samcfmt.h, csrc/samcollate.hip;
+`read_sam_collated_host` / `read_bam_collated_host` are the contract).  `write_sam` is the way back: hit records as SAM text, the host statement (`_sam_text`); `SamDeviceWriter` writes the same
 file from the device mapper's batches where they lie (sfgpu_sam_write_text, csrc/samtext_write.hip, rules in csrc/samwfmt.h).
 
 BAM (what `samtools view -b` makes of the same alignments) is read too: a BGZF file whose first member inflates to "BAM\1".  What
@@ -24,6 +26,7 @@ import numpy as np
 from .hits import HIT_DTYPE
 
 BAD_FIELDS, BAD_NUMBER, BAD_FLAG, BAD_RNAME, BAD_CIGAR, BAD_LENGTH = 1, 2, 4, 8, 16, 32
+BAD_QNAME = 64                                         # the collated reading only (COLLATED_KINDS)
 KINDS = {BAD_FIELDS: "fewer than 11 tab-separated fields",
          BAD_NUMBER: "FLAG is not a number up to 65535, or POS of a mapped line is not a number in 1 .. 2^31 - 1",
          BAD_FLAG: "the FLAG does not fit the library: a paired call needs 0x1 and exactly one of 0x40 / 0x80, a single-end call no 0x1",
@@ -37,6 +40,10 @@ BAM_KINDS = {BAD_FIELDS: "block_size is below 32 or below what l_read_name, n_ci
              BAD_RNAME: "refID of a mapped record is not in 0 .. n_ref - 1, or its reference is not one of the transcript names",
              BAD_CIGAR: "a CIGAR op code above 8",
              BAD_LENGTH: "the read is longer than 65535 bases, or l_seq and the CIGAR disagree about its length"}
+# what the collated reading (collate=True) adds to KINDS: PNEXT is read, QNAME is bounded
+COLLATED_KINDS = {**KINDS,
+                  BAD_NUMBER: KINDS[BAD_NUMBER] + ", or (collated, paired) PNEXT of a mapped line is not a number in 0 .. 2^31 - 1",
+                  BAD_QNAME: "QNAME is longer than 254 bytes"}
 BAM_MAGIC = b"BAM\x01"
 _CIGAR = re.compile(rb"(?:[0-9]{1,9}[MIDNSHP=X])+")
 _CIGAR_OP = re.compile(rb"([0-9]+)([MIDNSHP=X])")
@@ -45,6 +52,10 @@ _LEAD = re.compile(rb"(?:[0-9]+H)*((?:[0-9]+S)*)")
 
 def _malformed(path, line, kind):
     return ValueError(f"{path}: line {line} is malformed: {KINDS[kind]} (kind {kind})")
+
+
+def _malformed_collated(path, line, kind):
+    return ValueError(f"{path}: line {line} is malformed: {COLLATED_KINDS[kind]} (kind {kind})")
 
 
 def _malformed_bam(path, record, kind):
@@ -297,6 +308,142 @@ def read_bam_host(data, names, paired, path="<bam>", counts=None):
     if counts is not None:
         counts.update(lines=n, header=0, reads=len(groups), hits=len(recs), pairs=sum(r[8] == 3 for r in recs))
     return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
+
+
+# ---- the collated contract (csrc/samcfmt.h) -----------------------------------------------------------------------------------
+
+def _line_mate(line, paired):
+    """what the collated reading adds to _parse_line for one non-header line -> (kinds, POS, PNEXT): the BAD_* bits it adds, the
+    written POS of a mapped line, and PNEXT when the line names a mate (else 0).  A line that is BAD_FIELDS or whose FLAG is no
+    number is not looked at (it is malformed already, by an earlier rule)."""
+    f = line.split(b"\t")
+    if len(f) < 11 or not (f[1].isdigit() and len(f[1]) <= 5 and int(f[1]) <= 65535):
+        return 0, 0, 0
+    flag, bad = int(f[1]), 0
+    if len(f[0]) > 254:
+        bad |= BAD_QNAME
+    if flag & (0x4 | 0x800):
+        return bad, 0, 0
+    pos = int(f[3]) if f[3].isdigit() and len(f[3]) <= 10 and 1 <= int(f[3]) <= 2 ** 31 - 1 else 0      # (else BAD_NUMBER already)
+    if not paired:
+        return bad, pos, 0
+    if not (f[7].isdigit() and len(f[7]) <= 10 and int(f[7]) <= 2 ** 31 - 1):
+        return bad | BAD_NUMBER, pos, 0
+    names_mate = not flag & 0x8 and f[6] in (b"=", f[2]) and int(f[7]) >= 1
+    return bad, pos, int(f[7]) if names_mate else 0
+
+
+def _record_mate(data, p, paired):
+    """the same for the BAM record at p (mapped, well-formed) -> (POS, PNEXT or 0)"""
+    _bs, ref, pos, _l, _mq, _bin, _nc, flag, _ls, nref, npos = struct.unpack_from("<iiiBBHHHIii", data, p)
+    names_mate = paired and not flag & 0x8 and nref == ref and npos >= 0
+    return pos + 1, npos + 1 if names_mate else 0
+
+
+def _collated_records(lines, paired):
+    """the records of one fragment: lines = [(rec, POS, PNEXT)] in file order, rec as _parse_line returns it"""
+    pairs = []
+    if paired:
+        by_key = {}                                   # (tid, POS of mate 1, POS of mate 2) -> (side-1 lines, side-2 lines), file order
+        for n, (l, pos, pnext) in enumerate(lines):
+            if l[1] and pnext:
+                key = (l[3], pos, pnext) if l[2] == 1 else (l[3], pnext, pos)
+                by_key.setdefault(key, ([], []))[l[2] - 1].append(n)
+        for ones, twos in by_key.values():
+            for na, nb in zip(ones, twos):            # the i-th with the i-th; what is left over pairs with nothing
+                a, b = lines[na][0], lines[nb][0]
+                frag = max(a[4] + a[5], b[4] + b[5]) - min(a[4], b[4])
+                pairs.append((na, (a[3], a[4], b[4], frag, a[5], b[5], a[6], b[6], 3, 0)))
+    if pairs:
+        return [r for _, r in sorted(pairs, key=lambda x: (x[1][0], x[0]))]      # tid, then the side-1 line's place in the file
+    singles = [(l[3], l[4], 0, 0, l[5], 0, l[6], 0, l[2], 0) for l, _, _ in lines if l[1]]
+    return sorted(singles, key=lambda r: (r[8] == 2, r[0]))
+
+
+def _collated_result(frags, paired, counts, n_lines, n_header):
+    recs, off = [], [0]
+    for g in frags.values():                          # (a dict keeps the order of first insertion: of the fragments' first lines)
+        recs.extend(_collated_records(g, paired))
+        off.append(len(recs))
+    if counts is not None:
+        counts.update(lines=n_lines, header=n_header, reads=len(frags), hits=len(recs), pairs=sum(r[8] == 3 for r in recs))
+    return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
+
+
+def read_sam_collated_host(data, names, paired, path="<sam>", counts=None):
+    """The rules of the collated reading (csrc/samcfmt.h), on the host, written to be read: what read_sam_host returns, for a text
+    whose lines may stand in any order.  ALL non-header lines with byte-equal QNAME are one fragment, numbered by their first
+    lines; a mapped line of a paired call NAMES A MATE iff FLAG lacks 0x8, RNEXT is "=" or its RNAME, and PNEXT >= 1; a side-1 line a
+    and a side-2 line b of a fragment pair when both are mapped on one transcript, both name a mate, a.PNEXT == b.POS and
+    b.PNEXT == a.POS (the written POS), the i-th such a with the i-th such b in file order.  What a fragment yields, and in which
+    order, is read_sam_host's.  Raises the ValueError SamFile(collate=True) raises."""
+    tid_of = {nm: i for i, nm in enumerate(_name_bytes(names))}
+    lines = data.split(b"\n")
+    if lines[-1] == b"":
+        lines.pop()
+    frags, n_header = {}, 0
+    for n, line in enumerate(lines, 1):
+        if line.endswith(b"\r"):
+            line = line[:-1]
+        if line.startswith(b"@"):
+            n_header += 1
+            continue
+        kind, rec = _parse_line(line, tid_of, paired)
+        more, pos, pnext = _line_mate(line, paired)
+        kind |= more
+        if kind:
+            raise _malformed_collated(path, n, kind & -kind)
+        frags.setdefault(rec[0], []).append((rec, pos, pnext))
+    return _collated_result(frags, paired, counts, len(lines), n_header)
+
+
+def read_bam_collated_host(data, names, paired, path="<bam>", counts=None):
+    """The same for an inflated BAM stream: read_bam_host's walk of the record chain, read_sam_collated_host's fragments and pairs.
+    A record names a mate iff FLAG lacks 0x8, next_refID == refID and next_pos >= 0; POS and PNEXT are pos + 1 and next_pos + 1."""
+    data = bytes(data)
+    head = _bam_header(data)
+    if head is None:
+        raise ValueError(f"{path}: the file ends inside the BAM header")
+    refs, _, p, _ = head
+    tid_of = {nm: i for i, nm in enumerate(_name_bytes(names))}
+    ref_tid = [tid_of.get(r) for r in _name_bytes(refs)]
+    frags, n = {}, 0
+    while p < len(data):
+        n += 1
+        if len(data) - p < 4:
+            raise _malformed_bam(path, n, BAD_FIELDS)
+        block_size = struct.unpack_from("<i", data, p)[0]
+        if block_size < 32 or p + 4 + block_size > len(data):
+            raise _malformed_bam(path, n, BAD_FIELDS)
+        kind, rec = _parse_record(data, p, ref_tid, paired)
+        if kind:
+            raise _malformed_bam(path, n, kind)
+        pos, pnext = _record_mate(data, p, paired) if rec[1] else (0, 0)
+        frags.setdefault(rec[0], []).append((rec, pos, pnext))
+        p += 4 + block_size
+    return _collated_result(frags, paired, counts, n, 0)
+
+
+def header_sort_order(path):
+    """the SO: tag of the @HD line of a SAM file (plain or gzip) or of the header text a BAM file carries, e.g. "coordinate",
+    "queryname", "unsorted"; None without an @HD line or without the tag"""
+    if is_bam(path):
+        lines = read_bam_header(path)[3].split(b"\n")
+    else:
+        lines = []
+        with _open_text(path) as f:
+            for line in f:
+                if not line.startswith(b"@"):
+                    break
+                lines.append(line)
+    for line in lines:
+        fields = line.rstrip(b"\r\n").split(b"\t")
+        if fields[0] == b"@HD":
+            for x in fields[1:]:
+                if x.startswith(b"SO:"):
+                    return x[3:].decode("utf-8", "surrogateescape")
+            return None
+    return None
 
 
 # ---- SAM text <-> BAM stream (host) ------------------------------------------------------------------------------------------
@@ -762,14 +909,31 @@ class SamFile:
     `format` says what the file is: "sam" or "bam" (a gzip file whose first bytes inflate to "BAM\1").  A BAM file goes through
     readfile.DeviceInflate and sfgpu_bam_parse_device (inflate "auto" or "device") or gzip, BlockCarry and sfgpu_bam_parse_host
     ("host", and whenever the gzip file is not BGZF); its reference list is the default for `names`, `lines` counts its alignment
-    records (`header_lines` stays 0) and a malformed record is named by its 1-based number among them (BAM_KINDS)."""
+    records (`header_lines` stays 0) and a malformed record is named by its 1-based number among them (BAM_KINDS).
 
-    def __init__(self, path, device="cuda", paired=True, names=None, block_bytes=32 << 20, inflate="auto"):
+    `collate`: False (the default) reads a name-grouped file as described.  True reads a file whose lines stand in any order -- a
+    position-sorted one -- by the rules of csrc/samcfmt.h (read_sam_collated_host / read_bam_collated_host): iterating first runs
+    the whole file through sfgpu_sam_collect_* / sfgpu_bam_collect_* (the same carriers, one call per block), which keeps 32 bytes
+    and the QNAME of every alignment line on the device; sfgpu_samc_finish then groups the lines by QNAME exactly and pairs them
+    through their mate fields, and the batches are slices of `batch_reads` fragments (sfgpu_samc_emit), numbered by their first
+    lines.  "auto" collates iff the header says SO:coordinate (header_sort_order).  `collated` says what was decided.  `stats` then
+    also holds fragments, sort_rounds, state_bytes (device memory held while the batches are emitted), ms_collect, ms_finish and
+    ms_emit; `blocks` counts the collect calls that consumed something.  A malformed line raises the same ValueError (COLLATED_KINDS
+    for SAM text) before any batch is emitted."""
+
+    def __init__(self, path, device="cuda", paired=True, names=None, block_bytes=32 << 20, inflate="auto", collate=False, batch_reads=1_000_000):
         import torch
 
         from . import _lib, readfile
         if inflate not in ("auto", "host", "device"):
             raise ValueError("inflate must be 'auto', 'host' or 'device'")
+        if collate not in (False, True, "auto"):
+            raise ValueError("collate must be False, True or 'auto'")
+        if int(batch_reads) < 1:
+            raise ValueError("batch_reads must be at least 1")
+        self.collated = header_sort_order(str(path)) == "coordinate" if collate == "auto" else bool(collate)
+        self.batch_reads = int(batch_reads)
+        self._c = None
         self.path, self.device, self.paired = str(path), torch.device(device), bool(paired)
         self.format = "bam" if is_bam(self.path) else "sam"
         if self.format == "bam":
@@ -790,6 +954,9 @@ class SamFile:
         self.stats = dict(lines=0, header_lines=0, reads=0, hits=0, pairs=0, blocks=0, calls=0, bytes_parsed=0, ms_copy=0.0, ms_kernels=0.0,
                           ms_inflate=0.0, bytes_compressed=0, members=0, chunks=0, candidates=0, false_starts=0, ms_find=0.0, ms_decode=0.0,
                           ms_propagate=0.0, ms_emit=0.0)
+        if self.collated:
+            self.stats.update(fragments=0, sort_rounds=0, state_bytes=0, ms_collect=0.0, ms_finish=0.0)
+
         def on_device(items):
             nb = _name_bytes(items)
             blob = np.frombuffer(b"".join(nb), np.uint8)
@@ -808,6 +975,10 @@ class SamFile:
         if rc == _lib.ERR_INVALID:
             raise ValueError(f"{self.path}: {self._L.sfgpu_last_error().decode('utf-8', 'replace')}")
         _lib.check(rc)
+        if self.collated:
+            self._c = C.c_void_p()
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.sfgpu_samc_open(C.byref(self._c), int(self.paired), _lib.current_stream_ptr()))
         if self.inflate == "device":
             self._f = open(self.path, "rb", buffering=0)
             self._carry = (readfile.DeviceInflate if bgzf else readfile.DeviceGunzip)(self, self._f, block_bytes)
@@ -844,9 +1015,31 @@ class SamFile:
             st[k] += int(v)
         return readfile.Parsed(int(res.n_reads), int(res.consumed), (hits[: int(res.n_hits) * 24].clone(), off[: int(res.n_reads) + 1].clone()))
 
+    def _collect(self, final, call):
+        """one collect call -> readfile.Parsed: n_reads is 1 when the call consumed something (the carriers' "go on"), else 0"""
+        import torch
+
+        from . import _lib, readfile
+        res = _lib.SamResult()
+        with torch.cuda.device(self.device):
+            rc = call(res)
+        if rc == _lib.ERR_FORMAT and res.bad:
+            raise (_malformed_bam if self.format == "bam" else _malformed_collated)(self.path, self.stats["lines"] + int(res.bad_line) + 1, int(res.bad))
+        _lib.check(rc)
+        st = self.stats
+        st["calls"] += 1; st["ms_copy"] += res.ms_copy; st["ms_kernels"] += res.ms_kernels; st["ms_collect"] += res.ms_kernels
+        if not (res.consumed or final):
+            return readfile.Parsed(0, 0)                   # no whole line or record yet: the carrier presents more
+        for k, v in (("lines", res.n_lines), ("header_lines", res.n_header), ("blocks", 1), ("bytes_parsed", res.consumed)):
+            st[k] += int(v)
+        return readfile.Parsed(1 if res.consumed else 0, int(res.consumed))
+
     def _parse_host(self, text, final, _max_reads):
         from . import _lib
         n = int(text.size)
+        if self.collated:
+            collect = self._L.sfgpu_bam_collect_host if self.format == "bam" else self._L.sfgpu_sam_collect_host
+            return self._collect(final, lambda res: collect(self._h, self._c, _lib.ptr(text), n, int(final), C.byref(res), _lib.current_stream_ptr()))
         parse = self._L.sfgpu_bam_parse_host if self.format == "bam" else self._L.sfgpu_sam_parse_host
         return self._call(n, final, lambda hits, ch, off, cr, res: parse(
             self._h, _lib.ptr(text), n, int(final), _lib.ptr(hits), ch, _lib.ptr(off), cr, C.byref(res), _lib.current_stream_ptr()))
@@ -858,6 +1051,12 @@ class SamFile:
             text[:n] = text[lo:hi].clone()
             self._carry.lo, self._carry.hi, lo, hi = 0, n, 0, n
         view = text[lo:]
+        if self.collated:
+            collect = self._L.sfgpu_bam_collect_device if self.format == "bam" else self._L.sfgpu_sam_collect_device
+            out = self._collect(final, lambda res: collect(self._h, self._c, _lib.ptr(view), n, view.numel(), int(final), C.byref(res),
+                                                           _lib.current_stream_ptr()))
+            self._carry.starved = True                     # what is left is a line or record that has not ended: inflate before the next call
+            return out
         parse = self._L.sfgpu_bam_parse_device if self.format == "bam" else self._L.sfgpu_sam_parse_device
         out = self._call(n, final, lambda hits, ch, off, cr, res: parse(
             self._h, _lib.ptr(view), n, view.numel(), int(final), _lib.ptr(hits), ch, _lib.ptr(off), cr, C.byref(res), _lib.current_stream_ptr()))
@@ -865,10 +1064,43 @@ class SamFile:
             self._carry.starved = True                     # what is left is one group that has not ended: inflate before the next call
         return out
 
+    def _iter_collated(self):
+        """the whole file through the collect calls, finish, then slices of batch_reads fragments"""
+        import torch
+
+        from . import _lib
+        while (self._carry.next(1 << 62) if self.inflate == "device" else self._carry.next(self._parse_host, 1 << 62)) is not None:
+            pass
+        info = _lib.SamcInfo()
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.sfgpu_samc_finish(self._c, C.byref(info), _lib.current_stream_ptr()))
+        st = self.stats
+        st.update(fragments=int(info.n_reads), sort_rounds=int(info.sort_rounds), state_bytes=int(info.state_bytes), ms_finish=info.ms_finish)
+        total, first, per_read = int(info.n_reads), 0, max(1, -(-int(info.n_hits) // max(1, int(info.n_reads))))
+        while first < total:
+            n = min(self.batch_reads, total - first)
+            cap_hits = n * per_read + 1024                 # a guess: the call says what it needs
+            off = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+            res = _lib.SamResult()
+            with torch.cuda.device(self.device):
+                for _ in range(2):
+                    hits = torch.empty(cap_hits * 24, dtype=torch.uint8, device=self.device)
+                    rc = self._L.sfgpu_samc_emit(self._c, first, n, _lib.ptr(hits), cap_hits, _lib.ptr(off), C.byref(res), _lib.current_stream_ptr())
+                    if rc != _lib.ERR_CAPACITY:
+                        break
+                    cap_hits = int(res.need_hits)
+            _lib.check(rc)
+            st["reads"] += n; st["hits"] += int(res.n_hits); st["pairs"] += int(res.n_pairs); st["ms_emit"] += res.ms_kernels
+            first += n
+            yield hits[: int(res.n_hits) * 24], off
+
     def __iter__(self):
         if self._h is None:
             raise ValueError("the SAM file is closed")
         try:
+            if self.collated:
+                yield from self._iter_collated()
+                return
             while True:
                 res = self._carry.next(1 << 62) if self.inflate == "device" else self._carry.next(self._parse_host, 1 << 62)
                 if res is None:
@@ -882,7 +1114,9 @@ class SamFile:
             import torch
             with torch.cuda.device(self.device):
                 (self._L.sfgpu_bam_close if self.format == "bam" else self._L.sfgpu_sam_close)(self._h)
-            self._h = None
+                if self._c is not None:
+                    self._L.sfgpu_samc_close(self._c)
+            self._h = self._c = None
             self._f.close()
             if self.inflate == "device":
                 self._carry.close()

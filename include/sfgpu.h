@@ -841,6 +841,55 @@ SFGPU_API int sfgpu_sam_write_bgzf_q(const struct sfgpu_hit* d_hits, const uint3
                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
                                      int oriented);
+/* The compressed size of every member a BGZF handle writes, kept on the device: what virtual file offsets are made of.
+ *   track_members  from this call on every write also keeps its members' sizes (4 bytes a member of device memory, in file order).
+ *                  The bytes written, the results and the other calls do not change.
+ *   member_sizes   *d_sizes[0 .. *n_members): the sizes of the members written since, the EOF member not among them; the pointer
+ *                  holds until the next write.  SFGPU_ERR_STATE on a handle that does not track. */
+SFGPU_API int sfgpu_bgzw_track_members(sfgpu_bgzw* z);
+SFGPU_API int sfgpu_bgzw_member_sizes(sfgpu_bgzw* z, const uint32_t** d_sizes, uint64_t* n_members);
+/* A coordinate-sorted BAM file with its BAI index, from the device.  What the file and the index say -- the order, the member cut,
+ * virtual offsets, chunks, the linear index -- is stated once in csrc/baifmt.h; the kernels are csrc/bamsort.hip; the Python
+ * statements are samfile.write_bam(sort="coordinate") and samfile.build_bai.
+ *   open     an empty record store on the current device.
+ *   collect  the arguments, checks, errors and `out` of sfgpu_sam_write_bgzf_q with SFGPU_SAMW_BAM, the handle in place of `z` (and no
+ *            chunk_bytes): the batch's records are formatted into one device segment owned by the handle and listed (key, address,
+ *            length); out->n_chunks stays 0.  A batch that breaks a rule stores nothing.  The store holds fewer than 2^32 records:
+ *            the call that would reach that returns SFGPU_ERR_RANGE and stores nothing.  Device memory: the records' bytes and
+ *            20 bytes a record; nothing is spilled to the host.
+ *   finish   `z` must track its members (sfgpu_bgzw_track_members, from its first write) and hold the file's header already.  The
+ *            records are sorted stably by (uint32)refID << 32 | (uint32)(pos + 1), gathered into the sorted stream in pieces of
+ *            piece_bytes (0 = 32 MiB, else 16 .. 2^30; rounded down to a multiple of 32 768, at least that) and written through `z`,
+ *            piece i + 1 gathered while piece i is encoded: the file does not depend on piece_bytes.  With index_sink != NULL the
+ *            BAI of n_refs references is then built on the device and handed to index_sink in pieces of at most 32 MiB (a nonzero
+ *            return: SFGPU_ERR_IO).  The caller closes `z` afterwards (the EOF member, whose offset the index already names).  An
+ *            index of 2^28 chunks or more is SFGPU_ERR_RANGE.  finish adds 28 bytes a record, two pieces and, for the index,
+ *            40 bytes a record and 28 bytes a chunk of device memory.
+ *   close    frees the store.
+ * collect after finish and finish twice are SFGPU_ERR_STATE.  All calls are synchronous and ordered behind the work on `stream`. */
+typedef struct sfgpu_bamsort sfgpu_bamsort;
+typedef struct {
+    uint64_t n_records;
+    uint64_t n_no_coor;       /* records with refID < 0: they stand last */
+    uint64_t n_bytes;         /* the sorted record stream, uncompressed */
+    uint64_t state_bytes;     /* peak device bytes held by the handle and by finish */
+    uint64_t index_bytes;     /* 0 without an index */
+    uint64_t n_pieces;        /* writes made to `z` */
+    uint64_t n_index_chunks;
+    uint64_t n_index_bins;    /* the pseudo-bins not counted */
+    double sort_ms;           /* device events: the sort */
+    double gather_ms;         /* device events: the gather kernels of all pieces */
+    double index_ms;          /* host clock: the index kernels, their copies and the sink */
+} sfgpu_bamsort_result;
+SFGPU_API int sfgpu_bamsort_open(sfgpu_bamsort** out);
+SFGPU_API int sfgpu_bamsort_collect(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                    const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                                    const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented);
+SFGPU_API int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,
+                                   void* user, sfgpu_bamsort_result* res, sfgpu_stream stream);
+SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);
 /* ---- the class-table exchange of a multi-GPU run (the reference has one table in one process) ----------
  * One process / thread per GPU builds the table of ITS reads; afterwards every rank must hold the table a single
  * builder would have produced from all reads.  The library does the device work on class tables in CSR form (the

@@ -167,6 +167,15 @@ class BgzwResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BamsortResult(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("n_no_coor", C.c_uint64), ("n_bytes", C.c_uint64), ("state_bytes", C.c_uint64),
+                ("index_bytes", C.c_uint64), ("n_pieces", C.c_uint64), ("n_index_chunks", C.c_uint64), ("n_index_bins", C.c_uint64),
+                ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("index_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _LOG_CB = C.CFUNCTYPE(None, C.c_int, C.c_char_p)
 TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p)      # sfgpu_text_sink
 ALLREDUCE_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p)      # sfgpu_allreduce_fn
@@ -285,6 +294,13 @@ _SIGS = {
     "sfgpu_bgzw_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_bgzw_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_bgzw_close": (C.c_int, [_P, C.POINTER(BgzwResult)]),
+    "sfgpu_bgzw_track_members": (C.c_int, [_P]),
+    "sfgpu_bgzw_member_sizes": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "sfgpu_bamsort_open": (C.c_int, [C.POINTER(_P)]),
+    "sfgpu_bamsort_collect": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                        C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
+    "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
+    "sfgpu_bamsort_close": (C.c_int, [_P]),
     "sfgpu_sam_write_bgzf": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
                                        C.POINTER(SamWriteResult), _P]),
     "sfgpu_sam_write_bgzf_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,

@@ -191,6 +191,9 @@ struct sfgpu_bgzw {
     sfgpu_bgzw_result stats{};                          // n_members, and the three counters as last copied
     uint64_t* h_stats = nullptr;                        // stored members, matches, literals so far; the pipe's scope owns it
     DevBuf<unsigned long long> d_stats;                 // the same on the device, summed by the kernel over all launches
+    bool track = false;                                 // sfgpu_bgzw_track_members: every batch's mem_len is kept in d_sizes
+    DevBuf<uint32_t> d_sizes;                           // compressed bytes of the members written since, in file order
+    uint64_t n_sizes = 0;
     SlotPipe pipe;                                      // last, so that it drains before d_stats goes
 };
 
@@ -219,14 +222,32 @@ extern "C" int sfgpu_bgzw_write_device(sfgpu_bgzw* z, const void* d_src, uint64_
         [&](const uint8_t* src, uint64_t bytes, uint32_t nm, uint4* slots, uint32_t* mem_len) {
             hipLaunchKernelGGL(k_bgzw_encode, dim3(nm), dim3(kThreads), 0, st, src, bytes, slots, mem_len, z->d_stats.p);
         },
-        [&](uint32_t) -> int {
+        [&](uint32_t nm) -> int {
             SF_HIP(hipMemcpyAsync(z->h_stats, z->d_stats.p, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+            if (z->track) {                             // behind the batch on st: the sizes stay on the device
+                if (int rc = z->d_sizes.reserve(z->n_sizes + nm, st, true, z->n_sizes)) return rc;
+                SF_HIP(hipMemcpyAsync(z->d_sizes.p + z->n_sizes, z->pipe.len.p, nm * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+                z->n_sizes += nm;
+            }
             return SFGPU_OK;
         },
         [&](uint64_t, uint32_t nm) {
             z->stats.n_stored_members = z->h_stats[0]; z->stats.n_matches = z->h_stats[1]; z->stats.n_literals = z->h_stats[2];
             z->stats.n_members += nm;
         });
+}
+
+extern "C" int sfgpu_bgzw_track_members(sfgpu_bgzw* z) {
+    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_bgzw_track_members: null handle");
+    z->track = true;
+    return SFGPU_OK;
+}
+
+extern "C" int sfgpu_bgzw_member_sizes(sfgpu_bgzw* z, const uint32_t** d_sizes, uint64_t* n_members) {
+    SF_REQUIRE(z && d_sizes && n_members, SFGPU_ERR_INVALID, "sfgpu_bgzw_member_sizes: null argument");
+    SF_REQUIRE(z->track, SFGPU_ERR_STATE, "sfgpu_bgzw_member_sizes: the handle does not track its members");
+    *d_sizes = z->d_sizes.p; *n_members = z->n_sizes;
+    return SFGPU_OK;
 }
 
 extern "C" int sfgpu_bgzw_close(sfgpu_bgzw* z, sfgpu_bgzw_result* res) {

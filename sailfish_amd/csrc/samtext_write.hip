@@ -34,6 +34,7 @@
 #include "samwfmt.h"
 #include "bamwfmt.h"
 #include "textchunks.h"
+#include "bamsort.h"
 
 #include <cstring>
 
@@ -422,13 +423,13 @@ using namespace sfgpu;
 
 namespace {
 
-// sfgpu_sam_write_text[_q] (sink) and sfgpu_sam_write_bgzf[_q] (z; format SFGPU_SAMW_TEXT or SFGPU_SAMW_BAM): everything up to the
-// chunk loop is the same but for the kernels that size and check a unit
+// sfgpu_sam_write_text[_q] (sink), sfgpu_sam_write_bgzf[_q] (z; format SFGPU_SAMW_TEXT or SFGPU_SAMW_BAM) and sfgpu_bamsort_collect
+// (store; SFGPU_SAMW_BAM): everything up to the chunk loop is the same but for the kernels that size and check a unit
 int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired, const char* d_ref_names,
               const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames, const uint64_t* d_qname_off, const uint8_t* d_seq1,
               const int64_t* d_seq1_off, const uint8_t* d_seq2, const int64_t* d_seq2_off, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
               uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user, sfgpu_bgzw* z, int format,
-              sfgpu_samwrite_result* out, sfgpu_stream stream) {
+              sfgpu_samwrite_result* out, sfgpu_stream stream, BamRecordStore* store) {
     const bool bam = format == SFGPU_SAMW_BAM;
     auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
     if (!out) return fail(SFGPU_ERR_INVALID, "null result");
@@ -554,6 +555,13 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     if (h_misc[0] & kTooLong) return fail(SFGPU_ERR_RANGE, "a unit is longer than 2^32 - 1 bytes");
     const uint64_t total = h_misc[kMisc];
     out->n_bytes = total; out->n_lines = h_misc[4]; out->max_unit_bytes = h_misc[1];
+    if (store)              // sfgpu_bamsort_collect: every tile at once into a segment of the store, which then lists the records
+        return store->take(total, out->n_lines, S.unit_start.p, n_units, st, &out->format_ms, [&](uint4* buf, hipStream_t s) -> int {
+            hipLaunchKernelGGL(k_format_bam, dim3((unsigned)(((total - 1) >> kTileShift) + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
+                               S.unit_start.p, n_units, total, (uint64_t)0, (uint64_t)0, buf);
+            SF_HIP(hipGetLastError());
+            return SFGPU_OK;
+        });
     if (!sink && !z) return SFGPU_OK;
     if (out->max_unit_bytes > chunk_bytes) return fail(SFGPU_ERR_RANGE, "a unit (a line, or the two lines of a pair) is longer than chunk_bytes");
 
@@ -585,7 +593,7 @@ extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d
                                       const uint8_t* d_qual2, int oriented) {
     return sam_write("sfgpu_sam_write_text", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
                      d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, sink, user, nullptr,
-                     SFGPU_SAMW_TEXT, out, stream);
+                     SFGPU_SAMW_TEXT, out, stream, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
@@ -607,7 +615,7 @@ extern "C" int sfgpu_sam_write_bgzf_q(const sfgpu_hit* d_hits, const uint32_t* d
     SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
     return sam_write("sfgpu_sam_write_bgzf", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
                      d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, nullptr, nullptr, z, format,
-                     out, stream);
+                     out, stream, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
@@ -617,4 +625,15 @@ extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_h
                                     sfgpu_samwrite_result* out, sfgpu_stream stream) {
     return sfgpu_sam_write_bgzf_q(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1,
                                   d_seq1_off, d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, nullptr, nullptr, 0);
+}
+
+// bamsort.h: the batch's BAM records, checked, sized and formatted as for sfgpu_sam_write_bgzf_q, into `store`
+int sfgpu::samw_collect_bam(BamRecordStore* store, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                            const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                            const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                            const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                            const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
+    return sam_write("sfgpu_bamsort_collect", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, 0, nullptr, nullptr, nullptr, SFGPU_SAMW_BAM,
+                     out, stream, store);
 }

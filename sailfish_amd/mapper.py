@@ -108,16 +108,22 @@ def hits_to_numpy(hits, offsets):
     return hits.cpu().numpy().view(HIT_DTYPE), offsets.cpu().numpy().view(np.uint32)
 
 
-def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", oriented=False):
+def _check_mappings_sorted(mappings_sorted, mappings_format):
+    if mappings_sorted and mappings_format != "bam":
+        raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
+
+
+def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", oriented=False, mappings_sorted=False):
     """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
     if write_mappings is None:
         return None
     from .samfile import SamDeviceWriter
-    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format, oriented=oriented)
+    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format, oriented=oriented,
+                           sort="coordinate" if mappings_sorted else None)
 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, **kw):
+                   write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -125,12 +131,15 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     SamDeviceWriter's `format` ("sam"; "sam.gz" for the text, "bam" for BAM records, in BGZF members encoded on the device); it is never
     inferred from the path.  quals1 / quals2: the reads' qualities (lists like reads1 / reads2, of as many bytes a read as it has
     bases), written as QUAL; default '*'.  mappings_oriented=True puts the lines with 0x10 on the transcript's strand, as the SAM
-    specification stores them (SEQ reverse-complemented, QUAL reversed): the file other tools expect.
+    specification stores them (SEQ reverse-complemented, QUAL reversed): the file other tools expect.  mappings_sorted=True (with
+    mappings_format="bam", else ValueError) writes the file coordinate-sorted with its .bai index beside it (SamDeviceWriter's
+    sort="coordinate": the records stay on the device until the run ends); the estimates never depend on it.
     -> (rc, experiment)"""
     from . import quant
+    _check_mappings_sorted(mappings_sorted, mappings_format)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
-    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented)
+    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
 
     def batches():
         for a in range(0, n, batch_reads):
@@ -169,7 +178,7 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, **kw):
+                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -179,12 +188,13 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     read where the files are out of step, naming the record counted from the start of the files and both names
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
-    reverse-complemented and QUAL reversed.  -> (rc, experiment)"""
+    reverse-complemented and QUAL reversed.  mappings_sorted as in quantify_reads.  -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
+    _check_mappings_sorted(mappings_sorted, mappings_format)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
-    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented)
+    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
     keep = sam is not None and bool(mappings_oriented)
 
     def batches():

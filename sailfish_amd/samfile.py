@@ -18,6 +18,7 @@ sfgpu_bam_parse_host / _device, and `SamFile` picks the format by itself (`SamFi
 `write_bam` are host-side converters, for tests and for the way back."""
 import ctypes as C
 import gzip
+import os
 import re
 import struct
 
@@ -690,12 +691,283 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
             f.write(data)
 
 
-def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False):
+def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False, sort=None):
     """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
-    members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf)."""
+    members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf).  sort="coordinate": the same records in
+    coordinate order under an @HD SO:coordinate header (sort_bam_stream; csrc/baifmt.h), the header in members of its own, so that
+    the first record begins a member; `build_bai` gives its index."""
     from . import gzfile
-    gzfile.write_bgzf(path, sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented)),
-                      member_bytes=member_bytes)
+    if sort not in SORT_ORDERS:
+        raise ValueError(f"sort must be one of {SORT_ORDERS}, not {sort!r}")
+    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented))
+    if sort is None:
+        gzfile.write_bgzf(path, data, member_bytes=member_bytes)
+        return
+    data = sort_bam_stream(data)
+    p = _bam_header(data)[2]
+    with open(path, "wb") as f:
+        for part in (data[:p], data[p:]):
+            for a in range(0, len(part), member_bytes):
+                f.write(gzfile.bgzf_member(part[a:a + member_bytes]))
+        f.write(gzfile.BGZF_EOF)
+
+
+# ---- the coordinate-sorted file and its index (csrc/baifmt.h; host statements) ---------------------------------------------------
+
+SORT_ORDERS = (None, "coordinate")
+_HD_COORDINATE = b"@HD\tVN:1.6\tSO:coordinate\n"
+BAI_MAGIC = b"BAI\x01"
+_PSEUDO_BIN = 37450
+_REF_OPS = (0, 2, 3, 7, 8)                              # M D N = X consume the reference
+
+
+def _bam_records(data, p):
+    """the offsets of the records of the inflated stream `data` from p on; ValueError where the chain breaks"""
+    out = []
+    while p < len(data):
+        if len(data) - p < 36:
+            raise ValueError(f"the stream ends inside the record at byte {p}")
+        block_size = struct.unpack_from("<i", data, p)[0]
+        if block_size < 32 or p + 4 + block_size > len(data):
+            raise ValueError(f"the record at byte {p} of the stream is broken")
+        out.append(p)
+        p += 4 + block_size
+    return out
+
+
+def _sort_key(data, p):
+    ref, pos = struct.unpack_from("<ii", data, p + 4)
+    return (ref & 0xffffffff) << 32 | ((pos + 1) & 0xffffffff)
+
+
+def sort_bam_stream(data):
+    """an inflated BAM stream -> the coordinate-sorted stream of the same records: the header text begins with @HD VN:1.6
+    SO:coordinate (in place of an @HD line, if there is one), the records stand in stable order of
+    (uint32)refID << 32 | (uint32)(pos + 1) -- records without a reference last, ties in the order they had."""
+    data = bytes(data)
+    head = _bam_header(data)
+    if head is None:
+        raise ValueError("the stream ends inside the BAM header")
+    _, _, p, text = head
+    lines = [l for l in text.split(b"\n") if l]
+    if lines and lines[0].startswith(b"@HD"):
+        lines.pop(0)
+    at = _bam_records(data, p)
+    order = sorted(range(len(at)), key=lambda i: _sort_key(data, at[i]))       # (sorted is stable)
+    ends = at[1:] + [len(data)]
+    return sam_to_bam(_HD_COORDINATE + b"".join(l + b"\n" for l in lines)) + b"".join(data[at[i]:ends[i]] for i in order)
+
+
+def _bgzf_member_at(blob, c):
+    """the member at byte c of a BGZF file -> (its bytes, its payload)"""
+    import zlib
+    if len(blob) - c < 18 or bytes(blob[c:c + 4]) != b"\x1f\x8b\x08\x04":
+        raise ValueError(f"no BGZF member at byte {c}")
+    xlen = struct.unpack_from("<H", blob, c + 10)[0]
+    q, size = c + 12, None
+    while q + 4 <= c + 12 + xlen:
+        si, slen = bytes(blob[q:q + 2]), struct.unpack_from("<H", blob, q + 2)[0]
+        if si == b"BC" and slen == 2:
+            size = struct.unpack_from("<H", blob, q + 4)[0] + 1
+        q += 4 + slen
+    if size is None or c + size > len(blob):
+        raise ValueError(f"the member at byte {c} has no BSIZE, or the file ends inside it")
+    return size, zlib.decompress(bytes(blob[c + 12 + xlen:c + size - 8]), -15)
+
+
+def _bgzf_members(blob):
+    """[(file offset, first payload byte in the stream)] of every member, the stream, and the offset of the EOF member (the file's
+    last empty member; the file's length without one)"""
+    members, parts, c, n = [], [], 0, 0
+    while c < len(blob):
+        size, payload = _bgzf_member_at(blob, c)
+        members.append((c, n, len(payload)))
+        parts.append(payload)
+        c += size
+        n += len(payload)
+    eof = members[-1][0] if members and members[-1][2] == 0 else len(blob)
+    return members, b"".join(parts), eof
+
+
+def _ref_end(data, p):
+    """(beg, end) of the record at p: end = pos + the reference-consuming CIGAR lengths, at least beg + 1"""
+    pos, l_name, _mq, _bin, n_cigar = struct.unpack_from("<iBBHH", data, p + 8)
+    span = sum(w >> 4 for w in struct.unpack_from("<%dI" % n_cigar, data, p + 36 + l_name) if w & 15 in _REF_OPS)
+    return pos, pos + max(span, 1)
+
+
+def build_bai(bam_path_or_bytes):
+    """The BAI index (bytes) of a coordinate-sorted BAM file, given as a path or as the file's bytes: the SAM specification's index
+    with every choice fixed (csrc/baifmt.h), the statement the device index is judged by.  The members are inflated with zlib and
+    walked with the records.  V(x) of stream byte x is coffset(member holding x) << 16 | offset in its payload, V(end of the stream)
+    = coffset(EOF member) << 16.  A record with refID >= 0 spans [pos, pos + reference-consuming CIGAR lengths) (at least one base)
+    and lies in bin reg2bin of that; a maximal run of records consecutive in the file with the same (refID, bin) is one chunk, and
+    nothing else is merged.  Per reference: the bins ascending with their chunks in file order, pseudo-bin 37450 with (V(first
+    record), V(end of the last)) and (mapped, unmapped by FLAG 0x4), then the linear index of ((max end - 1) >> 14) + 1 windows:
+    the smallest vbeg of the records touching the window, an untouched window taking the next touched one to its right.  Then
+    n_no_coor.  Raises ValueError if the keys (uint32)refID << 32 | (uint32)(pos + 1) ever descend."""
+    import bisect
+    blob = bam_path_or_bytes
+    if not isinstance(blob, (bytes, bytearray, memoryview)):
+        with open(blob, "rb") as f:
+            blob = f.read()
+    members, data, eof = _bgzf_members(blob)
+    head = _bam_header(data)
+    if head is None:
+        raise ValueError("the file ends inside the BAM header")
+    refs, _, p, _ = head
+    starts = [m[1] for m in members]
+
+    def v(x):
+        if x >= len(data):
+            return eof << 16
+        m = bisect.bisect_right(starts, x) - 1           # the last member that starts at or before x: never an empty one
+        return members[m][0] << 16 | (x - members[m][1])
+
+    per = [dict(bins={}, lin=[], n=[0, 0], span=None) for _ in refs]
+    no_coor, last, last_bin = 0, 0, None
+    for n, q in enumerate(_bam_records(data, p)):
+        ref, flag = struct.unpack_from("<i", data, q + 4)[0], struct.unpack_from("<H", data, q + 18)[0]
+        key = _sort_key(data, q)
+        if key < last:
+            raise ValueError(f"record {n} stands behind a record of a higher (reference, position): the file is not coordinate-sorted")
+        last = key
+        if ref < 0:
+            no_coor += 1
+            continue
+        if ref >= len(refs):
+            raise ValueError(f"record {n}: refID {ref} is no reference")
+        beg, end = _ref_end(data, q)
+        vbeg, vend = v(q), v(q + 4 + struct.unpack_from("<i", data, q)[0])
+        R, b = per[ref], _reg2bin(beg, end)
+        chunks = R["bins"].setdefault(b, [])
+        if last_bin == (ref, b):
+            chunks[-1][1] = vend
+        else:
+            chunks.append([vbeg, vend])
+        last_bin = (ref, b)
+        R["span"] = [vbeg if R["span"] is None else R["span"][0], vend]
+        R["n"][1 if flag & 0x4 else 0] += 1
+        w1 = (end - 1) >> 14
+        R["lin"] += [None] * (w1 + 1 - len(R["lin"]))
+        for w in range(beg >> 14, w1 + 1):
+            if R["lin"][w] is None or vbeg < R["lin"][w]:
+                R["lin"][w] = vbeg
+    out = [BAI_MAGIC, struct.pack("<I", len(refs))]
+    for R in per:
+        out.append(struct.pack("<I", len(R["bins"]) + 1 if R["span"] else 0))
+        for b in sorted(R["bins"]):
+            out.append(struct.pack("<II", b, len(R["bins"][b])) + b"".join(struct.pack("<QQ", *c) for c in R["bins"][b]))
+        if R["span"]:
+            out.append(struct.pack("<IIQQQQ", _PSEUDO_BIN, 2, *R["span"], *R["n"]))
+        lin = R["lin"]
+        for w in range(len(lin) - 2, -1, -1):
+            if lin[w] is None:
+                lin[w] = lin[w + 1]
+        out.append(struct.pack("<I", len(lin)) + struct.pack("<%dQ" % len(lin), *lin))
+    out.append(struct.pack("<Q", no_coor))
+    return b"".join(out)
+
+
+def reg2bins(beg, end):
+    """the SAM specification's bins that may hold a record overlapping the zero-based half-open [beg, end)"""
+    end -= 1
+    bins = [0]
+    for shift, first in ((26, 1), (23, 9), (20, 73), (17, 585), (14, 4681)):
+        bins += range(first + (beg >> shift), first + (end >> shift) + 1)
+    return bins
+
+
+def read_bai(bai):
+    """BAI bytes -> per reference (bins {bin: [(vbeg, vend)]}, the pseudo-bin not among them; linear index; pseudo-bin chunks or
+    None), and n_no_coor (None where the file ends without it)"""
+    bai = bytes(bai)
+    if bai[:4] != BAI_MAGIC:
+        raise ValueError("not a BAI index: it does not begin with 'BAI\\1'")
+    n_ref, p, refs = struct.unpack_from("<I", bai, 4)[0], 8, []
+    for _ in range(n_ref):
+        n_bin, bins, pseudo = struct.unpack_from("<I", bai, p)[0], {}, None
+        p += 4
+        for _ in range(n_bin):
+            b, n_chunk = struct.unpack_from("<II", bai, p)
+            chunks = [struct.unpack_from("<QQ", bai, p + 8 + 16 * k) for k in range(n_chunk)]
+            p += 8 + 16 * n_chunk
+            if b == _PSEUDO_BIN:
+                pseudo = chunks
+            else:
+                bins[b] = chunks
+        n_intv = struct.unpack_from("<I", bai, p)[0]
+        refs.append((bins, list(struct.unpack_from("<%dQ" % n_intv, bai, p + 4)), pseudo))
+        p += 4 + 8 * n_intv
+    return refs, struct.unpack_from("<Q", bai, p)[0] if len(bai) >= p + 8 else None
+
+
+def fetch(bam_path, name_or_tid, beg, end, bai=None):
+    """The records (bytes each, block_size included, in file order) of the coordinate-sorted BAM file at bam_path that overlap the
+    zero-based half-open region [beg, end) of a reference, named or numbered, found through the index: `bai` is the index's bytes or
+    its path, default bam_path + ".bai".  The bins of reg2bins(beg, end) give the chunks, chunks that end at or before the linear
+    index's entry for beg >> 14 are dropped, every other chunk is sought (the member at vbeg >> 16 is inflated, records are read
+    from byte vbeg & 0xffff on, across members, until vend) and its records are kept when they lie on the reference, begin before
+    `end` and end behind `beg`.  Host only: a convenience, and the check that an index can be used."""
+    names = read_bam_header(bam_path)[0]
+    tid = name_or_tid if isinstance(name_or_tid, int) else names.index(name_or_tid if isinstance(name_or_tid, str) else name_or_tid.decode("utf-8", "surrogateescape"))
+    if not 0 <= tid < len(names):
+        raise ValueError(f"reference {tid} of {len(names)}")
+    if bai is None:
+        bai = bam_path + ".bai"
+    if not isinstance(bai, (bytes, bytearray, memoryview)):
+        with open(bai, "rb") as f:
+            bai = f.read()
+    refs, _ = read_bai(bai)
+    if len(refs) != len(names):
+        raise ValueError(f"the index holds {len(refs)} references, the file {len(names)}")
+    bins, lin, _ = refs[tid]
+    beg = max(int(beg), 0)
+    if beg >= end or (beg >> 14) >= len(lin):           # (a record that overlaps the region touches window beg >> 14 or a later one)
+        return []
+    min_off = lin[beg >> 14]
+    chunks = sorted(c for b in reg2bins(beg, end) for c in bins.get(b, ()) if c[1] > min_off)
+    out = []
+    with open(bam_path, "rb") as f:
+        size = f.seek(0, 2)
+
+        def member(c):
+            f.seek(c)
+            head = f.read(18)
+            if len(head) < 18:
+                return 0, b""
+            xlen = struct.unpack_from("<H", head, 10)[0]
+            blob = head + f.read(12 + xlen - 18 + 65536)
+            return _bgzf_member_at(blob, 0)
+
+        for vbeg, vend in chunks:
+            c, u = vbeg >> 16, vbeg & 0xffff
+            msize, payload = member(c)
+            while True:
+                while u >= len(payload) and msize and c + msize < size:       # on to the member that holds the next byte
+                    c, u = c + msize, u - len(payload)
+                    msize, payload = member(c)
+                if u >= len(payload) or (c << 16 | u) >= vend:
+                    break
+                rec = bytearray()
+                need = 4
+                while len(rec) < need:                  # the record may straddle members
+                    take = payload[u:u + need - len(rec)]
+                    rec += take
+                    u += len(take)
+                    if len(rec) == 4 and need == 4:
+                        need = 4 + struct.unpack_from("<i", rec, 0)[0]
+                    if len(rec) < need and u >= len(payload):
+                        if not msize or c + msize >= size:
+                            raise ValueError(f"{bam_path}: the file ends inside a record")
+                        c, u = c + msize, 0
+                        msize, payload = member(c)
+                rec = bytes(rec)
+                ref = struct.unpack_from("<i", rec, 4)[0]
+                b0, b1 = _ref_end(rec, 0)
+                if ref == tid and b0 < end and b1 > beg:
+                    out.append(rec)
+    return out
 
 
 # ---- the way back, on the device ------------------------------------------------------------------------------------------
@@ -712,9 +984,9 @@ BAM_WRITE_KINDS = {3: "the read name is not of 1 .. 254 bytes: BAM cannot say th
                    5: "the alignment ends beyond 2^29: BAM cannot say that"}
 
 
-def sam_header(names, ref_len):
-    """the @HD and @SQ lines _sam_text begins with"""
-    return b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n" + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(_name_bytes(names), ref_len))
+def sam_header(names, ref_len, sort=None):
+    """the @HD and @SQ lines _sam_text begins with; sort="coordinate": the @HD line of the sorted file (csrc/baifmt.h)"""
+    return (_HD_COORDINATE if sort else b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n") + b"".join(b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(_name_bytes(names), ref_len))
 
 
 class SamDeviceWriter:
@@ -740,22 +1012,40 @@ class SamDeviceWriter:
     the formatter to the encoder on the device, only compressed bytes are copied; close() writes the EOF member and adds
     bytes_out, members, stored_members, matches, literals, ms_encode and chunks_out to `stats`.  "bam" writes the BAM file
     write_bam writes (sam_to_bam of the same text: magic, header text, reference list, one record per line; csrc/bamwfmt.h) through
-    the same encoder; BAM_WRITE_KINDS are then errors too, a read without records counting as record 0.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times."""
+    the same encoder; BAM_WRITE_KINDS are then errors too, a read without records counting as record 0.  `stats` sums reads, hits, lines, bytes, chunks, batches and the device / copy / sink times.
+    `sort`: None (the default) writes the records in read order, as above.  "coordinate" (format="bam" only, else ValueError) writes
+    the file write_bam(sort="coordinate") writes (csrc/baifmt.h, csrc/bamsort.hip): write() has the same signature, checks and
+    errors, but formats the batch's records and KEEPS them on the device (a failing batch keeps nothing); close() sorts them stably
+    by (uint32)refID << 32 | (uint32)(pos + 1), gathers the sorted stream in pieces of chunk_bytes rounded down to a multiple of
+    32 768 (the file does not depend on it), encodes them behind the @HD SO:coordinate header and builds the BAI index on the
+    device.  `index`: a path or a binary file object (left open) for the index; None: path + ".bai" when path_or_file is a path, no
+    index when it is a file object; False: no index.  The state is NOT spilled to the host: it takes the records' bytes plus 20
+    bytes per record of device memory until close(), which adds 28 bytes per record, two pieces and, for the index, 40 bytes per
+    record and 28 per chunk; fewer than 2^32 records.  `stats` gains records, state_bytes (peak device bytes held), no_coor,
+    index_bytes, ms_sort, ms_gather and ms_index."""
 
-    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False):
+    def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False, sort=None, index=None):
         from . import _lib, quantfile
         if format not in WRITE_FORMATS:
             raise ValueError(f"format must be one of {WRITE_FORMATS}, not {format!r}")
+        if sort not in SORT_ORDERS:
+            raise ValueError(f"sort must be one of {SORT_ORDERS}, not {sort!r}")
+        if sort is not None and format != "bam":
+            raise ValueError(f'sort="coordinate" needs format="bam", not {format!r}')
+        self._sort, self._b = sort is not None, None
         self._L = _lib.lib()
         self.paired, self.chunk_bytes, self.format, self.oriented = bool(paired), int(chunk_bytes), format, bool(oriented)
         self._names = quantfile.names_blob(_name_bytes(names))
         self._n_refs = len(self._names[1]) - 1
         self._d_names = None                               # uploaded to the device of the first batch
         self._own = not hasattr(path_or_file, "write")
+        self._index = None                                 # where the BAI goes: a path, a file object or None
+        if self._sort and index is not False:
+            self._index = index if index is not None else (os.fsdecode(path_or_file) + ".bai" if self._own else None)
         self._f = open(path_or_file, "wb") if self._own else path_or_file
         self.n_reads = 0                                   # the running read index
         self.stats = dict(reads=0, hits=0, lines=0, bytes=0, chunks=0, batches=0, ms_format=0.0, ms_copy=0.0, ms_sink=0.0)
-        head = sam_header(names, ref_len)
+        head = sam_header(names, ref_len, sort)
         if format == "bam":
             head = sam_to_bam(head)                        # magic, header text and reference list
         self.stats["header_bytes"] = len(head)
@@ -768,8 +1058,13 @@ class SamDeviceWriter:
 
     def _write_head(self, dev):
         import torch
+
+        from . import _lib
         if self._head is not None:
             head, self._head = self._head, None
+            if self._sort:                                 # the index is made of the members' sizes: kept from the first member on
+                self._z._open(dev)
+                _lib.check(self._L.sfgpu_bgzw_track_members(self._z._h))
             self._z.write(torch.from_numpy(np.frombuffer(head, np.uint8).copy()).to(dev))
 
     @staticmethod
@@ -848,6 +1143,10 @@ class SamDeviceWriter:
         with torch.cuda.device(dev):
             if self._z is None:
                 rc = self._L.sfgpu_sam_write_text_q(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra)
+            elif self._sort:
+                self._write_head(dev)
+                self._open_store()
+                rc = self._L.sfgpu_bamsort_collect(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra)
             else:
                 self._write_head(dev)
                 rc = self._L.sfgpu_sam_write_bgzf_q(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra)
@@ -865,6 +1164,49 @@ class SamDeviceWriter:
         st["ms_format"] += res.format_ms; st["ms_copy"] += res.d2h_ms; st["ms_sink"] += res.sink_ms
         return res.as_dict()
 
+    def _open_store(self):
+        from . import _lib
+        if self._b is None:
+            b = C.c_void_p()
+            _lib.check(self._L.sfgpu_bamsort_open(C.byref(b)))
+            self._b = b
+
+    def _finish_sorted(self):
+        """sort, gather and encode the records kept, then the index: everything of close() that is the sorted file's own"""
+        import torch
+
+        from . import _lib
+        dev = self._z._device
+        raised, own, xf = [], isinstance(self._index, (str, bytes, os.PathLike)), None
+
+        def sink(addr, nb, _user):
+            try:                                   # nothing may unwind through the C frame
+                xf.write(memoryview((C.c_char * nb).from_address(addr)))
+                return 0
+            except BaseException as e:             # noqa: BLE001  (re-raised below)
+                raised.append(e)
+                return 1
+
+        if self._index is not None:
+            xf = open(self._index, "wb") if own else self._index
+        try:
+            res = _lib.BamsortResult()
+            with torch.cuda.device(dev):
+                self._open_store()
+                rc = self._L.sfgpu_bamsort_finish(self._b, self._z._h, self._n_refs, self.chunk_bytes,
+                                                  _lib.TEXT_SINK(sink) if xf is not None else _lib.TEXT_SINK(0), None, C.byref(res),
+                                                  _lib.current_stream_ptr())
+            for sunk in (raised, self._z._raised):
+                if sunk:
+                    raise sunk.pop(0)
+            _lib.check(rc)
+        finally:
+            if xf is not None:
+                xf.close() if own else xf.flush()
+        for k, v in (("records", res.n_records), ("state_bytes", res.state_bytes), ("no_coor", res.n_no_coor), ("index_bytes", res.index_bytes),
+                     ("ms_sort", res.sort_ms), ("ms_gather", res.gather_ms), ("ms_index", res.index_ms)):
+            self.stats[k] = v
+
     def close(self):
         if self._f is None:
             return
@@ -874,7 +1216,14 @@ class SamDeviceWriter:
                     if not self._z._raised and self._z._h is None:
                         import torch
                         self._write_head(torch.device("cuda", torch.cuda.current_device()))
-                    res = self._z.close()              # the EOF member
+                    try:
+                        if self._sort and not self._z._raised:
+                            self._finish_sorted()
+                    finally:
+                        b, self._b = self._b, None
+                        if b is not None:
+                            self._L.sfgpu_bamsort_close(b)
+                        res = self._z.close()          # the EOF member
                 finally:
                     self._z = None
                 for k, v in (("bytes_out", res["n_bytes_out"]), ("members", res["n_members"]), ("stored_members", res["n_stored_members"]),

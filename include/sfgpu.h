@@ -1241,6 +1241,45 @@ SFGPU_API int sfgpu_filter_hits(const sfgpu_hit* d_hits, const uint32_t* d_hit_o
                       const sfgpu_filter_opts* opts, uint32_t* d_ids_out, uint32_t* d_offsets_out,
                       uint32_t* d_fl_counts, int64_t* remaining_fl_ops, sfgpu_filter_stats* stats, sfgpu_stream stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Verification of the mapper's hit records against the transcripts' bases: an optional pass between sfgpu_map_reads and whatever
+ * consumes its records.  The mapper places a mate on the strength of one exact match and never compares the rest; this pass scores
+ * every record, ungapped, on the diagonal the mapper recorded, drops the records that fail and optionally all but the best of a
+ * read.  What it means is stated once, serially, in csrc/verifyfmt.h (hits.verify_hits_host is the Python statement):
+ *   job     one mate of one record.  mate_status 0 / 1: mate 1's bases on strand fwd at pos; 2: mate 2's bases on strand fwd at
+ *           pos; 3: two jobs -- mate 1, fwd, pos and mate 2, mate_fwd, mate_pos.  len = the mate's length from d_off1 / d_off2
+ *           (not the record's 16-bit read_len / mate_len).
+ *   bases   oriented base j: forward code(r[j]), reverse 3 - code(r[len - 1 - j]) (A C G T in either case -> 0 .. 3, anything else
+ *           4 on either strand).  Transcript position x = pos + j: x < 0 or x >= the transcript's length counts in `over`;
+ *           otherwise a mismatch (`mism`) when either code is 4 or the codes differ (N against N is a mismatch).
+ *   pass    a job passes iff 1000 * (len - over - mism) >= min_identity_permille * len; a record passes iff all its jobs do (a
+ *           pair stands or falls as a whole).  keep_best != 0: of a read's passing records only those with the read's minimum
+ *           cost (mism + over summed over the record's jobs) survive.
+ *   output  the survivors in input order (d_hits_out, room for d_hit_offsets[n_reads] records), CSR offsets over the same reads
+ *           (d_offsets_out, n_reads + 1), one score per survivor (d_scores_out, may be NULL; the fields saturate at 65 535, the
+ *           decisions use the unsaturated counts), *n_out = the survivors.  The outputs must not overlap the inputs.
+ *   errors  a record with tid >= the index's transcript count: SFGPU_ERR_RANGE, sfgpu_last_error names the lowest such record, the
+ *           outputs are left untouched.  NULL idx / opts / n_out / stats, min_identity_permille > 1000, or NULL reads, records or
+ *           outputs where n_reads > 0 needs them: SFGPU_ERR_INVALID.  d_seq2 / d_off2 = NULL: single end (a record that
+ *           names mate 2 is then SFGPU_ERR_INVALID).
+ * Ungapped: a read with an indel fails past the indel.  Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_hit_score { uint16_t mism, over, mate_mism, mate_over; } sfgpu_hit_score;      /* 8 bytes */
+typedef struct sfgpu_verify_opts {
+    uint32_t min_identity_permille;   /* 0 .. 1000 */
+    int32_t  keep_best;
+} sfgpu_verify_opts;
+typedef struct sfgpu_verify_stats {
+    uint64_t records_in, records_out;
+    uint64_t reads_in, reads_out;     /* reads with at least one record, before and after */
+    uint64_t failed_identity;         /* records with a job below min_identity_permille */
+    uint64_t dropped_not_best;        /* passing records dropped by keep_best */
+    uint64_t sum_mism;                /* mism over the survivors' jobs, unsaturated */
+} sfgpu_verify_stats;
+SFGPU_API int sfgpu_hits_verify(const sfgpu_index* idx, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_verify_opts* opts,
+                                sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, sfgpu_hit_score* d_scores_out, uint64_t* n_out,
+                                sfgpu_verify_stats* stats, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

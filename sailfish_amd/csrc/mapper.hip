@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mapidx.h"
 #include "primitives.h"
 
 namespace sfgpu {
@@ -453,13 +454,6 @@ using namespace sfgpu;
 // waits for the stream when it goes out of scope
 struct StreamSyncOnExit { hipStream_t s; ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); } };
 
-struct sfgpu_index {
-    uint32_t k = 31, shift = 0, max_occ = 1000, n_seeds = 2;
-    uint32_t seed_len = 0;                 // != 0: scan mode with seeds of this many bases (the default: min(19, k)); 0: end seeds
-    uint64_t n_valid = 0, n_slots = 0, M = 0, n_buckets = 0;
-    DevBuf<uint64_t> keys; DevBuf<uint32_t> tid, tpos, bucket;
-    DevBuf<char> tseq; DevBuf<uint64_t> tseq_off; DevBuf<uint32_t> tlen;      // the transcripts' text (scan mode extends matches on it)
-};
 constexpr uint32_t kDefaultSeedLen = 19;
 
 extern "C" {

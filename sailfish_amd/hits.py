@@ -14,6 +14,9 @@ from . import _lib
 HIT_DTYPE = np.dtype([("tid", "<u4"), ("pos", "<i4"), ("mate_pos", "<i4"), ("frag_len", "<u4"), ("read_len", "<u2"),
                       ("mate_len", "<u2"), ("fwd", "u1"), ("mate_fwd", "u1"), ("mate_status", "u1"), ("pad_", "u1")])
 assert HIT_DTYPE.itemsize == 24
+# one score per record that survives verify_hits: sfgpu_hit_score
+SCORE_DTYPE = np.dtype([("mism", "<u2"), ("over", "<u2"), ("mate_mism", "<u2"), ("mate_over", "<u2")])
+assert SCORE_DTYPE.itemsize == 8
 SINGLE_END, PAIRED_END_LEFT, PAIRED_END_RIGHT, PAIRED_END_PAIRED = 0, 1, 2, 3        # rapmap::utils::MateStatus
 SAME, AWAY, TOWARD, NONE = 0, 1, 2, 3                                                # ReadOrientation
 SA, AS, S, A, U = 0, 1, 2, 3, 4                                                      # ReadStrandedness
@@ -108,6 +111,121 @@ def _device_hits(hits, hit_offsets, dev):
     off = hit_offsets
     d_off = off.to(dev).contiguous() if isinstance(off, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(off, np.uint32).view(np.int32).copy()).to(dev)
     return d_hits, d_off
+
+
+_BASE_CODE = np.full(256, 4, np.uint8)
+for _i, _b in enumerate(b"ACGT"):
+    _BASE_CODE[_b] = _BASE_CODE[_b + 32] = _i
+VERIFY_STATS = ("records_in", "records_out", "reads_in", "reads_out", "failed_identity", "dropped_not_best", "sum_mism")
+
+
+def _permille(min_identity):
+    p = int(round(float(min_identity) * 1000))
+    if not 0 <= p <= 1000:
+        raise ValueError(f"min_identity = {min_identity!r} lies outside 0 .. 1")
+    return p
+
+
+def verify_hits_host(transcripts, hits, offsets, reads1, reads2, min_identity_permille, keep_best):
+    """The statement of hit verification (csrc/verifyfmt.h restated in numpy; what sfgpu_hits_verify is judged by).  transcripts,
+    reads1, reads2 (or None): lists of bytes; hits: HIT_DTYPE records in CSR form over the reads (offsets[R + 1]).  A job is one mate
+    of one record -- status 0 / 1: mate 1, strand fwd, at pos; 2: mate 2, fwd, pos; 3: both, the second with mate_fwd at mate_pos --
+    of len(mate) bases.  Oriented base j is code(r[j]) forward and 3 - code(r[len - 1 - j]) reverse (A C G T in either case 0 .. 3,
+    anything else 4 on either strand); at x = pos + j off the transcript it counts in `over`, else it is a mismatch when either code is
+    4 or the codes differ.  A job passes iff 1000 (len - over - mism) >= permille len, a record iff all its jobs pass; keep_best keeps,
+    of a read's passing records, those of minimum mism + over.  -> (hits, offsets uint32[R + 1], scores SCORE_DTYPE, stats dict);
+    ValueError naming the lowest record whose tid is not a transcript."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    permille = int(min_identity_permille)
+    if not 0 <= permille <= 1000:
+        raise ValueError("min_identity_permille lies outside 0 .. 1000")
+    bad = np.nonzero(hits["tid"][: off[-1]] >= len(transcripts))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(transcripts)}")
+    tcodes = {}
+
+    def count(read, fwd, tid, pos):
+        c = _BASE_CODE[np.frombuffer(read, np.uint8)]
+        q = c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
+        if tid not in tcodes:
+            tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
+        t = tcodes[tid]
+        x = int(pos) + np.arange(len(q), dtype=np.int64)
+        on = (x >= 0) & (x < len(t))
+        a, b = q[on], t[x[on]]
+        return int(((a > 3) | (b > 3) | (a != b)).sum()), int(len(q) - on.sum())
+
+    keep, scores, out_off = [], [], [0]
+    stats = dict.fromkeys(VERIFY_STATS, 0)
+    stats["records_in"] = int(off[-1]) if len(off) else 0
+    for r in range(len(off) - 1):
+        recs = []
+        for i in range(off[r], off[r + 1]):
+            h = hits[i]
+            st = int(h["mate_status"])
+            jobs = [(reads2[r] if st == 2 else reads1[r], bool(h["fwd"]), h["pos"])]
+            if st == 3:
+                jobs.append((reads2[r], bool(h["mate_fwd"]), h["mate_pos"]))
+            counts = [count(rd, f, int(h["tid"]), p) for rd, f, p in jobs]
+            ok = all(1000 * (len(rd) - ov - mm) >= permille * len(rd) for (rd, _, _), (mm, ov) in zip(jobs, counts))
+            recs.append((i, ok, sum(mm + ov for mm, ov in counts), counts))
+        passing = [x for x in recs if x[1]]
+        stats["failed_identity"] += len(recs) - len(passing)
+        if keep_best and passing:
+            best = min(x[2] for x in passing)
+            stats["dropped_not_best"] += sum(x[2] != best for x in passing)
+            passing = [x for x in passing if x[2] == best]
+        for i, _, _, counts in passing:
+            keep.append(i)
+            flat = [min(v, 65535) for c in counts for v in c] + [0, 0]
+            scores.append(tuple(flat[:4]))
+            stats["sum_mism"] += sum(mm for mm, _ in counts)
+        stats["reads_in"] += int(off[r + 1] > off[r])
+        stats["reads_out"] += int(bool(passing))
+        out_off.append(len(keep))
+    stats["records_out"] = len(keep)
+    return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=SCORE_DTYPE), stats
+
+
+def _device_reads(reads, dev):
+    """(uint8 bases, int64 offsets) on the device, from such a pair or from a list of str / bytes"""
+    if not isinstance(reads, tuple):
+        from .mapper import pack_sequences
+        reads = pack_sequences(reads)
+    return reads[0].to(dev).contiguous(), reads[1].to(dev).contiguous()
+
+
+def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, keep_best=False):
+    """Verify the mapper's hit records against the transcripts' bases on the device (sfgpu_hits_verify; the rules are
+    verify_hits_host's).  index: the mapper.QuasiIndex the records come from; hits / offsets: device tensors as QuasiIndex.map_reads
+    returns them; reads1 / reads2: the batch's reads, packed (bases, offsets) pairs or lists, as map_reads takes them.  A job passes
+    with at least min_identity of its bases equal to the transcript's on the recorded diagonal (the permille is
+    int(round(min_identity * 1000)); outside 0 .. 1000: ValueError); keep_best keeps only a read's records of least mism + over.
+    -> (hits, offsets, scores: uint8 device tensor of SCORE_DTYPE records, stats dict)"""
+    permille = _permille(min_identity)
+    dev = index.device
+    d_hits, d_off = _device_hits(hits, offsets, dev)
+    R = int(d_off.numel()) - 1
+    s1, o1 = _device_reads(reads1, dev)
+    s2 = o2 = None
+    if reads2 is not None:
+        s2, o2 = _device_reads(reads2, dev)
+    if int(o1.numel()) - 1 != R or (o2 is not None and int(o2.numel()) - 1 != R):
+        raise ValueError("the reads and the hit offsets do not cover the same number of reads")
+    n = d_hits.numel() // 24
+    out_hits = torch.empty(max(n, 1) * 24, dtype=torch.uint8, device=dev)
+    out_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    scores = torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
+    o = _lib.VerifyOpts(permille, int(bool(keep_best)))
+    st = _lib.VerifyStats()
+    n_out = C.c_uint64(0)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.lib().sfgpu_hits_verify(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                                C.byref(o), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(st),
+                                                _lib.current_stream_ptr()))
+    return out_hits[: n_out.value * 24], out_off, scores[: n_out.value * 8], st.as_dict()
 
 
 def gc_prefix(seq, seq_off, ref_len):

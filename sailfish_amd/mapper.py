@@ -66,8 +66,11 @@ class QuasiIndex:
         _lib.check(self._L.sfgpu_index_set_seeds(self._h, int(seeds)))
         self.seeds = int(seeds)
 
-    def map_reads(self, reads1, reads2=None):
+    def map_reads(self, reads1, reads2=None, validate=None):
         """reads1 / reads2: lists of str / bytes, or (uint8 tensor, int64 offsets) pairs already packed.
+        validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best; {} = its defaults): the records are then
+        verified against the transcripts' bases before they are returned, and `last_scores` / `last_verify_stats` hold the
+        survivors' scores and the pass's counters.
         -> (hits: uint8 device tensor [n_hits * 24] of HIT_DTYPE records, offsets: int32 device tensor [R + 1])"""
         dev = self.device
         s1, o1 = reads1 if isinstance(reads1, tuple) else pack_sequences(reads1)
@@ -91,7 +94,11 @@ class QuasiIndex:
                     break
                 cap = n_hits.value
             _lib.check(rc)
-        return hits[: n_hits.value * 24], off
+        hits = hits[: n_hits.value * 24]
+        if validate is not None:
+            from .hits import verify_hits
+            hits, off, self.last_scores, self.last_verify_stats = verify_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), **validate)
+        return hits, off
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -113,6 +120,34 @@ def _check_mappings_sorted(mappings_sorted, mappings_format):
         raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
 
 
+def _validation(validate_mappings, min_identity, keep_best):
+    """-> (the `validate` dict for QuasiIndex.map_reads or None, the counters to accumulate over the batches); ValueError at once
+    for a min_identity outside 0 .. 1, before anything is indexed"""
+    if not validate_mappings:
+        return None, None
+    from .hits import VERIFY_STATS, _permille
+    _permille(min_identity)
+    return dict(min_identity=min_identity, keep_best=bool(keep_best)), dict.fromkeys(VERIFY_STATS, 0)
+
+
+def _add_verify_stats(total, idx):
+    if total is not None:
+        for key, v in idx.last_verify_stats.items():
+            total[key] += v
+
+
+def _report_verify_stats(exp, total, validate, sopt):
+    """the accumulated counters: on the experiment as `verify_stats` (None when the pass did not run) and as one log line"""
+    if exp is not None:
+        exp.verify_stats = total
+    log = getattr(sopt, "jointLog", None) if sopt is not None else None
+    if total is not None and log is not None:
+        log(0, "validated mappings (min identity {:g}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
+               "{} of {} mapped reads keep a record; {} mismatches in the kept records".format(
+                   validate["min_identity"], ", best only" if validate["keep_best"] else "", total["records_out"], total["records_in"],
+                   total["failed_identity"], total["dropped_not_best"], total["reads_out"], total["reads_in"], total["sum_mism"]))
+
+
 def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", oriented=False, mappings_sorted=False):
     """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
     if write_mappings is None:
@@ -123,7 +158,8 @@ def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", 
 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False, **kw):
+                   write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
+                   validate_mappings=False, min_identity=0.9, keep_best=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -134,9 +170,13 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     specification stores them (SEQ reverse-complemented, QUAL reversed): the file other tools expect.  mappings_sorted=True (with
     mappings_format="bam", else ValueError) writes the file coordinate-sorted with its .bai index beside it (SamDeviceWriter's
     sort="coordinate": the records stay on the device until the run ends); the estimates never depend on it.
+    validate_mappings=True verifies every batch's records against the transcripts' bases (hits.verify_hits with min_identity and
+    keep_best) before the batch is written and quantified: the mappings file and the estimates see the same, surviving records; the
+    counters of all batches are left on the experiment as `verify_stats` and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     _check_mappings_sorted(mappings_sorted, mappings_format)
+    validate, vstats = _validation(validate_mappings, min_identity, keep_best)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
     sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -151,7 +191,8 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
                 r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
                 q1 = None if quals1 is None else pack_sequences(quals1[a:b])[0].to(idx.device)
                 q2 = None if quals2 is None or r2 is None else pack_sequences(quals2[a:b])[0].to(idx.device)
-            h, o = idx.map_reads(r1, r2)
+            h, o = idx.map_reads(r1, r2, validate=validate)
+            _add_verify_stats(vstats, idx)
             if sam is not None:
                 sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
             yield h, o
@@ -165,6 +206,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
         if sam is not None:
             sam.close()
     idx.close()
+    _report_verify_stats(exp, vstats, validate, sopt)
     return rc, exp
 
 
@@ -178,7 +220,8 @@ def _dollar_separated(bases, off):
 
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
-                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False, **kw):
+                   inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
+                   validate_mappings=False, min_identity=0.9, keep_best=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -188,10 +231,12 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     read where the files are out of step, naming the record counted from the start of the files and both names
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
-    reverse-complemented and QUAL reversed.  mappings_sorted as in quantify_reads.  -> (rc, experiment)"""
+    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity and keep_best as in quantify_reads.
+    -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     _check_mappings_sorted(mappings_sorted, mappings_format)
+    validate, vstats = _validation(validate_mappings, min_identity, keep_best)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -218,7 +263,8 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                         raise ValueError(f"{reads1_path} and {reads2_path} are out of step at record {done + bad}: "
                                          f"{nm1.decode('utf-8', 'replace')!r} against {nm2.decode('utf-8', 'replace')!r}")
                 done += n
-                h, o = idx.map_reads(r1, r2)
+                h, o = idx.map_reads(r1, r2, validate=validate)
+                _add_verify_stats(vstats, idx)
                 if sam is not None:
                     q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals
                     sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
@@ -238,4 +284,5 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
         if sam is not None:
             sam.close()
         idx.close()
+    _report_verify_stats(exp, vstats, validate, sopt)
     return rc, exp

@@ -1,0 +1,73 @@
+// verify_harness.cpp -- csrc/verifyfmt.h alone, as plain C++ (g++ -Wall -Wextra -Werror): a job counted byte by byte and sixteen bases
+// at a time, and the whole pass run serially.  tests/test_verify_cpu.py compares them with hits.verify_hits_host.  Built with
+// -DVERIFY_HARNESS_MAIN (and -fsanitize=address,undefined) it is a stand-alone program: it reads cases with their expected results
+// from a file (tests/verify_corpus.py: blob) and runs both ways of counting over them; every text is copied to a block of its own
+// size first (vf_serial_verify), so a byte read outside a mate or a transcript is a sanitizer report.
+#include "verifyfmt.h"
+
+#include <cstdio>
+#include <cstring>
+
+using namespace sfgpu;
+
+extern "C" {
+
+uint32_t vfh_code(uint32_t b) { return vf_code((unsigned char)b); }
+
+void vfh_job(const char* r, uint64_t len, int fwd, const char* t, uint64_t tlen, int64_t pos, int windows, uint32_t lanes, uint64_t* mism, uint64_t* over) {
+    const VfCount c = windows ? vf_job_windows(r, len, fwd != 0, t, tlen, pos, lanes) : vf_job_serial(r, len, fwd != 0, t, tlen, pos);
+    *mism = c.mism; *over = c.over;
+}
+
+int vfh_passes(uint64_t len, uint64_t mism, uint64_t over, uint32_t permille) { return vf_passes(len, mism, over, permille); }
+
+// the whole pass; -> the number of survivors (the outputs have room for the input's records), or -(1 + the lowest record with tid >= M)
+int64_t vfh_verify(const char* tseq, const uint64_t* tseq_off, const uint32_t* tlen, uint64_t M, const char* seq1, const uint64_t* off1, const char* seq2,
+                   const uint64_t* off2, uint32_t n_reads, const sfgpu_hit* hits, const uint32_t* hit_off, uint32_t permille, int keep_best, int windows,
+                   sfgpu_hit* out_hits, uint32_t* out_off, sfgpu_hit_score* out_scores, sfgpu_verify_stats* stats) {
+    std::vector<sfgpu_hit> h; std::vector<uint32_t> o; std::vector<sfgpu_hit_score> s;
+    const uint64_t bad = vf_serial_verify(tseq, tseq_off, tlen, M, seq1, off1, seq2, off2, n_reads, hits, hit_off, permille, keep_best != 0, windows != 0, 16, &h, &o, &s, stats);
+    if (bad) return -(int64_t)bad;
+    if (!h.empty()) { memcpy(out_hits, h.data(), h.size() * sizeof(sfgpu_hit)); memcpy(out_scores, s.data(), s.size() * sizeof(sfgpu_hit_score)); }
+    memcpy(out_off, o.data(), o.size() * 4);
+    return (int64_t)h.size();
+}
+
+}
+
+#ifdef VERIFY_HARNESS_MAIN
+template <typename T>
+static bool take(FILE* f, std::vector<T>* v, uint64_t n) {
+    v->resize(n);
+    return n == 0 || fread(v->data(), sizeof(T), n, f) == n;
+}
+
+int main(int argc, char** argv) {
+    if (argc != 2) { fprintf(stderr, "usage: %s cases.bin\n", argv[0]); return 2; }
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) { perror(argv[1]); return 2; }
+    uint64_t n_cases = 0, hd[11];
+    while (fread(hd, 8, 11, f) == 11) {
+        const uint64_t M = hd[0], n_reads = hd[2], n_rec = hd[5], n_out = hd[9];
+        const bool paired = hd[8] != 0;
+        std::vector<char> ts, s1, s2; std::vector<uint64_t> toff, o1, o2, want_stats; std::vector<uint32_t> tl, hoff, want_off;
+        std::vector<sfgpu_hit> hits, want_hits; std::vector<sfgpu_hit_score> want_scores;
+        if (!take(f, &ts, hd[1]) || !take(f, &toff, M) || !take(f, &tl, M) || !take(f, &s1, hd[3]) || !take(f, &o1, n_reads + 1) || !take(f, &s2, hd[4]) ||
+            !take(f, &o2, paired ? n_reads + 1 : 0) || !take(f, &hits, n_rec) || !take(f, &hoff, n_reads + 1) || !take(f, &want_hits, n_out) ||
+            !take(f, &want_off, n_reads + 1) || !take(f, &want_scores, n_out) || !take(f, &want_stats, 7)) { fprintf(stderr, "case %llu: short file\n", (unsigned long long)n_cases); return 2; }
+        for (int windows = 0; windows < 2; ++windows) {
+            std::vector<sfgpu_hit> h; std::vector<uint32_t> o; std::vector<sfgpu_hit_score> s; sfgpu_verify_stats st;
+            const uint64_t bad = vf_serial_verify(ts.data(), toff.data(), tl.data(), M, s1.data(), o1.data(), paired ? s2.data() : nullptr, paired ? o2.data() : nullptr,
+                                                  (uint32_t)n_reads, hits.data(), hoff.data(), (uint32_t)hd[6], hd[7] != 0, windows != 0, 16, &h, &o, &s, &st);
+            const uint64_t got_stats[7] = {st.records_in, st.records_out, st.reads_in, st.reads_out, st.failed_identity, st.dropped_not_best, st.sum_mism};
+            const bool ok = !bad && h.size() == n_out && o == want_off && (n_out == 0 || (!memcmp(h.data(), want_hits.data(), n_out * sizeof(sfgpu_hit)) &&
+                            !memcmp(s.data(), want_scores.data(), n_out * sizeof(sfgpu_hit_score)))) && !memcmp(got_stats, want_stats.data(), sizeof got_stats);
+            if (!ok) { fprintf(stderr, "case %llu (%s): differs from the statement\n", (unsigned long long)n_cases, windows ? "windows" : "serial"); return 1; }
+        }
+        ++n_cases;
+    }
+    fclose(f);
+    printf("verify harness ok: %llu cases\n", (unsigned long long)n_cases);
+    return 0;
+}
+#endif

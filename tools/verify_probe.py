@@ -1,0 +1,169 @@
+"""dev probe: what hit verification (sfgpu_hits_verify) costs and what it drops -> profiles/verify_probe.json
+
+1. cost, on the batch of tools/mapper_probe.py (80 000 transcripts, VERIFY_R pairs of 2 x 100 bases from fragments of 250), error-free
+   and with 2 % substitutions: the device's result is first asserted equal to hits.verify_hits_host on a slice; then medians of 5 after
+   a warm-up of sfgpu_hits_verify, of sfgpu_map_reads on the same batch, and of a plain device-to-device copy of the bytes the pass has
+   to move (each job's mate bases, 24 + 24 bytes a surviving record, 8 bytes of score).
+2. effect, on a spliced synthetic transcriptome (60 random exons of 40 - 220 bases, ten genes of four isoforms, 600 single-end reads of
+   100 bases from either strand) at 0 / 1 / 2 / 4 % substitutions and min_identity 0.85 / 0.9 / 0.95: records dropped, TRUE records
+   (source transcript, strand and position) dropped, reads left without a record."""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import sailfish_amd as sf
+from sailfish_amd import _lib, hits as H, synth
+
+dev = torch.device("cuda:0")
+ACGT = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=dev)
+
+
+def timed(fn, reps=5):
+    fn(); torch.cuda.synchronize()                                     # warm-up
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize(); out.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(out), out
+
+
+class Transcripts:
+    """the transcripts as verify_hits_host wants them (bytes by index), cut from the host copy on demand"""
+    def __init__(self, seq, off):
+        self.seq, self.off = seq.cpu().numpy(), off.cpu().numpy()
+
+    def __len__(self):
+        return len(self.off) - 1
+
+    def __getitem__(self, t):
+        return self.seq[self.off[t]:self.off[t + 1]].tobytes()
+
+
+def cost(M, R, L=100):
+    g = torch.Generator(device=dev); g.manual_seed(1)
+    ref_len = synth.transcript_lengths(M, device=dev).long()
+    off = torch.zeros(M + 1, dtype=torch.int64, device=dev); torch.cumsum(ref_len, 0, out=off[1:])
+    N = int(off[-1])
+    seq = ACGT[torch.randint(0, 4, (N,), generator=g, device=dev)]
+    t = torch.randint(0, M, (R,), generator=g, device=dev)
+    p = (torch.rand(R, generator=g, device=dev, dtype=torch.float64) * (ref_len[t] - 250).clamp_min(0).double()).long()
+    start = off[t] + p
+    comp = torch.zeros(256, dtype=torch.uint8, device=dev); comp[list(b"ACGT")] = torch.tensor(list(b"TGCA"), dtype=torch.uint8, device=dev)
+    m1 = torch.empty((R, L), dtype=torch.uint8, device=dev); m2 = torch.empty((R, L), dtype=torch.uint8, device=dev)
+    idxs = torch.arange(L, device=dev)
+    for a in range(0, R, 1 << 20):                                     # (in pieces: the gather indices are 8 bytes a base)
+        s = start[a:a + (1 << 20), None]
+        m1[a:a + (1 << 20)] = seq[(s + idxs[None, :]).clamp_max(N - 1)]
+        m2[a:a + (1 << 20)] = comp[seq[(s + 249 - idxs[None, :]).clamp_max(N - 1)].long()]
+    roff = torch.arange(R + 1, device=dev, dtype=torch.int64) * L
+    index = sf.mapper.QuasiIndex((seq, off), device=dev)
+    Lb = _lib.lib()
+    rows = []
+    for rate in (0.0, 0.02):
+        if rate:
+            for m in (m1, m2):
+                hit = torch.rand(m.shape, generator=g, device=dev) < rate
+                m[hit] = ACGT[torch.randint(0, 4, (int(hit.sum()),), generator=g, device=dev)]
+        r1, r2 = (m1.reshape(-1), roff), (m2.reshape(-1), roff)
+        hits, hoff = index.map_reads(r1, r2)
+        n = hits.numel() // 24
+        # the device against the statement on a slice
+        k = min(R, 1500)
+        cut = int(hoff[k].item())
+        sl1, sl2 = ([bytes(x) for x in m[:k].cpu().numpy()] for m in (m1, m2))
+        tx = Transcripts(seq, off)
+        for kb in (False, True):
+            dh, do, ds, dst = H.verify_hits(index, hits[: cut * 24], hoff[: k + 1], sl1, sl2, min_identity=0.9, keep_best=kb)
+            wh, wo, ws, wst = H.verify_hits_host(tx, hits[: cut * 24].cpu().numpy().view(H.HIT_DTYPE), hoff[: k + 1].cpu().numpy(), sl1, sl2, 900, kb)
+            assert np.array_equal(dh.cpu().numpy().view(H.HIT_DTYPE), wh) and np.array_equal(do.cpu().numpy().view(np.uint32), wo)
+            assert np.array_equal(ds.cpu().numpy().view(H.SCORE_DTYPE), ws) and dst == wst, (dst, wst)
+        out_hits, out_off, scores = torch.empty_like(hits), torch.empty_like(hoff), torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
+        o = _lib.VerifyOpts(900, 0); st = _lib.VerifyStats(); n_out = C.c_uint64(0); nh = C.c_uint64(0)
+        scratch = torch.empty_like(hits)
+
+        def verify():
+            _lib.check(Lb.sfgpu_hits_verify(index._h, _lib.ptr(r1[0]), _lib.ptr(roff), _lib.ptr(r2[0]), _lib.ptr(roff), R, _lib.ptr(hits), _lib.ptr(hoff),
+                                            C.byref(o), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(st), None))
+
+        def remap():
+            _lib.check(Lb.sfgpu_map_reads(index._h, _lib.ptr(r1[0]), _lib.ptr(roff), _lib.ptr(r2[0]), _lib.ptr(roff), R, _lib.ptr(scratch), n, _lib.ptr(out_off),
+                                          C.byref(nh), None))
+        v_ms, v_all = timed(verify)
+        m_ms, m_all = timed(remap)
+        status = hits.view(-1, 24)[:, 22]
+        jobs = int(n + (status == 3).sum().item())
+        moved = jobs * L + 56 * n_out.value
+        src = torch.empty(moved, dtype=torch.uint8, device=dev); dst = torch.empty_like(src)
+        c_ms, c_all = timed(lambda: dst.copy_(src))
+        rows.append(dict(substitution_rate=rate, pairs=R, records=n, jobs=jobs, stats=st.as_dict(), verify_ms=v_ms, verify_ms_runs=v_all, map_reads_ms=m_ms,
+                         map_reads_ms_runs=m_all, bytes_moved=moved, d2d_copy_ms=c_ms, d2d_copy_ms_runs=c_all, verify_over_map=v_ms / m_ms,
+                         verify_over_copy=v_ms / c_ms, verify_ms_per_10M_pairs=v_ms * 1e7 / R, map_reads_ms_per_10M_pairs=m_ms * 1e7 / R))
+        print(json.dumps(rows[-1]), flush=True)
+        del src, dst
+    index.close()
+    return rows
+
+
+def effect():
+    rng = np.random.default_rng(7)
+    bases = np.frombuffer(b"ACGT", np.uint8)
+    exons = [bytes(rng.choice(bases, rng.integers(40, 221))) for _ in range(60)]
+    seqs = []
+    for gene in range(10):
+        own = exons[6 * gene:6 * gene + 6]
+        for iso in range(4):
+            keep = [e for i, e in enumerate(own) if i in (0, 5) or rng.random() < 0.6]
+            seqs.append(b"".join(keep))
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    truth, clean = [], []
+    while len(clean) < 600:
+        t = int(rng.integers(0, len(seqs)))
+        if len(seqs[t]) < 100:
+            continue
+        p = int(rng.integers(0, len(seqs[t]) - 99)); fwd = int(rng.random() < 0.5)
+        r = seqs[t][p:p + 100]
+        clean.append(r if fwd else r.translate(comp)[::-1]); truth.append((t, fwd, p))
+    index = sf.mapper.QuasiIndex(seqs, device=dev)
+    sub = {65: b"CGT", 67: b"AGT", 71: b"ACT", 84: b"ACG"}
+    rows = []
+    for rate in (0.0, 0.01, 0.02, 0.04):
+        reads = []
+        for r in clean:
+            b = bytearray(r)
+            for i in np.nonzero(rng.random(100) < rate)[0]:
+                b[i] = sub[b[i]][int(rng.integers(0, 3))]
+            reads.append(bytes(b))
+        hits, off = index.map_reads(reads)
+        h, o = sf.mapper.hits_to_numpy(hits, off)
+
+        def true_records(h, o):
+            return sum(int(((h["tid"][o[r]:o[r + 1]] == t) & (h["fwd"][o[r]:o[r + 1]] == f) & (h["pos"][o[r]:o[r + 1]] == p)).any()) for r, (t, f, p) in enumerate(truth))
+        for mi in (0.85, 0.9, 0.95):
+            vh, vo, _, st = H.verify_hits(index, hits, off, reads, min_identity=mi)
+            kh, ko = sf.mapper.hits_to_numpy(vh, vo)
+            rows.append(dict(substitution_rate=rate, min_identity=mi, records=len(h), records_dropped=len(h) - len(kh), true_records=true_records(h, o),
+                             true_records_dropped=true_records(h, o) - true_records(kh, ko), reads_mapped=st["reads_in"],
+                             reads_left_without_records=st["reads_in"] - st["reads_out"]))
+            print(json.dumps(rows[-1]), flush=True)
+    index.close()
+    return rows
+
+
+if __name__ == "__main__":
+    M, R = int(os.environ.get("VERIFY_M", 80000)), int(os.environ.get("VERIFY_R", 10_000_000))
+    out = dict(device=torch.cuda.get_device_name(0), transcripts=M, effect=effect(), cost=cost(M, R))
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "verify_probe.json")
+    if len(sys.argv) > 1:
+        path = sys.argv[1]
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", path)

@@ -1280,6 +1280,46 @@ SFGPU_API int sfgpu_hits_verify(const sfgpu_index* idx, const char* d_seq1, cons
                                 sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, sfgpu_hit_score* d_scores_out, uint64_t* n_out,
                                 sfgpu_verify_stats* stats, sfgpu_stream stream);
 
+/* The same pass scored WITH GAPS: a job's banded edit distance in place of its ungapped count, so that a read with an indel against
+ * the transcript keeps its true record.  Arguments, jobs, base codes, orientation, output layout and order are sfgpu_hits_verify's;
+ * the rule is stated once in csrc/verifygfmt.h (hits.gapped_edits_host / hits.verify_hits_gapped_host are the Python statement).
+ * For a job of len oriented bases a[] at pos on a transcript of tlen bases, with band k = max_indel (1 .. 15):
+ *   cells   D[i][d], rows i = -1 .. len - 1, diagonals d = -k .. k; cell (i, d) aligns read base i to x = pos + i + d.  The column
+ *           character is the transcript's base code for 0 <= x < tlen and OFF elsewhere; sub(i, x) = 0 iff a[i] is a base and equals
+ *           it, else 1 (N matches nothing, OFF matches nothing).
+ *   start   D[-1][d] = 0 for every d: the start diagonal is free, since the mapper's seed may lie behind an indel.
+ *   row     V[d] = min(D[i-1][d] + sub(i, pos + i + d), D[i-1][d+1] + 1) (the second term for d < k), then
+ *           D[i][d] = min over d' <= d of V[d'] + (d - d').
+ *   edits   min over d of D[len-1][d]; 0 for len == 0.  edits <= mism + over of the ungapped pass (k = 0 would be equal).
+ *   pass    a job passes iff 1000 * (len - edits) >= min_identity_permille * len; a record iff all its jobs do.  keep_best: of a
+ *           read's passing records those of least cost (edits summed over the record's jobs, unsaturated).
+ *   score   per survivor {edits, ungapped, mate_edits, mate_ungapped}: ungapped = mism + over on the recorded diagonal; the fields
+ *           saturate at 65 535 (the decisions use the unsaturated values); the mate fields are 0 unless the status is 3.
+ *   stats   as sfgpu_verify_stats with sum_edits for sum_mism, and `rescued`: the survivors with at least one job that the ungapped
+ *           rule (1000 * (len - over - mism) >= min_identity_permille * len) fails.
+ *   errors  as sfgpu_hits_verify (tid >= M: SFGPU_ERR_RANGE naming the lowest record, the outputs untouched; a record naming mate 2 of
+ *           a single-end batch: SFGPU_ERR_INVALID); max_indel outside 1 .. 15: SFGPU_ERR_INVALID.
+ * The records' pos, and so the CIGAR and POS a mappings writer derives from them, still describe the recorded diagonal.  Mates
+ * shorter than 2^30 bases.  Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_hit_gscore { uint16_t edits, ungapped, mate_edits, mate_ungapped; } sfgpu_hit_gscore;      /* 8 bytes */
+typedef struct sfgpu_verify_gopts {
+    uint32_t min_identity_permille;   /* 0 .. 1000 */
+    int32_t  keep_best;
+    uint32_t max_indel;               /* 1 .. 15: the band's half width */
+} sfgpu_verify_gopts;
+typedef struct sfgpu_verify_gstats {
+    uint64_t records_in, records_out;
+    uint64_t reads_in, reads_out;     /* reads with at least one record, before and after */
+    uint64_t failed_identity;         /* records with a job below min_identity_permille */
+    uint64_t dropped_not_best;        /* passing records dropped by keep_best */
+    uint64_t sum_edits;               /* edits over the survivors' jobs, unsaturated */
+    uint64_t rescued;                 /* survivors that the ungapped rule would have dropped */
+} sfgpu_verify_gstats;
+SFGPU_API int sfgpu_hits_verify_gapped(const sfgpu_index* idx, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                       uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_verify_gopts* opts,
+                                       sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, sfgpu_hit_gscore* d_scores_out, uint64_t* n_out,
+                                       sfgpu_verify_gstats* stats, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

@@ -212,6 +212,18 @@ class VerifyStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class VerifyGOpts(C.Structure):
+    _fields_ = [("min_identity_permille", C.c_uint32), ("keep_best", C.c_int32), ("max_indel", C.c_uint32)]
+
+
+class VerifyGStats(C.Structure):
+    _fields_ = [("records_in", C.c_uint64), ("records_out", C.c_uint64), ("reads_in", C.c_uint64), ("reads_out", C.c_uint64),
+                ("failed_identity", C.c_uint64), ("dropped_not_best", C.c_uint64), ("sum_edits", C.c_uint64), ("rescued", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BiasSampler(C.Structure):
     _fields_ = [("d_seq", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_ref_len", C.c_void_p), ("d_read_bias", C.c_void_p),
                 ("remaining_bias_samples", C.POINTER(C.c_int64)), ("d_observed_gc", C.c_void_p), ("d_gc_prefix", C.c_void_p),
@@ -333,6 +345,8 @@ _SIGS = {
                                     C.POINTER(FilterStats), _P]),
     "sfgpu_hits_verify": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(VerifyOpts), _P, _P, _P, C.POINTER(C.c_uint64),
                                     C.POINTER(VerifyStats), _P]),
+    "sfgpu_hits_verify_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(VerifyGOpts), _P, _P, _P, C.POINTER(C.c_uint64),
+                                           C.POINTER(VerifyGStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

@@ -17,6 +17,10 @@ assert HIT_DTYPE.itemsize == 24
 # one score per record that survives verify_hits: sfgpu_hit_score
 SCORE_DTYPE = np.dtype([("mism", "<u2"), ("over", "<u2"), ("mate_mism", "<u2"), ("mate_over", "<u2")])
 assert SCORE_DTYPE.itemsize == 8
+# ... and one per record that survives verify_hits(max_indel=1 .. 15): sfgpu_hit_gscore
+GSCORE_DTYPE = np.dtype([("edits", "<u2"), ("ungapped", "<u2"), ("mate_edits", "<u2"), ("mate_ungapped", "<u2")])
+assert GSCORE_DTYPE.itemsize == 8
+MAX_INDEL = 15
 SINGLE_END, PAIRED_END_LEFT, PAIRED_END_RIGHT, PAIRED_END_PAIRED = 0, 1, 2, 3        # rapmap::utils::MateStatus
 SAME, AWAY, TOWARD, NONE = 0, 1, 2, 3                                                # ReadOrientation
 SA, AS, S, A, U = 0, 1, 2, 3, 4                                                      # ReadStrandedness
@@ -117,6 +121,14 @@ _BASE_CODE = np.full(256, 4, np.uint8)
 for _i, _b in enumerate(b"ACGT"):
     _BASE_CODE[_b] = _BASE_CODE[_b + 32] = _i
 VERIFY_STATS = ("records_in", "records_out", "reads_in", "reads_out", "failed_identity", "dropped_not_best", "sum_mism")
+VERIFYG_STATS = ("records_in", "records_out", "reads_in", "reads_out", "failed_identity", "dropped_not_best", "sum_edits", "rescued")
+
+
+def _max_indel(max_indel):
+    k = int(max_indel)
+    if k != max_indel or not 0 <= k <= MAX_INDEL:
+        raise ValueError(f"max_indel = {max_indel!r} is no integer in 0 .. {MAX_INDEL}")
+    return k
 
 
 def _permille(min_identity):
@@ -188,6 +200,129 @@ def verify_hits_host(transcripts, hits, offsets, reads1, reads2, min_identity_pe
     return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=SCORE_DTYPE), stats
 
 
+def _record_jobs(h, r, reads1, reads2):
+    """the jobs of record h of read r: (mate's bytes, forward?, pos) each"""
+    st = int(h["mate_status"])
+    jobs = [(reads2[r] if st == 2 else reads1[r], bool(h["fwd"]), int(h["pos"]))]
+    if st == 3:
+        jobs.append((reads2[r], bool(h["mate_fwd"]), int(h["mate_pos"])))
+    return jobs
+
+
+def gapped_edits_host(transcripts, hits, offsets, reads1, reads2, max_indel):
+    """The statement of a job's banded edit distance (csrc/verifygfmt.h restated in numpy).  Arguments as verify_hits_host; band k =
+    max_indel (0 .. 15; 0 is the ungapped pass's diagonal alone).  For a job of len oriented bases a[] at pos on a transcript of tlen
+    bases: cell (i, d), d = -k .. k, aligns read base i to x = pos + i + d; b(x) is the transcript's code for 0 <= x < tlen and OFF
+    elsewhere; sub(i, x) = 0 iff a[i] <= 3 and b(x) == a[i], else 1.  D[-1][d] = 0 for every d; per row V[d] = min(D[i-1][d] +
+    sub(i, pos + i + d), D[i-1][d+1] + 1) (the second term for d < k), then D[i][d] = min over d' <= d of V[d'] + (d - d'); edits =
+    min over d of D[len-1][d], 0 for len == 0.  One row at a time, the band at once (and the jobs of one length side by side).
+    -> (edits, ungapped): int64 arrays [records, 2], job 1's column 0 where a record has one job; ungapped = mism + over of
+    verify_hits_host on the recorded diagonal.  ValueError naming the lowest record whose tid is not a transcript."""
+    k = _max_indel(max_indel)
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    n_rec = int(off[-1]) if len(off) else 0
+    bad = np.nonzero(hits["tid"][:n_rec] >= len(transcripts))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(transcripts)}")
+    OFF = 5
+    d = np.arange(-k, k + 1, dtype=np.int64)
+    ramp = np.arange(2 * k + 1, dtype=np.int64)
+    tcodes = {}
+
+    def oriented(read, fwd):
+        c = _BASE_CODE[np.frombuffer(read, np.uint8)]
+        return c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
+
+    def same_length_jobs(jobs, n):
+        """jobs: (read, fwd, tid, pos) of n bases each -> (edits, ungapped), the rows in step over all of them"""
+        sub = np.empty((len(jobs), n, 2 * k + 1), np.int8)
+        for j, (read, fwd, tid, pos) in enumerate(jobs):
+            a = oriented(read, fwd)
+            if tid not in tcodes:
+                tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
+            t = tcodes[tid]
+            x = pos + np.arange(n, dtype=np.int64)[:, None] + d[None, :]
+            on = (x >= 0) & (x < len(t))
+            b = np.full(x.shape, OFF, np.uint8)
+            b[on] = t[x[on]]
+            sub[j] = ~((a[:, None] <= 3) & (b == a[:, None]))
+        D = np.zeros((len(jobs), 2 * k + 1), np.int64)
+        for i in range(n):
+            V = D + sub[:, i, :]
+            if k:
+                np.minimum(V[:, :-1], D[:, 1:] + 1, out=V[:, :-1])
+            V -= ramp
+            np.minimum.accumulate(V, axis=1, out=V)
+            V += ramp
+            D = V
+        return D.min(axis=1), sub[:, :, k].astype(np.int64).sum(axis=1)
+
+    by_len, where = {}, {}                             # the distinct jobs by length; (job) -> (length, index among them)
+    slots = []
+    for r in range(len(off) - 1):
+        for i in range(off[r], off[r + 1]):
+            for j, (rd, f, p) in enumerate(_record_jobs(hits[i], r, reads1, reads2)):
+                key = (r, rd is not reads1[r], f, int(hits[i]["tid"]), p)
+                if key not in where:
+                    group = by_len.setdefault(len(rd), [])
+                    where[key] = (len(rd), len(group))
+                    group.append((rd, f, int(hits[i]["tid"]), p))
+                slots.append((i, j, where[key]))
+    done = {n: same_length_jobs(jobs, n) for n, jobs in by_len.items() if n}
+    edits, ungapped = np.zeros((n_rec, 2), np.int64), np.zeros((n_rec, 2), np.int64)
+    for i, j, (n, at) in slots:
+        if n:
+            edits[i, j], ungapped[i, j] = done[n][0][at], done[n][1][at]
+    return edits, ungapped
+
+
+def verify_hits_gapped_host(transcripts, hits, offsets, reads1, reads2, min_identity_permille, keep_best, max_indel, edits=None):
+    """The statement of gapped hit verification (what sfgpu_hits_verify_gapped is judged by), on top of gapped_edits_host (whose
+    result for the same batch and max_indel may be handed in as `edits`: it depends on neither permille nor keep_best).  A job passes
+    iff 1000 (len - edits) >= permille len, a record iff all its jobs pass; keep_best keeps, of a read's passing records, those of
+    least summed edits.  Score: {edits, ungapped, mate_edits, mate_ungapped}, saturating at 65 535, the mate fields 0 unless the status
+    is 3.  Stats: VERIFYG_STATS -- `rescued` counts the survivors with a job that fails the ungapped rule 1000 (len - ungapped) >=
+    permille len.  max_indel: 1 .. 15.  -> (hits, offsets uint32[R + 1], scores GSCORE_DTYPE, stats dict)"""
+    k = _max_indel(max_indel)
+    if k < 1:
+        raise ValueError("max_indel lies outside 1 .. 15")
+    permille = int(min_identity_permille)
+    if not 0 <= permille <= 1000:
+        raise ValueError("min_identity_permille lies outside 0 .. 1000")
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    ed, ung = gapped_edits_host(transcripts, hits, offsets, reads1, reads2, k) if edits is None else edits
+    keep, scores, out_off = [], [], [0]
+    stats = dict.fromkeys(VERIFYG_STATS, 0)
+    stats["records_in"] = int(off[-1]) if len(off) else 0
+    for r in range(len(off) - 1):
+        recs = []
+        for i in range(off[r], off[r + 1]):
+            lens = [len(rd) for rd, _, _ in _record_jobs(hits[i], r, reads1, reads2)]
+            e, u = [int(v) for v in ed[i, :len(lens)]], [int(v) for v in ung[i, :len(lens)]]
+            ok = all(1000 * (n - x) >= permille * n for n, x in zip(lens, e))
+            rescued = any(1000 * (n - x) < permille * n for n, x in zip(lens, u))
+            recs.append((i, ok, sum(e), e, u, rescued))
+        passing = [x for x in recs if x[1]]
+        stats["failed_identity"] += len(recs) - len(passing)
+        if keep_best and passing:
+            best = min(x[2] for x in passing)
+            stats["dropped_not_best"] += sum(x[2] != best for x in passing)
+            passing = [x for x in passing if x[2] == best]
+        for i, _, cost, e, u, rescued in passing:
+            keep.append(i)
+            flat = [min(v, 65535) for pair in zip(e, u) for v in pair] + [0, 0]
+            scores.append(tuple(flat[:4]))
+            stats["sum_edits"] += cost
+            stats["rescued"] += int(rescued)
+        stats["reads_in"] += int(off[r + 1] > off[r])
+        stats["reads_out"] += int(bool(passing))
+        out_off.append(len(keep))
+    stats["records_out"] = len(keep)
+    return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=GSCORE_DTYPE), stats
+
+
 def _device_reads(reads, dev):
     """(uint8 bases, int64 offsets) on the device, from such a pair or from a list of str / bytes"""
     if not isinstance(reads, tuple):
@@ -196,14 +331,19 @@ def _device_reads(reads, dev):
     return reads[0].to(dev).contiguous(), reads[1].to(dev).contiguous()
 
 
-def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, keep_best=False):
+def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, keep_best=False, max_indel=0):
     """Verify the mapper's hit records against the transcripts' bases on the device (sfgpu_hits_verify; the rules are
     verify_hits_host's).  index: the mapper.QuasiIndex the records come from; hits / offsets: device tensors as QuasiIndex.map_reads
     returns them; reads1 / reads2: the batch's reads, packed (bases, offsets) pairs or lists, as map_reads takes them.  A job passes
     with at least min_identity of its bases equal to the transcript's on the recorded diagonal (the permille is
     int(round(min_identity * 1000)); outside 0 .. 1000: ValueError); keep_best keeps only a read's records of least mism + over.
+    max_indel = 1 .. 15 scores with gaps instead (sfgpu_hits_verify_gapped; the rules are verify_hits_gapped_host's): a job's cost is
+    its banded edit distance, within max_indel diagonals of the recorded one and with a free start diagonal, so a read with an indel
+    keeps its true record; the scores are then GSCORE_DTYPE records and the stats VERIFYG_STATS.  The records are returned as they
+    came: pos still names the recorded diagonal.  Anything else than 0 .. 15: ValueError.
     -> (hits, offsets, scores: uint8 device tensor of SCORE_DTYPE records, stats dict)"""
     permille = _permille(min_identity)
+    k = _max_indel(max_indel)
     dev = index.device
     d_hits, d_off = _device_hits(hits, offsets, dev)
     R = int(d_off.numel()) - 1
@@ -217,14 +357,14 @@ def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, 
     out_hits = torch.empty(max(n, 1) * 24, dtype=torch.uint8, device=dev)
     out_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
     scores = torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
-    o = _lib.VerifyOpts(permille, int(bool(keep_best)))
-    st = _lib.VerifyStats()
+    o = _lib.VerifyGOpts(permille, int(bool(keep_best)), k) if k else _lib.VerifyOpts(permille, int(bool(keep_best)))
+    st = _lib.VerifyGStats() if k else _lib.VerifyStats()
+    entry = _lib.lib().sfgpu_hits_verify_gapped if k else _lib.lib().sfgpu_hits_verify
     n_out = C.c_uint64(0)
     with torch.cuda.device(dev):
         torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.lib().sfgpu_hits_verify(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
-                                                C.byref(o), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(st),
-                                                _lib.current_stream_ptr()))
+        _lib.check(entry(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                         C.byref(o), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(st), _lib.current_stream_ptr()))
     return out_hits[: n_out.value * 24], out_off, scores[: n_out.value * 8], st.as_dict()
 
 

@@ -68,7 +68,7 @@ class QuasiIndex:
 
     def map_reads(self, reads1, reads2=None, validate=None):
         """reads1 / reads2: lists of str / bytes, or (uint8 tensor, int64 offsets) pairs already packed.
-        validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best; {} = its defaults): the records are then
+        validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best, max_indel; {} = its defaults): the records are then
         verified against the transcripts' bases before they are returned, and `last_scores` / `last_verify_stats` hold the
         survivors' scores and the pass's counters.
         -> (hits: uint8 device tensor [n_hits * 24] of HIT_DTYPE records, offsets: int32 device tensor [R + 1])"""
@@ -120,14 +120,17 @@ def _check_mappings_sorted(mappings_sorted, mappings_format):
         raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
 
 
-def _validation(validate_mappings, min_identity, keep_best):
+def _validation(validate_mappings, min_identity, keep_best, max_indel=0):
     """-> (the `validate` dict for QuasiIndex.map_reads or None, the counters to accumulate over the batches); ValueError at once
-    for a min_identity outside 0 .. 1, before anything is indexed"""
+    for a min_identity outside 0 .. 1 or a max_indel outside 0 .. 15, before anything is indexed"""
     if not validate_mappings:
         return None, None
-    from .hits import VERIFY_STATS, _permille
+    from .hits import VERIFY_STATS, VERIFYG_STATS, _max_indel, _permille
     _permille(min_identity)
-    return dict(min_identity=min_identity, keep_best=bool(keep_best)), dict.fromkeys(VERIFY_STATS, 0)
+    k = _max_indel(max_indel)
+    if not k:
+        return dict(min_identity=min_identity, keep_best=bool(keep_best)), dict.fromkeys(VERIFY_STATS, 0)
+    return dict(min_identity=min_identity, keep_best=bool(keep_best), max_indel=k), dict.fromkeys(VERIFYG_STATS, 0)
 
 
 def _add_verify_stats(total, idx):
@@ -141,7 +144,12 @@ def _report_verify_stats(exp, total, validate, sopt):
     if exp is not None:
         exp.verify_stats = total
     log = getattr(sopt, "jointLog", None) if sopt is not None else None
-    if total is not None and log is not None:
+    if total is not None and log is not None and validate.get("max_indel"):
+        log(0, "validated mappings (min identity {:g}, max indel {}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
+               "{} of {} mapped reads keep a record; {} edits in the kept records; {} records kept only with gaps".format(
+                   validate["min_identity"], validate["max_indel"], ", best only" if validate["keep_best"] else "", total["records_out"], total["records_in"],
+                   total["failed_identity"], total["dropped_not_best"], total["reads_out"], total["reads_in"], total["sum_edits"], total["rescued"]))
+    elif total is not None and log is not None:
         log(0, "validated mappings (min identity {:g}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
                "{} of {} mapped reads keep a record; {} mismatches in the kept records".format(
                    validate["min_identity"], ", best only" if validate["keep_best"] else "", total["records_out"], total["records_in"],
@@ -159,7 +167,7 @@ def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -172,11 +180,15 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     sort="coordinate": the records stay on the device until the run ends); the estimates never depend on it.
     validate_mappings=True verifies every batch's records against the transcripts' bases (hits.verify_hits with min_identity and
     keep_best) before the batch is written and quantified: the mappings file and the estimates see the same, surviving records; the
-    counters of all batches are left on the experiment as `verify_stats` and go to sopt.jointLog as one line.
+    counters of all batches are left on the experiment as `verify_stats` and go to sopt.jointLog as one line.  max_indel = 1 .. 15
+    (with validate_mappings; outside 0 .. 15: ValueError) scores every mate with gaps -- its banded edit distance within max_indel
+    diagonals of the recorded one -- so reads that carry an indel keep their true records; `verify_stats` then holds `sum_edits` for
+    `sum_mism`, and `rescued`: the records kept only with gaps.  The mappings file receives the surviving records as before: its
+    CIGAR and POS still describe the recorded diagonal, not the gapped alignment.
     -> (rc, experiment)"""
     from . import quant
     _check_mappings_sorted(mappings_sorted, mappings_format)
-    validate, vstats = _validation(validate_mappings, min_identity, keep_best)
+    validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
     sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -221,7 +233,7 @@ def _dollar_separated(bases, off):
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -231,12 +243,12 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     read where the files are out of step, naming the record counted from the start of the files and both names
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
-    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity and keep_best as in quantify_reads.
+    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best and max_indel as in quantify_reads.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     _check_mappings_sorted(mappings_sorted, mappings_format)
-    validate, vstats = _validation(validate_mappings, min_identity, keep_best)
+    validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)

@@ -739,6 +739,18 @@ SFGPU_API int sfgpu_sam_write_text_q(const struct sfgpu_hit* d_hits, const uint3
                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
                                      const uint8_t* d_qual2, int oriented);
+/* sfgpu_sam_write_text_q with the batch's gapped alignment (sfgpu_hits_align_gapped's d_pos, d_op_off, d_ops for the same records:
+ * slot 2 h + which is line `which` of record h); sfgpu_sam_write_text_q is this call with NULL, NULL, NULL, and then every byte is
+ * the same.  Given, a mapped line's POS is d_aln_pos[slot] + 1, its CIGAR the slot's operations (len << 4 | op, MIDNSHP=X), PNEXT the
+ * other line's POS written this way; FLAG and TLEN are unchanged.  A line whose slot has no operation has no base on the transcript:
+ * error_kind 1, and the record's own pos is not consulted.  The three go together (SFGPU_ERR_INVALID otherwise). */
+SFGPU_API int sfgpu_sam_write_text_a(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
+                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
+                                     const uint32_t* d_aln_ops);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
@@ -841,6 +853,15 @@ SFGPU_API int sfgpu_sam_write_bgzf_q(const struct sfgpu_hit* d_hits, const uint3
                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
                                      int oriented);
+/* ... and with the batch's gapped alignment, as sfgpu_sam_write_text_a.  SFGPU_SAMW_BAM: the CIGAR words are the slot's; bin and
+ * error_kind 5 take the reference span (M + D), error_kind 4 compares the bases given with S + M + I and covers more than 65 535
+ * operations. */
+SFGPU_API int sfgpu_sam_write_bgzf_a(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
+                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
 /* The compressed size of every member a BGZF handle writes, kept on the device: what virtual file offsets are made of.
  *   track_members  from this call on every write also keeps its members' sizes (4 bytes a member of device memory, in file order).
  *                  The bytes written, the results and the other calls do not change.
@@ -887,6 +908,14 @@ SFGPU_API int sfgpu_bamsort_collect(sfgpu_bamsort* b, const struct sfgpu_hit* d_
                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                     const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
                                     const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented);
+/* collect with the batch's gapped alignment, as sfgpu_sam_write_bgzf_a: the sort key and the index follow, since both are read from
+ * the records' own pos and CIGAR words */
+SFGPU_API int sfgpu_bamsort_collect_a(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
+                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
 SFGPU_API int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,
                                    void* user, sfgpu_bamsort_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);
@@ -1319,6 +1348,43 @@ SFGPU_API int sfgpu_hits_verify_gapped(const sfgpu_index* idx, const char* d_seq
                                        uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_verify_gopts* opts,
                                        sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, sfgpu_hit_gscore* d_scores_out, uint64_t* n_out,
                                        sfgpu_verify_gstats* stats, sfgpu_stream stream);
+
+/* The gapped ALIGNMENT of the records that survive sfgpu_hits_verify_gapped: the path through the same band, as a position and
+ * BAM CIGAR words per job.  Arguments, jobs, base codes and orientation are sfgpu_hits_verify_gapped's; the rule, with its tie
+ * rules, is stated once in csrc/aligngfmt.h (hits.align_hits_host is the Python statement):
+ *   walk    from the end cell (D[len-1][d] == edits with least |d|, the negative one on a tie) back to row -1, a gap once opened
+ *           continued while it is a candidate, else the first candidate of diagonal, read base unaligned (I), transcript base
+ *           skipped (D).
+ *   trim    at either end columns are dropped until a base aligned to a transcript position 0 <= x < tlen remains: dropped read bases
+ *           are that end's soft clip, dropped D columns vanish.  Nothing left: the job is unalignable and has no operations.
+ *   slots   two per record: slot 2 h + j is job j of record h; the second slot of a record with one job is empty.
+ *   output  d_pos[slot] (the transcript position of the first remaining column, 0-based; 0 where there are no operations),
+ *           d_nm[slot] (mismatching aligned bases + I + D bases), d_op_off[2 n + 1] (CSR over the slots, n =
+ *           d_hit_offsets[n_reads]), d_ops[] (len << 4 | op with M 0, I 1, D 2, S 4, in reference order; room for cap_ops words).
+ *           *n_ops = the words needed.  They do not fit cap_ops: SFGPU_ERR_RANGE, *n_ops is still set and nothing is written.
+ *   scratch 8 * width * ceil(len / 16) bytes per job whose ungapped count is not 0 (width 16 for max_indel <= 7, else 32).  The
+ *           slots run in slices whose scratch stays within scratch_cap_bytes (0: 256 MiB); a single job above it runs alone.
+ *           The cap bounds memory and never changes a result.
+ *   errors  as sfgpu_hits_verify_gapped, the outputs untouched: tid >= M: SFGPU_ERR_RANGE naming the lowest record; NULL
+ *           pointers, max_indel outside 1 .. 15, a record naming mate 2 of a single-end batch: SFGPU_ERR_INVALID.
+ * Mates shorter than 2^28 bases.  Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_align_gopts {
+    uint32_t max_indel;               /* 1 .. 15 */
+    uint32_t reserved;                /* 0 */
+    uint64_t scratch_cap_bytes;       /* 0: 256 MiB */
+} sfgpu_align_gopts;
+typedef struct sfgpu_align_gstats {
+    uint64_t jobs;                    /* slots that are a job */
+    uint64_t jobs_traced;             /* ... whose ungapped count is not 0: the recurrence and the walk ran */
+    uint64_t unalignable;             /* jobs without an operation */
+    uint64_t sum_nm;
+    uint64_t words;                   /* operations over all slots */
+    uint64_t scratch_bytes;           /* the largest slice's scratch */
+} sfgpu_align_gstats;
+SFGPU_API int sfgpu_hits_align_gapped(const sfgpu_index* idx, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                      uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_align_gopts* opts,
+                                      int32_t* d_pos, uint32_t* d_nm, uint64_t* d_op_off, uint32_t* d_ops, uint64_t cap_ops, uint64_t* n_ops,
+                                      sfgpu_align_gstats* stats, sfgpu_stream stream);
 
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,

@@ -224,6 +224,18 @@ class VerifyGStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class AlignGOpts(C.Structure):
+    _fields_ = [("max_indel", C.c_uint32), ("reserved", C.c_uint32), ("scratch_cap_bytes", C.c_uint64)]
+
+
+class AlignGStats(C.Structure):
+    _fields_ = [("jobs", C.c_uint64), ("jobs_traced", C.c_uint64), ("unalignable", C.c_uint64), ("sum_nm", C.c_uint64), ("words", C.c_uint64),
+                ("scratch_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BiasSampler(C.Structure):
     _fields_ = [("d_seq", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_ref_len", C.c_void_p), ("d_read_bias", C.c_void_p),
                 ("remaining_bias_samples", C.POINTER(C.c_int64)), ("d_observed_gc", C.c_void_p), ("d_gc_prefix", C.c_void_p),
@@ -312,6 +324,8 @@ _SIGS = {
                                        C.POINTER(SamWriteResult), _P]),
     "sfgpu_sam_write_text_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
                                        C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
+    "sfgpu_sam_write_text_a": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
+                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -323,12 +337,16 @@ _SIGS = {
     "sfgpu_bamsort_open": (C.c_int, [C.POINTER(_P)]),
     "sfgpu_bamsort_collect": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
                                         C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
+    "sfgpu_bamsort_collect_a": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
+                                          C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
     "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
     "sfgpu_bamsort_close": (C.c_int, [_P]),
     "sfgpu_sam_write_bgzf": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
                                        C.POINTER(SamWriteResult), _P]),
     "sfgpu_sam_write_bgzf_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
                                        C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
+    "sfgpu_sam_write_bgzf_a": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
+                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -347,6 +365,8 @@ _SIGS = {
                                     C.POINTER(VerifyStats), _P]),
     "sfgpu_hits_verify_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(VerifyGOpts), _P, _P, _P, C.POINTER(C.c_uint64),
                                            C.POINTER(VerifyGStats), _P]),
+    "sfgpu_hits_align_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(AlignGOpts), _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(AlignGStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

@@ -1,0 +1,282 @@
+// align_gapped.hip -- sfgpu_hits_align_gapped: the gapped alignment of the records that survive sfgpu_hits_verify_gapped, as a
+// position and BAM CIGAR words per job.  WHAT the alignment of a job is -- candidates, end cell, walk, trim -- is
+// csrc/aligngfmt.h, stated once and run here unchanged; this file is only the way the work is laid out.
+//
+// Two slots per record (slot 2 h + j is job j of record h); count -> scan -> fill, twice:
+//   k_aligng_reads      a lane per read names the read of each of its records
+//   k_aligng_size<W>    a group of W lanes per slot (W = 16 for max_indel <= 7, 32 up to 15) counts the job's ungapped mismatches
+//                       (vf_job_lane + a group sum) and with them its kind -- no job, no bases, all bases match, traced -- and the
+//                       steps of scratch it needs (ceil(len / 16) for a traced job, else none); errors are found here
+//   scan                steps -> the scratch's CSR; the host cuts the slots into slices whose scratch fits the cap (k_aligng_cut)
+//   k_aligng_trace<W, false>  per slice, a group per slot.  Forward: lanes are DIAGONALS, the row is verify_gapped.hip's plus one
+//                       exchange for the lower neighbour's new cell; every 16 rows a lane stores the 4 bits of its 16 cells as one
+//                       64-bit word, the group W consecutive words (128 or 256 bytes).  Backward: ag_walk over those words, a lane
+//                       loading its own word of a step once and the group taking the current lane's by shuffle; this pass counts
+//                       the operations only.
+//   scan                operations -> the outputs' CSR; too many for the caller's room: SFGPU_ERR_RANGE, nothing written
+//   k_aligng_trace<W, true>   the same walk again, writing each run where it belongs, and pos, nm, op_off and the counters.  With one
+//                       slice the scratch still holds the cells and the forward pass is not repeated.
+#include "common.h"
+#include "mapidx.h"
+#include "primitives.h"
+#include "aligngfmt.h"
+
+#include <vector>
+
+namespace sfgpu {
+
+constexpr int kAgBlock = 256;
+constexpr uint64_t kAgDefaultCap = 256ull << 20;
+enum { kAgBadTid = 0, kAgBadMate, kAgJobs, kAgTraced, kAgUnalignable, kAgSumNm, kAgCounters };
+enum : uint8_t { kAgNoJob = 0, kAgNoBases, kAgAllMatch, kAgTracedJob };
+
+template <int W> __device__ __forceinline__ uint64_t ag_group_sum(uint64_t v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, W);
+    return v;
+}
+template <int W> __device__ __forceinline__ uint32_t ag_group_min(uint32_t v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o, W); v = u < v ? u : v; }
+    return v;
+}
+
+__global__ void __launch_bounds__(kAgBlock)
+k_aligng_reads(uint64_t n_reads, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t* __restrict__ rec_read) {
+    const uint64_t r = (uint64_t)blockIdx.x * kAgBlock + threadIdx.x;
+    if (r >= n_reads) return;
+    uint64_t e = hit_off[r + 1], b = hit_off[r];
+    e = e < n_rec ? e : n_rec; b = b < e ? b : e;
+    for (uint64_t i = b; i < e; ++i) rec_read[i] = (uint32_t)r;
+}
+
+struct AgJobDev { const char* m; const char* t; uint64_t len, tl; int64_t pos; bool fwd; };
+__device__ __forceinline__ AgJobDev ag_job_dev(const sfgpu_hit& h, uint32_t j, uint32_t r, const char* tseq, const uint64_t* tseq_off, const uint32_t* tlen,
+                                               const char* seq1, const uint64_t* off1, const char* seq2, const uint64_t* off2) {
+    const VfJob jb = vf_job(h, j);
+    const uint64_t* off = jb.mate ? off2 : off1;
+    const uint64_t mb = off[r];
+    return AgJobDev{(jb.mate ? seq2 : seq1) + mb, tseq + tseq_off[h.tid], off[r + 1] - mb, tlen[h.tid], (int64_t)jb.pos, jb.fwd};
+}
+
+template <int W> __global__ void __launch_bounds__(kAgBlock)
+k_aligng_size(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen, uint64_t M,
+              const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
+              const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ rec_read, uint64_t n_slots, uint32_t* __restrict__ steps /* [n_slots] */,
+              uint8_t* __restrict__ kind /* [n_slots] */, unsigned long long* ctr) {
+    const uint64_t s = (uint64_t)blockIdx.x * (kAgBlock / W) + threadIdx.x / W;
+    const uint32_t lane = threadIdx.x % W;
+    if (s >= n_slots) return;                                        // (a whole group)
+    const sfgpu_hit h = hits[s >> 1];
+    const uint32_t j = (uint32_t)(s & 1u), r = rec_read[s >> 1];
+    uint32_t need = 0; uint8_t kd = kAgNoJob;
+    if (h.tid >= M) { if (lane == 0) atomicMin(&ctr[kAgBadTid], (unsigned long long)(s >> 1)); }
+    else if ((h.mate_status == 2 || vf_n_jobs(h) > 1) && !seq2) { if (lane == 0) atomicMin(&ctr[kAgBadMate], (unsigned long long)(s >> 1)); }
+    else if (j < vf_n_jobs(h) && r != ~0u) {
+        const AgJobDev jb = ag_job_dev(h, j, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+        const VfCount c = vf_job_lane(jb.m, jb.len, jb.fwd, jb.t, jb.tl, jb.pos, lane, W);
+        const uint64_t ungapped = ag_group_sum<W>(c.mism + c.over);
+        kd = jb.len == 0 ? kAgNoBases : ungapped == 0 ? kAgAllMatch : kAgTracedJob;
+        need = kd == kAgTracedJob ? (uint32_t)ag_steps(jb.len) : 0u;
+    }
+    if (lane == 0) { steps[s] = need; kind[s] = kd; }
+}
+
+// the largest b in (a, n_slots] whose slots a .. b - 1 need at most cap_steps of scratch; a + 1 where slot a alone needs more
+__global__ void k_aligng_cut(const uint64_t* __restrict__ prefix, uint64_t n_slots, uint64_t a, uint64_t cap_steps, uint64_t* __restrict__ out /* [2]: b, steps */) {
+    if (threadIdx.x || blockIdx.x) return;
+    uint64_t lo = a + 1, hi = n_slots;                               // prefix[lo] - prefix[a] may exceed the cap: slot a then runs alone
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (prefix[mid] - prefix[a] <= cap_steps) lo = mid; else hi = mid - 1;
+    }
+    out[0] = lo; out[1] = prefix[lo] - prefix[a];
+}
+
+// the forward pass of one job over the group's lanes: the cells' bits into `cells` (W words a step) -> the end lane
+template <int W> __device__ __forceinline__ uint32_t ag_forward_dev(const AgJobDev& jb, uint32_t k, uint32_t lane, uint64_t* __restrict__ cells) {
+    uint32_t D = vg_lane_start(lane, k);
+    for (uint64_t i0 = 0; i0 < jb.len; i0 += kVfStep) {
+        const uint32_t mask = vg_lane_submask(vf_mate_window(jb.m, (int64_t)jb.len, jb.fwd, (int64_t)i0), jb.t, jb.tl, jb.pos, i0, lane, k, jb.fwd);
+        const uint32_t n = jb.len - i0 < kVfStep ? (uint32_t)(jb.len - i0) : kVfStep;
+        uint64_t word = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t up = __shfl_down(D, 1, W), sub = (mask >> j) & 1u;      // (lane W - 1 gets its own: it is never in the band)
+            uint32_t key = vg_key(vg_lane_v(D, up, sub), lane, W);
+#pragma unroll
+            for (int o = 1; o < W; o <<= 1) key = vg_scan_step(key, __shfl_up(key, o, W), lane, (uint32_t)o);
+            const uint32_t nd = vg_lane_d(key, lane, W, k), below = __shfl_up(nd, 1, W);
+            word |= (uint64_t)ag_lane_cand(D, up, sub, nd, below, lane, k) << (4u * j);
+            D = nd;
+        }
+        cells[(i0 / kVfStep) * W + lane] = word;                     // (the group: W consecutive words)
+    }
+    const uint32_t m = ag_group_min<W>(D);
+    return ag_rank_lane(ag_group_min<W>(ag_end_rank(D, m, lane, k)), k);
+}
+
+// ag_walk's fetch: a lane keeps its own word of the step the walk is in; the group takes the current lane's by shuffle
+template <int W> struct AgFetchDev {
+    const uint64_t* cells; uint32_t lane; uint64_t q_have; uint64_t word;
+    __device__ __forceinline__ uint64_t operator()(uint64_t q, uint32_t l) {
+        if (q != q_have) { word = cells[q * W + lane]; q_have = q; }
+        return (uint64_t)__shfl((unsigned long long)word, (int)l, W);
+    }
+};
+
+template <int W, bool WRITE> __global__ void __launch_bounds__(kAgBlock)
+k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen,
+               const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
+               const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ rec_read, const uint8_t* __restrict__ kind, const uint64_t* __restrict__ prefix,
+               uint64_t n_slots, uint64_t a, uint64_t b, uint32_t k, int do_forward, uint64_t* cells /* the slice's */, uint8_t* lane_end /* [n_slots] */,
+               uint32_t* __restrict__ n_ops /* [n_slots], !WRITE */, const uint64_t* __restrict__ woff /* [n_slots + 1], WRITE */, int32_t* __restrict__ pos_out,
+               uint32_t* __restrict__ nm_out, uint64_t* __restrict__ op_off_out, uint32_t* __restrict__ ops_out, unsigned long long* ctr) {
+    __shared__ unsigned long long s_ctr[kAgCounters];
+    if (WRITE) {
+        if (threadIdx.x < kAgCounters) s_ctr[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const uint64_t s = a + (uint64_t)blockIdx.x * (kAgBlock / W) + threadIdx.x / W;
+    const uint32_t lane = threadIdx.x % W;
+    if (s < b) {                                                     // (a whole group)
+        const uint8_t kd = kind[s];
+        const int64_t lo = WRITE ? (int64_t)woff[s] : 0, hi = WRITE ? (int64_t)woff[s + 1] : 0;
+        uint32_t* ops = (WRITE && lane == 0) ? ops_out : nullptr;
+        AgTrace w{};
+        if (kd >= kAgAllMatch) {
+            const AgJobDev jb = ag_job_dev(hits[s >> 1], (uint32_t)(s & 1u), rec_read[s >> 1], tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+            if (kd == kAgAllMatch) w = ag_all_match(jb.len, jb.pos, ops, lo, hi);
+            else {
+                uint64_t* mine = cells + (prefix[s] - prefix[a]) * W;
+                uint32_t le;
+                if (do_forward) { le = ag_forward_dev<W>(jb, k, lane, mine); if (lane == 0) lane_end[s] = (uint8_t)le; }
+                else le = lane_end[s];
+                AgFetchDev<W> fetch{mine, lane, ~0ull, 0ull};
+                w = ag_walk(jb.len, jb.pos, jb.tl, k, le, fetch, ops, lo, hi);
+            }
+        }
+        if (lane == 0) {
+            if (!WRITE) n_ops[s] = ag_n_ops(w);
+            else {
+                pos_out[s] = (int32_t)w.x0; nm_out[s] = w.nm; op_off_out[s] = (uint64_t)lo;
+                if (s + 1 == n_slots) op_off_out[n_slots] = (uint64_t)hi;
+                if (kd != kAgNoJob) atomicAdd(&s_ctr[kAgJobs], 1ull);
+                if (kd == kAgTracedJob) atomicAdd(&s_ctr[kAgTraced], 1ull);
+                if (kd != kAgNoJob && !w.started) atomicAdd(&s_ctr[kAgUnalignable], 1ull);
+                if (w.nm) atomicAdd(&s_ctr[kAgSumNm], (unsigned long long)w.nm);
+            }
+        }
+    }
+    if (WRITE) {
+        __syncthreads();
+        if (threadIdx.x >= kAgJobs && threadIdx.x < kAgCounters && s_ctr[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], s_ctr[threadIdx.x]);
+    }
+}
+
+}  // namespace sfgpu
+
+using namespace sfgpu;
+
+struct AlignGSyncOnExit { hipStream_t s; ~AlignGSyncOnExit() { (void)hipStreamSynchronize(s); } };
+struct AgSlice { uint64_t a, b, steps; };
+
+extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                       uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_align_gopts* opts,
+                                       int32_t* d_pos, uint32_t* d_nm, uint64_t* d_op_off, uint32_t* d_ops, uint64_t cap_ops, uint64_t* n_ops,
+                                       sfgpu_align_gstats* stats, sfgpu_stream stream) {
+    SF_REQUIRE(x && opts && n_ops && stats && d_op_off, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null pointer");
+    SF_REQUIRE(opts->max_indel >= 1u && opts->max_indel <= kVgMaxIndel, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: max_indel is 1 .. 15");
+    SF_REQUIRE(n_reads == 0 || (d_seq1 && d_off1 && d_hit_offsets && (!d_seq2 || d_off2)), SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null reads");
+    SF_REQUIRE(cap_ops == 0 || d_ops, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null operations");
+    hipStream_t st = as_stream(stream);
+    uint32_t n_rec32 = 0;
+    if (n_reads) {
+        SF_HIP(hipMemcpyAsync(&n_rec32, d_hit_offsets + n_reads, 4, hipMemcpyDeviceToHost, st));
+        SF_HIP(hipStreamSynchronize(st));
+    }
+    const uint64_t n_rec = n_rec32, n_slots = 2 * n_rec;
+    if (n_rec == 0) {
+        SF_HIP(hipMemsetAsync(d_op_off, 0, 8, st)); SF_HIP(hipStreamSynchronize(st));
+        *n_ops = 0; *stats = sfgpu_align_gstats{};
+        return SFGPU_OK;
+    }
+    SF_REQUIRE(d_hits && d_pos && d_nm, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null records");
+    const uint32_t k = opts->max_indel, W = vg_width(k), per_block = kAgBlock / W;
+    int rc;
+    // (steps and cnt: n_slots + 1 entries, exclusive_scan_u32 reads one past the last)
+    DevBuf<uint32_t> rec_read, steps, cnt; DevBuf<uint8_t> kind, lane_end; DevBuf<uint64_t> prefix, woff, cells, cut; DevBuf<unsigned long long> ctr;
+    AlignGSyncOnExit sync_first{st};         // (declared after the buffers: an early return waits for the kernels before scratch goes back)
+    if ((rc = rec_read.reserve(n_rec, st, false)) || (rc = steps.reserve(n_slots + 1, st, false)) || (rc = cnt.reserve(n_slots + 1, st, false)) ||
+        (rc = kind.reserve(n_slots, st, false)) || (rc = lane_end.reserve(n_slots, st, false)) || (rc = prefix.reserve(n_slots + 1, st, false)) ||
+        (rc = woff.reserve(n_slots + 1, st, false)) || (rc = cut.reserve(2, st, false)) || (rc = ctr.reserve(kAgCounters, st, false))) return rc;
+    unsigned long long h_ctr[kAgCounters] = {~0ull, ~0ull, 0, 0, 0, 0};
+    SF_HIP(hipMemcpyAsync(ctr.p, h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, st));
+    SF_HIP(hipMemsetAsync(rec_read.p, 0xFF, n_rec * 4, st));
+    hipLaunchKernelGGL(k_aligng_reads, dim3((unsigned)(((uint64_t)n_reads + kAgBlock - 1) / kAgBlock)), dim3(kAgBlock), 0, st, (uint64_t)n_reads, d_hit_offsets, n_rec, rec_read.p);
+    SF_CHECK_LAUNCH();
+    auto size_kernel = W == 16u ? k_aligng_size<16> : k_aligng_size<32>;
+    hipLaunchKernelGGL(size_kernel, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, x->M, d_seq1, d_off1,
+                       d_seq2, d_off2, d_hits, rec_read.p, n_slots, steps.p, kind.p, ctr.p);
+    SF_CHECK_LAUNCH();
+    if ((rc = exclusive_scan_u32(steps.p, prefix.p, n_slots, st, false))) return rc;
+    uint64_t total_steps = 0;
+    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&total_steps, prefix.p + n_slots, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    if (h_ctr[kAgBadTid] != ~0ull) {
+        set_error("sfgpu_hits_align_gapped: record %llu names transcript >= %llu", h_ctr[kAgBadTid], (unsigned long long)x->M);
+        return SFGPU_ERR_RANGE;
+    }
+    if (h_ctr[kAgBadMate] != ~0ull) {
+        set_error("sfgpu_hits_align_gapped: record %llu names mate 2 of a single-end batch", h_ctr[kAgBadMate]);
+        return SFGPU_ERR_INVALID;
+    }
+    // the slices
+    const uint64_t cap_bytes = opts->scratch_cap_bytes ? opts->scratch_cap_bytes : kAgDefaultCap;
+    const uint64_t cap_steps = cap_bytes / (8ull * W) ? cap_bytes / (8ull * W) : 1ull;
+    std::vector<AgSlice> slices;
+    uint64_t peak_steps = 0;
+    if (total_steps <= cap_steps) { slices.push_back(AgSlice{0, n_slots, total_steps}); peak_steps = total_steps; }
+    else {
+        for (uint64_t a = 0; a < n_slots;) {
+            uint64_t h_cut[2] = {0, 0};
+            hipLaunchKernelGGL(k_aligng_cut, dim3(1), dim3(1), 0, st, prefix.p, n_slots, a, cap_steps, cut.p);
+            SF_CHECK_LAUNCH();
+            SF_HIP(hipMemcpyAsync(h_cut, cut.p, 16, hipMemcpyDeviceToHost, st));
+            SF_HIP(hipStreamSynchronize(st));
+            SF_REQUIRE(h_cut[0] > a && h_cut[0] <= n_slots, SFGPU_ERR_STATE, "sfgpu_hits_align_gapped: a slice without slots");
+            slices.push_back(AgSlice{a, h_cut[0], h_cut[1]});
+            peak_steps = h_cut[1] > peak_steps ? h_cut[1] : peak_steps;
+            a = h_cut[0];
+        }
+    }
+    if ((rc = cells.reserve(peak_steps * W, st, false))) return rc;
+    auto count_kernel = W == 16u ? k_aligng_trace<16, false> : k_aligng_trace<32, false>;
+    auto write_kernel = W == 16u ? k_aligng_trace<16, true> : k_aligng_trace<32, true>;
+    for (const AgSlice& sl : slices) {
+        hipLaunchKernelGGL(count_kernel, dim3((unsigned)((sl.b - sl.a + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, d_seq1, d_off1,
+                           d_seq2, d_off2, d_hits, rec_read.p, kind.p, prefix.p, n_slots, sl.a, sl.b, k, 1, cells.p, lane_end.p, cnt.p, (const uint64_t*)nullptr,
+                           (int32_t*)nullptr, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, ctr.p);
+        SF_CHECK_LAUNCH();
+    }
+    if ((rc = exclusive_scan_u32(cnt.p, woff.p, n_slots, st, false))) return rc;
+    uint64_t total = 0;
+    SF_HIP(hipMemcpyAsync(&total, woff.p + n_slots, 8, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    *n_ops = total;
+    if (total > cap_ops) {
+        set_error("sfgpu_hits_align_gapped: %llu operations, room for %llu", (unsigned long long)total, (unsigned long long)cap_ops);
+        return SFGPU_ERR_RANGE;
+    }
+    for (const AgSlice& sl : slices) {
+        hipLaunchKernelGGL(write_kernel, dim3((unsigned)((sl.b - sl.a + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, d_seq1, d_off1,
+                           d_seq2, d_off2, d_hits, rec_read.p, kind.p, prefix.p, n_slots, sl.a, sl.b, k, (int)(slices.size() > 1), cells.p, lane_end.p, (uint32_t*)nullptr,
+                           (const uint64_t*)woff.p, d_pos, d_nm, d_op_off, d_ops, ctr.p);
+        SF_CHECK_LAUNCH();
+    }
+    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipStreamSynchronize(st));
+    stats->jobs = h_ctr[kAgJobs]; stats->jobs_traced = h_ctr[kAgTraced]; stats->unalignable = h_ctr[kAgUnalignable]; stats->sum_nm = h_ctr[kAgSumNm];
+    stats->words = total; stats->scratch_bytes = peak_steps * W * 8ull;
+    return SFGPU_OK;
+}

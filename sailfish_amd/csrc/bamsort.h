@@ -22,6 +22,7 @@ int samw_collect_bam(BamRecordStore* store, const sfgpu_hit* d_hits, const uint3
                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                     const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented);
+                     const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos = nullptr,
+                     const uint64_t* d_aln_op_off = nullptr, const uint32_t* d_aln_ops = nullptr);
 
 }  // namespace sfgpu

@@ -20,6 +20,8 @@
 //   4  bases given whose number differs from the line's read length (clip + match; an unmapped line has none to differ from), or
 //      more than 65 535 bases
 //   5  the alignment ends beyond 2^29: pos + match > 2^29
+// With an alignment given (samwfmt.h: samw_line) the CIGAR words are the slot's; bin and rule 5 take the reference span (M + D) for
+// `match`, rule 4 compares the bases with the read bases the CIGAR names (S + M + I) and also covers more than 65 535 operations.
 #pragma once
 #include "samwfmt.h"
 
@@ -64,7 +66,7 @@ SAMW_HD uint8_t bamw_packed_byte_rev(const uint8_t* seq, uint64_t n, uint64_t i)
     return (uint8_t)(hi << 4 | lo);
 }
 
-SAMW_HD uint32_t bamw_cigar_ops(const SamwLine& l) { return l.mapped ? (l.clip ? 2u : 1u) : 0u; }
+SAMW_HD uint32_t bamw_cigar_ops(const SamwLine& l) { return !l.mapped ? 0u : l.ops ? l.n_ops : (l.clip ? 2u : 1u); }
 // l_seq of the line of read r
 SAMW_HD uint64_t bamw_l_seq(const SamwArgs& a, const SamwLine& l, uint64_t r, const uint8_t** seq) {
     uint64_t n;
@@ -77,20 +79,25 @@ SAMW_HD int bamw_check_line(const SamwArgs& a, const SamwLine& l, uint64_t r) {
     if (qn < 1 || qn > 254) return BAMW_BAD_QNAME;
     const uint8_t* seq;
     uint64_t n;
-    if (samw_seq(a, l, r, &seq, &n) && (n > kBamwMaxSeq || (l.mapped && n != (uint64_t)l.clip + l.match))) return BAMW_BAD_SEQ;
-    if (l.mapped && (uint64_t)(l.pos - 1u) + l.match > (1ull << 29)) return BAMW_BAD_END;
+    if (samw_seq(a, l, r, &seq, &n) && (n > kBamwMaxSeq || (l.mapped && n != (uint64_t)l.query))) return BAMW_BAD_SEQ;
+    if (l.mapped && l.n_ops > 65535u) return BAMW_BAD_SEQ;
+    if (l.mapped && (uint64_t)(l.pos - 1u) + l.ref_span > (1ull << 29)) return BAMW_BAD_END;
     return 0;
 }
-// 0, or the first rule the unit breaks, samwfmt.h's rules first (h == nullptr: the read has no record)
-SAMW_HD int bamw_check(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
-    if (h) if (const int kind = samw_check(*h, a.n_refs)) return kind;
+// 0, or the first rule the unit breaks, samwfmt.h's rules first (h == nullptr: the read has no record; hidx: h's index in a.hits)
+SAMW_HD int bamw_check(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
+    if (h) if (const int kind = samw_check_a(a, *h, hidx)) return kind;
     const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
     int worst = 0;
     for (uint32_t w = 0; w < n; ++w) {
-        const int kind = bamw_check_line(a, h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r);
+        const int kind = bamw_check_line(a, h ? samw_line(a, *h, rank, w, hidx) : samw_empty_line(a.paired != 0, w), r);
         if (kind && (!worst || kind < worst)) worst = kind;
     }
     return worst;
+}
+// the same where h is nullptr or points INTO a.hits (never at a copy)
+SAMW_HD int bamw_check(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+    return bamw_check(a, r, h, rank, h ? (uint64_t)(h - a.hits) : 0ull);
 }
 
 SAMW_HD uint64_t bamw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r) {
@@ -98,11 +105,14 @@ SAMW_HD uint64_t bamw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r)
     const uint64_t n = bamw_l_seq(a, l, r, &seq);
     return kBamwFixed + samw_qname_len(a, r) + 1u + 4u * bamw_cigar_ops(l) + (n + 1) / 2 + n;
 }
-SAMW_HD uint64_t bamw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+SAMW_HD uint64_t bamw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
     const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
     uint64_t len = 0;
-    for (uint32_t w = 0; w < n; ++w) len += bamw_line_len(a, h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r);
+    for (uint32_t w = 0; w < n; ++w) len += bamw_line_len(a, h ? samw_line(a, *h, rank, w, hidx) : samw_empty_line(a.paired != 0, w), r);
     return len;
+}
+SAMW_HD uint64_t bamw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {      // (h nullptr or INTO a.hits)
+    return bamw_unit_len(a, r, h, rank, h ? (uint64_t)(h - a.hits) : 0ull);
 }
 
 // the kBamwFixed bytes in front of QNAME: put(i, byte); line_len is bamw_line_len, qname_len without the NUL
@@ -116,7 +126,7 @@ SAMW_HD void bamw_put_fixed(const SamwLine& l, uint32_t tid, uint64_t line_len, 
     le(pos0, 4);
     le((uint32_t)qname_len + 1u, 1);
     le(255u, 1);
-    le(l.mapped ? bamw_reg2bin(pos0, pos0 + (l.match ? l.match : 1u)) : kBamwUnmappedBin, 2);
+    le(l.mapped ? bamw_reg2bin(pos0, pos0 + (l.ref_span ? l.ref_span : 1u)) : kBamwUnmappedBin, 2);
     le(bamw_cigar_ops(l), 2);
     le(l.flag, 2);
     le((uint32_t)l_seq, 4);
@@ -130,6 +140,7 @@ SAMW_HD void bamw_put_cigar(const SamwLine& l, Put put) {
     int p = 0;
     auto le = [&](uint32_t v) { for (int i = 0; i < 4; ++i) put(p++, (uint8_t)(v >> (8 * i))); };
     if (!l.mapped) return;
+    if (l.ops) { for (uint32_t i = 0; i < l.n_ops; ++i) le(l.ops[i]); return; }
     if (l.clip) le(l.clip << 4 | 4u);
     le(l.match << 4);
 }
@@ -173,7 +184,7 @@ inline int bamw_serial(const SamwArgs& a, uint8_t* out, SamwSerial* res) {
     auto unit = [&](uint64_t r, const sfgpu_hit* h, uint64_t rank) {
         const uint64_t before = at;
         const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
-        for (uint32_t w = 0; w < n; ++w) line(h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
+        for (uint32_t w = 0; w < n; ++w) line(h ? samw_line(a, *h, rank, w, (uint64_t)(h - a.hits)) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
         res->n_units++;
         if (at - before > res->max_unit_bytes) res->max_unit_bytes = at - before;
     };

@@ -134,9 +134,9 @@ k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before
         const uint64_t r = lo, rank = h - a.hit_off[r], u = h + e_before[r];
         const sfgpu_hit rec = a.hits[h];
         uint64_t len = 0;
-        if (const int kind = BAM ? bamw_check(a, r, &rec, rank) : samw_check(rec, a.n_refs))
+        if (const int kind = BAM ? bamw_check(a, r, &rec, rank, h) : samw_check_a(a, rec, h))
             atomicMin(&misc[misc_of_kind(kind)], (unsigned long long)(r << 32 | rank));
-        else len = BAM ? bamw_unit_len(a, r, &rec, rank) : samw_unit_len(a, r, &rec, rank);
+        else len = BAM ? bamw_unit_len(a, r, &rec, rank, h) : samw_unit_len(a, r, &rec, rank, h);
         if (len > 0xffffffffull) { atomicOr(&misc[0], kTooLong); len = 0; }
         unit_len[u] = (uint32_t)len;
         unit_read[u] = (uint32_t)r;
@@ -211,7 +211,8 @@ k_format(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __re
         const uint32_t k = atomicAdd(&n_jobs, 1u);
         if (k < kJobCap) jobs[k] = CopyJob{mode == kFwd ? src + (lo - s) : src + (n - 1 - (lo - s)), (uint32_t)(lo - base), (uint32_t)(hi - lo), mode};
     };
-    // two line slots per unit: a unit's second line is absent unless it is a pair record or a record-less paired read
+    // two line slots per unit: a unit's second line is absent unless it is a pair record or a record-less paired read.  (With an
+    // alignment given -- the _a entries -- a line's CIGAR is its slot's operations, put one after the other through put_at.)
     for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
         const uint64_t u = u_lo + (slot >> 1);
         const uint32_t which = (uint32_t)(slot & 1);
@@ -219,17 +220,17 @@ k_format(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __re
         const uint32_t h0 = a.hit_off[r];
         const bool empty = h0 == a.hit_off[r + 1];
         sfgpu_hit rec = {};
-        uint64_t rank = 0;
+        uint64_t rank = 0, h = 0;
         if (!empty) {
-            const uint64_t h = u - e_before[r];
+            h = u - e_before[r];
             rec = a.hits[h];
             rank = h - h0;
         }
         if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
         const uint32_t tid = empty ? 0u : rec.tid;
         uint64_t s = unit_start[u];
-        if (which) s += samw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_record_line(rec, rank, 0), r, tid);
-        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_record_line(rec, rank, which);
+        if (which) s += samw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_line(a, rec, rank, 0, h), r, tid);
+        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_line(a, rec, rank, which, h);
         if (s >= end || s + samw_line_len(a, l, r, tid) <= base) continue;
         // QNAME
         if (a.qname_off) {
@@ -357,17 +358,17 @@ k_format_bam(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* 
         const uint32_t h0 = a.hit_off[r];
         const bool empty = h0 == a.hit_off[r + 1];
         sfgpu_hit rec = {};
-        uint64_t rank = 0;
+        uint64_t rank = 0, h = 0;
         if (!empty) {
-            const uint64_t h = u - e_before[r];
+            h = u - e_before[r];
             rec = a.hits[h];
             rank = h - h0;
         }
         if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
         const uint32_t tid = empty ? 0u : rec.tid;
         uint64_t s = unit_start[u];
-        if (which) s += bamw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_record_line(rec, rank, 0), r);
-        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_record_line(rec, rank, which);
+        if (which) s += bamw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_line(a, rec, rank, 0, h), r);
+        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_line(a, rec, rank, which, h);
         const uint64_t len = bamw_line_len(a, l, r), qn = samw_qname_len(a, r);
         if (s >= end || s + len <= base) continue;
         const uint8_t* seq;
@@ -429,7 +430,8 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
               const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames, const uint64_t* d_qname_off, const uint8_t* d_seq1,
               const int64_t* d_seq1_off, const uint8_t* d_seq2, const int64_t* d_seq2_off, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
               uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user, sfgpu_bgzw* z, int format,
-              sfgpu_samwrite_result* out, sfgpu_stream stream, BamRecordStore* store) {
+              sfgpu_samwrite_result* out, sfgpu_stream stream, BamRecordStore* store, const int32_t* d_aln_pos = nullptr,
+              const uint64_t* d_aln_op_off = nullptr, const uint32_t* d_aln_ops = nullptr) {
     const bool bam = format == SFGPU_SAMW_BAM;
     auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
     if (!out) return fail(SFGPU_ERR_INVALID, "null result");
@@ -443,9 +445,10 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     if (!((!d_seq1 || d_seq1_off) && (!d_seq2 || d_seq2_off))) return fail(SFGPU_ERR_INVALID, "bases without their offsets");
     if (!((!d_qual1 || d_seq1_off) && (!d_qual2 || d_seq2_off))) return fail(SFGPU_ERR_INVALID, "qualities of a mate whose bases are not given");
     if (!(n_reads < 0xffffffffu)) return fail(SFGPU_ERR_RANGE, "n_reads must be below 2^32 - 1");
+    if (!((d_aln_pos != nullptr) == (d_aln_op_off != nullptr) && (!d_aln_ops || d_aln_pos))) return fail(SFGPU_ERR_INVALID, "an alignment is positions, offsets and operations together");
     SamwArgs a = {d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
                   d_seq1, d_seq1_off, paired ? d_seq2 : nullptr, paired ? d_seq2_off : nullptr, read_index_base,
-                  d_qual1, paired ? d_qual2 : nullptr, oriented != 0};
+                  d_qual1, paired ? d_qual2 : nullptr, oriented != 0, d_aln_pos, d_aln_op_off, d_aln_ops};
 
     Scratch S;
     CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
@@ -508,6 +511,7 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     if (h_misc[0] & kNullBytes) return fail(SFGPU_ERR_INVALID, "offsets name bytes of a null array");
     const uint64_t n_hits = h_counts[0], n_units = n_hits + h_counts[1];
     if (n_hits && !d_hits) return fail(SFGPU_ERR_INVALID, "null hits");
+    if (n_hits && d_aln_pos && !d_aln_ops) return fail(SFGPU_ERR_INVALID, "an alignment without operations");
 
     // ---- sizing and validation: unit lengths, unit starts, the longest unit, the lowest record that cannot be written
     if (int rc = S.unit_len.reserve(n_units + 1, st, false)) return rc;
@@ -596,6 +600,30 @@ extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d
                      SFGPU_SAMW_TEXT, out, stream, nullptr);
 }
 
+extern "C" int sfgpu_sam_write_text_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
+                                      const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
+    return sam_write("sfgpu_sam_write_text", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, sink, user, nullptr,
+                     SFGPU_SAMW_TEXT, out, stream, nullptr, d_aln_pos, d_aln_op_off, d_aln_ops);
+}
+
+extern "C" int sfgpu_sam_write_bgzf_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
+                                      int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
+    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
+    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
+    return sam_write("sfgpu_sam_write_bgzf", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
+                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, nullptr, nullptr, z, format,
+                     out, stream, nullptr, d_aln_pos, d_aln_op_off, d_aln_ops);
+}
+
 extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
@@ -632,8 +660,8 @@ int sfgpu::samw_collect_bam(BamRecordStore* store, const sfgpu_hit* d_hits, cons
                             const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                             const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                             const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                            const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
+                            const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
     return sam_write("sfgpu_bamsort_collect", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
                      d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, 0, nullptr, nullptr, nullptr, SFGPU_SAMW_BAM,
-                     out, stream, store);
+                     out, stream, store, d_aln_pos, d_aln_op_off, d_aln_ops);
 }

@@ -29,6 +29,11 @@
 //          length).  With `oriented` != 0 a line whose FLAG has 0x10 stores them on the reference's strand, as the SAM
 //          specification has it: SEQ reverse-complemented (samw_comp, byte by byte), QUAL reversed.  Lines without 0x10 -- every
 //          line of a read without records among them -- are as given.
+//   Alignments: with aln_pos / aln_op_off / aln_ops given (sfgpu_hits_align_gapped's outputs for the same records: two slots per
+//          record, slot 2 h + which is line `which` of record h) a mapped line takes POS = aln_pos[slot] + 1 and its CIGAR from the
+//          slot's words len << 4 | op (MIDNSHP=X), PNEXT is the other line's POS written this way; FLAG and TLEN stay.  The position
+//          rule is then the slot's: a line whose slot has no operation has no base on the transcript (SAMW_BAD_POS), and the record's
+//          own pos is not consulted.  Without them every byte is what it is above.
 #pragma once
 #include <cstdint>
 
@@ -45,7 +50,7 @@ namespace sfgpu {
 
 constexpr uint32_t kSamwTail = 2;                 // \t and \n around QUAL
 // (the head \t FLAG \t is at most 5 bytes: the largest FLAG is 0x1b3 = 435; the middle \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
-// at most 54: 65535S65535M, -4294967295)
+// at most 54 without an alignment: 65535S65535M, -4294967295; with one the CIGAR is as long as its operations make it)
 enum { SAMW_OK = 0, SAMW_BAD_POS = 1, SAMW_BAD_TID = 2, SAMW_BAD_QUAL = 6 };     // (3 .. 5 are bamwfmt.h's)
 
 // the complement of a base: A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, in either case (kept); S, W, N and every other byte as it is
@@ -70,6 +75,9 @@ struct SamwLine {
     int64_t tlen;
     uint32_t flag, pos, pnext;
     uint32_t clip, match;        // CIGAR <clip>S<match>M (clip = 0: <match>M); unmapped: '*'
+    const uint32_t* ops;         // an alignment is given: the CIGAR is these n_ops words (clip and match are then 0), else nullptr
+    uint32_t n_ops;
+    uint32_t ref_span, query;    // the transcript bases the CIGAR covers (M + D) and the read bases it names (S + M + I)
     uint8_t mapped;              // RNAME is the name of the record's tid; else '*'
     uint8_t rnext;               // '=' or '*'
     uint8_t mate2;               // SEQ is mate 2's
@@ -100,7 +108,7 @@ SAMW_HD SamwLine samw_record_line(const sfgpu_hit& h, uint64_t rank, uint32_t wh
     const uint32_t sec = rank ? 0x100u : 0u, st = h.mate_status;
     uint32_t p1, c1, m1;
     samw_aligned(h.pos, h.read_len, &p1, &c1, &m1);
-    l.mapped = 1;
+    l.mapped = 1; l.ops = nullptr; l.n_ops = 0;
     if (st == 3) {
         uint32_t p2, c2, m2;
         samw_aligned(h.mate_pos, h.mate_len, &p2, &c2, &m2);
@@ -110,13 +118,16 @@ SAMW_HD SamwLine samw_record_line(const sfgpu_hit& h, uint64_t rank, uint32_t wh
         if (which == 0) {
             l.flag = 0x1u | 0x2u | 0x40u | sec | (r1 ? 0x10u : 0u) | (r2 ? 0x20u : 0u);
             l.pos = p1; l.clip = c1; l.match = m1; l.pnext = p2; l.tlen = tlen; l.mate2 = 0;
+            l.ref_span = m1; l.query = c1 + m1;
         } else {
             l.flag = 0x1u | 0x2u | 0x80u | sec | (r2 ? 0x10u : 0u) | (r1 ? 0x20u : 0u);
             l.pos = p2; l.clip = c2; l.match = m2; l.pnext = p1; l.tlen = -tlen; l.mate2 = 1;
+            l.ref_span = m2; l.query = c2 + m2;
         }
         return l;
     }
     l.pos = p1; l.clip = c1; l.match = m1; l.rnext = '*'; l.pnext = 0; l.tlen = 0;
+    l.ref_span = m1; l.query = c1 + m1;
     l.flag = sec | (h.fwd ? 0u : 0x10u);
     l.mate2 = 0;
     if (st) {
@@ -131,6 +142,7 @@ SAMW_HD SamwLine samw_empty_line(bool paired, uint32_t which) {
     SamwLine l;
     l.flag = paired ? (which ? 141u : 77u) : 4u;
     l.pos = 0; l.clip = 0; l.match = 0; l.pnext = 0; l.tlen = 0;
+    l.ops = nullptr; l.n_ops = 0; l.ref_span = 0; l.query = 0;
     l.mapped = 0; l.rnext = '*'; l.mate2 = (uint8_t)(paired && which);
     return l;
 }
@@ -156,6 +168,11 @@ SAMW_HD void samw_put_head(const SamwLine& l, Put put) {
 
 SAMW_HD uint32_t samw_cigar_len(const SamwLine& l) {
     if (!l.mapped) return 1;
+    if (l.ops) {
+        uint32_t n = 0;
+        for (uint32_t i = 0; i < l.n_ops; ++i) n += (uint32_t)dec_len_u32(l.ops[i] >> 4) + 1u;
+        return n;
+    }
     return (l.clip ? (uint32_t)dec_len_u32(l.clip) + 1u : 0u) + (uint32_t)dec_len_u32(l.match) + 1u;
 }
 
@@ -176,6 +193,7 @@ SAMW_HD void samw_put_mid(const SamwLine& l, Put put) {
     put(p++, '\t'); num(l.pos);
     put(p++, '\t'); put(p++, '2'); put(p++, '5'); put(p++, '5'); put(p++, '\t');
     if (!l.mapped) put(p++, '*');
+    else if (l.ops) for (uint32_t i = 0; i < l.n_ops; ++i) { num(l.ops[i] >> 4); put(p++, "MIDNSHP=X???????"[l.ops[i] & 15u]); }
     else {
         if (l.clip) { num(l.clip); put(p++, 'S'); }
         num(l.match); put(p++, 'M');
@@ -209,7 +227,37 @@ struct SamwArgs {
     const uint8_t* qual1 = nullptr;
     const uint8_t* qual2 = nullptr;
     int oriented = 0;
+    const int32_t* aln_pos = nullptr;        // [2 * records] sfgpu_hits_align_gapped's d_pos, or nullptr: no alignment is given
+    const uint64_t* aln_op_off = nullptr;    // [2 * records + 1]
+    const uint32_t* aln_ops = nullptr;
 };
+
+// The lines of a record WITH the batch's alignment, where one is given.  `hidx` is the record's index in a.hits: its slots are
+// 2 * hidx and 2 * hidx + 1 (h itself may be a copy of the record, as in the kernels).
+SAMW_HD SamwLine samw_line(const SamwArgs& a, const sfgpu_hit& h, uint64_t rank, uint32_t which, uint64_t hidx) {
+    SamwLine l = samw_record_line(h, rank, which);
+    if (!a.aln_pos) return l;
+    const uint64_t slot = 2 * hidx + which;
+    l.pos = (uint32_t)a.aln_pos[slot] + 1u;
+    if (h.mate_status == 3) l.pnext = (uint32_t)a.aln_pos[slot ^ 1ull] + 1u;
+    l.clip = 0; l.match = 0; l.ref_span = 0; l.query = 0;
+    l.ops = a.aln_ops + a.aln_op_off[slot];
+    l.n_ops = (uint32_t)(a.aln_op_off[slot + 1] - a.aln_op_off[slot]);
+    for (uint32_t i = 0; i < l.n_ops; ++i) {
+        const uint32_t n = l.ops[i] >> 4, op = l.ops[i] & 15u;
+        if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) l.ref_span += n;      // M D N = X
+        if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) l.query += n;         // M I S = X
+    }
+    return l;
+}
+// samw_check with the position rule taken from the alignment where one is given
+SAMW_HD int samw_check_a(const SamwArgs& a, const sfgpu_hit& h, uint64_t hidx) {
+    if (!a.aln_pos) return samw_check(h, a.n_refs);
+    const uint64_t slot = 2 * hidx;
+    for (uint32_t w = 0; w < samw_record_lines(h); ++w) if (a.aln_op_off[slot + w + 1] == a.aln_op_off[slot + w]) return SAMW_BAD_POS;
+    if (h.tid >= a.n_refs) return SAMW_BAD_TID;
+    return SAMW_OK;
+}
 
 SAMW_HD uint64_t samw_qname_len(const SamwArgs& a, uint64_t r) {
     return a.qname_off ? a.qname_off[r + 1] - a.qname_off[r] : (uint64_t)samw_default_qname_len(a.read_index_base + r);
@@ -246,12 +294,16 @@ SAMW_HD uint64_t samw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r,
     (void)samw_qual(a, l, r, &p, &ql);
     return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail;
 }
-// the bytes of unit (read r, record h of rank `rank`; h == nullptr: the read has no record)
-SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+// the bytes of unit (read r, record h of rank `rank` and index hidx in a.hits; h == nullptr: the read has no record)
+SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
     const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
     uint64_t len = 0;
-    for (uint32_t w = 0; w < n; ++w) len += samw_line_len(a, h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
+    for (uint32_t w = 0; w < n; ++w) len += samw_line_len(a, h ? samw_line(a, *h, rank, w, hidx) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
     return len;
+}
+// the same where h is nullptr or points INTO a.hits (never at a copy): the index is the pointer's
+SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank) {
+    return samw_unit_len(a, r, h, rank, h ? (uint64_t)(h - a.hits) : 0ull);
 }
 
 #if !defined(__HIPCC__)
@@ -293,7 +345,7 @@ inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
     *res = SamwSerial();
     for (uint64_t r = 0; r < a.n_reads && !res->error_kind; ++r)
         for (uint64_t h = a.hit_off[r]; h < a.hit_off[r + 1]; ++h)
-            if (int kind = samw_check(a.hits[h], a.n_refs)) {
+            if (int kind = samw_check_a(a, a.hits[h], h)) {
                 res->error_read = r; res->error_record = h - a.hit_off[r]; res->error_kind = kind;
                 break;
             }
@@ -325,7 +377,7 @@ inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
     auto unit = [&](uint64_t r, const sfgpu_hit* h, uint64_t rank) {
         const uint64_t before = at;
         const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
-        for (uint32_t w = 0; w < n; ++w) line(h ? samw_record_line(*h, rank, w) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
+        for (uint32_t w = 0; w < n; ++w) line(h ? samw_line(a, *h, rank, w, (uint64_t)(h - a.hits)) : samw_empty_line(a.paired != 0, w), r, h ? h->tid : 0);
         res->n_units++;
         if (at - before > res->max_unit_bytes) res->max_unit_bytes = at - before;
     };

@@ -368,6 +368,166 @@ def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, 
     return out_hits[: n_out.value * 24], out_off, scores[: n_out.value * 8], st.as_dict()
 
 
+ALIGNG_STATS = ("jobs", "jobs_traced", "unalignable", "sum_nm", "words", "scratch_bytes")
+CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_S = 0, 1, 2, 4                                       # BAM's operation codes
+_DIAG, _INS, _DEL = 1, 2, 4
+
+
+def _align_job_host(a, t, pos, k):
+    """One job by the rule of csrc/aligngfmt.h: a = the oriented base codes, t = the transcript's codes -> (x0, ops, nm, clipped,
+    trimmed D columns, edits, ungapped count).  The whole matrix D[i][d] (gapped_edits_host's rows, kept), then CANDIDATES, END, WALK, TRIM, RESULT."""
+    n, tl = len(a), len(t)
+    if n == 0:
+        return 0, [], 0, 0, 0, 0, 0
+    d = np.arange(-k, k + 1, dtype=np.int64)
+    ramp = np.arange(2 * k + 1, dtype=np.int64)
+    x = pos + np.arange(n, dtype=np.int64)[:, None] + d[None, :]
+    on = (x >= 0) & (x < tl)
+    b = np.full(x.shape, 5, np.uint8)
+    b[on] = t[x[on]]
+    sub = (~((a[:, None] <= 3) & (b == a[:, None]))).astype(np.int64)
+    D = np.zeros((n + 1, 2 * k + 1), np.int64)                                        # row i is D[i + 1]
+    for i in range(n):
+        V = D[i] + sub[i]
+        np.minimum(V[:-1], D[i, 1:] + 1, out=V[:-1])
+        V -= ramp
+        np.minimum.accumulate(V, out=V)
+        V += ramp
+        D[i + 1] = V
+    ungapped = int(sub[:, k].sum())
+    D, sub = D.tolist(), sub.tolist()
+    edits = min(D[n])
+    l = next(c for m in range(k + 1) for c in (k - m, k + m) if D[n][c] == edits)      # END: least |d|, the negative one on a tie
+    cols, i, prev = [], n - 1, 0
+    while i >= 0:                                                                      # WALK
+        here = D[i + 1][l]
+        diag = D[i][l] + sub[i][l] == here
+        ins = l < 2 * k and D[i][l + 1] + 1 == here
+        dele = l > 0 and D[i + 1][l - 1] + 1 == here
+        op = _DEL if prev == _DEL and dele else _INS if prev == _INS and ins else _DIAG if diag else _INS if ins else _DEL
+        xx = pos + i + l - k
+        if op == _DIAG:
+            cols.append((CIGAR_M, xx, sub[i][l])); i -= 1
+        elif op == _INS:
+            cols.append((CIGAR_I, xx, 1)); i -= 1; l += 1
+        else:
+            cols.append((CIGAR_D, xx, 1)); l -= 1
+        prev = op
+    cols.reverse()
+    remains = [c[0] == CIGAR_M and 0 <= c[1] < tl for c in cols]                      # TRIM
+    if not any(remains):
+        return 0, [], 0, n, sum(c[0] == CIGAR_D for c in cols), edits, ungapped
+    lo, hi = remains.index(True), len(cols) - remains[::-1].index(True)
+    dropped = cols[:lo] + cols[hi:]
+    clip_l, clip_r = sum(c[0] != CIGAR_D for c in cols[:lo]), sum(c[0] != CIGAR_D for c in cols[hi:])
+    ops = [clip_l << 4 | CIGAR_S] if clip_l else []
+    last = None
+    for kind, _, _ in cols[lo:hi]:
+        if kind == last:
+            ops[-1] += 1 << 4
+        else:
+            ops.append(1 << 4 | kind)
+        last = kind
+    if clip_r:
+        ops.append(clip_r << 4 | CIGAR_S)
+    return cols[lo][1], ops, sum(c[2] for c in cols[lo:hi]), clip_l + clip_r, sum(c[0] == CIGAR_D for c in dropped), edits, ungapped
+
+
+def align_hits_host(transcripts, hits, offsets, reads1, reads2, max_indel):
+    """The statement of gapped alignment (csrc/aligngfmt.h restated; what sfgpu_hits_align_gapped is judged by), extending
+    gapped_edits_host: the same cells, then for each job the walk back through the band -- from the cell of the last row that holds
+    the edits with least |d| (the negative d on a tie); a gap continued while it is a candidate, else the first candidate of DIAG,
+    INS, DEL -- trimmed at either end to the first base aligned on the transcript (dropped bases are soft clip, dropped D columns
+    vanish; nothing left: unalignable, no operations).  Arguments as verify_hits_host; max_indel 1 .. 15.  Two slots per record: slot
+    2 h + j is job j of record h, a missing second job an empty slot.
+    -> (pos int32[2 n], nm uint32[2 n], op_off uint64[2 n + 1], ops uint32[] of len << 4 | op with M 0, I 1, D 2, S 4,
+        stats dict (ALIGNG_STATS; scratch_bytes as of one slice), detail int64[2 n, 3]: clipped, trimmed D columns, edits);
+    nm + clipped + trimmed D == edits in every slot.  ValueError naming the lowest record whose tid is not a transcript."""
+    k = _max_indel(max_indel)
+    if k < 1:
+        raise ValueError("max_indel lies outside 1 .. 15")
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    n_rec = int(off[-1]) if len(off) else 0
+    bad = np.nonzero(hits["tid"][:n_rec] >= len(transcripts))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(transcripts)}")
+    width = 16 if k <= 7 else 32
+    tcodes, done = {}, {}
+    pos, nm = np.zeros(2 * n_rec, np.int32), np.zeros(2 * n_rec, np.uint32)
+    op_off, ops = np.zeros(2 * n_rec + 1, np.uint64), []
+    detail = np.zeros((2 * n_rec, 3), np.int64)
+    stats = dict.fromkeys(ALIGNG_STATS, 0)
+    for r in range(len(off) - 1):
+        for i in range(off[r], off[r + 1]):
+            tid = int(hits[i]["tid"])
+            if tid not in tcodes:
+                tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
+            for j, (rd, fwd, p) in enumerate(_record_jobs(hits[i], r, reads1, reads2)):
+                key = (r, rd is not reads1[r], fwd, tid, p)
+                if key not in done:
+                    c = _BASE_CODE[np.frombuffer(rd, np.uint8)]
+                    a = c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
+                    done[key] = _align_job_host(a, tcodes[tid], p, k)
+                x0, job_ops, job_nm, clipped, trimmed, edits, ungapped = done[key]
+                s = 2 * i + j
+                pos[s], nm[s], detail[s] = x0, job_nm, (clipped, trimmed, edits)
+                ops.extend(job_ops)
+                op_off[s + 1] = len(job_ops)
+                stats["jobs"] += 1
+                stats["jobs_traced"] += int(ungapped > 0)
+                stats["unalignable"] += int(not job_ops)
+                stats["sum_nm"] += job_nm
+                if ungapped > 0:
+                    stats["scratch_bytes"] += 8 * width * ((len(rd) + 15) // 16)
+    op_off = np.cumsum(op_off, dtype=np.uint64)
+    stats["words"] = len(ops)
+    return pos, nm, op_off, np.array(ops, np.uint32), stats, detail
+
+
+def align_hits(index, hits, offsets, reads1, reads2=None, *, max_indel, scratch_cap_bytes=0):
+    """The gapped alignment of hit records on the device (sfgpu_hits_align_gapped; the rule is align_hits_host's): for the records
+    that verify_hits(max_indel=) kept, the path through the same band as a position and CIGAR words per job.  Arguments as
+    verify_hits; max_indel 1 .. 15 (anything else: ValueError).  scratch_cap_bytes bounds the device scratch of one slice of the batch
+    (0: 256 MiB); it never changes a result.  The operations' room is sized at two words a slot and the call repeated once with the
+    count the library reports where they do not fit.
+    -> (pos int32[2 n], nm int32[2 n] (the bits of uint32), op_off int64[2 n + 1], ops int32[] (the bits of uint32), stats dict):
+    device tensors, two slots per record (slot 2 h + j is job j of record h)."""
+    k = _max_indel(max_indel)
+    if k < 1:
+        raise ValueError("max_indel lies outside 1 .. 15")
+    dev = index.device
+    d_hits, d_off = _device_hits(hits, offsets, dev)
+    R = int(d_off.numel()) - 1
+    s1, o1 = _device_reads(reads1, dev)
+    s2 = o2 = None
+    if reads2 is not None:
+        s2, o2 = _device_reads(reads2, dev)
+    if int(o1.numel()) - 1 != R or (o2 is not None and int(o2.numel()) - 1 != R):
+        raise ValueError("the reads and the hit offsets do not cover the same number of reads")
+    n = d_hits.numel() // 24
+    pos = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+    nm = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+    op_off = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+    o = _lib.AlignGOpts(k, 0, int(scratch_cap_bytes))
+    st = _lib.AlignGStats()
+    need = C.c_uint64(0)
+    cap = max(4 * n, 1)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        for attempt in range(2):
+            ops = torch.empty(cap, dtype=torch.int32, device=dev)
+            rc = _lib.lib().sfgpu_hits_align_gapped(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                                    C.byref(o), _lib.ptr(pos), _lib.ptr(nm), _lib.ptr(op_off), _lib.ptr(ops), cap, C.byref(need), C.byref(st),
+                                                    _lib.current_stream_ptr())
+            if rc == _lib.ERR_RANGE and attempt == 0 and need.value > cap:
+                cap = int(need.value)
+                continue
+            _lib.check(rc)
+            break
+    return pos, nm, op_off, ops[: need.value], st.as_dict()
+
+
 def gc_prefix(seq, seq_off, ref_len):
     """Transcript::GCCount_ of every transcript (include/Transcript.hpp:183-196), laid out like `seq`: int32 device
     tensor of seq.numel() entries (4 bytes per base) -- what sample_bias reads for the fragment-GC samples."""

@@ -70,8 +70,16 @@ class QuasiIndex:
         """reads1 / reads2: lists of str / bytes, or (uint8 tensor, int64 offsets) pairs already packed.
         validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best, max_indel; {} = its defaults): the records are then
         verified against the transcripts' bases before they are returned, and `last_scores` / `last_verify_stats` hold the
-        survivors' scores and the pass's counters.
+        survivors' scores and the pass's counters.  With "align": True beside a max_indel of 1 .. 15 (else ValueError) the survivors
+        are then aligned with gaps (hits.align_hits): `last_alignments` holds (pos, nm, op_off, ops), two slots per surviving record,
+        as SamDeviceWriter.write(alignments=) takes them, and `last_align_stats` the pass's counters.
         -> (hits: uint8 device tensor [n_hits * 24] of HIT_DTYPE records, offsets: int32 device tensor [R + 1])"""
+        align = False
+        if validate is not None and "align" in validate:
+            validate = dict(validate)
+            align = bool(validate.pop("align"))
+            if align and not 1 <= int(validate.get("max_indel", 0)) <= 15:
+                raise ValueError('validate: "align" needs a max_indel of 1 .. 15')
         dev = self.device
         s1, o1 = reads1 if isinstance(reads1, tuple) else pack_sequences(reads1)
         s1, o1 = s1.to(dev).contiguous(), o1.to(dev).contiguous()
@@ -98,6 +106,11 @@ class QuasiIndex:
         if validate is not None:
             from .hits import verify_hits
             hits, off, self.last_scores, self.last_verify_stats = verify_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), **validate)
+            self.last_alignments = self.last_align_stats = None
+            if align:
+                from .hits import align_hits
+                *aln, self.last_align_stats = align_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), max_indel=validate["max_indel"])
+                self.last_alignments = tuple(aln)
         return hits, off
 
     def close(self):
@@ -139,6 +152,33 @@ def _add_verify_stats(total, idx):
             total[key] += v
 
 
+def _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate):
+    """mappings_gapped= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless there is a
+    mappings file, the validation pass and a band to align in.  -> (the `validate` dict with "align" set, the counters to accumulate)"""
+    if not mappings_gapped:
+        return validate, None
+    if write_mappings is None or not validate_mappings or not (validate or {}).get("max_indel"):
+        raise ValueError("mappings_gapped=True needs write_mappings, validate_mappings=True and a max_indel of 1 .. 15")
+    from .hits import ALIGNG_STATS
+    return dict(validate, align=True), dict.fromkeys(ALIGNG_STATS, 0)
+
+
+def _add_align_stats(total, idx):
+    if total is not None:
+        for key, v in idx.last_align_stats.items():
+            total[key] = max(total[key], v) if key == "scratch_bytes" else total[key] + v
+
+
+def _report_align_stats(exp, total, sopt):
+    """the alignment pass's counters: on the experiment as `align_stats` (None when it did not run) and as one log line"""
+    if exp is not None:
+        exp.align_stats = total
+    log = getattr(sopt, "jointLog", None) if sopt is not None else None
+    if total is not None and log is not None:
+        log(0, "gapped mappings: {} of {} mates traced through the band; {} mismatches, inserted and deleted bases in the written alignments; "
+               "{} mates unalignable".format(total["jobs_traced"], total["jobs"], total["sum_nm"], total["unalignable"]))
+
+
 def _report_verify_stats(exp, total, validate, sopt):
     """the accumulated counters: on the experiment as `verify_stats` (None when the pass did not run) and as one log line"""
     if exp is not None:
@@ -167,7 +207,7 @@ def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -184,11 +224,17 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     (with validate_mappings; outside 0 .. 15: ValueError) scores every mate with gaps -- its banded edit distance within max_indel
     diagonals of the recorded one -- so reads that carry an indel keep their true records; `verify_stats` then holds `sum_edits` for
     `sum_mism`, and `rescued`: the records kept only with gaps.  The mappings file receives the surviving records as before: its
-    CIGAR and POS still describe the recorded diagonal, not the gapped alignment.
+    CIGAR and POS still describe the recorded diagonal, not the gapped alignment -- unless mappings_gapped=True (it needs write_mappings,
+    validate_mappings=True and max_indel >= 1, else ValueError before anything is indexed): then every surviving mate is aligned
+    through the band on the device (hits.align_hits) and its line carries that alignment's POS and CIGAR (I, D and soft clips where the
+    mate hangs over an end), PNEXT following; with every mappings_format, mappings_oriented and mappings_sorted.  The estimates never
+    depend on it; the counters are left on the experiment as `align_stats` and go to sopt.jointLog as one line.  (A surviving mate
+    with no base on its transcript -- possible only at a min_identity near 0 -- fails the batch, as it does without the option.)
     -> (rc, experiment)"""
     from . import quant
     _check_mappings_sorted(mappings_sorted, mappings_format)
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
+    validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
     sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -205,8 +251,10 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
                 q2 = None if quals2 is None or r2 is None else pack_sequences(quals2[a:b])[0].to(idx.device)
             h, o = idx.map_reads(r1, r2, validate=validate)
             _add_verify_stats(vstats, idx)
+            _add_align_stats(astats, idx)
             if sam is not None:
-                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
+                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
+                          alignments=idx.last_alignments if astats is not None else None)
             yield h, o
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
@@ -219,6 +267,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
             sam.close()
     idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
+    _report_align_stats(exp, astats, sopt)
     return rc, exp
 
 
@@ -233,7 +282,7 @@ def _dollar_separated(bases, off):
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -243,12 +292,14 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     read where the files are out of step, naming the record counted from the start of the files and both names
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
-    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best and max_indel as in quantify_reads.
+    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel and mappings_gapped as in
+    quantify_reads.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     _check_mappings_sorted(mappings_sorted, mappings_format)
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
+    validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -277,10 +328,12 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                 done += n
                 h, o = idx.map_reads(r1, r2, validate=validate)
                 _add_verify_stats(vstats, idx)
+                _add_align_stats(astats, idx)
                 if sam is not None:
                     q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals
                     sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
-                              quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
+                              quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
+                              alignments=idx.last_alignments if astats is not None else None)
                 yield h, o
         finally:
             f1.close()
@@ -297,4 +350,5 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
             sam.close()
         idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
+    _report_align_stats(exp, astats, sopt)
     return rc, exp

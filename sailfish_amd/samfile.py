@@ -607,10 +607,27 @@ def _aligned(pos, length, what):
 _COMP = bytes.maketrans(b"ACGTURYKMBDHVacgturykmbdhv", b"TGCAAYRMKVHDBtgcaayrmkvhdb")
 
 
-def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False):
+def _alignment_arrays(alignments, n_records):
+    """(pos, op_off, ops) as numpy arrays from what hits.align_hits / hits.align_hits_host return -- (pos, nm, op_off, ops, ...),
+    device tensors or arrays, two slots per record"""
+    def host(a, dtype):
+        return (a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)).view(dtype).reshape(-1)
+    pos, op_off, ops = host(alignments[0], np.int32), host(alignments[2], np.uint64), host(alignments[3], np.uint32)
+    if len(pos) != 2 * n_records or len(op_off) != 2 * n_records + 1:
+        raise ValueError(f"an alignment of {len(pos)} slots for {n_records} records (two slots a record)")
+    return pos, op_off, ops
+
+
+def _cigar_text(words):
+    return b"".join(b"%d%c" % (int(w) >> 4, _OPS[int(w) & 15]) for w in words)
+
+
+def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False, alignments=None):
     """the text write_sam writes.  quals: per read the quality bytes (single end) or a (mate 1, mate 2) pair, a mate's None for
     "not given" (QUAL '*'); they go with the mate's SEQ on every line.  oriented: a line with 0x10 carries SEQ reverse-complemented
-    and QUAL reversed.  The rules are stated in csrc/samwfmt.h."""
+    and QUAL reversed.  alignments: what hits.align_hits / align_hits_host returned for the same records -- a mapped line then takes
+    POS and CIGAR from its slot (2 * record + line) and PNEXT from the other line's slot, and a slot without an operation is the
+    "no base on the transcript" error.  The rules are stated in csrc/samwfmt.h."""
     if quals is not None and seqs is None:
         raise ValueError("qualities of reads whose bases are not given")
     hits = np.asarray(hits).view(HIT_DTYPE).reshape(-1)
@@ -620,6 +637,17 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
     out = [b"@HD\tVN:1.6\tSO:unsorted\tGO:query\n"]
     out += [b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(nm, ref_len)]
     fmt = b"%s\t%d\t%s\t%d\t255\t%s\t%s\t%d\t%d\t%s\t%s\n"
+    aln = _alignment_arrays(alignments, int(off[-1]) if len(off) else 0) if alignments is not None else None
+
+    def placed(h, which, pos, length, what):
+        """(POS, CIGAR) of line `which` of record h"""
+        if aln is None:
+            return _aligned(pos, length, what)
+        slot = 2 * h + which
+        words = aln[2][int(aln[1][slot]):int(aln[1][slot + 1])]
+        if not len(words):
+            raise ValueError(f"{what}: the alignment has no operation, so {WRITE_KINDS[1]}")
+        return int(aln[0][slot]) + 1, _cigar_text(words)
 
     def line(q, flag, rname, p, cigar, rnext, pnext, tlen, sq):
         """sq: the mate's (SEQ, QUAL or None)"""
@@ -654,9 +682,9 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
         for i, (tid, pos, mpos, frag, rlen, mlen, fwd, mfwd, status, _) in enumerate(recs):
             sec = 0x100 if i else 0
             what = f"read {r}, record {i}"
-            p1, c1 = _aligned(pos, rlen, what)
+            p1, c1 = placed(int(off[r]) + i, 0, pos, rlen, what)
             if status == 3:
-                p2, c2 = _aligned(mpos, mlen, what)
+                p2, c2 = placed(int(off[r]) + i, 1, mpos, mlen, what)
             rname = nm[tid]
             if i == 0:
                 check_quals(r, (s1, s2))
@@ -672,7 +700,7 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
     return b"".join(out)
 
 
-def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False):
+def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False, alignments=None):
     """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
     line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
     a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
@@ -681,8 +709,9 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     reverse-complemented and QUAL reversed, as the SAM specification stores them.  A quality byte outside '!' .. '~' is a ValueError
     (QUAL_WRITE_KINDS); a 1-base read whose quality is '*' reads as "no qualities", the format's ambiguity.  `read_names`: per read, default
     r<index>.  The library is taken as paired when any record is, or, without records, when seqs holds pairs.  bgzf=True writes
-    blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan."""
-    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented)
+    blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan.  `alignments`: the gapped alignment
+    of the same records (hits.align_hits / align_hits_host): POS, CIGAR and PNEXT are then the alignment's."""
+    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments)
     if bgzf:
         from . import gzfile
         gzfile.write_bgzf(path, data)
@@ -691,7 +720,8 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
             f.write(data)
 
 
-def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False, sort=None):
+def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False, sort=None,
+              alignments=None):
     """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
     members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf).  sort="coordinate": the same records in
     coordinate order under an @HD SO:coordinate header (sort_bam_stream; csrc/baifmt.h), the header in members of its own, so that
@@ -699,7 +729,7 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     from . import gzfile
     if sort not in SORT_ORDERS:
         raise ValueError(f"sort must be one of {SORT_ORDERS}, not {sort!r}")
-    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented))
+    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments))
     if sort is None:
         gzfile.write_bgzf(path, data, member_bytes=member_bytes)
         return
@@ -1003,6 +1033,9 @@ class SamDeviceWriter:
                   pairs; default '*'.
       quals       the qualities that go with `seqs`: a device uint8 tensor that shares the bases' offsets (readfile.ReadFile's
                   last_quals), or (paired) a pair of them, either member None; default QUAL '*'.
+      alignments  what hits.align_hits returned for the batch's records (pos, nm, op_off, ops, ...): a mapped line then takes POS
+                  and CIGAR from its slot, PNEXT from the other line's; a slot without an operation is WRITE_KINDS[1]; default: the
+                  recorded diagonal, <len>M at pos.
     Bases and qualities are written as given, also on 0x10 lines, unless `oriented=True`: then a 0x10 line carries SEQ
     reverse-complemented and QUAL reversed (the SAM specification's orientation, what other tools expect).
     A record SAM cannot express (WRITE_KINDS) raises ValueError naming the lowest such read -- counted over all batches, as
@@ -1080,7 +1113,7 @@ class SamDeviceWriter:
             raise TypeError("expected (bytes, 64-bit integer offsets)")
         return b.to(dev).contiguous(), o.to(dev).contiguous()
 
-    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None):
+    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None):
         import torch
 
         from . import _lib, quantfile
@@ -1140,16 +1173,29 @@ class SamDeviceWriter:
         batch = (p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs, p(q[0]), p(q[1]),
                  p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads, self.chunk_bytes)
         extra = (None if ql[0] is None else _lib.ptr(ql[0]), None if ql[1] is None else _lib.ptr(ql[1]), int(self.oriented))
+        aln = (None, None, None)
+        if alignments is not None:
+            a_pos, a_off, a_ops = (alignments[i].to(dev).contiguous() for i in (0, 2, 3))
+            if a_pos.element_size() != 4 or a_off.element_size() != 8 or a_ops.element_size() != 4:
+                raise TypeError("alignments: expected what hits.align_hits returns (32-bit positions, 64-bit offsets, 32-bit operations)")
+            n_rec = d_hits.numel() // 24
+            if a_pos.numel() != 2 * n_rec or a_off.numel() != 2 * n_rec + 1:
+                raise ValueError(f"an alignment of {a_pos.numel()} slots for {n_rec} records (two slots a record)")
+            if not a_ops.numel():
+                a_ops = torch.zeros(1, dtype=torch.int32, device=dev)          # no operation at all: still "given"
+            if not a_pos.numel():
+                a_pos = torch.zeros(1, dtype=torch.int32, device=dev)
+            aln = (_lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops))
         with torch.cuda.device(dev):
             if self._z is None:
-                rc = self._L.sfgpu_sam_write_text_q(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra)
+                rc = self._L.sfgpu_sam_write_text_a(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
             elif self._sort:
                 self._write_head(dev)
                 self._open_store()
-                rc = self._L.sfgpu_bamsort_collect(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra)
+                rc = self._L.sfgpu_bamsort_collect_a(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
             else:
                 self._write_head(dev)
-                rc = self._L.sfgpu_sam_write_bgzf_q(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra)
+                rc = self._L.sfgpu_sam_write_bgzf_a(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
         sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
         if sunk:
             raise sunk.pop(0)

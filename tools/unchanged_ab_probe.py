@@ -1,0 +1,125 @@
+"""One leg of a parent / new / parent comparison of device paths that a change is meant to leave alone, each leg a fresh process:
+
+ - the device writers (samfile.SamDeviceWriter, formats "sam", "sam.gz", "bam") on the batch of tools/samwrite_probe.py (100 000
+   pairs of 2 x 100 bases, 0 .. 3 records each, 30 000 transcript names): host wall time of open + write + close into memory
+   (io.BytesIO), after torch.cuda.synchronize(), and the formatter's device time from the writer's stats (`ms_format`);
+ - sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (--pairs, default 2 M; 80 000 transcripts; 2 % substitutions, an
+   indel of 1 - 3 bases in 5 % of the mates; max_indel 3, min identity 0.9): host wall time around the call, synchronised.
+
+Every figure is the median of --repeats (default 7) runs after one warm-up run; all runs are kept.  --root names the tree whose
+`sailfish_amd` is measured (built there beforehand; default: the tree this file is in), so that the same driver measures a checkout
+of the parent commit and this one:
+
+    python tools/unchanged_ab_probe.py --label parent1 --root /path/to/parent/checkout --json profiles/NAME.json
+    python tools/unchanged_ab_probe.py --label new --json profiles/NAME.json
+    python tools/unchanged_ab_probe.py --label parent2 --root /path/to/parent/checkout --json profiles/NAME.json
+
+Each call appends its leg to the `runs` of the JSON file (created if absent) and prints it as one line."""
+import argparse
+import ctypes as C
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+WHAT = ("parent / new / parent in fresh processes on one device, one call of tools/unchanged_ab_probe.py a leg: the device writers on the batch of "
+        "tools/samwrite_probe.py (100 000 pairs; wall ms of SamDeviceWriter open + write + close into memory, and the formatter's device ms) and "
+        "sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (2 % substitutions, an indel in 5 % of the mates, max_indel 3); medians of "
+        "`repeats` runs after a warm-up")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--label", required=True)
+    ap.add_argument("--root", default=os.path.dirname(HERE))
+    ap.add_argument("--json", required=True)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--pairs", type=int, default=2_000_000)
+    ap.add_argument("--transcripts", type=int, default=80_000)
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    import numpy as np
+    import torch
+    import sailfish_amd as sf                      # the measured tree's: imported before the probes below would find their own
+    from sailfish_amd import _lib, samfile, synth
+    assert os.path.samefile(os.path.dirname(os.path.dirname(sf.__file__)), a.root), sf.__file__
+    sys.path.insert(0, HERE)
+    import samwrite_probe
+    import verify_probe
+
+    dev = torch.device("cuda:0")
+    med = statistics.median
+    leg = dict(label=a.label, device=torch.cuda.get_device_name(0), repeats=a.repeats)
+
+    # the writers
+    rng = np.random.default_rng(23)
+    n_reads, read_len, n_refs = 100_000, 100, 30_000
+    names = [f"ENST{i:011d}.{i % 9 + 1}" for i in range(n_refs)]
+    ref_len = rng.integers(6200, 20000, n_refs)
+    hits, off, b1, b2, boff = samwrite_probe.batch(n_reads, read_len, n_refs, rng)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).copy()).to(dev)  # noqa: E731
+    d_hits, d_off = up(hits.view(np.uint8).reshape(-1)), up(off.view(np.int32))
+    d_seqs = ((up(b1), up(boff)), (up(b2), up(boff)))
+    for fmt in ("sam", "sam.gz", "bam"):
+        ms, ms_format, n_bytes = [], [], 0
+        for i in range(a.repeats + 1):
+            f = io.BytesIO()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with samfile.SamDeviceWriter(f, names, ref_len, True, format=fmt) as w:
+                w.write(d_hits, d_off, seqs=d_seqs)
+                st = dict(w.stats)
+            dt = 1e3 * (time.perf_counter() - t0)
+            n_bytes = len(f.getvalue())
+            if i:
+                ms.append(dt); ms_format.append(st["ms_format"])
+        leg[fmt] = dict(ms=med(ms), ms_format=med(ms_format), ms_runs=ms, ms_format_runs=ms_format, bytes=n_bytes)
+
+    # the gapped scoring pass
+    M, R, L, K = a.transcripts, a.pairs, 100, 3
+    ACGT = verify_probe.ACGT
+    g = torch.Generator(device=dev); g.manual_seed(1)
+    tlen = synth.transcript_lengths(M, device=dev).long()
+    toff = torch.zeros(M + 1, dtype=torch.int64, device=dev); torch.cumsum(tlen, 0, out=toff[1:])
+    N = int(toff[-1])
+    seq = ACGT[torch.randint(0, 4, (N,), generator=g, device=dev)]
+    t = torch.randint(0, M, (R,), generator=g, device=dev)
+    p = (torch.rand(R, generator=g, device=dev, dtype=torch.float64) * (tlen[t] - 250).clamp_min(0).double()).long()
+    comp = torch.zeros(256, dtype=torch.uint8, device=dev); comp[list(b"ACGT")] = torch.tensor(list(b"TGCA"), dtype=torch.uint8, device=dev)
+    roff = torch.arange(R + 1, device=dev, dtype=torch.int64) * L
+    index = sf.mapper.QuasiIndex((seq, toff), device=dev)
+    m1, m2 = verify_probe.make_mates(seq, N, toff[t] + p, L, comp, g, 0.05)
+    for m in (m1, m2):
+        hit = torch.rand(m.shape, generator=g, device=dev) < 0.02
+        m[hit] = ACGT[torch.randint(0, 4, (int(hit.sum()),), generator=g, device=dev)]
+    r1, r2 = m1.reshape(-1), m2.reshape(-1)
+    h, hoff = index.map_reads((r1, roff), (r2, roff))
+    n = h.numel() // 24
+    out_hits, out_off, scores = torch.empty_like(h), torch.empty_like(hoff), torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
+    go = _lib.VerifyGOpts(900, 0, K); gst = _lib.VerifyGStats(); n_out = C.c_uint64(0)
+    Lb = _lib.lib()
+
+    def gapped():
+        _lib.check(Lb.sfgpu_hits_verify_gapped(index._h, _lib.ptr(r1), _lib.ptr(roff), _lib.ptr(r2), _lib.ptr(roff), R, _lib.ptr(h), _lib.ptr(hoff), C.byref(go),
+                                               _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(gst), None))
+    g_ms, g_all = verify_probe.timed(gapped, a.repeats)
+    leg["verify_gapped"] = dict(ms=g_ms, ms_runs=g_all, pairs=R, records=n, stats=gst.as_dict())
+    index.close()
+
+    print(json.dumps(leg), flush=True)
+    doc = dict(what=WHAT, runs=[])
+    if os.path.exists(a.json):
+        with open(a.json) as f:
+            doc = json.load(f)
+    doc["runs"].append(leg)
+    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+    with open(a.json, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()

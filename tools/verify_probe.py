@@ -15,7 +15,15 @@
    share of jobs that ran the recurrence (ungapped count > 0, and not behind a failed first job) and that stopped on a band minimum
    above the edits that can still pass, both counted on the device from the entries' own scores at permille 0.
 4. effect, on the spliced transcriptome, of reads with one indel of 1 - 3 bases (and 1 % substitutions) at min_identity 0.9: true
-   records lost at max_indel 0 and K, and the false records K lets in."""
+   records lost at max_indel 0 and K, and the false records K lets in.
+
+--max-indel [K] --align runs the alignment leg instead (sfgpu_hits_align_gapped) -> profiles/aligng_probe.json
+5. cost, on the same batch, error-free and with 2 % substitutions plus one indel of 1 - 3 bases in 5 % of the mates: the batch's
+   records are reduced to the survivors of sfgpu_hits_verify_gapped at 0.9; the alignment of a slice is first asserted equal to
+   hits.align_hits_host; then medians of 5 after a warm-up of sfgpu_hits_align_gapped on the survivors (with exactly the room it
+   needs), of sfgpu_hits_verify_gapped on the batch they came from, and of a plain device-to-device copy of the bytes the pass moves
+   (each job's mate bases, 24 bytes a record, 16 bytes a slot, the operations, and the scratch written and read once); the share of
+   jobs traced, the slices' scratch peak and the whole batch's."""
 import ctypes as C
 import json
 import os
@@ -229,6 +237,78 @@ def cost_gapped(M, R, K, L=100):
     return rows
 
 
+def cost_align(M, R, K, L=100):
+    g = torch.Generator(device=dev); g.manual_seed(1)
+    ref_len = synth.transcript_lengths(M, device=dev).long()
+    off = torch.zeros(M + 1, dtype=torch.int64, device=dev); torch.cumsum(ref_len, 0, out=off[1:])
+    N = int(off[-1])
+    seq = ACGT[torch.randint(0, 4, (N,), generator=g, device=dev)]
+    t = torch.randint(0, M, (R,), generator=g, device=dev)
+    p = (torch.rand(R, generator=g, device=dev, dtype=torch.float64) * (ref_len[t] - 250).clamp_min(0).double()).long()
+    start = off[t] + p
+    comp = torch.zeros(256, dtype=torch.uint8, device=dev); comp[list(b"ACGT")] = torch.tensor(list(b"TGCA"), dtype=torch.uint8, device=dev)
+    roff = torch.arange(R + 1, device=dev, dtype=torch.int64) * L
+    index = sf.mapper.QuasiIndex((seq, off), device=dev)
+    Lb = _lib.lib()
+    W = 16 if K <= 7 else 32
+    rows = []
+    for rate, indel_rate in ((0.0, 0.0), (0.02, 0.05)):
+        m1, m2 = make_mates(seq, N, start, L, comp, g, indel_rate)
+        if rate:
+            for m in (m1, m2):
+                hit = torch.rand(m.shape, generator=g, device=dev) < rate
+                m[hit] = ACGT[torch.randint(0, 4, (int(hit.sum()),), generator=g, device=dev)]
+        r1, r2 = (m1.reshape(-1), roff), (m2.reshape(-1), roff)
+        hits, hoff = index.map_reads(r1, r2)
+        n_in = hits.numel() // 24
+        # the alignment of a slice's survivors against the statement
+        k = min(R, 600)
+        cut = int(hoff[k].item())
+        sl1, sl2 = ([bytes(x) for x in m[:k].cpu().numpy()] for m in (m1, m2))
+        tx = Transcripts(seq, off)
+        sh, so, _, _ = H.verify_hits(index, hits[: cut * 24], hoff[: k + 1], sl1, sl2, min_identity=0.9, max_indel=K)
+        dp, dn, do, dops, dst = H.align_hits(index, sh, so, sl1, sl2, max_indel=K)
+        wp, wn, wo, wops, wst, _ = H.align_hits_host(tx, sh.cpu().numpy().view(H.HIT_DTYPE), so.cpu().numpy().view(np.uint32), sl1, sl2, K)
+        assert np.array_equal(dp.cpu().numpy(), wp) and np.array_equal(dn.cpu().numpy().view(np.uint32), wn) and np.array_equal(do.cpu().numpy().view(np.uint64), wo)
+        assert np.array_equal(dops.cpu().numpy().view(np.uint32), wops) and dst == wst, (dst, wst)
+        # the whole batch: its survivors, then the pass on them
+        s_hits, s_off, _, gstats = H.verify_hits(index, hits, hoff, r1, r2, min_identity=0.9, max_indel=K)
+        s_hits, s_off = s_hits.clone(), s_off.clone()
+        n = s_hits.numel() // 24
+        pos = torch.empty(2 * n, dtype=torch.int32, device=dev); nm = torch.empty_like(pos); op_off = torch.empty(2 * n + 1, dtype=torch.int64, device=dev)
+        ao = _lib.AlignGOpts(K, 0, 0); ast = _lib.AlignGStats(); need = C.c_uint64(0)
+        args = (index._h, _lib.ptr(r1[0]), _lib.ptr(roff), _lib.ptr(r2[0]), _lib.ptr(roff), R)
+        rc = Lb.sfgpu_hits_align_gapped(*args, _lib.ptr(s_hits), _lib.ptr(s_off), C.byref(ao), _lib.ptr(pos), _lib.ptr(nm), _lib.ptr(op_off), None, 0, C.byref(need),
+                                        C.byref(ast), None)
+        assert rc in (_lib.OK, _lib.ERR_RANGE), rc
+        ops = torch.empty(max(need.value, 1), dtype=torch.int32, device=dev)
+
+        def align():
+            _lib.check(Lb.sfgpu_hits_align_gapped(*args, _lib.ptr(s_hits), _lib.ptr(s_off), C.byref(ao), _lib.ptr(pos), _lib.ptr(nm), _lib.ptr(op_off), _lib.ptr(ops),
+                                                  ops.numel(), C.byref(need), C.byref(ast), None))
+        out_hits, out_off, scores = torch.empty_like(hits), torch.empty_like(hoff), torch.empty(max(n_in, 1) * 8, dtype=torch.uint8, device=dev)
+        go = _lib.VerifyGOpts(900, 0, K); gst = _lib.VerifyGStats(); n_out = C.c_uint64(0)
+
+        def gapped():
+            _lib.check(Lb.sfgpu_hits_verify_gapped(*args, _lib.ptr(hits), _lib.ptr(hoff), C.byref(go), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores),
+                                                   C.byref(n_out), C.byref(gst), None))
+        a_ms, a_all = timed(align)
+        stats = ast.as_dict()
+        g_ms, g_all = timed(gapped)
+        whole_scratch = stats["jobs_traced"] * 8 * W * ((L + 15) // 16)
+        moved = stats["jobs"] * L + 24 * n + 16 * 2 * n + 4 * stats["words"] + 2 * whole_scratch
+        src = torch.empty(moved, dtype=torch.uint8, device=dev); dst = torch.empty_like(src)
+        c_ms, c_all = timed(lambda: dst.copy_(src))
+        rows.append(dict(substitution_rate=rate, indel_mate_rate=indel_rate, max_indel=K, pairs=R, records_mapped=n_in, records_aligned=n, align_stats=stats,
+                         rescued=gstats["rescued"], align_ms=a_ms, align_ms_runs=a_all, gapped_ms=g_ms, gapped_ms_runs=g_all, bytes_moved=moved, d2d_copy_ms=c_ms,
+                         d2d_copy_ms_runs=c_all, align_over_gapped=a_ms / g_ms, align_over_copy=a_ms / c_ms, traced_job_share=stats["jobs_traced"] / max(stats["jobs"], 1),
+                         scratch_peak_bytes=stats["scratch_bytes"], scratch_whole_batch_bytes=whole_scratch, words_per_job=stats["words"] / max(stats["jobs"], 1)))
+        print(json.dumps(rows[-1]), flush=True)
+        del src, dst, m1, m2, out_hits, scores, ops, pos, nm, op_off, s_hits
+    index.close()
+    return rows
+
+
 def effect_gapped(K):
     rng = np.random.default_rng(7)
     bases = np.frombuffer(b"ACGT", np.uint8)
@@ -333,13 +413,19 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("path", nargs="?", default=None, help="where the JSON goes (default: profiles/verify_probe.json, or verifyg_probe.json with --max-indel)")
     ap.add_argument("--max-indel", type=int, nargs="?", const=3, default=None, metavar="K", help="run the gapped legs (sfgpu_hits_verify_gapped) with band K, default 3")
+    ap.add_argument("--align", action="store_true", help="with --max-indel: run the alignment leg (sfgpu_hits_align_gapped) -> profiles/aligng_probe.json")
     a = ap.parse_args()
+    if a.align and a.max_indel is None:
+        ap.error("--align needs --max-indel")
     M, R = int(os.environ.get("VERIFY_M", 80000)), int(os.environ.get("VERIFY_R", 10_000_000))
-    if a.max_indel is None:
+    if a.align:
+        out = dict(device=torch.cuda.get_device_name(0), transcripts=M, max_indel=a.max_indel, cost=cost_align(M, R, a.max_indel))
+    elif a.max_indel is None:
         out = dict(device=torch.cuda.get_device_name(0), transcripts=M, effect=effect(), cost=cost(M, R))
     else:
         out = dict(device=torch.cuda.get_device_name(0), transcripts=M, max_indel=a.max_indel, effect=effect_gapped(a.max_indel), cost=cost_gapped(M, R, a.max_indel))
-    path = a.path or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "verifyg_probe.json" if a.max_indel is not None else "verify_probe.json")
+    path = a.path or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                  "aligng_probe.json" if a.align else "verifyg_probe.json" if a.max_indel is not None else "verify_probe.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
         f.write("\n")

@@ -1,6 +1,7 @@
 // align_gapped.hip -- sfgpu_hits_align_gapped: the gapped alignment of the records that survive sfgpu_hits_verify_gapped, as a
 // position and BAM CIGAR words per job.  WHAT the alignment of a job is -- candidates, end cell, walk, trim -- is
-// csrc/aligngfmt.h, stated once and run here unchanged; this file is only the way the work is laid out.
+// csrc/aligngfmt.h, stated once and run here unchanged; this file is only the way the work is laid out, and what the hit passes
+// share of that -- the job decode, the group tools, the band -- is csrc/hitgroup.h.
 //
 // Two slots per record (slot 2 h + j is job j of record h); count -> scan -> fill, twice:
 //   k_aligng_reads      a lane per read names the read of each of its records
@@ -8,8 +9,8 @@
 //                       (vf_job_lane + a group sum) and with them its kind -- no job, no bases, all bases match, traced -- and the
 //                       steps of scratch it needs (ceil(len / 16) for a traced job, else none); errors are found here
 //   scan                steps -> the scratch's CSR; the host cuts the slots into slices whose scratch fits the cap (k_aligng_cut)
-//   k_aligng_trace<W, false>  per slice, a group per slot.  Forward: lanes are DIAGONALS, the row is verify_gapped.hip's plus one
-//                       exchange for the lower neighbour's new cell; every 16 rows a lane stores the 4 bits of its 16 cells as one
+//   k_aligng_trace<W, false>  per slice, a group per slot.  Forward (hit_band_dev<W, true>): lanes are DIAGONALS, the row is the
+//                       scoring pass's plus one exchange for the lower neighbour's new cell; every 16 rows a lane stores the 4 bits of its 16 cells as one
 //                       64-bit word, the group W consecutive words (128 or 256 bytes).  Backward: ag_walk over those words, a lane
 //                       loading its own word of a step once and the group taking the current lane's by shuffle; this pass counts
 //                       the operations only.
@@ -19,44 +20,24 @@
 #include "common.h"
 #include "mapidx.h"
 #include "primitives.h"
-#include "aligngfmt.h"
+#include "hitgroup.h"
 
 #include <vector>
 
 namespace sfgpu {
 
-constexpr int kAgBlock = 256;
+constexpr int kAgBlock = kHitBlock;
 constexpr uint64_t kAgDefaultCap = 256ull << 20;
-enum { kAgBadTid = 0, kAgBadMate, kAgJobs, kAgTraced, kAgUnalignable, kAgSumNm, kAgCounters };
+enum { kAgJobs = kHitFirstCounter, kAgTraced, kAgUnalignable, kAgSumNm, kAgCounters };
 enum : uint8_t { kAgNoJob = 0, kAgNoBases, kAgAllMatch, kAgTracedJob };
-
-template <int W> __device__ __forceinline__ uint64_t ag_group_sum(uint64_t v) {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor((unsigned long long)v, o, W);
-    return v;
-}
-template <int W> __device__ __forceinline__ uint32_t ag_group_min(uint32_t v) {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(v, o, W); v = u < v ? u : v; }
-    return v;
-}
 
 __global__ void __launch_bounds__(kAgBlock)
 k_aligng_reads(uint64_t n_reads, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t* __restrict__ rec_read) {
     const uint64_t r = (uint64_t)blockIdx.x * kAgBlock + threadIdx.x;
     if (r >= n_reads) return;
-    uint64_t e = hit_off[r + 1], b = hit_off[r];
-    e = e < n_rec ? e : n_rec; b = b < e ? b : e;
+    uint64_t b, e;
+    hit_range(hit_off, r, n_rec, &b, &e);
     for (uint64_t i = b; i < e; ++i) rec_read[i] = (uint32_t)r;
-}
-
-struct AgJobDev { const char* m; const char* t; uint64_t len, tl; int64_t pos; bool fwd; };
-__device__ __forceinline__ AgJobDev ag_job_dev(const sfgpu_hit& h, uint32_t j, uint32_t r, const char* tseq, const uint64_t* tseq_off, const uint32_t* tlen,
-                                               const char* seq1, const uint64_t* off1, const char* seq2, const uint64_t* off2) {
-    const VfJob jb = vf_job(h, j);
-    const uint64_t* off = jb.mate ? off2 : off1;
-    const uint64_t mb = off[r];
-    return AgJobDev{(jb.mate ? seq2 : seq1) + mb, tseq + tseq_off[h.tid], off[r + 1] - mb, tlen[h.tid], (int64_t)jb.pos, jb.fwd};
 }
 
 template <int W> __global__ void __launch_bounds__(kAgBlock)
@@ -70,12 +51,12 @@ k_aligng_size(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_o
     const sfgpu_hit h = hits[s >> 1];
     const uint32_t j = (uint32_t)(s & 1u), r = rec_read[s >> 1];
     uint32_t need = 0; uint8_t kd = kAgNoJob;
-    if (h.tid >= M) { if (lane == 0) atomicMin(&ctr[kAgBadTid], (unsigned long long)(s >> 1)); }
-    else if ((h.mate_status == 2 || vf_n_jobs(h) > 1) && !seq2) { if (lane == 0) atomicMin(&ctr[kAgBadMate], (unsigned long long)(s >> 1)); }
+    const int bad = hit_bad_record(h, M, seq2);
+    if (bad >= 0) { if (lane == 0) atomicMin(&ctr[bad], (unsigned long long)(s >> 1)); }
     else if (j < vf_n_jobs(h) && r != ~0u) {
-        const AgJobDev jb = ag_job_dev(h, j, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+        const HitJobDev jb = hit_job_dev(h, j, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
         const VfCount c = vf_job_lane(jb.m, jb.len, jb.fwd, jb.t, jb.tl, jb.pos, lane, W);
-        const uint64_t ungapped = ag_group_sum<W>(c.mism + c.over);
+        const uint64_t ungapped = group_sum<W>(c.mism + c.over);
         kd = jb.len == 0 ? kAgNoBases : ungapped == 0 ? kAgAllMatch : kAgTracedJob;
         need = kd == kAgTracedJob ? (uint32_t)ag_steps(jb.len) : 0u;
     }
@@ -91,28 +72,6 @@ __global__ void k_aligng_cut(const uint64_t* __restrict__ prefix, uint64_t n_slo
         if (prefix[mid] - prefix[a] <= cap_steps) lo = mid; else hi = mid - 1;
     }
     out[0] = lo; out[1] = prefix[lo] - prefix[a];
-}
-
-// the forward pass of one job over the group's lanes: the cells' bits into `cells` (W words a step) -> the end lane
-template <int W> __device__ __forceinline__ uint32_t ag_forward_dev(const AgJobDev& jb, uint32_t k, uint32_t lane, uint64_t* __restrict__ cells) {
-    uint32_t D = vg_lane_start(lane, k);
-    for (uint64_t i0 = 0; i0 < jb.len; i0 += kVfStep) {
-        const uint32_t mask = vg_lane_submask(vf_mate_window(jb.m, (int64_t)jb.len, jb.fwd, (int64_t)i0), jb.t, jb.tl, jb.pos, i0, lane, k, jb.fwd);
-        const uint32_t n = jb.len - i0 < kVfStep ? (uint32_t)(jb.len - i0) : kVfStep;
-        uint64_t word = 0;
-        for (uint32_t j = 0; j < n; ++j) {
-            const uint32_t up = __shfl_down(D, 1, W), sub = (mask >> j) & 1u;      // (lane W - 1 gets its own: it is never in the band)
-            uint32_t key = vg_key(vg_lane_v(D, up, sub), lane, W);
-#pragma unroll
-            for (int o = 1; o < W; o <<= 1) key = vg_scan_step(key, __shfl_up(key, o, W), lane, (uint32_t)o);
-            const uint32_t nd = vg_lane_d(key, lane, W, k), below = __shfl_up(nd, 1, W);
-            word |= (uint64_t)ag_lane_cand(D, up, sub, nd, below, lane, k) << (4u * j);
-            D = nd;
-        }
-        cells[(i0 / kVfStep) * W + lane] = word;                     // (the group: W consecutive words)
-    }
-    const uint32_t m = ag_group_min<W>(D);
-    return ag_rank_lane(ag_group_min<W>(ag_end_rank(D, m, lane, k)), k);
 }
 
 // ag_walk's fetch: a lane keeps its own word of the step the walk is in; the group takes the current lane's by shuffle
@@ -144,12 +103,12 @@ k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
         uint32_t* ops = (WRITE && lane == 0) ? ops_out : nullptr;
         AgTrace w{};
         if (kd >= kAgAllMatch) {
-            const AgJobDev jb = ag_job_dev(hits[s >> 1], (uint32_t)(s & 1u), rec_read[s >> 1], tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+            const HitJobDev jb = hit_job_dev(hits[s >> 1], (uint32_t)(s & 1u), rec_read[s >> 1], tseq, tseq_off, tlen, seq1, off1, seq2, off2);
             if (kd == kAgAllMatch) w = ag_all_match(jb.len, jb.pos, ops, lo, hi);
             else {
                 uint64_t* mine = cells + (prefix[s] - prefix[a]) * W;
                 uint32_t le;
-                if (do_forward) { le = ag_forward_dev<W>(jb, k, lane, mine); if (lane == 0) lane_end[s] = (uint8_t)le; }
+                if (do_forward) { le = (uint32_t)hit_band_dev<W, true>(jb, k, lane, 0, mine); if (lane == 0) lane_end[s] = (uint8_t)le; }
                 else le = lane_end[s];
                 AgFetchDev<W> fetch{mine, lane, ~0ull, 0ull};
                 w = ag_walk(jb.len, jb.pos, jb.tl, k, le, fetch, ops, lo, hi);
@@ -177,7 +136,6 @@ k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
 
 using namespace sfgpu;
 
-struct AlignGSyncOnExit { hipStream_t s; ~AlignGSyncOnExit() { (void)hipStreamSynchronize(s); } };
 struct AgSlice { uint64_t a, b, steps; };
 
 extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
@@ -189,12 +147,10 @@ extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1,
     SF_REQUIRE(n_reads == 0 || (d_seq1 && d_off1 && d_hit_offsets && (!d_seq2 || d_off2)), SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null reads");
     SF_REQUIRE(cap_ops == 0 || d_ops, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null operations");
     hipStream_t st = as_stream(stream);
-    uint32_t n_rec32 = 0;
-    if (n_reads) {
-        SF_HIP(hipMemcpyAsync(&n_rec32, d_hit_offsets + n_reads, 4, hipMemcpyDeviceToHost, st));
-        SF_HIP(hipStreamSynchronize(st));
-    }
-    const uint64_t n_rec = n_rec32, n_slots = 2 * n_rec;
+    int rc;
+    uint64_t n_rec = 0;
+    if ((rc = hit_n_rec(d_hit_offsets, n_reads, st, &n_rec))) return rc;
+    const uint64_t n_slots = 2 * n_rec;
     if (n_rec == 0) {
         SF_HIP(hipMemsetAsync(d_op_off, 0, 8, st)); SF_HIP(hipStreamSynchronize(st));
         *n_ops = 0; *stats = sfgpu_align_gstats{};
@@ -202,10 +158,9 @@ extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1,
     }
     SF_REQUIRE(d_hits && d_pos && d_nm, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null records");
     const uint32_t k = opts->max_indel, W = vg_width(k), per_block = kAgBlock / W;
-    int rc;
     // (steps and cnt: n_slots + 1 entries, exclusive_scan_u32 reads one past the last)
     DevBuf<uint32_t> rec_read, steps, cnt; DevBuf<uint8_t> kind, lane_end; DevBuf<uint64_t> prefix, woff, cells, cut; DevBuf<unsigned long long> ctr;
-    AlignGSyncOnExit sync_first{st};         // (declared after the buffers: an early return waits for the kernels before scratch goes back)
+    StreamSyncOnExit sync_first{st};          // (declared after the buffers: an early return waits for the kernels before scratch goes back)
     if ((rc = rec_read.reserve(n_rec, st, false)) || (rc = steps.reserve(n_slots + 1, st, false)) || (rc = cnt.reserve(n_slots + 1, st, false)) ||
         (rc = kind.reserve(n_slots, st, false)) || (rc = lane_end.reserve(n_slots, st, false)) || (rc = prefix.reserve(n_slots + 1, st, false)) ||
         (rc = woff.reserve(n_slots + 1, st, false)) || (rc = cut.reserve(2, st, false)) || (rc = ctr.reserve(kAgCounters, st, false))) return rc;
@@ -223,14 +178,7 @@ extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1,
     SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(&total_steps, prefix.p + n_slots, 8, hipMemcpyDeviceToHost, st));
     SF_HIP(hipStreamSynchronize(st));
-    if (h_ctr[kAgBadTid] != ~0ull) {
-        set_error("sfgpu_hits_align_gapped: record %llu names transcript >= %llu", h_ctr[kAgBadTid], (unsigned long long)x->M);
-        return SFGPU_ERR_RANGE;
-    }
-    if (h_ctr[kAgBadMate] != ~0ull) {
-        set_error("sfgpu_hits_align_gapped: record %llu names mate 2 of a single-end batch", h_ctr[kAgBadMate]);
-        return SFGPU_ERR_INVALID;
-    }
+    if ((rc = hit_report_bad("sfgpu_hits_align_gapped", h_ctr, x->M))) return rc;
     // the slices
     const uint64_t cap_bytes = opts->scratch_cap_bytes ? opts->scratch_cap_bytes : kAgDefaultCap;
     const uint64_t cap_steps = cap_bytes / (8ull * W) ? cap_bytes / (8ull * W) : 1ull;

@@ -1,6 +1,6 @@
 // aligngfmt.h -- gapped alignment of a job: the path through verifygfmt.h's band, as CIGAR words and a position, stated once.  Plain
 // C++, host and device, on top of verifygfmt.h: the same cells D[i][d], the same sub, the free start row, the band k = max_indel
-// (1 .. 15).  align_gapped.hip runs the lane functions and ag_walk below inside its kernel, tests/aligng_harness.cpp runs them alone
+// (1 .. 15).  align_gapped.hip runs the band (hitgroup.h: hit_band_dev) and ag_walk below inside its kernel, tests/aligng_harness.cpp runs them alone
 // (ag_serial_align), and hits.align_hits_host is the Python statement both are judged by.  The tie rules are part of the contract.
 //
 // CANDIDATES of cell (i, d):  DIAG iff D[i-1][d] + sub(i, pos + i + d) == D[i][d];  INS iff d < k and D[i-1][d+1] + 1 == D[i][d];
@@ -22,9 +22,9 @@
 // STATS    jobs; jobs_traced (ungapped count > 0: the recurrence ran); unalignable; sum_nm; words (operations over all slots);
 //          scratch_bytes (of the largest slice; the whole batch's, 8 * width * ceil(len / 16) per traced job, where nothing is sliced).
 //
-// Lanes are DIAGONALS, as in verifygfmt.h.  The forward pass repeats its row (vg_lane_v, vg_scan_step, vg_lane_d) and adds one
-// exchange, the lower neighbour's new cell; ag_lane_cand turns a row into 4 bits a lane -- the three candidates and sub -- and every
-// kVfStep rows a lane has one 64-bit word: step q of a job is `width` consecutive words.  ag_walk walks back over those words, the
+// Lanes are DIAGONALS, as in verifygfmt.h, and the forward pass IS its band function handed `cells` (vg_band_group; hit_band_dev on
+// the device): its row plus one exchange, the lower neighbour's new cell; ag_lane_cand (stated there, beside the row it reads)
+// turns a row into 4 bits a lane -- the three candidates and sub -- and every kVfStep rows a lane has one 64-bit word: step q of a job is `width` consecutive words.  ag_walk walks back over those words, the
 // same in every lane of the group (`fetch` hands it lane l's word of step q), and streams its columns into ag_column, which merges,
 // trims and, given the slot's place [lo, hi) in the operations, writes each run where it belongs, from the right end: the first pass
 // (ops == nullptr) only counts.  Operation lengths are 28 bits: mates shorter than 2^28 bases.
@@ -33,26 +33,12 @@
 
 namespace sfgpu {
 
-constexpr uint32_t kAgDiag = 1u, kAgIns = 2u, kAgDel = 4u;                  // candidate bits of a cell; bit 3 is sub on its diagonal
 constexpr uint32_t kAgM = 0u, kAgI = 1u, kAgD = 2u, kAgS = 4u;              // BAM's operation codes
 constexpr uint32_t kAgOff = 3u;                                            // here only: an M column off the transcript
-constexpr uint32_t kAgNoEnd = 0xFFFFu;
 
 VF_HD uint64_t ag_steps(uint64_t len) { return (len + kVfStep - 1u) / kVfStep; }
 VF_HD uint64_t ag_scratch_bytes(uint64_t len, uint32_t width) { return 8ull * width * ag_steps(len); }
 
-// the 4 bits of this lane's cell: d_prev = its D[i-1], up = the next lane's D[i-1], d_new = its D[i], below = the lane before's D[i]
-VF_HD uint32_t ag_lane_cand(uint32_t d_prev, uint32_t up, uint32_t sub, uint32_t d_new, uint32_t below, uint32_t lane, uint32_t k) {
-    if (lane > 2u * k) return 0u;
-    return (d_prev + sub == d_new ? kAgDiag : 0u) | ((lane < 2u * k && up + 1u == d_new) ? kAgIns : 0u) |
-           ((lane > 0u && below + 1u == d_new) ? kAgDel : 0u) | sub << 3;
-}
-// END: the least rank over the lanes names the end diagonal
-VF_HD uint32_t ag_end_rank(uint32_t d_last, uint32_t edits, uint32_t lane, uint32_t k) {
-    if (lane > 2u * k || d_last != edits) return kAgNoEnd;
-    return lane >= k ? 2u * (lane - k) + (lane > k ? 1u : 0u) : 2u * (k - lane);
-}
-VF_HD uint32_t ag_rank_lane(uint32_t rank, uint32_t k) { return (rank & 1u) ? k + (rank >> 1) : k - (rank >> 1); }
 // WALK's choice (a cell without a candidate does not exist; it would be taken as DIAG, so that the walk ends)
 VF_HD uint32_t ag_pick(uint32_t cand, uint32_t prev) {
     if (prev == kAgDel && (cand & kAgDel)) return kAgDel;
@@ -128,34 +114,6 @@ VF_HD AgTrace ag_walk(uint64_t len, int64_t pos, uint64_t tlen, uint32_t k, uint
     }
     ag_finish(w, ops, lo, hi);
     return w;
-}
-
-// a group of `width` lanes in lockstep on the host: the forward pass into `cells` (width * ag_steps(len) words) -> the end lane
-VF_HD uint32_t ag_forward_group(const char* r, uint64_t len, bool fwd, const char* t, uint64_t tlen, int64_t pos, uint32_t k, uint32_t width, uint64_t* cells) {
-    uint32_t D[kVgMaxWidth], key[kVgMaxWidth], nxt[kVgMaxWidth], mask[kVgMaxWidth], nd[kVgMaxWidth];
-    uint64_t word[kVgMaxWidth];
-    for (uint32_t l = 0; l < width; ++l) D[l] = vg_lane_start(l, k);
-    for (uint64_t i0 = 0; i0 < len; i0 += kVfStep) {
-        const VfWin mate = vf_mate_window(r, (int64_t)len, fwd, (int64_t)i0);
-        for (uint32_t l = 0; l < width; ++l) { mask[l] = vg_lane_submask(mate, t, tlen, pos, i0, l, k, fwd); word[l] = 0; }
-        const uint32_t n = len - i0 < kVfStep ? (uint32_t)(len - i0) : kVfStep;
-        for (uint32_t j = 0; j < n; ++j) {
-            for (uint32_t l = 0; l < width; ++l) key[l] = vg_key(vg_lane_v(D[l], D[l + 1u < width ? l + 1u : l], (mask[l] >> j) & 1u), l, width);
-            for (uint32_t o = 1; o < width; o <<= 1) {
-                for (uint32_t l = 0; l < width; ++l) nxt[l] = vg_scan_step(key[l], key[l >= o ? l - o : l], l, o);
-                for (uint32_t l = 0; l < width; ++l) key[l] = nxt[l];
-            }
-            for (uint32_t l = 0; l < width; ++l) nd[l] = vg_lane_d(key[l], l, width, k);
-            for (uint32_t l = 0; l < width; ++l)
-                word[l] |= (uint64_t)ag_lane_cand(D[l], D[l + 1u < width ? l + 1u : l], (mask[l] >> j) & 1u, nd[l], nd[l > 0 ? l - 1u : l], l, k) << (4u * j);
-            for (uint32_t l = 0; l < width; ++l) D[l] = nd[l];
-        }
-        for (uint32_t l = 0; l < width; ++l) cells[(i0 / kVfStep) * width + l] = word[l];
-    }
-    uint32_t m = D[0], rank = kAgNoEnd;
-    for (uint32_t l = 1; l < width; ++l) m = D[l] < m ? D[l] : m;
-    for (uint32_t l = 0; l < width; ++l) { const uint32_t q = ag_end_rank(D[l], m, l, k); rank = q < rank ? q : rank; }
-    return ag_rank_lane(rank, k);
 }
 
 #if !defined(__HIPCC__)
@@ -239,7 +197,8 @@ inline AgAlignment ag_job_lanes(const char* r, uint64_t len, bool fwd, const cha
     } else {
         const uint32_t width = vg_width(k);
         std::vector<uint64_t> cells(width * ag_steps(len));
-        const uint32_t lane_end = ag_forward_group(r, len, fwd, t, tlen, pos, k, width, cells.data());
+        uint32_t lane_end = 0;
+        vg_band_group(r, len, fwd, t, tlen, pos, k, width, 0, cells.data(), &lane_end);
         auto fetch = [&](uint64_t q, uint32_t l) { return cells[q * width + l]; };
         w = ag_walk(len, pos, tlen, k, lane_end, fetch, nullptr, 0, 0);
         out.ops.assign(ag_n_ops(w), 0xFFFFFFFFu);
@@ -257,36 +216,26 @@ inline uint64_t ag_serial_align(const char* tseq, const uint64_t* tseq_off, cons
                                 const char* seq2, const uint64_t* off2, uint32_t n_reads, const sfgpu_hit* hits, const uint32_t* hit_off, uint32_t k,
                                 bool lanes, std::vector<int32_t>* pos, std::vector<uint32_t>* nm, std::vector<uint64_t>* op_off, std::vector<uint32_t>* ops,
                                 std::vector<uint64_t>* extra, sfgpu_align_gstats* stats) {
-    const uint64_t n = n_reads ? hit_off[n_reads] : 0;
-    for (uint64_t i = 0; i < n; ++i) if (hits[i].tid >= M) return i + 1;
+    const VfBatch b{tseq, tseq_off, tlen, M, seq1, off1, seq2, off2, n_reads, hits, hit_off};
+    if (const uint64_t bad = vf_bad_tid(b)) return bad;
+    const uint64_t n = b.n_rec();
     *stats = sfgpu_align_gstats{};
-    pos->assign(2 * n, 0); nm->assign(2 * n, 0u); op_off->assign(1, 0ull); ops->clear();
+    pos->assign(2 * n, 0); nm->assign(2 * n, 0u); ops->clear();
     if (extra) extra->assign(6 * n, 0ull);
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        for (uint32_t i = hit_off[r]; i < hit_off[r + 1]; ++i) {
-            const sfgpu_hit& h = hits[i];
-            for (uint32_t j = 0; j < 2u; ++j) {
-                if (j < vf_n_jobs(h)) {
-                    const VfJob jb = vf_job(h, j);
-                    const char* m = (jb.mate ? seq2 : seq1) + (jb.mate ? off2 : off1)[r];
-                    const uint64_t len = (jb.mate ? off2 : off1)[r + 1] - (jb.mate ? off2 : off1)[r];
-                    // each text on its own, exactly as long as it is: a sanitizer sees every byte read outside it
-                    const std::vector<char> mate(m, m + len), tx(tseq + tseq_off[h.tid], tseq + tseq_off[h.tid] + tlen[h.tid]);
-                    const VfCount c = vf_job_serial(mate.data(), len, jb.fwd, tx.data(), tlen[h.tid], jb.pos);
-                    const uint64_t ungapped = c.mism + c.over;
-                    const AgAlignment a = lanes ? ag_job_lanes(mate.data(), len, jb.fwd, tx.data(), tlen[h.tid], jb.pos, k, ungapped)
-                                                : ag_job_serial(mate.data(), len, jb.fwd, tx.data(), tlen[h.tid], jb.pos, k);
-                    const uint64_t s = 2ull * i + j;
-                    (*pos)[s] = (int32_t)a.x0; (*nm)[s] = (uint32_t)a.nm;
-                    ops->insert(ops->end(), a.ops.begin(), a.ops.end());
-                    if (extra) { (*extra)[3 * s] = a.clipped; (*extra)[3 * s + 1] = a.trimmed_d; (*extra)[3 * s + 2] = a.edits; }
-                    ++stats->jobs; stats->jobs_traced += ungapped > 0; stats->unalignable += a.ops.empty(); stats->sum_nm += a.nm;
-                    if (ungapped > 0) stats->scratch_bytes += ag_scratch_bytes(len, vg_width(k));
-                }
-                op_off->push_back(ops->size());
-            }
-        }
-    }
+    std::vector<uint64_t> words(2 * n, 0ull);                        // operations per slot
+    vf_each_job(b, [&](uint32_t, uint32_t i, uint32_t j, const char* mate, uint64_t len, const char* tx, uint64_t tl, bool fwd, int64_t p) {
+        const VfCount c = vf_job_serial(mate, len, fwd, tx, tl, p);
+        const uint64_t ungapped = c.mism + c.over;
+        const AgAlignment a = lanes ? ag_job_lanes(mate, len, fwd, tx, tl, p, k, ungapped) : ag_job_serial(mate, len, fwd, tx, tl, p, k);
+        const uint64_t s = 2ull * i + j;
+        (*pos)[s] = (int32_t)a.x0; (*nm)[s] = (uint32_t)a.nm; words[s] = a.ops.size();
+        ops->insert(ops->end(), a.ops.begin(), a.ops.end());
+        if (extra) { (*extra)[3 * s] = a.clipped; (*extra)[3 * s + 1] = a.trimmed_d; (*extra)[3 * s + 2] = a.edits; }
+        ++stats->jobs; stats->jobs_traced += ungapped > 0; stats->unalignable += a.ops.empty(); stats->sum_nm += a.nm;
+        if (ungapped > 0) stats->scratch_bytes += ag_scratch_bytes(len, vg_width(k));
+    });
+    op_off->assign(1, 0ull);
+    for (uint64_t s = 0; s < 2 * n; ++s) op_off->push_back(op_off->back() + words[s]);
     stats->words = ops->size();
     return 0;
 }

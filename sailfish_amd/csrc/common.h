@@ -83,6 +83,10 @@ struct DevBuf {
     }
 };
 
+// waits for the stream when it goes out of scope.  Declare it AFTER the call's DevBufs: an early return then waits for the kernels
+// before any scratch block goes back to the pool
+struct StreamSyncOnExit { hipStream_t s; ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); } };
+
 // What a file-facing call (eqtext.hip, readtext.hip, textchunks.h, ...) borrows for its duration: streams, events and pinned host
 // blocks.  None of them may go back while a copy can still touch a pinned block, so the scope waits for every stream before it
 // gives anything back.  The same holds for the call's device scratch, and that cannot be read off the type: declare the scope

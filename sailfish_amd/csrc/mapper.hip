@@ -451,9 +451,6 @@ __global__ void k_narrow_off(uint64_t n, const uint64_t* __restrict__ in, uint32
 
 using namespace sfgpu;
 
-// waits for the stream when it goes out of scope
-struct StreamSyncOnExit { hipStream_t s; ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); } };
-
 constexpr uint32_t kDefaultSeedLen = 19;
 
 extern "C" {

@@ -196,48 +196,77 @@ VF_HD VfRecord vf_record(const sfgpu_hit& h, const VfCount* job /* [vf_n_jobs] *
 }
 
 #if !defined(__HIPCC__)
+// ---- a batch on the host: what the serial passes of this header, verifygfmt.h and aligngfmt.h walk -------------------------------
+struct VfBatch {
+    const char* tseq; const uint64_t* tseq_off; const uint32_t* tlen; uint64_t M;
+    const char* seq1; const uint64_t* off1; const char* seq2; const uint64_t* off2;
+    uint32_t n_reads; const sfgpu_hit* hits; const uint32_t* hit_off;
+    uint64_t n_rec() const { return n_reads ? hit_off[n_reads] : 0; }
+};
+// 1 + the lowest record with tid >= M, or 0
+inline uint64_t vf_bad_tid(const VfBatch& b) {
+    for (uint64_t i = 0; i < b.n_rec(); ++i) if (b.hits[i].tid >= b.M) return i + 1;
+    return 0;
+}
+// every job of the batch in order: fn(read, record, job index, mate, len, transcript, tlen, fwd, pos).  Each text is handed over on
+// its own, in a block of exactly its length: a sanitizer sees every byte read outside it
+template <typename Fn>
+inline void vf_each_job(const VfBatch& b, Fn&& fn) {
+    for (uint32_t r = 0; r < b.n_reads; ++r)
+        for (uint32_t i = b.hit_off[r]; i < b.hit_off[r + 1]; ++i) {
+            const sfgpu_hit& h = b.hits[i];
+            for (uint32_t j = 0; j < vf_n_jobs(h); ++j) {
+                const VfJob jb = vf_job(h, j);
+                const uint64_t* off = jb.mate ? b.off2 : b.off1;
+                const char* m = (jb.mate ? b.seq2 : b.seq1) + off[r];
+                const std::vector<char> mate(m, m + (off[r + 1] - off[r])), tx(b.tseq + b.tseq_off[h.tid], b.tseq + b.tseq_off[h.tid] + b.tlen[h.tid]);
+                fn(r, i, j, mate.data(), (uint64_t)mate.size(), tx.data(), (uint64_t)tx.size(), jb.fwd, (int64_t)jb.pos);
+            }
+        }
+}
+// PASS, BEST, ORDER and the stats both verification passes share, over the batch's records as scored (rec[i]: VfRecord or verifygfmt.h's
+// VgRecord); kept(record, stats) adds what a survivor means to the pass's own stats
+template <typename Record, typename Score, typename Stats, typename Kept>
+inline void vf_select(const VfBatch& b, const std::vector<Record>& rec, bool keep_best, std::vector<sfgpu_hit>* out_hits, std::vector<uint32_t>* out_off,
+                      std::vector<Score>* out_scores, Stats* stats, Kept&& kept) {
+    *stats = Stats{};
+    out_hits->clear(); out_scores->clear(); out_off->assign(1, 0u);
+    stats->records_in = b.n_rec();
+    for (uint32_t r = 0; r < b.n_reads; ++r) {
+        uint64_t best = ~0ull;
+        for (uint32_t i = b.hit_off[r]; i < b.hit_off[r + 1]; ++i) if (rec[i].pass && rec[i].cost < best) best = rec[i].cost;
+        const size_t before = out_hits->size();
+        for (uint32_t i = b.hit_off[r]; i < b.hit_off[r + 1]; ++i) {
+            const Record& v = rec[i];
+            if (!v.pass) { ++stats->failed_identity; continue; }
+            if (keep_best && v.cost != best) { ++stats->dropped_not_best; continue; }
+            out_hits->push_back(b.hits[i]); out_scores->push_back(v.score);
+            kept(v, stats);
+        }
+        stats->reads_in += b.hit_off[r + 1] > b.hit_off[r];
+        stats->reads_out += out_hits->size() > before;
+        out_off->push_back((uint32_t)out_hits->size());
+    }
+    stats->records_out = out_hits->size();
+}
+
 // the whole pass, serially (windows = false: byte by byte; true: as a group of `lanes` lanes counts).  -> 0, or 1 + the lowest record
 // with tid >= M (nothing is emitted then)
 inline uint64_t vf_serial_verify(const char* tseq, const uint64_t* tseq_off, const uint32_t* tlen, uint64_t M, const char* seq1, const uint64_t* off1,
                                  const char* seq2, const uint64_t* off2, uint32_t n_reads, const sfgpu_hit* hits, const uint32_t* hit_off,
                                  uint32_t permille, bool keep_best, bool windows, uint32_t lanes, std::vector<sfgpu_hit>* out_hits,
                                  std::vector<uint32_t>* out_off, std::vector<sfgpu_hit_score>* out_scores, sfgpu_verify_stats* stats) {
-    const uint64_t n = n_reads ? hit_off[n_reads] : 0;
-    for (uint64_t i = 0; i < n; ++i) if (hits[i].tid >= M) return i + 1;
-    *stats = sfgpu_verify_stats{};
-    out_hits->clear(); out_scores->clear(); out_off->assign(1, 0u);
-    stats->records_in = n;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        std::vector<VfRecord> rec;
-        uint64_t best = ~0ull;
-        for (uint32_t i = hit_off[r]; i < hit_off[r + 1]; ++i) {
-            const sfgpu_hit& h = hits[i];
-            VfCount job[2] = {{0, 0}, {0, 0}}; uint64_t len[2] = {0, 0};
-            for (uint32_t j = 0; j < vf_n_jobs(h); ++j) {
-                const VfJob jb = vf_job(h, j);
-                const char* m = (jb.mate ? seq2 : seq1) + (jb.mate ? off2 : off1)[r];
-                len[j] = (jb.mate ? off2 : off1)[r + 1] - (jb.mate ? off2 : off1)[r];
-                // each text on its own, exactly as long as it is: a sanitizer sees every byte read outside it
-                const std::vector<char> mate(m, m + len[j]), tx(tseq + tseq_off[h.tid], tseq + tseq_off[h.tid] + tlen[h.tid]);
-                job[j] = windows ? vf_job_windows(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos, lanes)
-                                 : vf_job_serial(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos);
-            }
-            rec.push_back(vf_record(h, job, len, permille));
-            if (rec.back().pass && rec.back().cost < best) best = rec.back().cost;
-        }
-        uint32_t kept = 0;
-        for (uint32_t i = hit_off[r]; i < hit_off[r + 1]; ++i) {
-            const VfRecord& v = rec[i - hit_off[r]];
-            if (!v.pass) { ++stats->failed_identity; continue; }
-            if (keep_best && v.cost != best) { ++stats->dropped_not_best; continue; }
-            out_hits->push_back(hits[i]); out_scores->push_back(v.score); ++kept;
-            stats->sum_mism += v.mism;
-        }
-        stats->reads_in += hit_off[r + 1] > hit_off[r];
-        stats->reads_out += kept > 0;
-        out_off->push_back((uint32_t)out_hits->size());
-    }
-    stats->records_out = out_hits->size();
+    const VfBatch b{tseq, tseq_off, tlen, M, seq1, off1, seq2, off2, n_reads, hits, hit_off};
+    if (const uint64_t bad = vf_bad_tid(b)) return bad;
+    std::vector<VfRecord> rec(b.n_rec());
+    VfCount job[2]; uint64_t len[2];
+    vf_each_job(b, [&](uint32_t, uint32_t i, uint32_t j, const char* mate, uint64_t n, const char* tx, uint64_t tl, bool fwd, int64_t pos) {
+        if (j == 0) { job[0] = job[1] = VfCount{0, 0}; len[0] = len[1] = 0; }
+        len[j] = n;
+        job[j] = windows ? vf_job_windows(mate, n, fwd, tx, tl, pos, lanes) : vf_job_serial(mate, n, fwd, tx, tl, pos);
+        if (j + 1u == vf_n_jobs(b.hits[i])) rec[i] = vf_record(b.hits[i], job, len, permille);
+    });
+    vf_select(b, rec, keep_best, out_hits, out_off, out_scores, stats, [](const VfRecord& v, sfgpu_verify_stats* st) { st->sum_mism += v.mism; });
     return 0;
 }
 #endif

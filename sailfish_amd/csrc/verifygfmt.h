@@ -1,6 +1,6 @@
 // verifygfmt.h -- gapped hit verification: a job's banded edit distance, stated once.  Plain C++, host and device.  Jobs, base codes,
-// orientation and the record -> jobs mapping are verifyfmt.h's (vf_job, vf_code, vf_oriented); verify_gapped.hip runs the lane
-// functions below inside its kernel, tests/verifyg_harness.cpp runs them alone (vg_serial_verify), and hits.gapped_edits_host /
+// orientation and the record -> jobs mapping are verifyfmt.h's (vf_job, vf_code, vf_oriented); hitgroup.h runs the lane functions
+// below inside the kernels of verify.hip and align_gapped.hip (hit_band_dev), tests/verifyg_harness.cpp runs them alone (vg_serial_verify), and hits.gapped_edits_host /
 // hits.verify_hits_gapped_host are the Python statement both are judged by.
 //
 // A job of len oriented bases a[0 .. len) at recorded position pos on a transcript of tlen bases, band k = max_indel (1 .. 15):
@@ -24,8 +24,9 @@
 // exchange), vg_lane_v, then an inclusive prefix minimum of V + (width - l) over the lanes (log2 width exchanges of vg_scan_step).
 // Every kVfStep rows a lane refills its transcript window on its own diagonal and the mate's window, classifies the sixteen pairs at
 // once (vg_submask) and the group takes the band's minimum: row minima never fall, so a job whose minimum exceeds vg_max_edits has
-// failed (kVgFail) and stops.  vg_job_group runs these functions for all lanes of a group in lockstep on the host.  The cells are 32
-// bits: mates shorter than kVgInf bases.
+// failed (kVgFail) and stops.  vg_band_group runs these functions for all lanes of a group in lockstep on the host -- the ONE host
+// statement of the band's row, for this pass and, with `cells`, for aligngfmt.h's forward pass.  The cells are 32 bits: mates shorter
+// than kVgInf bases.
 #pragma once
 #include "verifyfmt.h"
 
@@ -85,14 +86,34 @@ VF_HD uint32_t vg_key(uint32_t v, uint32_t lane, uint32_t width) { return v + (w
 VF_HD uint32_t vg_scan_step(uint32_t key, uint32_t below, uint32_t lane, uint32_t o) { return (lane >= o && below < key) ? below : key; }
 VF_HD uint32_t vg_lane_d(uint32_t key, uint32_t lane, uint32_t width, uint32_t k) { return lane <= 2u * k ? key - (width - lane) : kVgInf; }
 
-// a group of `width` lanes in lockstep on the host -> the job's edits, or kVgFail once they are known to exceed max_edits
-VF_HD uint64_t vg_job_group(const char* r, uint64_t len, bool fwd, const char* t, uint64_t tlen, int64_t pos, uint32_t k, uint32_t width, uint64_t max_edits) {
+// aligngfmt.h's view of a row (its CANDIDATES and END), here because the one band function below stores it: the 4 bits of this
+// lane's cell -- d_prev = its D[i-1], up = the next lane's D[i-1], d_new = its D[i], below = the lane before's D[i]
+constexpr uint32_t kAgDiag = 1u, kAgIns = 2u, kAgDel = 4u;                  // candidate bits of a cell; bit 3 is sub on its diagonal
+constexpr uint32_t kAgNoEnd = 0xFFFFu;
+VF_HD uint32_t ag_lane_cand(uint32_t d_prev, uint32_t up, uint32_t sub, uint32_t d_new, uint32_t below, uint32_t lane, uint32_t k) {
+    if (lane > 2u * k) return 0u;
+    return (d_prev + sub == d_new ? kAgDiag : 0u) | ((lane < 2u * k && up + 1u == d_new) ? kAgIns : 0u) |
+           ((lane > 0u && below + 1u == d_new) ? kAgDel : 0u) | sub << 3;
+}
+// END: the least rank over the lanes names the end diagonal
+VF_HD uint32_t ag_end_rank(uint32_t d_last, uint32_t edits, uint32_t lane, uint32_t k) {
+    if (lane > 2u * k || d_last != edits) return kAgNoEnd;
+    return lane >= k ? 2u * (lane - k) + (lane > k ? 1u : 0u) : 2u * (k - lane);
+}
+VF_HD uint32_t ag_rank_lane(uint32_t rank, uint32_t k) { return (rank & 1u) ? k + (rank >> 1) : k - (rank >> 1); }
+
+// a group of `width` lanes in lockstep on the host: the forward pass of one job.  cells == nullptr -> the job's edits, or kVgFail
+// once they are known to exceed max_edits.  With cells (width words a step of kVfStep rows) every row's candidate bits are stored,
+// the pass never stops early, and *lane_end is the END lane.
+VF_HD uint64_t vg_band_group(const char* r, uint64_t len, bool fwd, const char* t, uint64_t tlen, int64_t pos, uint32_t k, uint32_t width, uint64_t max_edits,
+                             uint64_t* cells, uint32_t* lane_end) {
     uint32_t D[kVgMaxWidth], key[kVgMaxWidth], nxt[kVgMaxWidth], mask[kVgMaxWidth];
+    uint64_t word[kVgMaxWidth];
     for (uint32_t l = 0; l < width; ++l) D[l] = vg_lane_start(l, k);
     uint32_t m = 0;
     for (uint64_t i0 = 0; i0 < len; i0 += kVfStep) {
         const VfWin mate = vf_mate_window(r, (int64_t)len, fwd, (int64_t)i0);
-        for (uint32_t l = 0; l < width; ++l) mask[l] = vg_lane_submask(mate, t, tlen, pos, i0, l, k, fwd);
+        for (uint32_t l = 0; l < width; ++l) { mask[l] = vg_lane_submask(mate, t, tlen, pos, i0, l, k, fwd); word[l] = 0; }
         const uint32_t n = len - i0 < kVfStep ? (uint32_t)(len - i0) : kVfStep;
         for (uint32_t j = 0; j < n; ++j) {
             for (uint32_t l = 0; l < width; ++l) key[l] = vg_key(vg_lane_v(D[l], D[l + 1u < width ? l + 1u : l], (mask[l] >> j) & 1u), l, width);
@@ -100,11 +121,20 @@ VF_HD uint64_t vg_job_group(const char* r, uint64_t len, bool fwd, const char* t
                 for (uint32_t l = 0; l < width; ++l) nxt[l] = vg_scan_step(key[l], key[l >= o ? l - o : l], l, o);
                 for (uint32_t l = 0; l < width; ++l) key[l] = nxt[l];
             }
-            for (uint32_t l = 0; l < width; ++l) D[l] = vg_lane_d(key[l], l, width, k);
+            for (uint32_t l = 0; l < width; ++l) nxt[l] = vg_lane_d(key[l], l, width, k);
+            for (uint32_t l = 0; cells && l < width; ++l)
+                word[l] |= (uint64_t)ag_lane_cand(D[l], D[l + 1u < width ? l + 1u : l], (mask[l] >> j) & 1u, nxt[l], nxt[l > 0 ? l - 1u : l], l, k) << (4u * j);
+            for (uint32_t l = 0; l < width; ++l) D[l] = nxt[l];
         }
+        for (uint32_t l = 0; cells && l < width; ++l) cells[(i0 / kVfStep) * width + l] = word[l];
         m = D[0];
         for (uint32_t l = 1; l < width; ++l) m = D[l] < m ? D[l] : m;
-        if (m > max_edits) return kVgFail;
+        if (!cells && m > max_edits) return kVgFail;
+    }
+    if (cells) {
+        uint32_t rank = kAgNoEnd;
+        for (uint32_t l = 0; l < width; ++l) { const uint32_t q = ag_end_rank(D[l], m, l, k); rank = q < rank ? q : rank; }
+        *lane_end = ag_rank_lane(rank, k);
     }
     return m;
 }
@@ -135,46 +165,22 @@ inline uint64_t vg_serial_verify(const char* tseq, const uint64_t* tseq_off, con
                                  const char* seq2, const uint64_t* off2, uint32_t n_reads, const sfgpu_hit* hits, const uint32_t* hit_off,
                                  uint32_t permille, bool keep_best, uint32_t k, bool lanes, std::vector<sfgpu_hit>* out_hits,
                                  std::vector<uint32_t>* out_off, std::vector<sfgpu_hit_gscore>* out_scores, sfgpu_verify_gstats* stats) {
-    const uint64_t n = n_reads ? hit_off[n_reads] : 0;
-    for (uint64_t i = 0; i < n; ++i) if (hits[i].tid >= M) return i + 1;
-    *stats = sfgpu_verify_gstats{};
-    out_hits->clear(); out_scores->clear(); out_off->assign(1, 0u);
-    stats->records_in = n;
-    for (uint32_t r = 0; r < n_reads; ++r) {
-        std::vector<VgRecord> rec;
-        uint64_t best = ~0ull;
-        for (uint32_t i = hit_off[r]; i < hit_off[r + 1]; ++i) {
-            const sfgpu_hit& h = hits[i];
-            VgJob job[2] = {{0, 0, true}, {0, 0, true}}; uint64_t len[2] = {0, 0};
-            for (uint32_t j = 0; j < vf_n_jobs(h); ++j) {
-                const VfJob jb = vf_job(h, j);
-                const char* m = (jb.mate ? seq2 : seq1) + (jb.mate ? off2 : off1)[r];
-                len[j] = (jb.mate ? off2 : off1)[r + 1] - (jb.mate ? off2 : off1)[r];
-                // each text on its own, exactly as long as it is: a sanitizer sees every byte read outside it
-                const std::vector<char> mate(m, m + len[j]), tx(tseq + tseq_off[h.tid], tseq + tseq_off[h.tid] + tlen[h.tid]);
-                const VfCount c = lanes ? vf_job_windows(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos, 16)
-                                        : vf_job_serial(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos);
-                job[j].ungapped = c.mism + c.over;
-                job[j].ungapped_pass = vf_passes(len[j], c.mism, c.over, permille);
-                job[j].edits = lanes ? vg_job_group(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos, k, vg_width(k), vg_max_edits(len[j], permille))
-                                     : vg_job_serial(mate.data(), len[j], jb.fwd, tx.data(), tlen[h.tid], jb.pos, k);
-            }
-            rec.push_back(vg_record(h, job, len, permille));
-            if (rec.back().pass && rec.back().cost < best) best = rec.back().cost;
-        }
-        uint32_t kept = 0;
-        for (uint32_t i = hit_off[r]; i < hit_off[r + 1]; ++i) {
-            const VgRecord& v = rec[i - hit_off[r]];
-            if (!v.pass) { ++stats->failed_identity; continue; }
-            if (keep_best && v.cost != best) { ++stats->dropped_not_best; continue; }
-            out_hits->push_back(hits[i]); out_scores->push_back(v.score); ++kept;
-            stats->sum_edits += v.cost; stats->rescued += v.rescued;
-        }
-        stats->reads_in += hit_off[r + 1] > hit_off[r];
-        stats->reads_out += kept > 0;
-        out_off->push_back((uint32_t)out_hits->size());
-    }
-    stats->records_out = out_hits->size();
+    const VfBatch b{tseq, tseq_off, tlen, M, seq1, off1, seq2, off2, n_reads, hits, hit_off};
+    if (const uint64_t bad = vf_bad_tid(b)) return bad;
+    std::vector<VgRecord> rec(b.n_rec());
+    VgJob job[2]; uint64_t len[2];
+    vf_each_job(b, [&](uint32_t, uint32_t i, uint32_t j, const char* mate, uint64_t n, const char* tx, uint64_t tl, bool fwd, int64_t pos) {
+        if (j == 0) { job[0] = job[1] = VgJob{0, 0, true}; len[0] = len[1] = 0; }
+        len[j] = n;
+        const VfCount c = lanes ? vf_job_windows(mate, n, fwd, tx, tl, pos, 16) : vf_job_serial(mate, n, fwd, tx, tl, pos);
+        job[j].ungapped = c.mism + c.over;
+        job[j].ungapped_pass = vf_passes(n, c.mism, c.over, permille);
+        job[j].edits = lanes ? vg_band_group(mate, n, fwd, tx, tl, pos, k, vg_width(k), vg_max_edits(n, permille), nullptr, nullptr)
+                             : vg_job_serial(mate, n, fwd, tx, tl, pos, k);
+        if (j + 1u == vf_n_jobs(b.hits[i])) rec[i] = vg_record(b.hits[i], job, len, permille);
+    });
+    vf_select(b, rec, keep_best, out_hits, out_off, out_scores, stats,
+              [](const VgRecord& v, sfgpu_verify_gstats* st) { st->sum_edits += v.cost; st->rescued += v.rescued; });
     return 0;
 }
 #endif

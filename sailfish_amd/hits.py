@@ -138,6 +138,53 @@ def _permille(min_identity):
     return p
 
 
+def _oriented_codes(read, fwd):
+    """a mate's oriented base codes: code(r[j]) forward, 3 - code(r[len - 1 - j]) reverse, 4 staying 4 on either strand"""
+    c = _BASE_CODE[np.frombuffer(read, np.uint8)]
+    return c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
+
+
+def _record_jobs(h, r, reads1, reads2):
+    """the jobs of record h of read r: (mate's bytes, forward?, pos) each"""
+    st = int(h["mate_status"])
+    jobs = [(reads2[r] if st == 2 else reads1[r], bool(h["fwd"]), int(h["pos"]))]
+    if st == 3:
+        jobs.append((reads2[r], bool(h["mate_fwd"]), int(h["mate_pos"])))
+    return jobs
+
+
+def _score4(per_job):
+    """a survivor's score: two fields a job, saturating at 65 535, the mate's 0 where the record has one job"""
+    flat = [min(v, 65535) for pair in per_job for v in pair] + [0, 0]
+    return tuple(flat[:4])
+
+
+def _select_survivors(hits, off, record, keep_best, stat_names, score_dtype):
+    """PASS, BEST, ORDER and the stats of both verification statements.  record(r, i) -> (ok, cost, score tuple, what a survivor adds
+    to the stats: a dict) for record i of read r.  -> (hits, offsets uint32[R + 1], scores, stats dict)"""
+    keep, scores, out_off = [], [], [0]
+    stats = dict.fromkeys(stat_names, 0)
+    stats["records_in"] = int(off[-1]) if len(off) else 0
+    for r in range(len(off) - 1):
+        recs = [(i, *record(r, i)) for i in range(off[r], off[r + 1])]
+        passing = [x for x in recs if x[1]]
+        stats["failed_identity"] += len(recs) - len(passing)
+        if keep_best and passing:
+            best = min(x[2] for x in passing)
+            stats["dropped_not_best"] += sum(x[2] != best for x in passing)
+            passing = [x for x in passing if x[2] == best]
+        for i, _, _, score, extra in passing:
+            keep.append(i)
+            scores.append(score)
+            for key, v in extra.items():
+                stats[key] += v
+        stats["reads_in"] += int(off[r + 1] > off[r])
+        stats["reads_out"] += int(bool(passing))
+        out_off.append(len(keep))
+    stats["records_out"] = len(keep)
+    return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=score_dtype), stats
+
+
 def verify_hits_host(transcripts, hits, offsets, reads1, reads2, min_identity_permille, keep_best):
     """The statement of hit verification (csrc/verifyfmt.h restated in numpy; what sfgpu_hits_verify is judged by).  transcripts,
     reads1, reads2 (or None): lists of bytes; hits: HIT_DTYPE records in CSR form over the reads (offsets[R + 1]).  A job is one mate
@@ -158,8 +205,7 @@ def verify_hits_host(transcripts, hits, offsets, reads1, reads2, min_identity_pe
     tcodes = {}
 
     def count(read, fwd, tid, pos):
-        c = _BASE_CODE[np.frombuffer(read, np.uint8)]
-        q = c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
+        q = _oriented_codes(read, fwd)
         if tid not in tcodes:
             tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
         t = tcodes[tid]
@@ -168,45 +214,13 @@ def verify_hits_host(transcripts, hits, offsets, reads1, reads2, min_identity_pe
         a, b = q[on], t[x[on]]
         return int(((a > 3) | (b > 3) | (a != b)).sum()), int(len(q) - on.sum())
 
-    keep, scores, out_off = [], [], [0]
-    stats = dict.fromkeys(VERIFY_STATS, 0)
-    stats["records_in"] = int(off[-1]) if len(off) else 0
-    for r in range(len(off) - 1):
-        recs = []
-        for i in range(off[r], off[r + 1]):
-            h = hits[i]
-            st = int(h["mate_status"])
-            jobs = [(reads2[r] if st == 2 else reads1[r], bool(h["fwd"]), h["pos"])]
-            if st == 3:
-                jobs.append((reads2[r], bool(h["mate_fwd"]), h["mate_pos"]))
-            counts = [count(rd, f, int(h["tid"]), p) for rd, f, p in jobs]
-            ok = all(1000 * (len(rd) - ov - mm) >= permille * len(rd) for (rd, _, _), (mm, ov) in zip(jobs, counts))
-            recs.append((i, ok, sum(mm + ov for mm, ov in counts), counts))
-        passing = [x for x in recs if x[1]]
-        stats["failed_identity"] += len(recs) - len(passing)
-        if keep_best and passing:
-            best = min(x[2] for x in passing)
-            stats["dropped_not_best"] += sum(x[2] != best for x in passing)
-            passing = [x for x in passing if x[2] == best]
-        for i, _, _, counts in passing:
-            keep.append(i)
-            flat = [min(v, 65535) for c in counts for v in c] + [0, 0]
-            scores.append(tuple(flat[:4]))
-            stats["sum_mism"] += sum(mm for mm, _ in counts)
-        stats["reads_in"] += int(off[r + 1] > off[r])
-        stats["reads_out"] += int(bool(passing))
-        out_off.append(len(keep))
-    stats["records_out"] = len(keep)
-    return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=SCORE_DTYPE), stats
+    def record(r, i):
+        jobs = _record_jobs(hits[i], r, reads1, reads2)
+        counts = [count(rd, f, int(hits[i]["tid"]), p) for rd, f, p in jobs]
+        ok = all(1000 * (len(rd) - ov - mm) >= permille * len(rd) for (rd, _, _), (mm, ov) in zip(jobs, counts))
+        return ok, sum(mm + ov for mm, ov in counts), _score4(counts), dict(sum_mism=sum(mm for mm, _ in counts))
 
-
-def _record_jobs(h, r, reads1, reads2):
-    """the jobs of record h of read r: (mate's bytes, forward?, pos) each"""
-    st = int(h["mate_status"])
-    jobs = [(reads2[r] if st == 2 else reads1[r], bool(h["fwd"]), int(h["pos"]))]
-    if st == 3:
-        jobs.append((reads2[r], bool(h["mate_fwd"]), int(h["mate_pos"])))
-    return jobs
+    return _select_survivors(hits, off, record, keep_best, VERIFY_STATS, SCORE_DTYPE)
 
 
 def gapped_edits_host(transcripts, hits, offsets, reads1, reads2, max_indel):
@@ -230,15 +244,11 @@ def gapped_edits_host(transcripts, hits, offsets, reads1, reads2, max_indel):
     ramp = np.arange(2 * k + 1, dtype=np.int64)
     tcodes = {}
 
-    def oriented(read, fwd):
-        c = _BASE_CODE[np.frombuffer(read, np.uint8)]
-        return c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
-
     def same_length_jobs(jobs, n):
         """jobs: (read, fwd, tid, pos) of n bases each -> (edits, ungapped), the rows in step over all of them"""
         sub = np.empty((len(jobs), n, 2 * k + 1), np.int8)
         for j, (read, fwd, tid, pos) in enumerate(jobs):
-            a = oriented(read, fwd)
+            a = _oriented_codes(read, fwd)
             if tid not in tcodes:
                 tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
             t = tcodes[tid]
@@ -293,34 +303,15 @@ def verify_hits_gapped_host(transcripts, hits, offsets, reads1, reads2, min_iden
     hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
     off = np.asarray(offsets).astype(np.int64)
     ed, ung = gapped_edits_host(transcripts, hits, offsets, reads1, reads2, k) if edits is None else edits
-    keep, scores, out_off = [], [], [0]
-    stats = dict.fromkeys(VERIFYG_STATS, 0)
-    stats["records_in"] = int(off[-1]) if len(off) else 0
-    for r in range(len(off) - 1):
-        recs = []
-        for i in range(off[r], off[r + 1]):
-            lens = [len(rd) for rd, _, _ in _record_jobs(hits[i], r, reads1, reads2)]
-            e, u = [int(v) for v in ed[i, :len(lens)]], [int(v) for v in ung[i, :len(lens)]]
-            ok = all(1000 * (n - x) >= permille * n for n, x in zip(lens, e))
-            rescued = any(1000 * (n - x) < permille * n for n, x in zip(lens, u))
-            recs.append((i, ok, sum(e), e, u, rescued))
-        passing = [x for x in recs if x[1]]
-        stats["failed_identity"] += len(recs) - len(passing)
-        if keep_best and passing:
-            best = min(x[2] for x in passing)
-            stats["dropped_not_best"] += sum(x[2] != best for x in passing)
-            passing = [x for x in passing if x[2] == best]
-        for i, _, cost, e, u, rescued in passing:
-            keep.append(i)
-            flat = [min(v, 65535) for pair in zip(e, u) for v in pair] + [0, 0]
-            scores.append(tuple(flat[:4]))
-            stats["sum_edits"] += cost
-            stats["rescued"] += int(rescued)
-        stats["reads_in"] += int(off[r + 1] > off[r])
-        stats["reads_out"] += int(bool(passing))
-        out_off.append(len(keep))
-    stats["records_out"] = len(keep)
-    return hits[np.array(keep, np.int64)] if keep else hits[:0], np.array(out_off, np.uint32), np.array(scores, dtype=GSCORE_DTYPE), stats
+
+    def record(r, i):
+        lens = [len(rd) for rd, _, _ in _record_jobs(hits[i], r, reads1, reads2)]
+        e, u = [int(v) for v in ed[i, :len(lens)]], [int(v) for v in ung[i, :len(lens)]]
+        ok = all(1000 * (n - x) >= permille * n for n, x in zip(lens, e))
+        rescued = any(1000 * (n - x) < permille * n for n, x in zip(lens, u))
+        return ok, sum(e), _score4(zip(e, u)), dict(sum_edits=sum(e), rescued=int(rescued))
+
+    return _select_survivors(hits, off, record, keep_best, VERIFYG_STATS, GSCORE_DTYPE)
 
 
 def _device_reads(reads, dev):
@@ -329,6 +320,21 @@ def _device_reads(reads, dev):
         from .mapper import pack_sequences
         reads = pack_sequences(reads)
     return reads[0].to(dev).contiguous(), reads[1].to(dev).contiguous()
+
+
+def _device_batch(index, hits, offsets, reads1, reads2):
+    """what verify_hits and align_hits hand the library: -> (device, hits, offsets, reads R, bases 1, offsets 1, bases 2 or None,
+    offsets 2 or None, records n); ValueError where the reads and the hit offsets do not cover the same reads"""
+    dev = index.device
+    d_hits, d_off = _device_hits(hits, offsets, dev)
+    R = int(d_off.numel()) - 1
+    s1, o1 = _device_reads(reads1, dev)
+    s2 = o2 = None
+    if reads2 is not None:
+        s2, o2 = _device_reads(reads2, dev)
+    if int(o1.numel()) - 1 != R or (o2 is not None and int(o2.numel()) - 1 != R):
+        raise ValueError("the reads and the hit offsets do not cover the same number of reads")
+    return dev, d_hits, d_off, R, s1, o1, s2, o2, d_hits.numel() // 24
 
 
 def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, keep_best=False, max_indel=0):
@@ -344,16 +350,7 @@ def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, 
     -> (hits, offsets, scores: uint8 device tensor of SCORE_DTYPE records, stats dict)"""
     permille = _permille(min_identity)
     k = _max_indel(max_indel)
-    dev = index.device
-    d_hits, d_off = _device_hits(hits, offsets, dev)
-    R = int(d_off.numel()) - 1
-    s1, o1 = _device_reads(reads1, dev)
-    s2 = o2 = None
-    if reads2 is not None:
-        s2, o2 = _device_reads(reads2, dev)
-    if int(o1.numel()) - 1 != R or (o2 is not None and int(o2.numel()) - 1 != R):
-        raise ValueError("the reads and the hit offsets do not cover the same number of reads")
-    n = d_hits.numel() // 24
+    dev, d_hits, d_off, R, s1, o1, s2, o2, n = _device_batch(index, hits, offsets, reads1, reads2)
     out_hits = torch.empty(max(n, 1) * 24, dtype=torch.uint8, device=dev)
     out_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
     scores = torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
@@ -466,9 +463,7 @@ def align_hits_host(transcripts, hits, offsets, reads1, reads2, max_indel):
             for j, (rd, fwd, p) in enumerate(_record_jobs(hits[i], r, reads1, reads2)):
                 key = (r, rd is not reads1[r], fwd, tid, p)
                 if key not in done:
-                    c = _BASE_CODE[np.frombuffer(rd, np.uint8)]
-                    a = c if fwd else np.where(c > 3, 4, 3 - c).astype(np.uint8)[::-1]
-                    done[key] = _align_job_host(a, tcodes[tid], p, k)
+                    done[key] = _align_job_host(_oriented_codes(rd, fwd), tcodes[tid], p, k)
                 x0, job_ops, job_nm, clipped, trimmed, edits, ungapped = done[key]
                 s = 2 * i + j
                 pos[s], nm[s], detail[s] = x0, job_nm, (clipped, trimmed, edits)
@@ -496,16 +491,7 @@ def align_hits(index, hits, offsets, reads1, reads2=None, *, max_indel, scratch_
     k = _max_indel(max_indel)
     if k < 1:
         raise ValueError("max_indel lies outside 1 .. 15")
-    dev = index.device
-    d_hits, d_off = _device_hits(hits, offsets, dev)
-    R = int(d_off.numel()) - 1
-    s1, o1 = _device_reads(reads1, dev)
-    s2 = o2 = None
-    if reads2 is not None:
-        s2, o2 = _device_reads(reads2, dev)
-    if int(o1.numel()) - 1 != R or (o2 is not None and int(o2.numel()) - 1 != R):
-        raise ValueError("the reads and the hit offsets do not cover the same number of reads")
-    n = d_hits.numel() // 24
+    dev, d_hits, d_off, R, s1, o1, s2, o2, n = _device_batch(index, hits, offsets, reads1, reads2)
     pos = torch.zeros(2 * n, dtype=torch.int32, device=dev)
     nm = torch.zeros(2 * n, dtype=torch.int32, device=dev)
     op_off = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)

@@ -1,10 +1,10 @@
 // aligng_harness.cpp -- csrc/aligngfmt.h alone, as plain C++ (g++ -Wall -Wextra -Werror): the alignment rule in plain loops
-// (ag_job_serial: the whole matrix, a list of columns, trimmed and merged) and as a group of lanes runs it (ag_forward_group into
+// (ag_job_serial: the whole matrix, a list of columns, trimmed and merged) and as a group of lanes runs it (vg_band_group into
 // scratch words, ag_walk over them twice: counting, then writing each run to its place), over whole batches.
 // tests/test_aligng_cpu.py compares both with hits.align_hits_host.  Built with -DALIGNG_HARNESS_MAIN (and
 // -fsanitize=address,undefined) it is a stand-alone program: it reads cases with their expected results from a file
 // (tests/aligng_corpus.py: blob) and runs both forms over them; every text is copied to a block of its own size first
-// (ag_serial_align), and a job's scratch and operations are blocks of exactly their size, so a byte outside any of them is a
+// (vf_each_job), and a job's scratch and operations are blocks of exactly their size, so a byte outside any of them is a
 // sanitizer report.  agh_write runs the serial writers of csrc/samwfmt.h / csrc/bamwfmt.h (samw_serial, bamw_serial) with an
 // alignment handed in, for the comparison with samfile._sam_text(alignments=) and sam_to_bam of it; the per-unit sizes the kernels
 // take are cross-checked against the serial pass on the way.
@@ -68,11 +68,7 @@ int agh_write(int bam, const void* hits, const uint32_t* hit_off, uint32_t n_rea
 }
 
 #ifdef ALIGNG_HARNESS_MAIN
-template <typename T>
-static bool take(FILE* f, std::vector<T>* v, uint64_t n) {
-    v->resize(n);
-    return n == 0 || fread(v->data(), sizeof(T), n, f) == n;
-}
+#include "hit_harness.h"
 
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: %s cases.bin\n", argv[0]); return 2; }
@@ -80,18 +76,14 @@ int main(int argc, char** argv) {
     if (!f) { perror(argv[1]); return 2; }
     uint64_t n_cases = 0, hd[9];
     while (fread(hd, 8, 9, f) == 9) {
-        const uint64_t M = hd[0], n_reads = hd[2], n_rec = hd[5], n_words = hd[7];
-        const bool paired = hd[6] != 0;
-        std::vector<char> ts, s1, s2; std::vector<uint64_t> toff, o1, o2, want_off, want_extra, want_stats; std::vector<uint32_t> tl, hoff, want_nm, want_ops;
-        std::vector<int32_t> want_pos; std::vector<sfgpu_hit> hits;
-        if (!take(f, &ts, hd[1]) || !take(f, &toff, M) || !take(f, &tl, M) || !take(f, &s1, hd[3]) || !take(f, &o1, n_reads + 1) || !take(f, &s2, hd[4]) ||
-            !take(f, &o2, paired ? n_reads + 1 : 0) || !take(f, &hits, n_rec) || !take(f, &hoff, n_reads + 1) || !take(f, &want_pos, 2 * n_rec) ||
-            !take(f, &want_nm, 2 * n_rec) || !take(f, &want_off, 2 * n_rec + 1) || !take(f, &want_ops, n_words) || !take(f, &want_extra, 6 * n_rec) ||
-            !take(f, &want_stats, 6)) { fprintf(stderr, "case %llu: short file\n", (unsigned long long)n_cases); return 2; }
+        const uint64_t n_rec = hd[5], n_words = hd[7];
+        HarnessBatch b; std::vector<uint64_t> want_off, want_extra, want_stats; std::vector<uint32_t> want_nm, want_ops; std::vector<int32_t> want_pos;
+        if (!b.read(f, hd, 6) || !take(f, &want_pos, 2 * n_rec) || !take(f, &want_nm, 2 * n_rec) || !take(f, &want_off, 2 * n_rec + 1) ||
+            !take(f, &want_ops, n_words) || !take(f, &want_extra, 6 * n_rec) || !take(f, &want_stats, 6)) { fprintf(stderr, "case %llu: short file\n", (unsigned long long)n_cases); return 2; }
         for (int lanes = 0; lanes < 2; ++lanes) {
             std::vector<int32_t> p; std::vector<uint32_t> n, o; std::vector<uint64_t> off, x; sfgpu_align_gstats st;
-            const uint64_t bad = ag_serial_align(ts.data(), toff.data(), tl.data(), M, s1.data(), o1.data(), paired ? s2.data() : nullptr, paired ? o2.data() : nullptr,
-                                                 (uint32_t)n_reads, hits.data(), hoff.data(), (uint32_t)hd[8], lanes != 0, &p, &n, &off, &o, &x, &st);
+            const uint64_t bad = ag_serial_align(b.ts.data(), b.toff.data(), b.tl.data(), b.M, b.s1.data(), b.o1.data(), b.paired ? b.s2.data() : nullptr, b.paired ? b.o2.data() : nullptr,
+                                                  (uint32_t)b.n_reads, b.hits.data(), b.hoff.data(), (uint32_t)hd[8], lanes != 0, &p, &n, &off, &o, &x, &st);
             const uint64_t got_stats[6] = {st.jobs, st.jobs_traced, st.unalignable, st.sum_nm, st.words, st.scratch_bytes};
             const bool ok = !bad && p == want_pos && n == want_nm && off == want_off && o == want_ops && x == want_extra && !memcmp(got_stats, want_stats.data(), sizeof got_stats);
             if (!ok) { fprintf(stderr, "case %llu (%s): differs from the statement\n", (unsigned long long)n_cases, lanes ? "lanes" : "serial"); return 1; }

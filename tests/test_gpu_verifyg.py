@@ -1,4 +1,4 @@
-"""Gapped hit verification on the device (csrc/verify_gapped.hip: sfgpu_hits_verify_gapped; hits.verify_hits(max_indel=);
+"""Gapped hit verification on the device (csrc/verify.hip: sfgpu_hits_verify_gapped; hits.verify_hits(max_indel=);
 QuasiIndex.map_reads(validate=); validate_mappings= / max_indel= of mapper.quantify_reads) against the Python statement
 hits.verify_hits_gapped_host: record for record, offsets, scores and stats over the shared corpus (tests/verifyg_corpus.py) for both
 group widths, the contract's errors and shapes, max_indel = 0 unchanged, and end to end."""
@@ -266,3 +266,61 @@ def test_map_reads_and_quantify_with_gapped_validation(gpu, tmp_path):
     assert rc == 0 and "rescued" not in exp0.verify_stats and "max indel" not in "".join(log)
     assert exp.verify_stats["records_out"] > exp0.verify_stats["records_out"] and exp.verify_stats["records_in"] == exp0.verify_stats["records_in"]
     assert exp.verify_stats["records_out"] - exp0.verify_stats["records_out"] == total["rescued"]
+
+
+BOUNDARY_READS = (7, 8, 9, 15, 16, 17)          # a block holds 16 reads at 16 lanes a read and 8 at 32: on, before and after its edge
+
+
+def _boundary_batch(n_reads=max(BOUNDARY_READS), seed=41):
+    """three transcripts of about 200 bases and single-end reads of 20 - 40 bases from either strand: every read's first record is its
+    true place, every second read has a second record on another transcript (it fails, but on transcript 1, a near copy of transcript
+    0, where it passes at a higher cost and goes with keep_best), and every third read lacks one base in its middle (ungapped it fails
+    at 0.9, with gaps it costs one edit).  The first n reads of the batch are a batch."""
+    from sailfish_amd import hits as H
+    rng = np.random.default_rng(seed)
+    seqs = [bytes(rng.choice(old_corpus.ACGT, n)) for n in (197, 200, 211)]
+    near = bytearray(seqs[0] + seqs[1][:3])                           # transcript 1: transcript 0 with every 13th base another one
+    near[::13] = bytes(b"CGTA"[b"ACGT".index(b)] for b in near[::13])
+    seqs[1] = bytes(near)
+    reads, recs, off = [], [], [0]
+    for r in range(n_reads):
+        tid, n = r % 3, int(rng.integers(20, 41))
+        p = int(rng.integers(0, len(seqs[tid]) - n - 1))
+        read = seqs[tid][p:p + n + 1]
+        read = read[:n // 2] + read[n // 2 + 1:] if r % 3 == 1 else read[:n]
+        fwd = r % 4 < 2
+        reads.append(read if fwd else old_corpus.revcomp(read))
+        recs.append((tid, p, 0, 0, n, 0, int(fwd), 0, 0, 0))
+        if r % 2:
+            recs.append(((tid + 1) % 3, p if tid == 0 else int(rng.integers(0, 150)), 0, 0, n, 0, int(fwd), 0, 0, 0))
+        off.append(len(recs))
+    return seqs, reads, np.array(recs, dtype=H.HIT_DTYPE), np.array(off, np.uint32)
+
+
+def test_last_group_next_to_a_block_boundary(gpu):
+    """the group that owns r == n_reads writes cnt[n_reads]: read counts that put it at the end of a block, at the start of the next
+    and beside either, for the ungapped pass and both widths of the gapped one, keep_best on and off; then the alignment of the
+    survivors.  Everything equals the statements, and the inputs hold survivors, failed records and rescued ones"""
+    import sailfish_amd as sf
+    from sailfish_amd import hits as H
+    import test_gpu_aligng as A
+    seqs, reads, recs, off = _boundary_batch()
+    idx = sf.mapper.QuasiIndex(seqs, device=gpu)
+    seen = dict(records_out=0, failed_identity=0, rescued=0, dropped_not_best=0, jobs_traced=0)
+    for n in BOUNDARY_READS:
+        rd, o = reads[:n], off[:n + 1]
+        h = recs[:o[-1]]
+        for k in (0, 3, 8):
+            for kb in (False, True):
+                want = H.verify_hits_gapped_host(seqs, h, o, rd, None, 900, kb, k) if k else H.verify_hits_host(seqs, h, o, rd, None, 900, kb)
+                gh, go, gs, gst = H.verify_hits(idx, h, o, rd, min_identity=0.9, keep_best=kb, max_indel=k)
+                _same((*_numpy(gh, go, gs, H.GSCORE_DTYPE if k else H.SCORE_DTYPE), gst), want, (n, k, kb))
+                for key in seen:
+                    seen[key] += want[3].get(key, 0)
+                if k:
+                    pos, nm, op_off, ops, ast = H.align_hits(idx, gh, go, rd, max_indel=k)
+                    want_a = H.align_hits_host(seqs, want[0], want[1], rd, None, k)
+                    A._same((*A._numpy(pos, nm, op_off, ops), ast), want_a, (n, k, kb))
+                    seen["jobs_traced"] += want_a[4]["jobs_traced"]
+    idx.close()
+    assert all(v > 0 for v in seen.values()), seen

@@ -2,7 +2,7 @@
 // at a time, and the whole pass run serially.  tests/test_verify_cpu.py compares them with hits.verify_hits_host.  Built with
 // -DVERIFY_HARNESS_MAIN (and -fsanitize=address,undefined) it is a stand-alone program: it reads cases with their expected results
 // from a file (tests/verify_corpus.py: blob) and runs both ways of counting over them; every text is copied to a block of its own
-// size first (vf_serial_verify), so a byte read outside a mate or a transcript is a sanitizer report.
+// size first (vf_each_job), so a byte read outside a mate or a transcript is a sanitizer report.
 #include "verifyfmt.h"
 
 #include <cstdio>
@@ -36,11 +36,7 @@ int64_t vfh_verify(const char* tseq, const uint64_t* tseq_off, const uint32_t* t
 }
 
 #ifdef VERIFY_HARNESS_MAIN
-template <typename T>
-static bool take(FILE* f, std::vector<T>* v, uint64_t n) {
-    v->resize(n);
-    return n == 0 || fread(v->data(), sizeof(T), n, f) == n;
-}
+#include "hit_harness.h"
 
 int main(int argc, char** argv) {
     if (argc != 2) { fprintf(stderr, "usage: %s cases.bin\n", argv[0]); return 2; }
@@ -48,17 +44,15 @@ int main(int argc, char** argv) {
     if (!f) { perror(argv[1]); return 2; }
     uint64_t n_cases = 0, hd[11];
     while (fread(hd, 8, 11, f) == 11) {
-        const uint64_t M = hd[0], n_reads = hd[2], n_rec = hd[5], n_out = hd[9];
-        const bool paired = hd[8] != 0;
-        std::vector<char> ts, s1, s2; std::vector<uint64_t> toff, o1, o2, want_stats; std::vector<uint32_t> tl, hoff, want_off;
-        std::vector<sfgpu_hit> hits, want_hits; std::vector<sfgpu_hit_score> want_scores;
-        if (!take(f, &ts, hd[1]) || !take(f, &toff, M) || !take(f, &tl, M) || !take(f, &s1, hd[3]) || !take(f, &o1, n_reads + 1) || !take(f, &s2, hd[4]) ||
-            !take(f, &o2, paired ? n_reads + 1 : 0) || !take(f, &hits, n_rec) || !take(f, &hoff, n_reads + 1) || !take(f, &want_hits, n_out) ||
-            !take(f, &want_off, n_reads + 1) || !take(f, &want_scores, n_out) || !take(f, &want_stats, 7)) { fprintf(stderr, "case %llu: short file\n", (unsigned long long)n_cases); return 2; }
+        const uint64_t n_out = hd[9];
+        HarnessBatch b; std::vector<uint64_t> want_stats; std::vector<uint32_t> want_off;
+        std::vector<sfgpu_hit> want_hits; std::vector<sfgpu_hit_score> want_scores;
+        if (!b.read(f, hd, 8) || !take(f, &want_hits, n_out) || !take(f, &want_off, b.n_reads + 1) || !take(f, &want_scores, n_out) ||
+            !take(f, &want_stats, 7)) { fprintf(stderr, "case %llu: short file\n", (unsigned long long)n_cases); return 2; }
         for (int windows = 0; windows < 2; ++windows) {
             std::vector<sfgpu_hit> h; std::vector<uint32_t> o; std::vector<sfgpu_hit_score> s; sfgpu_verify_stats st;
-            const uint64_t bad = vf_serial_verify(ts.data(), toff.data(), tl.data(), M, s1.data(), o1.data(), paired ? s2.data() : nullptr, paired ? o2.data() : nullptr,
-                                                  (uint32_t)n_reads, hits.data(), hoff.data(), (uint32_t)hd[6], hd[7] != 0, windows != 0, 16, &h, &o, &s, &st);
+            const uint64_t bad = vf_serial_verify(b.ts.data(), b.toff.data(), b.tl.data(), b.M, b.s1.data(), b.o1.data(), b.paired ? b.s2.data() : nullptr, b.paired ? b.o2.data() : nullptr,
+                                                  (uint32_t)b.n_reads, b.hits.data(), b.hoff.data(), (uint32_t)hd[6], hd[7] != 0, windows != 0, 16, &h, &o, &s, &st);
             const uint64_t got_stats[7] = {st.records_in, st.records_out, st.reads_in, st.reads_out, st.failed_identity, st.dropped_not_best, st.sum_mism};
             const bool ok = !bad && h.size() == n_out && o == want_off && (n_out == 0 || (!memcmp(h.data(), want_hits.data(), n_out * sizeof(sfgpu_hit)) &&
                             !memcmp(s.data(), want_scores.data(), n_out * sizeof(sfgpu_hit_score)))) && !memcmp(got_stats, want_stats.data(), sizeof got_stats);

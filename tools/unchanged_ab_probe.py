@@ -4,7 +4,8 @@
    pairs of 2 x 100 bases, 0 .. 3 records each, 30 000 transcript names): host wall time of open + write + close into memory
    (io.BytesIO), after torch.cuda.synchronize(), and the formatter's device time from the writer's stats (`ms_format`);
  - sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (--pairs, default 2 M; 80 000 transcripts; 2 % substitutions, an
-   indel of 1 - 3 bases in 5 % of the mates; max_indel 3, min identity 0.9): host wall time around the call, synchronised.
+   indel of 1 - 3 bases in 5 % of the mates; max_indel 3, min identity 0.9): host wall time around the call, synchronised;
+ - on that same batch, sfgpu_hits_verify (0.9), and sfgpu_hits_align_gapped (max_indel 3) on the gapped pass's survivors.
 
 Every figure is the median of --repeats (default 7) runs after one warm-up run; all runs are kept.  --root names the tree whose
 `sailfish_amd` is measured (built there beforehand; default: the tree this file is in), so that the same driver measures a checkout
@@ -27,8 +28,8 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 WHAT = ("parent / new / parent in fresh processes on one device, one call of tools/unchanged_ab_probe.py a leg: the device writers on the batch of "
         "tools/samwrite_probe.py (100 000 pairs; wall ms of SamDeviceWriter open + write + close into memory, and the formatter's device ms) and "
-        "sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (2 % substitutions, an indel in 5 % of the mates, max_indel 3); medians of "
-        "`repeats` runs after a warm-up")
+        "sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (2 % substitutions, an indel in 5 % of the mates, max_indel 3), with "
+        "sfgpu_hits_verify on that batch and sfgpu_hits_align_gapped on the gapped pass's survivors; medians of `repeats` runs after a warm-up")
 
 
 def main():
@@ -107,6 +108,32 @@ def main():
                                                _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(gst), None))
     g_ms, g_all = verify_probe.timed(gapped, a.repeats)
     leg["verify_gapped"] = dict(ms=g_ms, ms_runs=g_all, pairs=R, records=n, stats=gst.as_dict())
+    s_hits, s_off = out_hits[: n_out.value * 24].clone(), out_off.clone()     # the gapped pass's survivors
+
+    # the ungapped scoring pass on the same batch
+    uo = _lib.VerifyOpts(900, 0); ust = _lib.VerifyStats()
+
+    def ungapped():
+        _lib.check(Lb.sfgpu_hits_verify(index._h, _lib.ptr(r1), _lib.ptr(roff), _lib.ptr(r2), _lib.ptr(roff), R, _lib.ptr(h), _lib.ptr(hoff), C.byref(uo),
+                                        _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(scores), C.byref(n_out), C.byref(ust), None))
+    u_ms, u_all = verify_probe.timed(ungapped, a.repeats)
+    leg["verify"] = dict(ms=u_ms, ms_runs=u_all, pairs=R, records=n, stats=ust.as_dict())
+
+    # the alignment of the gapped pass's survivors, with exactly the room it needs
+    n_s = s_hits.numel() // 24
+    pos, nm = torch.zeros(2 * n_s, dtype=torch.int32, device=dev), torch.zeros(2 * n_s, dtype=torch.int32, device=dev)
+    op_off = torch.zeros(2 * n_s + 1, dtype=torch.int64, device=dev)
+    ao = _lib.AlignGOpts(K, 0, 0); ast = _lib.AlignGStats(); need = C.c_uint64(0)
+    al = (index._h, _lib.ptr(r1), _lib.ptr(roff), _lib.ptr(r2), _lib.ptr(roff), R, _lib.ptr(s_hits), _lib.ptr(s_off), C.byref(ao), _lib.ptr(pos), _lib.ptr(nm),
+          _lib.ptr(op_off))
+    rc = Lb.sfgpu_hits_align_gapped(*al, None, 0, C.byref(need), C.byref(ast), None)
+    assert rc in (_lib.OK, _lib.ERR_RANGE), rc
+    ops = torch.empty(max(need.value, 1), dtype=torch.int32, device=dev)
+
+    def align():
+        _lib.check(Lb.sfgpu_hits_align_gapped(*al, _lib.ptr(ops), ops.numel(), C.byref(need), C.byref(ast), None))
+    a_ms, a_all = verify_probe.timed(align, a.repeats)
+    leg["align_gapped"] = dict(ms=a_ms, ms_runs=a_all, records=n_s, stats=ast.as_dict())
     index.close()
 
     print(json.dumps(leg), flush=True)

@@ -934,7 +934,8 @@ SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);
  *      of (first id, hash) keys and a gather, nothing is hashed again.  *same_key_twice = 1 (and no output) if two
  *      different labels share first id and XXH64: fold the blocks through a builder instead (never seen).
  * Integer work throughout: the result equals the single-builder table class for class, in order.  n_owners <= 256,
- * n_parts <= 64; the h_* arrays are host arrays; calls are synchronous on `stream`. */
+ * n_parts <= 64; the h_* arrays are host arrays; calls are synchronous on `stream`.  A call refused with SFGPU_ERR_INVALID has
+ * written none of its outputs. */
 #define SFGPU_BLOCK_BYTES(c, l) ((12ull * (uint64_t)(c) + 4ull * (uint64_t)(l) + 7ull) & ~7ull)
 #define SFGPU_GATHER_BYTES(c, l) (20ull * (uint64_t)(c) + 4ull * (uint64_t)(l))
 SFGPU_API int sfgpu_eqvec_owner_sizes(const uint32_t* d_rowptr, const uint64_t* d_hashes, uint64_t n_classes, uint32_t n_owners,

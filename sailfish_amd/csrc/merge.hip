@@ -233,11 +233,11 @@ int sfgpu_eqvec_pack_by_owner(const uint32_t* d_rowptr, const uint32_t* d_ids, c
         t.cls0[d + 1] = t.cls0[d] + h_classes[d]; t.ids0[d + 1] = t.ids0[d] + h_ids[d];
         t.blk0[d + 1] = t.blk0[d] + SFGPU_BLOCK_BYTES(h_classes[d], h_ids[d]);
     }
-    for (uint32_t d = 0; d <= n_owners; ++d) h_block_off[d] = t.blk0[d];
     SF_REQUIRE(t.cls0[n_owners] == C, SFGPU_ERR_INVALID, "sfgpu_eqvec_pack_by_owner: sizes do not add up to the table");
-    if (C == 0) return SFGPU_OK;
-    SF_REQUIRE(d_rowptr && d_ids && d_counts && d_hashes && d_blocks, SFGPU_ERR_INVALID, "sfgpu_eqvec_pack_by_owner: null pointer");
+    SF_REQUIRE(C == 0 || (d_rowptr && d_ids && d_counts && d_hashes && d_blocks), SFGPU_ERR_INVALID, "sfgpu_eqvec_pack_by_owner: null pointer");
     SF_REQUIRE(C < (1ull << 32), SFGPU_ERR_RANGE, "sfgpu_eqvec_pack_by_owner: more than 2^32 classes");
+    for (uint32_t d = 0; d <= n_owners; ++d) h_block_off[d] = t.blk0[d];          // (a refused call leaves the caller's arrays as they were)
+    if (C == 0) return SFGPU_OK;
     DevBuf<uint64_t> keys_in, keys_out, ids_off; DevBuf<uint32_t> vals_in, perm, lens;
     int rc;
     if ((rc = keys_in.reserve(C, st, false)) || (rc = keys_out.reserve(C, st, false)) || (rc = vals_in.reserve(C, st, false)) ||
@@ -306,10 +306,10 @@ int sfgpu_eqvec_merge_disjoint(const void* const* d_blocks, const uint64_t* n_cl
         n += n_classes[p]; L += n_ids[p]; t.cls0[p + 1] = n;
         SF_REQUIRE(n_classes[p] == 0 || d_blocks[p], SFGPU_ERR_INVALID, "sfgpu_eqvec_merge_disjoint: null block");
     }
+    SF_REQUIRE(n == 0 || (d_ids && d_counts), SFGPU_ERR_INVALID, "sfgpu_eqvec_merge_disjoint: null output");
     if (same_key_twice) *same_key_twice = 0;
     SF_REQUIRE(n < (1ull << 32) && L < (1ull << 32), SFGPU_ERR_RANGE, "sfgpu_eqvec_merge_disjoint: the union must hold < 2^32 classes and ids");
     if (n == 0) { SF_HIP(hipMemsetAsync(d_rowptr, 0, 4, st)); SF_HIP(hipStreamSynchronize(st)); return SFGPU_OK; }
-    SF_REQUIRE(d_ids && d_counts, SFGPU_ERR_INVALID, "sfgpu_eqvec_merge_disjoint: null output");
     DevBuf<uint32_t> lens, vals_in, order, lens_sorted; DevBuf<uint64_t> scan, src_off, keys_in, keys_out, dst_off; DevBuf<unsigned int> flag;
     int rc;
     if ((rc = lens.reserve(n + 1, st, false)) || (rc = vals_in.reserve(n, st, false)) || (rc = order.reserve(n, st, false)) ||

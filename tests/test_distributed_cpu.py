@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import merge_corpus as MC
 from oracle import oracle as O
 
 
@@ -219,54 +220,30 @@ class CheckerEngine:
     def new_builder(self, expected=0):
         return _Builder()
 
-    # ---- the exchange primitives (csrc/merge.hip in the product), restated with numpy for the control-flow tests
+    # ---- the exchange primitives (csrc/merge.hip in the product): the numpy statement of tests/merge_corpus.py
     @staticmethod
     def _csr(vec):
         return (vec.rowptr.numpy().view(np.uint32).astype(np.int64), vec.ids.numpy().view(np.uint32), vec.counts.numpy().astype(np.uint64),
                 vec.hashes.numpy().view(np.uint64))
 
     def pack_by_owner(self, vec, n):
-        from sailfish_amd.distributed import block_bytes
-        rp, ids, cnt, hs = self._csr(vec)
-        owner = ((hs >> np.uint64(33)) & np.uint64(0x3FFFFFFF)) % np.uint64(n)
-        parts, sizes = [], []
-        for d in range(n):
-            sel = np.flatnonzero(owner == d)
-            lens = (rp[sel + 1] - rp[sel]).astype("<u4")
-            idl = np.concatenate([ids[rp[c]:rp[c + 1]] for c in sel]).astype("<u4") if len(sel) else np.zeros(0, "<u4")
-            blk = cnt[sel].astype("<u8").tobytes() + lens.tobytes() + idl.tobytes()
-            parts.append(blk + b"\0" * (block_bytes(len(sel), len(idl)) - len(blk)))
-            sizes.append((len(sel), len(idl)))
-        raw = b"".join(parts)
+        raw, sizes = MC.pack_by_owner(self._csr(vec), n)
         return torch.frombuffer(bytearray(raw + b"\0" * 8), dtype=torch.uint8)[:len(raw)], sizes
 
     def fold_block(self, builder, block, c, l):
-        if c == 0:
-            return
-        b = block.numpy().tobytes()
-        cnt = np.frombuffer(b[:8 * c], "<u8"); lens = np.frombuffer(b[8 * c:12 * c], "<u4"); ids = np.frombuffer(b[12 * c:12 * c + 4 * l], "<u4")
-        off = np.zeros(c + 1, np.int64); off[1:] = np.cumsum(lens)
-        builder._add(torch.from_numpy(ids.view(np.int32).copy()), torch.from_numpy(off.astype(np.uint32).view(np.int32).copy()), cnt.astype(np.int64))
+        MC.fold_block(builder.d, block.numpy().tobytes(), c, l)
 
     def export_block(self, vec):
-        rp, ids, cnt, hs = self._csr(vec)
-        raw = cnt.astype("<u8").tobytes() + hs.astype("<u8").tobytes() + np.diff(rp).astype("<u4").tobytes() + ids.astype("<u4").tobytes()
+        raw = MC.export_block(self._csr(vec))
         return torch.frombuffer(bytearray(raw + b"\0" * 8), dtype=torch.uint8)[:len(raw)]
 
     def merge_disjoint(self, blocks, sizes):
-        rows = []
-        for blk, (c, l) in zip(blocks, sizes):
-            b = blk.numpy().tobytes()
-            cnt = np.frombuffer(b[:8 * c], "<u8"); hs = np.frombuffer(b[8 * c:16 * c], "<u8"); lens = np.frombuffer(b[16 * c:20 * c], "<u4")
-            ids = np.frombuffer(b[20 * c:20 * c + 4 * l], "<u4")
-            o = np.zeros(c + 1, np.int64); o[1:] = np.cumsum(lens)
-            rows += [(int(ids[o[k]]), int(hs[k]), tuple(ids[o[k]:o[k + 1]].tolist()), int(cnt[k])) for k in range(c)]
-        rows.sort(key=lambda r: (r[0], r[1], len(r[2]), r[2]))
-        if any(a[0] == b[0] and a[1] == b[1] for a, b in zip(rows, rows[1:])):
+        t = MC.merge_disjoint([blk.numpy().tobytes() for blk in blocks], sizes)
+        if t is None:
             return None
-        rowptr = np.zeros(len(rows) + 1, np.int64); rowptr[1:] = np.cumsum([len(r[2]) for r in rows])
-        v = _Vec(rowptr, np.array([t for r in rows for t in r[2]], np.uint32), np.array([r[3] for r in rows], np.int64), sum(r[3] for r in rows))
-        v.hashes = torch.from_numpy(np.array([r[1] for r in rows], np.uint64).view(np.int64).copy())
+        rowptr, ids, cnt, hs = t
+        v = _Vec(rowptr, ids, cnt.astype(np.int64), int(cnt.sum()))
+        v.hashes = torch.from_numpy(hs.view(np.int64).copy())
         return v
 
     def gibbs_sample(self, length, mass, rowptr, ids, counts, num_mapped, n, n_chains=0, seed=1):
@@ -289,7 +266,16 @@ class CheckerEngine:
         pass
 
 
-def _worker(rank, world, port, mode, vb, out, merge_mode="auto"):
+class _NoConcatEngine(CheckerEngine):
+    """merge_disjoint always reports two labels under one (first id, hash): the driver must fold the partitions instead"""
+    refused = 0
+
+    def merge_disjoint(self, blocks, sizes):
+        self.refused += 1
+        return None
+
+
+def _worker(rank, world, port, mode, vb, out, merge_mode="auto", refuse_concat=False):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
@@ -301,14 +287,16 @@ def _worker(rank, world, port, mode, vb, out, merge_mode="auto"):
         ids, off = synth.reads_from_pool(poff, pids, R, seed=7 + 1000 * rank)       # this rank's shard
         sopt = sf.SailfishOpts(useVBOpt=vb)
         exp = sf.ReadExperiment(sf.Transcripts([str(i) for i in range(M)], ref_len.numpy().view(np.uint32), device="cpu"), sopt)
-        q = sfd.DistributedQuant(exp, sopt, group=dist.group.WORLD, em_mode=mode, engine=CheckerEngine(), poll_every=7,
+        engine = _NoConcatEngine() if refuse_concat else CheckerEngine()
+        q = sfd.DistributedQuant(exp, sopt, group=dist.group.WORLD, em_mode=mode, engine=engine, poll_every=7,
                                  merge_mode=merge_mode)
         info = q.run(ids, off)
         t = exp.transcripts()
         v = q.last_vec
         out.put((rank, info["em_mode"], info["n_classes"], info["nnz"], exp.numMappedFragments(), info["em_stats"]["iters"],
                  t.estCount.numpy().copy(), info["tpm"].numpy().copy(), ids.numpy().copy(), off.numpy().copy(),
-                 v.rowptr.numpy().view(np.uint32).copy(), v.ids.numpy().view(np.uint32).copy(), v.counts.numpy().copy()))
+                 v.rowptr.numpy().view(np.uint32).copy(), v.ids.numpy().view(np.uint32).copy(), v.counts.numpy().copy(),
+                 getattr(engine, "refused", 0)))
     finally:
         dist.destroy_process_group()
 
@@ -372,10 +360,15 @@ def _free_port():
                                                  ("replicated", False, "owner", 2), ("sharded", False, "auto", 3)])
 def test_two_rank_quant_matches_single_process(built, mode, vb, merge, world):
     """world 2 merges by all-gather; merge="owner" / world 3 reduce every class at the rank that owns its hash first"""
+    quant_matches_single_process(mode, vb, merge, world)
+
+
+def quant_matches_single_process(mode, vb, merge, world, refuse_concat=False):
+    """-> the ranks' results, after they passed the comparison with one process over all shards"""
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, mode, vb, out, merge)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, mode, vb, out, merge, refuse_concat)) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted([out.get(timeout=240) for _ in procs], key=lambda r: r[0])
@@ -403,6 +396,7 @@ def test_two_rank_quant_matches_single_process(built, mode, vb, merge, world):
         # the merged table is the single-process table, class for class, in the canonical order
         assert np.array_equal(r[10], rp.astype(np.uint32)) and np.array_equal(r[11], ii) and np.array_equal(r[12].astype(np.uint64), cc)
     assert np.array_equal(res[0][6], res[1][6])      # both ranks hold the same answer
+    return res
 
 
 def test_nnz_balanced_slices():

@@ -1187,7 +1187,9 @@ SFGPU_API int sfgpu_gibbs_sample(const sfgpu_problem* prob, const double* d_mass
  *   sfgpu_map_reads   : reads of one batch, read r = d_seq1[d_off1[r] .. d_off1[r + 1]) (bytes; any case; other letters
  *                       than ACGT never match); d_seq2 / d_off2 = the mates or NULL.  Writes d_hit_offsets[n_reads + 1]
  *                       and, if they fit hit_capacity, the records (else SFGPU_ERR_RANGE with *n_hits set: size and
- *                       call again).  The output feeds sfgpu_filter_hits directly.  Synchronous. */
+ *                       call again; d_hits = NULL with capacity 0 is the sizing call).  n_reads = 0: OK, d_hit_offsets[0] = 0, the
+ *                       reads may be NULL.  A read with a mate of more than 65 535 bases gets no records (see sfgpu_index_set_scan).
+ *                       The output feeds sfgpu_filter_hits directly.  Synchronous. */
 typedef struct sfgpu_index sfgpu_index;
 struct sfgpu_hit;
 SFGPU_API int sfgpu_index_build(sfgpu_index** out, const char* d_seq, const uint64_t* d_seq_off, const uint32_t* d_ref_len, uint64_t M,
@@ -1200,14 +1202,19 @@ SFGPU_API int sfgpu_index_destroy(sfgpu_index* idx);
 SFGPU_API int sfgpu_index_set_seeds(sfgpu_index* x, uint32_t seeds_per_strand);
 /* The mapping mode.  seed_len != 0 (the DEFAULT after sfgpu_index_build: min(19, k)): SCAN mode, modelled on RapMap's maximal
  * mappable prefixes -- the sorted k-mer table is used as a suffix array of depth k, a seed of seed_len <= k bases is a prefix
- * range of it.  A mate is walked once per strand (forward first; the reverse complement is skipped when a forward match
- * covered the whole read): window at i -> prefix range; no occurrence, more than max_occ, or a non-ACGT base -> i += 1;
+ * range of it.  A mate is walked on both strands in LOCKSTEP (one step on the forward strand, one on the reverse complement, and
+ * so on; a match that covers the whole read ends both walks, and the 8 groups are shared by the two strands in the order they are
+ * found).  A step: window at i -> prefix range; no occurrence or more than max_occ -> i += 1 (windows that hold a non-ACGT base are
+ * skipped without a step);
  * otherwise every occurrence is extended base by base on the transcripts' text (the index keeps a copy), L = the longest
  * extension, the occurrences that reach L form a group, i += L - seed_len + 1 (at most 8 groups per mate).  A (transcript,
  * strand) is positioned by the first group that holds it and gets a vote per group; with several candidates only those with
  * the most votes are kept.  A read with substitutions maps as long as seed_len clean bases remain somewhere that an indexed
- * k-mer starts in: seeds are prefix ranges of WHOLE k-mers, so a seed that begins within the last k - seed_len bases of a
- * transcript, or within k - 1 bases upstream of a non-ACGT base, is not in the index.  Mates of >= 2^24 bases are left unmapped.
+ * k-mer starts in: seeds are prefix ranges of WHOLE k-mers, so a seed that begins within the last k - 1 bases of a
+ * transcript, or within k - 1 bases upstream of a non-ACGT base, is not in the index.
+ * LENGTHS, both modes: read_len and mate_len are 16-bit fields.  A read with a mate of more than 65 535 bases gets NO records, single
+ * end or paired and whichever mate it is (an orphan record carries the other mate's length too); at exactly 65 535 bases frag_len is
+ * computed from the true lengths.  (This subsumes the scan mode's older limit of 2^24 - 1 bases.)
  * seed_len == 0: the END-SEED contract above (exact k-mers at offsets 0 and len - k, or sfgpu_index_set_seeds' S seeds) -- the
  * baseline of rounds 1-2.  8 <= seed_len <= k.  Parity with RapMap is unpinned in both modes. */
 SFGPU_API int sfgpu_index_set_scan(sfgpu_index* x, uint32_t seed_len);

@@ -7,7 +7,7 @@ therefore not RapMap but the contract of this repository's mapper (sailfish_amd/
 exact-seed scheme that yields the KIND of record the hot path consumes (the QuasiAlignment fields sfgpu_hit carries),
 checked against the ground truth the reference's bundled sample_data carries in its read names.
 
-  index   : every k-mer (k = 31) of every transcript that consists of A/C/G/T only (case folded), with its
+  index   : every k-mer (8 <= k <= 31; every entry point takes k, default 31) of every transcript that consists of A/C/G/T only (case folded), with its
             (transcript, position); occurrences of a k-mer in (transcript, position) order, at most `max_occ` kept.
   a read  : two seeds, at offsets 0 and len - k (reads shorter than k do not map), looked up on the forward strand
             (fwd = 1) and as reverse complement (fwd = 0), in the order fwd-seed0, fwd-seed1, rc-seed0, rc-seed1; the FIRST
@@ -16,7 +16,9 @@ checked against the ground truth the reference's bundled sample_data carries in 
   a pair  : every (left hit, right hit) on one transcript with opposite strands is a PAIRED_END_PAIRED record (status 3,
             fragment length = max end - min start); if there is none, the left hits (status 1) then the right hits
             (status 2) are kept as orphans.
-  single  : status 0 records."""
+  single  : status 0 records.
+  lengths : read_len / mate_len are 16-bit fields: a read with a mate of more than 65 535 bases gets no records, in either mode
+            (pair_records); this subsumes the scan mode's older "mates of >= 2^24 bases are left unmapped"."""
 import numpy as np
 
 from .oracle import HIT_DTYPE
@@ -90,25 +92,36 @@ def map_read(index, read: bytes, k=31, seeds=2):
     return sorted((t, fwd, p) for (t, fwd), p in found.items())
 
 
-def map_reads(index, reads1, reads2=None, k=31, seeds=2):
-    """-> (hits HIT_DTYPE[n], offsets uint32[R + 1])"""
+MAX_MATE = 65535                # read_len / mate_len are 16-bit fields
+
+
+def pair_records(left, right, n1, n2):
+    """the records of one read from its mates' hits (right = None: single end); n1 / n2 = the mates' lengths.
+    THE LENGTH RULE: a read with a mate of more than MAX_MATE bases gets no records, in either mode, single end or paired,
+    whichever mate it is (an orphan record would still have to carry the other mate's length in mate_len).  At exactly MAX_MATE
+    bases the fragment length is computed from the true lengths."""
+    if n1 > MAX_MATE or (right is not None and n2 > MAX_MATE):
+        return []
+    if right is None:
+        return [(t, p, 0, 0, n1, 0, f, 0, 0, 0) for t, f, p in left]
+    paired = [(t, f, p, f2, p2) for t, f, p in left for t2, f2, p2 in right if t2 == t and f2 != f]
+    if paired:
+        return [(t, p, p2, max(p + n1, p2 + n2) - min(p, p2), n1, n2, f, f2, 3, 0) for t, f, p, f2, p2 in paired]
+    return [(t, p, 0, 0, n1, n2, f, 0, 1, 0) for t, f, p in left] + [(t, p, 0, 0, n2, n1, f, 0, 2, 0) for t, f, p in right]
+
+
+def _csr(per_read):
     recs, off = [], [0]
-    for i, r1 in enumerate(reads1):
-        left = map_read(index, r1, k, seeds)
-        if reads2 is None:
-            recs += [(t, p, 0, 0, len(r1), 0, f, 0, 0, 0) for t, f, p in left]
-        else:
-            r2 = reads2[i]
-            right = map_read(index, r2, k, seeds)
-            paired = [(t, f, p, f2, p2) for t, f, p in left for t2, f2, p2 in right if t2 == t and f2 != f]
-            if paired:
-                for t, f, p, f2, p2 in paired:
-                    recs.append((t, p, p2, max(p + len(r1), p2 + len(r2)) - min(p, p2), len(r1), len(r2), f, f2, 3, 0))
-            else:
-                recs += [(t, p, 0, 0, len(r1), len(r2), f, 0, 1, 0) for t, f, p in left]
-                recs += [(t, p, 0, 0, len(r2), len(r1), f, 0, 2, 0) for t, f, p in right]
+    for r in per_read:
+        recs += r
         off.append(len(recs))
     return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
+
+
+def map_reads(index, reads1, reads2=None, k=31, seeds=2):
+    """-> (hits HIT_DTYPE[n], offsets uint32[R + 1]); `index` = build_index(transcripts, k, max_occ) with the same k"""
+    return _csr(pair_records(map_read(index, r1, k, seeds), None if reads2 is None else map_read(index, reads2[i], k, seeds),
+                             len(r1), 0 if reads2 is None else len(reads2[i])) for i, r1 in enumerate(reads1))
 
 
 # ---- the SCAN contract (round 3): RapMap-style maximal-match extension instead of two fixed end seeds ----------------
@@ -147,25 +160,29 @@ def build_scan_index(transcripts, k=31):
 
 
 def _prefix_range(table, k, prefix, s):
+    """table: the sorted list of (key, t, p), or any object with prefix_range(lo key, hi key) and slices that yield (key, t, p)"""
+    lo_key, hi_key = prefix << (2 * (k - s)), (prefix + 1) << (2 * (k - s))
+    if hasattr(table, "prefix_range"):
+        return table.prefix_range(lo_key, hi_key)
     import bisect
-    lo = bisect.bisect_left(table, (prefix << (2 * (k - s)), -1, -1))
-    hi = bisect.bisect_left(table, ((prefix + 1) << (2 * (k - s)), -1, -1))
-    return lo, hi
+    return bisect.bisect_left(table, (lo_key, -1, -1)), bisect.bisect_left(table, (hi_key, -1, -1))
 
 
-def scan_read(sindex, read: bytes, s=19, max_occ=1000):
+def scan_groups(sindex, read: bytes, s=19, max_occ=1000, max_groups=MAX_GROUPS):
+    """the walk: -> the groups (fwd, i, L, [(t, p) that reach L, in table order]) in the order they are found.  max_groups above
+    MAX_GROUPS shows what the cap cuts off (the contract is max_groups = MAX_GROUPS, shared by both strands)."""
     table, tcodes, k = sindex
     c = _codes(read)
     n = len(c)
-    if n < s:
+    if n < s or n >= 1 << 24:
         return []
     rc = (3 - c[::-1]).astype(np.uint8); rc[c[::-1] > 3] = 4
     strands = [(1, c), (0, rc)]
     pos = [0, 0]; live = [True, True]
     groups, whole = [], False
-    while (live[0] or live[1]) and not whole and len(groups) < MAX_GROUPS:
+    while (live[0] or live[1]) and not whole and len(groups) < max_groups:
         for w in (0, 1):                                   # lockstep: one lookup on the forward strand, one on the reverse complement
-            if not live[w] or whole or len(groups) >= MAX_GROUPS:
+            if not live[w] or whole or len(groups) >= max_groups:
                 continue
             fwd, q = strands[w]
             i = pos[w]
@@ -178,21 +195,27 @@ def scan_read(sindex, read: bytes, s=19, max_occ=1000):
             if hi == lo or hi - lo > max_occ:
                 i += 1
             else:
+                occ = list(table[lo:hi])
                 ext = []
-                for _, t, p in table[lo:hi]:
+                for _, t, p in occ:
                     tc = tcodes[t]
                     e = s
                     while i + e < n and p + e < len(tc) and q[i + e] < 4 and tc[p + e] == q[i + e]:
                         e += 1
                     ext.append(e)
                 L = max(ext)
-                groups.append((fwd, i, L, [(t, p) for (_, t, p), e in zip(table[lo:hi], ext) if e == L]))
+                groups.append((fwd, i, L, [(t, p) for (_, t, p), e in zip(occ, ext) if e == L]))
                 if L == n:
                     whole = True                           # the whole read matched: both walks end
                 i += L - s + 1
             if i + s > n:
                 live[w] = False
             pos[w] = i
+    return groups
+
+
+def scan_vote(groups):
+    """the vote: groups -> the mate's hits [(t, fwd, pos)], sorted"""
     found, votes = {}, {}
     for g, (fwd, i, L, occ) in enumerate(groups):
         for t, p in occ:
@@ -204,22 +227,11 @@ def scan_read(sindex, read: bytes, s=19, max_occ=1000):
     return sorted((t, fwd, p) for (t, fwd), p in found.items())
 
 
+def scan_read(sindex, read: bytes, s=19, max_occ=1000):
+    return scan_vote(scan_groups(sindex, read, s, max_occ))
+
+
 def scan_reads(sindex, reads1, reads2=None, s=19, max_occ=1000):
-    """map_reads with the scan contract -> (hits HIT_DTYPE[n], offsets uint32[R + 1])"""
-    recs, off = [], [0]
-    for i, r1 in enumerate(reads1):
-        left = scan_read(sindex, r1, s, max_occ)
-        if reads2 is None:
-            recs += [(t, p, 0, 0, len(r1), 0, f, 0, 0, 0) for t, f, p in left]
-        else:
-            r2 = reads2[i]
-            right = scan_read(sindex, r2, s, max_occ)
-            paired = [(t, f, p, f2, p2) for t, f, p in left for t2, f2, p2 in right if t2 == t and f2 != f]
-            if paired:
-                for t, f, p, f2, p2 in paired:
-                    recs.append((t, p, p2, max(p + len(r1), p2 + len(r2)) - min(p, p2), len(r1), len(r2), f, f2, 3, 0))
-            else:
-                recs += [(t, p, 0, 0, len(r1), len(r2), f, 0, 1, 0) for t, f, p in left]
-                recs += [(t, p, 0, 0, len(r2), len(r1), f, 0, 2, 0) for t, f, p in right]
-        off.append(len(recs))
-    return np.array(recs, dtype=HIT_DTYPE), np.array(off, np.uint32)
+    """map_reads with the scan contract -> (hits HIT_DTYPE[n], offsets uint32[R + 1]); k is the scan index's"""
+    return _csr(pair_records(scan_read(sindex, r1, s, max_occ), None if reads2 is None else scan_read(sindex, reads2[i], s, max_occ),
+                             len(r1), 0 if reads2 is None else len(reads2[i])) for i, r1 in enumerate(reads1))

@@ -385,6 +385,10 @@ __global__ void k_seq_extent(uint64_t M, const uint64_t* __restrict__ seq_off, c
 }
 
 // pass C / D: records per read, then the records.  Paired: mates 2r (left) and 2r + 1 (right).
+// read_len / mate_len are 16-bit fields: a read with a mate of more than kMaxMateLen bases gets NO records, in either mode and
+// whichever mate it is (an orphan record carries the other mate's length too); narrowing the length instead made a 65 566-base
+// mate a 30-base one and its fragment 65 536 short.
+constexpr uint64_t kMaxMateLen = 65535;
 template <bool FILL>
 __global__ void __launch_bounds__(kMapBlock)
 k_map_records(uint64_t n_reads, int paired, const uint64_t* __restrict__ off, const uint64_t* __restrict__ cand_off, const uint64_t* __restrict__ cand,
@@ -394,7 +398,9 @@ k_map_records(uint64_t n_reads, int paired, const uint64_t* __restrict__ off, co
     if (r == n_reads) { if (!FILL) rec_cnt[r] = 0; return; }
     const uint64_t ml = paired ? 2 * r : r;
     const uint64_t* L = cand + cand_off[ml]; const uint32_t nl = n_hits[ml];
-    const uint16_t len1 = (uint16_t)(off[ml + 1] - off[ml]);
+    const uint64_t true1 = off[ml + 1] - off[ml], true2 = paired ? off[ml + 2] - off[ml + 1] : 0ull;
+    if (true1 > kMaxMateLen || true2 > kMaxMateLen) { if (!FILL) rec_cnt[r] = 0; return; }
+    const uint16_t len1 = (uint16_t)true1;
     sfgpu_hit* out = FILL ? hits + rec_off[r] : nullptr;
     uint32_t n = 0;
     if (!paired) {
@@ -402,7 +408,7 @@ k_map_records(uint64_t n_reads, int paired, const uint64_t* __restrict__ off, co
         n = nl;
     } else {
         const uint64_t* R = cand + cand_off[ml + 1]; const uint32_t nr = n_hits[ml + 1];
-        const uint16_t len2 = (uint16_t)(off[ml + 2] - off[ml + 1]);
+        const uint16_t len2 = (uint16_t)true2;
         // every (left, right) on one transcript with opposite strands, left-major in sorted order
         for (uint32_t i = 0; i < nl; ++i) {
             const uint32_t t = cand_tid(L[i]), f = cand_fwd(L[i]);

@@ -202,7 +202,8 @@ def test_scan_contract_maps_reads_with_substitutions(built):
 def test_device_scan_mapper_matches_its_contract(gpu, seed_len, rate):
     """scan mode on the device = the restated contract, record for record: random isoform-like transcriptome (shared segments, N,
     lower case, transcripts shorter than k, ragged and short reads, reads with N), substitutions, paired and single end, several
-    seed lengths (31 = whole k-mers, 8 = shorter than the bucket prefix: the range spans buckets), a repeat beyond max_occ"""
+    seed lengths (31 = whole k-mers, 8 = the shortest; this index has 2^12 buckets, so an 8-base seed's 16-bit prefix still lies inside one
+    bucket -- a range that spans buckets needs more than 524 288 k-mers: tests/test_gpu_mapper.py, span_k20_s8), a repeat beyond max_occ"""
     import sailfish_amd as sf
     rng = np.random.default_rng(90 + seed_len)
     seqs, r1, r2 = _random_case(rng, n_reads=1500, read_len=70)

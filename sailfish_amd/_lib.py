@@ -259,6 +259,15 @@ class BiasStats(C.Structure):
                     n_corrected=self.n_corrected, n_uncorrected=self.n_uncorrected)
 
 
+# The alignment writers (sfgpu_sam_write_*, sfgpu_bamsort_collect*) take one batch: hits, hit offsets, n_reads, paired, reference
+# names and offsets, n_refs, read names and offsets, bases and offsets of either mate, read_index_base.  Behind the destination's own
+# arguments come the result and the stream; the _q entries add the qualities of either mate and `oriented`, the _a entries the
+# alignment (positions, operation offsets, operations) behind those.
+_SAMW_BATCH = [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64]
+_SAMW_OUT = [C.POINTER(SamWriteResult), _P]
+_SAMW_QUAL = [_P, _P, C.c_int]
+_SAMW_ALN = [_P, _P, _P]
+
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
     "sfgpu_has_variants": (C.c_int, []),
@@ -320,12 +329,9 @@ _SIGS = {
     "sfgpu_samc_finish": (C.c_int, [_P, C.POINTER(SamcInfo), _P]),
     "sfgpu_samc_emit": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(SamResult), _P]),
     "sfgpu_samc_close": (C.c_int, [_P]),
-    "sfgpu_sam_write_text": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
-                                       C.POINTER(SamWriteResult), _P]),
-    "sfgpu_sam_write_text_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
-                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
-    "sfgpu_sam_write_text_a": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, TEXT_SINK, _P,
-                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
+    "sfgpu_sam_write_text": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT]),
+    "sfgpu_sam_write_text_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL]),
+    "sfgpu_sam_write_text_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -335,18 +341,13 @@ _SIGS = {
     "sfgpu_bgzw_track_members": (C.c_int, [_P]),
     "sfgpu_bgzw_member_sizes": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "sfgpu_bamsort_open": (C.c_int, [C.POINTER(_P)]),
-    "sfgpu_bamsort_collect": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
-                                        C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
-    "sfgpu_bamsort_collect_a": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64,
-                                          C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
+    "sfgpu_bamsort_collect": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL]),
+    "sfgpu_bamsort_collect_a": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
     "sfgpu_bamsort_close": (C.c_int, [_P]),
-    "sfgpu_sam_write_bgzf": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
-                                       C.POINTER(SamWriteResult), _P]),
-    "sfgpu_sam_write_bgzf_q": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
-                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int]),
-    "sfgpu_sam_write_bgzf_a": (C.c_int, [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, C.c_int,
-                                       C.POINTER(SamWriteResult), _P, _P, _P, C.c_int, _P, _P, _P]),
+    "sfgpu_sam_write_bgzf": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT]),
+    "sfgpu_sam_write_bgzf_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL]),
+    "sfgpu_sam_write_bgzf_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

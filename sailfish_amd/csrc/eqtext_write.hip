@@ -17,7 +17,7 @@
 #include "common.h"
 #include "decfmt.h"
 #include "primitives.h"
-#include "textchunks.h"
+#include "texttile.h"
 
 #include <cstring>
 
@@ -104,31 +104,25 @@ k_format(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, 
          const uint64_t* __restrict__ tok_start, const uint32_t* __restrict__ tok_class, const uint64_t* __restrict__ tile_first,
          uint64_t n_tok, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
     __shared__ uint4 tile4[kBlock];
-    char* tile = reinterpret_cast<char*>(tile4);
-    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
-    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);      // (the bytes behind the end of the table)
+    const textchunks::Tile tile(tile4, first_tile, n_bytes);
     __syncthreads();
     // tokens [t_lo, t_hi]: t_hi holds the first byte of the next tile (it may begin there: then nothing of it is in this tile)
-    const uint64_t t_lo = tile_first[ti];
-    uint64_t t_hi = tile_first[ti + 1];
+    const uint64_t t_lo = tile_first[tile.index];
+    uint64_t t_hi = tile_first[tile.index + 1];
     if (t_hi >= n_tok) t_hi = n_tok - 1;
     for (uint64_t t = t_lo + threadIdx.x; t <= t_hi; t += kBlock) {
         const uint64_t s = tok_start[t];
         const int nd = (int)(tok_start[t + 1] - s) - 1;
         bool is_count;
         const uint64_t v = token_value(rowptr, ids, counts, t, tok_class[t], &is_count);
-        const int64_t last = (int64_t)(s - base) + nd - 1;          // tile offset of the last digit (may lie before or behind the tile)
-        auto put = [&](int i, char ch) {
-            const int64_t p = last - i;
-            if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = ch;
-        };
+        const int64_t last = (int64_t)(s - tile.base) + nd - 1;     // tile offset of the last digit (may lie before or behind the tile)
+        auto put = [&](int i, char ch) { tile.put(last - i, ch); };
         if (v <= 0xffffffffull) dec_put_fixed_u32((uint32_t)v, nd, 0, put);
         else dec_put_u64(v, put);
-        if (last + 1 >= 0 && last + 1 < (int64_t)kTileBytes) tile[last + 1] = is_count ? '\n' : '\t';
+        tile.put(last + 1, is_count ? '\n' : '\t');
     }
     __syncthreads();
-    const uint64_t g = base + 16ull * threadIdx.x;
-    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+    tile.store(out_base, out);
 }
 
 struct WriteScratch {

@@ -18,7 +18,7 @@
 #include "decfmt.h"
 #include "gfmt.h"
 #include "primitives.h"
-#include "textchunks.h"
+#include "texttile.h"
 
 #include <cstring>
 
@@ -27,7 +27,6 @@ namespace rowtext {
 
 using textchunks::kBlock;
 using textchunks::kTileBytes;
-using textchunks::kTileShift;
 using textchunks::kDefaultChunk;
 using textchunks::kMaxChunk;
 using textchunks::grid_of;
@@ -104,16 +103,6 @@ __global__ void k_row_size(const uint64_t* __restrict__ name_off, const uint32_t
     row_len[r] = len;
 }
 
-// the row that holds byte x of the text (x < row_start[n_rows]); rows are never empty, so the starts increase strictly
-__device__ inline uint64_t row_of(const uint64_t* __restrict__ row_start, uint64_t n_rows, uint64_t x) {
-    uint64_t lo = 0, hi = n_rows;                         // row_start[lo] <= x < row_start[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (row_start[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // one block per tile of the output; `out` is the chunk buffer, whose byte 0 is text byte out_base (a multiple of kTileBytes)
 template <bool kGene>
 __global__ void __launch_bounds__(kBlock)
@@ -123,42 +112,31 @@ k_format(const char* __restrict__ names, const uint64_t* __restrict__ name_off, 
     __shared__ uint4 tile4[kBlock];
     __shared__ uint32_t long_rows[kLongCap];
     __shared__ uint32_t n_long;
-    char* tile = reinterpret_cast<char*>(tile4);
-    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
-    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);      // (the bytes behind the end of the text)
+    const textchunks::Tile tile(tile4, first_tile, n_bytes);
     if (threadIdx.x == 0) n_long = 0;
     __syncthreads();
-    const uint64_t end = base + kTileBytes < n_bytes ? base + kTileBytes : n_bytes;      // base < n_bytes: the grid ends with the chunk
-    const uint64_t r_lo = row_of(row_start, n_rows, base), r_hi = row_of(row_start, n_rows, end - 1);
+    // rows are never empty, so their starts increase strictly
+    const uint64_t r_lo = textchunks::holder_of(row_start, n_rows, tile.base), r_hi = textchunks::holder_of(row_start, n_rows, tile.end() - 1);
     for (uint64_t r = r_lo + threadIdx.x; r <= r_hi; r += kBlock) {
         const uint64_t ni = name_of<kGene>(first, r);
         const uint64_t s = row_start[r], no = name_off[ni];
         const uint32_t nl = (uint32_t)(name_off[ni + 1] - no);
-        const int64_t p0 = (int64_t)(s - base);           // tile offset of the row's first byte (may lie before the tile)
+        const int64_t p0 = (int64_t)(s - tile.base);      // tile offset of the row's first byte (may lie before the tile)
         if (nl > kShortName) {
             const uint32_t k = atomicAdd(&n_long, 1u);
             if (k < (uint32_t)kLongCap) long_rows[k] = (uint32_t)(r - r_lo);
         } else {
-            for (uint32_t i = 0; i < nl; ++i) {
-                const int64_t p = p0 + i;
-                if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = names[no + i];
-            }
+            for (uint32_t i = 0; i < nl; ++i) tile.put(p0 + i, names[no + i]);
         }
         int64_t p = p0 + nl;                              // the tail: \t [Length \t] the doubles, \t between them, \n
         if (p + (int64_t)tail_max<kGene>() <= 0 || p >= (int64_t)kTileBytes) continue;
-        auto sep = [&](char ch) {
-            if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = ch;
-            ++p;
-        };
+        auto sep = [&](char ch) { tile.put(p++, ch); };
         if (!kGene) {
             sep('\t');
             const uint32_t v = first[r];
             const int nd = dec_len_u32(v);
             const int64_t last = p + nd - 1;
-            dec_put_fixed_u32(v, nd, 0, [&](int i, char ch) {
-                const int64_t q = last - i;
-                if (q >= 0 && q < (int64_t)kTileBytes) tile[q] = ch;
-            });
+            dec_put_fixed_u32(v, nd, 0, [&](int i, char ch) { tile.put(last - i, ch); });
             p += nd;
         }
 #pragma unroll
@@ -166,10 +144,7 @@ k_format(const char* __restrict__ names, const uint64_t* __restrict__ name_off, 
             sep('\t');
             const uint32_t g = rec[(uint64_t)c * n_rows + r];
             const int64_t last = p + gfmt_len(g) - 1;
-            p += gfmt_put(g, [&](int i, char ch) {
-                const int64_t q = last - i;
-                if (q >= 0 && q < (int64_t)kTileBytes) tile[q] = ch;
-            });
+            p += gfmt_put(g, [&](int i, char ch) { tile.put(last - i, ch); });
         }
         sep('\n');
     }
@@ -180,12 +155,11 @@ k_format(const char* __restrict__ names, const uint64_t* __restrict__ name_off, 
         const uint64_t r = r_lo + long_rows[k];
         const uint64_t ni = name_of<kGene>(first, r);
         const uint64_t s = row_start[r], no = name_off[ni], e = s + (name_off[ni + 1] - no);
-        const uint64_t a = s > base ? s : base, b = e < end ? e : end;
-        for (uint64_t x = a + threadIdx.x; x < b; x += kBlock) tile[x - base] = names[no + (x - s)];
+        const uint64_t a = s > tile.base ? s : tile.base, b = e < tile.end() ? e : tile.end();
+        for (uint64_t x = a + threadIdx.x; x < b; x += kBlock) tile.bytes[x - tile.base] = names[no + (x - s)];
     }
     __syncthreads();
-    const uint64_t g = base + 16ull * threadIdx.x;
-    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+    tile.store(out_base, out);
 }
 
 struct Scratch {

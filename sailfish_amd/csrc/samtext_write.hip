@@ -10,30 +10,24 @@
 //           offender of either kind wins an atomicMin) and writes the bytes of its unit; k_empty_size: one lane per read writes
 //           the bytes of its record-less unit.  An exclusive scan (primitives.h) gives every unit its 64-bit byte start.
 //           textchunks.h: the longest unit and the greedy chunk ends.
-//   format  k_format: one block per 4 KB tile of the output.  The units that overlap the tile are found by binary search of the
-//           unit starts (a unit may span many tiles: SEQ is of any length).  One lane per line writes the numeric parts, the
-//           default QNAME and every name or SEQ of at most kShortCopy bytes into an LDS image of the tile, clipped to the tile;
-//           longer names and SEQs are queued as copy jobs, clipped to the tile, and copied a byte per lane and step, the block's
-//           wavefronts taking the jobs in turn.  Then every lane stores one aligned 16-byte group: global memory sees only
-//           full-width coalesced stores.  Names are copied, never inspected; so are SEQ and QUAL but for the lines samwfmt.h puts
-//           on the reference's strand (sfgpu_sam_write_text_q with oriented != 0): there output byte i of a run of n comes
-//           from source byte n - 1 - i (SEQ through samw_comp), so a clipped job carries where its source ENDS and the lanes read
-//           consecutive addresses downwards.  The quality rule (every byte in '!' .. '~') is one flat pass over each mate's bytes
-//           in the sizing step (k_qual_check); the lowest offending byte is mapped to its read through the offsets.
-// The chunks are planned and handed to the sink by textchunks.h, the loop of eqtext_write.hip and rowtext.h.
-//
-// sfgpu_sam_write_bgzf hands the chunks to the BGZF encoder (bgzf_write.hip) on the device instead, and with SFGPU_SAMW_BAM the
-// lines are BAM records (WHAT a record says is bamwfmt.h): the same units, scan, tiles and chunks; the sizing kernels take the
-// record sizes and bamwfmt.h's three further checks (template argument BAM), and k_format_bam builds a tile of records -- the
-// fixed 36 bytes, NUL and CIGAR words by the line's lane, names copied, SEQ packed two bases a byte and QUAL filled with 0xff, or
-// made of the quality bytes - 33, by whole wavefronts where they are longer than kShortCopy bytes of output; both from the last
-// byte to the first on a line that goes on the reference's strand.
+//           The quality rule (every byte in '!' .. '~') is one flat pass over each mate's bytes (k_qual_check); the lowest
+//           offending byte is mapped to its read through the offsets.
+//   format  k_format_units<Fmt>: one block per 4 KB tile of the output (texttile.h).  The units that overlap the tile are found
+//           by binary search of the unit starts (a unit may span many tiles: SEQ is of any length).  One lane per line has Fmt
+//           write it into the LDS image, clipped to the tile: the numeric parts and every run (a name, SEQ, QUAL) of at most
+//           kShortCopy bytes by that lane; longer runs are queued as jobs, clipped to the tile, and made a byte per lane and step,
+//           the block's wavefronts taking the jobs in turn.  Then every lane stores one aligned 16-byte group.
+//           TextFmt is samwfmt.h's line: runs are copied, never inspected, on a line that goes on the reference's strand (oriented
+//           != 0) from the last byte to the first, SEQ through samw_comp.  BamFmt is bamwfmt.h's record: SEQ packed two bases a
+//           byte, QUAL 0xff or the quality bytes - 33.  The sizing kernels take the format as their template argument BAM.
+// The chunks are planned by textchunks.h and go to the sink (sfgpu_sam_write_text*), on the device to the BGZF encoder of
+// bgzf_write.hip (sfgpu_sam_write_bgzf*), or all at once into bamsort.hip's record store (sfgpu_bamsort_collect*).
 #include "common.h"
 #include "decfmt.h"
 #include "primitives.h"
 #include "samwfmt.h"
 #include "bamwfmt.h"
-#include "textchunks.h"
+#include "texttile.h"
 #include "bamsort.h"
 
 #include <cstring>
@@ -93,12 +87,7 @@ __global__ void k_qual_check(const uint8_t* __restrict__ q, const int64_t* __res
         for (int64_t p = p1 - 1; p >= p0; --p) if (!samw_qual_ok(q[p])) bad = p;
     }
     if (bad < 0) return;
-    uint64_t a = 0, b = n_reads;                          // off[a] <= bad < off[b]
-    while (b - a > 1) {
-        const uint64_t mid = a + (b - a) / 2;
-        if (off[mid] <= bad) a = mid; else b = mid;
-    }
-    atomicMin(&misc[kMiscQual], (unsigned long long)(a << 32));
+    atomicMin(&misc[kMiscQual], (unsigned long long)(textchunks::holder_of(off, n_reads, bad) << 32));
 }
 
 // empty[r] = 1 for a read without records; the CSR offsets start at 0 and never decrease
@@ -126,12 +115,8 @@ k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before
     const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t lines = 0;
     if (h < n_hits) {
-        uint64_t lo = 0, hi = a.n_reads;                  // hit_off[lo] <= h < hit_off[hi]: the last such lo is the read that holds h
-        while (hi - lo > 1) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (a.hit_off[mid] <= h) lo = mid; else hi = mid;
-        }
-        const uint64_t r = lo, rank = h - a.hit_off[r], u = h + e_before[r];
+        const uint64_t r = textchunks::holder_of(a.hit_off, a.n_reads, h);      // the last read whose records start at or before h
+        const uint64_t rank = h - a.hit_off[r], u = h + e_before[r];
         const sfgpu_hit rec = a.hits[h];
         uint64_t len = 0;
         if (const int kind = BAM ? bamw_check(a, r, &rec, rank, h) : samw_check_a(a, rec, h))
@@ -164,251 +149,184 @@ k_empty_size(SamwArgs a, const uint32_t* __restrict__ e_before, uint32_t* __rest
     count_lines(lines, misc);
 }
 
-// the unit that holds byte x of the text (x < unit_start[n_units]); units are never empty, so the starts increase strictly
-__device__ inline uint64_t unit_of(const uint64_t* __restrict__ unit_start, uint64_t n_units, uint64_t x) {
-    uint64_t lo = 0, hi = n_units;                        // unit_start[lo] <= x < unit_start[hi]
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (unit_start[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-struct CopyJob {
-    const char* src;        // the source of the first byte that lies in the tile; a reversed job goes down from it
+// ---- format: one skeleton, k_format_units<Fmt>, for text lines (TextFmt) and BAM records (BamFmt)
+// A RUN is a stretch of a line whose bytes are a function of a source array: byte i of a run of `kind` over src, of which `left`
+// source units count, is Fmt::run_byte(kind, src, left, i).  A kind with kReversed set reads its source from the last unit to the first.
+// A run cut by the tile's start is the run of the same kind over fewer units: `skip` output bytes use up skip * Fmt::units(kind) of
+// them, from the front on a forward kind (src moves up), from the back on a reversed one (src stays where it is).
+constexpr uint32_t kReversed = 4;
+struct Job {
+    const uint8_t* src;     // the source of the first byte that lies in the tile; a reversed kind: the run's first source unit
     uint32_t at, n;         // tile offset and bytes
-    uint32_t mode;
+    uint32_t kind, left;    // the source units from src on that count
 };
-enum : uint32_t { kFwd = 0, kRev = 1, kRevComp = 2 };    // as given; from the last byte to the first; that, complemented
 
-// one block per tile of the output; `out` is the chunk buffer, whose byte 0 is text byte out_base (a multiple of kTileBytes)
-__global__ void __launch_bounds__(kBlock)
-k_format(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
-         uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
-    __shared__ uint4 tile4[kBlock];
-    __shared__ CopyJob jobs[kJobCap];
-    __shared__ uint32_t n_jobs;
-    char* tile = reinterpret_cast<char*>(tile4);
-    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
-    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);      // (the bytes behind the end of the text)
-    if (threadIdx.x == 0) n_jobs = 0;
-    __syncthreads();
-    const uint64_t end = base + kTileBytes < n_bytes ? base + kTileBytes : n_bytes;      // base < n_bytes: the grid ends with the chunk
-    const uint64_t u_lo = unit_of(unit_start, n_units, base), u_hi = unit_of(unit_start, n_units, end - 1);
-    auto put_at = [&](int64_t p, char ch) {               // tile offset p, which may lie before or behind the tile
-        if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = ch;
-    };
-    // bytes src[0 .. n) to text offset s: by this lane when short, else queued for the wavefronts (the part inside the tile)
-    auto copy = [&](const char* src, uint64_t s, uint64_t n, uint32_t mode) {
+// what the skeleton knows of a line when a format writes it
+struct LineCtx {
+    uint64_t r, rank, hidx; // the read; the record's rank among its read's records and its index in a.hits (0, 0: the read has none)
+    uint32_t tid, which;
+    SamwLine l;
+    uint64_t s, len;        // the line's first byte in the text, and its bytes (Fmt::line_len)
+};
+
+// where a format puts a line's pieces, one after the other; `p` is the tile offset of the next byte, before or behind the tile or in it
+template <typename Fmt>
+struct LineOut {
+    const textchunks::Tile& tile;
+    Job* jobs;
+    uint32_t* n_jobs;
+    int64_t p;
+    __device__ __forceinline__ void put(int i, uint8_t b) const { tile.put(p + i, (char)b); }     // byte i from here on; skip() then passes them
+    __device__ __forceinline__ void skip(uint64_t n) { p += (int64_t)n; }
+    __device__ __forceinline__ void byte(uint8_t b) { tile.put(p++, (char)b); }
+    // the n bytes of a run: by this lane when short, else its part inside the tile is queued for the wavefronts
+    __device__ __forceinline__ void run(uint32_t kind, const uint8_t* src, uint64_t n, uint64_t left) {
         if (n <= kShortCopy) {
-            const int64_t p0 = (int64_t)(s - base);
-            if (mode == kFwd) for (uint32_t i = 0; i < (uint32_t)n; ++i) put_at(p0 + i, src[i]);
-            else for (uint32_t i = 0; i < (uint32_t)n; ++i) put_at(p0 + i, mode == kRev ? src[n - 1 - i] : (char)samw_comp((uint8_t)src[n - 1 - i]));
-            return;
+            for (uint32_t i = 0; i < (uint32_t)n; ++i) tile.put(p + i, (char)Fmt::run_byte(kind, src, (uint32_t)left, i));
+        } else {
+            const int64_t room = (int64_t)(tile.end() - tile.base), lo = p > 0 ? p : 0, hi = p + (int64_t)n < room ? p + (int64_t)n : room;
+            if (lo < hi) {
+                const uint32_t k = atomicAdd(n_jobs, 1u);
+                const uint64_t used = (uint64_t)(lo - p) * Fmt::units(kind);
+                if (k < kJobCap) jobs[k] = Job{kind & kReversed ? src : src + used, (uint32_t)lo, (uint32_t)(hi - lo), kind, (uint32_t)(left - used)};
+            }
         }
-        const uint64_t lo = s > base ? s : base, hi = s + n < end ? s + n : end;
-        if (lo >= hi) return;
-        const uint32_t k = atomicAdd(&n_jobs, 1u);
-        if (k < kJobCap) jobs[k] = CopyJob{mode == kFwd ? src + (lo - s) : src + (n - 1 - (lo - s)), (uint32_t)(lo - base), (uint32_t)(hi - lo), mode};
-    };
-    // two line slots per unit: a unit's second line is absent unless it is a pair record or a record-less paired read.  (With an
-    // alignment given -- the _a entries -- a line's CIGAR is its slot's operations, put one after the other through put_at.)
-    for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
-        const uint64_t u = u_lo + (slot >> 1);
-        const uint32_t which = (uint32_t)(slot & 1);
-        const uint64_t r = unit_read[u];
-        const uint32_t h0 = a.hit_off[r];
-        const bool empty = h0 == a.hit_off[r + 1];
-        sfgpu_hit rec = {};
-        uint64_t rank = 0, h = 0;
-        if (!empty) {
-            h = u - e_before[r];
-            rec = a.hits[h];
-            rank = h - h0;
+        p += (int64_t)n;
+    }
+};
+
+// samwfmt.h's line: names, SEQ and QUAL are runs of bytes as given, or -- on a line that goes on the reference's strand -- from the
+// last byte to the first, SEQ through samw_comp
+struct TextFmt {
+    enum : uint32_t { kCopy = 0, kCopyRev = kReversed, kCompRev = kReversed | 1 };
+    static __device__ __forceinline__ uint32_t units(uint32_t) { return 1; }
+    static __device__ __forceinline__ uint8_t run_byte(uint32_t kind, const uint8_t* __restrict__ src, uint32_t left, uint32_t i) {
+        switch (kind) {
+            case kCopy: return src[i];
+            case kCopyRev: return src[left - 1 - i];
+            default: return samw_comp(src[left - 1 - i]);
         }
-        if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
-        const uint32_t tid = empty ? 0u : rec.tid;
-        uint64_t s = unit_start[u];
-        if (which) s += samw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_line(a, rec, rank, 0, h), r, tid);
-        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_line(a, rec, rank, which, h);
-        if (s >= end || s + samw_line_len(a, l, r, tid) <= base) continue;
-        // QNAME
+    }
+    static __device__ __forceinline__ uint64_t line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t tid) { return samw_line_len(a, l, r, tid); }
+    static __device__ __forceinline__ void emit(const SamwArgs& a, const LineCtx& c, LineOut<TextFmt>& out) {
+        auto put = [&](int i, char ch) { out.put(i, (uint8_t)ch); };
         if (a.qname_off) {
-            const uint64_t o = a.qname_off[r], n = a.qname_off[r + 1] - o;
-            copy(a.qnames + o, s, n, kFwd);
-            s += n;
+            const uint64_t o = a.qname_off[c.r], n = a.qname_off[c.r + 1] - o;
+            out.run(kCopy, reinterpret_cast<const uint8_t*>(a.qnames) + o, n, n);
         } else {
-            const int64_t p0 = (int64_t)(s - base);
-            samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { put_at(p0 + i, ch); });
-            s += samw_default_qname_len(a.read_index_base + r);
+            samw_put_default_qname(a.read_index_base + c.r, put);
+            out.skip(samw_default_qname_len(a.read_index_base + c.r));
         }
-        {   // \t FLAG \t
-            const int64_t p0 = (int64_t)(s - base);
-            samw_put_head(l, [&](int i, char ch) { put_at(p0 + i, ch); });
-            s += samw_head_len(l);
-        }
-        // RNAME
-        if (l.mapped) {
-            const uint64_t o = a.ref_name_off[tid], n = a.ref_name_off[tid + 1] - o;
-            copy(a.ref_names + o, s, n, kFwd);
-            s += n;
-        } else {
-            put_at((int64_t)(s - base), '*');
-            s += 1;
-        }
-        {   // \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
-            const int64_t p0 = (int64_t)(s - base);
-            samw_put_mid(l, [&](int i, char ch) { put_at(p0 + i, ch); });
-            s += samw_mid_len(l);
-        }
-        // SEQ
-        const uint8_t* seq;
-        uint64_t sl;
-        const bool rev = samw_reversed(a, l);
-        if (samw_seq(a, l, r, &seq, &sl)) copy(reinterpret_cast<const char*>(seq), s, sl, rev ? kRevComp : kFwd);
-        else put_at((int64_t)(s - base), '*');
-        s += sl;
-        put_at((int64_t)(s - base), '\t');
-        s += 1;
-        // QUAL
-        if (samw_qual(a, l, r, &seq, &sl)) copy(reinterpret_cast<const char*>(seq), s, sl, rev ? kRev : kFwd);
-        else put_at((int64_t)(s - base), '*');
-        s += sl;
-        put_at((int64_t)(s - base), '\n');
+        samw_put_head(c.l, put);                          // \t FLAG \t
+        out.skip(samw_head_len(c.l));
+        if (c.l.mapped) {
+            const uint64_t o = a.ref_name_off[c.tid], n = a.ref_name_off[c.tid + 1] - o;
+            out.run(kCopy, reinterpret_cast<const uint8_t*>(a.ref_names) + o, n, n);
+        } else out.byte('*');
+        samw_put_mid(c.l, put);                           // \t POS \t 255 \t CIGAR \t RNEXT \t PNEXT \t TLEN \t
+        out.skip(samw_mid_len(c.l));
+        const bool rev = samw_reversed(a, c.l);
+        const uint8_t* src;
+        uint64_t n;
+        if (samw_seq(a, c.l, c.r, &src, &n)) out.run(rev ? kCompRev : kCopy, src, n, n);
+        else out.byte('*');
+        out.byte('\t');
+        if (samw_qual(a, c.l, c.r, &src, &n)) out.run(rev ? kCopyRev : kCopy, src, n, n);
+        else out.byte('*');
+        out.byte('\n');
     }
-    __syncthreads();
-    // the long names, SEQs and QUALs: the wavefronts take the jobs in turn, a byte per lane and step
-    const uint32_t nj = n_jobs < kJobCap ? n_jobs : kJobCap;
-    const uint32_t wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    for (uint32_t k = wave; k < nj; k += kBlock / kWave) {
-        const CopyJob j = jobs[k];
-        if (j.mode == kFwd) for (uint32_t i = lane; i < j.n; i += kWave) tile[j.at + i] = j.src[i];
-        else if (j.mode == kRev) for (uint32_t i = lane; i < j.n; i += kWave) tile[j.at + i] = *(j.src - i);
-        else for (uint32_t i = lane; i < j.n; i += kWave) tile[j.at + i] = (char)samw_comp((uint8_t) * (j.src - i));
-    }
-    __syncthreads();
-    const uint64_t g = base + 16ull * threadIdx.x;
-    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
-}
-
-// ---- BAM records (bamwfmt.h): the same tiles, units and scan; a unit's lines are records
-struct BamJob {
-    const uint8_t* src;     // kCopy, kQual: the first byte that lies in the tile; kPack: the base of the first packed byte that does;
-                            // the reversed kinds: the run's first source byte
-    uint32_t at, n;         // tile offset and bytes
-    uint32_t kind, left;    // kPack: the bases from src on; the reversed kinds: the source bytes not yet used up in front of the tile
 };
-// a name; bases packed; 0xff; qualities - 33; and the last two from the last source byte to the first (the bases complemented)
-enum : uint32_t { kCopy = 0, kPack = 1, kFill = 2, kQual = 3, kPackRev = 4, kQualRev = 5 };
 
-// byte i of a run of `kind` over src, of which `left` bytes count (kPack, kPackRev: bases; kQualRev: qualities)
-__device__ __forceinline__ uint8_t bam_run_byte(uint32_t kind, const uint8_t* __restrict__ src, uint32_t left, uint32_t i) {
-    switch (kind) {
-        case kCopy: return src[i];
-        case kPack: return bamw_packed_byte(src, left, i);
-        case kQual: return (uint8_t)(src[i] - 33u);
-        case kPackRev: return bamw_packed_byte_rev(src, left, i);
-        case kQualRev: return (uint8_t)(src[left - 1 - i] - 33u);
-        default: return (uint8_t)0xff;
+// bamwfmt.h's record: the 36 fixed bytes, the NUL and the CIGAR words by the line's lane; the name is a run copied, SEQ a run of
+// bytes packed from two bases each, QUAL a run of 0xff or of the quality bytes - 33.  A packed run's units are bases: a reversed
+// one cut by the tile's start keeps its parity, so the one packed byte with a 0 low nibble stays the last.
+struct BamFmt {
+    enum : uint32_t { kCopy = 0, kQual = 1, kFill = 2, kPack = 3, kQualRev = kReversed | kQual, kPackRev = kReversed | kPack };
+    static __device__ __forceinline__ uint32_t units(uint32_t kind) { return (kind & 3u) == kPack ? 2u : 1u; }
+    static __device__ __forceinline__ uint8_t run_byte(uint32_t kind, const uint8_t* __restrict__ src, uint32_t left, uint32_t i) {
+        switch (kind) {
+            case kCopy: return src[i];
+            case kPack: return bamw_packed_byte(src, left, i);
+            case kQual: return (uint8_t)(src[i] - 33u);
+            case kPackRev: return bamw_packed_byte_rev(src, left, i);
+            case kQualRev: return (uint8_t)(src[left - 1 - i] - 33u);
+            default: return (uint8_t)0xff;
+        }
     }
-}
-
-// k_format for BAM records.  One lane per record writes the 36 fixed bytes, the NUL, the CIGAR words, the default QNAME and
-// every name, packed SEQ or QUAL run of at most kShortCopy bytes; longer ones are queued, clipped to the tile, and done by the
-// wavefronts in turn, a byte per lane and step: a name copied, a packed byte made from its two bases, a QUAL byte set to 0xff or
-// to its quality - 33.  A reversed run cut by the tile's start is the reversed run of fewer source bytes: skipping `skip` output
-// bytes leaves the first n - skip qualities, or the first n_bases - 2 * skip bases (of the same parity, so the one packed byte
-// with a 0 low nibble stays the last).
-__global__ void __launch_bounds__(kBlock)
-k_format_bam(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
-             uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
-    __shared__ uint4 tile4[kBlock];
-    __shared__ BamJob jobs[kJobCap];
-    __shared__ uint32_t n_jobs;
-    uint8_t* tile = reinterpret_cast<uint8_t*>(tile4);
-    const uint64_t ti = first_tile + blockIdx.x, base = ti << kTileShift;
-    tile4[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    if (threadIdx.x == 0) n_jobs = 0;
-    __syncthreads();
-    const uint64_t end = base + kTileBytes < n_bytes ? base + kTileBytes : n_bytes;
-    const uint64_t u_lo = unit_of(unit_start, n_units, base), u_hi = unit_of(unit_start, n_units, end - 1);
-    auto put_at = [&](int64_t p, uint8_t b) {
-        if (p >= 0 && p < (int64_t)kTileBytes) tile[p] = b;
-    };
-    // output bytes [s, s + n) of `kind` from src (kPack, kPackRev: n packed bytes of n_bases bases; kQualRev: n_bases = n)
-    auto run = [&](uint32_t kind, const uint8_t* src, uint64_t s, uint64_t n, uint64_t n_bases) {
-        if (n <= kShortCopy) {
-            const int64_t p0 = (int64_t)(s - base);
-            for (uint32_t i = 0; i < (uint32_t)n; ++i) put_at(p0 + i, bam_run_byte(kind, src, (uint32_t)n_bases, i));
-            return;
-        }
-        const uint64_t lo = s > base ? s : base, hi = s + n < end ? s + n : end;
-        if (lo >= hi) return;
-        const uint32_t k = atomicAdd(&n_jobs, 1u);
-        if (k >= kJobCap) return;
-        const uint64_t skip = lo - s;
-        const bool packed = kind == kPack || kind == kPackRev;
-        jobs[k] = BamJob{kind == kCopy || kind == kQual ? src + skip : kind == kPack ? src + 2 * skip : src, (uint32_t)(lo - base), (uint32_t)(hi - lo),
-                         kind, packed ? (uint32_t)(n_bases - 2 * skip) : kind == kQualRev ? (uint32_t)(n_bases - skip) : 0u};
-    };
-    for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
-        const uint64_t u = u_lo + (slot >> 1);
-        const uint32_t which = (uint32_t)(slot & 1);
-        const uint64_t r = unit_read[u];
-        const uint32_t h0 = a.hit_off[r];
-        const bool empty = h0 == a.hit_off[r + 1];
-        sfgpu_hit rec = {};
-        uint64_t rank = 0, h = 0;
-        if (!empty) {
-            h = u - e_before[r];
-            rec = a.hits[h];
-            rank = h - h0;
-        }
-        if (which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
-        const uint32_t tid = empty ? 0u : rec.tid;
-        uint64_t s = unit_start[u];
-        if (which) s += bamw_line_len(a, empty ? samw_empty_line(a.paired != 0, 0) : samw_line(a, rec, rank, 0, h), r);
-        const SamwLine l = empty ? samw_empty_line(a.paired != 0, which) : samw_line(a, rec, rank, which, h);
-        const uint64_t len = bamw_line_len(a, l, r), qn = samw_qname_len(a, r);
-        if (s >= end || s + len <= base) continue;
+    static __device__ __forceinline__ uint64_t line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t) { return bamw_line_len(a, l, r); }
+    static __device__ __forceinline__ void emit(const SamwArgs& a, const LineCtx& c, LineOut<BamFmt>& out) {
+        auto put = [&](int i, uint8_t b) { out.put(i, b); };
+        const uint64_t qn = samw_qname_len(a, c.r);
         const uint8_t* seq;
-        const uint64_t n_bases = bamw_l_seq(a, l, r, &seq);
-        {
-            const int64_t p0 = (int64_t)(s - base);
-            bamw_put_fixed(l, tid, len, qn, n_bases, [&](int i, uint8_t b) { put_at(p0 + i, b); });
-            s += kBamwFixed;
-        }
-        if (a.qname_off) run(kCopy, reinterpret_cast<const uint8_t*>(a.qnames) + a.qname_off[r], s, qn, 0);
+        const uint64_t n_bases = bamw_l_seq(a, c.l, c.r, &seq);
+        bamw_put_fixed(c.l, c.tid, c.len, qn, n_bases, put);
+        out.skip(kBamwFixed);
+        if (a.qname_off) out.run(kCopy, reinterpret_cast<const uint8_t*>(a.qnames) + a.qname_off[c.r], qn, qn);
         else {
-            const int64_t p0 = (int64_t)(s - base);
-            samw_put_default_qname(a.read_index_base + r, [&](int i, char ch) { put_at(p0 + i, (uint8_t)ch); });
+            samw_put_default_qname(a.read_index_base + c.r, [&](int i, char ch) { out.put(i, (uint8_t)ch); });
+            out.skip(qn);
         }
-        s += qn;
-        put_at((int64_t)(s - base), 0);
-        s += 1;
-        {
-            const int64_t p0 = (int64_t)(s - base);
-            bamw_put_cigar(l, [&](int i, uint8_t b) { put_at(p0 + i, b); });
-            s += 4 * bamw_cigar_ops(l);
-        }
-        const bool rev = samw_reversed(a, l);
-        run(rev ? kPackRev : kPack, seq, s, (n_bases + 1) / 2, n_bases);
-        s += (n_bases + 1) / 2;
+        out.byte(0);
+        bamw_put_cigar(c.l, put);
+        out.skip(4 * bamw_cigar_ops(c.l));
+        const bool rev = samw_reversed(a, c.l);
+        out.run(rev ? kPackRev : kPack, seq, (n_bases + 1) / 2, n_bases);
         const uint8_t* qual;
         uint64_t ql;
-        if (samw_qual(a, l, r, &qual, &ql)) run(rev ? kQualRev : kQual, qual, s, n_bases, n_bases);
-        else run(kFill, nullptr, s, n_bases, 0);
+        if (samw_qual(a, c.l, c.r, &qual, &ql)) out.run(rev ? kQualRev : kQual, qual, n_bases, n_bases);
+        else out.run(kFill, seq, n_bases, n_bases);       // (the source of a kFill run is never read)
+    }
+};
+
+// One block per tile of the output; `out` is the chunk buffer, whose byte 0 is text byte out_base (a multiple of kTileBytes).  The
+// units that overlap the tile are found by binary search of the unit starts (units are never empty, so the starts increase strictly).
+// Two line slots per unit, a lane each: a unit's second line is absent unless it is a pair record or a record-less paired read.
+// The lane of a line inside the tile has Fmt write it; then the wavefronts take the queued runs in turn, a byte per lane and step.
+template <typename Fmt>
+__global__ void __launch_bounds__(kBlock)
+k_format_units(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
+               uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
+    __shared__ uint4 tile4[kBlock];
+    __shared__ Job jobs[kJobCap];
+    __shared__ uint32_t n_jobs;
+    const textchunks::Tile tile(tile4, first_tile, n_bytes);
+    if (threadIdx.x == 0) n_jobs = 0;
+    __syncthreads();
+    const uint64_t u_lo = textchunks::holder_of(unit_start, n_units, tile.base), u_hi = textchunks::holder_of(unit_start, n_units, tile.end() - 1);
+    for (uint64_t slot = threadIdx.x; slot < 2 * (u_hi - u_lo + 1); slot += kBlock) {
+        const uint64_t u = u_lo + (slot >> 1);
+        LineCtx c;
+        c.which = (uint32_t)(slot & 1);
+        c.r = unit_read[u];
+        c.rank = 0; c.hidx = 0;
+        const uint32_t h0 = a.hit_off[c.r];
+        const bool empty = h0 == a.hit_off[c.r + 1];
+        sfgpu_hit rec = {};
+        if (!empty) {
+            c.hidx = u - e_before[c.r];
+            rec = a.hits[c.hidx];
+            c.rank = c.hidx - h0;
+        }
+        if (c.which >= (empty ? samw_empty_lines(a.paired != 0) : samw_record_lines(rec))) continue;
+        c.tid = empty ? 0u : rec.tid;
+        auto line = [&](uint32_t w) { return empty ? samw_empty_line(a.paired != 0, w) : samw_line(a, rec, c.rank, w, c.hidx); };
+        c.s = unit_start[u];
+        if (c.which) c.s += Fmt::line_len(a, line(0), c.r, c.tid);
+        c.l = line(c.which);
+        c.len = Fmt::line_len(a, c.l, c.r, c.tid);
+        if (c.s >= tile.end() || c.s + c.len <= tile.base) continue;
+        LineOut<Fmt> lo{tile, jobs, &n_jobs, (int64_t)(c.s - tile.base)};
+        Fmt::emit(a, c, lo);
     }
     __syncthreads();
     const uint32_t nj = n_jobs < kJobCap ? n_jobs : kJobCap;
     const uint32_t wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
     for (uint32_t k = wave; k < nj; k += kBlock / kWave) {
-        const BamJob j = jobs[k];
-        for (uint32_t i = lane; i < j.n; i += kWave) tile[j.at + i] = bam_run_byte(j.kind, j.src, j.left, i);
+        const Job j = jobs[k];
+        for (uint32_t i = lane; i < j.n; i += kWave) tile.bytes[j.at + i] = (char)Fmt::run_byte(j.kind, j.src, j.left, i);
     }
     __syncthreads();
-    const uint64_t g = base + 16ull * threadIdx.x;
-    if (g < n_bytes) out[(g - out_base) >> 4] = tile4[threadIdx.x];
+    tile.store(out_base, out);
 }
 
 struct Scratch {
@@ -424,31 +342,37 @@ using namespace sfgpu;
 
 namespace {
 
-// sfgpu_sam_write_text[_q] (sink), sfgpu_sam_write_bgzf[_q] (z; format SFGPU_SAMW_TEXT or SFGPU_SAMW_BAM) and sfgpu_bamsort_collect
-// (store; SFGPU_SAMW_BAM): everything up to the chunk loop is the same but for the kernels that size and check a unit
-int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired, const char* d_ref_names,
-              const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames, const uint64_t* d_qname_off, const uint8_t* d_seq1,
-              const int64_t* d_seq1_off, const uint8_t* d_seq2, const int64_t* d_seq2_off, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-              uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user, sfgpu_bgzw* z, int format,
-              sfgpu_samwrite_result* out, sfgpu_stream stream, BamRecordStore* store, const int32_t* d_aln_pos = nullptr,
-              const uint64_t* d_aln_op_off = nullptr, const uint32_t* d_aln_ops = nullptr) {
-    const bool bam = format == SFGPU_SAMW_BAM;
+// where a batch goes: the chunks to a sink (sfgpu_sam_write_text*), to the BGZF encoder as text or as BAM records
+// (sfgpu_sam_write_bgzf*), or every record at once into a store (sfgpu_bamsort_collect*; BAM)
+struct Dest {
+    sfgpu_text_sink sink = nullptr;
+    void* user = nullptr;
+    sfgpu_bgzw* z = nullptr;
+    int format = SFGPU_SAMW_TEXT;
+    BamRecordStore* store = nullptr;
+};
+
+// Everything up to the chunk loop is the same for every destination but for the kernels that size and check a unit.  `in` is the
+// batch as the entry was given it; what a single-end batch does not use is dropped once the arguments are checked.
+int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const Dest& dest, sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    const bool bam = dest.format == SFGPU_SAMW_BAM;
+    const uint32_t n_reads = in.n_reads;
     auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
     if (!out) return fail(SFGPU_ERR_INVALID, "null result");
     memset(out, 0, sizeof(*out));
     if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
     if (!(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk)) return fail(SFGPU_ERR_INVALID, "chunk_bytes must lie in [16, 2^30] (0 = default)");
     if (n_reads == 0) return SFGPU_OK;
-    if (!d_hit_offsets) return fail(SFGPU_ERR_INVALID, "null hit offsets");
-    if (!(d_ref_name_off || n_refs == 0)) return fail(SFGPU_ERR_INVALID, "null reference name offsets");
-    if (!(!d_qnames || d_qname_off)) return fail(SFGPU_ERR_INVALID, "read names without their offsets");
-    if (!((!d_seq1 || d_seq1_off) && (!d_seq2 || d_seq2_off))) return fail(SFGPU_ERR_INVALID, "bases without their offsets");
-    if (!((!d_qual1 || d_seq1_off) && (!d_qual2 || d_seq2_off))) return fail(SFGPU_ERR_INVALID, "qualities of a mate whose bases are not given");
+    if (!in.hit_off) return fail(SFGPU_ERR_INVALID, "null hit offsets");
+    if (!(in.ref_name_off || in.n_refs == 0)) return fail(SFGPU_ERR_INVALID, "null reference name offsets");
+    if (!(!in.qnames || in.qname_off)) return fail(SFGPU_ERR_INVALID, "read names without their offsets");
+    if (!((!in.seq1 || in.seq1_off) && (!in.seq2 || in.seq2_off))) return fail(SFGPU_ERR_INVALID, "bases without their offsets");
+    if (!((!in.qual1 || in.seq1_off) && (!in.qual2 || in.seq2_off))) return fail(SFGPU_ERR_INVALID, "qualities of a mate whose bases are not given");
     if (!(n_reads < 0xffffffffu)) return fail(SFGPU_ERR_RANGE, "n_reads must be below 2^32 - 1");
-    if (!((d_aln_pos != nullptr) == (d_aln_op_off != nullptr) && (!d_aln_ops || d_aln_pos))) return fail(SFGPU_ERR_INVALID, "an alignment is positions, offsets and operations together");
-    SamwArgs a = {d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                  d_seq1, d_seq1_off, paired ? d_seq2 : nullptr, paired ? d_seq2_off : nullptr, read_index_base,
-                  d_qual1, paired ? d_qual2 : nullptr, oriented != 0, d_aln_pos, d_aln_op_off, d_aln_ops};
+    if (!((in.aln_pos != nullptr) == (in.aln_op_off != nullptr) && (!in.aln_ops || in.aln_pos))) return fail(SFGPU_ERR_INVALID, "an alignment is positions, offsets and operations together");
+    SamwArgs a = in;
+    if (!a.paired) { a.seq2 = nullptr; a.seq2_off = nullptr; a.qual2 = nullptr; }
+    a.oriented = a.oriented != 0;
 
     Scratch S;
     CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
@@ -473,15 +397,15 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     SF_HIP(hipMemsetAsync(S.misc.p + 2, 0xff, 2 * sizeof(unsigned long long), st));
     SF_HIP(hipMemsetAsync(S.misc.p + 5, 0xff, 4 * sizeof(unsigned long long), st));
     SF_HIP(hipEventRecord(ev_a[0], st));
-    hipLaunchKernelGGL(k_read_flags, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, d_hit_offsets, n_reads, S.empty.p, S.misc.p);
+    hipLaunchKernelGGL(k_read_flags, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, a.hit_off, n_reads, S.empty.p, S.misc.p);
     SF_HIP(hipGetLastError());
-    if (n_refs) {
-        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(n_refs)), dim3(kBlock), 0, st, (const void*)d_ref_names, d_ref_name_off,
-                           (uint64_t)n_refs, S.misc.p);
+    if (a.n_refs) {
+        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(a.n_refs)), dim3(kBlock), 0, st, (const void*)a.ref_names, a.ref_name_off,
+                           (uint64_t)a.n_refs, S.misc.p);
         SF_HIP(hipGetLastError());
     }
-    if (d_qname_off) {
-        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, (const void*)d_qnames, d_qname_off,
+    if (a.qname_off) {
+        hipLaunchKernelGGL(k_check_off<uint64_t>, dim3(grid_of(n_reads)), dim3(kBlock), 0, st, (const void*)a.qnames, a.qname_off,
                            (uint64_t)n_reads, S.misc.p);
         SF_HIP(hipGetLastError());
     }
@@ -496,7 +420,7 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     SF_HIP(hipEventRecord(ev_a[1], st));
     uint32_t* h_counts = reinterpret_cast<uint32_t*>(&h_misc[kMisc + 1]);
     SF_HIP(hipMemcpyAsync(&h_misc[0], S.misc.p, 8, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipMemcpyAsync(&h_counts[0], d_hit_offsets + n_reads, 4, hipMemcpyDeviceToHost, st));
+    SF_HIP(hipMemcpyAsync(&h_counts[0], a.hit_off + n_reads, 4, hipMemcpyDeviceToHost, st));
     SF_HIP(hipMemcpyAsync(&h_counts[1], S.e_before.p + n_reads, 4, hipMemcpyDeviceToHost, st));
     int64_t* h_span = reinterpret_cast<int64_t*>(&h_misc[kMisc + 2]);
     for (int m = 0; m < 2; ++m) {
@@ -510,8 +434,8 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     if (h_misc[0] & kBadOffsets) return fail(SFGPU_ERR_INVALID, "an offset array decreases, or the hit offsets do not start at 0");
     if (h_misc[0] & kNullBytes) return fail(SFGPU_ERR_INVALID, "offsets name bytes of a null array");
     const uint64_t n_hits = h_counts[0], n_units = n_hits + h_counts[1];
-    if (n_hits && !d_hits) return fail(SFGPU_ERR_INVALID, "null hits");
-    if (n_hits && d_aln_pos && !d_aln_ops) return fail(SFGPU_ERR_INVALID, "an alignment without operations");
+    if (n_hits && !a.hits) return fail(SFGPU_ERR_INVALID, "null hits");
+    if (n_hits && a.aln_pos && !a.aln_ops) return fail(SFGPU_ERR_INVALID, "an alignment without operations");
 
     // ---- sizing and validation: unit lengths, unit starts, the longest unit, the lowest record that cannot be written
     if (int rc = S.unit_len.reserve(n_units + 1, st, false)) return rc;
@@ -559,91 +483,90 @@ int sam_write(const char* who, const sfgpu_hit* d_hits, const uint32_t* d_hit_of
     if (h_misc[0] & kTooLong) return fail(SFGPU_ERR_RANGE, "a unit is longer than 2^32 - 1 bytes");
     const uint64_t total = h_misc[kMisc];
     out->n_bytes = total; out->n_lines = h_misc[4]; out->max_unit_bytes = h_misc[1];
-    if (store)              // sfgpu_bamsort_collect: every tile at once into a segment of the store, which then lists the records
-        return store->take(total, out->n_lines, S.unit_start.p, n_units, st, &out->format_ms, [&](uint4* buf, hipStream_t s) -> int {
-            hipLaunchKernelGGL(k_format_bam, dim3((unsigned)(((total - 1) >> kTileShift) + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
+    if (dest.store)            // sfgpu_bamsort_collect: every tile at once into a segment of the store, which then lists the records
+        return dest.store->take(total, out->n_lines, S.unit_start.p, n_units, st, &out->format_ms, [&](uint4* buf, hipStream_t s) -> int {
+            hipLaunchKernelGGL(k_format_units<BamFmt>, dim3((unsigned)(((total - 1) >> kTileShift) + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
                                S.unit_start.p, n_units, total, (uint64_t)0, (uint64_t)0, buf);
             SF_HIP(hipGetLastError());
             return SFGPU_OK;
         });
-    if (!sink && !z) return SFGPU_OK;
+    if (!dest.sink && !dest.z) return SFGPU_OK;
     if (out->max_unit_bytes > chunk_bytes) return fail(SFGPU_ERR_RANGE, "a unit (a line, or the two lines of a pair) is longer than chunk_bytes");
 
     // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this text's tiles
     textchunks::Stats ts;
     auto format_tiles = [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-        hipLaunchKernelGGL(bam ? k_format_bam : k_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p,
+        hipLaunchKernelGGL(bam ? k_format_units<BamFmt> : k_format_units<TextFmt>, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p,
                            S.unit_read.p, S.unit_start.p, n_units, total, first_tile, out_base, buf);
         SF_HIP(hipGetLastError());
         return SFGPU_OK;
     };
     // the compressed formats: the chunk's device bytes go to the BGZF encoder, which copies and sinks what IT writes
-    const int rc = z ? textchunks::deliver_device(who, S.unit_start.p, n_units, total, chunk_bytes, st, &ts,
+    const int rc = dest.z ? textchunks::deliver_device(who, S.unit_start.p, n_units, total, chunk_bytes, st, &ts,
                                                   [&](const uint8_t* d_bytes, uint64_t n, hipStream_t ready) -> int {
-                                                      return sfgpu_bgzw_write_device(z, d_bytes, n, reinterpret_cast<sfgpu_stream>(ready));
+                                                      return sfgpu_bgzw_write_device(dest.z, d_bytes, n, reinterpret_cast<sfgpu_stream>(ready));
                                                   }, format_tiles)
-                     : textchunks::deliver(who, S.unit_start.p, n_units, total, chunk_bytes, sink, user, st, &ts, format_tiles);
+                     : textchunks::deliver(who, S.unit_start.p, n_units, total, chunk_bytes, dest.sink, dest.user, st, &ts, format_tiles);
     out->format_ms += ts.format_ms; out->d2h_ms = ts.d2h_ms; out->sink_ms = ts.sink_ms; out->n_chunks = ts.n_chunks;
     return rc;
 }
 
 }  // namespace
 
-extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                      const uint8_t* d_qual2, int oriented) {
-    return sam_write("sfgpu_sam_write_text", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, sink, user, nullptr,
-                     SFGPU_SAMW_TEXT, out, stream, nullptr);
-}
-
+// ---- the entries: the widest of a family builds the batch, the others forward to it
 extern "C" int sfgpu_sam_write_text_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                      const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    return sam_write("sfgpu_sam_write_text", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, sink, user, nullptr,
-                     SFGPU_SAMW_TEXT, out, stream, nullptr, d_aln_pos, d_aln_op_off, d_aln_ops);
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops);
+    Dest dest;
+    dest.sink = sink; dest.user = user;
+    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+}
+
+extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
+    return sfgpu_sam_write_text_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                    sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    return sfgpu_sam_write_text_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_bgzf_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                      int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
     SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
     SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
-    return sam_write("sfgpu_sam_write_bgzf", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, nullptr, nullptr, z, format,
-                     out, stream, nullptr, d_aln_pos, d_aln_op_off, d_aln_ops);
-}
-
-extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                    void* user, sfgpu_samwrite_result* out, sfgpu_stream stream) {
-    return sfgpu_sam_write_text_q(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1,
-                                  d_seq1_off, d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, nullptr, nullptr, 0);
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops);
+    Dest dest;
+    dest.z = z; dest.format = format;
+    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
 }
 
 extern "C" int sfgpu_sam_write_bgzf_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                      int oriented) {
-    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
-    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
-    return sam_write("sfgpu_sam_write_bgzf", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, chunk_bytes, nullptr, nullptr, z, format,
-                     out, stream, nullptr);
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
+    return sfgpu_sam_write_bgzf_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, nullptr, nullptr, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
@@ -651,17 +574,13 @@ extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_h
                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                     sfgpu_samwrite_result* out, sfgpu_stream stream) {
-    return sfgpu_sam_write_bgzf_q(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1,
-                                  d_seq1_off, d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, nullptr, nullptr, 0);
+    return sfgpu_sam_write_bgzf_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
-// bamsort.h: the batch's BAM records, checked, sized and formatted as for sfgpu_sam_write_bgzf_q, into `store`
-int sfgpu::samw_collect_bam(BamRecordStore* store, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                            const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                            const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                            const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                            const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    return sam_write("sfgpu_bamsort_collect", d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off,
-                     d_seq1, d_seq1_off, d_seq2, d_seq2_off, d_qual1, d_qual2, oriented, read_index_base, 0, nullptr, nullptr, nullptr, SFGPU_SAMW_BAM,
-                     out, stream, store, d_aln_pos, d_aln_op_off, d_aln_ops);
+// bamsort.h: the batch's BAM records, checked, sized and formatted as for sfgpu_sam_write_bgzf_a, into `store`
+int sfgpu::samw_collect_bam(BamRecordStore* store, const SamwArgs& batch, sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    Dest dest;
+    dest.store = store; dest.format = SFGPU_SAMW_BAM;
+    return sam_write("sfgpu_bamsort_collect", batch, 0, dest, out, stream);
 }

@@ -1113,12 +1113,13 @@ class SamDeviceWriter:
             raise TypeError("expected (bytes, 64-bit integer offsets)")
         return b.to(dev).contiguous(), o.to(dev).contiguous()
 
-    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None):
+    def _batch_args(self, hits, offsets, read_names, seqs, quals, alignments):
+        """write()'s arguments as the entries take them: (batch, extra, aln, keepalive) -- the batch of _lib._SAMW_BATCH with chunk_bytes
+        behind it, the qualities and `oriented`, the alignment, and the tensors whose addresses those three hold: the caller keeps
+        `keepalive` referenced until the entry has returned."""
         import torch
 
         from . import _lib, quantfile
-        if self._f is None:
-            raise ValueError("the SAM writer is closed")
         dev = hits.device
         d_hits, d_off = hits.contiguous(), offsets.contiguous()
         n = int(d_off.numel()) - 1
@@ -1158,22 +1159,11 @@ class SamDeviceWriter:
                 if t.numel() != s[m][0].numel():
                     raise ValueError(f"{t.numel()} quality bytes for {s[m][0].numel()} bases")
                 ql[m] = t if t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)     # no base at all: still "given"
-        raised = []
-
-        def sink(addr, nb, _user):
-            try:                                   # nothing may unwind through the C frame
-                self._f.write(memoryview((C.c_char * nb).from_address(addr)))
-                return 0
-            except BaseException as e:             # noqa: BLE001  (re-raised below)
-                raised.append(e)
-                return 1
-
-        res = _lib.SamWriteResult()
         p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
         batch = (p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs, p(q[0]), p(q[1]),
                  p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads, self.chunk_bytes)
         extra = (None if ql[0] is None else _lib.ptr(ql[0]), None if ql[1] is None else _lib.ptr(ql[1]), int(self.oriented))
-        aln = (None, None, None)
+        aln, aln_t = (None, None, None), None
         if alignments is not None:
             a_pos, a_off, a_ops = (alignments[i].to(dev).contiguous() for i in (0, 2, 3))
             if a_pos.element_size() != 4 or a_off.element_size() != 8 or a_ops.element_size() != 4:
@@ -1185,7 +1175,29 @@ class SamDeviceWriter:
                 a_ops = torch.zeros(1, dtype=torch.int32, device=dev)          # no operation at all: still "given"
             if not a_pos.numel():
                 a_pos = torch.zeros(1, dtype=torch.int32, device=dev)
-            aln = (_lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops))
+            aln, aln_t = (_lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops)), (a_pos, a_off, a_ops)
+        return batch, extra, aln, (d_hits, d_off, self._d_names, q, s, ql, aln_t)
+
+    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None):
+        import torch
+
+        from . import _lib
+        if self._f is None:
+            raise ValueError("the SAM writer is closed")
+        dev = hits.device
+        batch, extra, aln, keepalive = self._batch_args(hits, offsets, read_names, seqs, quals, alignments)
+        n = batch[2]
+        raised = []
+
+        def sink(addr, nb, _user):
+            try:                                   # nothing may unwind through the C frame
+                self._f.write(memoryview((C.c_char * nb).from_address(addr)))
+                return 0
+            except BaseException as e:             # noqa: BLE001  (re-raised below)
+                raised.append(e)
+                return 1
+
+        res = _lib.SamWriteResult()
         with torch.cuda.device(dev):
             if self._z is None:
                 rc = self._L.sfgpu_sam_write_text_a(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
@@ -1203,9 +1215,10 @@ class SamDeviceWriter:
             what = {**WRITE_KINDS, **BAM_WRITE_KINDS, **QUAL_WRITE_KINDS}[int(res.error_kind)]
             raise ValueError(f"read {self.n_reads + int(res.error_read)}, record {int(res.error_record)}: {what}")
         _lib.check(rc)
+        del keepalive                              # (referenced up to here: the entry has returned)
         self.n_reads += n
         st = self.stats
-        for k, v in (("reads", n), ("hits", d_hits.numel() // 24), ("lines", res.n_lines), ("bytes", res.n_bytes), ("chunks", res.n_chunks), ("batches", 1)):
+        for k, v in (("reads", n), ("hits", hits.numel() // 24), ("lines", res.n_lines), ("bytes", res.n_bytes), ("chunks", res.n_chunks), ("batches", 1)):
             st[k] += int(v)
         st["ms_format"] += res.format_ms; st["ms_copy"] += res.d2h_ms; st["ms_sink"] += res.sink_ms
         return res.as_dict()

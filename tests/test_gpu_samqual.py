@@ -132,6 +132,37 @@ def test_bgzf_text_and_bam_inflate_to_the_host_statement(gpu, text_corpora, bam_
         assert rc == 0 and got == wants[(False, False)]
 
 
+def _dense(piece, n_bases, tid):
+    """64 single-end reads, each with a name of `piece` bytes, n_bases bases and qualities and one record on the reverse strand of
+    transcript tid (whose name has `piece` bytes too)"""
+    rng = np.random.default_rng(piece)
+    assert len(sw.NAMES[tid]) == piece
+    reads = [((b"dense%02d" % i).ljust(piece, b"q"), corpus._bases(rng, n_bases), [sw.rec(tid, 3, 0, 0, n_bases, 0, 0, 0, 0)]) for i in range(64)]
+    case = dict(sw._case(False, reads), names=sw.NAMES, ref_len=sw.REF_LEN)
+    return dict(case, quals=[corpus._quals(rng, n_bases) for _ in reads])
+
+
+def test_the_job_queue_at_its_densest(gpu):
+    """Every run of every line is one byte longer than what a lane copies itself (49 = kShortCopy + 1), so every name, SEQ and QUAL is
+    queued: four jobs per line of about 225 bytes in the text, as many per tile as the line grammar allows; a job that was dropped
+    would leave zeros in the tile.  In BAM 97 bases pack into 49 bytes.  With 48-byte pieces nothing is queued at all."""
+    text, packed, short = _dense(49, 49, 4), _dense(49, 97, 4), _dense(48, 48, 3)
+    for oriented in (False, True):
+        want = corpus.expected(text, True, oriented)
+        assert 3 * 4096 < len(want) <= 4 * 4096 and want.count(b"\n") == 64
+        rc, res, chunks, _ = _call(text, gpu, True, oriented)
+        got = b"".join(chunks)
+        assert rc == 0 and got == want, (oriented, _first_difference(got, want))
+        want = _records(packed, corpus.expected(packed, True, oriented, header=True))
+        rc, res, _, got = _call(packed, gpu, True, oriented, fmt="bam")
+        assert rc == 0 and got == want, (oriented, _first_difference(got, want))
+        want = corpus.expected(short, True, oriented)
+        rc, res, chunks, _ = _call(short, gpu, True, oriented)
+        got = b"".join(chunks)
+        assert rc == 0 and got == want, (oriented, _first_difference(got, want))
+    assert corpus.expected(text, True, True) != corpus.expected(text, True, False)
+
+
 @pytest.mark.parametrize("paired", [True, False], ids=["paired", "single"])
 def test_quality_bytes_that_cannot_be_written(gpu, paired):
     from sailfish_amd import _lib, samfile

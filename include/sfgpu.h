@@ -751,6 +751,23 @@ SFGPU_API int sfgpu_sam_write_text_a(const struct sfgpu_hit* d_hits, const uint3
                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
                                      const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
                                      const uint32_t* d_aln_ops);
+/* sfgpu_sam_write_text_a with the batch's NM / MD tags (sfgpu_hits_md_tags' d_nm, d_md_off, d_md for the same records and the same
+ * alignment: slot 2 h + which is line `which` of record h); sfgpu_sam_write_text_a is this call with tags == NULL, and then every
+ * byte is the same.  Given, a mapped line ends ... QUAL \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh> \n, nh being the read's record count
+ * d_hit_offsets[r + 1] - d_hit_offsets[r]; the lines of a read without records carry no tags.  The three pointers go together, and
+ * tags need the mates' bases (d_seq1_off, and d_seq2_off of a paired batch): SFGPU_ERR_INVALID otherwise. */
+typedef struct sfgpu_samw_tags {
+    const uint32_t* d_nm;        /* [2 n] */
+    const uint64_t* d_md_off;    /* [2 n + 1] */
+    const uint8_t* d_md;
+} sfgpu_samw_tags;
+SFGPU_API int sfgpu_sam_write_text_t(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
+                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
+                                     const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
@@ -862,6 +879,16 @@ SFGPU_API int sfgpu_sam_write_bgzf_a(const struct sfgpu_hit* d_hits, const uint3
                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
                                      int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
+/* ... and with the batch's NM / MD tags, as sfgpu_sam_write_text_t; with tags == NULL this is sfgpu_sam_write_bgzf_a, byte for byte.
+ * SFGPU_SAMW_BAM: a mapped line's record ends, behind QUAL, NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>, <t> being the first of
+ * c C s S i I that holds the value, and block_size counts them: the bytes of sam_to_bam of the tagged text. */
+SFGPU_API int sfgpu_sam_write_bgzf_t(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
+                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
+                                     const sfgpu_samw_tags* tags);
 /* The compressed size of every member a BGZF handle writes, kept on the device: what virtual file offsets are made of.
  *   track_members  from this call on every write also keeps its members' sizes (4 bytes a member of device memory, in file order).
  *                  The bytes written, the results and the other calls do not change.
@@ -916,6 +943,14 @@ SFGPU_API int sfgpu_bamsort_collect_a(sfgpu_bamsort* b, const struct sfgpu_hit* 
                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
                                       const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
+/* collect with the batch's NM / MD tags, as sfgpu_sam_write_bgzf_t (tags == NULL: sfgpu_bamsort_collect_a, byte for byte).  The sort
+ * key, the bin and the index come from the record's own position and CIGAR, so tags change none of them. */
+SFGPU_API int sfgpu_bamsort_collect_t(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
+                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
 SFGPU_API int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,
                                    void* user, sfgpu_bamsort_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);
@@ -1393,6 +1428,36 @@ SFGPU_API int sfgpu_hits_align_gapped(const sfgpu_index* idx, const char* d_seq1
                                       uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_align_gopts* opts,
                                       int32_t* d_pos, uint32_t* d_nm, uint64_t* d_op_off, uint32_t* d_ops, uint64_t cap_ops, uint64_t* n_ops,
                                       sfgpu_align_gstats* stats, sfgpu_stream stream);
+
+/* The NM and MD tags of the lines a mappings file holds for these records (the rule is stated once in csrc/mdfmt.h;
+ * hits.md_tags_host is the Python statement).  Records, reads, jobs, base codes and orientation are sfgpu_hits_align_gapped's.
+ *   slots   two per record: slot 2 h + which is line `which` of record h; a record's missing second slot has nm 0 and no MD byte.
+ *   cigar   d_aln_pos / d_aln_op_off / d_aln_ops (sfgpu_hits_align_gapped's d_pos, d_op_off, d_ops for the same records; all three
+ *           or none, anything else: SFGPU_ERR_INVALID): the slot's words at POS - 1 = d_aln_pos[slot].  Without them the line's
+ *           ungapped CIGAR, <clip>S<match>M from the record's pos and read_len (mate_pos and mate_len on the second line).  A line
+ *           the writer refuses (no base on the transcript; a slot without an operation) has nm 0 and MD "0".
+ *   walk    over the ORIENTED mate and the transcript from POS - 1.  An M / = / X column is a mismatch iff it lies off the
+ *           transcript or past the mate's bases, or either base is not A C G T, or the bases differ: <run><reference character>,
+ *           nm + 1; else the run of matches grows.  I n: nm + n.  D n / N n: <run>^<n reference characters>, nm + n.  At the end
+ *           <run>.  The reference character is the transcript's byte upper-cased, N where that is no letter or off the transcript.
+ *           For a slot sfgpu_hits_align_gapped produced, nm equals its d_nm.
+ *   output  d_nm[2 n], d_md_off[2 n + 1] (CSR over the slots, n = d_hit_offsets[n_reads]), d_md[] (room for cap_md bytes; no
+ *           terminator).  *n_md = the bytes needed.  They do not fit cap_md: SFGPU_ERR_RANGE, *n_md is still set and nothing is
+ *           written.  NH is not an output: it is d_hit_offsets[r + 1] - d_hit_offsets[r], which the writer reads itself.
+ *   errors  the outputs untouched: tid >= M: SFGPU_ERR_RANGE naming the lowest record; NULL pointers, a record naming mate 2 of a
+ *           single-end batch: SFGPU_ERR_INVALID.
+ * Mates and operations shorter than 2^28 bases.  Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_mdtag_stats {
+    uint64_t slots;                   /* slots that are a line */
+    uint64_t sum_nm;
+    uint64_t md_bytes;                /* over all slots */
+    uint64_t max_md_bytes;            /* of the longest MD */
+    uint64_t slots_plain;             /* lines whose CIGAR is one M operation and whose nm is 0: the MD is <len> */
+} sfgpu_mdtag_stats;
+SFGPU_API int sfgpu_hits_md_tags(const sfgpu_index* idx, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                 uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const int32_t* d_aln_pos,
+                                 const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, uint32_t* d_nm, uint64_t* d_md_off, uint8_t* d_md,
+                                 uint64_t cap_md, uint64_t* n_md, sfgpu_mdtag_stats* stats, sfgpu_stream stream);
 
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,

@@ -236,6 +236,13 @@ class AlignGStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class MdTagStats(C.Structure):
+    _fields_ = [("slots", C.c_uint64), ("sum_nm", C.c_uint64), ("md_bytes", C.c_uint64), ("max_md_bytes", C.c_uint64), ("slots_plain", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class BiasSampler(C.Structure):
     _fields_ = [("d_seq", C.c_void_p), ("d_seq_off", C.c_void_p), ("d_ref_len", C.c_void_p), ("d_read_bias", C.c_void_p),
                 ("remaining_bias_samples", C.POINTER(C.c_int64)), ("d_observed_gc", C.c_void_p), ("d_gc_prefix", C.c_void_p),
@@ -267,6 +274,13 @@ _SAMW_BATCH = [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, 
 _SAMW_OUT = [C.POINTER(SamWriteResult), _P]
 _SAMW_QUAL = [_P, _P, C.c_int]
 _SAMW_ALN = [_P, _P, _P]
+
+
+class SamwTags(C.Structure):
+    _fields_ = [("d_nm", C.c_void_p), ("d_md_off", C.c_void_p), ("d_md", C.c_void_p)]
+
+
+_SAMW_TAGS = [C.POINTER(SamwTags)]
 
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
@@ -332,6 +346,7 @@ _SIGS = {
     "sfgpu_sam_write_text": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT]),
     "sfgpu_sam_write_text_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_sam_write_text_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
+    "sfgpu_sam_write_text_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -343,11 +358,13 @@ _SIGS = {
     "sfgpu_bamsort_open": (C.c_int, [C.POINTER(_P)]),
     "sfgpu_bamsort_collect": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_bamsort_collect_a": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
+    "sfgpu_bamsort_collect_t": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
     "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
     "sfgpu_bamsort_close": (C.c_int, [_P]),
     "sfgpu_sam_write_bgzf": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT]),
     "sfgpu_sam_write_bgzf_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_sam_write_bgzf_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
+    "sfgpu_sam_write_bgzf_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -368,6 +385,8 @@ _SIGS = {
                                            C.POINTER(VerifyGStats), _P]),
     "sfgpu_hits_align_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(AlignGOpts), _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(AlignGStats), _P]),
+    "sfgpu_hits_md_tags": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(MdTagStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

@@ -20,6 +20,8 @@
 //   4  bases given whose number differs from the line's read length (clip + match; an unmapped line has none to differ from), or
 //      more than 65 535 bases
 //   5  the alignment ends beyond 2^29: pos + match > 2^29
+// With tags given (samwfmt.h: samw_tags) a mapped line's record ends, behind QUAL, NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>, <t>
+// being the first of c C s S i I that holds the value (what sam_to_bam picks), and block_size counts them.
 // With an alignment given (samwfmt.h: samw_line) the CIGAR words are the slot's; bin and rule 5 take the reference span (M + D) for
 // `match`, rule 4 compares the bases with the read bases the CIGAR names (S + M + I) and also covers more than 65 535 operations.
 #pragma once
@@ -100,10 +102,27 @@ SAMW_HD int bamw_check(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64
     return bamw_check(a, r, h, rank, h ? (uint64_t)(h - a.hits) : 0ull);
 }
 
+// an integer tag's type, the first of c C s S i I that holds v, and its value's bytes
+SAMW_HD char bamw_int_type(uint32_t v) { return v <= 127u ? 'c' : v <= 255u ? 'C' : v <= 32767u ? 's' : v <= 65535u ? 'S' : v <= 0x7fffffffu ? 'i' : 'I'; }
+SAMW_HD uint32_t bamw_int_bytes(uint32_t v) { return v <= 255u ? 1u : v <= 65535u ? 2u : 4u; }
+// tag, type and value through put(i, byte) -> their bytes
+template <typename Put>
+SAMW_HD uint32_t bamw_put_int_tag(char t0, char t1, uint32_t v, Put put) {
+    const uint32_t n = bamw_int_bytes(v);
+    put(0, (uint8_t)t0); put(1, (uint8_t)t1); put(2, (uint8_t)bamw_int_type(v));
+    for (uint32_t i = 0; i < n; ++i) put(3 + (int)i, (uint8_t)(v >> (8 * i)));
+    return 3u + n;
+}
+// the bytes behind QUAL
+SAMW_HD uint64_t bamw_tags_len(const SamwArgs& a, const SamwLine& l, uint64_t r) {
+    SamwTags t;
+    if (!samw_tags(a, l, r, &t)) return 0;
+    return 3ull + bamw_int_bytes(t.nm) + 3ull + t.md_len + 1ull + 3ull + bamw_int_bytes(t.nh);
+}
 SAMW_HD uint64_t bamw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r) {
     const uint8_t* seq;
     const uint64_t n = bamw_l_seq(a, l, r, &seq);
-    return kBamwFixed + samw_qname_len(a, r) + 1u + 4u * bamw_cigar_ops(l) + (n + 1) / 2 + n;
+    return kBamwFixed + samw_qname_len(a, r) + 1u + 4u * bamw_cigar_ops(l) + (n + 1) / 2 + n + bamw_tags_len(a, l, r);
 }
 SAMW_HD uint64_t bamw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
     const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
@@ -177,6 +196,14 @@ inline int bamw_serial(const SamwArgs& a, uint8_t* out, SamwSerial* res) {
             uint64_t ql;
             const bool given = samw_qual(a, l, r, &q, &ql);
             for (uint64_t i = 0; i < n; ++i) *p++ = given ? (uint8_t)((rev ? q[n - 1 - i] : q[i]) - 33u) : (uint8_t)0xff;
+            SamwTags t;
+            if (samw_tags(a, l, r, &t)) {
+                p += bamw_put_int_tag('N', 'M', t.nm, [&](int i, uint8_t b) { p[i] = b; });
+                *p++ = 'M'; *p++ = 'D'; *p++ = 'Z';
+                for (uint64_t i = 0; i < t.md_len; ++i) *p++ = t.md[i];
+                *p++ = 0;
+                p += bamw_put_int_tag('N', 'H', t.nh, [&](int i, uint8_t b) { p[i] = b; });
+            }
         }
         at += len;
         res->n_lines++;

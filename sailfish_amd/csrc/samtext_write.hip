@@ -233,6 +233,14 @@ struct TextFmt {
         out.byte('\t');
         if (samw_qual(a, c.l, c.r, &src, &n)) out.run(rev ? kCopyRev : kCopy, src, n, n);
         else out.byte('*');
+        SamwTags t;
+        if (samw_tags(a, c.l, c.r, &t)) {                 // \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh>; a long MD is a run like a name
+            out.skip(samw_put_int_tag('N', 'M', t.nm, put));
+            samw_put_md_lead(put);
+            out.skip(kSamwTagLead);
+            out.run(kCopy, t.md, t.md_len, t.md_len);
+            out.skip(samw_put_int_tag('N', 'H', t.nh, put));
+        }
         out.byte('\n');
     }
 };
@@ -275,6 +283,14 @@ struct BamFmt {
         uint64_t ql;
         if (samw_qual(a, c.l, c.r, &qual, &ql)) out.run(rev ? kQualRev : kQual, qual, n_bases, n_bases);
         else out.run(kFill, seq, n_bases, n_bases);       // (the source of a kFill run is never read)
+        SamwTags t;
+        if (samw_tags(a, c.l, c.r, &t)) {                 // NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>
+            out.skip(bamw_put_int_tag('N', 'M', t.nm, put));
+            out.byte('M'); out.byte('D'); out.byte('Z');
+            out.run(kCopy, t.md, t.md_len, t.md_len);
+            out.byte(0);
+            out.skip(bamw_put_int_tag('N', 'H', t.nh, put));
+        }
     }
 };
 
@@ -370,6 +386,8 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
     if (!((!in.qual1 || in.seq1_off) && (!in.qual2 || in.seq2_off))) return fail(SFGPU_ERR_INVALID, "qualities of a mate whose bases are not given");
     if (!(n_reads < 0xffffffffu)) return fail(SFGPU_ERR_RANGE, "n_reads must be below 2^32 - 1");
     if (!((in.aln_pos != nullptr) == (in.aln_op_off != nullptr) && (!in.aln_ops || in.aln_pos))) return fail(SFGPU_ERR_INVALID, "an alignment is positions, offsets and operations together");
+    if (!((in.tag_nm != nullptr) == (in.tag_md_off != nullptr) && (in.tag_nm != nullptr) == (in.tag_md != nullptr))) return fail(SFGPU_ERR_INVALID, "tags are nm, MD offsets and MD bytes together");
+    if (in.tag_nm && !(in.seq1_off && (!in.paired || in.seq2_off))) return fail(SFGPU_ERR_INVALID, "tags of mates whose bases are not given");
     SamwArgs a = in;
     if (!a.paired) { a.seq2 = nullptr; a.seq2_off = nullptr; a.qual2 = nullptr; }
     a.oriented = a.oriented != 0;
@@ -514,17 +532,27 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
 }  // namespace
 
 // ---- the entries: the widest of a family builds the batch, the others forward to it
+extern "C" int sfgpu_sam_write_text_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags);
+    Dest dest;
+    dest.sink = sink; dest.user = user;
+    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+}
+
 extern "C" int sfgpu_sam_write_text_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                       sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
                                       const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops);
-    Dest dest;
-    dest.sink = sink; dest.user = user;
-    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+    return sfgpu_sam_write_text_t(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
@@ -545,19 +573,29 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
                                   d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
+extern "C" int sfgpu_sam_write_bgzf_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
+    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
+    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags);
+    Dest dest;
+    dest.z = z; dest.format = format;
+    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
+}
+
 extern "C" int sfgpu_sam_write_bgzf_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                       sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
                                       const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
-    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops);
-    Dest dest;
-    dest.z = z; dest.format = format;
-    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
+    return sfgpu_sam_write_bgzf_t(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_bgzf_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,

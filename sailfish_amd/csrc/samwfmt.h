@@ -34,6 +34,10 @@
 //          slot's words len << 4 | op (MIDNSHP=X), PNEXT is the other line's POS written this way; FLAG and TLEN stay.  The position
 //          rule is then the slot's: a line whose slot has no operation has no base on the transcript (SAMW_BAD_POS), and the record's
 //          own pos is not consulted.  Without them every byte is what it is above.
+//   Tags: with tag_nm / tag_md_off / tag_md given (sfgpu_hits_md_tags' outputs for the same records and the same alignment, two
+//          slots per record as above; csrc/mdfmt.h) a mapped line ends ... QUAL \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh> \n, nh being the
+//          read's record count hit_off[r + 1] - hit_off[r].  The lines of a read without records carry no tags.  Without them every
+//          byte is what it is above.
 #pragma once
 #include <cstdint>
 
@@ -81,6 +85,7 @@ struct SamwLine {
     uint8_t mapped;              // RNAME is the name of the record's tid; else '*'
     uint8_t rnext;               // '=' or '*'
     uint8_t mate2;               // SEQ is mate 2's
+    uint64_t slot;               // of a record's line: 2 * (the record's index) + which, where its alignment and its tags lie
 };
 
 SAMW_HD uint32_t samw_record_lines(const sfgpu_hit& h) { return h.mate_status == 3 ? 2u : 1u; }
@@ -108,7 +113,7 @@ SAMW_HD SamwLine samw_record_line(const sfgpu_hit& h, uint64_t rank, uint32_t wh
     const uint32_t sec = rank ? 0x100u : 0u, st = h.mate_status;
     uint32_t p1, c1, m1;
     samw_aligned(h.pos, h.read_len, &p1, &c1, &m1);
-    l.mapped = 1; l.ops = nullptr; l.n_ops = 0;
+    l.mapped = 1; l.ops = nullptr; l.n_ops = 0; l.slot = 0;
     if (st == 3) {
         uint32_t p2, c2, m2;
         samw_aligned(h.mate_pos, h.mate_len, &p2, &c2, &m2);
@@ -142,7 +147,7 @@ SAMW_HD SamwLine samw_empty_line(bool paired, uint32_t which) {
     SamwLine l;
     l.flag = paired ? (which ? 141u : 77u) : 4u;
     l.pos = 0; l.clip = 0; l.match = 0; l.pnext = 0; l.tlen = 0;
-    l.ops = nullptr; l.n_ops = 0; l.ref_span = 0; l.query = 0;
+    l.ops = nullptr; l.n_ops = 0; l.ref_span = 0; l.query = 0; l.slot = 0;
     l.mapped = 0; l.rnext = '*'; l.mate2 = (uint8_t)(paired && which);
     return l;
 }
@@ -230,14 +235,18 @@ struct SamwArgs {
     const int32_t* aln_pos = nullptr;        // [2 * records] sfgpu_hits_align_gapped's d_pos, or nullptr: no alignment is given
     const uint64_t* aln_op_off = nullptr;    // [2 * records + 1]
     const uint32_t* aln_ops = nullptr;
+    const uint32_t* tag_nm = nullptr;        // [2 * records] sfgpu_hits_md_tags' d_nm, or nullptr: no tags are written
+    const uint64_t* tag_md_off = nullptr;    // [2 * records + 1]
+    const uint8_t* tag_md = nullptr;
 };
 
 // The lines of a record WITH the batch's alignment, where one is given.  `hidx` is the record's index in a.hits: its slots are
 // 2 * hidx and 2 * hidx + 1 (h itself may be a copy of the record, as in the kernels).
 SAMW_HD SamwLine samw_line(const SamwArgs& a, const sfgpu_hit& h, uint64_t rank, uint32_t which, uint64_t hidx) {
     SamwLine l = samw_record_line(h, rank, which);
-    if (!a.aln_pos) return l;
     const uint64_t slot = 2 * hidx + which;
+    l.slot = slot;
+    if (!a.aln_pos) return l;
     l.pos = (uint32_t)a.aln_pos[slot] + 1u;
     if (h.mate_status == 3) l.pnext = (uint32_t)a.aln_pos[slot ^ 1ull] + 1u;
     l.clip = 0; l.match = 0; l.ref_span = 0; l.query = 0;
@@ -287,12 +296,38 @@ SAMW_HD bool samw_qual(const SamwArgs& a, const SamwLine& l, uint64_t r, const u
 }
 // SEQ and QUAL of the line go on the reference's strand
 SAMW_HD bool samw_reversed(const SamwArgs& a, const SamwLine& l) { return a.oriented != 0 && (l.flag & 0x10u) != 0; }
+// the tags of the line of read r: whether it carries any, and NM, NH and the MD's bytes
+struct SamwTags { uint32_t nm, nh; const uint8_t* md; uint64_t md_len; };
+SAMW_HD bool samw_tags(const SamwArgs& a, const SamwLine& l, uint64_t r, SamwTags* t) {
+    if (!a.tag_nm || !l.mapped) return false;
+    t->nm = a.tag_nm[l.slot]; t->nh = a.hit_off[r + 1] - a.hit_off[r];
+    t->md_len = a.tag_md_off[l.slot + 1] - a.tag_md_off[l.slot];
+    t->md = a.tag_md + a.tag_md_off[l.slot];
+    return true;
+}
+constexpr uint32_t kSamwTagLead = 6;              // \t NM:i:   \t MD:Z:   \t NH:i:
+// the bytes between QUAL and the line's \n
+SAMW_HD uint64_t samw_tags_len(const SamwArgs& a, const SamwLine& l, uint64_t r) {
+    SamwTags t;
+    if (!samw_tags(a, l, r, &t)) return 0;
+    return 3ull * kSamwTagLead + (uint64_t)dec_len_u32(t.nm) + t.md_len + (uint64_t)dec_len_u32(t.nh);
+}
+// \t <tag> :i: <v> through put(i, ch) -> its bytes
+template <typename Put>
+SAMW_HD uint32_t samw_put_int_tag(char t0, char t1, uint32_t v, Put put) {
+    put(0, '\t'); put(1, t0); put(2, t1); put(3, ':'); put(4, 'i'); put(5, ':');
+    const int nd = dec_len_u32(v);
+    dec_put_fixed_u32(v, nd, 0, [&](int i, char ch) { put((int)kSamwTagLead + nd - 1 - i, ch); });
+    return kSamwTagLead + (uint32_t)nd;
+}
+template <typename Put>
+SAMW_HD void samw_put_md_lead(Put put) { put(0, '\t'); put(1, 'M'); put(2, 'D'); put(3, ':'); put(4, 'Z'); put(5, ':'); }
 SAMW_HD uint64_t samw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t tid) {
     const uint8_t* p;
     uint64_t sl, ql;
     (void)samw_seq(a, l, r, &p, &sl);
     (void)samw_qual(a, l, r, &p, &ql);
-    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail;
+    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail + samw_tags_len(a, l, r);
 }
 // the bytes of unit (read r, record h of rank `rank` and index hidx in a.hits; h == nullptr: the read has no record)
 SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
@@ -369,6 +404,13 @@ inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
             *p++ = '\t';
             if (samw_qual(a, l, r, &s, &sl)) for (uint64_t i = 0; i < sl; ++i) *p++ = (char)(rev ? s[sl - 1 - i] : s[i]);
             else *p++ = '*';
+            SamwTags t;
+            if (samw_tags(a, l, r, &t)) {
+                p += samw_put_int_tag('N', 'M', t.nm, [&](int i, char ch) { p[i] = ch; });
+                samw_put_md_lead([&](int i, char ch) { p[i] = ch; }); p += kSamwTagLead;
+                for (uint64_t i = 0; i < t.md_len; ++i) *p++ = (char)t.md[i];
+                p += samw_put_int_tag('N', 'H', t.nh, [&](int i, char ch) { p[i] = ch; });
+            }
             *p++ = '\n';
         }
         at += len;

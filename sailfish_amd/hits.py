@@ -514,6 +514,138 @@ def align_hits(index, hits, offsets, reads1, reads2=None, *, max_indel, scratch_
     return pos, nm, op_off, ops[: need.value], st.as_dict()
 
 
+MDTAG_STATS = ("slots", "sum_nm", "md_bytes", "max_md_bytes", "slots_plain")
+_MATCH_OPS, _DEL_OPS = (0, 7, 8), (2, 3)                                              # M = X; D N
+
+
+def _md_ref_char(t, x):
+    """the reference character of csrc/mdfmt.h: the transcript's byte upper-cased, N where that is no letter or off the transcript"""
+    if x < 0 or x >= len(t):
+        return 78
+    b = t[x] - 32 if 97 <= t[x] <= 122 else t[x]
+    return b if 65 <= b <= 90 else 78
+
+
+def _md_slot_host(words, x, a, t, tcode):
+    """One slot by the rule of csrc/mdfmt.h: words = the line's CIGAR (len << 4 | op), x = POS - 1, a = the mate's oriented codes,
+    t / tcode = the transcript's bytes and codes -> (nm, the MD's bytes)"""
+    q, run, nm, md = 0, 0, 0, bytearray()
+    for w in words:
+        n, op = int(w) >> 4, int(w) & 15
+        if op == CIGAR_S:
+            q += n
+        elif op == CIGAR_I:
+            q += n; nm += n
+        elif op in _DEL_OPS:
+            md += b"%d^" % run
+            md += bytes(_md_ref_char(t, x + j) for j in range(n))
+            run = 0; nm += n; x += n
+        elif op in _MATCH_OPS:
+            for _ in range(n):
+                if x < 0 or x >= len(t) or q >= len(a) or a[q] > 3 or tcode[x] > 3 or a[q] != tcode[x]:
+                    md += b"%d" % run
+                    md.append(_md_ref_char(t, x))
+                    run = 0; nm += 1
+                else:
+                    run += 1
+                q += 1; x += 1
+    md += b"%d" % run
+    return nm, bytes(md)
+
+
+def md_tags_host(transcripts, hits, offsets, reads1, reads2, alignments=None):
+    """The statement of the NM and MD tags of a mappings file's lines (csrc/mdfmt.h restated; what sfgpu_hits_md_tags is judged by),
+    in plain loops.  Arguments as verify_hits_host; alignments: what align_hits / align_hits_host returned for the same records
+    (pos, nm, op_off, ops, ...), or None.  Two slots per record: slot 2 h + which is line `which` of record h, its mate, strand and
+    bases those of _record_jobs.  The line's CIGAR is the one the writer writes: the slot's words at POS - 1 = pos[slot] with an
+    alignment, else <clip>S<match>M from the record's pos and read_len (mate_pos and mate_len on the second line); a line the writer
+    refuses (no base on the transcript, a slot without an operation) has no operation: nm 0, MD "0".  It is walked over the oriented
+    mate: S skips read bases; an M / = / X column off the transcript, past the mate's bases, with a base that is not A C G T, or with
+    differing bases is <run><reference character> and nm + 1, else the run grows; I n is nm + n; D n / N n is <run>^<n reference
+    characters> and nm + n; <run> ends the MD.  A record's missing second slot has nm 0 and an empty MD.
+    -> (nm uint32[2 n], md_off uint64[2 n + 1], md uint8[], stats dict (MDTAG_STATS)).  ValueError naming the lowest record whose
+    tid is not a transcript."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    n_rec = int(off[-1]) if len(off) else 0
+    bad = np.nonzero(hits["tid"][:n_rec] >= len(transcripts))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(transcripts)}")
+    aln = None
+    if alignments is not None:
+        host = lambda v, dt: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)).view(dt).reshape(-1)
+        aln = host(alignments[0], np.int32), host(alignments[2], np.uint64), host(alignments[3], np.uint32)
+        if len(aln[0]) != 2 * n_rec or len(aln[1]) != 2 * n_rec + 1:
+            raise ValueError(f"an alignment of {len(aln[0])} slots for {n_rec} records (two slots a record)")
+    nm, md_off, md = np.zeros(2 * n_rec, np.uint32), np.zeros(2 * n_rec + 1, np.uint64), []
+    stats = dict.fromkeys(MDTAG_STATS, 0)
+    tcodes = {}
+    for r in range(len(off) - 1):
+        for i in range(off[r], off[r + 1]):
+            h = hits[i]
+            tid = int(h["tid"])
+            if tid not in tcodes:
+                tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)].tolist()
+            for j, (rd, fwd, _) in enumerate(_record_jobs(h, r, reads1, reads2)):
+                s = 2 * i + j
+                if aln is not None:
+                    words, x = aln[2][int(aln[1][s]):int(aln[1][s + 1])].tolist(), int(aln[0][s])
+                else:
+                    pos, length = (int(h["mate_pos"]), int(h["mate_len"])) if j else (int(h["pos"]), int(h["read_len"]))
+                    if pos >= 0:
+                        words, x = [length << 4], pos
+                    elif -pos < length:
+                        words, x = [-pos << 4 | CIGAR_S, (length + pos) << 4], 0
+                    else:
+                        words, x = [], 0
+                got, text = _md_slot_host(words, x, _oriented_codes(rd, fwd).tolist(), transcripts[tid], tcodes[tid])
+                nm[s], md_off[s + 1] = got, len(text)
+                md.append(text)
+                stats["slots"] += 1
+                stats["sum_nm"] += got
+                stats["md_bytes"] += len(text)
+                stats["max_md_bytes"] = max(stats["max_md_bytes"], len(text))
+                stats["slots_plain"] += int(len(words) == 1 and words[0] & 15 == CIGAR_M and got == 0)
+    return nm, np.cumsum(md_off, dtype=np.uint64), np.frombuffer(b"".join(md), np.uint8), stats
+
+
+def md_tags(index, hits, offsets, reads1, reads2=None, alignments=None):
+    """The NM and MD tags of hit records on the device (sfgpu_hits_md_tags; the rule is md_tags_host's).  Arguments as verify_hits;
+    alignments: what align_hits returned for the same records (pos, nm, op_off, ops, ...) or None for the ungapped lines.  The MD's
+    room is sized at four bytes a slot and the call repeated once with the count the library reports where they do not fit.
+    -> (nm int32[2 n] (the bits of uint32), md_off int64[2 n + 1], md uint8[], stats dict (MDTAG_STATS)): device tensors, two slots
+    per record (slot 2 h + which is line `which` of record h).  NH is no output: it is the read's record count, offsets[r + 1] -
+    offsets[r]."""
+    dev, d_hits, d_off, R, s1, o1, s2, o2, n = _device_batch(index, hits, offsets, reads1, reads2)
+    a_pos = a_off = a_ops = None
+    if alignments is not None:
+        signed = {4: np.int32, 8: np.int64}
+        a_pos, a_off, a_ops = ((v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v).view(signed[v.dtype.itemsize]).copy())).to(dev).contiguous()
+                               for v in (alignments[0], alignments[2], alignments[3]))
+        if int(a_pos.numel()) != 2 * n or int(a_off.numel()) != 2 * n + 1:
+            raise ValueError(f"an alignment of {int(a_pos.numel())} slots for {n} records (two slots a record)")
+        if int(a_ops.numel()) == 0:
+            a_ops = torch.zeros(1, dtype=torch.int32, device=dev)
+    nm = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+    md_off = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
+    st = _lib.MdTagStats()
+    need = C.c_uint64(0)
+    cap = max(8 * n, 1)
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        for attempt in range(2):
+            md = torch.empty(cap, dtype=torch.uint8, device=dev)
+            rc = _lib.lib().sfgpu_hits_md_tags(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                               _lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops), _lib.ptr(nm), _lib.ptr(md_off), _lib.ptr(md), cap,
+                                               C.byref(need), C.byref(st), _lib.current_stream_ptr())
+            if rc == _lib.ERR_RANGE and attempt == 0 and need.value > cap:
+                cap = int(need.value)
+                continue
+            _lib.check(rc)
+            break
+    return nm, md_off, md[: need.value], st.as_dict()
+
+
 def gc_prefix(seq, seq_off, ref_len):
     """Transcript::GCCount_ of every transcript (include/Transcript.hpp:183-196), laid out like `seq`: int32 device
     tensor of seq.numel() entries (4 bytes per base) -- what sample_bias reads for the fragment-GC samples."""

@@ -66,15 +66,21 @@ class QuasiIndex:
         _lib.check(self._L.sfgpu_index_set_seeds(self._h, int(seeds)))
         self.seeds = int(seeds)
 
-    def map_reads(self, reads1, reads2=None, validate=None):
+    def map_reads(self, reads1, reads2=None, validate=None, tags=False):
         """reads1 / reads2: lists of str / bytes, or (uint8 tensor, int64 offsets) pairs already packed.
         validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best, max_indel; {} = its defaults): the records are then
         verified against the transcripts' bases before they are returned, and `last_scores` / `last_verify_stats` hold the
         survivors' scores and the pass's counters.  With "align": True beside a max_indel of 1 .. 15 (else ValueError) the survivors
         are then aligned with gaps (hits.align_hits): `last_alignments` holds (pos, nm, op_off, ops), two slots per surviving record,
         as SamDeviceWriter.write(alignments=) takes them, and `last_align_stats` the pass's counters.
+        "tags": True in `validate`, or tags=True where nothing is validated: the NM / MD tags of the records that are returned
+        (hits.md_tags, over `last_alignments` where there are any) are left as `last_tags` = (nm, md_off, md), as
+        SamDeviceWriter.write(tags=) takes them, with the pass's counters as `last_tag_stats`; both are None otherwise.
         -> (hits: uint8 device tensor [n_hits * 24] of HIT_DTYPE records, offsets: int32 device tensor [R + 1])"""
         align = False
+        if validate is not None and "tags" in validate:
+            validate = dict(validate)
+            tags = bool(validate.pop("tags")) or bool(tags)
         if validate is not None and "align" in validate:
             validate = dict(validate)
             align = bool(validate.pop("align"))
@@ -111,6 +117,12 @@ class QuasiIndex:
                 from .hits import align_hits
                 *aln, self.last_align_stats = align_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), max_indel=validate["max_indel"])
                 self.last_alignments = tuple(aln)
+        self.last_tags = self.last_tag_stats = None
+        if tags:
+            from .hits import md_tags
+            *t, self.last_tag_stats = md_tags(self, hits, off, (s1, o1), None if s2 is None else (s2, o2),
+                                              alignments=self.last_alignments if validate is not None else None)
+            self.last_tags = tuple(t)
         return hits, off
 
     def close(self):
@@ -179,6 +191,33 @@ def _report_align_stats(exp, total, sopt):
                "{} mates unalignable".format(total["jobs_traced"], total["jobs"], total["sum_nm"], total["unalignable"]))
 
 
+def _tagged_mappings(mappings_tags, write_mappings, mappings_oriented):
+    """mappings_tags= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless there is a mappings
+    file and it is oriented (NM and MD describe the read on the transcript's strand).  -> the counters to accumulate, or None"""
+    if not mappings_tags:
+        return None
+    if write_mappings is None or not mappings_oriented:
+        raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
+    from .hits import MDTAG_STATS
+    return dict.fromkeys(MDTAG_STATS, 0)
+
+
+def _add_tag_stats(total, idx):
+    if total is not None:
+        for key, v in idx.last_tag_stats.items():
+            total[key] = max(total[key], v) if key == "max_md_bytes" else total[key] + v
+
+
+def _report_tag_stats(exp, total, sopt):
+    """the tag pass's counters: on the experiment as `tag_stats` (None when it did not run) and as one log line"""
+    if exp is not None:
+        exp.tag_stats = total
+    log = getattr(sopt, "jointLog", None) if sopt is not None else None
+    if total is not None and log is not None:
+        log(0, "tagged mappings: NM, MD and NH on {} lines, {} of them <len>M without a mismatch; NM sums to {}; {} MD bytes, the longest MD {}".format(
+            total["slots"], total["slots_plain"], total["sum_nm"], total["md_bytes"], total["max_md_bytes"]))
+
+
 def _report_verify_stats(exp, total, validate, sopt):
     """the accumulated counters: on the experiment as `verify_stats` (None when the pass did not run) and as one log line"""
     if exp is not None:
@@ -207,7 +246,7 @@ def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -230,11 +269,17 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     mate hangs over an end), PNEXT following; with every mappings_format, mappings_oriented and mappings_sorted.  The estimates never
     depend on it; the counters are left on the experiment as `align_stats` and go to sopt.jointLog as one line.  (A surviving mate
     with no base on its transcript -- possible only at a min_identity near 0 -- fails the batch, as it does without the option.)
+    mappings_tags=True (it needs write_mappings and mappings_oriented=True, else ValueError before anything is indexed: NM and MD
+    describe the read on the transcript's strand) ends every mapped line with NM:i: (the line's edit distance), MD:Z: (its mismatch
+    string) and NH:i: (the read's record count), computed on the device after validation and alignment for the surviving records
+    (hits.md_tags), with every mappings_format, with mappings_sorted, and with and without mappings_gapped and validate_mappings.  The
+    estimates never depend on it; the counters are left on the experiment as `tag_stats` and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     _check_mappings_sorted(mappings_sorted, mappings_format)
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
+    tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
     sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -249,12 +294,13 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
                 r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
                 q1 = None if quals1 is None else pack_sequences(quals1[a:b])[0].to(idx.device)
                 q2 = None if quals2 is None or r2 is None else pack_sequences(quals2[a:b])[0].to(idx.device)
-            h, o = idx.map_reads(r1, r2, validate=validate)
+            h, o = idx.map_reads(r1, r2, validate=validate, tags=tstats is not None)
             _add_verify_stats(vstats, idx)
             _add_align_stats(astats, idx)
+            _add_tag_stats(tstats, idx)
             if sam is not None:
                 sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                          alignments=idx.last_alignments if astats is not None else None)
+                          alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
             yield h, o
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
@@ -268,6 +314,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
     _report_align_stats(exp, astats, sopt)
+    _report_tag_stats(exp, tstats, sopt)
     return rc, exp
 
 
@@ -282,7 +329,7 @@ def _dollar_separated(bases, off):
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -292,14 +339,15 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     read where the files are out of step, naming the record counted from the start of the files and both names
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
-    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel and mappings_gapped as in
-    quantify_reads.
+    reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel, mappings_gapped and
+    mappings_tags as in quantify_reads.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     _check_mappings_sorted(mappings_sorted, mappings_format)
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
+    tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
@@ -326,14 +374,15 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                         raise ValueError(f"{reads1_path} and {reads2_path} are out of step at record {done + bad}: "
                                          f"{nm1.decode('utf-8', 'replace')!r} against {nm2.decode('utf-8', 'replace')!r}")
                 done += n
-                h, o = idx.map_reads(r1, r2, validate=validate)
+                h, o = idx.map_reads(r1, r2, validate=validate, tags=tstats is not None)
                 _add_verify_stats(vstats, idx)
                 _add_align_stats(astats, idx)
+                _add_tag_stats(tstats, idx)
                 if sam is not None:
                     q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals
                     sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
                               quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                              alignments=idx.last_alignments if astats is not None else None)
+                              alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
                 yield h, o
         finally:
             f1.close()
@@ -351,4 +400,5 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
         idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
     _report_align_stats(exp, astats, sopt)
+    _report_tag_stats(exp, tstats, sopt)
     return rc, exp

@@ -622,14 +622,28 @@ def _cigar_text(words):
     return b"".join(b"%d%c" % (int(w) >> 4, _OPS[int(w) & 15]) for w in words)
 
 
-def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False, alignments=None):
+def _tag_arrays(tags, n_records):
+    """(nm, md_off, md) as numpy arrays from what hits.md_tags / hits.md_tags_host return, device tensors or arrays, two slots per record"""
+    def host(a, dtype):
+        return (a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)).view(dtype).reshape(-1)
+    nm, md_off, md = host(tags[0], np.uint32), host(tags[1], np.uint64), host(tags[2], np.uint8)
+    if len(nm) != 2 * n_records or len(md_off) != 2 * n_records + 1:
+        raise ValueError(f"tags of {len(nm)} slots for {n_records} records (two slots a record)")
+    return nm, md_off, md.tobytes()
+
+
+def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False, alignments=None, tags=None):
     """the text write_sam writes.  quals: per read the quality bytes (single end) or a (mate 1, mate 2) pair, a mate's None for
     "not given" (QUAL '*'); they go with the mate's SEQ on every line.  oriented: a line with 0x10 carries SEQ reverse-complemented
     and QUAL reversed.  alignments: what hits.align_hits / align_hits_host returned for the same records -- a mapped line then takes
     POS and CIGAR from its slot (2 * record + line) and PNEXT from the other line's slot, and a slot without an operation is the
-    "no base on the transcript" error.  The rules are stated in csrc/samwfmt.h."""
+    "no base on the transcript" error.  tags: what hits.md_tags / md_tags_host returned for the same records and the same alignments --
+    a mapped line then ends NM:i:<nm>, MD:Z:<md>, NH:i:<the read's records>; they describe the read on the transcript's strand, so the
+    text must be oriented and the bases given.  The rules are stated in csrc/samwfmt.h."""
     if quals is not None and seqs is None:
         raise ValueError("qualities of reads whose bases are not given")
+    if tags is not None and (seqs is None or not oriented):
+        raise ValueError("tags describe the read on the transcript's strand: they need seqs= and oriented=True")
     hits = np.asarray(hits).view(HIT_DTYPE).reshape(-1)
     off = np.asarray(offsets).astype(np.int64)
     paired = bool((hits["mate_status"] != 0).any()) if len(hits) else bool(seqs and isinstance(seqs[0], tuple))
@@ -638,6 +652,14 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
     out += [b"@SQ\tSN:%s\tLN:%d\n" % (n, int(l)) for n, l in zip(nm, ref_len)]
     fmt = b"%s\t%d\t%s\t%d\t255\t%s\t%s\t%d\t%d\t%s\t%s\n"
     aln = _alignment_arrays(alignments, int(off[-1]) if len(off) else 0) if alignments is not None else None
+    tg = _tag_arrays(tags, int(off[-1]) if len(off) else 0) if tags is not None else None
+
+    def tagged(text, h, which, nh):
+        """a mapped line with its slot's tags"""
+        if tg is None:
+            return text
+        slot = 2 * h + which
+        return text[:-1] + b"\tNM:i:%d\tMD:Z:%s\tNH:i:%d\n" % (int(tg[0][slot]), tg[2][int(tg[1][slot]):int(tg[1][slot + 1])], nh)
 
     def placed(h, which, pos, length, what):
         """(POS, CIGAR) of line `which` of record h"""
@@ -682,6 +704,7 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
         for i, (tid, pos, mpos, frag, rlen, mlen, fwd, mfwd, status, _) in enumerate(recs):
             sec = 0x100 if i else 0
             what = f"read {r}, record {i}"
+            hi, nh = int(off[r]) + i, len(recs)
             p1, c1 = placed(int(off[r]) + i, 0, pos, rlen, what)
             if status == 3:
                 p2, c2 = placed(int(off[r]) + i, 1, mpos, mlen, what)
@@ -690,17 +713,17 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
                 check_quals(r, (s1, s2))
             if status == 3:
                 tlen = frag if pos <= mpos else -frag
-                out.append(line(q, 0x1 | 0x2 | 0x40 | sec | (0 if fwd else 0x10) | (0 if mfwd else 0x20), rname, p1, c1, b"=", p2, tlen, s1))
-                out.append(line(q, 0x1 | 0x2 | 0x80 | sec | (0 if mfwd else 0x10) | (0 if fwd else 0x20), rname, p2, c2, b"=", p1, -tlen, s2))
+                out.append(tagged(line(q, 0x1 | 0x2 | 0x40 | sec | (0 if fwd else 0x10) | (0 if mfwd else 0x20), rname, p1, c1, b"=", p2, tlen, s1), hi, 0, nh))
+                out.append(tagged(line(q, 0x1 | 0x2 | 0x80 | sec | (0 if mfwd else 0x10) | (0 if fwd else 0x20), rname, p2, c2, b"=", p1, -tlen, s2), hi, 1, nh))
             elif status:
-                out.append(line(q, 0x1 | 0x8 | (0x40 if status == 1 else 0x80) | sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0,
-                                s1 if status == 1 else s2))
+                out.append(tagged(line(q, 0x1 | 0x8 | (0x40 if status == 1 else 0x80) | sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0,
+                                       s1 if status == 1 else s2), hi, 0, nh))
             else:
-                out.append(line(q, sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0, s1))
+                out.append(tagged(line(q, sec | (0 if fwd else 0x10), rname, p1, c1, b"*", 0, 0, s1), hi, 0, nh))
     return b"".join(out)
 
 
-def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False, alignments=None):
+def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False, alignments=None, tags=None):
     """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
     line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
     a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
@@ -710,8 +733,10 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     (QUAL_WRITE_KINDS); a 1-base read whose quality is '*' reads as "no qualities", the format's ambiguity.  `read_names`: per read, default
     r<index>.  The library is taken as paired when any record is, or, without records, when seqs holds pairs.  bgzf=True writes
     blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan.  `alignments`: the gapped alignment
-    of the same records (hits.align_hits / align_hits_host): POS, CIGAR and PNEXT are then the alignment's."""
-    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments)
+    of the same records (hits.align_hits / align_hits_host): POS, CIGAR and PNEXT are then the alignment's.  `tags`: the NM / MD tags
+    of the same records and alignments (hits.md_tags / md_tags_host): a mapped line then ends NM:i:, MD:Z: and NH:i: (the read's record
+    count); they need `seqs` and `oriented`."""
+    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags)
     if bgzf:
         from . import gzfile
         gzfile.write_bgzf(path, data)
@@ -721,7 +746,7 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
 
 
 def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False, sort=None,
-              alignments=None):
+              alignments=None, tags=None):
     """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
     members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf).  sort="coordinate": the same records in
     coordinate order under an @HD SO:coordinate header (sort_bam_stream; csrc/baifmt.h), the header in members of its own, so that
@@ -729,7 +754,7 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     from . import gzfile
     if sort not in SORT_ORDERS:
         raise ValueError(f"sort must be one of {SORT_ORDERS}, not {sort!r}")
-    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments))
+    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags))
     if sort is None:
         gzfile.write_bgzf(path, data, member_bytes=member_bytes)
         return
@@ -1055,7 +1080,11 @@ class SamDeviceWriter:
     index when it is a file object; False: no index.  The state is NOT spilled to the host: it takes the records' bytes plus 20
     bytes per record of device memory until close(), which adds 28 bytes per record, two pieces and, for the index, 40 bytes per
     record and 28 per chunk; fewer than 2^32 records.  `stats` gains records, state_bytes (peak device bytes held), no_coor,
-    index_bytes, ms_sort, ms_gather and ms_index."""
+    index_bytes, ms_sort, ms_gather and ms_index.
+    write(tags=): the batch's NM / MD tags as hits.md_tags returns them (nm, md_off, md: device tensors, two slots per record, computed
+    over the same `alignments`); a mapped line then ends NM:i:<nm>, MD:Z:<md>, NH:i:<the read's record count> (a BAM record: NM and NH
+    in the smallest integer type that holds them, MD as a Z string), in every format, sorted or not.  The writer must be oriented and
+    the bases given, else ValueError.  Without `tags` the calls and the bytes are what they were."""
 
     def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False, sort=None, index=None):
         from . import _lib, quantfile
@@ -1178,7 +1207,29 @@ class SamDeviceWriter:
             aln, aln_t = (_lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops)), (a_pos, a_off, a_ops)
         return batch, extra, aln, (d_hits, d_off, self._d_names, q, s, ql, aln_t)
 
-    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None):
+    def _tag_args(self, tags, hits, seqs):
+        """write()'s tags as the _t entries take them: (the sfgpu_samw_tags struct, the tensors whose addresses it holds)"""
+        import torch
+
+        from . import _lib
+        if not self.oriented:
+            raise ValueError("tags describe the read on the transcript's strand: the writer must be oriented=True")
+        if seqs is None:
+            raise ValueError("tags of reads whose bases are not given")
+        dev = hits.device
+        t_nm, t_off, t_md = (tags[i].to(dev).contiguous() for i in (0, 1, 2))
+        if t_nm.element_size() != 4 or t_off.element_size() != 8 or t_md.element_size() != 1:
+            raise TypeError("tags: expected what hits.md_tags returns (32-bit nm, 64-bit offsets, MD bytes)")
+        n_rec = hits.numel() // 24
+        if t_nm.numel() != 2 * n_rec or t_off.numel() != 2 * n_rec + 1:
+            raise ValueError(f"tags of {t_nm.numel()} slots for {n_rec} records (two slots a record)")
+        if not t_md.numel():
+            t_md = torch.zeros(1, dtype=torch.uint8, device=dev)               # no MD byte at all: still "given"
+        if not t_nm.numel():
+            t_nm = torch.zeros(1, dtype=torch.int32, device=dev)
+        return _lib.SamwTags(_lib.ptr(t_nm), _lib.ptr(t_off), _lib.ptr(t_md)), (t_nm, t_off, t_md)
+
+    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None, tags=None):
         import torch
 
         from . import _lib
@@ -1187,6 +1238,11 @@ class SamDeviceWriter:
         dev = hits.device
         batch, extra, aln, keepalive = self._batch_args(hits, offsets, read_names, seqs, quals, alignments)
         n = batch[2]
+        text_entry, collect_entry, bgzf_entry, last = self._L.sfgpu_sam_write_text_a, self._L.sfgpu_bamsort_collect_a, self._L.sfgpu_sam_write_bgzf_a, ()
+        if tags is not None:                       # the _t entries; without tags the calls are the ones they were
+            t_struct, t_keep = self._tag_args(tags, hits, seqs)
+            keepalive = (keepalive, t_struct, t_keep)
+            text_entry, collect_entry, bgzf_entry, last = self._L.sfgpu_sam_write_text_t, self._L.sfgpu_bamsort_collect_t, self._L.sfgpu_sam_write_bgzf_t, (C.byref(t_struct),)
         raised = []
 
         def sink(addr, nb, _user):
@@ -1200,14 +1256,14 @@ class SamDeviceWriter:
         res = _lib.SamWriteResult()
         with torch.cuda.device(dev):
             if self._z is None:
-                rc = self._L.sfgpu_sam_write_text_a(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
+                rc = text_entry(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
             elif self._sort:
                 self._write_head(dev)
                 self._open_store()
-                rc = self._L.sfgpu_bamsort_collect_a(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
+                rc = collect_entry(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
             else:
                 self._write_head(dev)
-                rc = self._L.sfgpu_sam_write_bgzf_a(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra, *aln)
+                rc = bgzf_entry(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
         sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
         if sunk:
             raise sunk.pop(0)

@@ -37,8 +37,8 @@ enum {
     SFGPU_ERR_RANGE = 5,     /* a size exceeds what the device layout holds (see each call) */
     SFGPU_ERR_STATE = 6,     /* call order violated (e.g. export before finish, sfgpu_samc_emit before sfgpu_samc_finish) */
     SFGPU_ERR_UNSUPPORTED = 7, /* reserved: an option of the reference this build does not implement (none at present) */
-    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*, sfgpu_sam_parse_*, sfgpu_bam_parse_*, sfgpu_sam_collect_*, sfgpu_bam_collect_*) */
-    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_gz_*, sfgpu_bgzw_*) */
+    SFGPU_ERR_FORMAT = 8,    /* malformed input (sfgpu_eq_add_text_host, sfgpu_reads_parse_host / _device, sfgpu_bgzf_inflate_host, sfgpu_gzrd_*, sfgpu_sam_parse_*, sfgpu_bam_parse_*, sfgpu_sam_collect_*, sfgpu_bam_collect_*, sfgpu_reads_write_*) */
+    SFGPU_ERR_IO = 9,        /* the caller's sink refused the output (sfgpu_eqvec_write_text, sfgpu_quant_write_text, sfgpu_genes_write_text, sfgpu_sam_write_text, sfgpu_reads_write_text, sfgpu_gz_*, sfgpu_bgzw_*) */
     SFGPU_ERR_CAPACITY = 10  /* an output array of the caller is too small; the result says what is needed (sfgpu_sam_parse_*, sfgpu_bam_parse_*, sfgpu_samc_emit) */
 };
 
@@ -889,6 +889,48 @@ SFGPU_API int sfgpu_sam_write_bgzf_t(const struct sfgpu_hit* d_hits, const uint3
                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
                                      int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
                                      const sfgpu_samw_tags* tags);
+/* Reads as a FASTA / FASTQ text, formatted on the device from the batch where it lies: the mirror of sfgpu_reads_parse_*.  What a
+ * record says is csrc/readwfmt.h (the bytes of readfile.reads_text_host):
+ *   d_bases / d_off[n_reads + 1]   the bases back to back and their int64 offsets (never decreasing, none negative)
+ *   d_qual                         the qualities, sharing d_off: the text is then FASTQ, '@' name \n bases \n + \n qualities \n;
+ *                                  NULL: FASTA, '>' name \n bases \n, never wrapped
+ *   d_names / d_name_off[n_reads + 1]   the names back to back and their 64-bit offsets; both NULL: the name of record r is 'r' and
+ *                                  the decimal of read_index_base + r (the default QNAME of sfgpu_sam_write_text)
+ *   d_select                       one byte a record, nonzero = write it; NULL: every record.  The text is the selected records in
+ *                                  input order; unselected records are neither written nor checked
+ * All pointers are device pointers of any alignment; the inputs are not modified.  n_reads < 2^32 - 1 and records of less than
+ * 2^32 bytes (else SFGPU_ERR_RANGE); an offset array that decreases, offsets that name bytes of a NULL array and names without
+ * offsets are SFGPU_ERR_INVALID.  A selected record that cannot be written is SFGPU_ERR_FORMAT before any sink call, `out` naming
+ * the lowest (record << 8 | kind): error_kind SFGPU_READW_NAME_NEWLINE a name holds '\n', _SEQ_NEWLINE the bases do, _QUAL_NEWLINE
+ * the qualities do, _FASTA_SEQ_START the first base of a FASTA record is '>'.  A '\r' is written as given.
+ * The text goes to `sink` in chunks of at most chunk_bytes (0 = 32 MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID), greedy, each
+ * a whole number of records, through two pinned buffers owned by the call; a record longer than chunk_bytes is SFGPU_ERR_RANGE
+ * before the first sink call (`out` holds the sizes), a nonzero return of the sink SFGPU_ERR_IO.  sink == NULL sizes and checks
+ * only.  With nothing selected, or n_reads == 0, the call returns SFGPU_OK, reports 0 bytes and does not call the sink.
+ * Synchronous, ordered behind the work already on `stream`, no CPU path.
+ * sfgpu_reads_write_bgzf is the same call into a BGZF handle, as sfgpu_sam_write_bgzf: the chunks go to `z` on the device
+ * (sfgpu_bgzw_write_device), d2h_ms and sink_ms stay 0, and a batch that cannot be written fails before anything reaches `z`. */
+enum {
+    SFGPU_READW_OK = 0,
+    SFGPU_READW_NAME_NEWLINE = 1,
+    SFGPU_READW_SEQ_NEWLINE = 2,
+    SFGPU_READW_QUAL_NEWLINE = 3,
+    SFGPU_READW_FASTA_SEQ_START = 4
+};
+typedef struct {
+    uint64_t n_reads, n_selected, n_bytes, n_chunks, max_record_bytes;
+    uint64_t error_record;   /* the record of the lowest (record << 8 | kind), valid when error_kind != 0 */
+    int32_t  error_kind;     /* 0, or SFGPU_READW_NAME_NEWLINE 1, _SEQ_NEWLINE 2, _QUAL_NEWLINE 3, _FASTA_SEQ_START 4 */
+    double   format_ms, d2h_ms, sink_ms;   /* device events around the kernels and the staged copies, host clock inside the sink */
+} sfgpu_readwrite_result;
+SFGPU_API int sfgpu_reads_write_text(const uint8_t* d_bases, const int64_t* d_off, uint64_t n_reads, const uint8_t* d_qual,
+                                     const uint8_t* d_names, const uint64_t* d_name_off, uint64_t read_index_base,
+                                     const uint8_t* d_select, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                     sfgpu_readwrite_result* out, sfgpu_stream stream);
+SFGPU_API int sfgpu_reads_write_bgzf(const uint8_t* d_bases, const int64_t* d_off, uint64_t n_reads, const uint8_t* d_qual,
+                                     const uint8_t* d_names, const uint64_t* d_name_off, uint64_t read_index_base,
+                                     const uint8_t* d_select, uint64_t chunk_bytes, sfgpu_bgzw* z, sfgpu_readwrite_result* out,
+                                     sfgpu_stream stream);
 /* The compressed size of every member a BGZF handle writes, kept on the device: what virtual file offsets are made of.
  *   track_members  from this call on every write also keeps its members' sizes (4 bytes a member of device memory, in file order).
  *                  The bytes written, the results and the other calls do not change.

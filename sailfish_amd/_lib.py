@@ -150,6 +150,15 @@ class SamWriteResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
 
 
+class ReadWriteResult(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_selected", C.c_uint64), ("n_bytes", C.c_uint64), ("n_chunks", C.c_uint64),
+                ("max_record_bytes", C.c_uint64), ("error_record", C.c_uint64), ("error_kind", C.c_int32), ("pad_", C.c_int32),
+                ("format_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class GzResult(C.Structure):
     _fields_ = [("n_bytes_in", C.c_uint64), ("n_bytes_out", C.c_uint64), ("n_blocks", C.c_uint64), ("n_stored_blocks", C.c_uint64),
                 ("n_chunks", C.c_uint64), ("encode_ms", C.c_double), ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
@@ -365,6 +374,8 @@ _SIGS = {
     "sfgpu_sam_write_bgzf_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_sam_write_bgzf_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_sam_write_bgzf_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
+    "sfgpu_reads_write_text": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(ReadWriteResult), _P]),
+    "sfgpu_reads_write_bgzf": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(ReadWriteResult), _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
     "sfgpu_eq_finish": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "sfgpu_eq_export_device": (C.c_int, [_P, _P, _P, _P, _P]),

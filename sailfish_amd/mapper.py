@@ -5,6 +5,7 @@ RapMap is not part of the reference tree (fetched at build time); this is an exa
 (csrc/mapper.hip), not RapMap's suffix-array search, and parity with RapMap is unpinned.  Host side: sequence packing
 (bytes + offsets), batching, and the driver `quantify_reads` = index -> map -> quantify()."""
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -244,9 +245,69 @@ def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", 
                            sort="coordinate" if mappings_sorted else None)
 
 
+def _is_sink(x):
+    return isinstance(x, (str, bytes, os.PathLike)) or hasattr(x, "write")
+
+
+def _unmapped_targets(write_unmapped, unmapped_compress, paired):
+    """write_unmapped= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless it is one path or
+    binary file object for a single-end run and a pair of them for a paired one.  -> the targets as a tuple, or None"""
+    if write_unmapped is None:
+        if unmapped_compress:
+            raise ValueError("unmapped_compress=True needs write_unmapped")
+        return None
+    if not paired:
+        if not _is_sink(write_unmapped):
+            raise ValueError("write_unmapped: one path or binary file object for a single-end run")
+        return (write_unmapped,)
+    if not (isinstance(write_unmapped, (tuple, list)) and len(write_unmapped) == 2 and all(_is_sink(x) for x in write_unmapped)):
+        raise ValueError("write_unmapped: a pair of paths or binary file objects for a paired run, one for either mate file")
+    return tuple(write_unmapped)
+
+
+class _UnmappedWriters:
+    """The ReadDeviceWriters behind write_unmapped=, one per mate file.  write() takes a batch as it is handed to quant.quantify: a
+    read goes out iff the batch holds no record for it (offsets[r + 1] == offsets[r]); the selector is computed on the device, and
+    both mates go out with the same one, so the files stay in step."""
+
+    def __init__(self, targets, compress):
+        from .readfile import ReadDeviceWriter
+        self.writers = []
+        try:
+            for t in targets:
+                self.writers.append(ReadDeviceWriter(t, compress=compress))
+        except BaseException:
+            self.close()
+            raise
+        self.reads = self.unmapped = 0
+
+    def write(self, offsets, mates, quals, names):
+        """mates / quals / names: one entry per writer -- (bases, offsets), the qualities or None, the name pair or None"""
+        select = offsets[1:] == offsets[:-1]
+        for w, reads, q, nm in zip(self.writers, mates, quals, names):
+            written = w.write(reads, quals=q, names=nm, select=select)
+        self.reads += int(offsets.numel()) - 1
+        self.unmapped += written
+
+    def close(self):
+        for w in self.writers:
+            w.close()
+
+    def report(self, exp, sopt):
+        """on the experiment as `unmapped_stats`, and as one log line"""
+        st = dict(reads=self.reads, unmapped=self.unmapped, bytes=[w.stats["bytes"] for w in self.writers])
+        if exp is not None:
+            exp.unmapped_stats = st
+        log = getattr(sopt, "jointLog", None) if sopt is not None else None
+        if log is not None:
+            log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
+                st["unmapped"], st["reads"], " + ".join(str(b) for b in st["bytes"]), "FASTQ" if self.writers[0].format == 2 else "FASTA"))
+
+
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
+                   write_unmapped=None, unmapped_compress=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -274,22 +335,32 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     string) and NH:i: (the read's record count), computed on the device after validation and alignment for the surviving records
     (hits.md_tags), with every mappings_format, with mappings_sorted, and with and without mappings_gapped and validate_mappings.  The
     estimates never depend on it; the counters are left on the experiment as `tag_stats` and go to sopt.jointLog as one line.
+    write_unmapped: where the reads that did not map go, as a read file formatted on the device (readfile.ReadDeviceWriter): one path
+    or binary file object for a single-end run, a pair of them (mate 1, mate 2) for a paired one, anything else a ValueError before
+    anything is indexed.  A read is written iff the batch handed to quant.quantify holds no record for it -- after validation,
+    keep_best and the gapped pass; a pair with one orphan record is mapped; what the hit filter decides later does not enter --
+    which are the reads of the 4 / 77 / 141 lines of the mappings file.  Both mates go out with the same selector.  The records are
+    called r<index of the read>, FASTQ where quals1 (quals2) is given, else FASTA.  unmapped_compress=True (it needs write_unmapped)
+    writes BGZF files.  Neither the estimates nor the mappings file depend on it; the counts are left on the experiment as
+    `unmapped_stats` (reads, unmapped, bytes per file) and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     _check_mappings_sorted(mappings_sorted, mappings_format)
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
     tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
+    targets = _unmapped_targets(write_unmapped, unmapped_compress, reads2 is not None)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
     sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
+    unm = None if targets is None else _UnmappedWriters(targets, unmapped_compress)
 
     def batches():
         for a in range(0, n, batch_reads):
             b = min(n, a + batch_reads)
             r1, r2 = reads1[a:b], None if reads2 is None else reads2[a:b]
             q1 = q2 = None
-            if sam is not None:                              # the bases are wanted on the device beyond the mapper's call
+            if sam is not None or unm is not None:           # the bases are wanted on the device beyond the mapper's call
                 r1 = tuple(t.to(idx.device) for t in pack_sequences(r1))
                 r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
                 q1 = None if quals1 is None else pack_sequences(quals1[a:b])[0].to(idx.device)
@@ -301,6 +372,8 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
             if sam is not None:
                 sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
                           alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
+            if unm is not None:
+                unm.write(o, (r1,) if r2 is None else (r1, r2), (q1, q2), (None, None))
             yield h, o
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
@@ -311,10 +384,14 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     finally:
         if sam is not None:
             sam.close()
+        if unm is not None:
+            unm.close()
     idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
     _report_align_stats(exp, astats, sopt)
     _report_tag_stats(exp, tstats, sopt)
+    if unm is not None:
+        unm.report(exp, sopt)
     return rc, exp
 
 
@@ -329,7 +406,8 @@ def _dollar_separated(bases, off):
 
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
-                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False, **kw):
+                   validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
+                   write_unmapped=None, unmapped_compress=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -340,7 +418,10 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
     reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel, mappings_gapped and
-    mappings_tags as in quantify_reads.
+    mappings_tags as in quantify_reads.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
+    as they came in -- each mate file's own names up to the first space or tab (names="device" on both files), bases and quality lines
+    (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
+    FASTA unmapped file.  No name, base or offset visits the host.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
@@ -348,15 +429,19 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
     validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
     tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
+    targets = _unmapped_targets(write_unmapped, unmapped_compress, reads2_path is not None)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
-    keep = sam is not None and bool(mappings_oriented)
+    unm = None if targets is None else _UnmappedWriters(targets, unmapped_compress)
+    keep = sam is not None and bool(mappings_oriented)       # the mappings file carries QUAL
 
     def batches():
         check = bool(check_mate_names) and reads2_path is not None
-        f1 = ReadFile(reads1_path, device, names="device" if sam is not None or check else False, inflate=inflate, quals=keep)
-        f2 = None if reads2_path is None else ReadFile(reads2_path, device, names="device" if check else False, inflate=inflate, quals=keep)
+        f1 = ReadFile(reads1_path, device, names="device" if sam is not None or check or unm is not None else False, inflate=inflate,
+                      quals=keep or unm is not None)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device, names="device" if check or unm is not None else False, inflate=inflate,
+                                                       quals=keep or unm is not None)
         done = 0                                              # records of the batches before this one
         try:
             while True:
@@ -379,10 +464,13 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                 _add_align_stats(astats, idx)
                 _add_tag_stats(tstats, idx)
                 if sam is not None:
-                    q1, q2 = f1.last_quals, None if f2 is None else f2.last_quals
+                    q1, q2 = (f1.last_quals, None if f2 is None else f2.last_quals) if keep else (None, None)
                     sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
                               quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
                               alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
+                if unm is not None:
+                    unm.write(o, (r1,) if r2 is None else (r1, r2), (f1.last_quals, None if f2 is None else f2.last_quals),
+                              (f1.last_names, None if f2 is None else f2.last_names))
                 yield h, o
         finally:
             f1.close()
@@ -397,8 +485,12 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     finally:
         if sam is not None:
             sam.close()
+        if unm is not None:
+            unm.close()
         idx.close()
     _report_verify_stats(exp, vstats, validate, sopt)
     _report_align_stats(exp, astats, sopt)
     _report_tag_stats(exp, tstats, sopt)
+    if unm is not None:
+        unm.report(exp, sopt)
     return rc, exp

@@ -1,6 +1,9 @@
 """Transcript and read files in, packed sequences on the device out: the file side of sfgpu_reads_parse_host
 (csrc/readtext.hip; the record rules are csrc/readfmt.h).
 
+`ReadDeviceWriter` is the way back: batches of records that lie on the device become a FASTA / FASTQ file (plain or BGZF), formatted
+there (sfgpu_reads_write_text / _bgzf, csrc/readtext_write.hip; the rules are csrc/readwfmt.h, and `reads_text_host` states them).
+
 `ReadFile` reads a FASTA or FASTQ file in blocks, keeps the bytes the parser has not consumed, and hands out batches of records
 as the `(uint8 bases, int64 offsets)` pairs that `QuasiIndex` and `QuasiIndex.map_reads` take.  Nothing is parsed on the host:
 the host reads the file, the device finds the records.
@@ -14,6 +17,7 @@ chunk by chunk (sfgpu_gzrd_*, csrc/gz_read.hip: block starts are found speculati
 trailer's CRC-32 says whether the result is right) and parsed where it lands, like a BGZF file."""
 import ctypes as C
 import gzip
+import os
 
 import numpy as np
 import torch
@@ -29,6 +33,8 @@ KINDS = {1: "a record does not begin with '@' (or the file with neither '>' nor 
          2: "the third line of the record does not begin with '+'",
          3: "quality and sequence differ in length",
          4: "the last record has fewer than four lines"}
+WRITE_KINDS = {1: "the name holds a line end", 2: "the bases hold a line end", 3: "the qualities hold a line end",
+               4: "the first base of a FASTA record is '>'"}
 
 
 class Parsed:
@@ -525,3 +531,158 @@ def read_transcripts(path, device="cuda", block_bytes=32 << 20, inflate="auto"):
     if off.numel() <= 1:
         raise ValueError(f"{path}: no records")
     return names, (bases, off)
+
+
+# ---- the way back: records on the device -> a read file --------------------------------------------------------------------
+
+def reads_text_host(seqs, quals=None, names=None, select=None, index_base=0):
+    """The text sfgpu_reads_write_text writes, stated on the host over lists of bytes (csrc/readwfmt.h): the records r with
+    select[r] (all of them without `select`) in input order, FASTQ '@' name \\n bases \\n + \\n qualities \\n when `quals` is given,
+    else FASTA '>' name \\n bases \\n, never wrapped; without `names` record r is called r<index_base + r>.  A selected record that
+    cannot be written raises ValueError naming the lowest such record and the lowest WRITE_KINDS kind it breaks."""
+    out = []
+    for r, seq in enumerate(seqs):
+        if select is not None and not select[r]:
+            continue
+        seq = bytes(seq)
+        name = bytes(names[r]) if names is not None else b"r%d" % (index_base + r)
+        qual = None if quals is None else bytes(quals[r])
+        kind = (1 if b"\n" in name else 2 if b"\n" in seq else 3 if qual is not None and b"\n" in qual else
+                4 if qual is None and seq[:1] == b">" else 0)
+        if kind:
+            raise ValueError(f"record {r}: {WRITE_KINDS[kind]} (kind {kind})")
+        if qual is None:
+            out.append(b">" + name + b"\n" + seq + b"\n")
+        else:
+            if len(qual) != len(seq):
+                raise ValueError(f"record {r}: {len(qual)} quality bytes for {len(seq)} bases")
+            out.append(b"@" + name + b"\n" + seq + b"\n+\n" + qual + b"\n")
+    return b"".join(out)
+
+
+class ReadDeviceWriter:
+    """A FASTA / FASTQ file written from batches of records that lie on the device: the mirror of ReadFile.
+
+    `path_or_file`: a path, or a binary file object (left open by close()).  write((bases, offsets), quals=, names=, select=) takes
+    one batch as ReadFile.read returns it -- a uint8 device tensor of the bases and the int64 device tensor of their offsets --
+    with, optionally, the qualities (a uint8 device tensor that shares the offsets: ReadFile's last_quals), the names (the
+    (uint8, 64-bit offsets) pair of ReadFile(names="device").last_names) and a selector (one uint8 or bool a record: nonzero =
+    write it; default all), and appends the selected records in input order; -> the number of records written.  No name, base or
+    offset visits the host.  The first write fixes the format: FASTQ iff `quals` is given; a later batch of the other kind is a
+    ValueError.  Without `names` a record is called r<index>, the index counted over all records SEEN so far, written or not: the
+    name says where the read stood in the input.  A selected record that cannot be written (WRITE_KINDS) raises ValueError naming
+    the record, counted from the first batch, and the kind; nothing of that batch is written.
+    compress=True writes a BGZF file whose members are encoded on the device (gzfile.BgzfDeviceWriter): the formatted chunks go
+    from the formatter to the encoder on the device, only compressed bytes are copied, and close() writes the EOF member; the
+    format is never inferred from the path.  chunk_bytes: 0 (the library's 32 MiB) or 16 .. 2^30; no record may be longer.
+    `stats` sums batches, reads_in, reads_written, bytes (of text), bytes_out (of the file: known at close() when compressed),
+    chunks and the device / copy / sink / encode times."""
+
+    def __init__(self, path_or_file, *, compress=False, chunk_bytes=0):
+        self._L = _lib.lib()
+        self.compress, self.chunk_bytes = bool(compress), int(chunk_bytes)
+        self._own = isinstance(path_or_file, (str, bytes, os.PathLike))
+        self._f = open(path_or_file, "wb") if self._own else path_or_file
+        self.format = 0                                    # 1 FASTA, 2 FASTQ (SFGPU_READS_*), fixed by the first write
+        self.n_seen = 0                                    # the running record index
+        self.stats = dict(batches=0, reads_in=0, reads_written=0, bytes=0, bytes_out=0, chunks=0, ms_format=0.0, ms_copy=0.0, ms_sink=0.0,
+                          ms_encode=0.0)
+        self._z = None
+        if self.compress:
+            from . import gzfile
+            self._z = gzfile.BgzfDeviceWriter(self._f, chunk_bytes=self.chunk_bytes)
+
+    def write(self, reads, *, quals=None, names=None, select=None):
+        if self._f is None:
+            raise ValueError("the read writer is closed")
+        bases, off = reads
+        dev = off.device
+        if bases.dtype != torch.uint8 or off.dtype != torch.int64 or not off.is_cuda or bases.device != dev:
+            raise TypeError("expected (uint8 bases, int64 offsets) on one device")
+        n = int(off.numel()) - 1
+        if n < 0:
+            raise ValueError("the offsets of a batch have at least one entry")
+        fmt = 1 if quals is None else 2
+        if self.format and fmt != self.format:
+            raise ValueError("a {} batch for a {} file: the first write fixed the format".format(*(("FASTA", "FASTQ") if fmt == 1 else ("FASTQ", "FASTA"))))
+        one = lambda: torch.zeros(1, dtype=torch.uint8, device=dev)        # nothing at all: still "given"
+        bases, off = bases.contiguous(), off.contiguous()
+        if quals is not None:
+            if quals.dtype != torch.uint8 or quals.device != dev:
+                raise TypeError("quals: expected a uint8 tensor on the bases' device")
+            if quals.numel() != bases.numel():
+                raise ValueError(f"{quals.numel()} quality bytes for {bases.numel()} bases")
+            quals = quals.contiguous() if quals.numel() else one()
+        nb = no = None
+        if names is not None:
+            nb, no = names
+            if nb.element_size() != 1 or no.is_floating_point() or no.element_size() != 8 or nb.device != dev or no.device != dev:
+                raise TypeError("names: expected (bytes, 64-bit integer offsets) on the bases' device")
+            if no.numel() != n + 1:
+                raise ValueError(f"{no.numel() - 1} names for {n} reads")
+            nb, no = nb.contiguous() if nb.numel() else one(), no.contiguous()
+        if select is not None:
+            if select.element_size() != 1 or select.is_floating_point() or select.device != dev:
+                raise TypeError("select: expected one uint8 or bool a record on the bases' device")
+            if select.numel() != n:
+                raise ValueError(f"a selector of {select.numel()} entries for {n} reads")
+            select = select.contiguous().view(torch.uint8) if n else None
+        raised = []
+
+        def sink(addr, nbytes, _user):
+            try:                                   # nothing may unwind through the C frame
+                self._f.write(memoryview((C.c_char * nbytes).from_address(addr)))
+                return 0
+            except BaseException as e:             # noqa: BLE001  (re-raised below)
+                raised.append(e)
+                return 1
+
+        res = _lib.ReadWriteResult()
+        batch = (_lib.ptr(bases if bases.numel() else one()), _lib.ptr(off), n, _lib.ptr(quals), _lib.ptr(nb), _lib.ptr(no), self.n_seen,
+                 _lib.ptr(select), self.chunk_bytes)
+        with torch.cuda.device(dev):
+            if self._z is None:
+                rc = self._L.sfgpu_reads_write_text(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
+            else:
+                self._z._open(dev)
+                rc = self._L.sfgpu_reads_write_bgzf(*batch, self._z._h, C.byref(res), _lib.current_stream_ptr())
+        sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
+        if sunk:
+            raise sunk.pop(0)
+        if rc == _lib.ERR_FORMAT and res.error_kind:
+            raise ValueError(f"record {self.n_seen + int(res.error_record)}: {WRITE_KINDS.get(res.error_kind, 'cannot be written')} (kind {res.error_kind})")
+        _lib.check(rc)
+        self.format = fmt
+        self.n_seen += n
+        st = self.stats
+        for k, v in (("batches", 1), ("reads_in", n), ("reads_written", res.n_selected), ("bytes", res.n_bytes), ("chunks", res.n_chunks)):
+            st[k] += int(v)
+        if self._z is None:
+            st["bytes_out"] += int(res.n_bytes)
+        st["ms_format"] += res.format_ms; st["ms_copy"] += res.d2h_ms; st["ms_sink"] += res.sink_ms
+        return int(res.n_selected)
+
+    def close(self):
+        if self._f is None:
+            return
+        try:
+            if self._z is not None:
+                try:
+                    res = self._z.close()              # the EOF member
+                finally:
+                    self._z = None
+                st = self.stats
+                st["bytes_out"], st["ms_encode"] = res["n_bytes_out"], res["encode_ms"]
+                st["ms_copy"] += res["d2h_ms"]; st["ms_sink"] += res["sink_ms"]
+        finally:                                       # the file is released also when the encoder's close raises
+            f, self._f = self._f, None
+            if self._own:
+                f.close()
+            else:
+                f.flush()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

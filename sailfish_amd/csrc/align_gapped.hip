@@ -1,10 +1,10 @@
 // align_gapped.hip -- sfgpu_hits_align_gapped: the gapped alignment of the records that survive sfgpu_hits_verify_gapped, as a
 // position and BAM CIGAR words per job.  WHAT the alignment of a job is -- candidates, end cell, walk, trim -- is
 // csrc/aligngfmt.h, stated once and run here unchanged; this file is only the way the work is laid out, and what the hit passes
-// share of that -- the job decode, the group tools, the band -- is csrc/hitgroup.h.
+// share of that -- the batch, the job decode, the group tools, the band, the slot pass's host side (HitSlotPass) -- is csrc/hitgroup.h.
 //
 // Two slots per record (slot 2 h + j is job j of record h); count -> scan -> fill, twice:
-//   k_aligng_reads      a lane per read names the read of each of its records
+//   k_hits_rec_read     (hitgroup.h) a lane per read names the read of each of its records
 //   k_aligng_size<W>    a group of W lanes per slot (W = 16 for max_indel <= 7, 32 up to 15) counts the job's ungapped mismatches
 //                       (vf_job_lane + a group sum) and with them its kind -- no job, no bases, all bases match, traced -- and the
 //                       steps of scratch it needs (ceil(len / 16) for a traced job, else none); errors are found here
@@ -31,30 +31,18 @@ constexpr uint64_t kAgDefaultCap = 256ull << 20;
 enum { kAgJobs = kHitFirstCounter, kAgTraced, kAgUnalignable, kAgSumNm, kAgCounters };
 enum : uint8_t { kAgNoJob = 0, kAgNoBases, kAgAllMatch, kAgTracedJob };
 
-__global__ void __launch_bounds__(kAgBlock)
-k_aligng_reads(uint64_t n_reads, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t* __restrict__ rec_read) {
-    const uint64_t r = (uint64_t)blockIdx.x * kAgBlock + threadIdx.x;
-    if (r >= n_reads) return;
-    uint64_t b, e;
-    hit_range(hit_off, r, n_rec, &b, &e);
-    for (uint64_t i = b; i < e; ++i) rec_read[i] = (uint32_t)r;
-}
-
 template <int W> __global__ void __launch_bounds__(kAgBlock)
-k_aligng_size(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen, uint64_t M,
-              const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
-              const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ rec_read, uint64_t n_slots, uint32_t* __restrict__ steps /* [n_slots] */,
-              uint8_t* __restrict__ kind /* [n_slots] */, unsigned long long* ctr) {
+k_aligng_size(const HitBatchDev B, uint32_t* __restrict__ steps /* [n_slots] */, uint8_t* __restrict__ kind /* [n_slots] */, unsigned long long* ctr) {
     const uint64_t s = (uint64_t)blockIdx.x * (kAgBlock / W) + threadIdx.x / W;
     const uint32_t lane = threadIdx.x % W;
-    if (s >= n_slots) return;                                        // (a whole group)
-    const sfgpu_hit h = hits[s >> 1];
-    const uint32_t j = (uint32_t)(s & 1u), r = rec_read[s >> 1];
+    if (s >= B.n_slots) return;                                      // (a whole group)
+    const sfgpu_hit h = B.hits[s >> 1];
+    const uint32_t j = (uint32_t)(s & 1u), r = B.rec_read[s >> 1];
     uint32_t need = 0; uint8_t kd = kAgNoJob;
-    const int bad = hit_bad_record(h, M, seq2);
+    const int bad = hit_bad_record(h, B.M, B.seq2);
     if (bad >= 0) { if (lane == 0) atomicMin(&ctr[bad], (unsigned long long)(s >> 1)); }
     else if (j < vf_n_jobs(h) && r != ~0u) {
-        const HitJobDev jb = hit_job_dev(h, j, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+        const HitJobDev jb = hit_job_dev(B, h, j, r);
         const VfCount c = vf_job_lane(jb.m, jb.len, jb.fwd, jb.t, jb.tl, jb.pos, lane, W);
         const uint64_t ungapped = group_sum<W>(c.mism + c.over);
         kd = jb.len == 0 ? kAgNoBases : ungapped == 0 ? kAgAllMatch : kAgTracedJob;
@@ -84,17 +72,12 @@ template <int W> struct AgFetchDev {
 };
 
 template <int W, bool WRITE> __global__ void __launch_bounds__(kAgBlock)
-k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen,
-               const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
-               const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ rec_read, const uint8_t* __restrict__ kind, const uint64_t* __restrict__ prefix,
-               uint64_t n_slots, uint64_t a, uint64_t b, uint32_t k, int do_forward, uint64_t* cells /* the slice's */, uint8_t* lane_end /* [n_slots] */,
+k_aligng_trace(const HitBatchDev B, const uint8_t* __restrict__ kind, const uint64_t* __restrict__ prefix, uint64_t a, uint64_t b, uint32_t k, int do_forward,
+               uint64_t* cells /* the slice's */, uint8_t* lane_end /* [n_slots] */,
                uint32_t* __restrict__ n_ops /* [n_slots], !WRITE */, const uint64_t* __restrict__ woff /* [n_slots + 1], WRITE */, int32_t* __restrict__ pos_out,
                uint32_t* __restrict__ nm_out, uint64_t* __restrict__ op_off_out, uint32_t* __restrict__ ops_out, unsigned long long* ctr) {
     __shared__ unsigned long long s_ctr[kAgCounters];
-    if (WRITE) {
-        if (threadIdx.x < kAgCounters) s_ctr[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (WRITE) hit_ctr_zero(s_ctr);
     const uint64_t s = a + (uint64_t)blockIdx.x * (kAgBlock / W) + threadIdx.x / W;
     const uint32_t lane = threadIdx.x % W;
     if (s < b) {                                                     // (a whole group)
@@ -103,7 +86,7 @@ k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
         uint32_t* ops = (WRITE && lane == 0) ? ops_out : nullptr;
         AgTrace w{};
         if (kd >= kAgAllMatch) {
-            const HitJobDev jb = hit_job_dev(hits[s >> 1], (uint32_t)(s & 1u), rec_read[s >> 1], tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+            const HitJobDev jb = hit_job_dev(B, B.hits[s >> 1], (uint32_t)(s & 1u), B.rec_read[s >> 1]);
             if (kd == kAgAllMatch) w = ag_all_match(jb.len, jb.pos, ops, lo, hi);
             else {
                 uint64_t* mine = cells + (prefix[s] - prefix[a]) * W;
@@ -118,7 +101,7 @@ k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
             if (!WRITE) n_ops[s] = ag_n_ops(w);
             else {
                 pos_out[s] = (int32_t)w.x0; nm_out[s] = w.nm; op_off_out[s] = (uint64_t)lo;
-                if (s + 1 == n_slots) op_off_out[n_slots] = (uint64_t)hi;
+                if (s + 1 == B.n_slots) op_off_out[B.n_slots] = (uint64_t)hi;
                 if (kd != kAgNoJob) atomicAdd(&s_ctr[kAgJobs], 1ull);
                 if (kd == kAgTracedJob) atomicAdd(&s_ctr[kAgTraced], 1ull);
                 if (kd != kAgNoJob && !w.started) atomicAdd(&s_ctr[kAgUnalignable], 1ull);
@@ -126,10 +109,7 @@ k_aligng_trace(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
             }
         }
     }
-    if (WRITE) {
-        __syncthreads();
-        if (threadIdx.x >= kAgJobs && threadIdx.x < kAgCounters && s_ctr[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], s_ctr[threadIdx.x]);
-    }
+    if (WRITE) hit_ctr_flush(s_ctr, ctr);
 }
 
 }  // namespace sfgpu
@@ -144,41 +124,29 @@ extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1,
                                        sfgpu_align_gstats* stats, sfgpu_stream stream) {
     SF_REQUIRE(x && opts && n_ops && stats && d_op_off, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null pointer");
     SF_REQUIRE(opts->max_indel >= 1u && opts->max_indel <= kVgMaxIndel, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: max_indel is 1 .. 15");
-    SF_REQUIRE(n_reads == 0 || (d_seq1 && d_off1 && d_hit_offsets && (!d_seq2 || d_off2)), SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null reads");
-    SF_REQUIRE(cap_ops == 0 || d_ops, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null operations");
     hipStream_t st = as_stream(stream);
+    HitSlotPass sp("sfgpu_hits_align_gapped", x, d_seq1, d_off1, d_seq2, d_off2, n_reads, d_hits, d_hit_offsets, kAgCounters, st);
     int rc;
-    uint64_t n_rec = 0;
-    if ((rc = hit_n_rec(d_hit_offsets, n_reads, st, &n_rec))) return rc;
-    const uint64_t n_slots = 2 * n_rec;
-    if (n_rec == 0) {
-        SF_HIP(hipMemsetAsync(d_op_off, 0, 8, st)); SF_HIP(hipStreamSynchronize(st));
+    if ((rc = sp.null_reads())) return rc;
+    SF_REQUIRE(cap_ops == 0 || d_ops, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null operations");
+    if ((rc = sp.count_records())) return rc;
+    if (sp.n_rec == 0) {
         *n_ops = 0; *stats = sfgpu_align_gstats{};
-        return SFGPU_OK;
+        return sp.empty(d_op_off);
     }
     SF_REQUIRE(d_hits && d_pos && d_nm, SFGPU_ERR_INVALID, "sfgpu_hits_align_gapped: null records");
+    const uint64_t n_slots = 2 * sp.n_rec;
     const uint32_t k = opts->max_indel, W = vg_width(k), per_block = kAgBlock / W;
     // (steps and cnt: n_slots + 1 entries, exclusive_scan_u32 reads one past the last)
-    DevBuf<uint32_t> rec_read, steps, cnt; DevBuf<uint8_t> kind, lane_end; DevBuf<uint64_t> prefix, woff, cells, cut; DevBuf<unsigned long long> ctr;
+    DevBuf<uint32_t> steps, cnt; DevBuf<uint8_t> kind, lane_end; DevBuf<uint64_t> prefix, woff, cells, cut;
     StreamSyncOnExit sync_first{st};          // (declared after the buffers: an early return waits for the kernels before scratch goes back)
-    if ((rc = rec_read.reserve(n_rec, st, false)) || (rc = steps.reserve(n_slots + 1, st, false)) || (rc = cnt.reserve(n_slots + 1, st, false)) ||
-        (rc = kind.reserve(n_slots, st, false)) || (rc = lane_end.reserve(n_slots, st, false)) || (rc = prefix.reserve(n_slots + 1, st, false)) ||
-        (rc = woff.reserve(n_slots + 1, st, false)) || (rc = cut.reserve(2, st, false)) || (rc = ctr.reserve(kAgCounters, st, false))) return rc;
-    unsigned long long h_ctr[kAgCounters] = {~0ull, ~0ull, 0, 0, 0, 0};
-    SF_HIP(hipMemcpyAsync(ctr.p, h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, st));
-    SF_HIP(hipMemsetAsync(rec_read.p, 0xFF, n_rec * 4, st));
-    hipLaunchKernelGGL(k_aligng_reads, dim3((unsigned)(((uint64_t)n_reads + kAgBlock - 1) / kAgBlock)), dim3(kAgBlock), 0, st, (uint64_t)n_reads, d_hit_offsets, n_rec, rec_read.p);
+    if ((rc = steps.reserve(n_slots + 1, st, false)) || (rc = cnt.reserve(n_slots + 1, st, false)) || (rc = kind.reserve(n_slots, st, false)) ||
+        (rc = lane_end.reserve(n_slots, st, false)) || (rc = prefix.reserve(n_slots + 1, st, false)) || (rc = woff.reserve(n_slots + 1, st, false)) ||
+        (rc = cut.reserve(2, st, false)) || (rc = sp.start())) return rc;
+    hipLaunchKernelGGL(W == 16u ? k_aligng_size<16> : k_aligng_size<32>, sp.grid(n_slots, per_block), dim3(kAgBlock), 0, st, sp.B, steps.p, kind.p, sp.ctr.p);
     SF_CHECK_LAUNCH();
-    auto size_kernel = W == 16u ? k_aligng_size<16> : k_aligng_size<32>;
-    hipLaunchKernelGGL(size_kernel, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, x->M, d_seq1, d_off1,
-                       d_seq2, d_off2, d_hits, rec_read.p, n_slots, steps.p, kind.p, ctr.p);
-    SF_CHECK_LAUNCH();
-    if ((rc = exclusive_scan_u32(steps.p, prefix.p, n_slots, st, false))) return rc;
     uint64_t total_steps = 0;
-    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipMemcpyAsync(&total_steps, prefix.p + n_slots, 8, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    if ((rc = hit_report_bad("sfgpu_hits_align_gapped", h_ctr, x->M))) return rc;
+    if ((rc = sp.scan(steps.p, prefix.p, &total_steps, true))) return rc;
     // the slices
     const uint64_t cap_bytes = opts->scratch_cap_bytes ? opts->scratch_cap_bytes : kAgDefaultCap;
     const uint64_t cap_steps = cap_bytes / (8ull * W) ? cap_bytes / (8ull * W) : 1ull;
@@ -202,29 +170,21 @@ extern "C" int sfgpu_hits_align_gapped(const sfgpu_index* x, const char* d_seq1,
     auto count_kernel = W == 16u ? k_aligng_trace<16, false> : k_aligng_trace<32, false>;
     auto write_kernel = W == 16u ? k_aligng_trace<16, true> : k_aligng_trace<32, true>;
     for (const AgSlice& sl : slices) {
-        hipLaunchKernelGGL(count_kernel, dim3((unsigned)((sl.b - sl.a + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, d_seq1, d_off1,
-                           d_seq2, d_off2, d_hits, rec_read.p, kind.p, prefix.p, n_slots, sl.a, sl.b, k, 1, cells.p, lane_end.p, cnt.p, (const uint64_t*)nullptr,
-                           (int32_t*)nullptr, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, ctr.p);
+        hipLaunchKernelGGL(count_kernel, sp.grid(sl.b - sl.a, per_block), dim3(kAgBlock), 0, st, sp.B, kind.p, prefix.p, sl.a, sl.b, k, 1, cells.p, lane_end.p, cnt.p,
+                           (const uint64_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr, sp.ctr.p);
         SF_CHECK_LAUNCH();
     }
-    if ((rc = exclusive_scan_u32(cnt.p, woff.p, n_slots, st, false))) return rc;
     uint64_t total = 0;
-    SF_HIP(hipMemcpyAsync(&total, woff.p + n_slots, 8, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
+    if ((rc = sp.scan(cnt.p, woff.p, &total, false))) return rc;
     *n_ops = total;
-    if (total > cap_ops) {
-        set_error("sfgpu_hits_align_gapped: %llu operations, room for %llu", (unsigned long long)total, (unsigned long long)cap_ops);
-        return SFGPU_ERR_RANGE;
-    }
+    if ((rc = sp.room(total, cap_ops, "operations"))) return rc;
     for (const AgSlice& sl : slices) {
-        hipLaunchKernelGGL(write_kernel, dim3((unsigned)((sl.b - sl.a + per_block - 1) / per_block)), dim3(kAgBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, d_seq1, d_off1,
-                           d_seq2, d_off2, d_hits, rec_read.p, kind.p, prefix.p, n_slots, sl.a, sl.b, k, (int)(slices.size() > 1), cells.p, lane_end.p, (uint32_t*)nullptr,
-                           (const uint64_t*)woff.p, d_pos, d_nm, d_op_off, d_ops, ctr.p);
+        hipLaunchKernelGGL(write_kernel, sp.grid(sl.b - sl.a, per_block), dim3(kAgBlock), 0, st, sp.B, kind.p, prefix.p, sl.a, sl.b, k, (int)(slices.size() > 1), cells.p,
+                           lane_end.p, (uint32_t*)nullptr, (const uint64_t*)woff.p, d_pos, d_nm, d_op_off, d_ops, sp.ctr.p);
         SF_CHECK_LAUNCH();
     }
-    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    stats->jobs = h_ctr[kAgJobs]; stats->jobs_traced = h_ctr[kAgTraced]; stats->unalignable = h_ctr[kAgUnalignable]; stats->sum_nm = h_ctr[kAgSumNm];
+    if ((rc = sp.finish())) return rc;
+    stats->jobs = sp.h_ctr[kAgJobs]; stats->jobs_traced = sp.h_ctr[kAgTraced]; stats->unalignable = sp.h_ctr[kAgUnalignable]; stats->sum_nm = sp.h_ctr[kAgSumNm];
     stats->words = total; stats->scratch_bytes = peak_steps * W * 8ull;
     return SFGPU_OK;
 }

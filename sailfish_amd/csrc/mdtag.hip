@@ -1,9 +1,10 @@
 // mdtag.hip -- sfgpu_hits_md_tags: the NM and MD tags of the lines a mappings file holds for a batch of hit records.  WHAT a
 // slot's tags are -- the CIGAR walked, what a mismatch is, the reference character -- is csrc/mdfmt.h, stated once and run here
-// unchanged; this file is only the way the work is laid out, and what the hit passes share of that is csrc/hitgroup.h.
+// unchanged; this file is only the way the work is laid out, and what the hit passes share of that -- the batch, the job decode,
+// the block's counters, the slot pass's host side (HitSlotPass) -- is csrc/hitgroup.h.
 //
 // Two slots per record (slot 2 h + which is line `which` of record h); count -> scan -> write:
-//   k_mdtag_reads       a lane per read names the read of each of its records
+//   k_hits_rec_read     (hitgroup.h) a lane per read names the read of each of its records
 //   k_mdtag_walk<false> a group of 16 lanes per slot walks the slot's CIGAR.  Along an M run a lane takes 16 columns per step
 //                       (vf_window's clipped 16-byte loads, md_mask16: a 16-bit mismatch mask in registers), so the group 256; the
 //                       matches behind a lane's last mismatch reach the next lane's first token through a segmented shuffle scan
@@ -26,15 +27,6 @@ namespace sfgpu {
 constexpr int kMdBlock = kHitBlock;
 constexpr int kMdW = 16;
 enum { kMdSlots = kHitFirstCounter, kMdSumNm, kMdMax, kMdPlain, kMdCounters };
-
-__global__ void __launch_bounds__(kMdBlock)
-k_mdtag_reads(uint64_t n_reads, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t* __restrict__ rec_read) {
-    const uint64_t r = (uint64_t)blockIdx.x * kMdBlock + threadIdx.x;
-    if (r >= n_reads) return;
-    uint64_t b, e;
-    hit_range(hit_off, r, n_rec, &b, &e);
-    for (uint64_t i = b; i < e; ++i) rec_read[i] = (uint32_t)r;
-}
 
 // the lane's bytes of a number at out[at ..]
 __device__ __forceinline__ uint32_t md_put_number_dev(uint8_t* out, uint64_t at, uint32_t v) {
@@ -113,29 +105,23 @@ __device__ __forceinline__ uint64_t md_slot_dev(const MdCigar& c, const HitJobDe
 }
 
 template <bool WRITE> __global__ void __launch_bounds__(kMdBlock)
-k_mdtag_walk(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen, uint64_t M,
-             const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
-             const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ rec_read, uint64_t n_slots, const int32_t* __restrict__ aln_pos,
-             const uint64_t* __restrict__ aln_op_off, const uint32_t* __restrict__ aln_ops, uint32_t* __restrict__ bytes /* [n_slots], !WRITE */,
+k_mdtag_walk(const HitBatchDev B, const int32_t* __restrict__ aln_pos, const uint64_t* __restrict__ aln_op_off, const uint32_t* __restrict__ aln_ops, uint32_t* __restrict__ bytes /* [n_slots], !WRITE */,
              const uint64_t* __restrict__ woff /* [n_slots + 1], WRITE */, uint32_t* __restrict__ nm_out, uint64_t* __restrict__ md_off_out,
              uint8_t* __restrict__ md_out, unsigned long long* ctr) {
     __shared__ unsigned long long s_ctr[kMdCounters];
-    if (WRITE) {
-        if (threadIdx.x < kMdCounters) s_ctr[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (WRITE) hit_ctr_zero(s_ctr);
     const uint64_t s = (uint64_t)blockIdx.x * (kMdBlock / kMdW) + threadIdx.x / kMdW;
     const uint32_t lane = threadIdx.x % kMdW;
-    if (s < n_slots) {                                               // (a whole group)
-        const sfgpu_hit h = hits[s >> 1];
-        const uint32_t which = (uint32_t)(s & 1u), r = rec_read[s >> 1];
-        const int bad = WRITE ? -1 : hit_bad_record(h, M, seq2);     // (the write pass runs only after a count pass without errors)
+    if (s < B.n_slots) {                                             // (a whole group)
+        const sfgpu_hit h = B.hits[s >> 1];
+        const uint32_t which = (uint32_t)(s & 1u), r = B.rec_read[s >> 1];
+        const int bad = WRITE ? -1 : hit_bad_record(h, B.M, B.seq2);    // (the write pass runs only after a count pass without errors)
         bool is_line = false, plain = false;
         uint64_t n = 0;
         uint32_t nm = 0;
         if (bad >= 0) { if (lane == 0) atomicMin(&ctr[bad], (unsigned long long)(s >> 1)); }
         else if (which < vf_n_jobs(h) && r != ~0u) {
-            const HitJobDev jb = hit_job_dev(h, which, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+            const HitJobDev jb = hit_job_dev(B, h, which, r);
             const MdCigar c = md_slot_cigar(h, which, s, aln_pos, aln_op_off, aln_ops);
             n = md_slot_dev<WRITE>(c, jb, lane, WRITE ? md_out + woff[s] : nullptr, &nm);
             is_line = true; plain = md_plain(c, nm);
@@ -144,7 +130,7 @@ k_mdtag_walk(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_of
             if (!WRITE) bytes[s] = (uint32_t)n;
             else {
                 nm_out[s] = nm; md_off_out[s] = woff[s];
-                if (s + 1 == n_slots) md_off_out[n_slots] = woff[n_slots];
+                if (s + 1 == B.n_slots) md_off_out[B.n_slots] = woff[B.n_slots];
                 if (is_line) atomicAdd(&s_ctr[kMdSlots], 1ull);
                 if (nm) atomicAdd(&s_ctr[kMdSumNm], (unsigned long long)nm);
                 if (is_line) atomicMax(&s_ctr[kMdMax], (unsigned long long)n);
@@ -152,13 +138,7 @@ k_mdtag_walk(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_of
             }
         }
     }
-    if (WRITE) {
-        __syncthreads();
-        if (threadIdx.x >= kMdSlots && threadIdx.x < kMdCounters && s_ctr[threadIdx.x]) {
-            if (threadIdx.x == kMdMax) atomicMax(&ctr[kMdMax], s_ctr[kMdMax]);
-            else atomicAdd(&ctr[threadIdx.x], s_ctr[threadIdx.x]);
-        }
-    }
+    if (WRITE) hit_ctr_flush<kMdCounters, kMdMax>(s_ctr, ctr);
 }
 
 }  // namespace sfgpu
@@ -170,53 +150,36 @@ extern "C" int sfgpu_hits_md_tags(const sfgpu_index* x, const char* d_seq1, cons
                                   const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, uint32_t* d_nm, uint64_t* d_md_off, uint8_t* d_md,
                                   uint64_t cap_md, uint64_t* n_md, sfgpu_mdtag_stats* stats, sfgpu_stream stream) {
     SF_REQUIRE(x && n_md && stats && d_md_off, SFGPU_ERR_INVALID, "sfgpu_hits_md_tags: null pointer");
-    SF_REQUIRE(n_reads == 0 || (d_seq1 && d_off1 && d_hit_offsets && (!d_seq2 || d_off2)), SFGPU_ERR_INVALID, "sfgpu_hits_md_tags: null reads");
+    hipStream_t st = as_stream(stream);
+    HitSlotPass sp("sfgpu_hits_md_tags", x, d_seq1, d_off1, d_seq2, d_off2, n_reads, d_hits, d_hit_offsets, kMdCounters, st);
+    int rc;
+    if ((rc = sp.null_reads())) return rc;
     SF_REQUIRE((d_aln_pos && d_aln_op_off && d_aln_ops) || (!d_aln_pos && !d_aln_op_off && !d_aln_ops), SFGPU_ERR_INVALID,
                "sfgpu_hits_md_tags: an alignment is d_aln_pos, d_aln_op_off and d_aln_ops, or none of them");
     SF_REQUIRE(cap_md == 0 || d_md, SFGPU_ERR_INVALID, "sfgpu_hits_md_tags: null MD bytes");
-    hipStream_t st = as_stream(stream);
-    int rc;
-    uint64_t n_rec = 0;
-    if ((rc = hit_n_rec(d_hit_offsets, n_reads, st, &n_rec))) return rc;
-    const uint64_t n_slots = 2 * n_rec;
-    if (n_rec == 0) {
-        SF_HIP(hipMemsetAsync(d_md_off, 0, 8, st)); SF_HIP(hipStreamSynchronize(st));
+    if ((rc = sp.count_records())) return rc;
+    if (sp.n_rec == 0) {
         *n_md = 0; *stats = sfgpu_mdtag_stats{};
-        return SFGPU_OK;
+        return sp.empty(d_md_off);
     }
     SF_REQUIRE(d_hits && d_nm, SFGPU_ERR_INVALID, "sfgpu_hits_md_tags: null records");
-    constexpr uint32_t per_block = kMdBlock / kMdW;
+    const uint64_t n_slots = 2 * sp.n_rec;
     // (cnt: n_slots + 1 entries, exclusive_scan_u32 reads one past the last)
-    DevBuf<uint32_t> rec_read, cnt; DevBuf<uint64_t> woff; DevBuf<unsigned long long> ctr;
+    DevBuf<uint32_t> cnt; DevBuf<uint64_t> woff;
     StreamSyncOnExit sync_first{st};          // (declared after the buffers: an early return waits for the kernels before scratch goes back)
-    if ((rc = rec_read.reserve(n_rec, st, false)) || (rc = cnt.reserve(n_slots + 1, st, false)) || (rc = woff.reserve(n_slots + 1, st, false)) ||
-        (rc = ctr.reserve(kMdCounters, st, false))) return rc;
-    unsigned long long h_ctr[kMdCounters] = {~0ull, ~0ull, 0, 0, 0, 0};
-    SF_HIP(hipMemcpyAsync(ctr.p, h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, st));
-    SF_HIP(hipMemsetAsync(rec_read.p, 0xFF, n_rec * 4, st));
-    hipLaunchKernelGGL(k_mdtag_reads, dim3((unsigned)(((uint64_t)n_reads + kMdBlock - 1) / kMdBlock)), dim3(kMdBlock), 0, st, (uint64_t)n_reads, d_hit_offsets, n_rec, rec_read.p);
+    if ((rc = cnt.reserve(n_slots + 1, st, false)) || (rc = woff.reserve(n_slots + 1, st, false)) || (rc = sp.start())) return rc;
+    const dim3 grid = sp.grid(n_slots, kMdBlock / kMdW);
+    hipLaunchKernelGGL(k_mdtag_walk<false>, grid, dim3(kMdBlock), 0, st, sp.B, d_aln_pos, d_aln_op_off, d_aln_ops, cnt.p, (const uint64_t*)nullptr, (uint32_t*)nullptr,
+                       (uint64_t*)nullptr, (uint8_t*)nullptr, sp.ctr.p);
     SF_CHECK_LAUNCH();
-    const dim3 grid((unsigned)((n_slots + per_block - 1) / per_block));
-    hipLaunchKernelGGL(k_mdtag_walk<false>, grid, dim3(kMdBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, x->M, d_seq1, d_off1, d_seq2, d_off2, d_hits,
-                       rec_read.p, n_slots, d_aln_pos, d_aln_op_off, d_aln_ops, cnt.p, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint64_t*)nullptr,
-                       (uint8_t*)nullptr, ctr.p);
-    SF_CHECK_LAUNCH();
-    if ((rc = exclusive_scan_u32(cnt.p, woff.p, n_slots, st, false))) return rc;
     uint64_t total = 0;
-    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipMemcpyAsync(&total, woff.p + n_slots, 8, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    if ((rc = hit_report_bad("sfgpu_hits_md_tags", h_ctr, x->M))) return rc;
+    if ((rc = sp.scan(cnt.p, woff.p, &total, true))) return rc;
     *n_md = total;
-    if (total > cap_md) {
-        set_error("sfgpu_hits_md_tags: %llu MD bytes, room for %llu", (unsigned long long)total, (unsigned long long)cap_md);
-        return SFGPU_ERR_RANGE;
-    }
-    hipLaunchKernelGGL(k_mdtag_walk<true>, grid, dim3(kMdBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, x->M, d_seq1, d_off1, d_seq2, d_off2, d_hits,
-                       rec_read.p, n_slots, d_aln_pos, d_aln_op_off, d_aln_ops, (uint32_t*)nullptr, (const uint64_t*)woff.p, d_nm, d_md_off, d_md, ctr.p);
+    if ((rc = sp.room(total, cap_md, "MD bytes"))) return rc;
+    hipLaunchKernelGGL(k_mdtag_walk<true>, grid, dim3(kMdBlock), 0, st, sp.B, d_aln_pos, d_aln_op_off, d_aln_ops, (uint32_t*)nullptr, (const uint64_t*)woff.p, d_nm, d_md_off,
+                       d_md, sp.ctr.p);
     SF_CHECK_LAUNCH();
-    SF_HIP(hipMemcpyAsync(h_ctr, ctr.p, sizeof h_ctr, hipMemcpyDeviceToHost, st));
-    SF_HIP(hipStreamSynchronize(st));
-    stats->slots = h_ctr[kMdSlots]; stats->sum_nm = h_ctr[kMdSumNm]; stats->md_bytes = total; stats->max_md_bytes = h_ctr[kMdMax]; stats->slots_plain = h_ctr[kMdPlain];
+    if ((rc = sp.finish())) return rc;
+    stats->slots = sp.h_ctr[kMdSlots]; stats->sum_nm = sp.h_ctr[kMdSumNm]; stats->md_bytes = total; stats->max_md_bytes = sp.h_ctr[kMdMax]; stats->slots_plain = sp.h_ctr[kMdPlain];
     return SFGPU_OK;
 }

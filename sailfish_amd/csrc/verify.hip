@@ -45,17 +45,14 @@ __device__ __forceinline__ VfRecord verify_record(const sfgpu_hit& h, const VfCo
 __device__ __forceinline__ VgRecord verify_record(const sfgpu_hit& h, const VgJob* job, const uint64_t* len, uint32_t permille) { return vg_record(h, job, len, permille); }
 
 template <bool GAPPED, int W> __global__ void __launch_bounds__(kHitBlock)
-k_verify_score(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_off, const uint32_t* __restrict__ tlen, uint64_t M,
-               const char* __restrict__ seq1, const uint64_t* __restrict__ off1, const char* __restrict__ seq2, const uint64_t* __restrict__ off2,
-               uint64_t n_reads, const sfgpu_hit* __restrict__ hits, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t permille, int keep_best,
+k_verify_score(const HitBatchDev B, uint64_t n_reads, const uint32_t* __restrict__ hit_off, uint64_t n_rec, uint32_t permille, int keep_best,
                [[maybe_unused]] uint32_t k /* GAPPED */, uint64_t* __restrict__ cost /* [n_rec]: cost | rescued << 62 | pass << 63 */,
                [[maybe_unused]] uint64_t* __restrict__ mism /* !GAPPED: unsaturated */, typename VerifyKind<GAPPED>::Score* __restrict__ score,
                uint8_t* __restrict__ keep, uint32_t* __restrict__ cnt /* [n_reads + 1] */, unsigned long long* ctr /* [kCounters] */) {
     using Kind = VerifyKind<GAPPED>;
     constexpr uint32_t kReadsPerBlock = kHitBlock / W;
     __shared__ unsigned long long s_ctr[Kind::kCounters];
-    if (threadIdx.x < Kind::kCounters) s_ctr[threadIdx.x] = 0ull;
-    __syncthreads();
+    hit_ctr_zero(s_ctr);
     const uint64_t r = (uint64_t)blockIdx.x * kReadsPerBlock + threadIdx.x / W;
     const uint32_t lane = threadIdx.x % W;
     if (r == n_reads && lane == 0) cnt[r] = 0;
@@ -66,8 +63,8 @@ k_verify_score(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
         [[maybe_unused]] uint64_t rescued = 0;
         uint32_t kept = 0;
         for (uint64_t i = b; i < e; ++i) {
-            const sfgpu_hit h = hits[i];
-            const int bad = hit_bad_record(h, M, seq2);
+            const sfgpu_hit h = B.hits[i];
+            const int bad = hit_bad_record(h, B.M, B.seq2);
             if (bad >= 0) { if (lane == 0) { atomicMin(&ctr[bad], (unsigned long long)i); cost[i] = 0; keep[i] = 0; } continue; }
             const uint32_t nj = vf_n_jobs(h);
             typename Kind::Job job[2] = {}; uint64_t len[2] = {0, 0};
@@ -76,7 +73,7 @@ k_verify_score(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
 #pragma unroll
             for (uint32_t j = 0; j < 2u; ++j) {                      // (unrolled: job[] and len[] stay in registers)
                 if (j >= nj || !alive) break;
-                const HitJobDev jb = hit_job_dev(h, j, r, tseq, tseq_off, tlen, seq1, off1, seq2, off2);
+                const HitJobDev jb = hit_job_dev(B, h, j, r);
                 len[j] = jb.len;
                 const VfCount c = vf_job_lane(jb.m, jb.len, jb.fwd, jb.t, jb.tl, jb.pos, lane, W);
                 const uint64_t mm = group_sum<W>(c.mism), over = group_sum<W>(c.over);
@@ -125,8 +122,7 @@ k_verify_score(const char* __restrict__ tseq, const uint64_t* __restrict__ tseq_
             if (kept) atomicAdd(&s_ctr[kVfReadsOut], 1ull);
         }
     }
-    __syncthreads();
-    if (threadIdx.x >= kVfFailed && threadIdx.x < Kind::kCounters && s_ctr[threadIdx.x]) atomicAdd(&ctr[threadIdx.x], s_ctr[threadIdx.x]);
+    hit_ctr_flush(s_ctr, ctr);
 }
 
 // both entries: `opts` is the entry's own struct, max_indel read from it where it has one
@@ -168,9 +164,8 @@ static int hits_verify(const sfgpu_index* x, const char* d_seq1, const uint64_t*
     const unsigned grid = (unsigned)(((uint64_t)n_reads + 1 + per_block - 1) / per_block);
     auto score_kernel = k_verify_score<GAPPED, 16>;
     if constexpr (GAPPED) if (W == 32u) score_kernel = k_verify_score<GAPPED, 32>;
-    hipLaunchKernelGGL(score_kernel, dim3(grid), dim3(kHitBlock), 0, st, x->tseq.p, x->tseq_off.p, x->tlen.p, x->M, d_seq1, d_off1, d_seq2, d_off2,
-                       (uint64_t)n_reads, d_hits, d_hit_offsets, n_rec, opts->min_identity_permille, (int)(opts->keep_best != 0), k, cost.p, mism.p, score.p, keep.p,
-                       cnt.p, ctr.p);
+    hipLaunchKernelGGL(score_kernel, dim3(grid), dim3(kHitBlock), 0, st, HitBatchDev(x, d_seq1, d_off1, d_seq2, d_off2, d_hits), (uint64_t)n_reads, d_hit_offsets, n_rec,
+                       opts->min_identity_permille, (int)(opts->keep_best != 0), k, cost.p, mism.p, score.p, keep.p, cnt.p, ctr.p);
     SF_CHECK_LAUNCH();
     if ((rc = exclusive_scan_u32(cnt.p, out_off.p, n_reads, st, false))) return rc;
     uint64_t total = 0;

@@ -337,6 +337,19 @@ def _device_batch(index, hits, offsets, reads1, reads2):
     return dev, d_hits, d_off, R, s1, o1, s2, o2, d_hits.numel() // 24
 
 
+def _call_with_room(cap, make, call):
+    """A library call whose output's size is known only afterwards.  make(cap) -> the tensor with room for cap; call(tensor, cap) ->
+    (rc, need).  SFGPU_ERR_RANGE with a need above cap: repeated once, with exactly that room; then _lib.check.  -> (tensor, need)"""
+    for attempt in range(2):
+        out = make(cap)
+        rc, need = call(out, cap)
+        if rc != _lib.ERR_RANGE or attempt or need <= cap:
+            break
+        cap = int(need)
+    _lib.check(rc)
+    return out, need
+
+
 def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, keep_best=False, max_indel=0):
     """Verify the mapper's hit records against the transcripts' bases on the device (sfgpu_hits_verify; the rules are
     verify_hits_host's).  index: the mapper.QuasiIndex the records come from; hits / offsets: device tensors as QuasiIndex.map_reads
@@ -498,20 +511,16 @@ def align_hits(index, hits, offsets, reads1, reads2=None, *, max_indel, scratch_
     o = _lib.AlignGOpts(k, 0, int(scratch_cap_bytes))
     st = _lib.AlignGStats()
     need = C.c_uint64(0)
-    cap = max(4 * n, 1)
+
+    def call(ops, cap):
+        rc = _lib.lib().sfgpu_hits_align_gapped(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                                C.byref(o), _lib.ptr(pos), _lib.ptr(nm), _lib.ptr(op_off), _lib.ptr(ops), cap, C.byref(need), C.byref(st),
+                                                _lib.current_stream_ptr())
+        return rc, need.value
     with torch.cuda.device(dev):
         torch.cuda.current_stream().synchronize()
-        for attempt in range(2):
-            ops = torch.empty(cap, dtype=torch.int32, device=dev)
-            rc = _lib.lib().sfgpu_hits_align_gapped(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
-                                                    C.byref(o), _lib.ptr(pos), _lib.ptr(nm), _lib.ptr(op_off), _lib.ptr(ops), cap, C.byref(need), C.byref(st),
-                                                    _lib.current_stream_ptr())
-            if rc == _lib.ERR_RANGE and attempt == 0 and need.value > cap:
-                cap = int(need.value)
-                continue
-            _lib.check(rc)
-            break
-    return pos, nm, op_off, ops[: need.value], st.as_dict()
+        ops, n_ops = _call_with_room(max(4 * n, 1), lambda cap: torch.empty(cap, dtype=torch.int32, device=dev), call)
+    return pos, nm, op_off, ops[:n_ops], st.as_dict()
 
 
 MDTAG_STATS = ("slots", "sum_nm", "md_bytes", "max_md_bytes", "slots_plain")
@@ -630,20 +639,16 @@ def md_tags(index, hits, offsets, reads1, reads2=None, alignments=None):
     md_off = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev)
     st = _lib.MdTagStats()
     need = C.c_uint64(0)
-    cap = max(8 * n, 1)
+
+    def call(md, cap):
+        rc = _lib.lib().sfgpu_hits_md_tags(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                           _lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops), _lib.ptr(nm), _lib.ptr(md_off), _lib.ptr(md), cap,
+                                           C.byref(need), C.byref(st), _lib.current_stream_ptr())
+        return rc, need.value
     with torch.cuda.device(dev):
         torch.cuda.current_stream().synchronize()
-        for attempt in range(2):
-            md = torch.empty(cap, dtype=torch.uint8, device=dev)
-            rc = _lib.lib().sfgpu_hits_md_tags(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
-                                               _lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops), _lib.ptr(nm), _lib.ptr(md_off), _lib.ptr(md), cap,
-                                               C.byref(need), C.byref(st), _lib.current_stream_ptr())
-            if rc == _lib.ERR_RANGE and attempt == 0 and need.value > cap:
-                cap = int(need.value)
-                continue
-            _lib.check(rc)
-            break
-    return nm, md_off, md[: need.value], st.as_dict()
+        md, n_md = _call_with_room(max(8 * n, 1), lambda cap: torch.empty(cap, dtype=torch.uint8, device=dev), call)
+    return nm, md_off, md[:n_md], st.as_dict()
 
 
 def gc_prefix(seq, seq_off, ref_len):

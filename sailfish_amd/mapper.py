@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .hits import HIT_DTYPE
+from .hits import HIT_DTYPE, _call_with_room
 
 
 def pack_sequences(seqs, device="cpu"):
@@ -98,18 +98,15 @@ class QuasiIndex:
             assert int(o2.numel()) - 1 == n, "both mate files hold the same number of reads"
         off = torch.empty(n + 1, dtype=torch.int32, device=dev)
         n_hits = C.c_uint64(0)
-        cap = max(4 * n, 1024)
+
+        def call(hits, cap):
+            rc = self._L.sfgpu_map_reads(self._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), n, _lib.ptr(hits), cap, _lib.ptr(off),
+                                         C.byref(n_hits), _lib.current_stream_ptr())
+            return rc, n_hits.value
         with torch.cuda.device(dev):
-            torch.cuda.current_stream().synchronize()
-            for _ in range(2):                               # second round only if the first capacity guess was too small
-                hits = torch.empty(cap * 24, dtype=torch.uint8, device=dev)
-                rc = self._L.sfgpu_map_reads(self._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), n, _lib.ptr(hits), cap, _lib.ptr(off),
-                                             C.byref(n_hits), _lib.current_stream_ptr())
-                if rc == _lib.OK or n_hits.value <= cap:
-                    break
-                cap = n_hits.value
-            _lib.check(rc)
-        hits = hits[: n_hits.value * 24]
+            torch.cuda.current_stream().synchronize()            # (a second call only if the first capacity guess was too small)
+            hits, n_rec = _call_with_room(max(4 * n, 1024), lambda cap: torch.empty(cap * 24, dtype=torch.uint8, device=dev), call)
+        hits = hits[: n_rec * 24]
         if validate is not None:
             from .hits import verify_hits
             hits, off, self.last_scores, self.last_verify_stats = verify_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), **validate)
@@ -141,11 +138,6 @@ def hits_to_numpy(hits, offsets):
     return hits.cpu().numpy().view(HIT_DTYPE), offsets.cpu().numpy().view(np.uint32)
 
 
-def _check_mappings_sorted(mappings_sorted, mappings_format):
-    if mappings_sorted and mappings_format != "bam":
-        raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
-
-
 def _validation(validate_mappings, min_identity, keep_best, max_indel=0):
     """-> (the `validate` dict for QuasiIndex.map_reads or None, the counters to accumulate over the batches); ValueError at once
     for a min_identity outside 0 .. 1 or a max_indel outside 0 .. 15, before anything is indexed"""
@@ -159,110 +151,12 @@ def _validation(validate_mappings, min_identity, keep_best, max_indel=0):
     return dict(min_identity=min_identity, keep_best=bool(keep_best), max_indel=k), dict.fromkeys(VERIFYG_STATS, 0)
 
 
-def _add_verify_stats(total, idx):
-    if total is not None:
-        for key, v in idx.last_verify_stats.items():
-            total[key] += v
-
-
-def _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate):
-    """mappings_gapped= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless there is a
-    mappings file, the validation pass and a band to align in.  -> (the `validate` dict with "align" set, the counters to accumulate)"""
-    if not mappings_gapped:
-        return validate, None
-    if write_mappings is None or not validate_mappings or not (validate or {}).get("max_indel"):
-        raise ValueError("mappings_gapped=True needs write_mappings, validate_mappings=True and a max_indel of 1 .. 15")
-    from .hits import ALIGNG_STATS
-    return dict(validate, align=True), dict.fromkeys(ALIGNG_STATS, 0)
-
-
-def _add_align_stats(total, idx):
-    if total is not None:
-        for key, v in idx.last_align_stats.items():
-            total[key] = max(total[key], v) if key == "scratch_bytes" else total[key] + v
-
-
-def _report_align_stats(exp, total, sopt):
-    """the alignment pass's counters: on the experiment as `align_stats` (None when it did not run) and as one log line"""
-    if exp is not None:
-        exp.align_stats = total
-    log = getattr(sopt, "jointLog", None) if sopt is not None else None
-    if total is not None and log is not None:
-        log(0, "gapped mappings: {} of {} mates traced through the band; {} mismatches, inserted and deleted bases in the written alignments; "
-               "{} mates unalignable".format(total["jobs_traced"], total["jobs"], total["sum_nm"], total["unalignable"]))
-
-
-def _tagged_mappings(mappings_tags, write_mappings, mappings_oriented):
-    """mappings_tags= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless there is a mappings
-    file and it is oriented (NM and MD describe the read on the transcript's strand).  -> the counters to accumulate, or None"""
-    if not mappings_tags:
-        return None
-    if write_mappings is None or not mappings_oriented:
-        raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
-    from .hits import MDTAG_STATS
-    return dict.fromkeys(MDTAG_STATS, 0)
-
-
-def _add_tag_stats(total, idx):
-    if total is not None:
-        for key, v in idx.last_tag_stats.items():
-            total[key] = max(total[key], v) if key == "max_md_bytes" else total[key] + v
-
-
-def _report_tag_stats(exp, total, sopt):
-    """the tag pass's counters: on the experiment as `tag_stats` (None when it did not run) and as one log line"""
-    if exp is not None:
-        exp.tag_stats = total
-    log = getattr(sopt, "jointLog", None) if sopt is not None else None
-    if total is not None and log is not None:
-        log(0, "tagged mappings: NM, MD and NH on {} lines, {} of them <len>M without a mismatch; NM sums to {}; {} MD bytes, the longest MD {}".format(
-            total["slots"], total["slots_plain"], total["sum_nm"], total["md_bytes"], total["max_md_bytes"]))
-
-
-def _report_verify_stats(exp, total, validate, sopt):
-    """the accumulated counters: on the experiment as `verify_stats` (None when the pass did not run) and as one log line"""
-    if exp is not None:
-        exp.verify_stats = total
-    log = getattr(sopt, "jointLog", None) if sopt is not None else None
-    if total is not None and log is not None and validate.get("max_indel"):
-        log(0, "validated mappings (min identity {:g}, max indel {}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
-               "{} of {} mapped reads keep a record; {} edits in the kept records; {} records kept only with gaps".format(
-                   validate["min_identity"], validate["max_indel"], ", best only" if validate["keep_best"] else "", total["records_out"], total["records_in"],
-                   total["failed_identity"], total["dropped_not_best"], total["reads_out"], total["reads_in"], total["sum_edits"], total["rescued"]))
-    elif total is not None and log is not None:
-        log(0, "validated mappings (min identity {:g}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
-               "{} of {} mapped reads keep a record; {} mismatches in the kept records".format(
-                   validate["min_identity"], ", best only" if validate["keep_best"] else "", total["records_out"], total["records_in"],
-                   total["failed_identity"], total["dropped_not_best"], total["reads_out"], total["reads_in"], total["sum_mism"]))
-
-
-def _mappings_writer(write_mappings, names, idx, paired, mappings_format="sam", oriented=False, mappings_sorted=False):
-    """the SamDeviceWriter behind write_mappings= (a path or a binary file object), or None"""
-    if write_mappings is None:
-        return None
-    from .samfile import SamDeviceWriter
-    return SamDeviceWriter(write_mappings, names, idx.ref_len.cpu().numpy().view(np.uint32), paired, format=mappings_format, oriented=oriented,
-                           sort="coordinate" if mappings_sorted else None)
+# the passes of a batch whose counters a run adds up: (name, QuasiIndex's attribute after map_reads, the keys that are maxima, not sums)
+_PASSES = (("verify", "last_verify_stats", ()), ("align", "last_align_stats", ("scratch_bytes",)), ("tag", "last_tag_stats", ("max_md_bytes",)))
 
 
 def _is_sink(x):
     return isinstance(x, (str, bytes, os.PathLike)) or hasattr(x, "write")
-
-
-def _unmapped_targets(write_unmapped, unmapped_compress, paired):
-    """write_unmapped= of quantify_reads / quantify_files: ValueError at once, before anything is indexed, unless it is one path or
-    binary file object for a single-end run and a pair of them for a paired one.  -> the targets as a tuple, or None"""
-    if write_unmapped is None:
-        if unmapped_compress:
-            raise ValueError("unmapped_compress=True needs write_unmapped")
-        return None
-    if not paired:
-        if not _is_sink(write_unmapped):
-            raise ValueError("write_unmapped: one path or binary file object for a single-end run")
-        return (write_unmapped,)
-    if not (isinstance(write_unmapped, (tuple, list)) and len(write_unmapped) == 2 and all(_is_sink(x) for x in write_unmapped)):
-        raise ValueError("write_unmapped: a pair of paths or binary file objects for a paired run, one for either mate file")
-    return tuple(write_unmapped)
 
 
 class _UnmappedWriters:
@@ -270,16 +164,32 @@ class _UnmappedWriters:
     read goes out iff the batch holds no record for it (offsets[r + 1] == offsets[r]); the selector is computed on the device, and
     both mates go out with the same one, so the files stay in step."""
 
+    @staticmethod
+    def targets(write_unmapped, unmapped_compress, paired):
+        """write_unmapped= of quantify_reads / quantify_files: ValueError unless it is one path or binary file object for a
+        single-end run and a pair of them for a paired one.  -> the targets as a tuple, or None"""
+        if write_unmapped is None:
+            if unmapped_compress:
+                raise ValueError("unmapped_compress=True needs write_unmapped")
+            return None
+        if not paired:
+            if not _is_sink(write_unmapped):
+                raise ValueError("write_unmapped: one path or binary file object for a single-end run")
+            return (write_unmapped,)
+        if not (isinstance(write_unmapped, (tuple, list)) and len(write_unmapped) == 2 and all(_is_sink(x) for x in write_unmapped)):
+            raise ValueError("write_unmapped: a pair of paths or binary file objects for a paired run, one for either mate file")
+        return tuple(write_unmapped)
+
     def __init__(self, targets, compress):
         from .readfile import ReadDeviceWriter
         self.writers = []
+        self.reads = self.unmapped = 0
         try:
             for t in targets:
                 self.writers.append(ReadDeviceWriter(t, compress=compress))
         except BaseException:
             self.close()
             raise
-        self.reads = self.unmapped = 0
 
     def write(self, offsets, mates, quals, names):
         """mates / quals / names: one entry per writer -- (bases, offsets), the qualities or None, the name pair or None"""
@@ -293,15 +203,100 @@ class _UnmappedWriters:
         for w in self.writers:
             w.close()
 
+    def stats(self):
+        return dict(reads=self.reads, unmapped=self.unmapped, bytes=[w.stats["bytes"] for w in self.writers])
+
+
+class _MappingsRun:
+    """What quantify_reads and quantify_files share from the mapper's call to the files beside the estimates: the
+    options' checks, the two kinds of writers, a batch's map -> validate -> align -> tag -> write, the counters added up over the
+    batches, and their report.  Constructed before anything is indexed: it raises the options' ValueErrors."""
+
+    def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
+                 mappings_gapped, mappings_tags, write_unmapped, unmapped_compress):
+        from .hits import ALIGNG_STATS, MDTAG_STATS
+        if mappings_sorted and mappings_format != "bam":
+            raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
+        self.validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
+        astats = tstats = None
+        if mappings_gapped:
+            if write_mappings is None or not validate_mappings or not (self.validate or {}).get("max_indel"):
+                raise ValueError("mappings_gapped=True needs write_mappings, validate_mappings=True and a max_indel of 1 .. 15")
+            self.validate, astats = dict(self.validate, align=True), dict.fromkeys(ALIGNG_STATS, 0)
+        if mappings_tags:
+            if write_mappings is None or not mappings_oriented:
+                raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
+            tstats = dict.fromkeys(MDTAG_STATS, 0)
+        self.stats = dict(verify=vstats, align=astats, tag=tstats)                 # None: the pass does not run
+        self.targets, self.compress = _UnmappedWriters.targets(write_unmapped, unmapped_compress, paired), unmapped_compress
+        self.paired, self.sink = paired, write_mappings
+        self.sam_kw = dict(format=mappings_format, oriented=mappings_oriented, sort="coordinate" if mappings_sorted else None)
+        self.mapped, self.unmapped = write_mappings is not None, self.targets is not None       # which files the run writes
+        self.sam = self.unm = None
+
+    def open(self, names, idx):
+        """the SamDeviceWriter behind write_mappings= and the ReadDeviceWriters behind write_unmapped="""
+        if self.mapped:
+            from .samfile import SamDeviceWriter
+            self.sam = SamDeviceWriter(self.sink, names, idx.ref_len.cpu().numpy().view(np.uint32), self.paired, **self.sam_kw)
+        if self.unmapped:
+            self.unm = _UnmappedWriters(self.targets, self.compress)
+
+    def batch(self, idx, r1, r2, *, quals=(None, None), sam_quals=True, read_names=None, mate_names=(None, None)):
+        """One batch: mapped (validated, aligned, tagged, as the options say), its counters added, and written to the run's files.
+        r1 / r2: what map_reads takes (packed pairs on the device where the run writes a file); quals / mate_names: one entry per mate
+        file; sam_quals: whether the mappings file takes the qualities too; read_names: its QNAMEs.  -> (hits, offsets)"""
+        h, o = idx.map_reads(r1, r2, validate=self.validate, tags=self.stats["tag"] is not None)
+        for name, attr, maxima in _PASSES:
+            total = self.stats[name]
+            if total is not None:
+                for key, v in getattr(idx, attr).items():
+                    total[key] = max(total[key], v) if key in maxima else total[key] + v
+        if self.sam is not None:
+            q1, q2 = quals if sam_quals else (None, None)
+            self.sam.write(h, o, read_names=read_names, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
+                           alignments=idx.last_alignments if self.stats["align"] is not None else None, tags=idx.last_tags if self.stats["tag"] is not None else None)
+        if self.unm is not None:
+            self.unm.write(o, (r1,) if r2 is None else (r1, r2), quals, mate_names)
+        return h, o
+
+    def close(self):
+        for w in (self.sam, self.unm):
+            if w is not None:
+                w.close()
+
     def report(self, exp, sopt):
-        """on the experiment as `unmapped_stats`, and as one log line"""
-        st = dict(reads=self.reads, unmapped=self.unmapped, bytes=[w.stats["bytes"] for w in self.writers])
+        """every pass's counters on the experiment (`verify_stats`, `align_stats`, `tag_stats`: None where the pass did not run;
+        `unmapped_stats` only with write_unmapped) and one line each to sopt.jointLog"""
+        v, a, t = (self.stats[name] for name, _, _ in _PASSES)
+        u = None if self.unm is None else self.unm.stats()
         if exp is not None:
-            exp.unmapped_stats = st
+            exp.verify_stats, exp.align_stats, exp.tag_stats = v, a, t
+            if u is not None:
+                exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
-        if log is not None:
+        if log is None:
+            return
+        val = self.validate
+        if v is not None and val.get("max_indel"):
+            log(0, "validated mappings (min identity {:g}, max indel {}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
+                   "{} of {} mapped reads keep a record; {} edits in the kept records; {} records kept only with gaps".format(
+                       val["min_identity"], val["max_indel"], ", best only" if val["keep_best"] else "", v["records_out"], v["records_in"],
+                       v["failed_identity"], v["dropped_not_best"], v["reads_out"], v["reads_in"], v["sum_edits"], v["rescued"]))
+        elif v is not None:
+            log(0, "validated mappings (min identity {:g}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
+                   "{} of {} mapped reads keep a record; {} mismatches in the kept records".format(
+                       val["min_identity"], ", best only" if val["keep_best"] else "", v["records_out"], v["records_in"],
+                       v["failed_identity"], v["dropped_not_best"], v["reads_out"], v["reads_in"], v["sum_mism"]))
+        if a is not None:
+            log(0, "gapped mappings: {} of {} mates traced through the band; {} mismatches, inserted and deleted bases in the written alignments; "
+                   "{} mates unalignable".format(a["jobs_traced"], a["jobs"], a["sum_nm"], a["unalignable"]))
+        if t is not None:
+            log(0, "tagged mappings: NM, MD and NH on {} lines, {} of them <len>M without a mismatch; NM sums to {}; {} MD bytes, the longest MD {}".format(
+                t["slots"], t["slots_plain"], t["sum_nm"], t["md_bytes"], t["max_md_bytes"]))
+        if u is not None:
             log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
-                st["unmapped"], st["reads"], " + ".join(str(b) for b in st["bytes"]), "FASTQ" if self.writers[0].format == 2 else "FASTA"))
+                u["unmapped"], u["reads"], " + ".join(str(b) for b in u["bytes"]), "FASTQ" if self.unm.writers[0].format == 2 else "FASTA"))
 
 
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
@@ -345,53 +340,33 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     `unmapped_stats` (reads, unmapped, bytes per file) and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
-    _check_mappings_sorted(mappings_sorted, mappings_format)
-    validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
-    validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
-    tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
-    targets = _unmapped_targets(write_unmapped, unmapped_compress, reads2 is not None)
+    run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
-    sam = _mappings_writer(write_mappings, names, idx, reads2 is not None, mappings_format, mappings_oriented, mappings_sorted)
-    unm = None if targets is None else _UnmappedWriters(targets, unmapped_compress)
 
     def batches():
         for a in range(0, n, batch_reads):
             b = min(n, a + batch_reads)
             r1, r2 = reads1[a:b], None if reads2 is None else reads2[a:b]
             q1 = q2 = None
-            if sam is not None or unm is not None:           # the bases are wanted on the device beyond the mapper's call
+            if run.mapped or run.unmapped:                   # the bases are wanted on the device beyond the mapper's call
                 r1 = tuple(t.to(idx.device) for t in pack_sequences(r1))
                 r2 = None if r2 is None else tuple(t.to(idx.device) for t in pack_sequences(r2))
                 q1 = None if quals1 is None else pack_sequences(quals1[a:b])[0].to(idx.device)
                 q2 = None if quals2 is None or r2 is None else pack_sequences(quals2[a:b])[0].to(idx.device)
-            h, o = idx.map_reads(r1, r2, validate=validate, tags=tstats is not None)
-            _add_verify_stats(vstats, idx)
-            _add_align_stats(astats, idx)
-            _add_tag_stats(tstats, idx)
-            if sam is not None:
-                sam.write(h, o, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                          alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
-            if unm is not None:
-                unm.write(o, (r1,) if r2 is None else (r1, r2), (q1, q2), (None, None))
-            yield h, o
+            yield run.batch(idx, r1, r2, quals=(q1, q2))
     seq_kw = {}
     if sopt is not None and (getattr(sopt, "biasCorrect", False) or getattr(sopt, "gcBiasCorrect", False)):
         s, o = pack_sequences([x + "$" if isinstance(x, str) else bytes(x) + b"$" for x in sequences])
         seq_kw = dict(seq=bytes(s.numpy().tobytes()), seq_off=o[:-1].numpy())
     try:
+        run.open(names, idx)
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     finally:
-        if sam is not None:
-            sam.close()
-        if unm is not None:
-            unm.close()
-    idx.close()
-    _report_verify_stats(exp, vstats, validate, sopt)
-    _report_align_stats(exp, astats, sopt)
-    _report_tag_stats(exp, tstats, sopt)
-    if unm is not None:
-        unm.report(exp, sopt)
+        run.close()
+        idx.close()
+    run.report(exp, sopt)
     return rc, exp
 
 
@@ -425,23 +400,17 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
-    _check_mappings_sorted(mappings_sorted, mappings_format)
-    validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
-    validate, astats = _gapped_mappings(mappings_gapped, write_mappings, validate_mappings, validate)
-    tstats = _tagged_mappings(mappings_tags, write_mappings, mappings_oriented)
-    targets = _unmapped_targets(write_unmapped, unmapped_compress, reads2_path is not None)
+    run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
-    sam = _mappings_writer(write_mappings, names, idx, reads2_path is not None, mappings_format, mappings_oriented, mappings_sorted)
-    unm = None if targets is None else _UnmappedWriters(targets, unmapped_compress)
-    keep = sam is not None and bool(mappings_oriented)       # the mappings file carries QUAL
+    keep = run.mapped and bool(mappings_oriented)            # the mappings file carries QUAL
 
     def batches():
         check = bool(check_mate_names) and reads2_path is not None
-        f1 = ReadFile(reads1_path, device, names="device" if sam is not None or check or unm is not None else False, inflate=inflate,
-                      quals=keep or unm is not None)
-        f2 = None if reads2_path is None else ReadFile(reads2_path, device, names="device" if check or unm is not None else False, inflate=inflate,
-                                                       quals=keep or unm is not None)
+        f1 = ReadFile(reads1_path, device, names="device" if run.mapped or check or run.unmapped else False, inflate=inflate, quals=keep or run.unmapped)
+        f2 = None if reads2_path is None else ReadFile(reads2_path, device, names="device" if check or run.unmapped else False, inflate=inflate,
+                                                       quals=keep or run.unmapped)
         done = 0                                              # records of the batches before this one
         try:
             while True:
@@ -459,19 +428,8 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                         raise ValueError(f"{reads1_path} and {reads2_path} are out of step at record {done + bad}: "
                                          f"{nm1.decode('utf-8', 'replace')!r} against {nm2.decode('utf-8', 'replace')!r}")
                 done += n
-                h, o = idx.map_reads(r1, r2, validate=validate, tags=tstats is not None)
-                _add_verify_stats(vstats, idx)
-                _add_align_stats(astats, idx)
-                _add_tag_stats(tstats, idx)
-                if sam is not None:
-                    q1, q2 = (f1.last_quals, None if f2 is None else f2.last_quals) if keep else (None, None)
-                    sam.write(h, o, read_names=f1.last_names, seqs=r1 if r2 is None else (r1, r2),
-                              quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                              alignments=idx.last_alignments if astats is not None else None, tags=idx.last_tags if tstats is not None else None)
-                if unm is not None:
-                    unm.write(o, (r1,) if r2 is None else (r1, r2), (f1.last_quals, None if f2 is None else f2.last_quals),
-                              (f1.last_names, None if f2 is None else f2.last_names))
-                yield h, o
+                yield run.batch(idx, r1, r2, quals=(f1.last_quals, None if f2 is None else f2.last_quals), sam_quals=keep, read_names=f1.last_names,
+                                mate_names=(f1.last_names, None if f2 is None else f2.last_names))
         finally:
             f1.close()
             if f2 is not None:
@@ -481,16 +439,10 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
         s, o = _dollar_separated(bases, off)
         seq_kw = dict(seq=s, seq_off=o)
     try:
+        run.open(names, idx)
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     finally:
-        if sam is not None:
-            sam.close()
-        if unm is not None:
-            unm.close()
+        run.close()
         idx.close()
-    _report_verify_stats(exp, vstats, validate, sopt)
-    _report_align_stats(exp, astats, sopt)
-    _report_tag_stats(exp, tstats, sopt)
-    if unm is not None:
-        unm.report(exp, sopt)
+    run.report(exp, sopt)
     return rc, exp

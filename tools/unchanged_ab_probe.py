@@ -5,7 +5,11 @@
    (io.BytesIO), after torch.cuda.synchronize(), and the formatter's device time from the writer's stats (`ms_format`);
  - sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (--pairs, default 2 M; 80 000 transcripts; 2 % substitutions, an
    indel of 1 - 3 bases in 5 % of the mates; max_indel 3, min identity 0.9): host wall time around the call, synchronised;
- - on that same batch, sfgpu_hits_verify (0.9), and sfgpu_hits_align_gapped (max_indel 3) on the gapped pass's survivors.
+ - on that same batch, sfgpu_hits_verify (0.9), sfgpu_hits_align_gapped (max_indel 3) on the gapped pass's survivors, and
+   sfgpu_hits_md_tags on those survivors with that alignment;
+ - mapper.quantify_reads end to end on the first 100 000 pairs of that batch, every mapping option on (sorted oriented BAM with the
+   gapped alignments and the tags, validation with max_indel 3, the unmapped reads), writing into a temporary directory: host wall
+   time of the whole call.
 
 Every figure is the median of --repeats (default 7) runs after one warm-up run; all runs are kept.  --root names the tree whose
 `sailfish_amd` is measured (built there beforehand; default: the tree this file is in), so that the same driver measures a checkout
@@ -23,13 +27,15 @@ import json
 import os
 import statistics
 import sys
+import tempfile
 import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 WHAT = ("parent / new / parent in fresh processes on one device, one call of tools/unchanged_ab_probe.py a leg: the device writers on the batch of "
         "tools/samwrite_probe.py (100 000 pairs; wall ms of SamDeviceWriter open + write + close into memory, and the formatter's device ms) and "
         "sfgpu_hits_verify_gapped on a batch of tools/verify_probe.py (2 % substitutions, an indel in 5 % of the mates, max_indel 3), with "
-        "sfgpu_hits_verify on that batch and sfgpu_hits_align_gapped on the gapped pass's survivors; medians of `repeats` runs after a warm-up")
+        "sfgpu_hits_verify on that batch, sfgpu_hits_align_gapped on the gapped pass's survivors and sfgpu_hits_md_tags on them with that alignment, "
+        "and mapper.quantify_reads on the first 100 000 pairs with every mapping option on; medians of `repeats` runs after a warm-up")
 
 
 def main():
@@ -134,7 +140,42 @@ def main():
         _lib.check(Lb.sfgpu_hits_align_gapped(*al, _lib.ptr(ops), ops.numel(), C.byref(need), C.byref(ast), None))
     a_ms, a_all = verify_probe.timed(align, a.repeats)
     leg["align_gapped"] = dict(ms=a_ms, ms_runs=a_all, records=n_s, stats=ast.as_dict())
+
+    # the tags of those survivors over that alignment, with exactly the room they need
+    md_off = torch.zeros(2 * n_s + 1, dtype=torch.int64, device=dev)
+    mst = _lib.MdTagStats()
+    ml = (index._h, _lib.ptr(r1), _lib.ptr(roff), _lib.ptr(r2), _lib.ptr(roff), R, _lib.ptr(s_hits), _lib.ptr(s_off), _lib.ptr(pos), _lib.ptr(op_off), _lib.ptr(ops),
+          _lib.ptr(nm), _lib.ptr(md_off))
+    rc = Lb.sfgpu_hits_md_tags(*ml, None, 0, C.byref(need), C.byref(mst), None)
+    assert rc in (_lib.OK, _lib.ERR_RANGE), rc
+    md = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+
+    def tag():
+        _lib.check(Lb.sfgpu_hits_md_tags(*ml, _lib.ptr(md), md.numel(), C.byref(need), C.byref(mst), None))
+    t_ms, t_all = verify_probe.timed(tag, a.repeats)
+    leg["md_tags"] = dict(ms=t_ms, ms_runs=t_all, records=n_s, stats=mst.as_dict())
     index.close()
+
+    # the driver, from the reads to the files
+    Q = min(R, 100_000)
+    l1, l2 = ([row.tobytes() for row in m[:Q].cpu().numpy()] for m in (m1, m2))
+    tnames = [f"t{i}" for i in range(M)]
+    q_all, q_stats = [], {}
+    for i in range(a.repeats + 1):
+        with tempfile.TemporaryDirectory() as tmp:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            qrc, exp = sf.mapper.quantify_reads(tnames, (seq, toff), l1, l2, "IU", os.path.join(tmp, "out"), device=dev, cmd_options={"libType": "IU"},
+                                                write_mappings=os.path.join(tmp, "m.bam"), mappings_format="bam", mappings_oriented=True, mappings_sorted=True,
+                                                validate_mappings=True, max_indel=K, mappings_gapped=True, mappings_tags=True,
+                                                write_unmapped=(os.path.join(tmp, "u1.fa"), os.path.join(tmp, "u2.fa")))
+            torch.cuda.synchronize()
+            dt = 1e3 * (time.perf_counter() - t0)
+            assert qrc == 0
+            q_stats = dict(verify=exp.verify_stats, align=exp.align_stats, tags=exp.tag_stats, unmapped=exp.unmapped_stats, bam_bytes=os.path.getsize(os.path.join(tmp, "m.bam")))
+        if i:
+            q_all.append(dt)
+    leg["quantify_reads"] = dict(ms=med(q_all), ms_runs=q_all, pairs=Q, stats=q_stats)
 
     print(json.dumps(leg), flush=True)
     doc = dict(what=WHAT, runs=[])

@@ -1245,10 +1245,39 @@ SFGPU_API int sfgpu_bootstrap_counts(sfgpu_em* em, uint64_t seed, uint64_t draw,
  *   d_out  : n_samples x M int32 on the device, or NULL
  *   cb     : writeSample (std::function<bool(const std::vector<int>&)>), host copy per sample; may be NULL
  * Device memory: 4 * nnz * n_chains + 4 * M * n_chains bytes of chain state.  Synchronous.
+ * Domain: every ratio of weights the sampler forms divides by a NORMAL, finite double whose reciprocal is normal too (2^-1022 <= b <=
+ * 2^1022; csrc/rng.h, ratio_of: reciprocal instruction plus two Newton steps, NaN outside).  Effective lengths are clamped at 1 and
+ * every weight carries the prior, so finite lengths and masses in [0, 1] stay ~300 binary orders inside it.
  * ------------------------------------------------------------------------------------------- */
 typedef int (*sfgpu_gibbs_cb)(const int32_t* h_counts, uint64_t M, void* user);
 SFGPU_API int sfgpu_gibbs_sample(const sfgpu_problem* prob, const double* d_mass, uint32_t n_samples, uint32_t n_chains,
                        uint64_t seed, int32_t* d_out, sfgpu_gibbs_cb cb, void* user, sfgpu_stream stream);
+/* Diagnostics, like sfgpu_vb_eval: the samplers' device arithmetic (csrc/rng.h, csrc/gibbsfmt.h, csrc/sampling.hip) on its own, for the
+ * tests that hold it to the host build of the same headers draw for draw (tests/test_gpu_rng.py).  Every draw is a function of (seed,
+ * stream, substream, arguments) alone.  All pointers are device memory, a count of 0 is fine, asynchronous on `stream`; an unknown form
+ * returns SFGPU_ERR_INVALID and writes nothing.
+ * sfgpu_rng_eval: one lane per element i, Philox(seed, d_stream ? d_stream[i] : i, d_substream ? d_substream[i] : 0) -- the lanes of a
+ * wavefront may hold different arguments.  A form reads only the arrays it names; the others may be NULL. */
+enum {
+    SFGPU_RNG_WORDS = 0,        /* d_out: uint32 [n][w], the first w words of next32() */
+    SFGPU_RNG_UNIFORM = 1,      /* d_out: double [n][w], the first w values of uniform() */
+    SFGPU_RNG_RATIO = 2,        /* d_out: double [n], ratio_of(d_a[i], d_b[i]) (no random numbers) */
+    SFGPU_RNG_BINOMIAL = 3,     /* d_out: uint32 [n], binomial(d_n[i], p = d_a[i]) */
+    SFGPU_RNG_BINOMIAL_INV = 4, /* d_out: uint32 [n], binomial_by_inversion(d_n[i], p = d_a[i]) */
+    SFGPU_RNG_BLOCK = 5         /* d_out: uint32 [n][4], one raw Philox4x32-10 block: key = seed's low and high word, counter words 0, 1 =
+                                 * d_stream[i]'s and 2, 3 = d_substream[i]'s (both required) -- the generator's published known answers */
+};
+SFGPU_API int sfgpu_rng_eval(int form, uint64_t seed, const uint64_t* d_stream, const uint64_t* d_substream, const uint32_t* d_n,
+                             const double* d_a, const double* d_b, uint32_t w, uint64_t n, void* d_out, sfgpu_stream stream);
+/* multinomial_chain over k weights d_w (their sum in member order is p_total): `count` draws of n reads with member `last` left out,
+ * draw d from Philox(seed, d, 0), one lane per draw; d_out: uint32 [count][k].  light = 1: binomial_by_inversion (the phase kernel's
+ * LIGHT form), 0: binomial; anything else is the unknown form. */
+SFGPU_API int sfgpu_chain_eval(int light, const double* d_w, uint32_t k, uint32_t n, uint32_t last, uint64_t seed, uint64_t count,
+                               uint32_t* d_out, sfgpu_stream stream);
+/* The bootstrap's multinomial tree over the caller's own prefix sums (d_prefix[0 .. C], exclusive, of the class counts in the caller's
+ * order -- sfgpu_bootstrap_counts works in the plan's): d_out[C] = draw `draw` of `seed` of n_total reads.  SFGPU_MN_TREE=levels as there. */
+SFGPU_API int sfgpu_mn_tree_eval(const uint64_t* d_prefix, uint64_t C, uint32_t n_total, uint64_t seed, uint64_t draw, uint32_t* d_out,
+                                 sfgpu_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (next) A quasi-mapping front end: reads in, sfgpu_hit records out -- what the reference gets from RapMap's

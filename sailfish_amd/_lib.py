@@ -442,6 +442,9 @@ _SIGS = {
     "sfgpu_bootstrap": (C.c_int, [_P, C.POINTER(EmOpts), C.c_uint32, C.c_uint64, _P, SAMPLE_CB, _P, _P]),
     "sfgpu_bootstrap_counts": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     "sfgpu_gibbs_sample": (C.c_int, [C.POINTER(Problem), _P, C.c_uint32, C.c_uint32, C.c_uint64, _P, GIBBS_CB, _P, _P]),
+    "sfgpu_rng_eval": (C.c_int, [C.c_int, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P]),
+    "sfgpu_chain_eval": (C.c_int, [C.c_int, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P]),
+    "sfgpu_mn_tree_eval": (C.c_int, [_P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, _P, _P]),
     "sfgpu_tpm": (C.c_int, [_P, _P, C.c_uint64, C.c_double, _P, _P]),
 }
 

@@ -35,7 +35,7 @@
 // :227-228), so parity is distributional.
 #include "colour.h"
 #include "common.h"
-#include "rng.h"
+#include "gibbsfmt.h"      // the chain, the two class visits, GibbsArgs and their constants: stated once for the kernels and the tests' harness
 
 #include <algorithm>
 #include <chrono>
@@ -45,107 +45,9 @@
 namespace sfgpu {
 
 constexpr int kGibbsBlock = 64;            // one wavefront of chains per block
-constexpr int kGibbsTile = 64;             // classes per tile
-constexpr uint32_t kWideSpan = 2048;       // classes spanning more transcripts than this are "wide"
 constexpr uint32_t kMaxPhases = 1024;      // more phases than this: fall back to one sequential scan
-constexpr uint32_t kWideSerial = 64;       // up to this many wide classes are visited one after another by one launch
 constexpr uint32_t kMaxColours = 1u << 16; // more colours than this: visit the wide classes one after another after all
 constexpr uint32_t kThinWidth = 12;        // a component of wide classes with fewer classes per colour than this is visited serially
-#if !defined(SFGPU_GIBBS_LIGHT_MAX)
-#define SFGPU_GIBBS_LIGHT_MAX 1500
-#endif
-constexpr uint64_t kGibbsLightMax = SFGPU_GIBBS_LIGHT_MAX;   // classes of more reads than this are HEAVY: visited by the phase kernel that carries BTPE (see k_gibbs_phase)
-constexpr double kGibbsPrior = 1e-8;       // priorAlpha (:215)
-constexpr double kGibbsTiny = 4.9406564584124654e-324;
-
-struct GibbsArgs {
-    uint32_t n_chains; uint64_t C;
-    const uint32_t* rowptr; const uint32_t* ids; const uint64_t* counts;
-    const double* inv_len; const double* w_mass;        // 1/effLen_t ; (prior + mass_t)/effLen_t
-    uint32_t* count_map; int32_t* txp_count;
-    const uint8_t* wide;                                 // per class: visited in the wide phase
-    const uint32_t* wide_list; uint32_t n_wide;
-    uint64_t seed; uint32_t round;
-};
-
-// multinomial(n; p_0..p_{k-1}) as conditional binomials; calls put(i, r_i) for every member.  Member `last` gets what the others
-// leave: a BINV walk costs its mean, so the chain costs n (1 - p_last) steps in all -- least when the LARGEST member is not sampled
-// at all.  `last` is the same for every chain of the wavefront (the member with the largest EM weight: the chains live around the EM
-// solution), so no lane idles; any order gives the same distribution.
-template <bool LIGHT, typename ProbFn, typename PutFn>
-__device__ __forceinline__ void multinomial_chain(Philox& g, uint32_t n, uint32_t k, double p_total, uint32_t last, ProbFn prob, PutFn put) {
-    double p_rem = p_total;
-    uint32_t n_rem = n;
-    for (uint32_t i = 0; i < k; ++i) {
-        if (i == last) continue;
-        const double p = prob(i);
-        const double ratio = (p_rem > 0.0) ? ratio_of(p, p_rem) : 0.0;
-        const double pr = ratio < 1.0 ? ratio : 1.0;
-        const uint32_t r = (n_rem == 0) ? 0u : (LIGHT ? binomial_by_inversion(g, n_rem, pr) : binomial(g, n_rem, pr));
-        p_rem -= p; if (p_rem < 0.0) p_rem = 0.0;
-        put(i, r);
-        n_rem -= r;
-    }
-    put(last, n_rem);
-}
-
-// initCountMap_ (:45-92) for one class and one chain
-template <bool LIGHT = false>
-__device__ __forceinline__ void gibbs_init_class(const GibbsArgs& a, uint64_t c, uint32_t ch) {
-    const uint32_t b = a.rowptr[c], k = a.rowptr[c + 1] - b;
-    const uint32_t n = (uint32_t)a.counts[c];            // uint32 n in MultinomialSampler (:15)
-    const uint32_t nch = a.n_chains;
-    if (k == 0) return;
-    if (k == 1) {                                        // :81-83
-        a.count_map[(uint64_t)b * nch + ch] = n;
-        a.txp_count[(uint64_t)a.ids[b] * nch + ch] += (int32_t)n;
-        return;
-    }
-    double denom = 0.0, w_top = -1.0; uint32_t last = 0;
-    for (uint32_t i = 0; i < k; ++i) { const double w = a.w_mass[a.ids[b + i]]; denom += w; if (w > w_top) { w_top = w; last = i; } }      // :58-63
-    if (!(denom > kGibbsTiny)) {                                                      // :65 -- nothing assigned
-        for (uint32_t i = 0; i < k; ++i) a.count_map[(uint64_t)(b + i) * nch + ch] = 0;
-        return;
-    }
-    Philox g; g.init(a.seed, ch, c);
-    multinomial_chain<LIGHT>(g, n, k, denom, last,
-        [&](uint32_t i) { return a.w_mass[a.ids[b + i]]; },
-        [&](uint32_t i, uint32_t r) {
-            a.count_map[(uint64_t)(b + i) * nch + ch] = r;                            // :76-79
-            a.txp_count[(uint64_t)a.ids[b + i] * nch + ch] += (int32_t)r;             // :86-89
-        });
-}
-
-// sampleRound_ (:113-184) for one class and one chain
-template <bool LIGHT = false>
-__device__ __forceinline__ void gibbs_round_class(const GibbsArgs& a, uint64_t c, uint32_t ch) {
-    const uint32_t b = a.rowptr[c], k = a.rowptr[c + 1] - b;
-    if (k <= 1) return;                                     // singletons keep their full count (:128)
-    const uint32_t nch = a.n_chains;
-    Philox g; g.init(a.seed, ((uint64_t)(a.round + 1) << 32) | ch, c);
-    const double frac = 0.25 + 0.5 * g.uniform();           // U(0.25, 0.75) per class (:106, :115)
-    // pass 1: take round(frac * current) reads away from every member (:138-148)
-    uint32_t n_res = 0, last = 0; double denom = 0.0, w_top = -1.0;
-    for (uint32_t i = 0; i < k; ++i) {
-        const uint64_t at = (uint64_t)(b + i) * nch + ch;
-        const uint32_t t = a.ids[b + i];
-        { const double w = a.w_mass[t]; if (w > w_top) { w_top = w; last = i; } }        // (wavefront-uniform: the member the chain does not sample)
-        const uint32_t cur = a.count_map[at];
-        const uint32_t r = (uint32_t)(frac * (double)cur + 0.5);                       // std::round, values >= 0 (:142)
-        n_res += r;
-        a.count_map[at] = cur - r;
-        const int32_t tc = a.txp_count[(uint64_t)t * nch + ch] - (int32_t)r;
-        a.txp_count[(uint64_t)t * nch + ch] = tc;
-        denom += (kGibbsPrior + (double)tc) * a.inv_len[t];                            // :147
-    }
-    // pass 2: re-draw them from p_i ~ (prior + txpCount_i) * aux_i (:150-170).  denom >= k*1e-8/len > 0,
-    // so the reference's "did not sample" branch (:172-179) cannot trigger for finite inputs.
-    multinomial_chain<LIGHT>(g, n_res, k, denom, last,
-        [&](uint32_t i) { const uint32_t t = a.ids[b + i]; return (kGibbsPrior + (double)a.txp_count[(uint64_t)t * nch + ch]) * a.inv_len[t]; },
-        [&](uint32_t i, uint32_t r) {
-            if (r) { a.count_map[(uint64_t)(b + i) * nch + ch] += r; a.txp_count[(uint64_t)a.ids[b + i] * nch + ch] += (int32_t)r; }
-        });
-}
 
 // one phase: blockIdx.x -> tile (phase + K * x), blockIdx.y -> group of 64 chains
 // Two forms (round 5).  The sampler is long chains of dependent f64 operations: what a SIMD needs is wavefronts to switch between, and
@@ -268,6 +170,18 @@ __global__ void k_gibbs_emit(uint32_t n_chains, uint32_t n_emit, uint64_t M, con
     out[i] = txp_count[t * n_chains + ch];
 }
 
+// sfgpu_chain_eval's kernel: one lane per draw of multinomial_chain over the caller's weights (p_total = their sum in member order)
+template <bool LIGHT>
+__global__ void __launch_bounds__(kGibbsBlock)
+k_chain_eval(const double* __restrict__ w, uint32_t k, uint32_t n, uint32_t last, uint64_t seed, uint64_t count, uint32_t* __restrict__ out) {
+    const uint64_t d = (uint64_t)blockIdx.x * kGibbsBlock + threadIdx.x;
+    if (d >= count) return;
+    double total = 0.0;
+    for (uint32_t i = 0; i < k; ++i) total += w[i];
+    Philox g; g.init(seed, d, 0);
+    multinomial_chain<LIGHT>(g, n, k, total, last, [&](uint32_t i) { return w[i]; }, [&](uint32_t i, uint32_t r) { out[d * k + i] = r; });
+}
+
 }  // namespace sfgpu
 
 using namespace sfgpu;
@@ -291,6 +205,20 @@ static uint32_t gibbs_phase_count(const std::vector<uint32_t>& lo, const std::ve
 }
 
 extern "C" {
+
+int sfgpu_chain_eval(int light, const double* d_w, uint32_t k, uint32_t n, uint32_t last, uint64_t seed, uint64_t count, uint32_t* d_out,
+                     sfgpu_stream stream) {
+    if (light != 0 && light != 1) { set_error("sfgpu_chain_eval: unknown form %d", light); return SFGPU_ERR_INVALID; }
+    SF_REQUIRE(k >= 1 && last < k, SFGPU_ERR_INVALID, "sfgpu_chain_eval: need k >= 1 and last < k");
+    SF_REQUIRE(count * (uint64_t)k <= (1ull << 31), SFGPU_ERR_RANGE, "sfgpu_chain_eval: count times k exceeds 2^31");
+    if (count == 0) return SFGPU_OK;
+    SF_REQUIRE(d_w && d_out, SFGPU_ERR_INVALID, "sfgpu_chain_eval: null pointer");
+    const dim3 g((unsigned)((count + kGibbsBlock - 1) / kGibbsBlock)), b(kGibbsBlock);
+    if (light) hipLaunchKernelGGL(k_chain_eval<true>, g, b, 0, as_stream(stream), d_w, k, n, last, seed, count, d_out);
+    else hipLaunchKernelGGL(k_chain_eval<false>, g, b, 0, as_stream(stream), d_w, k, n, last, seed, count, d_out);
+    SF_CHECK_LAUNCH();
+    return SFGPU_OK;
+}
 
 int sfgpu_gibbs_sample(const sfgpu_problem* prob, const double* d_mass, uint32_t n_samples, uint32_t n_chains,
                        uint64_t seed, int32_t* d_out, sfgpu_gibbs_cb cb, void* user, sfgpu_stream stream) {

@@ -100,6 +100,13 @@ constexpr double kBinvUnscale = binv_unscale(kBinvSwitch - 1u);      // ~ 1 / 16
 
 // a / b for the samplers' ratios (b > 0, finite): on the device the reciprocal instruction and two Newton steps instead of the IEEE
 // division sequence (~6 instead of ~15 instructions; the last bit may differ -- the ratio of two weights that are sums of products)
+// DOMAIN: b normal and finite with a normal reciprocal, 2^-1022 <= b <= 2^1022.  Outside it the device form is not a / b: a denormal b
+// (the reciprocal overflows: inf * 0 in the Newton step) and b = inf give NaN, b > 2^1022 a reciprocal without its low bits -- and
+// multinomial_chain (gibbsfmt.h) reads a NaN ratio as pr = 1: every remaining read to one member.  The callers stay far inside: the
+// Gibbs weights are (1e-8 + count) / effLen with effLen >= 1 and the divisor p_rem always still holds the class's largest weight
+// (member `last` is never subtracted), the tree divides by a count.  A guard (fall back to a / b when the result is not finite, or
+// when b leaves the range) was built and not kept: either form moves the Gibbs kernels' registers and spills -- the heavy round kernel
+// from 4 spilled VGPRs to 6 or 8 -- see profiles/gibbs_chain_resource_usage.md.  tests/test_gpu_rng.py states the domain.
 SF_HD double ratio_of(double a, double b) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(SFGPU_X_IEEE_DIV)
     double y = __builtin_amdgcn_rcp(b);

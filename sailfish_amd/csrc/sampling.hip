@@ -135,4 +135,70 @@ int multinomial_tree(const uint64_t* d_prefix, uint64_t C, uint32_t n_total, uin
     return SFGPU_OK;
 }
 
+// sfgpu_rng_eval's kernel: one lane per element, the form fixed at compile time.  Element i draws from Philox(seed, stream[i] or i,
+// sub[i] or 0): the lanes of a wavefront may hold different arguments, and a lane's draw can be repeated in another launch.
+template <int FORM> __global__ void __launch_bounds__(kSampBlock)
+k_rng_eval(uint64_t seed, const uint64_t* __restrict__ stream, const uint64_t* __restrict__ sub, const uint32_t* __restrict__ cnt,
+           const double* __restrict__ a, const double* __restrict__ b, uint32_t w, uint64_t n, void* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * kSampBlock + threadIdx.x;
+    if (i >= n) return;
+    if (FORM == SFGPU_RNG_RATIO) { ((double*)out)[i] = ratio_of(a[i], b[i]); return; }
+    if (FORM == SFGPU_RNG_BLOCK) {                       // the raw generator: key and counter as given, no init()
+        Philox r;
+        r.key[0] = (uint32_t)seed; r.key[1] = (uint32_t)(seed >> 32);
+        r.ctr[0] = (uint32_t)stream[i]; r.ctr[1] = (uint32_t)(stream[i] >> 32); r.ctr[2] = (uint32_t)sub[i]; r.ctr[3] = (uint32_t)(sub[i] >> 32);
+        r.block();
+        for (int j = 0; j < 4; ++j) ((uint32_t*)out)[i * 4 + j] = r.out[j];
+        return;
+    }
+    Philox g; g.init(seed, stream ? stream[i] : i, sub ? sub[i] : 0);
+    if (FORM == SFGPU_RNG_WORDS) { for (uint32_t j = 0; j < w; ++j) ((uint32_t*)out)[i * w + j] = g.next32(); }
+    else if (FORM == SFGPU_RNG_UNIFORM) { for (uint32_t j = 0; j < w; ++j) ((double*)out)[i * w + j] = g.uniform(); }
+    else if (FORM == SFGPU_RNG_BINOMIAL) ((uint32_t*)out)[i] = binomial(g, cnt[i], a[i]);
+    else ((uint32_t*)out)[i] = binomial_by_inversion(g, cnt[i], a[i]);
+}
+
 }  // namespace sfgpu
+
+using namespace sfgpu;
+
+extern "C" {
+
+int sfgpu_rng_eval(int form, uint64_t seed, const uint64_t* d_stream, const uint64_t* d_substream, const uint32_t* d_n, const double* d_a,
+                   const double* d_b, uint32_t w, uint64_t n, void* d_out, sfgpu_stream stream) {
+    if (form < SFGPU_RNG_WORDS || form > SFGPU_RNG_BLOCK) { set_error("sfgpu_rng_eval: unknown form %d", form); return SFGPU_ERR_INVALID; }
+    const bool per_w = form == SFGPU_RNG_WORDS || form == SFGPU_RNG_UNIFORM, draws = form == SFGPU_RNG_BINOMIAL || form == SFGPU_RNG_BINOMIAL_INV;
+    SF_REQUIRE(n <= (1ull << 31) && (!per_w || n * (uint64_t)w <= (1ull << 31)), SFGPU_ERR_RANGE, "sfgpu_rng_eval: n (times w) exceeds 2^31");
+    if (n == 0 || (per_w && w == 0)) return SFGPU_OK;
+    SF_REQUIRE(d_out && (!draws || (d_n && d_a)) && (form != SFGPU_RNG_RATIO || (d_a && d_b)) && (form != SFGPU_RNG_BLOCK || (d_stream && d_substream)), SFGPU_ERR_INVALID, "sfgpu_rng_eval: null pointer");
+    const dim3 g((unsigned)((n + kSampBlock - 1) / kSampBlock)), b(kSampBlock);
+    hipStream_t st = as_stream(stream);
+    switch (form) {
+    case SFGPU_RNG_WORDS:    hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_WORDS>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    case SFGPU_RNG_UNIFORM:  hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_UNIFORM>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    case SFGPU_RNG_RATIO:    hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_RATIO>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    case SFGPU_RNG_BINOMIAL: hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_BINOMIAL>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    case SFGPU_RNG_BINOMIAL_INV: hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_BINOMIAL_INV>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    default:                 hipLaunchKernelGGL(k_rng_eval<SFGPU_RNG_BLOCK>, g, b, 0, st, seed, d_stream, d_substream, d_n, d_a, d_b, w, n, d_out); break;
+    }
+    SF_CHECK_LAUNCH();
+    return SFGPU_OK;
+}
+
+int sfgpu_mn_tree_eval(const uint64_t* d_prefix, uint64_t C, uint32_t n_total, uint64_t seed, uint64_t draw, uint32_t* d_out, sfgpu_stream stream) {
+    if (C == 0) return SFGPU_OK;
+    SF_REQUIRE(d_prefix && d_out, SFGPU_ERR_INVALID, "sfgpu_mn_tree_eval: null pointer");
+    SF_REQUIRE(C <= (1ull << 31), SFGPU_ERR_RANGE, "sfgpu_mn_tree_eval: C exceeds 2^31");
+    hipStream_t st = as_stream(stream);
+    const uint64_t W = multinomial_tree_width(C);
+    uint32_t *sa = nullptr, *sb = nullptr;
+    SF_HIP(pool_malloc(&sa, W * 4));
+    hipError_t e = pool_malloc(&sb, W * 4);
+    if (e != hipSuccess) { pool_free(sa); SF_HIP(e); }
+    const int rc = multinomial_tree(d_prefix, C, n_total, seed, draw, nullptr, d_out, sa, sb, st);
+    void* both[2] = {sa, sb};
+    pool_free_on_many(both, 2, st);               // back to the cache behind the tree's kernels: no host wait
+    return rc;
+}
+
+}  // extern "C"

@@ -1463,6 +1463,51 @@ SFGPU_API int sfgpu_hits_verify_gapped(const sfgpu_index* idx, const char* d_seq
                                        sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, sfgpu_hit_gscore* d_scores_out, uint64_t* n_out,
                                        sfgpu_verify_gstats* stats, sfgpu_stream stream);
 
+/* MATE RESCUE: an optional pass between sfgpu_map_reads and sfgpu_hits_verify.  The mapper places a mate on one exact seed; a pair
+ * of which one mate found none leaves it as orphan records only.  This pass searches each such orphan's transcript for the missing
+ * mate, ungapped and with sfgpu_hits_verify's base comparison, inside the window an inward-facing fragment allows, and turns the
+ * orphan into a pair where it finds a placement.  Arguments, base codes and orientation are sfgpu_hits_verify's (paired batches
+ * only); the rule is stated once in csrc/rescuefmt.h (hits.rescue_mates_host is the Python statement):
+ *   reads       a read is eligible iff it has at least one record and every record has mate_status 1 or 2; every other read keeps
+ *               its records unchanged and in order.
+ *   job         one orphan record of an eligible read.  The anchor is the mate it places (mate 1 for status 1, mate 2 for status 2)
+ *               at p = pos on strand f = fwd, la bases long (from d_off1 / d_off2, not the 16-bit fields); the missing mate is the
+ *               other one, lb bases, oriented on strand 1 - f.
+ *   candidates  x with 0 <= x <= tlen - lb and, W = opts->window: f == 1: x >= p and x + lb <= p + W; f == 0: x + lb <= p + la and
+ *               x >= p + la - W (inward facing, no dovetail).  lb == 0, lb > tlen, lb > 65 535 and la > 65 535 give none.
+ *   score       mism(x) = the columns j < lb where either code is 4 or the codes differ against transcript base x + j.  A candidate
+ *               passes iff 1000 * (lb - mism) >= min_identity_permille * lb; the placement is the passing candidate of least mism,
+ *               the lowest x on a tie.
+ *   record      status 1 -> {tid, p, x, frag, len1, len2, f, 1 - f, 3, 0}; status 2 -> {tid, x, p, frag, len1, len2, 1 - f, f, 3, 0};
+ *               frag = max(ends) - min(starts), as sfgpu_map_reads computes it.
+ *   read        at least one job placed: the read's records become the placed records only, ordered by (tid, fwd) ascending and by
+ *               input order on equal keys (the order sfgpu_map_reads leaves for pairs); none placed: the read keeps its orphans.
+ *   output      d_hits_out (room for d_hit_offsets[n_reads] records: never more go out than came in), CSR offsets over the same
+ *               reads (d_offsets_out, n_reads + 1), per output record the placed mate's mism saturated at 65 535 (d_mism_out, may
+ *               be NULL; 0 for records that passed through), *n_out = the records.  The outputs must not overlap the inputs.
+ *   errors      a record with tid >= the index's transcript count: SFGPU_ERR_RANGE, sfgpu_last_error names the lowest such record,
+ *               the outputs are left untouched.  A single-end batch (d_seq2 == NULL), min_identity_permille > 1000, a window
+ *               outside 1 .. 2^20, NULL idx / opts / n_out / stats, or NULL reads, records or outputs where n_reads > 0 needs
+ *               them: SFGPU_ERR_INVALID.
+ * Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_rescue_opts {
+    uint32_t min_identity_permille;   /* 0 .. 1000 */
+    uint32_t window;                  /* 1 .. 2^20: the longest fragment searched for */
+} sfgpu_rescue_opts;
+typedef struct sfgpu_rescue_stats {
+    uint64_t reads_eligible;          /* reads whose records are all orphans */
+    uint64_t records_orphan;          /* their records: the jobs */
+    uint64_t jobs_with_candidates;
+    uint64_t candidates;              /* sum of the window sizes */
+    uint64_t reads_rescued, records_rescued;
+    uint64_t records_dropped;         /* orphans of rescued reads that found no mate */
+    uint64_t sum_mism;                /* mism of the placed mates, unsaturated */
+} sfgpu_rescue_stats;
+SFGPU_API int sfgpu_hits_rescue_mates(const sfgpu_index* idx, const char* d_seq1, const uint64_t* d_off1, const char* d_seq2, const uint64_t* d_off2,
+                                      uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const sfgpu_rescue_opts* opts,
+                                      sfgpu_hit* d_hits_out, uint32_t* d_offsets_out, uint16_t* d_mism_out, uint64_t* n_out,
+                                      sfgpu_rescue_stats* stats, sfgpu_stream stream);
+
 /* The gapped ALIGNMENT of the records that survive sfgpu_hits_verify_gapped: the path through the same band, as a position and
  * BAM CIGAR words per job.  Arguments, jobs, base codes and orientation are sfgpu_hits_verify_gapped's; the rule, with its tie
  * rules, is stated once in csrc/aligngfmt.h (hits.align_hits_host is the Python statement):

@@ -233,6 +233,18 @@ class VerifyGStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RescueOpts(C.Structure):
+    _fields_ = [("min_identity_permille", C.c_uint32), ("window", C.c_uint32)]
+
+
+class RescueStats(C.Structure):
+    _fields_ = [("reads_eligible", C.c_uint64), ("records_orphan", C.c_uint64), ("jobs_with_candidates", C.c_uint64), ("candidates", C.c_uint64),
+                ("reads_rescued", C.c_uint64), ("records_rescued", C.c_uint64), ("records_dropped", C.c_uint64), ("sum_mism", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class AlignGOpts(C.Structure):
     _fields_ = [("max_indel", C.c_uint32), ("reserved", C.c_uint32), ("scratch_cap_bytes", C.c_uint64)]
 
@@ -392,6 +404,8 @@ _SIGS = {
                                     C.POINTER(FilterStats), _P]),
     "sfgpu_hits_verify": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(VerifyOpts), _P, _P, _P, C.POINTER(C.c_uint64),
                                     C.POINTER(VerifyStats), _P]),
+    "sfgpu_hits_rescue_mates": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(RescueOpts), _P, _P, _P, C.POINTER(C.c_uint64),
+                                          C.POINTER(RescueStats), _P]),
     "sfgpu_hits_verify_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(VerifyGOpts), _P, _P, _P, C.POINTER(C.c_uint64),
                                            C.POINTER(VerifyGStats), _P]),
     "sfgpu_hits_align_gapped": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(AlignGOpts), _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),

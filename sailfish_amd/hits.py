@@ -378,6 +378,119 @@ def verify_hits(index, hits, offsets, reads1, reads2=None, *, min_identity=0.9, 
     return out_hits[: n_out.value * 24], out_off, scores[: n_out.value * 8], st.as_dict()
 
 
+RESCUE_STATS = ("reads_eligible", "records_orphan", "jobs_with_candidates", "candidates", "reads_rescued", "records_rescued", "records_dropped", "sum_mism")
+MAX_RESCUE_WINDOW = 1 << 20
+
+
+def _rescue_window(window):
+    w = int(window)
+    if w != window or not 1 <= w <= MAX_RESCUE_WINDOW:
+        raise ValueError(f"window = {window!r} is no integer in 1 .. {MAX_RESCUE_WINDOW}")
+    return w
+
+
+def rescue_mates_host(transcripts, hits, offsets, reads1, reads2, min_identity_permille, window):
+    """The statement of mate rescue (csrc/rescuefmt.h restated in numpy; what sfgpu_hits_rescue_mates is judged by).  Arguments as
+    verify_hits_host, of a paired batch (reads2 is None: ValueError); window = W, 1 .. 2^20.  A read is eligible iff it has a record
+    and every record has mate_status 1 or 2; every other read keeps its records.  A job is one orphan record of an eligible read: the
+    anchor (mate 1 for status 1, mate 2 for status 2; la bases) sits at p = pos on strand f = fwd, the missing mate (the other one, lb
+    bases) is oriented on strand 1 - f.  Candidates are the x with 0 <= x <= tlen - lb and, f == 1: x >= p and x + lb <= p + W; f == 0:
+    x + lb <= p + la and x >= p + la - W; lb == 0, lb > tlen, lb > 65 535 and la > 65 535 give none.  mism(x) counts the columns where
+    either code is 4 or the codes differ; a candidate passes iff 1000 (lb - mism) >= permille lb; the placement is the passing
+    candidate of least mism, the lowest x on a tie.  A placed job yields the pair record -- status 1: (tid, p, x, frag, len1, len2, f,
+    1 - f, 3, 0); status 2: (tid, x, p, frag, len1, len2, 1 - f, f, 3, 0); frag = max(ends) - min(starts).  A read with a placed job
+    keeps its placed records only, ordered by (tid, fwd) and by input order on equal keys; a read without keeps its orphans.
+    -> (hits, offsets uint32[R + 1], mism uint16 per output record: the placed mate's, saturated, 0 for records passed through,
+    stats dict of RESCUE_STATS); ValueError naming the lowest record whose tid is not a transcript."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    permille, W = int(min_identity_permille), _rescue_window(window)
+    if not 0 <= permille <= 1000:
+        raise ValueError("min_identity_permille lies outside 0 .. 1000")
+    if reads2 is None:
+        raise ValueError("a single-end batch has no mates to rescue")
+    n_rec = int(off[-1]) if len(off) else 0
+    bad = np.nonzero(hits["tid"][:n_rec] >= len(transcripts))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(transcripts)}")
+    stats = dict.fromkeys(RESCUE_STATS, 0)
+    tcodes = {}
+    out, mism_out, out_off = [], [], [0]
+    for r in range(len(off) - 1):
+        recs = [hits[i] for i in range(off[r], off[r + 1])]
+        placed = []
+        if recs and all(int(h["mate_status"]) in (1, 2) for h in recs):
+            stats["reads_eligible"] += 1
+            stats["records_orphan"] += len(recs)
+            len1, len2 = len(reads1[r]), len(reads2[r])
+            for n, h in enumerate(recs):
+                st, tid, p, f = int(h["mate_status"]), int(h["tid"]), int(h["pos"]), int(h["fwd"] != 0)
+                la, lb, mate = (len1, len2, reads2[r]) if st == 1 else (len2, len1, reads1[r])
+                if tid not in tcodes:
+                    tcodes[tid] = _BASE_CODE[np.frombuffer(transcripts[tid], np.uint8)]
+                t = tcodes[tid]
+                if lb == 0 or lb > len(t) or lb > 65535 or la > 65535:
+                    continue
+                lo, hi = (p, p + W - lb) if f else (p + la - W, p + la - lb)
+                lo, hi = max(lo, 0), min(hi, len(t) - lb)
+                if hi < lo:
+                    continue
+                stats["jobs_with_candidates"] += 1
+                stats["candidates"] += hi - lo + 1
+                q = _oriented_codes(mate, not f)
+                win = np.lib.stride_tricks.sliding_window_view(t[lo:hi + lb], lb)
+                mm = ((win != q) | (win > 3) | (q > 3)).sum(axis=1)
+                ok = np.nonzero(1000 * (lb - mm) >= permille * lb)[0]
+                if not len(ok):
+                    continue
+                at = int(ok[np.argmin(mm[ok])])                       # (argmin: the first of the least)
+                x, m = lo + at, int(mm[at])
+                frag = (max(p + la, x + lb) - min(p, x)) & 0xFFFFFFFF
+                rec = (tid, p, x, frag, len1, len2, f, 1 - f, 3, 0) if st == 1 else (tid, x, p, frag, len1, len2, 1 - f, f, 3, 0)
+                placed.append(((tid, rec[6], n), rec, m))
+        if placed:
+            stats["reads_rescued"] += 1
+            stats["records_rescued"] += len(placed)
+            stats["records_dropped"] += len(recs) - len(placed)
+            for _, rec, m in sorted(placed, key=lambda v: v[0]):
+                out.append(rec)
+                mism_out.append(min(m, 65535))
+                stats["sum_mism"] += m
+        else:
+            out.extend(h.tolist() for h in recs)
+            mism_out.extend([0] * len(recs))
+        out_off.append(len(out))
+    return np.array(out, dtype=HIT_DTYPE), np.array(out_off, np.uint32), np.array(mism_out, np.uint16), stats
+
+
+def rescue_mates(index, hits, offsets, reads1, reads2, *, min_identity=0.9, window=1000):
+    """Rescue the missing mates of orphan-only reads on the device (sfgpu_hits_rescue_mates; the rules are rescue_mates_host's).
+    index, hits / offsets, reads1 / reads2 as verify_hits takes them, of a paired batch.  Every orphan record of a read that has
+    nothing but orphans has its transcript searched for the other mate -- ungapped, on the opposite strand, inside the window an
+    inward-facing fragment of at most `window` bases (1 .. 2^20, else ValueError) allows; a placement needs at least min_identity of
+    the mate's bases equal to the transcript's (the permille is int(round(min_identity * 1000)); outside 0 .. 1000: ValueError).  A
+    read with a placement keeps its placed records, as PAIRED_END_PAIRED records in the mapper's form and order; every other read
+    keeps what it had.
+    -> (hits, offsets, mism: uint8 device tensor of '<u2' values, one per output record, stats dict)"""
+    permille = _permille(min_identity)
+    W = _rescue_window(window)
+    if reads2 is None:
+        raise ValueError("a single-end batch has no mates to rescue")
+    dev, d_hits, d_off, R, s1, o1, s2, o2, n = _device_batch(index, hits, offsets, reads1, reads2)
+    out_off = torch.empty(R + 1, dtype=torch.int32, device=dev)
+    mism = torch.empty(max(n, 1) * 2, dtype=torch.uint8, device=dev)
+    o, st, n_out = _lib.RescueOpts(permille, W), _lib.RescueStats(), C.c_uint64(0)
+
+    def call(out_hits, cap):                             # (never more records than came in: the room is known beforehand)
+        rc = _lib.lib().sfgpu_hits_rescue_mates(index._h, _lib.ptr(s1), _lib.ptr(o1), _lib.ptr(s2), _lib.ptr(o2), R, _lib.ptr(d_hits), _lib.ptr(d_off),
+                                                C.byref(o), _lib.ptr(out_hits), _lib.ptr(out_off), _lib.ptr(mism), C.byref(n_out), C.byref(st), _lib.current_stream_ptr())
+        return rc, n_out.value
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        out_hits, total = _call_with_room(max(n, 1), lambda cap: torch.empty(cap * 24, dtype=torch.uint8, device=dev), call)
+    return out_hits[: total * 24], out_off, mism[: total * 2], st.as_dict()
+
+
 ALIGNG_STATS = ("jobs", "jobs_traced", "unalignable", "sum_nm", "words", "scratch_bytes")
 CIGAR_M, CIGAR_I, CIGAR_D, CIGAR_S = 0, 1, 2, 4                                       # BAM's operation codes
 _DIAG, _INS, _DEL = 1, 2, 4

@@ -67,8 +67,12 @@ class QuasiIndex:
         _lib.check(self._L.sfgpu_index_set_seeds(self._h, int(seeds)))
         self.seeds = int(seeds)
 
-    def map_reads(self, reads1, reads2=None, validate=None, tags=False):
+    def map_reads(self, reads1, reads2=None, validate=None, tags=False, rescue=None):
         """reads1 / reads2: lists of str / bytes, or (uint8 tensor, int64 offsets) pairs already packed.
+        rescue: None, or a dict of hits.rescue_mates' keywords (min_identity, window; {} = its defaults) for a paired batch (else
+        ValueError): before anything is validated, the reads that have nothing but orphan records have their orphans' transcripts
+        searched for the missing mate, and where one is placed the read's records become pairs; `last_rescue_stats` holds the pass's
+        counters and `last_rescue_mism` the placed mates' mismatches, one '<u2' per record handed to the validation.
         validate: None, or a dict of hits.verify_hits' keywords (min_identity, keep_best, max_indel; {} = its defaults): the records are then
         verified against the transcripts' bases before they are returned, and `last_scores` / `last_verify_stats` hold the
         survivors' scores and the pass's counters.  With "align": True beside a max_indel of 1 .. 15 (else ValueError) the survivors
@@ -107,6 +111,9 @@ class QuasiIndex:
             torch.cuda.current_stream().synchronize()            # (a second call only if the first capacity guess was too small)
             hits, n_rec = _call_with_room(max(4 * n, 1024), lambda cap: torch.empty(cap * 24, dtype=torch.uint8, device=dev), call)
         hits = hits[: n_rec * 24]
+        if rescue is not None:
+            from .hits import rescue_mates
+            hits, off, self.last_rescue_mism, self.last_rescue_stats = rescue_mates(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), **rescue)
         if validate is not None:
             from .hits import verify_hits
             hits, off, self.last_scores, self.last_verify_stats = verify_hits(self, hits, off, (s1, o1), None if s2 is None else (s2, o2), **validate)
@@ -151,8 +158,26 @@ def _validation(validate_mappings, min_identity, keep_best, max_indel=0):
     return dict(min_identity=min_identity, keep_best=bool(keep_best), max_indel=k), dict.fromkeys(VERIFYG_STATS, 0)
 
 
+def _rescue(rescue_mates, rescue_window, min_identity, paired, lib_format, sopt):
+    """-> (the `rescue` dict for QuasiIndex.map_reads or None, the counters to accumulate over the batches); ValueError at once for
+    a single-end run, a library format whose mates do not face each other, a min_identity outside 0 .. 1 or a window outside
+    1 .. 2^20 (None: sopt.maxFragLen), before anything is indexed"""
+    if not rescue_mates:
+        return None, None
+    from .experiment import SailfishOpts
+    from .hits import LIBRARY_FORMATS, RESCUE_STATS, TOWARD, _permille, _rescue_window
+    if not paired:
+        raise ValueError("rescue_mates=True needs a paired run: a single-end read has no mate to rescue")
+    fmt = LIBRARY_FORMATS.get(lib_format.upper()) if isinstance(lib_format, str) else None if lib_format is None else tuple(lib_format)
+    if fmt is None or fmt[0] != 1 or fmt[1] != TOWARD:
+        raise ValueError(f"rescue_mates=True searches for inward-facing mates: the library format {lib_format!r} is not one of IU, ISF, ISR")
+    _permille(min_identity)
+    window = _rescue_window((sopt if sopt is not None else SailfishOpts()).maxFragLen if rescue_window is None else rescue_window)
+    return dict(min_identity=min_identity, window=window), dict.fromkeys(RESCUE_STATS, 0)
+
+
 # the passes of a batch whose counters a run adds up: (name, QuasiIndex's attribute after map_reads, the keys that are maxima, not sums)
-_PASSES = (("verify", "last_verify_stats", ()), ("align", "last_align_stats", ("scratch_bytes",)), ("tag", "last_tag_stats", ("max_md_bytes",)))
+_PASSES = (("rescue", "last_rescue_stats", ()), ("verify", "last_verify_stats", ()), ("align", "last_align_stats", ("scratch_bytes",)), ("tag", "last_tag_stats", ("max_md_bytes",)))
 
 
 def _is_sink(x):
@@ -209,14 +234,15 @@ class _UnmappedWriters:
 
 class _MappingsRun:
     """What quantify_reads and quantify_files share from the mapper's call to the files beside the estimates: the
-    options' checks, the two kinds of writers, a batch's map -> validate -> align -> tag -> write, the counters added up over the
+    options' checks, the two kinds of writers, a batch's map -> rescue -> validate -> align -> tag -> write, the counters added up over the
     batches, and their report.  Constructed before anything is indexed: it raises the options' ValueErrors."""
 
     def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                 mappings_gapped, mappings_tags, write_unmapped, unmapped_compress):
+                 mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None):
         from .hits import ALIGNG_STATS, MDTAG_STATS
         if mappings_sorted and mappings_format != "bam":
             raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
+        self.rescue, rstats = _rescue(rescue_mates, rescue_window, min_identity, paired, lib_format, sopt)
         self.validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
         astats = tstats = None
         if mappings_gapped:
@@ -227,7 +253,7 @@ class _MappingsRun:
             if write_mappings is None or not mappings_oriented:
                 raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
             tstats = dict.fromkeys(MDTAG_STATS, 0)
-        self.stats = dict(verify=vstats, align=astats, tag=tstats)                 # None: the pass does not run
+        self.stats = dict(rescue=rstats, verify=vstats, align=astats, tag=tstats)  # None: the pass does not run
         self.targets, self.compress = _UnmappedWriters.targets(write_unmapped, unmapped_compress, paired), unmapped_compress
         self.paired, self.sink = paired, write_mappings
         self.sam_kw = dict(format=mappings_format, oriented=mappings_oriented, sort="coordinate" if mappings_sorted else None)
@@ -246,7 +272,8 @@ class _MappingsRun:
         """One batch: mapped (validated, aligned, tagged, as the options say), its counters added, and written to the run's files.
         r1 / r2: what map_reads takes (packed pairs on the device where the run writes a file); quals / mate_names: one entry per mate
         file; sam_quals: whether the mappings file takes the qualities too; read_names: its QNAMEs.  -> (hits, offsets)"""
-        h, o = idx.map_reads(r1, r2, validate=self.validate, tags=self.stats["tag"] is not None)
+        opt = {} if self.rescue is None else dict(rescue=self.rescue)              # (without the option the call is the one it was)
+        h, o = idx.map_reads(r1, r2, validate=self.validate, tags=self.stats["tag"] is not None, **opt)
         for name, attr, maxima in _PASSES:
             total = self.stats[name]
             if total is not None:
@@ -266,17 +293,22 @@ class _MappingsRun:
                 w.close()
 
     def report(self, exp, sopt):
-        """every pass's counters on the experiment (`verify_stats`, `align_stats`, `tag_stats`: None where the pass did not run;
+        """every pass's counters on the experiment (`rescue_stats`, `verify_stats`, `align_stats`, `tag_stats`: None where the pass did not run;
         `unmapped_stats` only with write_unmapped) and one line each to sopt.jointLog"""
-        v, a, t = (self.stats[name] for name, _, _ in _PASSES)
+        res, v, a, t = (self.stats[name] for name, _, _ in _PASSES)
         u = None if self.unm is None else self.unm.stats()
         if exp is not None:
-            exp.verify_stats, exp.align_stats, exp.tag_stats = v, a, t
+            exp.rescue_stats, exp.verify_stats, exp.align_stats, exp.tag_stats = res, v, a, t
             if u is not None:
                 exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
         if log is None:
             return
+        if res is not None:
+            log(0, "rescued mates (min identity {:g}, window {}): {} reads had orphan records only ({} records); {} of them now pair, with {} records; "
+                   "{} of their orphans found no mate and were dropped; {} mismatches in the placed mates".format(
+                       self.rescue["min_identity"], self.rescue["window"], res["reads_eligible"], res["records_orphan"], res["reads_rescued"],
+                       res["records_rescued"], res["records_dropped"], res["sum_mism"]))
         val = self.validate
         if v is not None and val.get("max_indel"):
             log(0, "validated mappings (min identity {:g}, max indel {}{}): {} of {} records kept ({} below the identity, {} not the best of their read); "
@@ -302,7 +334,7 @@ class _MappingsRun:
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -338,10 +370,18 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     called r<index of the read>, FASTQ where quals1 (quals2) is given, else FASTA.  unmapped_compress=True (it needs write_unmapped)
     writes BGZF files.  Neither the estimates nor the mappings file depend on it; the counts are left on the experiment as
     `unmapped_stats` (reads, unmapped, bytes per file) and go to sopt.jointLog as one line.
+    rescue_mates=True (a paired run with an inward-facing library format -- IU, ISF, ISR -- else ValueError before anything is
+    indexed) searches, in every batch and before any validation, for the missing mates of the reads that mapped as orphans only
+    (hits.rescue_mates): each orphan's transcript, on the opposite strand, ungapped, inside the window a fragment of at most
+    rescue_window bases allows (None: sopt.maxFragLen; outside 1 .. 2^20: ValueError); a mate is placed where at least min_identity
+    of its bases match (the same keyword as the validation's, whether or not validate_mappings is on), and the read's records then
+    are pairs like any the mapper made: validation, alignment, tags, the mappings and unmapped files and the estimates see them so.
+    The search stays ungapped with max_indel > 0; the validation then scores the rescued pair with gaps like every record.  The
+    counters are left on the experiment as `rescue_stats` (None without the option) and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt)
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
 
@@ -382,7 +422,7 @@ def _dollar_separated(bases, off):
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -393,7 +433,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
     reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel, mappings_gapped and
-    mappings_tags as in quantify_reads.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
+    mappings_tags as in quantify_reads; so are rescue_mates and rescue_window.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
     as they came in -- each mate file's own names up to the first space or tab (names="device" on both files), bases and quality lines
     (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
     FASTA unmapped file.  No name, base or offset visits the host.
@@ -401,7 +441,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt)
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     keep = run.mapped and bool(mappings_oriented)            # the mappings file carries QUAL

@@ -768,6 +768,22 @@ SFGPU_API int sfgpu_sam_write_text_t(const struct sfgpu_hit* d_hits, const uint3
                                      void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
                                      const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
                                      const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
+/* sfgpu_sam_write_text_t with the batch's posteriors (sfgpu_hits_posteriors' d_rec and d_f32 for the same records: one entry per
+ * record, so both lines of a pair carry the record's value); sfgpu_sam_write_text_t is this call with post == NULL, and then every
+ * byte is the same.  Given, a mapped line ends ... QUAL [\t NM ... \t MD ... \t NH ...] \t ZW:f:<token> \n, the token being
+ * printf("%g") of the record's posterior probability, placed from d_zw_rec; the lines of a read without records carry nothing.
+ * The two pointers go together (SFGPU_ERR_INVALID otherwise); tags and posteriors are independent of each other. */
+typedef struct sfgpu_samw_post {
+    const uint32_t* d_zw_rec;    /* [n] */
+    const float* d_zw_f32;       /* [n] */
+} sfgpu_samw_post;
+SFGPU_API int sfgpu_sam_write_text_p(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
+                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
+                                     const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags, const sfgpu_samw_post* post);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
@@ -889,6 +905,16 @@ SFGPU_API int sfgpu_sam_write_bgzf_t(const struct sfgpu_hit* d_hits, const uint3
                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
                                      int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
                                      const sfgpu_samw_tags* tags);
+/* ... and with the batch's posteriors, as sfgpu_sam_write_text_p; with post == NULL this is sfgpu_sam_write_bgzf_t, byte for byte.
+ * SFGPU_SAMW_BAM: a mapped line's record ends, behind NH where there is one, Z W f and the four bytes of d_zw_f32's float, and
+ * block_size counts those seven bytes: the bytes of sam_to_bam of the text with its ZW:f: tokens. */
+SFGPU_API int sfgpu_sam_write_bgzf_p(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
+                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
+                                     const sfgpu_samw_tags* tags, const sfgpu_samw_post* post);
 /* Reads as a FASTA / FASTQ text, formatted on the device from the batch where it lies: the mirror of sfgpu_reads_parse_*.  What a
  * record says is csrc/readwfmt.h (the bytes of readfile.reads_text_host):
  *   d_bases / d_off[n_reads + 1]   the bases back to back and their int64 offsets (never decreasing, none negative)
@@ -993,6 +1019,15 @@ SFGPU_API int sfgpu_bamsort_collect_t(sfgpu_bamsort* b, const struct sfgpu_hit* 
                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
                                       const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
+/* collect with the batch's posteriors, as sfgpu_sam_write_bgzf_p (post == NULL: sfgpu_bamsort_collect_t, byte for byte).  Sort key,
+ * bin and index do not depend on the tag. */
+SFGPU_API int sfgpu_bamsort_collect_p(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
+                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
+                                      const sfgpu_samw_post* post);
 SFGPU_API int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,
                                    void* user, sfgpu_bamsort_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);
@@ -1574,6 +1609,32 @@ SFGPU_API int sfgpu_hits_md_tags(const sfgpu_index* idx, const char* d_seq1, con
                                  uint32_t n_reads, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, const int32_t* d_aln_pos,
                                  const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, uint32_t* d_nm, uint64_t* d_md_off, uint8_t* d_md,
                                  uint64_t cap_md, uint64_t* n_md, sfgpu_mdtag_stats* stats, sfgpu_stream stream);
+
+/* The posterior probability of every record of a batch under a weight per transcript, and what a mappings file says of it in its
+ * ZW:f: tag (the rule is stated once in csrc/postfmt.h; hits.posteriors_host is the Python statement).  Only tid is read of a
+ * record; no index and no read bases are needed.
+ *   weight  x_h = d_weights[tid_h], a weight below 2^-960 reading as 0.  Every record is a candidate of its own: a transcript that
+ *           holds two records of a read has two terms.
+ *   sum     S over the n records of a read, in a fixed order whatever way the work is laid out: 64 accumulators a_j = x_j +
+ *           x_{j+64} + ... serially and ascending, then a_j += a_{j xor k} for k = 32, 16, 8, 4, 2, 1; S = a_0.
+ *   value   p_h = x_h / S where S > 0, else 1 / n; a p_h below 2^-56 is written as 0.
+ *   output  d_p[n] the values; d_rec[n] their six-digit records (csrc/gfmt.h: the token is printf("%g", p)); d_f32[n] the float a
+ *           BAM reader gets from that token, (float)strtod(token); n = d_hit_offsets[n_reads].  n_reads == 0 is a valid call.
+ *   errors  the outputs untouched, the weights checked first: a weight that is negative, NaN, infinite or above 2^960:
+ *           SFGPU_ERR_INVALID naming the lowest transcript; tid >= n_refs: SFGPU_ERR_RANGE naming the lowest record; NULL pointers:
+ *           SFGPU_ERR_INVALID.
+ * Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_posterior_stats {
+    uint64_t reads;
+    uint64_t reads_mapped;            /* reads with a record */
+    uint64_t reads_multi;             /* ... with two or more */
+    uint64_t records;
+    uint64_t reads_flat;              /* reads with records whose S is 0: 1 / n each */
+    uint64_t records_zero;            /* records whose p is written as 0 */
+    uint64_t max_records;             /* of the read with the most */
+} sfgpu_posterior_stats;
+SFGPU_API int sfgpu_hits_posteriors(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, const double* d_weights, uint64_t n_refs,
+                                    double* d_p, uint32_t* d_rec, float* d_f32, sfgpu_posterior_stats* stats, sfgpu_stream stream);
 
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,

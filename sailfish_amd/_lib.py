@@ -297,11 +297,26 @@ _SAMW_QUAL = [_P, _P, C.c_int]
 _SAMW_ALN = [_P, _P, _P]
 
 
+class PosteriorStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("reads_mapped", C.c_uint64), ("reads_multi", C.c_uint64), ("records", C.c_uint64), ("reads_flat", C.c_uint64),
+                ("records_zero", C.c_uint64), ("max_records", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class SamwTags(C.Structure):
     _fields_ = [("d_nm", C.c_void_p), ("d_md_off", C.c_void_p), ("d_md", C.c_void_p)]
 
 
 _SAMW_TAGS = [C.POINTER(SamwTags)]
+
+
+class SamwPost(C.Structure):
+    _fields_ = [("d_zw_rec", C.c_void_p), ("d_zw_f32", C.c_void_p)]
+
+
+_SAMW_POST = [C.POINTER(SamwPost)]
 
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
@@ -368,6 +383,7 @@ _SIGS = {
     "sfgpu_sam_write_text_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_sam_write_text_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_sam_write_text_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
+    "sfgpu_sam_write_text_p": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -380,12 +396,14 @@ _SIGS = {
     "sfgpu_bamsort_collect": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_bamsort_collect_a": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_bamsort_collect_t": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
+    "sfgpu_bamsort_collect_p": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
     "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
     "sfgpu_bamsort_close": (C.c_int, [_P]),
     "sfgpu_sam_write_bgzf": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT]),
     "sfgpu_sam_write_bgzf_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL]),
     "sfgpu_sam_write_bgzf_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
     "sfgpu_sam_write_bgzf_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
+    "sfgpu_sam_write_bgzf_p": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
     "sfgpu_reads_write_text": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(ReadWriteResult), _P]),
     "sfgpu_reads_write_bgzf": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(ReadWriteResult), _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),
@@ -412,6 +430,7 @@ _SIGS = {
                                           C.POINTER(AlignGStats), _P]),
     "sfgpu_hits_md_tags": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(MdTagStats), _P]),
+    "sfgpu_hits_posteriors": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.POINTER(PosteriorStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

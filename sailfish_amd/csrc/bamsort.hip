@@ -373,16 +373,26 @@ extern "C" int sfgpu_bamsort_open(sfgpu_bamsort** out) {
     return SFGPU_OK;
 }
 
+extern "C" int sfgpu_bamsort_collect_p(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
+                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
+                                       const sfgpu_samw_tags* tags, const sfgpu_samw_post* post) {
+    SF_REQUIRE(b, SFGPU_ERR_INVALID, "sfgpu_bamsort_collect: null handle");
+    SF_REQUIRE(!b->finished, SFGPU_ERR_STATE, "sfgpu_bamsort_collect: the store is finished");
+    return samw_collect_bam(b, samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                          d_seq2, d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post), out, stream);
+}
+
 extern "C" int sfgpu_bamsort_collect_t(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                        const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                        const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                        const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
                                        const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
                                        const sfgpu_samw_tags* tags) {
-    SF_REQUIRE(b, SFGPU_ERR_INVALID, "sfgpu_bamsort_collect: null handle");
-    SF_REQUIRE(!b->finished, SFGPU_ERR_STATE, "sfgpu_bamsort_collect: the store is finished");
-    return samw_collect_bam(b, samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                          d_seq2, d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags), out, stream);
+    return sfgpu_bamsort_collect_p(b, d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                   d_seq2, d_seq2_off, read_index_base, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
 }
 
 extern "C" int sfgpu_bamsort_collect_a(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,

@@ -22,6 +22,8 @@
 //   5  the alignment ends beyond 2^29: pos + match > 2^29
 // With tags given (samwfmt.h: samw_tags) a mapped line's record ends, behind QUAL, NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>, <t>
 // being the first of c C s S i I that holds the value (what sam_to_bam picks), and block_size counts them.
+// With posteriors given (samwfmt.h: samw_zw) the record then ends Z W f and the four bytes of tag_zw_f32's float: what sam_to_bam
+// makes of the text's ZW:f:<token>; block_size counts those seven bytes.
 // With an alignment given (samwfmt.h: samw_line) the CIGAR words are the slot's; bin and rule 5 take the reference span (M + D) for
 // `match`, rule 4 compares the bases with the read bases the CIGAR names (S + M + I) and also covers more than 65 535 operations.
 #pragma once
@@ -119,10 +121,18 @@ SAMW_HD uint64_t bamw_tags_len(const SamwArgs& a, const SamwLine& l, uint64_t r)
     if (!samw_tags(a, l, r, &t)) return 0;
     return 3ull + bamw_int_bytes(t.nm) + 3ull + t.md_len + 1ull + 3ull + bamw_int_bytes(t.nh);
 }
+// Z W f and the float's bytes, behind the other tags
+constexpr uint32_t kBamwZw = 7;
+SAMW_HD uint64_t bamw_zw_len(const SamwArgs& a, const SamwLine& l) { return a.tag_zw_rec && l.mapped ? kBamwZw : 0u; }
+// byte i of them
+SAMW_HD uint8_t bamw_zw_byte(const SamwArgs& a, const SamwLine& l, uint32_t i) {
+    if (i < 3u) return (uint8_t)"ZWf"[i];
+    return reinterpret_cast<const uint8_t*>(a.tag_zw_f32 + (l.slot >> 1))[i - 3u];
+}
 SAMW_HD uint64_t bamw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r) {
     const uint8_t* seq;
     const uint64_t n = bamw_l_seq(a, l, r, &seq);
-    return kBamwFixed + samw_qname_len(a, r) + 1u + 4u * bamw_cigar_ops(l) + (n + 1) / 2 + n + bamw_tags_len(a, l, r);
+    return kBamwFixed + samw_qname_len(a, r) + 1u + 4u * bamw_cigar_ops(l) + (n + 1) / 2 + n + bamw_tags_len(a, l, r) + bamw_zw_len(a, l);
 }
 SAMW_HD uint64_t bamw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
     const uint32_t n = h ? samw_record_lines(*h) : samw_empty_lines(a.paired != 0);
@@ -204,6 +214,7 @@ inline int bamw_serial(const SamwArgs& a, uint8_t* out, SamwSerial* res) {
                 *p++ = 0;
                 p += bamw_put_int_tag('N', 'H', t.nh, [&](int i, uint8_t b) { p[i] = b; });
             }
+            for (uint32_t i = 0; i < bamw_zw_len(a, l); ++i) *p++ = bamw_zw_byte(a, l, i);
         }
         at += len;
         res->n_lines++;

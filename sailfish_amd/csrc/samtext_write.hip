@@ -12,7 +12,7 @@
 //           textchunks.h: the longest unit and the greedy chunk ends.
 //           The quality rule (every byte in '!' .. '~') is one flat pass over each mate's bytes (k_qual_check); the lowest
 //           offending byte is mapped to its read through the offsets.
-//   format  k_format_units<Fmt>: one block per 4 KB tile of the output (texttile.h).  The units that overlap the tile are found
+//   format  k_format_units<Fmt, ZW>: one block per 4 KB tile of the output (texttile.h).  The units that overlap the tile are found
 //           by binary search of the unit starts (a unit may span many tiles: SEQ is of any length).  One lane per line has Fmt
 //           write it into the LDS image, clipped to the tile: the numeric parts and every run (a name, SEQ, QUAL) of at most
 //           kShortCopy bytes by that lane; longer runs are queued as jobs, clipped to the tile, and made a byte per lane and step,
@@ -107,11 +107,18 @@ __device__ inline void count_lines(uint32_t n, unsigned long long* __restrict__ 
     if ((threadIdx.x & (kWave - 1)) == 0 && v) atomicAdd(&misc[4], v);
 }
 
+// A batch without posteriors runs the instantiations with ZW == false, which drop the two pointers at once: the compiler then removes
+// the field's code, and those kernels are what they were before the field existed (registers and occupancy included).
+template <bool ZW> __device__ __forceinline__ void without_zw(SamwArgs& a) {
+    if (!ZW) { a.tag_zw_rec = nullptr; a.tag_zw_f32 = nullptr; }
+}
+
 // BAM: the units are bamwfmt.h's records (one per line) with its checks behind samwfmt.h's, else the text's lines
-template <bool BAM>
+template <bool BAM, bool ZW>
 __global__ void __launch_bounds__(kBlock)
 k_record_size(SamwArgs a, uint64_t n_hits, const uint32_t* __restrict__ e_before, uint32_t* __restrict__ unit_len,
               uint32_t* __restrict__ unit_read, unsigned long long* __restrict__ misc) {
+    without_zw<ZW>(a);
     const uint64_t h = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t lines = 0;
     if (h < n_hits) {
@@ -241,6 +248,8 @@ struct TextFmt {
             out.run(kCopy, t.md, t.md_len, t.md_len);
             out.skip(samw_put_int_tag('N', 'H', t.nh, put));
         }
+        uint32_t zw;
+        if (samw_zw(a, c.l, &zw)) out.skip(samw_put_zw(zw, put));     // \t ZW:f:<token>
         out.byte('\n');
     }
 };
@@ -291,6 +300,7 @@ struct BamFmt {
             out.byte(0);
             out.skip(bamw_put_int_tag('N', 'H', t.nh, put));
         }
+        for (uint32_t i = 0; i < bamw_zw_len(a, c.l); ++i) out.byte(bamw_zw_byte(a, c.l, i));    // Z W f <float>
     }
 };
 
@@ -298,13 +308,14 @@ struct BamFmt {
 // units that overlap the tile are found by binary search of the unit starts (units are never empty, so the starts increase strictly).
 // Two line slots per unit, a lane each: a unit's second line is absent unless it is a pair record or a record-less paired read.
 // The lane of a line inside the tile has Fmt write it; then the wavefronts take the queued runs in turn, a byte per lane and step.
-template <typename Fmt>
+template <typename Fmt, bool ZW>
 __global__ void __launch_bounds__(kBlock)
 k_format_units(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t* __restrict__ unit_read, const uint64_t* __restrict__ unit_start,
                uint64_t n_units, uint64_t n_bytes, uint64_t first_tile, uint64_t out_base, uint4* __restrict__ out) {
     __shared__ uint4 tile4[kBlock];
     __shared__ Job jobs[kJobCap];
     __shared__ uint32_t n_jobs;
+    without_zw<ZW>(a);
     const textchunks::Tile tile(tile4, first_tile, n_bytes);
     if (threadIdx.x == 0) n_jobs = 0;
     __syncthreads();
@@ -344,6 +355,10 @@ k_format_units(SamwArgs a, const uint32_t* __restrict__ e_before, const uint32_t
     __syncthreads();
     tile.store(out_base, out);
 }
+
+// the instantiation for a batch with (zw) or without posteriors
+template <bool BAM> auto record_size_kernel(bool zw) { return zw ? k_record_size<BAM, true> : k_record_size<BAM, false>; }
+template <typename Fmt> auto format_kernel(bool zw) { return zw ? k_format_units<Fmt, true> : k_format_units<Fmt, false>; }
 
 struct Scratch {
     DevBuf<uint32_t> empty, e_before, unit_len, unit_read;
@@ -388,9 +403,11 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
     if (!((in.aln_pos != nullptr) == (in.aln_op_off != nullptr) && (!in.aln_ops || in.aln_pos))) return fail(SFGPU_ERR_INVALID, "an alignment is positions, offsets and operations together");
     if (!((in.tag_nm != nullptr) == (in.tag_md_off != nullptr) && (in.tag_nm != nullptr) == (in.tag_md != nullptr))) return fail(SFGPU_ERR_INVALID, "tags are nm, MD offsets and MD bytes together");
     if (in.tag_nm && !(in.seq1_off && (!in.paired || in.seq2_off))) return fail(SFGPU_ERR_INVALID, "tags of mates whose bases are not given");
+    if ((in.tag_zw_rec != nullptr) != (in.tag_zw_f32 != nullptr)) return fail(SFGPU_ERR_INVALID, "posteriors are records and floats together");
     SamwArgs a = in;
     if (!a.paired) { a.seq2 = nullptr; a.seq2_off = nullptr; a.qual2 = nullptr; }
     a.oriented = a.oriented != 0;
+    const bool zw = a.tag_zw_rec != nullptr;     // which instantiation of the sizing and format kernels runs
 
     Scratch S;
     CallScope scope;        // after S: it drains the stream before S's blocks go back to the pool
@@ -469,7 +486,7 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
         SF_HIP(hipGetLastError());
     }
     if (n_hits) {
-        hipLaunchKernelGGL(bam ? k_record_size<true> : k_record_size<false>, dim3(grid_of(n_hits)), dim3(kBlock), 0, st, a, n_hits, S.e_before.p, S.unit_len.p, S.unit_read.p,
+        hipLaunchKernelGGL(bam ? record_size_kernel<true>(zw) : record_size_kernel<false>(zw), dim3(grid_of(n_hits)), dim3(kBlock), 0, st, a, n_hits, S.e_before.p, S.unit_len.p, S.unit_read.p,
                            S.misc.p);
         SF_HIP(hipGetLastError());
     }
@@ -503,7 +520,7 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
     out->n_bytes = total; out->n_lines = h_misc[4]; out->max_unit_bytes = h_misc[1];
     if (dest.store)            // sfgpu_bamsort_collect: every tile at once into a segment of the store, which then lists the records
         return dest.store->take(total, out->n_lines, S.unit_start.p, n_units, st, &out->format_ms, [&](uint4* buf, hipStream_t s) -> int {
-            hipLaunchKernelGGL(k_format_units<BamFmt>, dim3((unsigned)(((total - 1) >> kTileShift) + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
+            hipLaunchKernelGGL(format_kernel<BamFmt>(zw), dim3((unsigned)(((total - 1) >> kTileShift) + 1)), dim3(kBlock), 0, s, a, S.e_before.p, S.unit_read.p,
                                S.unit_start.p, n_units, total, (uint64_t)0, (uint64_t)0, buf);
             SF_HIP(hipGetLastError());
             return SFGPU_OK;
@@ -514,7 +531,7 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
     // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this text's tiles
     textchunks::Stats ts;
     auto format_tiles = [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-        hipLaunchKernelGGL(bam ? k_format_units<BamFmt> : k_format_units<TextFmt>, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p,
+        hipLaunchKernelGGL(bam ? format_kernel<BamFmt>(zw) : format_kernel<TextFmt>(zw), dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, a, S.e_before.p,
                            S.unit_read.p, S.unit_start.p, n_units, total, first_tile, out_base, buf);
         SF_HIP(hipGetLastError());
         return SFGPU_OK;
@@ -532,17 +549,28 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
 }  // namespace
 
 // ---- the entries: the widest of a family builds the batch, the others forward to it
+extern "C" int sfgpu_sam_write_text_p(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
+                                      const sfgpu_samw_post* post) {
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post);
+    Dest dest;
+    dest.sink = sink; dest.user = user;
+    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+}
+
 extern "C" int sfgpu_sam_write_text_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                       sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
                                       const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags);
-    Dest dest;
-    dest.sink = sink; dest.user = user;
-    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+    return sfgpu_sam_write_text_p(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_text_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
@@ -573,19 +601,30 @@ extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_h
                                   d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
+extern "C" int sfgpu_sam_write_bgzf_p(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
+                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
+                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
+                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
+                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
+                                      const sfgpu_samw_post* post) {
+    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
+    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
+    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
+                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post);
+    Dest dest;
+    dest.z = z; dest.format = format;
+    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
+}
+
 extern "C" int sfgpu_sam_write_bgzf_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
                                       const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                       sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
                                       const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
-    SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
-    SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags);
-    Dest dest;
-    dest.z = z; dest.format = format;
-    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
+    return sfgpu_sam_write_bgzf_p(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
+                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
 }
 
 extern "C" int sfgpu_sam_write_bgzf_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,

@@ -38,11 +38,17 @@
 //          slots per record as above; csrc/mdfmt.h) a mapped line ends ... QUAL \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh> \n, nh being the
 //          read's record count hit_off[r + 1] - hit_off[r].  The lines of a read without records carry no tags.  Without them every
 //          byte is what it is above.
+//   Posteriors: with tag_zw_rec / tag_zw_f32 given (sfgpu_hits_posteriors' d_rec and d_f32 for the same records: one entry per
+//          record, slot >> 1) a mapped line ends, behind the tags above where they are given, \t ZW:f:<token>, the token being the
+//          "%g" of the record's posterior probability, placed from its six-digit record (gfmt_len / gfmt_put: no arithmetic on
+//          the value happens here).  Both lines of a pair carry the record's value; the lines of a read without records carry
+//          nothing.  tag_zw_f32 is what bamwfmt.h stores.  Without them every byte is what it is above.
 #pragma once
 #include <cstdint>
 
 #include "../../include/sfgpu.h"
 #include "decfmt.h"
+#include "gfmt.h"
 
 #if defined(__HIPCC__)
 #define SAMW_HD __host__ __device__ __forceinline__
@@ -238,6 +244,8 @@ struct SamwArgs {
     const uint32_t* tag_nm = nullptr;        // [2 * records] sfgpu_hits_md_tags' d_nm, or nullptr: no tags are written
     const uint64_t* tag_md_off = nullptr;    // [2 * records + 1]
     const uint8_t* tag_md = nullptr;
+    const uint32_t* tag_zw_rec = nullptr;    // [records] sfgpu_hits_posteriors' d_rec, or nullptr: no ZW is written
+    const float* tag_zw_f32 = nullptr;       // [records] its d_f32: the value of a BAM record's ZW
 };
 
 // The lines of a record WITH the batch's alignment, where one is given.  `hidx` is the record's index in a.hits: its slots are
@@ -322,12 +330,30 @@ SAMW_HD uint32_t samw_put_int_tag(char t0, char t1, uint32_t v, Put put) {
 }
 template <typename Put>
 SAMW_HD void samw_put_md_lead(Put put) { put(0, '\t'); put(1, 'M'); put(2, 'D'); put(3, ':'); put(4, 'Z'); put(5, ':'); }
+// the posterior of the line: whether it carries one, and the record of its token
+SAMW_HD bool samw_zw(const SamwArgs& a, const SamwLine& l, uint32_t* rec) {
+    if (!a.tag_zw_rec || !l.mapped) return false;
+    *rec = a.tag_zw_rec[l.slot >> 1];
+    return true;
+}
+// \t ZW:f:<token>, behind the other tags
+SAMW_HD uint64_t samw_zw_len(const SamwArgs& a, const SamwLine& l) {
+    uint32_t rec;
+    return samw_zw(a, l, &rec) ? (uint64_t)kSamwTagLead + (uint64_t)gfmt_len(rec) : 0ull;
+}
+template <typename Put>
+SAMW_HD uint32_t samw_put_zw(uint32_t rec, Put put) {
+    put(0, '\t'); put(1, 'Z'); put(2, 'W'); put(3, ':'); put(4, 'f'); put(5, ':');
+    const int n = gfmt_len(rec);
+    gfmt_put(rec, [&](int i, char ch) { put((int)kSamwTagLead + n - 1 - i, ch); });
+    return kSamwTagLead + (uint32_t)n;
+}
 SAMW_HD uint64_t samw_line_len(const SamwArgs& a, const SamwLine& l, uint64_t r, uint32_t tid) {
     const uint8_t* p;
     uint64_t sl, ql;
     (void)samw_seq(a, l, r, &p, &sl);
     (void)samw_qual(a, l, r, &p, &ql);
-    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail + samw_tags_len(a, l, r);
+    return samw_qname_len(a, r) + samw_head_len(l) + samw_rname_len(a, l, tid) + samw_mid_len(l) + sl + ql + kSamwTail + samw_tags_len(a, l, r) + samw_zw_len(a, l);
 }
 // the bytes of unit (read r, record h of rank `rank` and index hidx in a.hits; h == nullptr: the read has no record)
 SAMW_HD uint64_t samw_unit_len(const SamwArgs& a, uint64_t r, const sfgpu_hit* h, uint64_t rank, uint64_t hidx) {
@@ -411,6 +437,8 @@ inline int samw_serial(const SamwArgs& a, char* out, SamwSerial* res) {
                 for (uint64_t i = 0; i < t.md_len; ++i) *p++ = (char)t.md[i];
                 p += samw_put_int_tag('N', 'H', t.nh, [&](int i, char ch) { p[i] = ch; });
             }
+            uint32_t zw;
+            if (samw_zw(a, l, &zw)) p += samw_put_zw(zw, [&](int i, char ch) { p[i] = ch; });
             *p++ = '\n';
         }
         at += len;

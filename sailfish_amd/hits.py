@@ -764,6 +764,104 @@ def md_tags(index, hits, offsets, reads1, reads2=None, alignments=None):
     return nm, md_off, md[:n_md], st.as_dict()
 
 
+POSTERIOR_STATS = ("reads", "reads_mapped", "reads_multi", "records", "reads_flat", "records_zero", "max_records")
+POST_TINY, POST_HUGE, POST_FLUSH = 2.0 ** -960, 2.0 ** 960, 2.0 ** -56
+_POST_XOR = [np.arange(64) ^ k for k in (32, 16, 8, 4, 2, 1)]
+
+
+def post_sum_host(x):
+    """csrc/postfmt.h's SUM of float64 values: 64 accumulators a_j = x_j + x_{j+64} + ..., serially and ascending (0 where there
+    is no x_j), then a_j <- a_j + a_{j xor k} for k = 32, 16, 8, 4, 2, 1 and every j at once; a_0"""
+    a = np.zeros(64, np.float64)
+    for i in range(0, len(x), 64):
+        seg = x[i:i + 64]
+        a[:len(seg)] = a[:len(seg)] + seg
+    for perm in _POST_XOR:
+        a = a + a[perm]
+    return float(a[0])
+
+
+def posterior_record(p):
+    """csrc/gfmt.h's six-digit record of a value 0 or 2^-56 .. 1, read off Python's own '%.5e': the digits without their trailing
+    zeros in bits 0 .. 19, the decimal exponent + 512 in bits 20 .. 29; bit 31 alone for 0"""
+    if p == 0:
+        return 1 << 31
+    mant, exp = ("%.5e" % p).split("e")
+    return int(mant.replace(".", "").rstrip("0")) | (int(exp) + 512) << 20
+
+
+def posterior_token(rec):
+    """the '%g' token of such a record, placed from its digits alone (what the writers' formatter does with it)"""
+    rec = int(rec) & 0xFFFFFFFF
+    if rec >> 31:
+        return "0"
+    d, x = str(rec & 0xFFFFF), ((rec >> 20) & 0x3FF) - 512
+    if -4 <= x < 6:
+        if x < 0:
+            return "0." + "0" * (-x - 1) + d
+        return d + "0" * (x + 1 - len(d)) if len(d) <= x + 1 else d[:x + 1] + "." + d[x + 1:]
+    return d[0] + ("." + d[1:] if len(d) > 1 else "") + "e%+03d" % x
+
+
+def posteriors_host(hits, offsets, weights):
+    """The statement of the posterior pass (csrc/postfmt.h restated; what sfgpu_hits_posteriors is judged by).  hits: HIT_DTYPE
+    records in CSR form over the reads (offsets[R + 1]); weights: float64 per transcript.  For a read's n records x_h =
+    weights[tid_h], a weight below 2^-960 reading as 0 and every record a term of its own; S = post_sum_host(x); p_h = x_h / S where
+    S > 0, else 1 / n; a p_h below 2^-56 is written as 0.  The token is '%g' % p_h, rec its six-digit record (posterior_record) and
+    f32 the float32 nearest to float(token): what a BAM reader gets from the token.
+    -> (p float64[n], rec uint32[n], f32 float32[n], stats dict of POSTERIOR_STATS).  ValueError naming the lowest transcript whose
+    weight is negative, NaN, infinite or above 2^960, else the lowest record whose tid is not a transcript."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    n_rec = int(off[-1]) if len(off) else 0
+    with np.errstate(invalid="ignore"):
+        bad = np.nonzero(~(w >= 0) | (w > POST_HUGE))[0]
+    if len(bad):
+        raise ValueError(f"the weight of transcript {int(bad[0])} is negative, not finite or above 2^960")
+    bad = np.nonzero(hits["tid"][:n_rec] >= len(w))[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {len(w)}")
+    x_all = np.where(w < POST_TINY, 0.0, w)[hits["tid"][:n_rec].astype(np.int64)] if n_rec else np.zeros(0)
+    p = np.zeros(n_rec, np.float64)
+    sizes = np.diff(off) if len(off) else np.zeros(0, np.int64)
+    stats = dict(reads=len(sizes), reads_mapped=int((sizes >= 1).sum()), reads_multi=int((sizes >= 2).sum()), records=n_rec, reads_flat=0,
+                 records_zero=0, max_records=int(sizes.max()) if len(sizes) else 0)
+    for r in np.nonzero(sizes)[0]:
+        x = x_all[off[r]:off[r + 1]]
+        s = post_sum_host(x)
+        stats["reads_flat"] += int(not s > 0)
+        p[off[r]:off[r + 1]] = x / s if s > 0 else 1.0 / len(x)
+    p[p < POST_FLUSH] = 0.0
+    stats["records_zero"] = int((p == 0).sum())
+    rec = np.array([posterior_record(v) for v in p.tolist()], np.uint32)
+    f32 = np.array([float("%g" % v) for v in p.tolist()], np.float64).astype(np.float32)
+    return p, rec, f32, stats
+
+
+def posteriors(hits, offsets, weights, device="cuda"):
+    """The posterior probability of every hit record under a weight per transcript, on the device (sfgpu_hits_posteriors; the rule is
+    posteriors_host's).  hits / offsets: device tensors as QuasiIndex.map_reads returns them (or host arrays); weights: a float64
+    tensor or array, one per transcript, on the device of `hits` where that is a tensor.
+    -> (p float64[n], rec int32[n] (the bits of uint32: the six-digit record of '%g' % p), f32 float32[n], stats dict
+    (POSTERIOR_STATS)): device tensors, one entry per record."""
+    dev = hits.device if isinstance(hits, torch.Tensor) and hits.is_cuda else torch.device(device)
+    d_hits, d_off = _device_hits(hits, offsets, dev)
+    w = (weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(weights, np.float64).copy())).to(dev, torch.float64).contiguous()
+    R, n = int(d_off.numel()) - 1, d_hits.numel() // 24
+    if R < 0:
+        raise ValueError("hit offsets hold at least one entry")
+    p = torch.zeros(n, dtype=torch.float64, device=dev)
+    rec = torch.zeros(n, dtype=torch.int32, device=dev)
+    f32 = torch.zeros(n, dtype=torch.float32, device=dev)
+    st = _lib.PosteriorStats()
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.lib().sfgpu_hits_posteriors(_lib.ptr(d_hits), _lib.ptr(d_off), R, _lib.ptr(w), int(w.numel()), _lib.ptr(p), _lib.ptr(rec), _lib.ptr(f32),
+                                                    C.byref(st), _lib.current_stream_ptr()))
+    return p, rec, f32, st.as_dict()
+
+
 def gc_prefix(seq, seq_off, ref_len):
     """Transcript::GCCount_ of every transcript (include/Transcript.hpp:183-196), laid out like `seq`: int32 device
     tensor of seq.numel() entries (4 bytes per base) -- what sample_bias reads for the fragment-GC samples."""

@@ -238,8 +238,9 @@ class _MappingsRun:
     batches, and their report.  Constructed before anything is indexed: it raises the options' ValueErrors."""
 
     def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                 mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None):
-        from .hits import ALIGNG_STATS, MDTAG_STATS
+                 mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None,
+                 mappings_posteriors=False):
+        from .hits import ALIGNG_STATS, MDTAG_STATS, POSTERIOR_STATS
         if mappings_sorted and mappings_format != "bam":
             raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
         self.rescue, rstats = _rescue(rescue_mates, rescue_window, min_identity, paired, lib_format, sopt)
@@ -253,7 +254,14 @@ class _MappingsRun:
             if write_mappings is None or not mappings_oriented:
                 raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
             tstats = dict.fromkeys(MDTAG_STATS, 0)
+        if mappings_posteriors and write_mappings is None:
+            raise ValueError("mappings_posteriors=True needs write_mappings")
+        # With posteriors the reads pass twice: the first pass decides the records and quantifies them without a mappings
+        # file, the second maps them again and writes the file with the estimates' weights.  `second`: which pass batch() serves;
+        # `again`: the second pass's rescue / verify counters, which must reproduce the first's.
+        self.posteriors, self.second, self.weights, self.again = bool(mappings_posteriors), False, None, None
         self.stats = dict(rescue=rstats, verify=vstats, align=astats, tag=tstats)  # None: the pass does not run
+        self.post_stats = dict.fromkeys(POSTERIOR_STATS, 0) if self.posteriors else None
         self.targets, self.compress = _UnmappedWriters.targets(write_unmapped, unmapped_compress, paired), unmapped_compress
         self.paired, self.sink = paired, write_mappings
         self.sam_kw = dict(format=mappings_format, oriented=mappings_oriented, sort="coordinate" if mappings_sorted else None)
@@ -262,30 +270,75 @@ class _MappingsRun:
 
     def open(self, names, idx):
         """the SamDeviceWriter behind write_mappings= and the ReadDeviceWriters behind write_unmapped="""
-        if self.mapped:
-            from .samfile import SamDeviceWriter
-            self.sam = SamDeviceWriter(self.sink, names, idx.ref_len.cpu().numpy().view(np.uint32), self.paired, **self.sam_kw)
+        if self.mapped and not self.posteriors:              # (with posteriors the file is opened by second_pass)
+            self._open_sam(names, idx)
         if self.unmapped:
             self.unm = _UnmappedWriters(self.targets, self.compress)
+
+    def _open_sam(self, names, idx):
+        from .samfile import SamDeviceWriter
+        self.sam = SamDeviceWriter(self.sink, names, idx.ref_len.cpu().numpy().view(np.uint32), self.paired, **self.sam_kw)
 
     def batch(self, idx, r1, r2, *, quals=(None, None), sam_quals=True, read_names=None, mate_names=(None, None)):
         """One batch: mapped (validated, aligned, tagged, as the options say), its counters added, and written to the run's files.
         r1 / r2: what map_reads takes (packed pairs on the device where the run writes a file); quals / mate_names: one entry per mate
         file; sam_quals: whether the mappings file takes the qualities too; read_names: its QNAMEs.  -> (hits, offsets)"""
         opt = {} if self.rescue is None else dict(rescue=self.rescue)              # (without the option the call is the one it was)
-        h, o = idx.map_reads(r1, r2, validate=self.validate, tags=self.stats["tag"] is not None, **opt)
+        first = self.posteriors and not self.second            # only what decides the records runs: map -> rescue -> validate
+        validate = self.validate
+        if first and validate is not None:
+            validate = {key: v for key, v in validate.items() if key != "align"}
+        h, o = idx.map_reads(r1, r2, validate=validate, tags=self.stats["tag"] is not None and not first, **opt)
         for name, attr, maxima in _PASSES:
             total = self.stats[name]
-            if total is not None:
-                for key, v in getattr(idx, attr).items():
-                    total[key] = max(total[key], v) if key in maxima else total[key] + v
+            if total is None or (first and name in ("align", "tag")):
+                continue
+            if self.second and name in ("rescue", "verify"):
+                total = self.again[name]
+            for key, v in getattr(idx, attr).items():
+                total[key] = max(total[key], v) if key in maxima else total[key] + v
+        post = {}
+        if self.second:
+            from .hits import posteriors
+            *values, st = posteriors(h, o, self.weights)
+            post = dict(posteriors=tuple(values))
+            for key, v in st.items():
+                self.post_stats[key] = max(self.post_stats[key], v) if key == "max_records" else self.post_stats[key] + v
         if self.sam is not None:
             q1, q2 = quals if sam_quals else (None, None)
             self.sam.write(h, o, read_names=read_names, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                           alignments=idx.last_alignments if self.stats["align"] is not None else None, tags=idx.last_tags if self.stats["tag"] is not None else None)
-        if self.unm is not None:
+                           alignments=idx.last_alignments if self.stats["align"] is not None else None, tags=idx.last_tags if self.stats["tag"] is not None else None,
+                           **post)
+        if self.unm is not None and not self.second:
             self.unm.write(o, (r1,) if r2 is None else (r1, r2), quals, mate_names)
         return h, o
+
+    def second_pass(self, rc, exp, sopt, names, idx, batches):
+        """mappings_posteriors=True, behind quant.quantify: where that returned 0, the weights NumReads / EffectiveLength of the final
+        estimates (full doubles on the device; 0 where EffectiveLength <= 0 or the quotient is not finite; left on the experiment as
+        `posterior_weights`), the mappings file opened, and batches() -- the reads, produced again -- run through batch() once more.
+        RuntimeError where the second pass's rescue or verify counters are not the first's: the file would not show the records that
+        were quantified."""
+        if not self.posteriors:
+            return
+        log = (getattr(sopt, "jointLog", None) if sopt is not None else None) or (lambda lvl, msg: None)
+        if rc != 0 or exp is None:
+            self.post_stats = None
+            log(1, "mappings_posteriors: the quantification did not succeed (rc {}), so no mappings file is written".format(rc))
+            return
+        from . import writer
+        _, _, length, _, est = writer.abundance_columns(exp, sopt)
+        w = est.to(torch.float64) / length.to(torch.float64)
+        self.weights = exp.posterior_weights = torch.where((length > 0) & torch.isfinite(w), w, torch.zeros_like(w)).contiguous()
+        self.second = True
+        self.again = {name: dict.fromkeys(self.stats[name], 0) for name in ("rescue", "verify") if self.stats[name] is not None}
+        self._open_sam(names, idx)
+        for _ in batches():
+            pass
+        for name, again in self.again.items():
+            if again != self.stats[name]:
+                raise RuntimeError(f"mappings_posteriors: the second pass over the reads gave other {name} counters ({again}) than the first "
+                                   f"({self.stats[name]}): the mappings file does not show the records that were quantified")
 
     def close(self):
         for w in (self.sam, self.unm):
@@ -297,8 +350,10 @@ class _MappingsRun:
         `unmapped_stats` only with write_unmapped) and one line each to sopt.jointLog"""
         res, v, a, t = (self.stats[name] for name, _, _ in _PASSES)
         u = None if self.unm is None else self.unm.stats()
+        ps = self.post_stats if self.second else None
         if exp is not None:
             exp.rescue_stats, exp.verify_stats, exp.align_stats, exp.tag_stats = res, v, a, t
+            exp.posterior_stats = ps
             if u is not None:
                 exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
@@ -326,6 +381,10 @@ class _MappingsRun:
         if t is not None:
             log(0, "tagged mappings: NM, MD and NH on {} lines, {} of them <len>M without a mismatch; NM sums to {}; {} MD bytes, the longest MD {}".format(
                 t["slots"], t["slots_plain"], t["sum_nm"], t["md_bytes"], t["max_md_bytes"]))
+        if ps is not None:
+            log(0, "posteriors in the mappings file: ZW on the {} records of {} mapped reads, {} of them with more than one record (the largest has {}); "
+                   "{} reads have no weight at all and are spread evenly; {} records are written as 0".format(
+                       ps["records"], ps["reads_mapped"], ps["reads_multi"], ps["max_records"], ps["reads_flat"], ps["records_zero"]))
         if u is not None:
             log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
                 u["unmapped"], u["reads"], " + ".join(str(b) for b in u["bytes"]), "FASTQ" if self.unm.writers[0].format == 2 else "FASTA"))
@@ -334,7 +393,7 @@ class _MappingsRun:
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -378,10 +437,26 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     are pairs like any the mapper made: validation, alignment, tags, the mappings and unmapped files and the estimates see them so.
     The search stays ungapped with max_indel > 0; the validation then scores the rescued pair with gaps like every record.  The
     counters are left on the experiment as `rescue_stats` (None without the option) and go to sopt.jointLog as one line.
+    mappings_posteriors=True (it needs write_mappings, else ValueError before anything is indexed) ends every mapped line of the
+    mappings file with ZW:f:<p>, RSEM's tag: the posterior probability, under the run's final estimates, that the read came from that
+    record -- the record's weight NumReads / EffectiveLength over the sum of the weights of the read's records ("%g"; hits.posteriors;
+    both lines of a pair carry their record's value).  The estimates exist only after the EM, so the reads pass twice: the first pass
+    maps, rescues and validates the batches and quantifies them as ever, but opens no mappings file; the second, run iff the
+    quantification returned 0 (else no mappings file is created, and the log says so), slices the reads again, maps them again and
+    writes the file, with every mappings_format, mappings_oriented, mappings_sorted, mappings_gapped, mappings_tags, validate_mappings
+    and rescue_mates setting.  quant.sf, aux/ and the unmapped files are byte for byte those of the run without the option, and so
+    is the mappings file but for the tag.  ZW is a posterior over the records the file shows: what the hit filter drops later
+    (library compatibility, orphans, maxReadOccs) does not enter -- the same sentence write_unmapped carries.  The rescue and verify
+    counters reported are the first pass's, and the second must reproduce them (RuntimeError otherwise); the align and tag counters
+    are the second's; the pass's own are left on the experiment as `posterior_stats` (None without the option), its weights as
+    `posterior_weights`, and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors)
+    if run.posteriors and sopt is None:                      # (the second pass reads the columns under the options the run had)
+        from .experiment import SailfishOpts
+        sopt = SailfishOpts()
     idx = QuasiIndex(sequences, k=k, device=device)
     n = len(reads1)
 
@@ -403,6 +478,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     try:
         run.open(names, idx)
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+        run.second_pass(rc, exp, sopt, names, idx, batches)
     finally:
         run.close()
         idx.close()
@@ -422,7 +498,7 @@ def _dollar_separated(bases, off):
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -433,7 +509,8 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     (a single-end run, reads2_path = None, has no mates: the keyword then does nothing).  mappings_oriented=True writes the file other tools expect: the read files are
     opened with quals=True, so QUAL is the FASTQ's quality line ('*' for FASTA reads), and the lines with 0x10 carry SEQ
     reverse-complemented and QUAL reversed.  mappings_sorted, validate_mappings, min_identity, keep_best, max_indel, mappings_gapped and
-    mappings_tags as in quantify_reads; so are rescue_mates and rescue_window.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
+    mappings_tags as in quantify_reads; so are rescue_mates and rescue_window, and mappings_posteriors: the second pass then opens the read files again, with the
+    same ReadFile options.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
     as they came in -- each mate file's own names up to the first space or tab (names="device" on both files), bases and quality lines
     (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
     FASTA unmapped file.  No name, base or offset visits the host.
@@ -441,7 +518,10 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors)
+    if run.posteriors and sopt is None:                      # (the second pass reads the columns under the options the run had)
+        from .experiment import SailfishOpts
+        sopt = SailfishOpts()
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
     idx = QuasiIndex((bases, off), k=k, device=device)
     keep = run.mapped and bool(mappings_oriented)            # the mappings file carries QUAL
@@ -481,6 +561,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     try:
         run.open(names, idx)
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+        run.second_pass(rc, exp, sopt, names, idx, batches)
     finally:
         run.close()
         idx.close()

@@ -632,14 +632,26 @@ def _tag_arrays(tags, n_records):
     return nm, md_off, md.tobytes()
 
 
-def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False, alignments=None, tags=None):
+def _posterior_values(posteriors, n_records):
+    """the records' posterior probabilities as a float64 array, from what hits.posteriors / hits.posteriors_host return (p first), device
+    tensors or arrays"""
+    p = posteriors[0]
+    p = (p.cpu().numpy() if hasattr(p, "cpu") else np.asarray(p)).astype(np.float64).reshape(-1)
+    if len(p) != n_records:
+        raise ValueError(f"posteriors of {len(p)} records for {n_records} records")
+    return p
+
+
+def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, oriented=False, alignments=None, tags=None, posteriors=None):
     """the text write_sam writes.  quals: per read the quality bytes (single end) or a (mate 1, mate 2) pair, a mate's None for
     "not given" (QUAL '*'); they go with the mate's SEQ on every line.  oriented: a line with 0x10 carries SEQ reverse-complemented
     and QUAL reversed.  alignments: what hits.align_hits / align_hits_host returned for the same records -- a mapped line then takes
     POS and CIGAR from its slot (2 * record + line) and PNEXT from the other line's slot, and a slot without an operation is the
     "no base on the transcript" error.  tags: what hits.md_tags / md_tags_host returned for the same records and the same alignments --
     a mapped line then ends NM:i:<nm>, MD:Z:<md>, NH:i:<the read's records>; they describe the read on the transcript's strand, so the
-    text must be oriented and the bases given.  The rules are stated in csrc/samwfmt.h."""
+    text must be oriented and the bases given.  posteriors: what hits.posteriors / posteriors_host returned for the same records (the
+    values p first: (p,) will do) -- a mapped line then ends, behind the tags, ZW:f:<"%g" % p of its record>, both lines of a pair
+    alike; the lines of a read without records carry nothing.  The rules are stated in csrc/samwfmt.h."""
     if quals is not None and seqs is None:
         raise ValueError("qualities of reads whose bases are not given")
     if tags is not None and (seqs is None or not oriented):
@@ -653,13 +665,16 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
     fmt = b"%s\t%d\t%s\t%d\t255\t%s\t%s\t%d\t%d\t%s\t%s\n"
     aln = _alignment_arrays(alignments, int(off[-1]) if len(off) else 0) if alignments is not None else None
     tg = _tag_arrays(tags, int(off[-1]) if len(off) else 0) if tags is not None else None
+    zw = _posterior_values(posteriors, int(off[-1]) if len(off) else 0) if posteriors is not None else None
 
     def tagged(text, h, which, nh):
-        """a mapped line with its slot's tags"""
-        if tg is None:
-            return text
-        slot = 2 * h + which
-        return text[:-1] + b"\tNM:i:%d\tMD:Z:%s\tNH:i:%d\n" % (int(tg[0][slot]), tg[2][int(tg[1][slot]):int(tg[1][slot + 1])], nh)
+        """a mapped line with its slot's tags and its record's posterior"""
+        if tg is not None:
+            slot = 2 * h + which
+            text = text[:-1] + b"\tNM:i:%d\tMD:Z:%s\tNH:i:%d\n" % (int(tg[0][slot]), tg[2][int(tg[1][slot]):int(tg[1][slot + 1])], nh)
+        if zw is not None:
+            text = text[:-1] + b"\tZW:f:%s\n" % (b"%g" % float(zw[h]))
+        return text
 
     def placed(h, which, pos, length, what):
         """(POS, CIGAR) of line `which` of record h"""
@@ -723,7 +738,8 @@ def _sam_text(names, ref_len, hits, offsets, read_names, seqs, *, quals=None, or
     return b"".join(out)
 
 
-def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False, alignments=None, tags=None):
+def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, bgzf=False, quals=None, oriented=False, alignments=None, tags=None,
+              posteriors=None):
     """Hit records as SAM text at `path` (host side): @HD and @SQ lines, then per read mate 1 and mate 2 of every pair record, one
     line per orphan or single-end record (0x100 from the read's second record on), and 77 / 141 lines (single end: one 4 line) for
     a read with no record.  CIGAR is <len>M (<clip>S<rest>M where the read begins in front of the transcript), SEQ is '*' unless
@@ -735,8 +751,9 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     blocked gzip (gzfile.write_bgzf).  What SAM does not carry is lost: mate_len of an orphan.  `alignments`: the gapped alignment
     of the same records (hits.align_hits / align_hits_host): POS, CIGAR and PNEXT are then the alignment's.  `tags`: the NM / MD tags
     of the same records and alignments (hits.md_tags / md_tags_host): a mapped line then ends NM:i:, MD:Z: and NH:i: (the read's record
-    count); they need `seqs` and `oriented`."""
-    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags)
+    count); they need `seqs` and `oriented`.  `posteriors`: the records' posterior probabilities (hits.posteriors / posteriors_host): a
+    mapped line then ends ZW:f:<"%g" of its record's value>."""
+    data = _sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags, posteriors=posteriors)
     if bgzf:
         from . import gzfile
         gzfile.write_bgzf(path, data)
@@ -746,7 +763,7 @@ def write_sam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
 
 
 def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None, member_bytes=65280, quals=None, oriented=False, sort=None,
-              alignments=None, tags=None):
+              alignments=None, tags=None, posteriors=None):
     """Hit records as a BAM file at `path` (host side): sam_to_bam of the text write_sam writes for the same arguments, in BGZF
     members of member_bytes bytes with the EOF member behind them (gzfile.write_bgzf).  sort="coordinate": the same records in
     coordinate order under an @HD SO:coordinate header (sort_bam_stream; csrc/baifmt.h), the header in members of its own, so that
@@ -754,7 +771,8 @@ def write_bam(path, names, ref_len, hits, offsets, *, read_names=None, seqs=None
     from . import gzfile
     if sort not in SORT_ORDERS:
         raise ValueError(f"sort must be one of {SORT_ORDERS}, not {sort!r}")
-    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags))
+    data = sam_to_bam(_sam_text(names, ref_len, hits, offsets, read_names, seqs, quals=quals, oriented=oriented, alignments=alignments, tags=tags,
+                                posteriors=posteriors))
     if sort is None:
         gzfile.write_bgzf(path, data, member_bytes=member_bytes)
         return
@@ -1084,7 +1102,10 @@ class SamDeviceWriter:
     write(tags=): the batch's NM / MD tags as hits.md_tags returns them (nm, md_off, md: device tensors, two slots per record, computed
     over the same `alignments`); a mapped line then ends NM:i:<nm>, MD:Z:<md>, NH:i:<the read's record count> (a BAM record: NM and NH
     in the smallest integer type that holds them, MD as a Z string), in every format, sorted or not.  The writer must be oriented and
-    the bases given, else ValueError.  Without `tags` the calls and the bytes are what they were."""
+    the bases given, else ValueError.  Without `tags` the calls and the bytes are what they were.
+    write(posteriors=): what hits.posteriors returned for the batch's records (p, rec, f32, ...: device tensors, one entry per record);
+    a mapped line then ends, behind the tags where there are any, ZW:f:<"%g" of its record's posterior probability> (a BAM record:
+    ZW as a float), in every format, sorted or not.  Without `posteriors` the calls and the bytes are what they were."""
 
     def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False, sort=None, index=None):
         from . import _lib, quantfile
@@ -1229,7 +1250,26 @@ class SamDeviceWriter:
             t_nm = torch.zeros(1, dtype=torch.int32, device=dev)
         return _lib.SamwTags(_lib.ptr(t_nm), _lib.ptr(t_off), _lib.ptr(t_md)), (t_nm, t_off, t_md)
 
-    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None, tags=None):
+    @staticmethod
+    def _post_args(posteriors, hits):
+        """write()'s posteriors as the _p entries take them: (the sfgpu_samw_post struct, the tensors whose addresses it holds)"""
+        import torch
+
+        from . import _lib
+        dev = hits.device
+        if len(posteriors) < 3:
+            raise TypeError("posteriors: expected what hits.posteriors returns (p, rec, f32, ...)")
+        z_rec, z_f32 = (posteriors[i].to(dev).contiguous() for i in (1, 2))
+        if z_rec.element_size() != 4 or z_rec.is_floating_point() or z_f32.dtype != torch.float32:
+            raise TypeError("posteriors: expected what hits.posteriors returns (32-bit records, float32 values)")
+        n_rec = hits.numel() // 24
+        if z_rec.numel() != n_rec or z_f32.numel() != n_rec:
+            raise ValueError(f"posteriors of {z_rec.numel()} records for {n_rec} records")
+        if not n_rec:                                                                  # no record at all: still "given"
+            z_rec, z_f32 = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+        return _lib.SamwPost(_lib.ptr(z_rec), _lib.ptr(z_f32)), (z_rec, z_f32)
+
+    def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None, tags=None, posteriors=None):
         import torch
 
         from . import _lib
@@ -1243,6 +1283,11 @@ class SamDeviceWriter:
             t_struct, t_keep = self._tag_args(tags, hits, seqs)
             keepalive = (keepalive, t_struct, t_keep)
             text_entry, collect_entry, bgzf_entry, last = self._L.sfgpu_sam_write_text_t, self._L.sfgpu_bamsort_collect_t, self._L.sfgpu_sam_write_bgzf_t, (C.byref(t_struct),)
+        if posteriors is not None:                 # the _p entries: the tags' place holds them or NULL
+            z_struct, z_keep = self._post_args(posteriors, hits)
+            keepalive = (keepalive, z_struct, z_keep)
+            text_entry, collect_entry, bgzf_entry = self._L.sfgpu_sam_write_text_p, self._L.sfgpu_bamsort_collect_p, self._L.sfgpu_sam_write_bgzf_p
+            last = (last[0] if last else None, C.byref(z_struct))
         raised = []
 
         def sink(addr, nb, _user):

@@ -1636,6 +1636,44 @@ typedef struct sfgpu_posterior_stats {
 SFGPU_API int sfgpu_hits_posteriors(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, const double* d_weights, uint64_t n_refs,
                                     double* d_p, uint32_t* d_rec, float* d_f32, sfgpu_posterior_stats* stats, sfgpu_stream stream);
 
+/* What library format a batch's records show: the tally behind lib_format "A" and aux/lib_format_counts.json (the rule is stated
+ * once in csrc/libdetfmt.h; hits.library_kinds_host is the Python statement).  No index and no read bases are needed.
+ *   kind    of a record, SFGPU_LIBDET_KINDS of them: 0 .. 5 ISF ISR OSF OSR MSF MSR (mate_status 3, the reference's hitType on the
+ *           s1, s2 that sfgpu_filter_hits computes; the dovetail stretch iff can_dovetail), 6 .. 9 LF LR RF RR (orphans: status 1 / 2,
+ *           forward / reverse), 10 11 SF SR (status 0), 12 any other status byte.
+ *   read    no record: counted in `reads` only.  More than max_read_occs records: reads_over_occs and nothing else (the filter drops
+ *           it too).  Else reads_mapped; every record in records_kind; the read in reads_kind[k] where all its records are of kind k,
+ *           else in reads_mixed; with has_expected, in reads_compatible iff one of its kinds is one that sfgpu_filter_hits accepts
+ *           for `expected`.
+ *   votes   a mapped read votes iff all its records are of one kind and that is 0 .. 5 (paired_library) or 10 / 11 (single end).
+ *           The first *remaining_votes voters in read order are counted in votes_kind / votes and taken off *remaining_votes, which
+ *           carries the budget across calls as remaining_fl_ops does: the tally does not depend on how the reads were cut into
+ *           batches.  With *remaining_votes == 0 no vote is looked for.
+ *   errors  NULL d_hit_offsets (with n_reads > 0), opts, remaining_votes or stats, NULL d_hits with records: SFGPU_ERR_INVALID;
+ *           n_reads >= 2^31: SFGPU_ERR_RANGE.  Nothing is added then.  n_reads == 0 is a valid call.
+ * Synchronous.  The stats are ACCUMULATED by the call.  There is no host path. */
+#define SFGPU_LIBDET_KINDS 13
+typedef struct sfgpu_libdet_opts {
+    uint32_t max_read_occs;           /* sfOpts.maxReadOccs, as sfgpu_filter_opts */
+    int32_t  paired_library;          /* which kinds vote */
+    int32_t  can_dovetail;            /* sfOpts.allowDovetail */
+    int32_t  has_expected;            /* 1: count reads_compatible against `expected` */
+    sfgpu_libfmt expected;
+} sfgpu_libdet_opts;
+typedef struct sfgpu_libdet_stats {
+    uint64_t reads;
+    uint64_t reads_mapped;            /* 1 .. max_read_occs records */
+    uint64_t reads_over_occs;
+    uint64_t reads_mixed;             /* mapped, records of more than one kind */
+    uint64_t reads_compatible;
+    uint64_t votes;                   /* the sum of votes_kind */
+    uint64_t records_kind[SFGPU_LIBDET_KINDS];
+    uint64_t reads_kind[SFGPU_LIBDET_KINDS];
+    uint64_t votes_kind[SFGPU_LIBDET_KINDS];
+} sfgpu_libdet_stats;
+SFGPU_API int sfgpu_hits_library_kinds(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, const sfgpu_libdet_opts* opts,
+                                       int64_t* remaining_votes, sfgpu_libdet_stats* stats, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

@@ -305,6 +305,23 @@ class PosteriorStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class LibdetOpts(C.Structure):
+    _fields_ = [("max_read_occs", C.c_uint32), ("paired_library", C.c_int32), ("can_dovetail", C.c_int32), ("has_expected", C.c_int32),
+                ("expected", LibFmt)]
+
+
+LIBDET_KINDS = 13
+
+
+class LibdetStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("reads_mapped", C.c_uint64), ("reads_over_occs", C.c_uint64), ("reads_mixed", C.c_uint64),
+                ("reads_compatible", C.c_uint64), ("votes", C.c_uint64), ("records_kind", C.c_uint64 * LIBDET_KINDS),
+                ("reads_kind", C.c_uint64 * LIBDET_KINDS), ("votes_kind", C.c_uint64 * LIBDET_KINDS)]
+
+    def as_dict(self):
+        return {k: [int(v) for v in getattr(self, k)] if k.endswith("_kind") else int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class SamwTags(C.Structure):
     _fields_ = [("d_nm", C.c_void_p), ("d_md_off", C.c_void_p), ("d_md", C.c_void_p)]
 
@@ -431,6 +448,7 @@ _SIGS = {
     "sfgpu_hits_md_tags": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(MdTagStats), _P]),
     "sfgpu_hits_posteriors": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.POINTER(PosteriorStats), _P]),
+    "sfgpu_hits_library_kinds": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(LibdetOpts), C.POINTER(C.c_int64), C.POINTER(LibdetStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

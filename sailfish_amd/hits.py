@@ -862,6 +862,174 @@ def posteriors(hits, offsets, weights, device="cuda"):
     return p, rec, f32, st.as_dict()
 
 
+LIBDET_KINDS = ("ISF", "ISR", "OSF", "OSR", "MSF", "MSR", "LF", "LR", "RF", "RR", "SF", "SR", "other")
+LIBDET_STATS = ("reads", "reads_mapped", "reads_over_occs", "reads_mixed", "reads_compatible", "votes", "records_kind", "reads_kind", "votes_kind")
+LIBDET_PERMILLE = (501, 1000)
+_FORMAT_NAMES = {v: k for k, v in LIBRARY_FORMATS.items()}
+
+
+def _libdet_stats(stats=None):
+    """a fresh set of the counters, or a copy of `stats` to add to"""
+    if stats is None:
+        return {k: [0] * len(LIBDET_KINDS) if k.endswith("_kind") else 0 for k in LIBDET_STATS}
+    return {k: [int(v) for v in stats[k]] if k.endswith("_kind") else int(stats[k]) for k in LIBDET_STATS}
+
+
+def _libdet_permille(min_fraction):
+    p = int(round(float(min_fraction) * 1000))
+    if not LIBDET_PERMILLE[0] <= p <= LIBDET_PERMILLE[1]:
+        raise ValueError(f"min_fraction = {min_fraction!r} lies outside 0.501 .. 1")
+    return p
+
+
+def _format_triple(lib_format):
+    return LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(int(v) for v in lib_format)
+
+
+def record_kinds_host(hits, allow_dovetail=False):
+    """csrc/libdetfmt.h's KIND of every record, restated in numpy: an index into LIBDET_KINDS each.  Status 3: the mates' starts s1, s2
+    are pos (forward) or pos + len (reverse), the sum taken in uint32 and read as int32; mates on different strands are *SF where mate 1
+    is the forward one, inward iff s1 <= s2 + stretch (*SR: s2 <= s1 + stretch), stretch being the other mate's length with
+    allow_dovetail, else 0; mates on one strand are MSF / MSR.  Status 1 / 2 / 0: LF LR / RF RR / SF SR.  Any other status: other."""
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    st, f1, f2 = h["mate_status"], h["fwd"] != 0, h["mate_fwd"] != 0
+
+    def start(pos, length, fwd):
+        s = (pos.astype(np.int64) + np.where(fwd, 0, length.astype(np.int64))) & 0xFFFFFFFF
+        return np.where(s >= 1 << 31, s - (1 << 32), s)
+    s1, s2 = start(h["pos"], h["read_len"], f1), start(h["mate_pos"], h["mate_len"], f2)
+    stretch1 = h["mate_len"].astype(np.int64) if allow_dovetail else 0
+    stretch2 = h["read_len"].astype(np.int64) if allow_dovetail else 0
+    pair = np.where(f1 == f2, np.where(f1, 4, 5), np.where(f1, np.where(s1 <= s2 + stretch1, 0, 2), np.where(s2 <= s1 + stretch2, 1, 3)))
+    rev = (~f1).astype(np.int64)
+    return np.select([st == 3, st == 1, st == 2, st == 0], [pair, 6 + rev, 8 + rev, 10 + rev], 12).astype(np.uint8)
+
+
+def kind_compatible(lib_format, kind):
+    """does the library format accept a record of this kind (a LIBDET_KINDS name or index)?  What compatibleHit says of it: a pair
+    must show the format's orientation and, unless that is unstranded, its strandedness; a single-end read and an orphan must lie on
+    the strand the format puts that mate on (a right orphan of an inward or outward library on the opposite one)."""
+    _, eo, es = _format_triple(lib_format)
+    k = LIBDET_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+    if k <= 5:
+        oo = (TOWARD, AWAY, SAME)[k // 2]
+        os_ = (S, A)[k & 1] if oo == SAME else (SA, AS)[k & 1]
+        return eo == oo and es in (U, os_)
+    if k >= 12:
+        return False
+    fwd = (k - 6) % 2 == 0
+    if k < 10 and eo != SAME and k >= 8:
+        fwd = not fwd
+    return es in ((U, S) if fwd else (U, A))
+
+
+def library_compat_mask(lib_format):
+    """csrc/libdetfmt.h's ld_compat_mask: bit k set iff the format accepts kind k"""
+    return sum(1 << k for k in range(len(LIBDET_KINDS)) if kind_compatible(lib_format, k))
+
+
+def library_kinds_host(hits, offsets, *, paired_library, max_read_occs=200, allow_dovetail=False, remaining_votes=0, expected=None, stats=None):
+    """The statement of the library-format tally (csrc/libdetfmt.h restated in numpy; what sfgpu_hits_library_kinds is judged by).
+    hits: HIT_DTYPE records in CSR form over the reads (offsets[R + 1]).  A read without a record counts in `reads` only; one with more
+    than max_read_occs in `reads_over_occs` and nothing else; any other in `reads_mapped`, its records in records_kind (per
+    record_kinds_host), the read in reads_kind[k] where all its records are of kind k, else in reads_mixed, and -- with `expected`, a
+    library format -- in reads_compatible iff one of its kinds is compatible (kind_compatible).  A mapped read votes iff all its
+    records are of one kind and that is ISF .. MSR (paired_library) or SF / SR (single end); the first remaining_votes voters in read
+    order are counted in votes_kind / votes.  The counters are added to `stats` (a dict as returned; None: zeros).
+    -> (remaining_votes, stats dict of LIBDET_STATS: the *_kind entries lists in the order of LIBDET_KINDS)"""
+    off = np.asarray(offsets).astype(np.int64)
+    out = _libdet_stats(stats)
+    R, K = max(len(off) - 1, 0), len(LIBDET_KINDS)
+    remaining = int(remaining_votes)
+    if R == 0:
+        return remaining, out
+    kinds = record_kinds_host(np.ascontiguousarray(hits, dtype=HIT_DTYPE)[: off[-1]], allow_dovetail).astype(np.int64)
+    n = np.diff(off)
+    over = n > int(max_read_occs)
+    mapped = (n > 0) & ~over
+    read_of = np.repeat(np.arange(R), n)
+    mask = np.zeros(R, np.int64)
+    np.bitwise_or.at(mask, read_of, 1 << kinds)
+    mask[~mapped] = 0
+    single = mapped & ((mask & (mask - 1)) == 0)
+    read_kind = np.zeros(R, np.int64)
+    read_kind[single] = np.log2(mask[single]).astype(np.int64)
+    voting = 0x3F if paired_library else (1 << 10 | 1 << 11)
+    voters = np.nonzero(single & ((mask & voting) != 0))[0][:max(remaining, 0)]
+    compat = library_compat_mask(expected) if expected is not None else 0
+    add = dict(reads=R, reads_mapped=int(mapped.sum()), reads_over_occs=int(over.sum()), reads_mixed=int((mapped & ~single).sum()),
+               reads_compatible=int((mapped & ((mask & compat) != 0)).sum()), votes=len(voters),
+               records_kind=np.bincount(kinds[mapped[read_of]], minlength=K).tolist(), reads_kind=np.bincount(read_kind[single], minlength=K).tolist(),
+               votes_kind=np.bincount(read_kind[voters], minlength=K).tolist())
+    for k, v in add.items():
+        out[k] = [a + b for a, b in zip(out[k], v)] if isinstance(v, list) else out[k] + v
+    return remaining - len(voters), out
+
+
+def decide_library_format(votes, paired, min_fraction=0.7, min_votes=200):
+    """csrc/libdetfmt.h's DECIDE over the votes of library_kinds (the 13 votes_kind counts, or a stats dict that holds them), in
+    integers.  Paired: T = ISF + ISR, A = OSF + OSR, M = MSF + MSR; fewer than min_votes of them (or none): undetermined.  The
+    orientation is the largest of T, A, M, ties in that order; with s its *SF count and n its sum the library is sense (ISF / OSF /
+    MSF) iff 1000 s >= permille n, antisense (ISR / OSR / MSR) iff 1000 (n - s) >= permille n, else unstranded (IU / OU / MU).  Single
+    end: the same with s = SF, n = SF + SR (SF / SR / U).  permille = int(round(min_fraction * 1000)), 501 .. 1000 (else ValueError).
+    The default 0.7 is the customary threshold of other tools; nobody has measured it on real libraries here.  min_votes 200: at
+    p = 0.5 a 70 % majority of 200 votes lies 5.6 sigma out, so an unstranded library is not called stranded by chance.
+    -> (a name of LIBRARY_FORMATS or None where undetermined, detail dict: votes, orientation votes, sense, total, permille, min_votes)"""
+    permille = _libdet_permille(min_fraction)
+    v = [int(x) for x in (votes["votes_kind"] if isinstance(votes, dict) else votes)]
+    if len(v) != len(LIBDET_KINDS):
+        raise ValueError(f"{len(v)} vote counts, not one for each of the {len(LIBDET_KINDS)} kinds")
+    min_votes = int(min_votes)
+    if paired:
+        inward, outward, matching = v[0] + v[1], v[2] + v[3], v[4] + v[5]
+        total = inward + outward + matching
+        detail = dict(votes=total, inward=inward, outward=outward, matching=matching)
+        if inward >= outward and inward >= matching:
+            orientation, s, n = TOWARD, v[0], inward
+        elif outward >= matching:
+            orientation, s, n = AWAY, v[2], outward
+        else:
+            orientation, s, n = SAME, v[4], matching
+    else:
+        orientation, s, n = NONE, v[10], v[10] + v[11]
+        total = n
+        detail = dict(votes=total)
+    detail.update(sense=s, total=n, permille=permille, min_votes=min_votes)
+    if total < min_votes or total == 0:
+        return None, detail
+    one_mate = orientation in (SAME, NONE)
+    strand = U
+    if 1000 * s >= permille * n:
+        strand = S if one_mate else SA
+    elif 1000 * (n - s) >= permille * n:
+        strand = A if one_mate else AS
+    return _FORMAT_NAMES[(1 if paired else 0, orientation, strand)], detail
+
+
+def library_kinds(hits, offsets, *, paired_library, max_read_occs=200, allow_dovetail=False, remaining_votes=0, expected=None, stats=None, device="cuda"):
+    """The library formats a batch's records show, tallied on the device (sfgpu_hits_library_kinds; the rule is library_kinds_host's,
+    argument for argument).  hits / offsets: device tensors as QuasiIndex.map_reads returns them (or host arrays).  With
+    remaining_votes == 0 no vote is looked for.  -> (remaining_votes, stats dict of LIBDET_STATS)"""
+    dev = hits.device if isinstance(hits, torch.Tensor) and hits.is_cuda else torch.device(device)
+    d_hits, d_off = _device_hits(hits, offsets, dev)
+    R = int(d_off.numel()) - 1
+    if R < 0:
+        raise ValueError("hit offsets hold at least one entry")
+    fmt = _format_triple(expected) if expected is not None else (0, 0, 0)
+    o = _lib.LibdetOpts(int(max_read_occs), int(bool(paired_library)), int(bool(allow_dovetail)), int(expected is not None), _lib.LibFmt(fmt[0], fmt[1], fmt[2], 0))
+    st = _lib.LibdetStats()
+    for k, v in _libdet_stats(stats).items():
+        if k.endswith("_kind"):
+            getattr(st, k)[:] = v
+        else:
+            setattr(st, k, v)
+    rem = C.c_int64(int(remaining_votes))
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.lib().sfgpu_hits_library_kinds(_lib.ptr(d_hits), _lib.ptr(d_off), R, C.byref(o), C.byref(rem), C.byref(st), _lib.current_stream_ptr()))
+    return int(rem.value), st.as_dict()
+
+
 def gc_prefix(seq, seq_off, ref_len):
     """Transcript::GCCount_ of every transcript (include/Transcript.hpp:183-196), laid out like `seq`: int32 device
     tensor of seq.numel() entries (4 bytes per base) -- what sample_bias reads for the fragment-GC samples."""

@@ -450,6 +450,9 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     counters reported are the first pass's, and the second must reproduce them (RuntimeError otherwise); the align and tag counters
     are the second's; the pass's own are left on the experiment as `posterior_stats` (None without the option), its weights as
     `posterior_weights`, and go to sopt.jointLog as one line.
+    lib_format="A" detects the library format from the first batches' records (quant.quantify: the detect_* keywords and
+    lib_format_counts pass through **kw; whether mate 2 exists says which records vote) and writes aux/lib_format_counts.json; with
+    rescue_mates=True it is a ValueError before anything is indexed: the rescue needs to know that the pairs face inward.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
@@ -477,7 +480,8 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
         seq_kw = dict(seq=bytes(s.numpy().tobytes()), seq_off=o[:-1].numpy())
     try:
         run.open(names, idx)
-        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device,
+                                 paired_library=reads2 is not None, **seq_kw, **kw)
         run.second_pass(rc, exp, sopt, names, idx, batches)
     finally:
         run.close()
@@ -560,7 +564,8 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
         seq_kw = dict(seq=s, seq_off=o)
     try:
         run.open(names, idx)
-        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
+        rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device,
+                                 paired_library=reads2_path is not None, **seq_kw, **kw)
         run.second_pass(rc, exp, sopt, names, idx, batches)
     finally:
         run.close()

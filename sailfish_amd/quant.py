@@ -35,17 +35,33 @@ def write_cmd_info(out_dir, options):
 
 def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpts = None, *, seq=None, seq_off=None,
              allow_orphans=False, ignore_lib_compat=False, enforce_lib_compat=False, allow_dovetail=False,
-             num_bias_samples=1_000_000, gene_map=None, cmd_options=None, seed=None, device="cuda"):
+             num_bias_samples=1_000_000, gene_map=None, cmd_options=None, seed=None, device="cuda", paired_library=None,
+             detect_votes=50_000, detect_min_votes=200, detect_min_fraction=0.7, detect_max_reads=16_000_000, lib_format_counts=None):
     """names / ref_len: the index's transcripts.  hit_batches: iterable of (hits, hit_offsets) as hits.filter_hits takes
     them.  seq / seq_off: RapMapSAIndex::seq and txpOffsets (needed with biasCorrect / gcBiasCorrect).
+    lib_format="A" detects the format from the records: paired_library (required then, else ValueError before anything
+    is written) says which kinds vote; the incoming batches are held and their votes counted on the device (hits.library_kinds) until
+    detect_votes voters are in (a convention; anything at or above detect_min_votes works), detect_max_reads reads have been seen or
+    the input ends; hits.decide_library_format(votes, paired_library, detect_min_fraction, detect_min_votes) names the format, IU / U
+    standing in (with a level-1 warning) where it is undetermined; the held batches and then the rest run through the loop below
+    with that format, as if it had been given.  exp.lib_format_detected is then a dict: name, detected, fallback, votes, detail.
+    aux/lib_format_counts.json (writer.lib_format_counts_text) is written iff lib_format is "A" or lib_format_counts is true (also with
+    an explicit format): every batch is then tallied against the run's format as well.  Without either, no new call runs.
     Returns (rc, ReadExperiment)."""
     sopt = sopt or SailfishOpts()
     log = sopt.jointLog or (lambda lvl, msg: None)
     dev = torch.device(device)
+    detect = isinstance(lib_format, str) and lib_format.upper() == "A"
+    if detect:
+        if paired_library is None:
+            raise ValueError('lib_format="A" needs paired_library: whether the reads are pairs decides which records vote')
+        _hits._libdet_permille(detect_min_fraction)
+        if int(detect_votes) < int(detect_min_votes):
+            raise ValueError(f"detect_votes = {detect_votes!r} lies below detect_min_votes = {detect_min_votes!r}: no format could ever be decided")
     start_time = time.asctime()
     write_cmd_info(out_dir, cmd_options)
-    fmt = _hits.LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(lib_format)
-    paired = fmt[0] == 1
+    fmt = None if detect else _hits.LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(lib_format)
+    paired = bool(paired_library) if detect else fmt[0] == 1
     if sopt.numGibbsSamples > 0 and sopt.numBootstraps > 0:                  # :1280-1286
         log(2, "You cannot perform both Gibbs sampling and bootstrapping. Please choose one.")
         return 1, None
@@ -74,7 +90,15 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
     d_rb = torch.from_numpy(exp.readBias().view(np.int32).copy()).to(dev) if sopt.biasCorrect else None
     d_gc = torch.from_numpy(exp.observedGC().view(np.int32).copy()).to(dev) if sopt.gcBiasCorrect else None
     stats = None
+    detection = counts = None
+    tally_kw = dict(paired_library=paired, max_read_occs=sopt.maxReadOccs, allow_dovetail=allow_dovetail, device=dev)
+    if detect:
+        hit_batches, detection = _detect_library_format(hit_batches, log, detect_votes, detect_min_votes, detect_min_fraction, detect_max_reads, tally_kw)
+        lib_format = detection["name"]
+        fmt = _hits.LIBRARY_FORMATS[lib_format]
     for hits, off in hit_batches:                                            # the mapping threads' loop bodies
+        if detect or lib_format_counts:
+            _, counts = _hits.library_kinds(hits, off, expected=fmt, stats=counts, **tally_kw)
         ids, out_off, rem_fl, stats = _hits.filter_hits(hits, off, fmt, paired_library=paired, allow_orphans=allow_orphans,
                                                         ignore_lib_compat=ignore_lib_compat, enforce_lib_compat=enforce_lib_compat,
                                                         allow_dovetail=allow_dovetail, max_read_occs=sopt.maxReadOccs,
@@ -94,13 +118,64 @@ def quantify(names, ref_len, hit_batches, lib_format, out_dir, sopt: SailfishOpt
         exp.readBias()[:] = d_rb.cpu().numpy().view(np.uint32)
     if d_gc is not None:
         exp.observedGC()[:] = d_gc.cpu().numpy().view(np.uint32)
+    if detect:
+        exp.lib_format_detected = detection
+    if detect or lib_format_counts:
+        counts = counts or _hits._libdet_stats()
+        name = lib_format.upper() if isinstance(lib_format, str) else _hits._FORMAT_NAMES[fmt]
+        _writer.write_lib_format_counts(out_dir, sopt, _writer.lib_format_counts_text(
+            name, counts, votes=detection["stats"] if detect else None, detected=detection["detected"] if detect else None,
+            fallback=bool(detect and detection["fallback"])))
+        exp.lib_format_counts = counts
+        log(0, "library format {}: {} of {} mapped fragments have a compatible mapping (ratio {:g})".format(
+            name, counts["reads_compatible"], counts["reads_mapped"], counts["reads_compatible"] / counts["reads_mapped"] if counts["reads_mapped"] else 0.0))
     # quasiMapReads' tail: the fragment length distribution and the effective lengths (:937-991, :1035-1043), then the rest
     return _quantify_tail(exp, sopt, out_dir, start_time, fl_counts=fl.cpu().numpy().view(np.uint32) if paired else None,
                           remaining_fl_ops=rem_fl, gene_map=gene_map, seed=seed)
 
 
+def _owned(t):
+    """a batch tensor that keeps nothing alive but itself: a view of a larger allocation (the mapper's records are the front of a
+    buffer sized by a guess) is copied"""
+    if isinstance(t, torch.Tensor) and t.untyped_storage().nbytes() > t.numel() * t.element_size():
+        return t.clone()
+    return t
+
+
+def _detect_library_format(hit_batches, log, detect_votes, detect_min_votes, detect_min_fraction, detect_max_reads, tally_kw):
+    """lib_format="A": batches are taken off `hit_batches` and held while their votes are counted, until detect_votes voters are in,
+    detect_max_reads reads have been seen or the input ends.  -> (the batches to run: the held ones, released one by one, then the
+    rest; the detection: name, detected, fallback, votes, detail, stats)"""
+    it = iter(hit_batches)
+    held, stats, remaining, seen = [], None, int(detect_votes), 0
+    for hits, off in it:
+        hits, off = _owned(hits), _owned(off)
+        remaining, stats = _hits.library_kinds(hits, off, remaining_votes=remaining, stats=stats, **tally_kw)
+        held.append((hits, off))
+        seen += len(off) - 1
+        if remaining == 0 or seen >= int(detect_max_reads):
+            break
+    stats = stats or _hits._libdet_stats()
+    paired = tally_kw["paired_library"]
+    detected, detail = _hits.decide_library_format(stats["votes_kind"], paired, detect_min_fraction, detect_min_votes)
+    name = detected or ("IU" if paired else "U")
+    votes = {k: v for k, v in zip(_hits.LIBDET_KINDS, stats["votes_kind"]) if v}
+    if detected is None:
+        log(1, "lib_format A: the library format is undetermined ({} votes in {} reads, {} needed: {}); falling back to {}: {}".format(
+            detail["votes"], seen, detail["min_votes"], votes, name, _hits.format_str(_hits.LIBRARY_FORMATS[name])))
+    else:
+        log(0, "lib_format A: detected {} from {} votes in {} reads ({}): {}".format(name, detail["votes"], seen, votes, _hits.format_str(_hits.LIBRARY_FORMATS[name])))
+
+    def batches():
+        held.reverse()
+        while held:
+            yield held.pop()
+        yield from it
+    return batches(), dict(name=name, detected=detected, fallback=detected is None, votes=votes, detail=detail, stats=stats)
+
+
 def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, transcripts_path=None, device="cuda", block_bytes=32 << 20,
-                 inflate="auto", collate=False, **kw):
+                 inflate="auto", collate=False, paired=None, **kw):
     """`sailfish quant` from a mapper's SAM file on (RapMap's `quasimap -o`, bowtie2, bwa against the transcriptome; plain, BGZF or
     gzip; grouped by read name): the names and lengths come from the @SQ lines, the alignment lines are turned into hit records
     on the device (samfile.SamFile) and handed to quantify batch by batch.  `sam_path` may as well be the BAM file that
@@ -112,10 +187,20 @@ def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, tr
     them through their mate fields; "auto" does so iff the header says SO:coordinate.  The fragments then arrive in the order of
     their first lines, and the fragment-length sample (numFragSamples) is taken from the fragments that appear first, as always: in
     a position-sorted file those are the fragments of the first transcripts, not a sample of the whole library.
+    paired: whether the file holds pairs; None takes it from the library format, and lib_format="A" (quantify's detection) requires
+    it (ValueError otherwise): it is what the SamFile is opened with.
     -> (rc, experiment)"""
     from . import samfile
     sopt = sopt or SailfishOpts()
-    fmt = _hits.LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(lib_format)
+    if isinstance(lib_format, str) and lib_format.upper() == "A":
+        if paired is None:
+            raise ValueError('lib_format="A" needs paired=: whether the file holds pairs is what it is opened with')
+        kw["paired_library"] = bool(paired)
+    else:
+        fmt = _hits.LIBRARY_FORMATS[lib_format.upper()] if isinstance(lib_format, str) else tuple(lib_format)
+        if paired is not None and bool(paired) != (fmt[0] == 1):
+            raise ValueError(f"paired = {paired!r} contradicts the library format {lib_format!r}")
+        paired = fmt[0] == 1
     names, lengths = samfile.read_header(sam_path)
     if not names:
         raise ValueError(f"{sam_path}: no @SQ lines in the header")
@@ -130,7 +215,7 @@ def quantify_sam(sam_path, lib_format, out_dir, sopt: SailfishOpts = None, *, tr
             raise ValueError(f"{transcripts_path}: the names and lengths of the transcripts are not those of the @SQ lines of {sam_path}")
         s, o = _dollar_separated(bases, off)
         seq_kw = dict(seq=s, seq_off=o)
-    batches = samfile.SamFile(sam_path, device, fmt[0] == 1, names=names, block_bytes=block_bytes, inflate=inflate, collate=collate)
+    batches = samfile.SamFile(sam_path, device, bool(paired), names=names, block_bytes=block_bytes, inflate=inflate, collate=collate)
     try:
         return quantify(names, np.array(lengths, np.uint32), batches, lib_format, out_dir, sopt, device=device, **seq_kw, **kw)
     finally:

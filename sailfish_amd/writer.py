@@ -103,6 +103,38 @@ def write_meta(path, readExp: ReadExperiment, sopt: SailfishOpts, start_time: st
     return True
 
 
+def lib_format_counts_text(expected, counts, votes=None, detected=None, fallback=False):
+    """The text of aux/lib_format_counts.json, keys in a fixed order.  expected: the name of the format the run used; counts: the
+    hits.library_kinds stats of all its batches, tallied with expected= that format; votes: the stats that hold the detection's votes
+    (None: no detection ran, the votes are zeros); detected: the name the detection decided on, or None; fallback: the detection was
+    undetermined and `expected` is the unstranded default.  compatible_fragment_ratio = num_compatible / num_mapped (0 when nothing
+    mapped); strand_mapping_bias = the minority share of the two reads_kind counters of the expected orientation (ISF and ISR for an
+    inward format, SF and SR for a single-end one; 0 when both are 0)."""
+    from .hits import AWAY, LIBDET_KINDS, LIBRARY_FORMATS, NONE, TOWARD
+    name = expected.upper()
+    orientation = LIBRARY_FORMATS[name][1]
+    first = {TOWARD: 0, AWAY: 2, NONE: 10}.get(orientation, 4)
+    a, b = (int(counts["reads_kind"][first + i]) for i in (0, 1))
+    mapped, compatible = int(counts["reads_mapped"]), int(counts["reads_compatible"])
+    vk = [int(v) for v in votes["votes_kind"]] if votes is not None else [0] * len(LIBDET_KINDS)
+    per_kind = lambda vals: {k: int(v) for k, v in zip(LIBDET_KINDS, vals)}
+    info = [("expected_format", name), ("detected", detected), ("fallback", bool(fallback)), ("num_votes", sum(vk)), ("votes", per_kind(vk)),
+            ("num_reads", int(counts["reads"])), ("num_mapped", mapped), ("num_over_occs", int(counts["reads_over_occs"])),
+            ("num_consistent", mapped - int(counts["reads_mixed"])), ("num_mixed", int(counts["reads_mixed"])), ("num_compatible", compatible),
+            ("compatible_fragment_ratio", compatible / mapped if mapped else 0.0),
+            ("strand_mapping_bias", min(a, b) / (a + b) if a + b else 0.0),
+            ("records", per_kind(counts["records_kind"])), ("reads", per_kind(counts["reads_kind"]))]
+    return json.dumps(dict(info), indent=4)
+
+
+def write_lib_format_counts(path, sopt: SailfishOpts, text):
+    aux = os.path.join(path, sopt.auxDir)
+    os.makedirs(aux, exist_ok=True)
+    with open(os.path.join(aux, "lib_format_counts.json"), "w") as f:
+        f.write(text)
+    return True
+
+
 class BootstrapWriter:
     """writeBootstrap<T> (GZipWriter.cpp:249-285): every sample is appended as raw binary (float64 for
     bootstrap replicates, int32 for Gibbs samples) to aux/bootstrap/bootstraps.gz.  An instance is the callback

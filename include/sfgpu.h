@@ -684,23 +684,90 @@ SFGPU_API int sfgpu_samc_close(sfgpu_samc* c);
  * csrc/samwfmt.h (the bytes of samfile._sam_text); the kernels are csrc/samtext_write.hip.  In short, per read in order: a pair
  * record (mate_status 3) gives its 0x40 and its 0x80 line, any other record one line (orphans with 0x8, single-end records
  * without 0x1), 0x100 from the read's second record on; a read without records gives 77 / 141 (paired != 0) or one 4 line.
- * MAPQ 255, CIGAR <len>M or <clip>S<rest>M, QUAL '*'; SEQ is written as given, also on 0x10 lines (sfgpu_sam_write_text_q below
- * writes the qualities and puts 0x10 lines on the reference's strand).  The @HD / @SQ header is the host's business.
- *   d_hits / d_hit_offsets[n_reads + 1]   the batch (uint32 offsets, starting at 0, never decreasing, else SFGPU_ERR_INVALID).
- *   d_ref_names / d_ref_name_off[n_refs + 1]   the transcript names back to back, uint64 offsets (quantfile.names_blob).
- *   d_qnames / d_qname_off[n_reads + 1]   the read names, likewise; d_qname_off == NULL: read r is named r<read_index_base + r>.
- *   d_seq1 / d_seq1_off[n_reads + 1]   the bases of mate 1 (of the reads, single end) back to back with int64 offsets, as
- *            sfgpu_reads_parse_* and sfgpu_map_reads take them; d_seq1_off == NULL: SEQ is '*'.  d_seq2 / d_seq2_off: mate 2, read
+ * MAPQ 255, CIGAR <len>M or <clip>S<rest>M, QUAL '*'; SEQ is written as given, also on 0x10 lines.  The @HD / @SQ header is the
+ * host's business.
+ * The batch is one sfgpu_samw_batch of device pointers, the same for every destination: sfgpu_sam_write_text (a sink),
+ * sfgpu_sam_write_bgzf (a BGZF handle) and sfgpu_bamsort_collect (a sorted record store); batch == NULL is SFGPU_ERR_INVALID.
+ * Brace-initialise it: a group below left NULL (0) is not written, and every byte is then what it is without that group.
+ *   hits / hit_off[n_reads + 1]   the batch (uint32 offsets, starting at 0, never decreasing, else SFGPU_ERR_INVALID).  paired
+ *            decides what a read without records gives and whether mate 2 is read.
+ *   ref_names / ref_name_off[n_refs + 1]   the transcript names back to back, uint64 offsets (quantfile.names_blob).
+ *   qnames / qname_off[n_reads + 1]   the read names, likewise; qname_off == NULL: read r is named r<read_index_base + r>.
+ *   seq1 / seq1_off[n_reads + 1]   the bases of mate 1 (of the reads, single end) back to back with int64 offsets, as
+ *            sfgpu_reads_parse_* and sfgpu_map_reads take them; seq1_off == NULL: SEQ is '*'.  seq2 / seq2_off: mate 2, read
  *            only when paired != 0.  Names and bases are copied verbatim, never inspected, of any length including 0.
- * A record with pos < 0 and -pos >= read_len (no base on the transcript; for a pair record either mate), or with tid >= n_refs,
- * cannot be written: the call returns SFGPU_ERR_INVALID before any sink call, error_read / error_record name the lowest such
- * (read, record) of the batch and error_kind says which rule (1 position, 2 tid; the position first where one record breaks both).
- * The text is handed to `sink` as sfgpu_quant_write_text hands over its rows: consecutive chunks of at most chunk_bytes (0 = 32
- * MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID), greedy, each a whole number of UNITS -- a unit is what one record or one
- * record-less read produces, so the two lines of a pair are never split -- from a pinned staging buffer that is valid only during
- * the call, chunk c + 1 formatted and copied while the sink consumes chunk c.  A unit longer than chunk_bytes is SFGPU_ERR_RANGE
- * before the first sink call (`out` holds the sizes); a nonzero return of the sink ends the call with SFGPU_ERR_IO and no further
- * sink call; sink == NULL sizes (and checks) only; n_reads == 0 is SFGPU_OK with zero bytes and no sink call.
+ *   qual1 / qual2   the qualities of mate 1 / mate 2 (qual2 read only when paired != 0): bytes back to back that share the
+ *            mate's base offsets, so quality r is qual1[seq1_off[r] .. seq1_off[r + 1]).  NULL: QUAL is '*'.  Qualities of a
+ *            mate whose bases are not given (seq?_off == NULL) are SFGPU_ERR_INVALID.  QUAL is those bytes on every line that
+ *            carries the mate's SEQ, 0x100 lines and the lines of record-less reads included; a read of 0 bases has an empty QUAL.
+ *            (A 1-base read whose quality byte is '*' reads as "no qualities": the format's ambiguity, written as it is.)
+ *            BAM: QUAL is the quality bytes - 33 (0xff without qualities).
+ *   oriented != 0   a line whose FLAG has 0x10 stores SEQ and QUAL on the reference's strand, as the SAM specification has it: SEQ
+ *            reverse-complemented (A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, either case kept, every other byte as it is),
+ *            QUAL reversed.  Lines without 0x10, every line of a record-less read among them, are as given.  BAM: on a 0x10 record
+ *            the bases are complemented and packed from the last to the first, the qualities reversed: the record
+ *            samfile.sam_to_bam makes of the oriented text.
+ *   aln_pos / aln_op_off / aln_ops   the gapped alignment (sfgpu_hits_align_gapped's d_pos, d_op_off, d_ops for the same records:
+ *            slot 2 h + which is line `which` of record h).  A mapped line's POS is aln_pos[slot] + 1, its CIGAR the slot's
+ *            operations (len << 4 | op, MIDNSHP=X), PNEXT the other line's POS written this way; FLAG and TLEN are unchanged.  A
+ *            line whose slot has no operation has no base on the transcript: error_kind 1, and the record's own pos is not
+ *            consulted.  The three go together (SFGPU_ERR_INVALID otherwise).  BAM: the CIGAR words are the slot's; bin and
+ *            error_kind 5 take the reference span (M + D), error_kind 4 compares the bases given with S + M + I and covers more
+ *            than 65 535 operations.
+ *   tag_nm / tag_md_off / tag_md   the NM / MD tags (sfgpu_hits_md_tags' d_nm, d_md_off, d_md for the same records and the same
+ *            alignment, slots as above).  A mapped line ends ... QUAL \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh> \n, nh being the read's
+ *            record count hit_off[r + 1] - hit_off[r]; the lines of a read without records carry no tags.  The three go together,
+ *            and tags need the mates' bases (seq1_off, and seq2_off of a paired batch): SFGPU_ERR_INVALID otherwise.  BAM: a
+ *            mapped line's record ends, behind QUAL, NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>, <t> being the first of c C s S i I
+ *            that holds the value, and block_size counts them: the bytes of sam_to_bam of the tagged text.
+ *   tag_zw_rec / tag_zw_f32   the posteriors (sfgpu_hits_posteriors' d_rec and d_f32 for the same records: one entry per record,
+ *            so both lines of a pair carry the record's value).  A mapped line ends ... QUAL [\t NM ... \t MD ... \t NH ...]
+ *            \t ZW:f:<token> \n, the token being printf("%g") of the record's posterior probability, placed from tag_zw_rec; the
+ *            lines of a read without records carry nothing.  The two go together (SFGPU_ERR_INVALID otherwise); tags and
+ *            posteriors are independent of each other.  BAM: a mapped line's record ends, behind NH where there is one, Z W f and
+ *            the four bytes of tag_zw_f32's float, and block_size counts those seven bytes: the bytes of sam_to_bam of the text
+ *            with its ZW:f: tokens.
+ * A batch that breaks a rule fails with SFGPU_ERR_INVALID before anything is written; error_read / error_record name the lowest
+ * such (read, record) of the batch and error_kind says which rule: 1 no base on the transcript (a record with pos < 0 and
+ * -pos >= read_len; for a pair record either mate), 2 tid >= n_refs, 6 a quality byte outside '!' .. '~' (33 .. 126; a tab or a
+ * newline would break the text), reported as (read, record 0) for the lowest read that holds one.  BAM records add 3 a read name
+ * not of 1 .. 254 bytes, 4 bases given whose number differs from the record's read length, or more than 65 535 of them, 5 an
+ * alignment that ends beyond 2^29 (a record-less read counts as record 0).  The kinds are merged by the lowest (read, record),
+ * then the lowest kind. */
+typedef struct sfgpu_samw_batch {
+    const struct sfgpu_hit* hits;
+    const uint32_t* hit_off;         /* [n_reads + 1] */
+    uint32_t n_reads;
+    int paired;
+    const char* ref_names;
+    const uint64_t* ref_name_off;    /* [n_refs + 1] */
+    uint32_t n_refs;
+    const char* qnames;
+    const uint64_t* qname_off;       /* [n_reads + 1] */
+    const uint8_t* seq1;
+    const int64_t* seq1_off;         /* [n_reads + 1] */
+    const uint8_t* seq2;
+    const int64_t* seq2_off;         /* [n_reads + 1] */
+    uint64_t read_index_base;
+    const uint8_t* qual1;
+    const uint8_t* qual2;
+    int oriented;
+    const int32_t* aln_pos;          /* [2 records] */
+    const uint64_t* aln_op_off;      /* [2 records + 1] */
+    const uint32_t* aln_ops;
+    const uint32_t* tag_nm;          /* [2 records] */
+    const uint64_t* tag_md_off;      /* [2 records + 1] */
+    const uint8_t* tag_md;
+    const uint32_t* tag_zw_rec;      /* [records] */
+    const float* tag_zw_f32;         /* [records] */
+} sfgpu_samw_batch;
+/* sfgpu_sam_write_text hands the text to `sink` as sfgpu_quant_write_text hands over its rows: consecutive chunks of at most
+ * chunk_bytes (0 = 32 MiB; otherwise 16 .. 2^30, else SFGPU_ERR_INVALID), greedy, each a whole number of UNITS -- a unit is what
+ * one record or one record-less read produces, so the two lines of a pair are never split -- from a pinned staging buffer that is
+ * valid only during the call, chunk c + 1 formatted and copied while the sink consumes chunk c.  A batch that breaks a rule fails
+ * before any sink call.  A unit longer than chunk_bytes is SFGPU_ERR_RANGE before the first sink call (`out` holds the sizes); a
+ * nonzero return of the sink ends the call with SFGPU_ERR_IO and no further sink call; sink == NULL sizes (and checks) only;
+ * n_reads == 0 is SFGPU_OK with zero bytes and no sink call.
  * Synchronous; ordered behind whatever is queued on `stream`; independent calls may run from several threads.  Scratch on the
  * device: 8 bytes per read, 16 bytes per unit and two chunk buffers. */
 typedef struct {
@@ -716,74 +783,8 @@ typedef struct {
     double d2h_ms;            /* device events around the staged copies */
     double sink_ms;           /* host clock inside the sink */
 } sfgpu_samwrite_result;
-SFGPU_API int sfgpu_sam_write_text(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                   const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                   const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                   const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                   void* user, sfgpu_samwrite_result* out, sfgpu_stream stream);
-/* sfgpu_sam_write_text with qualities and orientation; sfgpu_sam_write_text is this call with NULL, NULL, 0.
- *   d_qual1 / d_qual2   the qualities of mate 1 / mate 2 (d_qual2 read only when paired != 0): bytes back to back that share the
- *            mate's base offsets, so quality r is d_qual1[d_seq1_off[r] .. d_seq1_off[r + 1]).  NULL: QUAL is '*'.  Qualities of a
- *            mate whose bases are not given (d_seq?_off == NULL) are SFGPU_ERR_INVALID.  QUAL is those bytes on every line that
- *            carries the mate's SEQ, 0x100 lines and the lines of record-less reads included; a read of 0 bases has an empty QUAL.
- *            (A 1-base read whose quality byte is '*' reads as "no qualities": the format's ambiguity, written as it is.)
- *   oriented != 0   a line whose FLAG has 0x10 stores SEQ and QUAL on the reference's strand, as the SAM specification has it: SEQ
- *            reverse-complemented (A<->T, C<->G, U->A, R<->Y, K<->M, B<->V, D<->H, either case kept, every other byte as it is),
- *            QUAL reversed.  Lines without 0x10, every line of a record-less read among them, are as given.
- * error_kind 6: a quality byte outside '!' .. '~' (33 .. 126) -- a tab or a newline would break the text.  The batch fails like
- * kinds 1 and 2, before any sink call; the lowest read that holds such a byte is reported as (read, record 0) and merged with
- * the other kinds by the lowest (read, record), then the lowest kind. */
-SFGPU_API int sfgpu_sam_write_text_q(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                     const uint8_t* d_qual2, int oriented);
-/* sfgpu_sam_write_text_q with the batch's gapped alignment (sfgpu_hits_align_gapped's d_pos, d_op_off, d_ops for the same records:
- * slot 2 h + which is line `which` of record h); sfgpu_sam_write_text_q is this call with NULL, NULL, NULL, and then every byte is
- * the same.  Given, a mapped line's POS is d_aln_pos[slot] + 1, its CIGAR the slot's operations (len << 4 | op, MIDNSHP=X), PNEXT the
- * other line's POS written this way; FLAG and TLEN are unchanged.  A line whose slot has no operation has no base on the transcript:
- * error_kind 1, and the record's own pos is not consulted.  The three go together (SFGPU_ERR_INVALID otherwise). */
-SFGPU_API int sfgpu_sam_write_text_a(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
-                                     const uint32_t* d_aln_ops);
-/* sfgpu_sam_write_text_a with the batch's NM / MD tags (sfgpu_hits_md_tags' d_nm, d_md_off, d_md for the same records and the same
- * alignment: slot 2 h + which is line `which` of record h); sfgpu_sam_write_text_a is this call with tags == NULL, and then every
- * byte is the same.  Given, a mapped line ends ... QUAL \t NM:i:<nm> \t MD:Z:<md> \t NH:i:<nh> \n, nh being the read's record count
- * d_hit_offsets[r + 1] - d_hit_offsets[r]; the lines of a read without records carry no tags.  The three pointers go together, and
- * tags need the mates' bases (d_seq1_off, and d_seq2_off of a paired batch): SFGPU_ERR_INVALID otherwise. */
-typedef struct sfgpu_samw_tags {
-    const uint32_t* d_nm;        /* [2 n] */
-    const uint64_t* d_md_off;    /* [2 n + 1] */
-    const uint8_t* d_md;
-} sfgpu_samw_tags;
-SFGPU_API int sfgpu_sam_write_text_t(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
-                                     const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
-/* sfgpu_sam_write_text_t with the batch's posteriors (sfgpu_hits_posteriors' d_rec and d_f32 for the same records: one entry per
- * record, so both lines of a pair carry the record's value); sfgpu_sam_write_text_t is this call with post == NULL, and then every
- * byte is the same.  Given, a mapped line ends ... QUAL [\t NM ... \t MD ... \t NH ...] \t ZW:f:<token> \n, the token being
- * printf("%g") of the record's posterior probability, placed from d_zw_rec; the lines of a read without records carry nothing.
- * The two pointers go together (SFGPU_ERR_INVALID otherwise); tags and posteriors are independent of each other. */
-typedef struct sfgpu_samw_post {
-    const uint32_t* d_zw_rec;    /* [n] */
-    const float* d_zw_f32;       /* [n] */
-} sfgpu_samw_post;
-SFGPU_API int sfgpu_sam_write_text_p(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink,
-                                     void* user, sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1,
-                                     const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off,
-                                     const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags, const sfgpu_samw_post* post);
+SFGPU_API int sfgpu_sam_write_text(const sfgpu_samw_batch* batch, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                   sfgpu_samwrite_result* out, sfgpu_stream stream);
 /* GZipWriter::writeBootstrap<T> (src/GZipWriter.cpp:249-285): the reference appends every sample as raw little-endian binary to ONE
  * gzip stream (boost::iostreams::gzip_compressor), aux/bootstrap/bootstraps.gz.  Here the stream is produced on the device from the
  * sample matrix where it lies (the d_out of sfgpu_bootstrap / sfgpu_gibbs_sample): a gzip (RFC 1952) writer whose DEFLATE
@@ -866,55 +867,11 @@ SFGPU_API int sfgpu_bgzw_close(sfgpu_bgzw* z, sfgpu_bgzw_result* res);
  * SFGPU_SAMW_BAM writes the same lines as BAM records (a BAM file when the caller has written the magic, the header text and the
  * reference list through the same handle): what samfile.sam_to_bam makes of the text, stated in csrc/bamwfmt.h -- mapq 255, the
  * specification's bin, CIGAR words S and M, SEQ 4-bit packed through =ACMGRSVTWYHKDBN after upper-casing (anything else 15), QUAL
- * 0xff, no SEQ given: l_seq 0.  A unit is then the one or two records of a hit record or record-less read, n_lines counts records,
- * and three more rules fail a batch, after kinds 1 and 2 where one record breaks several (a record-less read counts as record 0):
- * error_kind 3 a read name not of 1 .. 254 bytes; 4 bases given whose number differs from the record's read length, or more than
- * 65 535 of them; 5 an alignment that ends beyond 2^29. */
+ * 0xff, no SEQ given: l_seq 0; each group of the batch as sfgpu_samw_batch says.  A unit is then the one or two records of a hit
+ * record or record-less read, n_lines counts records, and error kinds 3 .. 5 apply. */
 enum { SFGPU_SAMW_TEXT = 0, SFGPU_SAMW_BAM = 1 };
-SFGPU_API int sfgpu_sam_write_bgzf(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                   const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                   const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                   const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
+SFGPU_API int sfgpu_sam_write_bgzf(const sfgpu_samw_batch* batch, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                    sfgpu_samwrite_result* out, sfgpu_stream stream);
-/* sfgpu_sam_write_bgzf with the qualities and the orientation of sfgpu_sam_write_text_q, error_kind 6 included; sfgpu_sam_write_bgzf
- * is this call with NULL, NULL, 0.  SFGPU_SAMW_BAM: QUAL is the quality bytes - 33 (0xff without qualities); on a 0x10 record of an
- * oriented file the bases are complemented and packed from the last to the first, the qualities reversed: the record
- * samfile.sam_to_bam makes of the oriented text. */
-SFGPU_API int sfgpu_sam_write_bgzf_q(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                     int oriented);
-/* ... and with the batch's gapped alignment, as sfgpu_sam_write_text_a.  SFGPU_SAMW_BAM: the CIGAR words are the slot's; bin and
- * error_kind 5 take the reference span (M + D), error_kind 4 compares the bases given with S + M + I and covers more than 65 535
- * operations. */
-SFGPU_API int sfgpu_sam_write_bgzf_a(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
-/* ... and with the batch's NM / MD tags, as sfgpu_sam_write_text_t; with tags == NULL this is sfgpu_sam_write_bgzf_a, byte for byte.
- * SFGPU_SAMW_BAM: a mapped line's record ends, behind QUAL, NM <t> <nm> | MD Z <md> NUL | NH <t> <nh>, <t> being the first of
- * c C s S i I that holds the value, and block_size counts them: the bytes of sam_to_bam of the tagged text. */
-SFGPU_API int sfgpu_sam_write_bgzf_t(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
-                                     const sfgpu_samw_tags* tags);
-/* ... and with the batch's posteriors, as sfgpu_sam_write_text_p; with post == NULL this is sfgpu_sam_write_bgzf_t, byte for byte.
- * SFGPU_SAMW_BAM: a mapped line's record ends, behind NH where there is one, Z W f and the four bytes of d_zw_f32's float, and
- * block_size counts those seven bytes: the bytes of sam_to_bam of the text with its ZW:f: tokens. */
-SFGPU_API int sfgpu_sam_write_bgzf_p(const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                     sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2,
-                                     int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
-                                     const sfgpu_samw_tags* tags, const sfgpu_samw_post* post);
 /* Reads as a FASTA / FASTQ text, formatted on the device from the batch where it lies: the mirror of sfgpu_reads_parse_*.  What a
  * record says is csrc/readwfmt.h (the bytes of readfile.reads_text_host):
  *   d_bases / d_off[n_reads + 1]   the bases back to back and their int64 offsets (never decreasing, none negative)
@@ -968,11 +925,12 @@ SFGPU_API int sfgpu_bgzw_member_sizes(sfgpu_bgzw* z, const uint32_t** d_sizes, u
  * virtual offsets, chunks, the linear index -- is stated once in csrc/baifmt.h; the kernels are csrc/bamsort.hip; the Python
  * statements are samfile.write_bam(sort="coordinate") and samfile.build_bai.
  *   open     an empty record store on the current device.
- *   collect  the arguments, checks, errors and `out` of sfgpu_sam_write_bgzf_q with SFGPU_SAMW_BAM, the handle in place of `z` (and no
+ *   collect  the batch, checks, errors and `out` of sfgpu_sam_write_bgzf with SFGPU_SAMW_BAM, the handle in place of `z` (and no
  *            chunk_bytes): the batch's records are formatted into one device segment owned by the handle and listed (key, address,
  *            length); out->n_chunks stays 0.  A batch that breaks a rule stores nothing.  The store holds fewer than 2^32 records:
  *            the call that would reach that returns SFGPU_ERR_RANGE and stores nothing.  Device memory: the records' bytes and
- *            20 bytes a record; nothing is spilled to the host.
+ *            20 bytes a record; nothing is spilled to the host.  The sort key, the bin and the index are read from the records' own
+ *            pos and CIGAR words: they follow the batch's alignment, and tags and posteriors change none of them.
  *   finish   `z` must track its members (sfgpu_bgzw_track_members, from its first write) and hold the file's header already.  The
  *            records are sorted stably by (uint32)refID << 32 | (uint32)(pos + 1), gathered into the sorted stream in pieces of
  *            piece_bytes (0 = 32 MiB, else 16 .. 2^30; rounded down to a multiple of 32 768, at least that) and written through `z`,
@@ -998,36 +956,7 @@ typedef struct {
     double index_ms;          /* host clock: the index kernels, their copies and the sink */
 } sfgpu_bamsort_result;
 SFGPU_API int sfgpu_bamsort_open(sfgpu_bamsort** out);
-SFGPU_API int sfgpu_bamsort_collect(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                    const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                    const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented);
-/* collect with the batch's gapped alignment, as sfgpu_sam_write_bgzf_a: the sort key and the index follow, since both are read from
- * the records' own pos and CIGAR words */
-SFGPU_API int sfgpu_bamsort_collect_a(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
-                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops);
-/* collect with the batch's NM / MD tags, as sfgpu_sam_write_bgzf_t (tags == NULL: sfgpu_bamsort_collect_a, byte for byte).  The sort
- * key, the bin and the index come from the record's own position and CIGAR, so tags change none of them. */
-SFGPU_API int sfgpu_bamsort_collect_t(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
-                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags);
-/* collect with the batch's posteriors, as sfgpu_sam_write_bgzf_p (post == NULL: sfgpu_bamsort_collect_t, byte for byte).  Sort key,
- * bin and index do not depend on the tag. */
-SFGPU_API int sfgpu_bamsort_collect_p(sfgpu_bamsort* b, const struct sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                      const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos,
-                                      const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
-                                      const sfgpu_samw_post* post);
+SFGPU_API int sfgpu_bamsort_collect(sfgpu_bamsort* b, const sfgpu_samw_batch* batch, sfgpu_samwrite_result* out, sfgpu_stream stream);
 SFGPU_API int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,
                                    void* user, sfgpu_bamsort_result* res, sfgpu_stream stream);
 SFGPU_API int sfgpu_bamsort_close(sfgpu_bamsort* b);

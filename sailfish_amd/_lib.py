@@ -287,14 +287,13 @@ class BiasStats(C.Structure):
                     n_corrected=self.n_corrected, n_uncorrected=self.n_uncorrected)
 
 
-# The alignment writers (sfgpu_sam_write_*, sfgpu_bamsort_collect*) take one batch: hits, hit offsets, n_reads, paired, reference
-# names and offsets, n_refs, read names and offsets, bases and offsets of either mate, read_index_base.  Behind the destination's own
-# arguments come the result and the stream; the _q entries add the qualities of either mate and `oriented`, the _a entries the
-# alignment (positions, operation offsets, operations) behind those.
-_SAMW_BATCH = [_P, _P, C.c_uint32, C.c_int, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_uint64]
-_SAMW_OUT = [C.POINTER(SamWriteResult), _P]
-_SAMW_QUAL = [_P, _P, C.c_int]
-_SAMW_ALN = [_P, _P, _P]
+# The batch of the alignment writers (sfgpu_sam_write_text, sfgpu_sam_write_bgzf, sfgpu_bamsort_collect): sfgpu_samw_batch, every
+# pointer a device address or None (a group left None is not written).
+class SamwBatch(C.Structure):
+    _fields_ = [("hits", _P), ("hit_off", _P), ("n_reads", C.c_uint32), ("paired", C.c_int), ("ref_names", _P), ("ref_name_off", _P),
+                ("n_refs", C.c_uint32), ("qnames", _P), ("qname_off", _P), ("seq1", _P), ("seq1_off", _P), ("seq2", _P), ("seq2_off", _P),
+                ("read_index_base", C.c_uint64), ("qual1", _P), ("qual2", _P), ("oriented", C.c_int), ("aln_pos", _P), ("aln_op_off", _P),
+                ("aln_ops", _P), ("tag_nm", _P), ("tag_md_off", _P), ("tag_md", _P), ("tag_zw_rec", _P), ("tag_zw_f32", _P)]
 
 
 class PosteriorStats(C.Structure):
@@ -321,19 +320,6 @@ class LibdetStats(C.Structure):
     def as_dict(self):
         return {k: [int(v) for v in getattr(self, k)] if k.endswith("_kind") else int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class SamwTags(C.Structure):
-    _fields_ = [("d_nm", C.c_void_p), ("d_md_off", C.c_void_p), ("d_md", C.c_void_p)]
-
-
-_SAMW_TAGS = [C.POINTER(SamwTags)]
-
-
-class SamwPost(C.Structure):
-    _fields_ = [("d_zw_rec", C.c_void_p), ("d_zw_f32", C.c_void_p)]
-
-
-_SAMW_POST = [C.POINTER(SamwPost)]
 
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
@@ -396,11 +382,7 @@ _SIGS = {
     "sfgpu_samc_finish": (C.c_int, [_P, C.POINTER(SamcInfo), _P]),
     "sfgpu_samc_emit": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(SamResult), _P]),
     "sfgpu_samc_close": (C.c_int, [_P]),
-    "sfgpu_sam_write_text": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT]),
-    "sfgpu_sam_write_text_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL]),
-    "sfgpu_sam_write_text_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
-    "sfgpu_sam_write_text_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
-    "sfgpu_sam_write_text_p": (C.c_int, [*_SAMW_BATCH, C.c_uint64, TEXT_SINK, _P, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
+    "sfgpu_sam_write_text": (C.c_int, [C.POINTER(SamwBatch), C.c_uint64, TEXT_SINK, _P, C.POINTER(SamWriteResult), _P]),
     "sfgpu_gz_open": (C.c_int, [C.POINTER(_P), TEXT_SINK, _P, C.c_uint64]),
     "sfgpu_gz_write_device": (C.c_int, [_P, _P, C.c_uint64, _P]),
     "sfgpu_gz_close": (C.c_int, [_P, C.POINTER(GzResult)]),
@@ -410,17 +392,10 @@ _SIGS = {
     "sfgpu_bgzw_track_members": (C.c_int, [_P]),
     "sfgpu_bgzw_member_sizes": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "sfgpu_bamsort_open": (C.c_int, [C.POINTER(_P)]),
-    "sfgpu_bamsort_collect": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL]),
-    "sfgpu_bamsort_collect_a": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
-    "sfgpu_bamsort_collect_t": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
-    "sfgpu_bamsort_collect_p": (C.c_int, [_P, *_SAMW_BATCH, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
+    "sfgpu_bamsort_collect": (C.c_int, [_P, C.POINTER(SamwBatch), C.POINTER(SamWriteResult), _P]),
     "sfgpu_bamsort_finish": (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, TEXT_SINK, _P, C.POINTER(BamsortResult), _P]),
     "sfgpu_bamsort_close": (C.c_int, [_P]),
-    "sfgpu_sam_write_bgzf": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT]),
-    "sfgpu_sam_write_bgzf_q": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL]),
-    "sfgpu_sam_write_bgzf_a": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN]),
-    "sfgpu_sam_write_bgzf_t": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS]),
-    "sfgpu_sam_write_bgzf_p": (C.c_int, [*_SAMW_BATCH, C.c_uint64, _P, C.c_int, *_SAMW_OUT, *_SAMW_QUAL, *_SAMW_ALN, *_SAMW_TAGS, *_SAMW_POST]),
+    "sfgpu_sam_write_bgzf": (C.c_int, [C.POINTER(SamwBatch), C.c_uint64, _P, C.c_int, C.POINTER(SamWriteResult), _P]),
     "sfgpu_reads_write_text": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(ReadWriteResult), _P]),
     "sfgpu_reads_write_bgzf": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, C.POINTER(ReadWriteResult), _P]),
     "sfgpu_eq_get_stats": (C.c_int, [_P, C.POINTER(EqStats)]),

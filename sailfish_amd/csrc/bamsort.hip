@@ -1,7 +1,7 @@
 // bamsort.hip -- the coordinate-sorted BAM file and its BAI index, written from the device: sfgpu_bamsort_open / _collect / _finish /
 // _close.  WHAT the file and the index say is baifmt.h (order, member cut, virtual offsets, chunks, linear index, layout); this file
 // keeps the records, orders them and builds the index.
-//   collect  the batch of sfgpu_sam_write_bgzf_q goes through samtext_write.hip's own checks, sizing, scan and k_format_units<BamFmt>
+//   collect  the batch of sfgpu_sam_write_bgzf goes through samtext_write.hip's own checks, sizing, scan and k_format_units<BamFmt>
 //            (bamsort.h) into ONE device segment per batch: nothing already stored is ever moved.  k_unit_records counts the records
 //            of every unit (the second record of a pair unit starts 4 + block_size behind the first), a scan numbers them, and
 //            k_append, one lane per unit, lists key, 64-bit address and length of each.
@@ -373,44 +373,11 @@ extern "C" int sfgpu_bamsort_open(sfgpu_bamsort** out) {
     return SFGPU_OK;
 }
 
-extern "C" int sfgpu_bamsort_collect_p(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
-                                       const sfgpu_samw_tags* tags, const sfgpu_samw_post* post) {
+extern "C" int sfgpu_bamsort_collect(sfgpu_bamsort* b, const sfgpu_samw_batch* batch, sfgpu_samwrite_result* out, sfgpu_stream stream) {
     SF_REQUIRE(b, SFGPU_ERR_INVALID, "sfgpu_bamsort_collect: null handle");
     SF_REQUIRE(!b->finished, SFGPU_ERR_STATE, "sfgpu_bamsort_collect: the store is finished");
-    return samw_collect_bam(b, samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                          d_seq2, d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post), out, stream);
-}
-
-extern "C" int sfgpu_bamsort_collect_t(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops,
-                                       const sfgpu_samw_tags* tags) {
-    return sfgpu_bamsort_collect_p(b, d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                   d_seq2, d_seq2_off, read_index_base, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
-}
-
-extern "C" int sfgpu_bamsort_collect_a(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                       const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                       const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                       const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                       const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented, const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    return sfgpu_bamsort_collect_t(b, d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                   d_seq2, d_seq2_off, read_index_base, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, nullptr);
-}
-
-extern "C" int sfgpu_bamsort_collect(sfgpu_bamsort* b, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                     const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                     const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                     const int64_t* d_seq2_off, uint64_t read_index_base, sfgpu_samwrite_result* out, sfgpu_stream stream,
-                                     const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
-    return sfgpu_bamsort_collect_a(b, d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                   d_seq2, d_seq2_off, read_index_base, out, stream, d_qual1, d_qual2, oriented, nullptr, nullptr, nullptr);
+    SF_REQUIRE(batch, SFGPU_ERR_INVALID, "sfgpu_bamsort_collect: null batch");
+    return samw_collect_bam(b, *batch, out, stream);
 }
 
 extern "C" int sfgpu_bamsort_finish(sfgpu_bamsort* b, sfgpu_bgzw* z, uint32_t n_refs, uint64_t piece_bytes, sfgpu_text_sink index_sink,

@@ -548,114 +548,26 @@ int sam_write(const char* who, const SamwArgs& in, uint64_t chunk_bytes, const D
 
 }  // namespace
 
-// ---- the entries: the widest of a family builds the batch, the others forward to it
-extern "C" int sfgpu_sam_write_text_p(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
-                                      const sfgpu_samw_post* post) {
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post);
+// ---- the entries: one per destination, each hands the batch to sam_write
+extern "C" int sfgpu_sam_write_text(const sfgpu_samw_batch* batch, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                                    sfgpu_samwrite_result* out, sfgpu_stream stream) {
+    SF_REQUIRE(batch, SFGPU_ERR_INVALID, "sfgpu_sam_write_text: null batch");
     Dest dest;
     dest.sink = sink; dest.user = user;
-    return sam_write("sfgpu_sam_write_text", batch, chunk_bytes, dest, out, stream);
+    return sam_write("sfgpu_sam_write_text", *batch, chunk_bytes, dest, out, stream);
 }
 
-extern "C" int sfgpu_sam_write_text_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
-    return sfgpu_sam_write_text_p(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_text_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    return sfgpu_sam_write_text_t(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_text_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
-    return sfgpu_sam_write_text_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, d_qual1, d_qual2, oriented, nullptr, nullptr, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_text(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+extern "C" int sfgpu_sam_write_bgzf(const sfgpu_samw_batch* batch, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
                                     sfgpu_samwrite_result* out, sfgpu_stream stream) {
-    return sfgpu_sam_write_text_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, sink, user, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_bgzf_p(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags,
-                                      const sfgpu_samw_post* post) {
     SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null BGZF handle");
     SF_REQUIRE(format == SFGPU_SAMW_TEXT || format == SFGPU_SAMW_BAM, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: unknown format");
-    const SamwArgs batch = samw_batch(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off, d_seq2,
-                                      d_seq2_off, read_index_base, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, post);
+    SF_REQUIRE(batch, SFGPU_ERR_INVALID, "sfgpu_sam_write_bgzf: null batch");
     Dest dest;
     dest.z = z; dest.format = format;
-    return sam_write("sfgpu_sam_write_bgzf", batch, chunk_bytes, dest, out, stream);
+    return sam_write("sfgpu_sam_write_bgzf", *batch, chunk_bytes, dest, out, stream);
 }
 
-extern "C" int sfgpu_sam_write_bgzf_t(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, const sfgpu_samw_tags* tags) {
-    return sfgpu_sam_write_bgzf_p(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, tags, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_bgzf_a(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented,
-                                      const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops) {
-    return sfgpu_sam_write_bgzf_t(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, d_aln_pos, d_aln_op_off, d_aln_ops, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_bgzf_q(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                      const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                      const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                      const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                      sfgpu_samwrite_result* out, sfgpu_stream stream, const uint8_t* d_qual1, const uint8_t* d_qual2, int oriented) {
-    return sfgpu_sam_write_bgzf_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, d_qual1, d_qual2, oriented, nullptr, nullptr, nullptr);
-}
-
-extern "C" int sfgpu_sam_write_bgzf(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, int paired,
-                                    const char* d_ref_names, const uint64_t* d_ref_name_off, uint32_t n_refs, const char* d_qnames,
-                                    const uint64_t* d_qname_off, const uint8_t* d_seq1, const int64_t* d_seq1_off, const uint8_t* d_seq2,
-                                    const int64_t* d_seq2_off, uint64_t read_index_base, uint64_t chunk_bytes, sfgpu_bgzw* z, int format,
-                                    sfgpu_samwrite_result* out, sfgpu_stream stream) {
-    return sfgpu_sam_write_bgzf_a(d_hits, d_hit_offsets, n_reads, paired, d_ref_names, d_ref_name_off, n_refs, d_qnames, d_qname_off, d_seq1, d_seq1_off,
-                                  d_seq2, d_seq2_off, read_index_base, chunk_bytes, z, format, out, stream, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
-}
-
-// bamsort.h: the batch's BAM records, checked, sized and formatted as for sfgpu_sam_write_bgzf_a, into `store`
+// bamsort.h: the batch's BAM records, checked, sized and formatted as for sfgpu_sam_write_bgzf, into `store`
 int sfgpu::samw_collect_bam(BamRecordStore* store, const SamwArgs& batch, sfgpu_samwrite_result* out, sfgpu_stream stream) {
     Dest dest;
     dest.store = store; dest.format = SFGPU_SAMW_BAM;

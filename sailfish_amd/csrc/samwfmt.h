@@ -216,37 +216,13 @@ SAMW_HD void samw_put_mid(const SamwLine& l, Put put) {
 }
 
 // ---- the arrays of one write call, and the serial statement over them ---------------------------------------------------------
-// What sfgpu_sam_write_text takes (include/sfgpu.h): names and SEQ as bytes back to back with n + 1 offsets; qname_off == nullptr
-// stands for r<read_index_base + r>, seq1_off / seq2_off == nullptr for '*'.  qual1 / qual2 (sfgpu_sam_write_text_q): the mate's
-// qualities at its base offsets, nullptr for '*'; oriented: 0x10 lines on the reference's strand.  (Appended with defaults: the
-// callers of the entries without them brace-initialise the rest.)
-struct SamwArgs {
-    const sfgpu_hit* hits;
-    const uint32_t* hit_off;
-    uint32_t n_reads;
-    int paired;
-    const char* ref_names;
-    const uint64_t* ref_name_off;
-    uint32_t n_refs;
-    const char* qnames;
-    const uint64_t* qname_off;
-    const uint8_t* seq1;
-    const int64_t* seq1_off;
-    const uint8_t* seq2;
-    const int64_t* seq2_off;
-    uint64_t read_index_base;
-    const uint8_t* qual1 = nullptr;
-    const uint8_t* qual2 = nullptr;
-    int oriented = 0;
-    const int32_t* aln_pos = nullptr;        // [2 * records] sfgpu_hits_align_gapped's d_pos, or nullptr: no alignment is given
-    const uint64_t* aln_op_off = nullptr;    // [2 * records + 1]
-    const uint32_t* aln_ops = nullptr;
-    const uint32_t* tag_nm = nullptr;        // [2 * records] sfgpu_hits_md_tags' d_nm, or nullptr: no tags are written
-    const uint64_t* tag_md_off = nullptr;    // [2 * records + 1]
-    const uint8_t* tag_md = nullptr;
-    const uint32_t* tag_zw_rec = nullptr;    // [records] sfgpu_hits_posteriors' d_rec, or nullptr: no ZW is written
-    const float* tag_zw_f32 = nullptr;       // [records] its d_f32: the value of a BAM record's ZW
-};
+// The batch of the writer entries, sfgpu_samw_batch (include/sfgpu.h, where each field group is described): names and SEQ as
+// bytes back to back with n + 1 offsets, the qualities, the alignment, the tags and the posteriors, each group nullptr when not
+// given.  C++ callers brace-initialise the leading fields they give (tests/*_harness.cpp) and leave the rest to the language's
+// zeroing, which is what "not given" means for every group; the C struct has no default member initialisers to say so, so the
+// -Wextra warning about exactly those omitted fields is off for the files that include this one.
+using SamwArgs = sfgpu_samw_batch;
+#pragma GCC diagnostic ignored "-Wmissing-field-initializers"
 
 // The lines of a record WITH the batch's alignment, where one is given.  `hidx` is the record's index in a.hits: its slots are
 // 2 * hidx and 2 * hidx + 1 (h itself may be a copy of the record, as in the kernels).

@@ -1102,10 +1102,10 @@ class SamDeviceWriter:
     write(tags=): the batch's NM / MD tags as hits.md_tags returns them (nm, md_off, md: device tensors, two slots per record, computed
     over the same `alignments`); a mapped line then ends NM:i:<nm>, MD:Z:<md>, NH:i:<the read's record count> (a BAM record: NM and NH
     in the smallest integer type that holds them, MD as a Z string), in every format, sorted or not.  The writer must be oriented and
-    the bases given, else ValueError.  Without `tags` the calls and the bytes are what they were.
+    the bases given, else ValueError.  Without `tags` the bytes are what they were.
     write(posteriors=): what hits.posteriors returned for the batch's records (p, rec, f32, ...: device tensors, one entry per record);
     a mapped line then ends, behind the tags where there are any, ZW:f:<"%g" of its record's posterior probability> (a BAM record:
-    ZW as a float), in every format, sorted or not.  Without `posteriors` the calls and the bytes are what they were."""
+    ZW as a float), in every format, sorted or not.  Without `posteriors` the bytes are what they were."""
 
     def __init__(self, path_or_file, names, ref_len, paired, *, chunk_bytes=0, format="sam", oriented=False, sort=None, index=None):
         from . import _lib, quantfile
@@ -1164,9 +1164,8 @@ class SamDeviceWriter:
         return b.to(dev).contiguous(), o.to(dev).contiguous()
 
     def _batch_args(self, hits, offsets, read_names, seqs, quals, alignments):
-        """write()'s arguments as the entries take them: (batch, extra, aln, keepalive) -- the batch of _lib._SAMW_BATCH with chunk_bytes
-        behind it, the qualities and `oriented`, the alignment, and the tensors whose addresses those three hold: the caller keeps
-        `keepalive` referenced until the entry has returned."""
+        """write()'s arguments as the entries take them: (batch, keepalive) -- the _lib.SamwBatch and the tensors whose addresses it
+        holds: the caller keeps `keepalive` referenced until the entry has returned."""
         import torch
 
         from . import _lib, quantfile
@@ -1210,10 +1209,10 @@ class SamDeviceWriter:
                     raise ValueError(f"{t.numel()} quality bytes for {s[m][0].numel()} bases")
                 ql[m] = t if t.numel() else torch.zeros(1, dtype=torch.uint8, device=dev)     # no base at all: still "given"
         p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
-        batch = (p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs, p(q[0]), p(q[1]),
-                 p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads, self.chunk_bytes)
-        extra = (None if ql[0] is None else _lib.ptr(ql[0]), None if ql[1] is None else _lib.ptr(ql[1]), int(self.oriented))
-        aln, aln_t = (None, None, None), None
+        batch = _lib.SamwBatch(p(d_hits), _lib.ptr(d_off), n, int(self.paired), p(self._d_names[0]), _lib.ptr(self._d_names[1]), self._n_refs,
+                               p(q[0]), p(q[1]), p(s[0][0]), p(s[0][1]), p(s[1][0]), p(s[1][1]), self.n_reads,
+                               None if ql[0] is None else _lib.ptr(ql[0]), None if ql[1] is None else _lib.ptr(ql[1]), int(self.oriented))
+        aln_t = None
         if alignments is not None:
             a_pos, a_off, a_ops = (alignments[i].to(dev).contiguous() for i in (0, 2, 3))
             if a_pos.element_size() != 4 or a_off.element_size() != 8 or a_ops.element_size() != 4:
@@ -1225,11 +1224,12 @@ class SamDeviceWriter:
                 a_ops = torch.zeros(1, dtype=torch.int32, device=dev)          # no operation at all: still "given"
             if not a_pos.numel():
                 a_pos = torch.zeros(1, dtype=torch.int32, device=dev)
-            aln, aln_t = (_lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops)), (a_pos, a_off, a_ops)
-        return batch, extra, aln, (d_hits, d_off, self._d_names, q, s, ql, aln_t)
+            batch.aln_pos, batch.aln_op_off, batch.aln_ops = _lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops)
+            aln_t = (a_pos, a_off, a_ops)
+        return batch, (d_hits, d_off, self._d_names, q, s, ql, aln_t)
 
-    def _tag_args(self, tags, hits, seqs):
-        """write()'s tags as the _t entries take them: (the sfgpu_samw_tags struct, the tensors whose addresses it holds)"""
+    def _tag_args(self, batch, tags, hits, seqs):
+        """write()'s tags into the batch's tag fields; returns the tensors whose addresses they hold"""
         import torch
 
         from . import _lib
@@ -1248,11 +1248,12 @@ class SamDeviceWriter:
             t_md = torch.zeros(1, dtype=torch.uint8, device=dev)               # no MD byte at all: still "given"
         if not t_nm.numel():
             t_nm = torch.zeros(1, dtype=torch.int32, device=dev)
-        return _lib.SamwTags(_lib.ptr(t_nm), _lib.ptr(t_off), _lib.ptr(t_md)), (t_nm, t_off, t_md)
+        batch.tag_nm, batch.tag_md_off, batch.tag_md = _lib.ptr(t_nm), _lib.ptr(t_off), _lib.ptr(t_md)
+        return t_nm, t_off, t_md
 
     @staticmethod
-    def _post_args(posteriors, hits):
-        """write()'s posteriors as the _p entries take them: (the sfgpu_samw_post struct, the tensors whose addresses it holds)"""
+    def _post_args(batch, posteriors, hits):
+        """write()'s posteriors into the batch's ZW fields; returns the tensors whose addresses they hold"""
         import torch
 
         from . import _lib
@@ -1267,7 +1268,8 @@ class SamDeviceWriter:
             raise ValueError(f"posteriors of {z_rec.numel()} records for {n_rec} records")
         if not n_rec:                                                                  # no record at all: still "given"
             z_rec, z_f32 = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
-        return _lib.SamwPost(_lib.ptr(z_rec), _lib.ptr(z_f32)), (z_rec, z_f32)
+        batch.tag_zw_rec, batch.tag_zw_f32 = _lib.ptr(z_rec), _lib.ptr(z_f32)
+        return z_rec, z_f32
 
     def write(self, hits, offsets, *, read_names=None, seqs=None, quals=None, alignments=None, tags=None, posteriors=None):
         import torch
@@ -1276,18 +1278,12 @@ class SamDeviceWriter:
         if self._f is None:
             raise ValueError("the SAM writer is closed")
         dev = hits.device
-        batch, extra, aln, keepalive = self._batch_args(hits, offsets, read_names, seqs, quals, alignments)
-        n = batch[2]
-        text_entry, collect_entry, bgzf_entry, last = self._L.sfgpu_sam_write_text_a, self._L.sfgpu_bamsort_collect_a, self._L.sfgpu_sam_write_bgzf_a, ()
-        if tags is not None:                       # the _t entries; without tags the calls are the ones they were
-            t_struct, t_keep = self._tag_args(tags, hits, seqs)
-            keepalive = (keepalive, t_struct, t_keep)
-            text_entry, collect_entry, bgzf_entry, last = self._L.sfgpu_sam_write_text_t, self._L.sfgpu_bamsort_collect_t, self._L.sfgpu_sam_write_bgzf_t, (C.byref(t_struct),)
-        if posteriors is not None:                 # the _p entries: the tags' place holds them or NULL
-            z_struct, z_keep = self._post_args(posteriors, hits)
-            keepalive = (keepalive, z_struct, z_keep)
-            text_entry, collect_entry, bgzf_entry = self._L.sfgpu_sam_write_text_p, self._L.sfgpu_bamsort_collect_p, self._L.sfgpu_sam_write_bgzf_p
-            last = (last[0] if last else None, C.byref(z_struct))
+        batch, keepalive = self._batch_args(hits, offsets, read_names, seqs, quals, alignments)
+        n = batch.n_reads
+        if tags is not None:
+            keepalive = (keepalive, self._tag_args(batch, tags, hits, seqs))
+        if posteriors is not None:
+            keepalive = (keepalive, self._post_args(batch, posteriors, hits))
         raised = []
 
         def sink(addr, nb, _user):
@@ -1301,14 +1297,15 @@ class SamDeviceWriter:
         res = _lib.SamWriteResult()
         with torch.cuda.device(dev):
             if self._z is None:
-                rc = text_entry(*batch, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
+                rc = self._L.sfgpu_sam_write_text(C.byref(batch), self.chunk_bytes, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
             elif self._sort:
                 self._write_head(dev)
                 self._open_store()
-                rc = collect_entry(self._b, *batch[:-1], C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
+                rc = self._L.sfgpu_bamsort_collect(self._b, C.byref(batch), C.byref(res), _lib.current_stream_ptr())
             else:
                 self._write_head(dev)
-                rc = bgzf_entry(*batch, self._z._h, _SAMW_FORMAT[self.format], C.byref(res), _lib.current_stream_ptr(), *extra, *aln, *last)
+                rc = self._L.sfgpu_sam_write_bgzf(C.byref(batch), self.chunk_bytes, self._z._h, _SAMW_FORMAT[self.format], C.byref(res),
+                                                  _lib.current_stream_ptr())
         sunk = raised if self._z is None else self._z._raised      # what this call's sink raised: the encoder's, when it does the sinking
         if sunk:
             raise sunk.pop(0)

@@ -34,7 +34,7 @@ int64_t agh_align(const char* tseq, const uint64_t* tseq_off, const uint32_t* tl
     return (int64_t)o.size();
 }
 
-// the arrays of sfgpu_sam_write_text_a / sfgpu_sam_write_bgzf_a (host pointers; QNAME r<index>, no qualities).  out[0 .. 8):
+// the arrays of sfgpu_sam_write_text / sfgpu_sam_write_bgzf (host pointers; QNAME r<index>, no qualities).  out[0 .. 8):
 // n_bytes, n_lines, n_units, max_unit_bytes, error_kind, error_read, error_record, 1 when the per-unit sizes disagree; bytes !=
 // nullptr (room for the n_bytes a first call gave): the text or the records.  -> the error kind
 int agh_write(int bam, const void* hits, const uint32_t* hit_off, uint32_t n_reads, int paired, const char* ref, const uint64_t* ref_off, uint32_t n_refs,

@@ -1,4 +1,4 @@
-// samqual_harness.cpp -- csrc/samwfmt.h and csrc/bamwfmt.h alone, as plain C++, with the inputs sfgpu_sam_write_text_q adds: the
+// samqual_harness.cpp -- csrc/samwfmt.h and csrc/bamwfmt.h alone, as plain C++, with the inputs sfgpu_sam_write_text adds: the
 // qualities of either mate and the orientation.  The serial writers (samw_serial, bamw_serial) behind one C call for
 // tests/test_samqual_cpu.py, which compares their bytes with samfile._sam_text(..., quals=, oriented=) and sam_to_bam of it, and --
 // with -DSAMQ_HARNESS_MAIN -- a stand-alone program over case files for the sanitizer run.  The per-unit sizes the kernels take
@@ -51,7 +51,7 @@ SamwArgs args_of(const void* hits, const uint32_t* hit_off, uint32_t n_reads, in
 
 extern "C" {
 
-// the arrays of sfgpu_sam_write_text_q (host pointers); k1 / k2: the qualities at the offsets of s1 / s2, nullptr for none.
+// the arrays of sfgpu_sam_write_text (host pointers); k1 / k2: the qualities at the offsets of s1 / s2, nullptr for none.
 // Returns -1 for qualities of a mate whose bases are not given (the entry's SFGPU_ERR_INVALID), else the error kind.
 int samq_harness(int bam, const void* hits, const uint32_t* hit_off, uint32_t n_reads, int paired, const char* ref, const uint64_t* ref_off,
                  uint32_t n_refs, const char* q, const uint64_t* q_off, const uint8_t* s1, const int64_t* s1_off, const uint8_t* s2,

@@ -39,6 +39,29 @@ def test_header_is_plain_c(built, tmp_path):
                            "-o", str(tmp_path / "t.o")])
 
 
+def test_samw_batch_layout_matches_ctypes(built, tmp_path):
+    """sfgpu_samw_batch as gcc lays it out and its ctypes mirror _lib.SamwBatch: the same size, the same offset for every field"""
+    from sailfish_amd import _lib
+    names = [n for n, _ in _lib.SamwBatch._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "sfgpu.h"\nint main(void) {\n'
+                   '    printf("%zu\\n", sizeof(sfgpu_samw_batch));\n'
+                   + "".join(f'    printf("%zu\\n", offsetof(sfgpu_samw_batch, {n}));\n' for n in names) + "    return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    assert got == [C.sizeof(_lib.SamwBatch)] + [getattr(_lib.SamwBatch, n).offset for n in names]
+
+
+def test_sam_write_text_refuses_a_null_batch(built):
+    """batch == NULL is SFGPU_ERR_INVALID, before anything touches a device"""
+    from sailfish_amd import _lib
+    L = _lib.lib()
+    res = _lib.SamWriteResult()
+    assert L.sfgpu_sam_write_text(None, 0, _lib.TEXT_SINK(0), None, C.byref(res), None) == _lib.ERR_INVALID
+    assert b"batch" in L.sfgpu_last_error()
+
+
 def test_library_links_only_hip_runtime(built):
     so = os.path.join(ROOT, "sailfish_amd", "csrc", "libsfgpu.so")
     out = subprocess.check_output(["readelf", "-d", so], text=True)

@@ -136,21 +136,9 @@ def _tags_device(tags, gpu):
     return _t64(tags[0], gpu, np.int32), _t64(tags[1], gpu, np.int64), _t64(tags[2], gpu, np.uint8)
 
 
-class _ThroughT:
-    """the library with every _a writer entry replaced by its _t entry given NULL tags"""
-    def __init__(self, L):
-        self._L = L
-
-    def __getattr__(self, name):
-        if name in ("sfgpu_sam_write_text_a", "sfgpu_sam_write_bgzf_a", "sfgpu_bamsort_collect_a"):
-            entry = getattr(self._L, name[:-1] + "t")
-            return lambda *args: entry(*args, None)
-        return getattr(self._L, name)
-
-
-def _written(case, aln, tags, gpu, fmt, sort=None, chunk_bytes=0, cuts=None, read_names=None, through_t=False, say_none=False):
+def _written(case, aln, tags, gpu, fmt, sort=None, chunk_bytes=0, cuts=None, read_names=None, say_none=False):
     """the case through an oriented SamDeviceWriter in one batch, or in the batches cut at the reads `cuts` -> (the file's bytes, the
-    index's).  say_none: write(tags=None), said aloud; through_t: the _t entries given NULL"""
+    index's).  say_none: write(tags=None), said aloud"""
     import io
     from sailfish_amd import samfile
     from test_gpu_aligng import corpus as AG
@@ -158,8 +146,6 @@ def _written(case, aln, tags, gpu, fmt, sort=None, chunk_bytes=0, cuts=None, rea
     paired = AG.is_paired(case)
     f, x = io.BytesIO(), io.BytesIO()
     w = samfile.SamDeviceWriter(f, names, ref_len, paired, format=fmt, oriented=True, sort=sort, chunk_bytes=chunk_bytes, index=x if sort else None)
-    if through_t:
-        w._L = _ThroughT(w._L)
     edges = [0] + list(cuts or []) + [len(case["r1"])]
     for a, b in zip(edges[:-1], edges[1:]):
         h0, h1 = int(case["off"][a]), int(case["off"][b])
@@ -193,8 +179,8 @@ def _host_text(case, aln, tags, read_names=None):
 def test_writers_write_the_tags(gpu, tmp_path, name):
     """"sam", "sam.gz", "bam" and the sorted "bam" with its index: byte-equal (the compressed ones inflated) to _sam_text(tags=),
     sam_to_bam of it and write_bam(sort="coordinate", tags=); the index is build_bai of the device's own file and fetch returns the
-    records; a small chunk_bytes and three batches change nothing; with tags=None, through the _t entries given NULL and through the
-    untouched _a entries, every file is the one written without the argument"""
+    records; a small chunk_bytes and three batches change nothing; with tags=None every file is the one written without the
+    argument"""
     import gzip
     from sailfish_amd import samfile
     from test_gpu_aligng import corpus as AG
@@ -226,7 +212,7 @@ def test_writers_write_the_tags(gpu, tmp_path, name):
     plain = _host_text(case, aln, None)
     for fmt, sort in (("sam", None), ("sam.gz", None), ("bam", None), ("bam", "coordinate")):
         before = _written(case, aln, None, gpu, fmt, sort=sort)
-        assert _written(case, aln, None, gpu, fmt, sort=sort, say_none=True) == before and _written(case, aln, None, gpu, fmt, sort=sort, through_t=True) == before, (fmt, sort)
+        assert _written(case, aln, None, gpu, fmt, sort=sort, say_none=True) == before, (fmt, sort)
         if sort is None:
             body = before[0] if fmt == "sam" else gzip.decompress(before[0])
             assert body == (samfile.sam_to_bam(plain) if fmt == "bam" else plain), fmt
@@ -273,16 +259,21 @@ def test_what_the_writer_refuses_with_tags(gpu):
     with pytest.raises(ValueError, match="slots"):
         w.write(d_hits, d_off, seqs=r1, tags=_tags_device(corpus.writable("runs_se")[2], gpu))
     # the raw entry
-    batch, extra, a3, keep = w._batch_args(d_hits, d_off, None, r1, None, None)
+    batch, keep = w._batch_args(d_hits, d_off, None, r1, None, None)
     sink = _lib.TEXT_SINK(lambda addr, nb, user: 0)
     res = _lib.SamWriteResult()
-    full = _lib.SamwTags(*[_lib.ptr(t) for t in tags])
-    call = lambda b, t: _lib.lib().sfgpu_sam_write_text_t(*b, sink, None, C.byref(res), _lib.current_stream_ptr(), *extra, *a3, None if t is None else C.byref(t))
-    no_bases = batch[:9] + (None, None) + batch[11:]
-    assert call(no_bases, full) == _lib.ERR_INVALID and b"bases" in _lib.lib().sfgpu_last_error()
-    for part in (_lib.SamwTags(None, full.d_md_off, full.d_md), _lib.SamwTags(full.d_nm, None, full.d_md), _lib.SamwTags(full.d_nm, full.d_md_off, None)):
-        assert call(batch, part) == _lib.ERR_INVALID and b"tags" in _lib.lib().sfgpu_last_error()
-    assert call(no_bases, None) == _lib.OK
+    full = tuple(_lib.ptr(t) for t in tags)
+
+    def call(no_bases, t):
+        b = _lib.SamwBatch.from_buffer_copy(batch)
+        if no_bases:
+            b.seq1, b.seq1_off = None, None
+        b.tag_nm, b.tag_md_off, b.tag_md = t
+        return _lib.lib().sfgpu_sam_write_text(C.byref(b), w.chunk_bytes, sink, None, C.byref(res), _lib.current_stream_ptr())
+    assert call(True, full) == _lib.ERR_INVALID and b"bases" in _lib.lib().sfgpu_last_error()
+    for part in ((None, full[1], full[2]), (full[0], None, full[2]), (full[0], full[1], None)):
+        assert call(False, part) == _lib.ERR_INVALID and b"tags" in _lib.lib().sfgpu_last_error()
+    assert call(True, (None, None, None)) == _lib.OK
     w.close()
     w = samfile.SamDeviceWriter(io.BytesIO(), names, ref_len, False)
     with pytest.raises(ValueError, match="oriented"):

@@ -132,22 +132,7 @@ def test_shapes_and_errors_of_the_contract(gpu):
 
 # ---- the writers take the posteriors -----------------------------------------------------------------------------------------------
 
-class _ThroughP:
-    """the library with every _t writer entry replaced by its _p entry given NULL posteriors"""
-    def __init__(self, L):
-        self._L = L
-
-    def __getattr__(self, name):
-        if name in ("sfgpu_sam_write_text_t", "sfgpu_sam_write_bgzf_t", "sfgpu_bamsort_collect_t"):
-            entry = getattr(self._L, name[:-1] + "p")
-            return lambda *args: entry(*args, None)
-        if name in ("sfgpu_sam_write_text_a", "sfgpu_sam_write_bgzf_a", "sfgpu_bamsort_collect_a"):
-            entry = getattr(self._L, name[:-1] + "p")
-            return lambda *args: entry(*args, None, None)
-        return getattr(self._L, name)
-
-
-def _written(case, gpu, fmt, *, aln=None, tags=None, post=None, quals=None, oriented=True, sort=None, read_names=None, through_p=False):
+def _written(case, gpu, fmt, *, aln=None, tags=None, post=None, quals=None, oriented=True, sort=None, read_names=None):
     """the case through a SamDeviceWriter in one batch -> (the file's bytes, the index's)"""
     import torch
     import aligng_corpus as AG
@@ -156,8 +141,6 @@ def _written(case, gpu, fmt, *, aln=None, tags=None, post=None, quals=None, orie
     paired = AG.is_paired(case)
     f, x = io.BytesIO(), io.BytesIO()
     w = samfile.SamDeviceWriter(f, names, ref_len, paired, format=fmt, oriented=oriented, sort=sort, index=x if sort else None)
-    if through_p:
-        w._L = _ThroughP(w._L)
     d_hits, d_off = _device(case, gpu)
     r1, r2 = _reads(case, gpu)
     kw = {}
@@ -200,8 +183,7 @@ def _options(name):
 def test_writers_write_the_posteriors(gpu, name):
     """about 40 reads, single-end and paired: "sam", "sam.gz", "bam" and the sorted "bam" with its index are byte-equal (the compressed
     ones inflated) to _sam_text(posteriors=), sam_to_bam of it and sort_bam_stream of that, and the index is build_bai of the device's
-    own file, with the bins of the file without the tag -- with no other option, with orientation, qualities and tags, and with a gapped alignment and tags; every _p entry given
-    NULL writes what its _t entry (and, with no tags either, its _a entry) writes"""
+    own file, with the bins of the file without the tag -- with no other option, with orientation, qualities and tags, and with a gapped alignment and tags"""
     from sailfish_amd import samfile
     case, _, _, post = corpus.writable(name)
     assert 30 <= len(case["r1"]) <= corpus.WRITER_READS and {len(t) for t in corpus.tokens(post[0])} >= {1, 3, 8, 11}
@@ -215,8 +197,6 @@ def test_writers_write_the_posteriors(gpu, name):
         got, bai = _written(case, gpu, "bam", post=post, sort="coordinate", **kw)
         assert gzip.decompress(got) == samfile.sort_bam_stream(bam), kw.keys()
         assert bai == samfile.build_bai(got) and _bai_shape(bai) == _bai_shape(_written(case, gpu, "bam", sort="coordinate", **kw)[1])
-        for fmt, sort in (("sam", None), ("sam.gz", None), ("bam", None), ("bam", "coordinate")):
-            assert _written(case, gpu, fmt, sort=sort, through_p=True, **kw) == _written(case, gpu, fmt, sort=sort, **kw), (fmt, sort, kw.keys())
 
 
 @pytest.mark.parametrize("token", corpus.TOKENS_AT_THE_EDGE)
@@ -237,9 +217,10 @@ def test_a_tile_edge_on_every_byte_of_the_zw_field(gpu, token):
 
 def test_what_the_writer_refuses_with_posteriors(gpu):
     """posteriors of another batch, or not what hits.posteriors returns: ValueError / TypeError; the raw entry with one of the two
-    pointers: SFGPU_ERR_INVALID"""
+    pointers, and every entry with a NULL batch: SFGPU_ERR_INVALID"""
+    import torch
     import aligng_corpus as AG
-    from sailfish_amd import _lib
+    from sailfish_amd import _lib, gzfile
     from sailfish_amd import samfile
     case, _, _, post = corpus.writable("runs_se")
     names, ref_len, _ = AG.sam_inputs(case)
@@ -253,13 +234,23 @@ def test_what_the_writer_refuses_with_posteriors(gpu):
         w.write(d_hits, d_off, seqs=r1, posteriors=(d_post[0], d_post[0], d_post[2]))
     with pytest.raises(TypeError, match="posteriors"):
         w.write(d_hits, d_off, seqs=r1, posteriors=d_post[:1])
-    batch, extra, a3, keep = w._batch_args(d_hits, d_off, None, r1, None, None)
+    batch, keep = w._batch_args(d_hits, d_off, None, r1, None, None)
     sink = _lib.TEXT_SINK(lambda addr, nb, user: 0)
     res = _lib.SamWriteResult()
-    for part in (_lib.SamwPost(_lib.ptr(d_post[1]), None), _lib.SamwPost(None, _lib.ptr(d_post[2]))):
-        rc = _lib.lib().sfgpu_sam_write_text_p(*batch, sink, None, C.byref(res), _lib.current_stream_ptr(), *extra, *a3, None, C.byref(part))
-        assert rc == _lib.ERR_INVALID and b"posteriors" in _lib.lib().sfgpu_last_error()
+    L = _lib.lib()
+    for part in ((_lib.ptr(d_post[1]), None), (None, _lib.ptr(d_post[2]))):
+        batch.tag_zw_rec, batch.tag_zw_f32 = part
+        rc = L.sfgpu_sam_write_text(C.byref(batch), w.chunk_bytes, sink, None, C.byref(res), _lib.current_stream_ptr())
+        assert rc == _lib.ERR_INVALID and b"posteriors" in L.sfgpu_last_error()
     w.close()
+    z = gzfile.BgzfDeviceWriter(io.BytesIO())
+    z._open(torch.device(gpu))
+    assert L.sfgpu_sam_write_bgzf(None, 0, z._h, 1, C.byref(res), _lib.current_stream_ptr()) == _lib.ERR_INVALID and b"batch" in L.sfgpu_last_error()
+    z.close()
+    b = C.c_void_p()
+    _lib.check(L.sfgpu_bamsort_open(C.byref(b)))
+    assert L.sfgpu_bamsort_collect(b, None, C.byref(res), _lib.current_stream_ptr()) == _lib.ERR_INVALID and b"batch" in L.sfgpu_last_error()
+    _lib.check(L.sfgpu_bamsort_close(b))
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,8 @@
-"""Qualities and orientation in the device SAM / BAM writer (sfgpu_sam_write_text_q, sfgpu_sam_write_bgzf_q;
+"""Qualities and orientation in the device SAM / BAM writer (sfgpu_sam_write_text, sfgpu_sam_write_bgzf;
 sailfish_amd/csrc/samtext_write.hip; samfile.SamDeviceWriter(oriented=).write(quals=); mappings_oriented= of mapper.quantify_files /
 quantify_reads).  The expected bytes are always the host statement's -- samfile._sam_text(..., quals=, oriented=), sam_to_bam of it
-for BAM -- which tests/test_samqual_cpu.py judges on its own; without qualities and orientation they are also what the entries
-without those arguments write."""
+for BAM -- which tests/test_samqual_cpu.py judges on its own; without qualities and orientation they are also what a batch
+without those fields writes."""
 import ctypes as C
 import gzip
 import io
@@ -22,16 +22,17 @@ pytestmark = pytest.mark.gpu
 
 def _call(case, gpu, quals, oriented, *, fmt=None, old=False, chunk_bytes=0, base=0, null_sink=False):
     """one C call over the case's arrays -> (status, result dict, chunks, inflated bytes or None).  fmt None: the text entry with a
-    sink that keeps every chunk; "sam.gz" / "bam": the BGZF entry into an encoder of its own.  old: the entry without the new
-    arguments (quals and oriented must then be off)."""
+    sink that keeps every chunk; "sam.gz" / "bam": the BGZF entry into an encoder of its own.  old: the batch without its quality
+    fields (quals and oriented must then be off)."""
     from sailfish_amd import _lib, gzfile
     L = _lib.lib()
     d = {k: _t(v, gpu) for k, v in corpus.arrays(case).items()}
     p = lambda t: _lib.ptr(t) if t is not None and t.numel() else None
-    batch = (p(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(case["paired"]), p(d["ref"]), _lib.ptr(d["ref_off"]),
-             len(case["names"]), p(d["q"]), p(d["q_off"]), p(d["s1"]), p(d["s1_off"]), p(d["s2"]), p(d["s2_off"]), base, chunk_bytes)
+    batch = _lib.SamwBatch(p(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(case["paired"]), p(d["ref"]), _lib.ptr(d["ref_off"]),
+                           len(case["names"]), p(d["q"]), p(d["q_off"]), p(d["s1"]), p(d["s1_off"]), p(d["s2"]), p(d["s2_off"]), base)
     assert not (old and (quals or oriented))
-    extra = () if old else (p(d["k1"]) if quals else None, p(d["k2"]) if quals else None, int(oriented))
+    if not old:
+        batch.qual1, batch.qual2, batch.oriented = p(d["k1"]) if quals else None, p(d["k2"]) if quals else None, int(oriented)
     chunks = []
 
     def sink(addr, n, _user):
@@ -41,14 +42,13 @@ def _call(case, gpu, quals, oriented, *, fmt=None, old=False, chunk_bytes=0, bas
     res = _lib.SamWriteResult()
     with torch.cuda.device(gpu):
         if fmt is None:
-            entry = L.sfgpu_sam_write_text if old else L.sfgpu_sam_write_text_q
-            rc = entry(*batch, _lib.TEXT_SINK(0) if null_sink else _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr(), *extra)
+            rc = L.sfgpu_sam_write_text(C.byref(batch), chunk_bytes, _lib.TEXT_SINK(0) if null_sink else _lib.TEXT_SINK(sink), None, C.byref(res),
+                                        _lib.current_stream_ptr())
             return rc, res.as_dict(), chunks, None
         out = io.BytesIO()
         z = gzfile.BgzfDeviceWriter(out)
         z._open(torch.device(gpu))
-        entry = L.sfgpu_sam_write_bgzf if old else L.sfgpu_sam_write_bgzf_q
-        rc = entry(*batch, z._h, 1 if fmt == "bam" else 0, C.byref(res), _lib.current_stream_ptr(), *extra)
+        rc = L.sfgpu_sam_write_bgzf(C.byref(batch), chunk_bytes, z._h, 1 if fmt == "bam" else 0, C.byref(res), _lib.current_stream_ptr())
         z.close()
     return rc, res.as_dict(), chunks, gzip.decompress(out.getvalue())
 
@@ -177,9 +177,9 @@ def test_quality_bytes_that_cannot_be_written(gpu, paired):
     d = {k: _t(v, gpu) for k, v in corpus.arrays(case).items()}
     res = _lib.SamWriteResult()
     with torch.cuda.device(gpu):
-        rc = _lib.lib().sfgpu_sam_write_text_q(_lib.ptr(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(paired), _lib.ptr(d["ref"]),
-                                               _lib.ptr(d["ref_off"]), len(case["names"]), None, None, None, None, None, None, 0, 0, _lib.TEXT_SINK(0),
-                                               None, C.byref(res), _lib.current_stream_ptr(), _lib.ptr(d["k1"]), None, 1)
+        batch = _lib.SamwBatch(_lib.ptr(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(paired), _lib.ptr(d["ref"]),
+                               _lib.ptr(d["ref_off"]), len(case["names"]), qual1=_lib.ptr(d["k1"]), oriented=1)
+        rc = _lib.lib().sfgpu_sam_write_text(C.byref(batch), 0, _lib.TEXT_SINK(0), None, C.byref(res), _lib.current_stream_ptr())
     assert rc == _lib.ERR_INVALID
     # the writer names the read counted over the batches
     bad, read, record, kind = corpus.failing(paired)[0]

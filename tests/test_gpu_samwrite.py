@@ -35,11 +35,12 @@ def _collect(case, gpu, chunk_bytes=0, base=0, refuse_at=None, null_sink=False, 
         return 1 if refuse_at is not None and len(chunks) == refuse_at else 0
 
     res = _lib.SamWriteResult()
+    batch = _lib.SamwBatch(p(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(case["paired"]), p(d["ref"]), _lib.ptr(d["ref_off"]),
+                           len(case["names"]) if n_refs is None else n_refs, p(d["q"]), p(d["q_off"]), p(d["s1"]), p(d["s1_off"]), p(d["s2"]),
+                           p(d["s2_off"]), base)
     with torch.cuda.device(gpu):
-        rc = _lib.lib().sfgpu_sam_write_text(p(d["hits"]), _lib.ptr(d["offsets"]), d["offsets"].numel() - 1, int(case["paired"]), p(d["ref"]),
-                                             _lib.ptr(d["ref_off"]), len(case["names"]) if n_refs is None else n_refs, p(d["q"]), p(d["q_off"]),
-                                             p(d["s1"]), p(d["s1_off"]), p(d["s2"]), p(d["s2_off"]), base, chunk_bytes,
-                                             _lib.TEXT_SINK(0) if null_sink else _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
+        rc = _lib.lib().sfgpu_sam_write_text(C.byref(batch), chunk_bytes, _lib.TEXT_SINK(0) if null_sink else _lib.TEXT_SINK(sink), None, C.byref(res),
+                                             _lib.current_stream_ptr())
     return rc, res.as_dict(), chunks
 
 

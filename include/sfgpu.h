@@ -1045,7 +1045,10 @@ typedef struct {
     uint64_t C;               /* eqVec().size() */
     const uint32_t* d_rowptr; /* C+1 */
     const uint32_t* d_ids;    /* rowptr[C] */
-    const uint64_t* d_counts; /* C; every count must be < 2^31 (SFGPU_ERR_RANGE) */
+    const uint64_t* d_counts; /* C; every count must be < 2^31 (SFGPU_ERR_RANGE).  The builder's counts are >= 1.  A class with
+                                 count 0 contributes nothing, under EM (the reference skips its 0 / 0 weights, :269) and under
+                                 VBEM alike (where the reference itself returns NaN for such a class of two or more members:
+                                 the kernels never form the stored weights); its members still count as active */
     uint64_t num_mapped;      /* ReadExperiment::numMappedFragments() (:792) */
 } sfgpu_problem;
 
@@ -1126,6 +1129,35 @@ enum {
 SFGPU_API int sfgpu_vb_eval(int form, const double* d_a, const double* d_c, const double* d_len, uint64_t n, double* d_out,
                             sfgpu_stream stream);
 SFGPU_API int sfgpu_em_rebase(sfgpu_em* em, const double* d_len);
+/* Diagnostic, like sfgpu_vb_eval: the PLAN of a handle (csrc/em.hip sfgpu_em_create, csrc/em_persist.h) in numbers, for the tests that
+ * build a class table for one boundary of the plan and must know that the run took that path.  Read-only: it waits for the plan's own
+ * stream, reads the plan's tables back and resolves the two lazy verdicts the way a run would; it changes no table, no launch and no
+ * result.  Synchronous.  A problem without classes reports zeros and verdict 1.  (The struct is named by its tag: `struct
+ * sfgpu_em_plan_info`.) */
+struct sfgpu_em_plan_info {
+    uint32_t n_tiles;          /* tiles of the plan */
+    uint32_t tile_nnz;         /* nonzeros per tile: the cuts fall at its multiples */
+    uint32_t redone;           /* times the plan was redone with one more round because a tile held more than 7800 classes */
+    uint32_t most_classes;     /* the most classes in one tile (the persistent loop's den_cap, the null class of the gather form) */
+    uint64_t P;                /* window slots over all tiles */
+    uint64_t E;                /* escapes: members outside their tile's window */
+    uint32_t renumbered;       /* 1: the plan runs in a transcript order of its own */
+    uint32_t gather;           /* 1: the gather form of the sweep; 0: the scatter form (SFGPU_EM_GATHER=0, or every member an escape) */
+    uint32_t cover_tiles;      /* tiles that more than six tiles overlap: they go by the cover list (gather form; 0 otherwise) */
+    uint32_t most_far_slots;   /* the most distinct far transcripts of a tile */
+    uint32_t longest_far_list; /* the most far members of a tile */
+    uint32_t fused_ok;         /* 1: the plan can run one kernel per iteration */
+    uint64_t n1, n2, n3, n4;   /* sums over the tiles of the persistent loop's class records: 4-, 8-, 16-byte, 16-byte + overflow */
+    uint64_t n_ov;             /* ... and of their overflow chunks (all 0 when the plan has no tables for the persistent loop) */
+    uint32_t persist_verdict;  /* 0: eligible for the persistent loop; else why not: 1 no tables (SFGPU_EM_PERSIST=0 when the plan was
+                                  made, the scatter form, no classes), 2 plan event, 3 a far member's transcript lies in no window,
+                                  4 a transcript fed by more than 16 far slots, 5 a tile that goes by the cover list, 6 LDS,
+                                  7 device query, 8 function attribute, 9 occupancy query, 10 more tiles than resident blocks;
+                                  11 the plan was eligible, but a persistent launch of this handle gave up waiting (a shared
+                                  device): the handle keeps one kernel per iteration from then on */
+    uint32_t pad_;
+};
+SFGPU_API int sfgpu_em_plan_info(sfgpu_em* em, struct sfgpu_em_plan_info* info);
 /* The sharded loop as ONE call (classes partitioned over the GPUs, alpha replicated, one SUM all-reduce of
  * alphaOut per iteration): `em` holds THIS rank's slice of the classes; `allreduce` must leave the element-wise sum over
  * all ranks in d_buf on every rank (in place; it may enqueue on `stream`, the stream the loop runs on, or synchronise --

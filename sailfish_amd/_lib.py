@@ -40,6 +40,18 @@ class EmStats(C.Structure):
                     alpha_sum=self.alpha_sum, n_active=self.n_active, loop_ms=self.loop_ms, fused=bool(self.fused), persistent=bool(self.persistent))
 
 
+class EmPlanInfo(C.Structure):
+    """struct sfgpu_em_plan_info"""
+    _fields_ = [("n_tiles", C.c_uint32), ("tile_nnz", C.c_uint32), ("redone", C.c_uint32), ("most_classes", C.c_uint32),
+                ("P", C.c_uint64), ("E", C.c_uint64), ("renumbered", C.c_uint32), ("gather", C.c_uint32),
+                ("cover_tiles", C.c_uint32), ("most_far_slots", C.c_uint32), ("longest_far_list", C.c_uint32), ("fused_ok", C.c_uint32),
+                ("n1", C.c_uint64), ("n2", C.c_uint64), ("n3", C.c_uint64), ("n4", C.c_uint64), ("n_ov", C.c_uint64),
+                ("persist_verdict", C.c_uint32), ("pad_", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "pad_"}
+
+
 class EqStats(C.Structure):
     _fields_ = [("insert_ms", C.c_double), ("insert_launches", C.c_uint64), ("table_grows", C.c_uint64),
                 ("deferred_reads", C.c_uint64), ("table_slots", C.c_uint64),
@@ -465,6 +477,7 @@ _SIGS = {
     "sfgpu_vb_eval": (C.c_int, [C.c_int, _P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_em_rebase": (C.c_int, [_P, _P]),
     "sfgpu_em_time_sweep": (C.c_int, [_P, C.POINTER(EmOpts), C.c_uint32, C.POINTER(C.c_double)]),
+    "sfgpu_em_plan_info": (C.c_int, [_P, C.POINTER(EmPlanInfo)]),
     "sfgpu_bootstrap": (C.c_int, [_P, C.POINTER(EmOpts), C.c_uint32, C.c_uint64, _P, SAMPLE_CB, _P, _P]),
     "sfgpu_bootstrap_counts": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P]),
     "sfgpu_gibbs_sample": (C.c_int, [C.POINTER(Problem), _P, C.c_uint32, C.c_uint32, C.c_uint64, _P, GIBBS_CB, _P, _P]),

@@ -1622,6 +1622,8 @@ struct sfgpu_em {
     bool xbuf_uncached = false;                             // ... in UNCACHED device memory (the default; SFGPU_EM_XBUF=pool: an ordinary pool block)
     uint32_t* pflags = nullptr;                             // device: [0] plan flags (!= 0: not eligible), [1] most far slots of a tile
     int persist_ok = -1;                                    // -1: not looked at yet; 0: this plan (or this device) does not run persistent
+    uint32_t persist_why = 0;                               // em_persist_check's verdict as a code: 0 eligible, k: its k-th `return no(...)`; 11: a launch gave up (sfgpu_em_plan_info)
+    uint32_t plan_redone = 0;                               // times the plan was redone with one more round for a tile of more than kTileNnz classes
     uint32_t far_cap = 0, esc_ln = 0;                       // LDS of the persistent loop: far slots of a tile at most; far members of a tile kept on chip
     bool no_persist = false;                                // set while several bootstrap lanes run (see sfgpu_bootstrap)
     int sharded_fused = 0;                                  // sfgpu_em_set_sharded_fused: the sharded loop runs one sweep kernel per iteration (every rank agreed)
@@ -2063,7 +2065,7 @@ int sfgpu_em_create(sfgpu_em** out, const sfgpu_problem* prob, sfgpu_stream stre
         EM_TRY(pool_malloc(&em->tsum, (size_t)nt_cap * 8));
         EM_TRY(hipMemsetAsync(em->tsum, 0, (size_t)nt_cap * 8, em->cur));      // empty tiles never write theirs
       for (;;) {                             // (the plan; twice or three times when the transcripts are renumbered)
-        rounds = rounds0; tile_nnz = tile_nnz0; nt = nt0; em->n_tiles = nt0;
+        rounds = rounds0; tile_nnz = tile_nnz0; nt = nt0; em->n_tiles = nt0; em->plan_redone = 0;
         EM_TRY(pool_malloc(&t_len8, ((size_t)nt_cap + 1) * 4)); EM_TRY(pool_malloc(&t_nesc, ((size_t)nt_cap + 1) * 4));
         // (the check of the tiles' class counts rides on the read-back of the plan's sizes: the window pass and the scans below run on a
         //  plan that may have to be redone with one more round -- rare, and harmless: they do not depend on the class counts)
@@ -2081,7 +2083,7 @@ int sfgpu_em_create(sfgpu_em** out, const sfgpu_problem* prob, sfgpu_stream stre
             lo_monotone = reinterpret_cast<const uint32_t*>(em->h_plan + 5)[1] == 0u;
             em->null_cls = most;                             // (<= kTileNnz when the loop ends: a tile holds no more classes than nonzeros)
             if (tile_nnz <= (uint32_t)kTileNnz || most <= (uint32_t)kTileNnz) break;
-            ++rounds;
+            ++rounds; ++em->plan_redone;
             tile_nnz = tile_for(rounds);
             if (tile_nnz < (uint32_t)kTileNnz) tile_nnz = kTileNnz;
             nt = (uint32_t)std::max<uint64_t>(1, ((uint64_t)rp_end + tile_nnz - 1) / tile_nnz);
@@ -2630,15 +2632,15 @@ static const void* em_persist_func(bool vb) {
 }
 // the plan's verdict (read back behind the tables), the LDS carve and the chip's residency: every block of the launch must be resident
 static void em_persist_check(sfgpu_em* em) {
-    em->persist_ok = 0;
+    em->persist_ok = 0; em->persist_why = 0;
     const bool say = env_timing();
-    auto no = [&](const char* why) { if (say) fprintf(stderr, "em persistent: not eligible -- %s\n", why); };
-    if (!em->xbuf || !em->pflags || !em->partial_a) return no("no tables (SFGPU_EM_PERSIST=0 at create, or the exchange buffer would pass 2 GB)");
-    if (hipEventSynchronize(em->ev_plan) != hipSuccess) return no("plan event");
+    auto no = [&](uint32_t code, const char* why) { em->persist_why = code; if (say) fprintf(stderr, "em persistent: not eligible -- %s\n", why); };
+    if (!em->xbuf || !em->pflags || !em->partial_a) return no(1u, "no tables (SFGPU_EM_PERSIST=0 at create, or the exchange buffer would pass 2 GB)");
+    if (hipEventSynchronize(em->ev_plan) != hipSuccess) return no(2u, "plan event");
     const uint32_t* pf = reinterpret_cast<const uint32_t*>(em->h_plan + 8);
-    if (pf[0] & 2u) return no("a far member's transcript lies in no window (no home thread)");
-    if (pf[0] & 4u) return no("a transcript is fed by more far slots than its home thread should walk");
-    if ((*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 1u) != 0u) return no("a tile that more than kNbMax tiles overlap (it goes by the cover list)");
+    if (pf[0] & 2u) return no(3u, "a far member's transcript lies in no window (no home thread)");
+    if (pf[0] & 4u) return no(4u, "a transcript is fed by more far slots than its home thread should walk");
+    if ((*reinterpret_cast<const uint32_t*>(em->h_plan + 4) & 1u) != 0u) return no(5u, "a tile that more than kNbMax tiles overlap (it goes by the cover list)");
     em->far_cap = pf[1];
     constexpr size_t kLdsPerBlock = 81920;                   // half a CU's LDS: two blocks per CU, like the sweep
     {   // the tiles' far members on chip: all of the plan's largest list, or what is left of the block's LDS
@@ -2647,14 +2649,14 @@ static void em_persist_check(sfgpu_em* em) {
         em->esc_ln = (uint32_t)std::min<size_t>(pf[2], room);
     }
     const size_t lds = em_persist_lds(em);
-    if (lds > kLdsPerBlock) return no("the tile's classes + far slots do not fit the LDS");
+    if (lds > kLdsPerBlock) return no(6u, "the tile's classes + far slots do not fit the LDS");
     int dev = 0, n_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return no("device query");
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return no(7u, "device query");
     for (int vb = 0; vb < 2; ++vb) {
         int nb = 0;
-        if (hipFuncSetAttribute(em_persist_func(vb != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerBlock) != hipSuccess) { (void)hipGetLastError(); return no("hipFuncSetAttribute"); }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, em_persist_func(vb != 0), kPB, lds) != hipSuccess) { (void)hipGetLastError(); return no("occupancy query"); }
-        if ((uint64_t)nb * (uint64_t)n_cu < em->n_tiles) return no("more tiles than resident blocks (a multi-round plan)");
+        if (hipFuncSetAttribute(em_persist_func(vb != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsPerBlock) != hipSuccess) { (void)hipGetLastError(); return no(8u, "hipFuncSetAttribute"); }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, em_persist_func(vb != 0), kPB, lds) != hipSuccess) { (void)hipGetLastError(); return no(9u, "occupancy query"); }
+        if ((uint64_t)nb * (uint64_t)n_cu < em->n_tiles) return no(10u, "more tiles than resident blocks (a multi-round plan)");
     }
     if (say) fprintf(stderr, "em persistent: eligible (%u tiles, %zu bytes of LDS, %u far slots at most per tile)\n", em->n_tiles, lds, em->far_cap);
     em->persist_ok = 1;
@@ -2738,6 +2740,42 @@ static int em_choose_form(sfgpu_em* em, const sfgpu_em_opts& o, const EmSwitches
     if (rc || em->fused_ok != 1) return rc;
     if (persist && em->persist_ok < 0) em_persist_check(em);
     *form = (persist && em->persist_ok == 1) ? EmForm::persistent : fuse ? EmForm::fused : EmForm::two_kernel;
+    return SFGPU_OK;
+}
+
+// Diagnostic (sfgpu.h): what the plan of this handle looks like, for the tests that build a class table for one path and must know that
+// it ran there.  Reads what the handle holds and, once the plan's stream has drained, the plan's own tables; forces the two lazy verdicts
+// exactly as em_choose_form would.  Changes no table, no launch and no result.
+int sfgpu_em_plan_info(sfgpu_em* em, struct sfgpu_em_plan_info* info) {
+    SF_REQUIRE(em && info, SFGPU_ERR_INVALID, "sfgpu_em_plan_info: null pointer");
+    memset(info, 0, sizeof(*info));
+    if (em->prob.C == 0) { info->persist_verdict = 1u; return SFGPU_OK; }      // (no plan: no tiles, no tables)
+    SF_HIP(hipStreamSynchronize(em->stream));                // (the plan was queued on the handle's own stream, ev_plan included)
+    const uint32_t nt = em->n_tiles;
+    info->n_tiles = nt; info->tile_nnz = em->tile_nnz; info->redone = em->plan_redone; info->most_classes = em->null_cls;
+    info->P = em->P; info->E = em->E;
+    info->renumbered = em->inv ? 1u : 0u; info->gather = em->gather ? 1u : 0u;
+    if (em->gather && em->td) {
+        std::vector<TileDesc> h(nt);
+        SF_HIP(hipMemcpy(h.data(), em->td, (size_t)nt * sizeof(TileDesc), hipMemcpyDeviceToHost));
+        for (const TileDesc& t : h) if (t.nb_n == kNbByList) ++info->cover_tiles;
+    }
+    if (em->pflags) {
+        const uint32_t* pf = reinterpret_cast<const uint32_t*>(em->h_plan + 8);
+        info->most_far_slots = pf[1]; info->longest_far_list = pf[2];
+    }
+    if (em->tp) {
+        std::vector<TilePack> h(nt);
+        SF_HIP(hipMemcpy(h.data(), em->tp, (size_t)nt * sizeof(TilePack), hipMemcpyDeviceToHost));
+        for (const TilePack& t : h) { info->n1 += t.n1; info->n2 += t.n2; info->n3 += t.n3; info->n4 += t.n4; info->n_ov += t.n_ov; }
+    }
+    if (em->gather && em->partial_a) {
+        const int rc = em_resolve_fused_ok(em);
+        if (rc) return rc;
+        info->fused_ok = em->fused_ok == 1 ? 1u : 0u;
+    }
+    if (em->persist_ok < 0) em_persist_check(em);
+    info->persist_verdict = em->persist_why;
     return SFGPU_OK;
 }
 
@@ -2871,7 +2909,7 @@ static int em_run(sfgpu_em* em, const sfgpu_em_opts* opts, double* d_alpha_out, 
         // a tile gave up waiting (its neighbours never became resident: the chip is shared with another process' kernels): this
         // handle goes back to one kernel per iteration, and the run is repeated from its start
         persist_lock.unlock();
-        em->persist_ok = 0;
+        em->persist_ok = 0; em->persist_why = 11u;             // (sfgpu_em_plan_info: this handle no longer runs persistent)
         unsigned long long who[4] = {0, 0, 0, 0};
         (void)hipMemcpy(who, em->xbuf + (size_t)(kCtlAbort + 1) * kCtlStride * 8, sizeof(who), hipMemcpyDeviceToHost);
         em_dbg_persist_progress(em);

@@ -130,6 +130,12 @@ class EMProblem:
         _lib.check(self._L.sfgpu_em_rebase(self._h, _lib.ptr(length)))
         torch.cuda.current_stream().synchronize()      # `length` may be a temporary
 
+    def plan_info(self):
+        """the handle's plan in numbers (sfgpu_em_plan_info; read-only diagnostics for the tests) -> dict"""
+        info = _lib.EmPlanInfo()
+        _lib.check(self._L.sfgpu_em_plan_info(self._h, C.byref(info)))
+        return info.as_dict()
+
     def time_sweep(self, n=100, **kw):
         o = self.opts(**kw); ms = C.c_double()
         _lib.check(self._L.sfgpu_em_time_sweep(self._h, C.byref(o), int(n), C.byref(ms)))

@@ -6,7 +6,8 @@ HIP kernels (same author) would show up as a disagreement with this file.
 Differences in kind from the C oracle, on purpose: the stored, normalised auxiliary weights w_{c,i} are materialised
 as one array and used exactly as the reference uses them (the HIP path folds them away); sums run over numpy
 reductions (pairwise), not serial loops; digamma comes from scipy (Boost in the reference, a series in the C oracle).
-An mpmath variant (50 digits) of the same recurrences arbitrates on small problems."""
+An mpmath variant (50 digits) of the same recurrences arbitrates on small problems; its skip_zero_count option follows the kernels'
+contract for a class with count 0 (include/sfgpu.h), not the reference, whose VBEM is NaN there."""
 import numpy as np
 from scipy.special import digamma
 
@@ -91,8 +92,13 @@ def tpm(alpha, length, num_mapped):
     return x / d * 1e6
 
 
-def optimize_mp(eff_len, rowptr, ids, counts, num_mapped, vb=False, n_iter=50, digits=50):
-    """the same recurrences in mpmath (small problems only): -> alpha after n_iter rounds, untruncated (floats)"""
+def optimize_mp(eff_len, rowptr, ids, counts, num_mapped, vb=False, n_iter=50, digits=50, keep=None, skip_zero_count=False):
+    """the same recurrences in mpmath (small problems only): -> alpha after n_iter rounds, untruncated (floats); with
+    keep = (i, j, ...) one run of max(keep) rounds -> {i: alpha after i rounds, ...}.  A zero-count class of two or more members
+    under VBEM is NaN in the reference and an error here, unless skip_zero_count says that it contributes nothing (what the
+    kernels do, include/sfgpu.h)"""
+    if keep is not None:
+        keep = sorted(set(int(k) for k in keep)); n_iter = keep[-1]; kept = {}
     import mpmath as mp
     mp.mp.dps = digits
     M = len(eff_len)
@@ -103,12 +109,17 @@ def optimize_mp(eff_len, rowptr, ids, counts, num_mapped, vb=False, n_iter=50, d
         ts = [int(t) for t in ids[rowptr[c]:rowptr[c + 1]]]
         v = [mp.mpf(int(counts[c])) / eff[t] for t in ts]
         s = mp.fsum(v)
+        if s == 0:                                         # a zero-count class: weights 0 / 0 = NaN, which EMUpdate_ skips (:269) and VBEMUpdate_ does not
+            if vb and len(ts) > 1 and not skip_zero_count: raise ValueError("VBEM with a zero-count class is NaN in the reference")
+            w.append((ts, None)); continue
         w.append((ts, [x / s for x in v]))
     act = sorted({t for ts, _ in w for t in ts})
     alpha = [mp.mpf(0)] * M
     for t in act:
         alpha[t] = mp.mpf(num_mapped) / len(act)
-    for _ in range(n_iter):
+    for it in range(n_iter):
+        if keep is not None and it in keep:
+            kept[it] = np.array([float(a) for a in alpha])
         if vb:
             ln = mp.digamma(mp.fsum(alpha))
             src = [mp.e ** (mp.digamma(a) - ln) if a > 0 else mp.mpf(0) for a in alpha]
@@ -116,6 +127,7 @@ def optimize_mp(eff_len, rowptr, ids, counts, num_mapped, vb=False, n_iter=50, d
         else:
             src = alpha; out = [mp.mpf(0)] * M
         for c, (ts, ws) in enumerate(w):
+            if ws is None: continue
             if len(ts) == 1:
                 out[ts[0]] += int(counts[c]); continue
             v = [src[t] * x for t, x in zip(ts, ws)]
@@ -124,4 +136,7 @@ def optimize_mp(eff_len, rowptr, ids, counts, num_mapped, vb=False, n_iter=50, d
                 for t, x in zip(ts, v):
                     out[t] += x * (mp.mpf(int(counts[c])) / d)
         alpha = out
+    if keep is not None:
+        kept[n_iter] = np.array([float(a) for a in alpha])
+        return kept
     return np.array([float(a) for a in alpha])

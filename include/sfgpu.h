@@ -1635,6 +1635,65 @@ typedef struct sfgpu_libdet_stats {
 SFGPU_API int sfgpu_hits_library_kinds(const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, const sfgpu_libdet_opts* opts,
                                        int64_t* remaining_votes, sfgpu_libdet_stats* stats, sfgpu_stream stream);
 
+/* Posterior-weighted coverage of the transcripts by the mappings, accumulated over the batches of a run, and its bedGraph file (the
+ * rule is stated once in csrc/coverfmt.h; hits.coverage_host is the Python statement).  Only a record's own fields and the transcript
+ * lengths are read; no index and no read bases are needed.
+ *   open     d_ref_len[M] is read once; the handle then holds ONE uint64 array of sum(len) + M slots (8 bytes each: about 3.6 GB for
+ *            a transcriptome of 450 M bases), transcript t owning len_t + 1 of them.  M == 0 is valid.  A length of 2^32 - 1:
+ *            SFGPU_ERR_RANGE.
+ *   add      a record's line 0 is (pos, read_len), a mate_status == 3 record has line 1, (mate_pos, mate_len).  Without alignments a
+ *            line is the interval [max(pos, 0), min(pos + len, len_t)).  With d_aln_pos / d_aln_op_off / d_aln_ops (all three or none:
+ *            sfgpu_hits_align_gapped's outputs for the same records, slot 2 h + which) its words are walked from d_aln_pos[slot]: M, =
+ *            and X cover [x, x + n) clipped to the transcript and advance x, D and N advance x, I, S, H and P do neither; a slot
+ *            without operations has no interval.  An interval [a, b) adds q to slot a and takes it off slot b, q = trunc(p 2^32) of
+ *            the record's d_p (both lines of a pair carry it), or floor(2^32 / n), n the read's record count, where d_p is NULL.
+ *            Empty intervals add nothing and are counted.  64-bit integer atomics: the result does not depend on any order.
+ *            errors, state and stats untouched: tid >= M: SFGPU_ERR_RANGE naming the lowest record; a p that is NaN, negative or above
+ *            1: SFGPU_ERR_INVALID naming the lowest record; lines that would bring the handle's total to 2^32: SFGPU_ERR_RANGE; a call
+ *            after finish: SFGPU_ERR_INVALID.  n_reads == 0 is a valid call.  The stats are ACCUMULATED by the call.
+ *   finish   one inclusive scan turns the slots into sums (every transcript's last slot then reads 0: `residue` counts those that do
+ *            not and must be 0); the runs -- maximal stretches of one transcript's bases with one nonzero sum, by transcript, then
+ *            start -- are counted per block, placed by a scan and written as (tid, start, end, sum); a wavefront per transcript
+ *            folds its bases into covered, the 128-bit sum and the maximum, and the three columns CoveredFraction = covered / len,
+ *            MeanDepth = (double)floor(S / len) 2^-32, MaxDepth = (double)max 2^-32 (0 for len == 0).  A second finish returns the
+ *            same result.
+ *   runs / summary   copies of the results into the caller's device arrays (n_runs and M entries; a NULL pointer is skipped); before
+ *            finish: SFGPU_ERR_STATE.
+ *   write    the rows name \t start \t end \t %g(sum 2^-32) \n, 0-based and half open, without a header line, formatted in 4 KB tiles
+ *            and handed over in chunks as sfgpu_quant_write_text's rows are (d_names / d_name_off[M + 1] and chunk_bytes as there; sink
+ *            NULL: only sized); sfgpu_cov_write_bgzf hands the chunks to the BGZF encoder where they lie, as sfgpu_reads_write_bgzf
+ *            does.  Before finish: SFGPU_ERR_STATE.
+ * Synchronous. */
+typedef struct sfgpu_cov sfgpu_cov;
+typedef struct sfgpu_cov_stats {
+    uint64_t reads;
+    uint64_t records;
+    uint64_t lines;
+    uint64_t intervals;               /* added */
+    uint64_t empty_intervals;         /* nothing left after the clip */
+    uint64_t bases_added;             /* the bases of the added intervals */
+} sfgpu_cov_stats;
+typedef struct sfgpu_cov_result {
+    uint64_t n_runs;
+    uint64_t bases_covered, bases_total;
+    uint64_t residue;                 /* transcripts whose last slot is not 0 after the scan: 0 */
+    uint64_t state_bytes;             /* device memory the handle holds */
+    uint64_t n_bytes, n_chunks, max_row_bytes;      /* of a write */
+    double finish_ms, format_ms, d2h_ms, sink_ms;
+} sfgpu_cov_result;
+SFGPU_API int sfgpu_cov_open(sfgpu_cov** out, const uint32_t* d_ref_len, uint64_t M, sfgpu_stream stream);
+SFGPU_API int sfgpu_cov_close(sfgpu_cov* c);
+SFGPU_API int sfgpu_cov_add(sfgpu_cov* c, const sfgpu_hit* d_hits, const uint32_t* d_hit_offsets, uint32_t n_reads, const double* d_p,
+                            const int32_t* d_aln_pos, const uint64_t* d_aln_op_off, const uint32_t* d_aln_ops, sfgpu_cov_stats* stats,
+                            sfgpu_stream stream);
+SFGPU_API int sfgpu_cov_finish(sfgpu_cov* c, sfgpu_cov_result* out, sfgpu_stream stream);
+SFGPU_API int sfgpu_cov_runs(sfgpu_cov* c, uint32_t* d_tid, uint32_t* d_start, uint32_t* d_end, uint64_t* d_sum);
+SFGPU_API int sfgpu_cov_summary(sfgpu_cov* c, double* d_covered_fraction, double* d_mean, double* d_max);
+SFGPU_API int sfgpu_cov_write_text(sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_text_sink sink,
+                                   void* user, sfgpu_cov_result* out, sfgpu_stream stream);
+SFGPU_API int sfgpu_cov_write_bgzf(sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_bgzw* z,
+                                   sfgpu_cov_result* out, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

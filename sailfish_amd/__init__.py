@@ -6,4 +6,4 @@ from .experiment import ReadExperiment, SailfishOpts, Transcripts  # noqa: F401
 from .eqclass import EquivalenceClassBuilder, EqVec, xxh64_labels  # noqa: F401
 from .optimizer import CollapsedEMOptimizer, EMProblem  # noqa: F401
 from .gibbs import CollapsedGibbsSampler, gibbs_sample  # noqa: F401
-from . import bias, efflen, eqfile, genes, gzfile, hits, mapper, quant, quantfile, readfile, samfile, writer  # noqa: F401
+from . import bias, coverage, efflen, eqfile, genes, gzfile, hits, mapper, quant, quantfile, readfile, samfile, writer  # noqa: F401

@@ -333,6 +333,23 @@ class LibdetStats(C.Structure):
         return {k: [int(v) for v in getattr(self, k)] if k.endswith("_kind") else int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class CovStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("records", C.c_uint64), ("lines", C.c_uint64), ("intervals", C.c_uint64), ("empty_intervals", C.c_uint64),
+                ("bases_added", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class CovResult(C.Structure):
+    _fields_ = [("n_runs", C.c_uint64), ("bases_covered", C.c_uint64), ("bases_total", C.c_uint64), ("residue", C.c_uint64), ("state_bytes", C.c_uint64),
+                ("n_bytes", C.c_uint64), ("n_chunks", C.c_uint64), ("max_row_bytes", C.c_uint64), ("finish_ms", C.c_double), ("format_ms", C.c_double),
+                ("d2h_ms", C.c_double), ("sink_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
     "sfgpu_has_variants": (C.c_int, []),
@@ -436,6 +453,14 @@ _SIGS = {
                                      C.POINTER(MdTagStats), _P]),
     "sfgpu_hits_posteriors": (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, C.POINTER(PosteriorStats), _P]),
     "sfgpu_hits_library_kinds": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(LibdetOpts), C.POINTER(C.c_int64), C.POINTER(LibdetStats), _P]),
+    "sfgpu_cov_open": (C.c_int, [C.POINTER(_P), _P, C.c_uint64, _P]),
+    "sfgpu_cov_close": (C.c_int, [_P]),
+    "sfgpu_cov_add": (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, _P, _P, C.POINTER(CovStats), _P]),
+    "sfgpu_cov_finish": (C.c_int, [_P, C.POINTER(CovResult), _P]),
+    "sfgpu_cov_runs": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sfgpu_cov_summary": (C.c_int, [_P, _P, _P, _P]),
+    "sfgpu_cov_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(CovResult), _P]),
+    "sfgpu_cov_write_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(CovResult), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

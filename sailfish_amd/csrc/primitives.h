@@ -19,4 +19,7 @@ int exclusive_scan_u32(const uint32_t* d_in, uint64_t* d_out, uint64_t n, hipStr
 // the same with 32-bit sums (the caller knows the total fits), nothing waited for
 int exclusive_scan_u32_u32(const uint32_t* d_in, uint32_t* d_out, uint64_t n, hipStream_t s);
 
+// d[i] = sum_{j<=i} d[j] modulo 2^64 for i in [0, n), in place, nothing waited for
+int inclusive_scan_u64(uint64_t* d, uint64_t n, hipStream_t s);
+
 }  // namespace sfgpu

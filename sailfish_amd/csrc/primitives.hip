@@ -55,4 +55,16 @@ int exclusive_scan_u32_u32(const uint32_t* d_in, uint32_t* d_out, uint64_t n, hi
     return SFGPU_OK;
 }
 
+int inclusive_scan_u64(uint64_t* d, uint64_t n, hipStream_t s) {
+    if (n == 0) return SFGPU_OK;
+    size_t tmp_bytes = 0;
+    SF_HIP(rocprim::inclusive_scan(nullptr, tmp_bytes, d, d, (size_t)n, rocprim::plus<uint64_t>(), s));
+    void* tmp = nullptr;
+    SF_HIP(pool_malloc(&tmp, tmp_bytes ? tmp_bytes : 8));
+    hipError_t e = rocprim::inclusive_scan(tmp, tmp_bytes, d, d, (size_t)n, rocprim::plus<uint64_t>(), s);
+    pool_free_on(tmp, s);
+    SF_HIP(e);
+    return SFGPU_OK;
+}
+
 }  // namespace sfgpu

@@ -1030,6 +1030,116 @@ def library_kinds(hits, offsets, *, paired_library, max_read_occs=200, allow_dov
     return int(rem.value), st.as_dict()
 
 
+COVERAGE_STATS = ("reads", "records", "lines", "intervals", "empty_intervals", "bases_added")
+COVERAGE_RESULT = ("runs", "bases_covered", "bases_total", "residue")
+COV_ONE = 1 << 32
+COV_MAX_LINES = (1 << 32) - 1
+
+
+def coverage_weight(p):
+    """csrc/coverfmt.h's WEIGHT of a posterior 0 <= p <= 1: trunc(p 2^32); the product is a scaling by a power of two, hence exact"""
+    return int(p * 4294967296.0)
+
+
+def coverage_host(ref_len, batches, *, finish=True):
+    """The statement of the coverage pass (csrc/coverfmt.h restated; what sfgpu_cov_* are judged by).  ref_len: the transcripts'
+    lengths; batches: an iterable of (hits, offsets, p, alignments) -- HIT_DTYPE records in CSR form over the reads, the posterior of
+    every record (float64) or None for the uniform weight floor(2^32 / n) of a read with n records, and (pos, op_off, ops) as
+    align_hits_host returns them (two slots a record) or None for the recorded diagonal.  Transcript t owns len_t + 1 slots of one
+    uint64 array from off_t + t on; a line (line 0: pos, read_len; line 1 of a mate_status == 3 record: mate_pos, mate_len) adds
+    q = trunc(p 2^32) at the start of each of its intervals, clipped to the transcript, and takes it off at the end; an inclusive
+    scan modulo 2^64 gives the sums; a run is a maximal stretch of one transcript's bases with one nonzero sum.
+    -> (runs = (tid uint32[], start uint32[], end uint32[], sum uint64[]), summary = (CoveredFraction, MeanDepth, MaxDepth float64[M]),
+        stats dict of COVERAGE_STATS + COVERAGE_RESULT).  ValueError naming the lowest record of a batch whose tid is not a
+    transcript, else the lowest whose p is NaN, negative or above 1, or saying that the lines would reach 2^32; nothing of that batch
+    is added then."""
+    ref_len = np.ascontiguousarray(ref_len, dtype=np.uint32)
+    M = len(ref_len)
+    base = np.zeros(M + 1, np.int64)
+    np.cumsum(ref_len.astype(np.int64) + 1, out=base[1:])
+    slot = np.zeros(int(base[M]), np.uint64)
+    stats = dict.fromkeys(COVERAGE_STATS + COVERAGE_RESULT, 0)
+    for hits, offsets, p, aln in batches:
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        off = np.asarray(offsets).astype(np.int64)
+        n_rec = int(off[-1]) if len(off) else 0
+        hits = hits[:n_rec]
+        bad = np.nonzero(hits["tid"] >= M)[0]
+        if len(bad):
+            raise ValueError(f"record {int(bad[0])} names transcript >= {M}")
+        if p is not None:
+            p = np.ascontiguousarray(p, dtype=np.float64)[:n_rec]
+            with np.errstate(invalid="ignore"):
+                bad = np.nonzero(~((p >= 0) & (p <= 1)))[0]
+            if len(bad):
+                raise ValueError(f"the posterior of record {int(bad[0])} is NaN, negative or above 1")
+            q = (p * 4294967296.0).astype(np.uint64)
+        else:
+            sizes = np.diff(off) if len(off) else np.zeros(0, np.int64)
+            q = np.repeat(COV_ONE // np.maximum(sizes, 1), sizes).astype(np.uint64)
+        paired = hits["mate_status"] == 3
+        lines = n_rec + int(paired.sum())
+        if stats["lines"] + lines > COV_MAX_LINES:
+            raise ValueError(f"{lines} lines more would bring the total to 2^32 or beyond")
+        stats["reads"] += max(len(off) - 1, 0)
+        stats["records"] += n_rec
+        stats["lines"] += lines
+        tid = hits["tid"].astype(np.int64)
+        len_t = ref_len[tid].astype(np.int64) if n_rec else np.zeros(0, np.int64)
+        if aln is None:                                    # the recorded diagonal: line 0 of every record, line 1 of the pairs
+            rec = np.concatenate([np.arange(n_rec), np.nonzero(paired)[0]])
+            a = np.concatenate([hits["pos"].astype(np.int64), hits["mate_pos"].astype(np.int64)[paired]])
+            b = a + np.concatenate([hits["read_len"].astype(np.int64), hits["mate_len"].astype(np.int64)[paired]])
+        else:                                              # the covering words of every line's slot, walked from its position
+            a_pos, a_off, a_ops = (np.asarray(x).astype(np.int64) for x in aln)
+            if len(a_pos) != 2 * n_rec or len(a_off) != 2 * n_rec + 1:
+                raise ValueError(f"alignments: expected {2 * n_rec} positions and {2 * n_rec + 1} offsets")
+            a_ops = a_ops[:int(a_off[-1])] & 0xFFFFFFFF
+            n, op = a_ops >> 4, a_ops & 15
+            covers, advances = np.isin(op, (0, 7, 8)), np.isin(op, (0, 7, 8, 2, 3))
+            slot_of = np.repeat(np.arange(2 * n_rec), np.diff(a_off))
+            before = np.cumsum(np.where(advances, n, 0)) - np.where(advances, n, 0)          # the bases advanced before each word ...
+            x = a_pos[slot_of] + before - before[np.minimum(a_off[:-1], max(len(before) - 1, 0))][slot_of] if len(a_ops) else np.zeros(0, np.int64)
+            is_line = ((slot_of & 1) == 0) | paired[slot_of >> 1]
+            sel = covers & is_line
+            rec, a, b = slot_of[sel] >> 1, x[sel], x[sel] + n[sel]
+        lo, hi = np.maximum(a, 0), np.minimum(b, len_t[rec])
+        ok = lo < hi
+        at, w = base[tid[rec]][ok], q[rec][ok]
+        np.add.at(slot, at + lo[ok], w)
+        np.subtract.at(slot, at + hi[ok], w)
+        stats["intervals"] += int(ok.sum())
+        stats["empty_intervals"] += int((~ok).sum())
+        stats["bases_added"] += int((hi[ok] - lo[ok]).sum())
+    if not finish:
+        return slot, stats
+    sums = np.cumsum(slot, dtype=np.uint64)
+    r_tid, r_start, r_end, r_sum = [], [], [], []
+    frac, mean, maxd = np.zeros(M), np.zeros(M), np.zeros(M)
+    for t in range(M):
+        n = int(ref_len[t])
+        s = sums[int(base[t]):int(base[t]) + n]
+        stats["residue"] += int(sums[int(base[t]) + n] != 0)
+        if n == 0:
+            continue
+        change = np.nonzero(np.concatenate([[True], s[1:] != s[:-1]]))[0]
+        ends = np.concatenate([change[1:], [n]])
+        keep = s[change] != 0
+        r_tid.append(np.full(int(keep.sum()), t, np.uint32))
+        r_start.append(change[keep].astype(np.uint32))
+        r_end.append(ends[keep].astype(np.uint32))
+        r_sum.append(s[change][keep])
+        covered = int((s != 0).sum())
+        total = int((s & np.uint64(0xFFFFFFFF)).sum(dtype=np.uint64)) + (int((s >> np.uint64(32)).sum(dtype=np.uint64)) << 32)      # 128 bits
+        stats["bases_covered"] += covered
+        frac[t], mean[t], maxd[t] = covered / n, float(total // n) * 2.0 ** -32, float(int(s.max())) * 2.0 ** -32
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)      # noqa: E731
+    runs = (cat(r_tid, np.uint32), cat(r_start, np.uint32), cat(r_end, np.uint32), cat(r_sum, np.uint64))
+    stats["runs"] = len(runs[0])
+    stats["bases_total"] = int(ref_len.astype(np.int64).sum())
+    return runs, (frac, mean, maxd), stats
+
+
 def gc_prefix(seq, seq_off, ref_len):
     """Transcript::GCCount_ of every transcript (include/Transcript.hpp:183-196), laid out like `seq`: int32 device
     tensor of seq.numel() entries (4 bytes per base) -- what sample_bias reads for the fragment-GC samples."""

@@ -239,8 +239,14 @@ class _MappingsRun:
 
     def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                  mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None,
-                 mappings_posteriors=False):
+                 mappings_posteriors=False, write_coverage=None, coverage_weights="posterior", coverage_compress=False, out_dir=None):
         from .hits import ALIGNG_STATS, MDTAG_STATS, POSTERIOR_STATS
+        if coverage_weights not in ("posterior", "uniform"):
+            raise ValueError(f'coverage_weights is "posterior" or "uniform", not {coverage_weights!r}')
+        if write_coverage is None and coverage_compress:
+            raise ValueError("coverage_compress=True needs write_coverage")
+        if write_coverage is not None and not _is_sink(write_coverage):
+            raise ValueError("write_coverage: one path or binary file object")
         if mappings_sorted and mappings_format != "bam":
             raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
         self.rescue, rstats = _rescue(rescue_mates, rescue_window, min_identity, paired, lib_format, sopt)
@@ -260,6 +266,13 @@ class _MappingsRun:
         # file, the second maps them again and writes the file with the estimates' weights.  `second`: which pass batch() serves;
         # `again`: the second pass's rescue / verify counters, which must reproduce the first's.
         self.posteriors, self.second, self.weights, self.again = bool(mappings_posteriors), False, None, None
+        # The coverage file is that of the records the mappings file shows.  With posterior weights it is accumulated in
+        # the second pass, which then runs for it alone too (opening no mappings file); with uniform weights in the first.
+        self.cov_sink, self.cov_compress, self.cov_dir = write_coverage, bool(coverage_compress), out_dir
+        self.cov_posterior = write_coverage is not None and coverage_weights == "posterior"
+        self.gapped = bool(mappings_gapped)
+        self.two_pass = self.posteriors or self.cov_posterior
+        self.cov = self.cov_stats = None
         self.stats = dict(rescue=rstats, verify=vstats, align=astats, tag=tstats)  # None: the pass does not run
         self.post_stats = dict.fromkeys(POSTERIOR_STATS, 0) if self.posteriors else None
         self.targets, self.compress = _UnmappedWriters.targets(write_unmapped, unmapped_compress, paired), unmapped_compress
@@ -274,6 +287,9 @@ class _MappingsRun:
             self._open_sam(names, idx)
         if self.unmapped:
             self.unm = _UnmappedWriters(self.targets, self.compress)
+        if self.cov_sink is not None:
+            from .coverage import CoverageDevice
+            self.cov = CoverageDevice(idx.ref_len, idx.device)
 
     def _open_sam(self, names, idx):
         from .samfile import SamDeviceWriter
@@ -284,14 +300,18 @@ class _MappingsRun:
         r1 / r2: what map_reads takes (packed pairs on the device where the run writes a file); quals / mate_names: one entry per mate
         file; sam_quals: whether the mappings file takes the qualities too; read_names: its QNAMEs.  -> (hits, offsets)"""
         opt = {} if self.rescue is None else dict(rescue=self.rescue)              # (without the option the call is the one it was)
-        first = self.posteriors and not self.second            # only what decides the records runs: map -> rescue -> validate
+        sam_now = self.sam is not None and self.second == self.posteriors       # the pass that writes the mappings file: the second with posteriors
+        cov_now = self.cov is not None and self.second == self.cov_posterior    # ... that adds to the coverage: the second with posterior weights
+        first = self.two_pass and not self.second
         validate = self.validate
-        if first and validate is not None:
-            validate = {key: v for key, v in validate.items() if key != "align"}
-        h, o = idx.map_reads(r1, r2, validate=validate, tags=self.stats["tag"] is not None and not first, **opt)
+        if validate is not None and not (sam_now or (cov_now and self.gapped)) and (self.two_pass or self.sam is None):
+            validate = {key: v for key, v in validate.items() if key != "align"}      # only what decides the records runs: map -> rescue -> validate
+        aligned = validate is not None and bool(validate.get("align"))
+        tagged = self.stats["tag"] is not None and (sam_now or not self.two_pass)
+        h, o = idx.map_reads(r1, r2, validate=validate, tags=tagged, **opt)
         for name, attr, maxima in _PASSES:
             total = self.stats[name]
-            if total is None or (first and name in ("align", "tag")):
+            if total is None or (name == "align" and not (aligned and (sam_now or not self.two_pass))) or (name == "tag" and not tagged):
                 continue
             if self.second and name in ("rescue", "verify"):
                 total = self.again[name]
@@ -301,10 +321,16 @@ class _MappingsRun:
         if self.second:
             from .hits import posteriors
             *values, st = posteriors(h, o, self.weights)
-            post = dict(posteriors=tuple(values))
-            for key, v in st.items():
+            post = dict(posteriors=tuple(values)) if self.posteriors else {}
+            for key, v in st.items() if self.post_stats is not None else ():
                 self.post_stats[key] = max(self.post_stats[key], v) if key == "max_records" else self.post_stats[key] + v
-        if self.sam is not None:
+        if cov_now:
+            aln = None
+            if aligned:
+                a_pos, _, a_off, a_ops = idx.last_alignments[:4]
+                aln = (a_pos, a_off, a_ops)
+            self.cov.add(h, o, posteriors=values[0] if self.cov_posterior else None, alignments=aln)
+        if sam_now:
             q1, q2 = quals if sam_quals else (None, None)
             self.sam.write(h, o, read_names=read_names, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
                            alignments=idx.last_alignments if self.stats["align"] is not None else None, tags=idx.last_tags if self.stats["tag"] is not None else None,
@@ -319,12 +345,15 @@ class _MappingsRun:
         `posterior_weights`), the mappings file opened, and batches() -- the reads, produced again -- run through batch() once more.
         RuntimeError where the second pass's rescue or verify counters are not the first's: the file would not show the records that
         were quantified."""
-        if not self.posteriors:
+        if not self.two_pass:
             return
         log = (getattr(sopt, "jointLog", None) if sopt is not None else None) or (lambda lvl, msg: None)
         if rc != 0 or exp is None:
             self.post_stats = None
-            log(1, "mappings_posteriors: the quantification did not succeed (rc {}), so no mappings file is written".format(rc))
+            if self.posteriors:
+                log(1, "mappings_posteriors: the quantification did not succeed (rc {}), so no mappings file is written".format(rc))
+            if self.cov_posterior:
+                log(1, "write_coverage: the quantification did not succeed (rc {}), so no coverage file is written".format(rc))
             return
         from . import writer
         _, _, length, _, est = writer.abundance_columns(exp, sopt)
@@ -332,7 +361,8 @@ class _MappingsRun:
         self.weights = exp.posterior_weights = torch.where((length > 0) & torch.isfinite(w), w, torch.zeros_like(w)).contiguous()
         self.second = True
         self.again = {name: dict.fromkeys(self.stats[name], 0) for name in ("rescue", "verify") if self.stats[name] is not None}
-        self._open_sam(names, idx)
+        if self.posteriors:
+            self._open_sam(names, idx)
         for _ in batches():
             pass
         for name, again in self.again.items():
@@ -340,8 +370,23 @@ class _MappingsRun:
                 raise RuntimeError(f"mappings_posteriors: the second pass over the reads gave other {name} counters ({again}) than the first "
                                    f"({self.stats[name]}): the mappings file does not show the records that were quantified")
 
+    def write_coverage(self, names, sopt):
+        """write_coverage=, behind the last pass: the runs found and the rows formatted on the device (coverage.CoverageDevice), the file
+        and aux/coverage_summary.tsv written.  With posterior weights and a quantification that failed there is no second pass and
+        nothing is written."""
+        if self.cov is None or (self.cov_posterior and not self.second):
+            return
+        res = self.cov.finish()
+        wrote = self.cov.write(self.cov_sink, names, compress=self.cov_compress)
+        if self.cov_dir is not None:
+            aux = os.path.join(self.cov_dir, getattr(sopt, "auxDir", "aux") if sopt is not None else "aux")
+            os.makedirs(aux, exist_ok=True)
+            self.cov.write_summary(os.path.join(aux, "coverage_summary.tsv"), names)
+        self.cov_stats = dict(self.cov.stats, runs=res["runs"], bases_covered=res["bases_covered"], bases_total=res["bases_total"], residue=res["residue"],
+                              state_bytes=res["state_bytes"], bytes=int(wrote["n_bytes"]), weights="posterior" if self.cov_posterior else "uniform")
+
     def close(self):
-        for w in (self.sam, self.unm):
+        for w in (self.sam, self.unm, self.cov):
             if w is not None:
                 w.close()
 
@@ -354,6 +399,7 @@ class _MappingsRun:
         if exp is not None:
             exp.rescue_stats, exp.verify_stats, exp.align_stats, exp.tag_stats = res, v, a, t
             exp.posterior_stats = ps
+            exp.coverage_stats = self.cov_stats
             if u is not None:
                 exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
@@ -385,6 +431,10 @@ class _MappingsRun:
             log(0, "posteriors in the mappings file: ZW on the {} records of {} mapped reads, {} of them with more than one record (the largest has {}); "
                    "{} reads have no weight at all and are spread evenly; {} records are written as 0".format(
                        ps["records"], ps["reads_mapped"], ps["reads_multi"], ps["max_records"], ps["reads_flat"], ps["records_zero"]))
+        if self.cov_stats is not None:
+            c = self.cov_stats
+            log(0, "coverage ({} weights): {} lines, {} empty intervals; {} runs over {} of {} bases; the device held {} bytes".format(
+                c["weights"], c["lines"], c["empty_intervals"], c["runs"], c["bases_covered"], c["bases_total"], c["state_bytes"]))
         if u is not None:
             log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
                 u["unmapped"], u["reads"], " + ".join(str(b) for b in u["bytes"]), "FASTQ" if self.unm.writers[0].format == 2 else "FASTA"))
@@ -393,7 +443,8 @@ class _MappingsRun:
 def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
+                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -453,11 +504,23 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     lib_format="A" detects the library format from the first batches' records (quant.quantify: the detect_* keywords and
     lib_format_counts pass through **kw; whether mate 2 exists says which records vote) and writes aux/lib_format_counts.json; with
     rescue_mates=True it is a ValueError before anything is indexed: the rescue needs to know that the pairs face inward.
+    write_coverage: a path (or a binary file object) that receives the coverage of the transcripts as bedGraph -- name, start, end,
+    depth, 0-based and half open, a row per maximal stretch of equal nonzero depth, no header line -- accumulated, scanned and
+    formatted on the device (coverage.CoverageDevice); aux/coverage_summary.tsv gets every transcript's covered fraction, mean and
+    largest depth.  It is the coverage of the mappings file the same options would write: the records after rescue and validation,
+    the gapped alignment's intervals iff mappings_gapped=True, else the recorded diagonal, a pair's two lines counted each.
+    coverage_weights="posterior" (the default) weighs a record by the posterior probability the ZW tag is made from, so the reads
+    pass twice as with mappings_posteriors -- also without write_mappings, no mappings file being opened then -- and a run whose
+    quantification failed writes no coverage file and says so in the log; "uniform" gives each of a read's n records 1 / n and
+    accumulates in the first pass; anything else is a ValueError before anything is indexed, as is coverage_compress=True (a BGZF
+    file, encoded on the device) without write_coverage.  The estimates never depend on it; the counters are left on the experiment
+    as `coverage_stats` (None without the option) and go to sopt.jointLog as one line.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors)
-    if run.posteriors and sopt is None:                      # (the second pass reads the columns under the options the run had)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
+                       write_coverage, coverage_weights, coverage_compress, out_dir)
+    if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()
     idx = QuasiIndex(sequences, k=k, device=device)
@@ -483,6 +546,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device,
                                  paired_library=reads2 is not None, **seq_kw, **kw)
         run.second_pass(rc, exp, sopt, names, idx, batches)
+        run.write_coverage(names, sopt)
     finally:
         run.close()
         idx.close()
@@ -502,7 +566,8 @@ def _dollar_separated(bases, off):
 def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_dir, sopt=None, *, k=31, batch_reads=1_000_000, device="cuda",
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
-                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False, **kw):
+                   write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
+                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -517,13 +582,15 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     same ReadFile options.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
     as they came in -- each mate file's own names up to the first space or tab (names="device" on both files), bases and quality lines
     (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
-    FASTA unmapped file.  No name, base or offset visits the host.
+    FASTA unmapped file.  No name, base or offset visits the host.  write_coverage, coverage_weights and coverage_compress as in
+    quantify_reads.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
-                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors)
-    if run.posteriors and sopt is None:                      # (the second pass reads the columns under the options the run had)
+                       mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
+                       write_coverage, coverage_weights, coverage_compress, out_dir)
+    if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()
     names, (bases, off) = read_transcripts(transcripts_path, device, inflate=inflate)
@@ -567,6 +634,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
         rc, exp = quant.quantify(names, idx.ref_len.cpu().numpy().view(np.uint32), batches(), lib_format, out_dir, sopt, device=device,
                                  paired_library=reads2_path is not None, **seq_kw, **kw)
         run.second_pass(rc, exp, sopt, names, idx, batches)
+        run.write_coverage(names, sopt)
     finally:
         run.close()
         idx.close()

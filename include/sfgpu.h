@@ -1694,6 +1694,57 @@ SFGPU_API int sfgpu_cov_write_text(sfgpu_cov* c, const char* d_names, const uint
 SFGPU_API int sfgpu_cov_write_bgzf(sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_bgzw* z,
                                    sfgpu_cov_result* out, sfgpu_stream stream);
 
+/* The coverage of the chromosomes: a finished sfgpu_cov's runs projected through the transcripts' exon blocks, summed per genomic base,
+ * and its bedGraph file (the rule is stated once in csrc/covgfmt.h; hits.coverage_genome_host is the Python statement).
+ *   open     the model, read once and copied onto the handle: d_status[M] (0 = placed, anything else not), d_chrom[M] and d_strand[M]
+ *            (+1 / -1; both read for placed transcripts only), d_exon_off[M + 1] and the blocks d_exon_start / d_exon_len
+ *            [d_exon_off[M]] in TRANSCRIPT order, 0-based.  It is validated on the device: the offsets start at 0 and never decrease;
+ *            every block has 1 <= len and start + len <= 2^32 - 1; a placed transcript has a chromosome below n_chrom, a strand of
+ *            +1 or -1, and blocks that ascend on + and descend on - without overlapping (touching is fine).  A model that fails:
+ *            SFGPU_ERR_INVALID with the lowest offending transcript in the error text.  2^32 - 1 blocks or more: SFGPU_ERR_RANGE.
+ *            The handle also keeps the 64-bit prefix sums of the block lengths, which place a block in its transcript.
+ *   project  `finished` is a handle after sfgpu_cov_finish (before: SFGPU_ERR_STATE; another M than the model's: SFGPU_ERR_INVALID).
+ *            A lane per transcript run finds its first and last block by binary search and leaves the piece count; the counts are
+ *            scanned; runs of up to 8 pieces write their events (key = chrom << 32 | position, +sum at a piece's start, -sum at its
+ *            end) a lane each, longer ones a wavefront each in a second launch.  The keys are sorted with the event index as payload,
+ *            the 64-bit deltas gathered and scanned inclusively: the sum after a key's LAST event is the sum that holds from it on
+ *            (a key's delta is the difference of the scan across its events -- a segmented sum by subtraction, no atomics on the
+ *            sums).  The last events of the keys are compacted; a key whose sum equals the key's before it has delta 0 and neither
+ *            opens nor closes anything; the runs are counted, placed by a scan and written as (chrom, start, end, sum), by chromosome,
+ *            then start.  2^32 - 1 events or more: SFGPU_ERR_RANGE, and the handle keeps what it had.  May be called again (for
+ *            instance after a refusal); the last result is the one runs and write show.
+ *   event_cap  for tests: projections of this handle refuse `cap` events or more (0, or anything above it: the 2^32 - 1 of the rule).
+ *   runs     copies of the result into the caller's device arrays (n_runs entries; a NULL pointer is skipped); before project:
+ *            SFGPU_ERR_STATE.
+ *   write    the rows chrom \t start \t end \t %g(sum 2^-32) \n through the transcript file's formatter and chunk loop:
+ *            d_chrom_names / d_chrom_name_off[n_chrom + 1], chunk_bytes, sink and z as in sfgpu_cov_write_text / _bgzf.  Before
+ *            project: SFGPU_ERR_STATE.
+ * Synchronous. */
+typedef struct sfgpu_covg sfgpu_covg;
+typedef struct sfgpu_covg_result {
+    uint64_t n_pieces, n_events;
+    uint64_t n_keys;                  /* distinct keys whose delta is not 0 */
+    uint64_t n_runs, bases_covered;
+    uint64_t runs_unplaced, bases_unplaced;         /* runs of transcripts that are not placed, dropped whole */
+    uint64_t bases_off_model;         /* bases of placed transcripts' runs at or beyond the blocks' total length */
+    uint64_t transcripts_placed;
+    uint64_t transcripts_length_mismatch;           /* placed, and the blocks' total length is not the transcript's */
+    uint64_t state_bytes;             /* device memory held at the projection's peak, scratch included */
+    uint64_t n_bytes, n_chunks, max_row_bytes;      /* of a write */
+    double project_ms, format_ms, d2h_ms, sink_ms;
+    double emit_ms, sort_ms, sum_ms, runs_ms;       /* project_ms by stage: count, scan and emit; the sort; gather and scan; the runs */
+} sfgpu_covg_result;
+SFGPU_API int sfgpu_covg_open(sfgpu_covg** out, const uint8_t* d_status, const int32_t* d_chrom, const int8_t* d_strand, const uint64_t* d_exon_off,
+                              const uint32_t* d_exon_start, const uint32_t* d_exon_len, uint64_t M, uint32_t n_chrom, sfgpu_stream stream);
+SFGPU_API int sfgpu_covg_close(sfgpu_covg* g);
+SFGPU_API int sfgpu_covg_event_cap(sfgpu_covg* g, uint64_t cap);
+SFGPU_API int sfgpu_covg_project(sfgpu_covg* g, sfgpu_cov* finished, sfgpu_covg_result* out, sfgpu_stream stream);
+SFGPU_API int sfgpu_covg_runs(sfgpu_covg* g, uint32_t* d_chrom, uint32_t* d_start, uint32_t* d_end, uint64_t* d_sum);
+SFGPU_API int sfgpu_covg_write_text(sfgpu_covg* g, const char* d_chrom_names, const uint64_t* d_chrom_name_off, uint64_t chunk_bytes,
+                                    sfgpu_text_sink sink, void* user, sfgpu_covg_result* out, sfgpu_stream stream);
+SFGPU_API int sfgpu_covg_write_bgzf(sfgpu_covg* g, const char* d_chrom_names, const uint64_t* d_chrom_name_off, uint64_t chunk_bytes, sfgpu_bgzw* z,
+                                    sfgpu_covg_result* out, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

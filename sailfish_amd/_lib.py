@@ -350,6 +350,15 @@ class CovResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CovgResult(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_pieces", "n_events", "n_keys", "n_runs", "bases_covered", "runs_unplaced", "bases_unplaced", "bases_off_model",
+                                          "transcripts_placed", "transcripts_length_mismatch", "state_bytes", "n_bytes", "n_chunks", "max_row_bytes")] + \
+               [(k, C.c_double) for k in ("project_ms", "format_ms", "d2h_ms", "sink_ms", "emit_ms", "sort_ms", "sum_ms", "runs_ms")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
     "sfgpu_has_variants": (C.c_int, []),
@@ -461,6 +470,13 @@ _SIGS = {
     "sfgpu_cov_summary": (C.c_int, [_P, _P, _P, _P]),
     "sfgpu_cov_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(CovResult), _P]),
     "sfgpu_cov_write_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(CovResult), _P]),
+    "sfgpu_covg_open": (C.c_int, [C.POINTER(_P), _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P]),
+    "sfgpu_covg_close": (C.c_int, [_P]),
+    "sfgpu_covg_event_cap": (C.c_int, [_P, C.c_uint64]),
+    "sfgpu_covg_project": (C.c_int, [_P, _P, C.POINTER(CovgResult), _P]),
+    "sfgpu_covg_runs": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sfgpu_covg_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(CovgResult), _P]),
+    "sfgpu_covg_write_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(CovgResult), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

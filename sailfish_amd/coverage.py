@@ -27,6 +27,12 @@ def coverage_text_host(names, runs):
                     for t, a, b, s in zip(tid.tolist(), start.tolist(), end.tolist(), total.tolist()))
 
 
+def genome_text_host(chrom_names, runs):
+    """The bytes of the genome bedGraph file for hits.coverage_genome_host's runs (chrom, start, end, sum): coverage_text_host's rows with
+    the chromosomes' names in place of the transcripts'"""
+    return coverage_text_host(chrom_names, runs)
+
+
 def summary_text_host(names, ref_len, summary):
     """The bytes of aux/coverage_summary.tsv for coverage_host's summary: the header and quantfile.format_rows over the three columns"""
     return SUMMARY_HEADER + quantfile.format_rows(names, ref_len, *summary)
@@ -141,39 +147,10 @@ class CoverageDevice:
         blob, off = _device_names(names, self.device)
         if off.numel() != self.M + 1:
             raise ValueError(f"{off.numel() - 1} names for {self.M} transcripts")
-        own = isinstance(path_or_file, (str, bytes, os.PathLike))
-        f = open(path_or_file, "wb") if own else path_or_file
-        res = _lib.CovResult()
-        raised = []
-
-        def sink(addr, n, _user):
-            try:                                   # nothing may unwind through the C frame
-                f.write(memoryview((C.c_char * n).from_address(addr)))
-                return 0
-            except BaseException as e:             # noqa: BLE001  (re-raised below)
-                raised.append(e)
-                return 1
-
         args = (self._h, _lib.ptr(blob) if blob.numel() else None, _lib.ptr(off), int(chunk_bytes))
-        try:
-            with torch.cuda.device(self.device):
-                torch.cuda.current_stream().synchronize()
-                if not compress:
-                    rc = self._L.sfgpu_cov_write_text(*args, _lib.TEXT_SINK(sink), None, C.byref(res), _lib.current_stream_ptr())
-                else:
-                    from . import gzfile
-                    z = gzfile.BgzfDeviceWriter(f, chunk_bytes=int(chunk_bytes))
-                    z._open(self.device)
-                    rc = self._L.sfgpu_cov_write_bgzf(*args, z._h, C.byref(res), _lib.current_stream_ptr())
-                    raised = z._raised
-                    z.close()
-            if raised:
-                raise raised[0]
-            _lib.check(rc)
-        finally:
-            if own:
-                f.close()
-        return res.as_dict()
+        return _write_rows(path_or_file, self.device, compress, chunk_bytes, _lib.CovResult(),
+                           lambda sink, res: self._L.sfgpu_cov_write_text(*args, sink, None, C.byref(res), _lib.current_stream_ptr()),
+                           lambda z, res: self._L.sfgpu_cov_write_bgzf(*args, z, C.byref(res), _lib.current_stream_ptr()))
 
     def write_summary(self, path_or_file, names):
         frac, mean, maxd = self.summary()
@@ -188,11 +165,138 @@ class CoverageDevice:
             if own:
                 f.close()
 
+    def project(self, placement):
+        """-> GenomeCoverageDevice: the runs projected through `placement` (genes.ExonModel.for_names of this coverage's transcripts)
+        onto the chromosomes and summed per genomic base, on the device (sfgpu_covg_*)"""
+        self._finished()
+        return GenomeCoverageDevice(self, placement)
+
     def close(self):
         if self._h is not None:
             h, self._h = self._h, None
             with torch.cuda.device(self.device):
                 self._L.sfgpu_cov_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+
+def _write_rows(f_or_path, device, compress, chunk_bytes, result, text_call, bgzf_call):
+    """one bedGraph file through a sink (text_call(sink, result)) or the device's BGZF encoder (bgzf_call(handle, result))"""
+    own = isinstance(f_or_path, (str, bytes, os.PathLike))
+    f = open(f_or_path, "wb") if own else f_or_path
+    raised = []
+
+    def sink(addr, n, _user):
+        try:                                   # nothing may unwind through the C frame
+            f.write(memoryview((C.c_char * n).from_address(addr)))
+            return 0
+        except BaseException as e:             # noqa: BLE001  (re-raised below)
+            raised.append(e)
+            return 1
+
+    try:
+        with torch.cuda.device(device):
+            torch.cuda.current_stream().synchronize()
+            if not compress:
+                rc = text_call(_lib.TEXT_SINK(sink), result)
+            else:
+                from . import gzfile
+                z = gzfile.BgzfDeviceWriter(f, chunk_bytes=int(chunk_bytes))
+                z._open(device)
+                rc = bgzf_call(z._h, result)
+                raised = z._raised
+                z.close()
+        if raised:
+            raise raised[0]
+        _lib.check(rc)
+    finally:
+        if own:
+            f.close()
+    return result.as_dict()
+
+
+class GenomeCoverageDevice:
+    """GenomeCoverageDevice(coverage, placement): a finished CoverageDevice's runs projected onto the chromosomes (csrc/covgfmt.h;
+    hits.coverage_genome_host is the statement).  placement: genes.ExonModel.for_names' result for the coverage's transcripts; a model
+    the device refuses is an SfgpuError naming the lowest offending transcript.  Usually made by CoverageDevice.project.
+    result   the projection's dict (hits.GENOME_COVERAGE_STATS, state_bytes, project_ms)
+    runs() -> (chrom int32, start int32, end int32, sum int64) device tensors (the bits of the unsigned values)
+    write(path_or_file, chrom_names, compress=False, chunk_bytes=0)   the bedGraph file, one row per run, named by chromosome;
+        compress=True: BGZF; -> the write's result dict
+    close() frees the device arrays; usable as a context manager."""
+
+    def __init__(self, coverage, placement, _event_cap=0):
+        self._L = _lib.lib()
+        self.device, self.M = coverage.device, coverage.M
+        dev = lambda a, dt, bits: torch.from_numpy(np.ascontiguousarray(a, dt).view(bits).copy()).to(self.device)      # noqa: E731
+        model = (dev(placement.status, np.uint8, np.uint8), dev(placement.chrom, np.int32, np.int32), dev(placement.strand, np.int8, np.int8),
+                 dev(placement.exon_off, np.uint64, np.int64), dev(placement.exon_start, np.uint32, np.int32), dev(placement.exon_len, np.uint32, np.int32))
+        if model[0].numel() != self.M or model[1].numel() != self.M or model[2].numel() != self.M or model[3].numel() != self.M + 1:
+            raise ValueError(f"the placement is not one of {self.M} transcripts")
+        E = int(placement.exon_off[-1])
+        if model[4].numel() != E or model[5].numel() != E:
+            raise ValueError(f"the placement's offsets end at {E} but it holds {model[4].numel()} block starts and {model[5].numel()} lengths")
+        self.n_chrom = int(placement.n_chrom)
+        self._h = None
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _lib.check(self._L.sfgpu_covg_open(C.byref(h), *(_lib.ptr(t) if t.numel() else None for t in model[:3]), _lib.ptr(model[3]),
+                                               *(_lib.ptr(t) if t.numel() else None for t in model[4:]), self.M, self.n_chrom, _lib.current_stream_ptr()))
+        self._h = h
+        if _event_cap:
+            _lib.check(self._L.sfgpu_covg_event_cap(self._h, int(_event_cap)))
+        self.result = None
+        self.project(coverage)
+
+    def project(self, coverage):
+        """the projection of `coverage` (finished, of as many transcripts); a refusal leaves the last result in place"""
+        if self._h is None or coverage._h is None:
+            raise ValueError("the coverage is closed")
+        res = _lib.CovgResult()
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _lib.check(self._L.sfgpu_covg_project(self._h, coverage._h, C.byref(res), _lib.current_stream_ptr()))
+        d = res.as_dict()
+        self.result = {k: d[k] for k in d if k not in ("n_bytes", "n_chunks", "max_row_bytes", "format_ms", "d2h_ms", "sink_ms")}
+        return self.result
+
+    def runs(self):
+        if self._h is None:
+            raise ValueError("the genome coverage is closed")
+        n = self.result["n_runs"]
+        chrom, start, end = (torch.zeros(n, dtype=torch.int32, device=self.device) for _ in range(3))
+        total = torch.zeros(n, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.sfgpu_covg_runs(self._h, *(_lib.ptr(t) if n else None for t in (chrom, start, end, total))))
+        return chrom, start, end, total
+
+    def write(self, path_or_file, chrom_names, compress=False, chunk_bytes=0):
+        if self._h is None:
+            raise ValueError("the genome coverage is closed")
+        blob, off = _device_names(chrom_names, self.device)
+        if off.numel() != self.n_chrom + 1:
+            raise ValueError(f"{off.numel() - 1} names for {self.n_chrom} chromosomes")
+        args = (self._h, _lib.ptr(blob) if blob.numel() else None, _lib.ptr(off), int(chunk_bytes))
+        return _write_rows(path_or_file, self.device, compress, chunk_bytes, _lib.CovgResult(),
+                           lambda sink, res: self._L.sfgpu_covg_write_text(*args, sink, None, C.byref(res), _lib.current_stream_ptr()),
+                           lambda z, res: self._L.sfgpu_covg_write_bgzf(*args, z, C.byref(res), _lib.current_stream_ptr()))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            with torch.cuda.device(self.device):
+                self._L.sfgpu_covg_close(h)
 
     def __enter__(self):
         return self

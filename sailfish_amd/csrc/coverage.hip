@@ -18,31 +18,19 @@
 //                   search of the bases, once a run.
 //   k_cov_summary   a wavefront per transcript strides over its bases: covered, the 128-bit sum as two words with the carry, the
 //                   maximum; a butterfly folds the lanes (integer sums: any tree gives the same bits) and lane 0 writes the columns.
-//   write           k_cov_decode / k_cov_decode_slow: the six-digit record of every run's depth; k_cov_row_size: a lane per run sizes
-//                   its row; a scan places the rows; k_cov_format: a block per 4 KB tile of the output formats the rows that touch
-//                   it in LDS (texttile.h; long names by the whole block) and every lane stores 16 bytes.  The chunks are planned and
-//                   delivered by textchunks.h, to the sink or on the device to the BGZF encoder.
+//   write           cov_write, over a run table (covwrite.h: the genome coverage calls it too): k_cov_decode / k_cov_decode_slow: the
+//                   six-digit record of every run's depth; k_cov_row_size: a lane per run sizes its row; a scan places the rows;
+//                   k_cov_format: a block per 4 KB tile of the output formats the rows that touch it in LDS (texttile.h; long names
+//                   by the whole block) and every lane stores 16 bytes.  The chunks are planned and delivered by textchunks.h, to
+//                   the sink or on the device to the BGZF encoder.
 #include "common.h"
 #include "coverfmt.h"
+#include "covwrite.h"
 #include "hitgroup.h"
 #include "primitives.h"
 #include "texttile.h"
 
 #include <cstring>
-
-struct sfgpu_cov {
-    uint64_t M = 0, N = 0;                                 // transcripts, slots
-    sfgpu::DevBuf<uint64_t> base, slot;                    // base[M + 1], slot[N]
-    sfgpu_cov_stats stats{};
-    bool finished = false;
-    sfgpu_cov_result res{};
-    sfgpu::DevBuf<uint32_t> r_tid, r_start, r_end;         // the runs
-    sfgpu::DevBuf<uint64_t> r_sum;
-    sfgpu::DevBuf<double> col;                             // CoveredFraction[M], MeanDepth[M], MaxDepth[M]
-    uint64_t state_bytes() const {
-        return 8 * (base.cap + slot.cap + r_sum.cap + col.cap) + 4 * (r_tid.cap + r_start.cap + r_end.cap);
-    }
-};
 
 namespace sfgpu {
 namespace {
@@ -300,17 +288,16 @@ struct WriteScratch {
     DevBuf<unsigned long long> misc;                       // [0] name table flags, [1] the longest row
 };
 
-int cov_write(const char* who, sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
-              sfgpu_bgzw* z, sfgpu_cov_result* out, sfgpu_stream stream) {
+}  // namespace
+
+// `out` starts zeroed; the caller has checked its handle and copies the figures into its own result
+int cov_write(const char* who, const CovRunTable& T, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+              sfgpu_bgzw* z, CovWriteStats* out, sfgpu_stream stream) {
     auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
-    if (!c || !out) return fail(SFGPU_ERR_INVALID, "null handle or result");
-    if (!c->finished) return fail(SFGPU_ERR_STATE, "called before sfgpu_cov_finish");
-    *out = c->res;
-    out->n_bytes = out->n_chunks = out->max_row_bytes = 0;
-    out->format_ms = out->d2h_ms = out->sink_ms = 0.0;
+    *out = CovWriteStats{};
     if (chunk_bytes == 0) chunk_bytes = kDefaultChunk;
     if (!(chunk_bytes >= 16 && chunk_bytes <= kMaxChunk)) return fail(SFGPU_ERR_INVALID, "chunk_bytes must lie in [16, 2^30] (0 = default)");
-    const uint64_t n_rows = c->res.n_runs, M = c->M;
+    const uint64_t n_rows = T.n_rows, M = T.n_names;
     if (n_rows == 0) return SFGPU_OK;
     if (!d_name_off) return fail(SFGPU_ERR_INVALID, "null name offsets");
     if (!(n_rows < kMaxRows)) return fail(SFGPU_ERR_RANGE, "the runs must be fewer than 2^32 - 1");
@@ -345,12 +332,12 @@ int cov_write(const char* who, sfgpu_cov* c, const char* d_names, const uint64_t
     if (int rc = S.row_len.reserve(n_rows + 1, st, false)) return rc;
     if (int rc = S.row_start.reserve(n_rows + 1, st, false)) return rc;
     SF_HIP(hipEventRecord(ev_s[0], st));
-    hipLaunchKernelGGL(k_cov_decode, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, (const uint64_t*)c->r_sum.p, n_rows, S.rec.p);
+    hipLaunchKernelGGL(k_cov_decode, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, T.sum, n_rows, S.rec.p);
     SF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cov_decode_slow, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, (const uint64_t*)c->r_sum.p, n_rows, S.rec.p);
+    hipLaunchKernelGGL(k_cov_decode_slow, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, T.sum, n_rows, S.rec.p);
     SF_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_cov_row_size, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_name_off, (const uint32_t*)c->r_tid.p, (const uint32_t*)c->r_start.p,
-                       (const uint32_t*)c->r_end.p, (const uint32_t*)S.rec.p, n_rows, S.row_len.p);
+    hipLaunchKernelGGL(k_cov_row_size, dim3(grid_of(n_rows)), dim3(kBlock), 0, st, d_name_off, T.id, T.start,
+                       T.end, (const uint32_t*)S.rec.p, n_rows, S.row_len.p);
     SF_HIP(hipGetLastError());
     if (int rc = exclusive_scan_u32(S.row_len.p, S.row_start.p, n_rows, st, false)) return rc;
     if (int rc = textchunks::line_max(S.row_start.p, n_rows, S.misc.p + 1, st)) return rc;
@@ -367,8 +354,8 @@ int cov_write(const char* who, sfgpu_cov* c, const char* d_names, const uint64_t
     // ---- the chunk plan and the format + copy + sink loop (textchunks.h), with this text's tiles
     textchunks::Stats ts;
     auto format_tiles = [&](uint64_t first_tile, uint64_t last_tile, uint64_t out_base, uint4* buf, hipStream_t s) -> int {
-        hipLaunchKernelGGL(k_cov_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_names, d_name_off, (const uint32_t*)c->r_tid.p,
-                           (const uint32_t*)c->r_start.p, (const uint32_t*)c->r_end.p, (const uint32_t*)S.rec.p, (const uint64_t*)S.row_start.p, n_rows, total,
+        hipLaunchKernelGGL(k_cov_format, dim3((unsigned)(last_tile - first_tile + 1)), dim3(kBlock), 0, s, d_names, d_name_off, T.id,
+                           T.start, T.end, (const uint32_t*)S.rec.p, (const uint64_t*)S.row_start.p, n_rows, total,
                            first_tile, out_base, buf);
         SF_HIP(hipGetLastError());
         return SFGPU_OK;
@@ -383,7 +370,6 @@ int cov_write(const char* who, sfgpu_cov* c, const char* d_names, const uint64_t
     return rc;
 }
 
-}  // namespace
 }  // namespace sfgpu
 
 using namespace sfgpu;
@@ -560,13 +546,28 @@ extern "C" int sfgpu_cov_summary(sfgpu_cov* c, double* d_covered_fraction, doubl
     return SFGPU_OK;
 }
 
+// the checks of the handle and the result's fields around covwrite.h's cov_write
+static int cov_write_handle(const char* who, sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
+                            sfgpu_bgzw* z, sfgpu_cov_result* out, sfgpu_stream stream) {
+    auto fail = [&](int code, const char* what) -> int { set_error("%s: %s", who, what); return code; };
+    if (!c || !out) return fail(SFGPU_ERR_INVALID, "null handle or result");
+    if (!c->finished) return fail(SFGPU_ERR_STATE, "called before sfgpu_cov_finish");
+    *out = c->res;
+    const CovRunTable T = {c->r_tid.p, c->r_start.p, c->r_end.p, c->r_sum.p, c->res.n_runs, c->M};
+    CovWriteStats w;
+    const int rc = cov_write(who, T, d_names, d_name_off, chunk_bytes, sink, user, z, &w, stream);
+    out->n_bytes = w.n_bytes; out->n_chunks = w.n_chunks; out->max_row_bytes = w.max_row_bytes;
+    out->format_ms = w.format_ms; out->d2h_ms = w.d2h_ms; out->sink_ms = w.sink_ms;
+    return rc;
+}
+
 extern "C" int sfgpu_cov_write_text(sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_text_sink sink, void* user,
                                     sfgpu_cov_result* out, sfgpu_stream stream) {
-    return cov_write("sfgpu_cov_write_text", c, d_names, d_name_off, chunk_bytes, sink, user, nullptr, out, stream);
+    return cov_write_handle("sfgpu_cov_write_text", c, d_names, d_name_off, chunk_bytes, sink, user, nullptr, out, stream);
 }
 
 extern "C" int sfgpu_cov_write_bgzf(sfgpu_cov* c, const char* d_names, const uint64_t* d_name_off, uint64_t chunk_bytes, sfgpu_bgzw* z, sfgpu_cov_result* out,
                                     sfgpu_stream stream) {
     SF_REQUIRE(z, SFGPU_ERR_INVALID, "sfgpu_cov_write_bgzf: null BGZF handle");
-    return cov_write("sfgpu_cov_write_bgzf", c, d_names, d_name_off, chunk_bytes, nullptr, nullptr, z, out, stream);
+    return cov_write_handle("sfgpu_cov_write_bgzf", c, d_names, d_name_off, chunk_bytes, nullptr, nullptr, z, out, stream);
 }

@@ -22,6 +22,7 @@ handling is restated from its use there: every record that carries a transcript_
 the grouping key is gene_id, gene_name, or any attribute named by `agg_key`; transcripts are ordered by name, genes
 numbered by first appearance in that order.  Parity unpinned for this reader (no reference vector exists for it)."""
 import bisect
+import collections
 import ctypes as C
 import gzip
 import os
@@ -33,6 +34,18 @@ import numpy as np
 from .writer import fmt_g
 
 DENORM_MIN = 4.9406564584124654e-324
+
+
+def _gtf_attrs(col8):
+    """column 9 of a GTF record, `key "value"; key "value"; ...` -> {key: value}, the first value of a key kept"""
+    attrs = {}
+    for field in col8.split(";"):
+        field = field.strip()
+        if not field:
+            continue
+        k, _, v = field.partition(" ")
+        attrs.setdefault(k, v.strip().strip('"'))
+    return attrs
 
 
 class TranscriptGeneMap:
@@ -65,13 +78,7 @@ class TranscriptGeneMap:
             cols = line.rstrip("\n").split("\t")
             if len(cols) < 9:
                 continue
-            attrs = {}
-            for field in cols[8].split(";"):
-                field = field.strip()
-                if not field:
-                    continue
-                k, _, v = field.partition(" ")
-                attrs.setdefault(k, v.strip().strip('"'))
+            attrs = _gtf_attrs(cols[8])
             t = attrs.get("transcript_id")
             if not t:
                 continue                                                  # gene records and the like: not a transcript (isTranscript())
@@ -151,6 +158,89 @@ class TranscriptGeneMap:
             ids[own] = uid[inv.reshape(-1)]
             table += uniq[~hit].tolist()
         return ids.astype(np.uint32), table
+
+
+EXON_STATUS = {0: "placed", 1: "absent from the annotation", 2: "exons on more than one chromosome or strand", 3: "a strand other than + or -",
+               4: "two exons overlap"}
+Placement = collections.namedtuple("Placement", "status chrom strand exon_off exon_start exon_len n_chrom chrom_names")
+
+
+class ExonModel:
+    """The exon structure of an annotation's transcripts, for the genome coverage track (csrc/covgfmt.h's MODEL).  from_gtf reads it on
+    the host, once a run; for_names joins it to a run's transcripts.
+    chrom_names   the chromosomes' names (bytes, as the file has them), numbered in BYTEWISE order -- the order `LC_ALL=C sort -k1,1`
+                  leaves, so the coverage file comes out sorted the way bedGraphToBigWig wants it
+    transcripts   {transcript_id bytes: (status, chrom id, strand +1 / -1 / 0, [(start0, len), ...] in transcript order)}; the blocks
+                  only where status is 0 (EXON_STATUS)"""
+
+    def __init__(self, chrom_names, transcripts):
+        self.chrom_names, self.transcripts = list(chrom_names), dict(transcripts)
+
+    @classmethod
+    def from_gtf(cls, path):
+        """Plain or gzip (by its magic bytes).  gtffmt.h's line rules: lines that start with # and lines of fewer than 9 tab-separated
+        columns are skipped, a \\r before the \\n is dropped.  A line counts iff column 3 is exactly `exon` and column 9 carries a
+        transcript_id that is not empty (TranscriptGeneMap.from_gtf's fields).  Column 1, the chromosome, must not be empty; columns
+        4 and 5 are decimal with 1 <= start <= end <= 4294967295; anything else is a ValueError naming the 1-based line.  A
+        transcript's exons are sorted by start and, on -, reversed; its status is 2 where they name more than one chromosome or
+        strand, else 3 where the strand is neither + nor -, else 4 where two of them overlap (identical ones included; touching
+        ones are fine), else 0."""
+        with open(path, "rb") as f:
+            magic = f.read(2)
+        with (gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")) as f:
+            data = f.read()
+        seen = {}                                                         # transcript_id -> [set of (chrom, strand), [(start0, len)]]
+        for no, line in enumerate(data.split(b"\n"), 1):
+            if line.endswith(b"\r"):
+                line = line[:-1]
+            if line.startswith(b"#"):
+                continue
+            cols = line.split(b"\t")
+            if len(cols) < 9 or cols[2] != b"exon":
+                continue
+            t = _gtf_attrs(cols[8].decode("latin-1")).get("transcript_id")
+            if not t:
+                continue
+            if not cols[0]:
+                raise ValueError(f"{path}: line {no}: an exon without a chromosome name")
+            if not (cols[3].isdigit() and cols[4].isdigit() and cols[3].isascii() and cols[4].isascii()):
+                raise ValueError(f"{path}: line {no}: the exon's start and end must be decimal integers")
+            a, b = int(cols[3]), int(cols[4])
+            if not 1 <= a <= b <= 4294967295:
+                raise ValueError(f"{path}: line {no}: an exon needs 1 <= start <= end <= 4294967295, not {a} and {b}")
+            where, blocks = seen.setdefault(t.encode("latin-1"), [set(), []])
+            where.add((cols[0], cols[6]))
+            blocks.append((a - 1, b - a + 1))
+        chrom_names = sorted({c for where, _ in seen.values() for c, _ in where})
+        chrom_id = {c: i for i, c in enumerate(chrom_names)}
+        transcripts = {}
+        for t, (where, blocks) in seen.items():
+            (c, strand), blocks = next(iter(where)), sorted(blocks)
+            if len(where) > 1:
+                transcripts[t] = (2, -1, 0, [])
+            elif strand not in (b"+", b"-"):
+                transcripts[t] = (3, -1, 0, [])
+            elif any(x[0] + x[1] > y[0] for x, y in zip(blocks, blocks[1:])):
+                transcripts[t] = (4, -1, 0, [])
+            else:
+                transcripts[t] = (0, chrom_id[c], 1 if strand == b"+" else -1, blocks if strand == b"+" else blocks[::-1])
+        return cls(chrom_names, transcripts)
+
+    def for_names(self, names):
+        """The model joined to a run's transcripts by exact byte equality of the names (str as UTF-8), the gene map's rule: a transcript
+        the annotation does not have gets status 1.  -> Placement(status uint8[M], chrom int32[M], strand int8[M], exon_off int64[M + 1],
+        exon_start uint32[E], exon_len uint32[E], n_chrom, chrom_names): what sfgpu_covg_open and hits.coverage_genome_host take."""
+        M = len(names)
+        status, chrom, strand, off = np.ones(M, np.uint8), np.full(M, -1, np.int32), np.zeros(M, np.int8), np.zeros(M + 1, np.int64)
+        starts, lens = [], []
+        for i, n in enumerate(names):
+            rec = self.transcripts.get(n.encode("utf-8") if isinstance(n, str) else bytes(n))
+            if rec is not None:
+                status[i], chrom[i], strand[i] = rec[:3]
+                starts += [b[0] for b in rec[3]]
+                lens += [b[1] for b in rec[3]]
+            off[i + 1] = len(starts)
+        return Placement(status, chrom, strand, off, np.array(starts, np.uint32), np.array(lens, np.uint32), len(self.chrom_names), list(self.chrom_names))
 
 
 HOST_REASONS = {1: "a byte >= 0x80", 2: "a NUL byte", 4: "a '\\r' that is not followed by '\\n'", 8: "a name longer than 256 bytes"}

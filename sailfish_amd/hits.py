@@ -1176,3 +1176,66 @@ def sample_bias(hits, hit_offsets, lib_format, seq, seq_off, ref_len, *, read_bi
         torch.cuda.current_stream().synchronize()
         _lib.check(_lib.lib().sfgpu_sample_bias(_lib.ptr(d_hits), _lib.ptr(d_off), R, C.byref(o), C.byref(sp), _lib.current_stream_ptr()))
     return int(rem.value), int(sp.n_bias_sampled), int(sp.n_gc_sampled)
+
+
+GENOME_COVERAGE_STATS = ("n_pieces", "n_events", "n_keys", "n_runs", "bases_covered", "runs_unplaced", "bases_unplaced", "bases_off_model",
+                         "transcripts_placed", "transcripts_length_mismatch")
+
+
+def coverage_genome_host(runs, placement, ref_len=None, with_distinct=False):
+    """The statement of the projection onto the chromosomes (csrc/covgfmt.h restated with Python integers; what sfgpu_covg_* are judged
+    by).  runs: coverage_host's (tid, start, end, sum); placement: genes.ExonModel.for_names' result (status, chrom, strand, exon_off,
+    exon_start, exon_len -- blocks in transcript order).  A run of a placed transcript is cut at its blocks; a piece [lo, hi) on
+    chromosome c adds +sum at key c << 32 | lo and -sum at c << 32 | hi, modulo 2^64; keys whose delta is 0 disappear; the running sum
+    over the ascending keys holds from a key to the next; the stretches of nonzero sum are the runs.  ref_len (the transcripts' lengths)
+    is only compared with the blocks' total for `transcripts_length_mismatch` (0 without it).  with_distinct=True adds two counts the
+    device's grids are sized by and its result does not carry: `n_distinct`, the keys before those of delta 0 are dropped, and `n_long`,
+    the runs of more than 8 pieces.
+    -> (runs = (chrom uint32[], start uint32[], end uint32[], sum uint64[]), stats dict of GENOME_COVERAGE_STATS)"""
+    status, chrom, strand, exon_off, exon_start, exon_len = (np.asarray(getattr(placement, k)) for k in ("status", "chrom", "strand", "exon_off", "exon_start", "exon_len"))
+    M, mask = len(status), (1 << 64) - 1
+    eo = [int(x) for x in exon_off]
+    gs, ln = [int(x) for x in exon_start], [int(x) for x in exon_len]
+    st = dict.fromkeys(GENOME_COVERAGE_STATS, 0)
+    total = [sum(ln[eo[t]:eo[t + 1]]) for t in range(M)]
+    for t in range(M):
+        if status[t] == 0:
+            st["transcripts_placed"] += 1
+            st["transcripts_length_mismatch"] += int(ref_len is not None and total[t] != int(ref_len[t]))
+    delta, n_long = {}, 0
+    for t, a, b, s in zip(*(np.asarray(x).tolist() for x in runs)):
+        if status[t] != 0:
+            st["runs_unplaced"] += 1
+            st["bases_unplaced"] += b - a
+            continue
+        if b > total[t]:
+            st["bases_off_model"] += b - max(a, total[t])
+            b = total[t]
+        c, toff, before = int(chrom[t]) << 32, 0, st["n_pieces"]
+        for e in range(eo[t], eo[t + 1]):
+            a1, b1 = max(a, toff), min(b, toff + ln[e])
+            if a1 < b1:
+                lo, hi = (gs[e] + a1 - toff, gs[e] + b1 - toff) if strand[t] > 0 else (gs[e] + ln[e] - (b1 - toff), gs[e] + ln[e] - (a1 - toff))
+                delta[c | lo] = (delta.get(c | lo, 0) + s) & mask
+                delta[c | hi] = (delta.get(c | hi, 0) - s) & mask
+                st["n_pieces"] += 1
+            toff += ln[e]
+        n_long += st["n_pieces"] - before > 8
+    st["n_events"] = 2 * st["n_pieces"]
+    out, acc = ([], [], [], []), 0
+    for key in sorted(delta):
+        if delta[key] == 0:
+            continue
+        st["n_keys"] += 1
+        if acc:
+            out[2].append(key & 0xFFFFFFFF)
+        acc = (acc + delta[key]) & mask
+        if acc:
+            out[0].append(key >> 32); out[1].append(key & 0xFFFFFFFF); out[3].append(acc)
+    if len(out[2]) != len(out[0]):
+        raise ValueError("a chromosome's deltas do not sum to 0")
+    st["n_runs"] = len(out[0])
+    st["bases_covered"] = sum(e - s for s, e in zip(out[1], out[2]))
+    if with_distinct:
+        st["n_distinct"], st["n_long"] = len(delta), n_long
+    return (np.array(out[0], np.uint32), np.array(out[1], np.uint32), np.array(out[2], np.uint32), np.array(out[3], np.uint64)), st

@@ -239,14 +239,19 @@ class _MappingsRun:
 
     def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                  mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None,
-                 mappings_posteriors=False, write_coverage=None, coverage_weights="posterior", coverage_compress=False, out_dir=None):
+                 mappings_posteriors=False, write_coverage=None, coverage_weights="posterior", coverage_compress=False, out_dir=None,
+                 write_genome_coverage=None, coverage_annotation=None):
         from .hits import ALIGNG_STATS, MDTAG_STATS, POSTERIOR_STATS
         if coverage_weights not in ("posterior", "uniform"):
             raise ValueError(f'coverage_weights is "posterior" or "uniform", not {coverage_weights!r}')
-        if write_coverage is None and coverage_compress:
-            raise ValueError("coverage_compress=True needs write_coverage")
+        if write_coverage is None and write_genome_coverage is None and coverage_compress:
+            raise ValueError("coverage_compress=True needs write_coverage or write_genome_coverage")
         if write_coverage is not None and not _is_sink(write_coverage):
             raise ValueError("write_coverage: one path or binary file object")
+        if (write_genome_coverage is None) != (coverage_annotation is None):
+            raise ValueError("write_genome_coverage and coverage_annotation (the GTF with the exons) come together")
+        if write_genome_coverage is not None and not _is_sink(write_genome_coverage):
+            raise ValueError("write_genome_coverage: one path or binary file object")
         if mappings_sorted and mappings_format != "bam":
             raise ValueError(f'mappings_sorted=True needs mappings_format="bam", not {mappings_format!r}')
         self.rescue, rstats = _rescue(rescue_mates, rescue_window, min_identity, paired, lib_format, sopt)
@@ -268,8 +273,15 @@ class _MappingsRun:
         self.posteriors, self.second, self.weights, self.again = bool(mappings_posteriors), False, None, None
         # The coverage file is that of the records the mappings file shows.  With posterior weights it is accumulated in
         # the second pass, which then runs for it alone too (opening no mappings file); with uniform weights in the first.
+        # The genome file is the same coverage projected through the annotation's exons, so either file opens the
+        # CoverageDevice; the annotation is read here, before anything is indexed: a bad line fails early.
         self.cov_sink, self.cov_compress, self.cov_dir = write_coverage, bool(coverage_compress), out_dir
-        self.cov_posterior = write_coverage is not None and coverage_weights == "posterior"
+        self.covg_sink, self.covg_model, self.covg_stats = write_genome_coverage, None, None
+        if write_genome_coverage is not None:
+            from .genes import ExonModel
+            self.covg_model = ExonModel.from_gtf(coverage_annotation)
+        self.cov_wanted = write_coverage is not None or write_genome_coverage is not None
+        self.cov_posterior = self.cov_wanted and coverage_weights == "posterior"
         self.gapped = bool(mappings_gapped)
         self.two_pass = self.posteriors or self.cov_posterior
         self.cov = self.cov_stats = None
@@ -287,7 +299,7 @@ class _MappingsRun:
             self._open_sam(names, idx)
         if self.unmapped:
             self.unm = _UnmappedWriters(self.targets, self.compress)
-        if self.cov_sink is not None:
+        if self.cov_wanted:
             from .coverage import CoverageDevice
             self.cov = CoverageDevice(idx.ref_len, idx.device)
 
@@ -352,8 +364,10 @@ class _MappingsRun:
             self.post_stats = None
             if self.posteriors:
                 log(1, "mappings_posteriors: the quantification did not succeed (rc {}), so no mappings file is written".format(rc))
-            if self.cov_posterior:
+            if self.cov_posterior and self.cov_sink is not None:
                 log(1, "write_coverage: the quantification did not succeed (rc {}), so no coverage file is written".format(rc))
+            if self.cov_posterior and self.covg_sink is not None:
+                log(1, "write_genome_coverage: the quantification did not succeed (rc {}), so no genome coverage file is written".format(rc))
             return
         from . import writer
         _, _, length, _, est = writer.abundance_columns(exp, sopt)
@@ -371,13 +385,23 @@ class _MappingsRun:
                                    f"({self.stats[name]}): the mappings file does not show the records that were quantified")
 
     def write_coverage(self, names, sopt):
-        """write_coverage=, behind the last pass: the runs found and the rows formatted on the device (coverage.CoverageDevice), the file
-        and aux/coverage_summary.tsv written.  With posterior weights and a quantification that failed there is no second pass and
-        nothing is written."""
+        """write_coverage= and write_genome_coverage=, behind the last pass: the runs found and the rows formatted on the device
+        (coverage.CoverageDevice), the transcript file (only with write_coverage) and aux/coverage_summary.tsv written; then the runs
+        projected onto the chromosomes (coverage.GenomeCoverageDevice) and the genome file written.  With posterior weights and a
+        quantification that failed there is no second pass and nothing is written."""
         if self.cov is None or (self.cov_posterior and not self.second):
             return
         res = self.cov.finish()
-        wrote = self.cov.write(self.cov_sink, names, compress=self.cov_compress)
+        wrote = self.cov.write(self.cov_sink, names, compress=self.cov_compress) if self.cov_sink is not None else dict(n_bytes=0)
+        if self.covg_sink is not None:
+            host = names
+            if isinstance(names, tuple) and isinstance(names[0], torch.Tensor):      # names on the device: their bytes, never decoded
+                blob, off = (x.cpu().numpy() for x in names)
+                host = [blob[a:b].tobytes() for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+            placement = self.covg_model.for_names(host)
+            with self.cov.project(placement) as g:
+                gw = g.write(self.covg_sink, placement.chrom_names, compress=self.cov_compress)
+                self.covg_stats = dict(g.result, transcripts=self.cov.M, bytes=int(gw["n_bytes"]))
         if self.cov_dir is not None:
             aux = os.path.join(self.cov_dir, getattr(sopt, "auxDir", "aux") if sopt is not None else "aux")
             os.makedirs(aux, exist_ok=True)
@@ -400,6 +424,7 @@ class _MappingsRun:
             exp.rescue_stats, exp.verify_stats, exp.align_stats, exp.tag_stats = res, v, a, t
             exp.posterior_stats = ps
             exp.coverage_stats = self.cov_stats
+            exp.genome_coverage_stats = self.covg_stats
             if u is not None:
                 exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
@@ -435,6 +460,16 @@ class _MappingsRun:
             c = self.cov_stats
             log(0, "coverage ({} weights): {} lines, {} empty intervals; {} runs over {} of {} bases; the device held {} bytes".format(
                 c["weights"], c["lines"], c["empty_intervals"], c["runs"], c["bases_covered"], c["bases_total"], c["state_bytes"]))
+        if self.covg_stats is not None:
+            c = self.covg_stats
+            log(0, "genome coverage: {} of {} transcripts placed; {} pieces, {} events; {} runs over {} bases; {} bases dropped as unplaced, {} off the "
+                   "model; the device held {} bytes".format(c["transcripts_placed"], c["transcripts"], c["n_pieces"], c["n_events"], c["n_runs"],
+                                                            c["bases_covered"], c["bases_unplaced"], c["bases_off_model"], c["state_bytes"]))
+            if c["transcripts_placed"] == 0:
+                log(1, "write_genome_coverage: the annotation places none of the {} transcripts (the names are matched byte for byte)".format(c["transcripts"]))
+            if c["transcripts_length_mismatch"] > 0:
+                log(1, "write_genome_coverage: the exons of {} placed transcripts do not sum to the transcript's length; bases beyond the exons "
+                       "are dropped".format(c["transcripts_length_mismatch"]))
         if u is not None:
             log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
                 u["unmapped"], u["reads"], " + ".join(str(b) for b in u["bytes"]), "FASTQ" if self.unm.writers[0].format == 2 else "FASTA"))
@@ -444,7 +479,8 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
                    write_mappings=None, mappings_format="sam", quals1=None, quals2=None, mappings_oriented=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
                    write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
-                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, **kw):
+                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, write_genome_coverage=None, coverage_annotation=None,
+                   **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -513,13 +549,25 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     pass twice as with mappings_posteriors -- also without write_mappings, no mappings file being opened then -- and a run whose
     quantification failed writes no coverage file and says so in the log; "uniform" gives each of a read's n records 1 / n and
     accumulates in the first pass; anything else is a ValueError before anything is indexed, as is coverage_compress=True (a BGZF
-    file, encoded on the device) without write_coverage.  The estimates never depend on it; the counters are left on the experiment
+    file, encoded on the device) without a coverage file.  The estimates never depend on it; the counters are left on the experiment
     as `coverage_stats` (None without the option) and go to sopt.jointLog as one line.
+    write_genome_coverage: a path (or a binary file object) that receives the same coverage in GENOME coordinates -- chromosome, start,
+    end, depth, the rows of write_coverage's shape, sorted by the chromosomes' names bytewise and then by start, which is what
+    bedGraphToBigWig and the genome browsers take -- with coverage_annotation, the GTF (plain or gzip) whose `exon` records place the
+    transcripts: genes.ExonModel reads it on the host before anything is indexed, matches transcript_id to the transcripts' names byte
+    for byte, and the device projects every run through the exon blocks, adds the isoforms' contributions per genomic base and
+    formats the rows (coverage.GenomeCoverageDevice, csrc/covgfmt.h).  Either keyword without the other, or a value that is neither a
+    path nor a binary file object, is a ValueError before anything is indexed.  It works with or without write_coverage (the
+    transcript file is written only with that; aux/coverage_summary.tsv in both cases); coverage_weights and coverage_compress govern
+    both files, and with posterior weights a failed quantification writes neither and the log says so for each.  Transcripts the
+    annotation does not place (genes.EXON_STATUS) and bases beyond a transcript's exons are dropped and counted; the counters are left
+    on the experiment as `genome_coverage_stats` (None without the option) and go to sopt.jointLog as one line, with a warning where
+    no transcript is placed or where exons do not sum to a transcript's length.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                        mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
-                       write_coverage, coverage_weights, coverage_compress, out_dir)
+                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation)
     if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()
@@ -567,7 +615,8 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                    inflate="auto", write_mappings=None, mappings_format="sam", mappings_oriented=False, check_mate_names=False, mappings_sorted=False,
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
                    write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
-                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, **kw):
+                   write_coverage=None, coverage_weights="posterior", coverage_compress=False, write_genome_coverage=None, coverage_annotation=None,
+                   **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -582,14 +631,15 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     same ReadFile options.  write_unmapped and unmapped_compress as in quantify_reads: the reads without a record go out
     as they came in -- each mate file's own names up to the first space or tab (names="device" on both files), bases and quality lines
     (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
-    FASTA unmapped file.  No name, base or offset visits the host.  write_coverage, coverage_weights and coverage_compress as in
-    quantify_reads.
+    FASTA unmapped file.  No name, base or offset visits the host.  write_coverage, coverage_weights, coverage_compress,
+    write_genome_coverage and coverage_annotation as in quantify_reads (the transcripts' names are matched to the annotation by
+    their bytes as the FASTA has them).
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                        mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
-                       write_coverage, coverage_weights, coverage_compress, out_dir)
+                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation)
     if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()

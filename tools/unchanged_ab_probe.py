@@ -11,6 +11,10 @@
    gapped alignments and the tags, validation with max_indel 3, the unmapped reads), writing into a temporary directory: host wall
    time of the whole call.
 
+ - with --coverage-only nothing of the above but, on the verification batch's records, the transcript coverage file
+   (coverage.CoverageDevice: uniform weights, add and finish once, then write into memory, plain and BGZF): host wall time of the
+   write, synchronised, and the format kernels' device time from its result.
+
 Every figure is the median of --repeats (default 7) runs after one warm-up run; all runs are kept.  --root names the tree whose
 `sailfish_amd` is measured (built there beforehand; default: the tree this file is in), so that the same driver measures a checkout
 of the parent commit and this one:
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--pairs", type=int, default=2_000_000)
     ap.add_argument("--transcripts", type=int, default=80_000)
+    ap.add_argument("--coverage-only", action="store_true")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import numpy as np
@@ -62,6 +67,12 @@ def main():
     leg = dict(label=a.label, device=torch.cuda.get_device_name(0), repeats=a.repeats)
 
     # the writers
+    if not a.coverage_only:
+        writers(a, leg, dev, np, torch, samfile, samwrite_probe, med)
+    rest(a, leg, dev, np, torch, sf, _lib, synth, verify_probe, med)
+
+
+def writers(a, leg, dev, np, torch, samfile, samwrite_probe, med):
     rng = np.random.default_rng(23)
     n_reads, read_len, n_refs = 100_000, 100, 30_000
     names = [f"ENST{i:011d}.{i % 9 + 1}" for i in range(n_refs)]
@@ -85,6 +96,32 @@ def main():
                 ms.append(dt); ms_format.append(st["ms_format"])
         leg[fmt] = dict(ms=med(ms), ms_format=med(ms_format), ms_runs=ms, ms_format_runs=ms_format, bytes=n_bytes)
 
+
+
+def coverage_writer(a, leg, dev, torch, sf, tlen, names, h, hoff, med):
+    """the transcript coverage file of the records (h, hoff), plain and BGZF, into memory"""
+    from sailfish_amd import coverage as cov
+    d_names = cov._device_names(names, dev)
+    with cov.CoverageDevice(tlen.to(torch.int32), dev) as c:
+        c.add(h, hoff)
+        res = c.finish()
+        out = dict(runs=res["runs"])
+        for kind, kw in (("text", {}), ("bgzf", dict(compress=True))):
+            ms, fmt, size = [], [], 0
+            for i in range(a.repeats + 1):
+                f = io.BytesIO()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                w = c.write(f, d_names, **kw)
+                torch.cuda.synchronize()
+                if i:
+                    ms.append(1e3 * (time.perf_counter() - t0)); fmt.append(w["format_ms"])
+                size = len(f.getvalue())
+            out[kind] = dict(ms=med(ms), ms_format=med(fmt), ms_runs=ms, ms_format_runs=fmt, bytes=size)
+    leg["coverage_write"] = out
+
+
+def rest(a, leg, dev, np, torch, sf, _lib, synth, verify_probe, med):
     # the gapped scoring pass
     M, R, L, K = a.transcripts, a.pairs, 100, 3
     ACGT = verify_probe.ACGT
@@ -105,6 +142,10 @@ def main():
     r1, r2 = m1.reshape(-1), m2.reshape(-1)
     h, hoff = index.map_reads((r1, roff), (r2, roff))
     n = h.numel() // 24
+    if a.coverage_only:
+        coverage_writer(a, leg, dev, torch, sf, tlen, [f"ENST{i:011d}.{i % 9 + 1}" for i in range(M)], h, hoff, med)
+        index.close()
+        return finish(a, leg)
     out_hits, out_off, scores = torch.empty_like(h), torch.empty_like(hoff), torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev)
     go = _lib.VerifyGOpts(900, 0, K); gst = _lib.VerifyGStats(); n_out = C.c_uint64(0)
     Lb = _lib.lib()
@@ -177,6 +218,10 @@ def main():
             q_all.append(dt)
     leg["quantify_reads"] = dict(ms=med(q_all), ms_runs=q_all, pairs=Q, stats=q_stats)
 
+    finish(a, leg)
+
+
+def finish(a, leg):
     print(json.dumps(leg), flush=True)
     doc = dict(what=WHAT, runs=[])
     if os.path.exists(a.json):

@@ -1745,6 +1745,76 @@ SFGPU_API int sfgpu_covg_write_text(sfgpu_covg* g, const char* d_chrom_names, co
 SFGPU_API int sfgpu_covg_write_bgzf(sfgpu_covg* g, const char* d_chrom_names, const uint64_t* d_chrom_name_off, uint64_t chunk_bytes, sfgpu_bgzw* z,
                                     sfgpu_covg_result* out, sfgpu_stream stream);
 
+/* A batch of hit records and their alignment slots rewritten from transcript into GENOME terms through the exon blocks, so that the
+ * alignment writers above, opened over the chromosomes' names, write a genome-coordinate SAM / BAM with spliced CIGARs (the rule is
+ * stated once in csrc/galnfmt.h; hits.project_alignments_host is the Python statement; csrc/genomealn.hip).  The writers are not told:
+ * they take RNAME from tid, POS and CIGAR from the alignment group and count N in the reference span.
+ *   open     the model sfgpu_covg_open takes, validated by the same rule with the same errors; the handle keeps a copy and the 64-bit
+ *            prefix sums of the block lengths.
+ *   project  batch: hits / hit_off[n_reads + 1] (the offsets start at 0 and never decrease, else SFGPU_ERR_INVALID; a tid that is no
+ *            transcript of the model: SFGPU_ERR_RANGE naming the lowest record); aln_pos / aln_op_off / aln_ops: the transcript
+ *            alignment (all three or none, SFGPU_ERR_INVALID otherwise; none: the writer's <clip>S<match>M); aln_nm: the slots' nm
+ *            (optional; gathered); tag_nm / tag_md_off / tag_md: the NM / MD tags (all three or none).
+ *            A lane per record sizes it: the start block by binary search of the prefix sums, the words walked, which gives the
+ *            record's fate, each line's interval, its output words and MD bytes.  Three scans give the new record index (the new
+ *            hit_off[r] is that index at the old hit_off[r]), the word offsets and the MD offsets.  A lane per slot of a kept record
+ *            then writes the record (line 0's lane), the slot's position, nm and offsets, walks the words again to their places
+ *            (back to front on a - transcript) and copies or reverses the MD.
+ *            out: hits[n], hit_off[n_reads + 1], aln_pos[2 n], aln_nm[2 n], aln_op_off[2 n + 1], aln_ops[cap_ops], tag_nm[2 n],
+ *            tag_md_off[2 n + 1], tag_md[cap_md], src_record[n], n = hit_off[n_reads] of the batch; the entries of the kept records
+ *            are written (stats->records_out of them, two slots each, and one closing offset).  aln_nm may be NULL; the tag outputs
+ *            are read only where the batch gives tags.  *n_ops / *n_md = the words / MD bytes needed; where they exceed cap_ops /
+ *            cap_md: SFGPU_ERR_RANGE, both still set, nothing written.
+ * Operations shorter than 2^28 bases.  Synchronous.  The stats are SET by the call. */
+typedef struct sfgpu_galn sfgpu_galn;
+typedef struct sfgpu_galn_batch {
+    const struct sfgpu_hit* hits;
+    const uint32_t* hit_off;         /* [n_reads + 1] */
+    uint32_t n_reads;
+    uint32_t pad_;
+    const int32_t* aln_pos;          /* [2 records] */
+    const uint64_t* aln_op_off;      /* [2 records + 1] */
+    const uint32_t* aln_ops;
+    const uint32_t* aln_nm;          /* [2 records] */
+    const uint32_t* tag_nm;          /* [2 records] */
+    const uint64_t* tag_md_off;      /* [2 records + 1] */
+    const uint8_t* tag_md;
+} sfgpu_galn_batch;
+typedef struct sfgpu_galn_out {
+    struct sfgpu_hit* hits;
+    uint32_t* hit_off;
+    int32_t* aln_pos;
+    uint32_t* aln_nm;
+    uint64_t* aln_op_off;
+    uint32_t* aln_ops;
+    uint64_t cap_ops;
+    uint32_t* tag_nm;
+    uint64_t* tag_md_off;
+    uint8_t* tag_md;
+    uint64_t cap_md;
+    uint32_t* src_record;
+} sfgpu_galn_out;
+typedef struct sfgpu_galn_stats {
+    uint64_t records_in, records_out;
+    uint64_t records_unplaced;        /* the transcript is not placed, or has no block */
+    uint64_t records_unalignable;     /* a line without a reference column */
+    uint64_t records_off_range;       /* a line that starts below 0 on its transcript, leaves [0, 2^31 - 1] on the chromosome or needs an N of 2^28 or more */
+    uint64_t reads_emptied;           /* reads that had records and keep none */
+    uint64_t lines;                   /* of the kept records, as the following */
+    uint64_t lines_spliced;           /* lines with an N */
+    uint64_t n_operations;            /* N operations inserted */
+    uint64_t lines_reversed;          /* lines of - transcripts */
+    uint64_t columns_beyond_model;    /* reference columns at or beyond the blocks' total length */
+    uint64_t words_in, words_out;
+    double project_ms;                /* device events around the whole pass */
+    double size_ms, scan_ms, emit_ms; /* ... by stage: the check and the size kernel; the three scans; the counts' way to the host, the reads and the emit kernel */
+} sfgpu_galn_stats;
+SFGPU_API int sfgpu_galn_open(sfgpu_galn** out, const uint8_t* d_status, const int32_t* d_chrom, const int8_t* d_strand, const uint64_t* d_exon_off,
+                              const uint32_t* d_exon_start, const uint32_t* d_exon_len, uint64_t M, uint32_t n_chrom, sfgpu_stream stream);
+SFGPU_API int sfgpu_galn_close(sfgpu_galn* g);
+SFGPU_API int sfgpu_galn_project(sfgpu_galn* g, const sfgpu_galn_batch* batch, const sfgpu_galn_out* out, uint64_t* n_ops, uint64_t* n_md,
+                                 sfgpu_galn_stats* stats, sfgpu_stream stream);
+
 /* The samples the same loop collects when bias correction is on (one more pass over the hit records, for the
  * callers that need it): for every read, the 6-mer context of the FIRST hit that yields one (needBiasSample,
  * src/SailfishQuantify.cpp:270-287 / :559-581; ReadKmerDist<6>::update, include/ReadKmerDist.hpp:35-73), while

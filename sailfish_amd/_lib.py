@@ -359,6 +359,26 @@ class CovgResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# sfgpu_galn_batch / sfgpu_galn_out / sfgpu_galn_stats: every pointer a device address or None
+class GalnBatch(C.Structure):
+    _fields_ = [("hits", _P), ("hit_off", _P), ("n_reads", C.c_uint32), ("pad_", C.c_uint32), ("aln_pos", _P), ("aln_op_off", _P), ("aln_ops", _P),
+                ("aln_nm", _P), ("tag_nm", _P), ("tag_md_off", _P), ("tag_md", _P)]
+
+
+class GalnOut(C.Structure):
+    _fields_ = [("hits", _P), ("hit_off", _P), ("aln_pos", _P), ("aln_nm", _P), ("aln_op_off", _P), ("aln_ops", _P), ("cap_ops", C.c_uint64),
+                ("tag_nm", _P), ("tag_md_off", _P), ("tag_md", _P), ("cap_md", C.c_uint64), ("src_record", _P)]
+
+
+class GalnStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("records_in", "records_out", "records_unplaced", "records_unalignable", "records_off_range", "reads_emptied",
+                                          "lines", "lines_spliced", "n_operations", "lines_reversed", "columns_beyond_model", "words_in", "words_out")] + \
+               [(k, C.c_double) for k in ("project_ms", "size_ms", "scan_ms", "emit_ms")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _SIGS = {
     "sfgpu_version": (C.c_int, []),
     "sfgpu_has_variants": (C.c_int, []),
@@ -477,6 +497,9 @@ _SIGS = {
     "sfgpu_covg_runs": (C.c_int, [_P, _P, _P, _P, _P]),
     "sfgpu_covg_write_text": (C.c_int, [_P, _P, _P, C.c_uint64, TEXT_SINK, _P, C.POINTER(CovgResult), _P]),
     "sfgpu_covg_write_bgzf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.POINTER(CovgResult), _P]),
+    "sfgpu_galn_open": (C.c_int, [C.POINTER(_P), _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P]),
+    "sfgpu_galn_close": (C.c_int, [_P]),
+    "sfgpu_galn_project": (C.c_int, [_P, C.POINTER(GalnBatch), C.POINTER(GalnOut), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(GalnStats), _P]),
     "sfgpu_gc_prefix": (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P]),
     "sfgpu_sample_bias": (C.c_int, [_P, _P, C.c_uint32, C.POINTER(FilterOpts), C.POINTER(BiasSampler), _P]),
     "sfgpu_bias_create": (C.c_int, [C.POINTER(_P), C.POINTER(BiasInputs), _P]),

@@ -242,6 +242,34 @@ class ExonModel:
             off[i + 1] = len(starts)
         return Placement(status, chrom, strand, off, np.array(starts, np.uint32), np.array(lens, np.uint32), len(self.chrom_names), list(self.chrom_names))
 
+    def chrom_lengths(self, sizes=None):
+        """LN of every chromosome, in the order of chrom_names, for the @SQ lines of a genome-coordinate mappings file.  sizes: the path
+        of a chrom.sizes / .fai-style file -- the first two tab-separated columns of every line that is not empty are the name (bytes,
+        matched exactly) and the decimal length; a chromosome of the model that the file does not name is a ValueError, as is a
+        length that is no decimal integer.  Without it LN is the furthest exon end of a placed transcript on that chromosome (1 where
+        none is placed there): a LOWER bound of the chromosome's length, which viewers accept; give `sizes` where a tool compares LN
+        with its own genome."""
+        if sizes is not None:
+            table = {}
+            with open(sizes, "rb") as f:
+                for no, line in enumerate(f.read().split(b"\n"), 1):
+                    line = line[:-1] if line.endswith(b"\r") else line
+                    if not line:
+                        continue
+                    cols = line.split(b"\t")
+                    if len(cols) < 2 or not (cols[1].isdigit() and cols[1].isascii()):
+                        raise ValueError(f"{sizes}: line {no}: expected a name, a tab and a decimal length")
+                    table.setdefault(cols[0], int(cols[1]))
+            missing = [c for c in self.chrom_names if c not in table]
+            if missing:
+                raise ValueError(f"{sizes}: no length for chromosome {missing[0].decode('utf-8', 'replace')!r} of the annotation ({len(missing)} missing)")
+            return [table[c] for c in self.chrom_names]
+        ends = [1] * len(self.chrom_names)
+        for status, c, _, blocks in self.transcripts.values():
+            if status == 0:
+                ends[c] = max([ends[c]] + [gs + n for gs, n in blocks])
+        return ends
+
 
 HOST_REASONS = {1: "a byte >= 0x80", 2: "a NUL byte", 4: "a '\\r' that is not followed by '\\n'", 8: "a name longer than 256 bytes"}
 

@@ -1239,3 +1239,283 @@ def coverage_genome_host(runs, placement, ref_len=None, with_distinct=False):
     if with_distinct:
         st["n_distinct"], st["n_long"] = len(delta), n_long
     return (np.array(out[0], np.uint32), np.array(out[1], np.uint32), np.array(out[2], np.uint32), np.array(out[3], np.uint64)), st
+
+
+GENOME_ALN_STATS = ("records_in", "records_out", "records_unplaced", "records_unalignable", "records_off_range", "reads_emptied", "lines", "lines_spliced",
+                    "n_operations", "lines_reversed", "columns_beyond_model", "words_in", "words_out")
+GALN_MAX_END = (1 << 31) - 1                            # a line's interval ends at or below it
+GALN_MAX_OP = 1 << 28                                   # an operation is shorter
+_MD_COMP = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+def md_reverse(md):
+    """csrc/galnfmt.h's MD of a line on a - transcript: the tokens num (letter | ^letters) num ... in reverse order, a letter complemented
+    (A<->T, C<->G, everything else as it is), a deletion's letters reversed and complemented: b"5^AC0T3" -> b"3A0^GT5" """
+    tokens, i, n = [], 0, len(md)
+    while i < n:
+        j = i + 1
+        if 48 <= md[i] <= 57:
+            while j < n and 48 <= md[j] <= 57:
+                j += 1
+            tokens.append(md[i:j])
+        elif md[i] == 94:
+            while j < n and not 48 <= md[j] <= 57 and md[j] != 94:
+                j += 1
+            tokens.append(b"^" + md[i + 1:j].translate(_MD_COMP)[::-1])
+        else:
+            tokens.append(md[i:j].translate(_MD_COMP))
+        i = j
+    return b"".join(reversed(tokens))
+
+
+def _galn_line_host(words, x0, blocks, strand):
+    """One line by the rule of csrc/galnfmt.h, column by column: words = its transcript CIGAR, x0 = POS - 1 >= 0, blocks = the
+    transcript's [(gs, len)] in transcript order (at least one) -> (the words in transcript order, lo, hi, N operations, columns beyond
+    the model, whether an N is too long)"""
+    toff = [0]
+    for _, ln in blocks:
+        toff.append(toff[-1] + ln)
+    L, last = toff[-1], len(blocks) - 1
+    out, x, b, prev, first, n_N, beyond, too_long = [], x0, 0, None, None, 0, 0, False
+    for w in words:
+        n, op = w >> 4, w & 15
+        if op not in _MATCH_OPS + _DEL_OPS or n == 0:
+            out.append(w)
+            continue
+        cur = 0
+        for _ in range(n):
+            while b < last and x >= toff[b + 1]:
+                b += 1
+            d = x - toff[b]
+            g = blocks[b][0] + d if strand > 0 else blocks[b][0] + blocks[b][1] - 1 - d
+            if prev is not None and abs(g - prev) > 1:      # the column does not touch the one before it: a junction lies between them
+                if cur:
+                    out.append(cur << 4 | op)
+                    cur = 0
+                gap = abs(g - prev) - 1
+                out.append(gap << 4 | 3)
+                n_N += 1
+                too_long |= gap >= GALN_MAX_OP
+            first = g if first is None else first
+            beyond += x >= L
+            prev, cur, x = g, cur + 1, x + 1
+        out.append(cur << 4 | op)
+    lo, hi = (first, prev + 1) if strand > 0 else (prev, first + 1)
+    return out, lo, hi, n_N, beyond, too_long
+
+
+def project_alignments_host(hits, offsets, placement, alignments=None, tags=None):
+    """The statement of the projection of a batch onto the genome (csrc/galnfmt.h restated in plain loops with Python integers; what
+    sfgpu_galn_project is judged by).  hits / offsets: HIT_DTYPE records in CSR form over the reads; placement: genes.ExonModel.for_names'
+    result for the transcripts the records name; alignments: what align_hits / align_hits_host returned for the same records (pos, nm,
+    op_off, ops, ...) or None for the writer's <clip>S<match>M; tags: what md_tags / md_tags_host returned (nm, md_off, md, ...) or None.
+    A record is kept iff its transcript is placed (status 0 and at least one block), every line -- line 0, and line 1 of a mate_status
+    3 record -- has a reference column (an M = X D N word of length > 0), and every line starts at x0 >= 0, projects into
+    [0, 2^31 - 1] and needs no N of 2^28 bases or more; the first failing test counts it as records_unplaced, records_unalignable or
+    records_off_range.  A kept line's reference columns are placed in the blocks (beyond the blocks' total length the last block goes
+    on: columns_beyond_model); where two consecutive columns do not touch on the chromosome the word is cut and <gap>N put between
+    them; on a - transcript the words are reversed, fwd / mate_fwd inverted and the MD reversed (md_reverse).  The record takes tid =
+    the chromosome id, pos / mate_pos = its lines' 0-based genome positions, frag_len of a pair = the span of both lines.
+    -> (hits, offsets uint32[R + 1], alignments = (pos int32[2 n'], nm uint32[2 n'], op_off uint64[2 n' + 1], ops uint32[]),
+        tags = (nm, md_off, md) or None, src_record uint32[n'], stats dict of GENOME_ALN_STATS); ValueError naming the lowest record
+    whose tid is not a transcript of the placement."""
+    hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    off = np.asarray(offsets).astype(np.int64)
+    n_rec = int(off[-1]) if len(off) else 0
+    status, chrom, strand, exon_off, exon_start, exon_len = (np.asarray(getattr(placement, k)) for k in ("status", "chrom", "strand", "exon_off", "exon_start", "exon_len"))
+    M = len(status)
+    bad = np.nonzero(hits["tid"][:n_rec] >= M)[0]
+    if len(bad):
+        raise ValueError(f"record {int(bad[0])} names transcript >= {M}")
+    host = lambda v, dt: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)).view(dt).reshape(-1)      # noqa: E731
+    aln = tg = None
+    if alignments is not None:
+        aln = host(alignments[0], np.int32), host(alignments[1], np.uint32), host(alignments[2], np.uint64), host(alignments[3], np.uint32)
+        if len(aln[0]) != 2 * n_rec or len(aln[2]) != 2 * n_rec + 1:
+            raise ValueError(f"an alignment of {len(aln[0])} slots for {n_rec} records (two slots a record)")
+    if tags is not None:
+        tg = host(tags[0], np.uint32), host(tags[1], np.uint64), host(tags[2], np.uint8).tobytes()
+        if len(tg[0]) != 2 * n_rec or len(tg[1]) != 2 * n_rec + 1:
+            raise ValueError(f"tags of {len(tg[0])} slots for {n_rec} records (two slots a record)")
+    st = dict.fromkeys(GENOME_ALN_STATS, 0)
+    o_hits, o_off, o_pos, o_nm, o_cnt, o_ops, t_nm, t_cnt, t_md, src = [], [0], [], [], [], [], [], [], [], []
+    for r in range(len(off) - 1):
+        for i in range(int(off[r]), int(off[r + 1])):
+            h = hits[i]
+            t, two = int(h["tid"]), int(h["mate_status"]) == 3
+            st["records_in"] += 1
+            blocks = [(int(exon_start[e]), int(exon_len[e])) for e in range(int(exon_off[t]), int(exon_off[t + 1]))]
+            if status[t] != 0 or not blocks:
+                st["records_unplaced"] += 1
+                continue
+            lines = []
+            for j in range(2 if two else 1):
+                s = 2 * i + j
+                if aln is not None:
+                    words, x0 = [int(w) for w in aln[3][int(aln[2][s]):int(aln[2][s + 1])]], int(aln[0][s])
+                else:
+                    pos, length = (int(h["mate_pos"]), int(h["mate_len"])) if j else (int(h["pos"]), int(h["read_len"]))
+                    if pos >= 0:
+                        words, x0 = [length << 4], pos
+                    elif -pos < length:
+                        words, x0 = [-pos << 4 | CIGAR_S, (length + pos) << 4], 0
+                    else:
+                        words, x0 = [], 0
+                lines.append((words, x0))
+            if any(not any((w & 15) in _MATCH_OPS + _DEL_OPS and w >> 4 for w in words) for words, _ in lines):
+                st["records_unalignable"] += 1
+                continue
+            walked = [None if x0 < 0 else _galn_line_host(words, x0, blocks, int(strand[t])) for words, x0 in lines]
+            if any(w is None or w[1] < 0 or w[2] > GALN_MAX_END or w[5] for w in walked):
+                st["records_off_range"] += 1
+                continue
+            st["records_out"] += 1
+            rev = int(strand[t]) < 0
+            rec = h.copy()
+            rec["tid"], rec["pos"] = int(chrom[t]), walked[0][1]
+            if two:
+                rec["mate_pos"] = walked[1][1]
+                rec["frag_len"] = max(walked[0][2], walked[1][2]) - min(walked[0][1], walked[1][1])
+            if rev:
+                rec["fwd"], rec["mate_fwd"] = int(not h["fwd"]), int(not h["mate_fwd"])
+            o_hits.append(rec)
+            src.append(i)
+            for j in range(2):
+                s = 2 * i + j
+                if j == 1 and not two:
+                    o_pos.append(0); o_nm.append(0); o_cnt.append(0); t_nm.append(0); t_cnt.append(0)
+                    continue
+                out, lo, _, n_N, beyond, _ = walked[j]
+                st["lines"] += 1
+                st["lines_spliced"] += int(n_N > 0)
+                st["n_operations"] += n_N
+                st["lines_reversed"] += int(rev)
+                st["columns_beyond_model"] += beyond
+                st["words_in"] += len(lines[j][0])
+                st["words_out"] += len(out)
+                o_pos.append(lo)
+                o_nm.append(int(aln[1][s]) if aln is not None else 0)
+                o_cnt.append(len(out))
+                o_ops += out[::-1] if rev else out
+                if tg is not None:
+                    md = tg[2][int(tg[1][s]):int(tg[1][s + 1])]
+                    t_nm.append(int(tg[0][s])); t_cnt.append(len(md))
+                    t_md.append(md_reverse(md) if rev else md)
+        st["reads_emptied"] += int(off[r + 1] > off[r] and len(o_hits) == o_off[-1])
+        o_off.append(len(o_hits))
+    csr = lambda counts: np.concatenate([[0], np.cumsum(np.array(counts, np.uint64), dtype=np.uint64)]).astype(np.uint64)      # noqa: E731
+    out_hits = np.array(o_hits, dtype=HIT_DTYPE) if o_hits else np.zeros(0, HIT_DTYPE)
+    out_aln = (np.array(o_pos, np.int32), np.array(o_nm, np.uint32), csr(o_cnt), np.array(o_ops, np.uint32))
+    out_tags = (np.array(t_nm, np.uint32), csr(t_cnt), np.frombuffer(b"".join(t_md), np.uint8)) if tg is not None else None
+    return out_hits, np.array(o_off, np.uint32), out_aln, out_tags, np.array(src, np.uint32), st
+
+
+class GenomeAlignments:
+    """GenomeAlignments(placement, device): the exon model on the device for project_alignments (sfgpu_galn_open: validated by the
+    rule of the genome coverage's model, an SfgpuError naming the lowest offending transcript otherwise).  close() frees it; usable as
+    a context manager.  `stats` sums the counters of the batches projected through it."""
+
+    def __init__(self, placement, device="cuda"):
+        self._L, self._h = _lib.lib(), None
+        self.device = torch.device(device)
+        dev = lambda a, dt, bits: torch.from_numpy(np.ascontiguousarray(a, dt).view(bits).copy()).to(self.device)      # noqa: E731
+        model = (dev(placement.status, np.uint8, np.uint8), dev(placement.chrom, np.int32, np.int32), dev(placement.strand, np.int8, np.int8),
+                 dev(placement.exon_off, np.uint64, np.int64), dev(placement.exon_start, np.uint32, np.int32), dev(placement.exon_len, np.uint32, np.int32))
+        self.M, self.n_chrom = int(model[0].numel()), int(placement.n_chrom)
+        if model[1].numel() != self.M or model[2].numel() != self.M or model[3].numel() != self.M + 1:
+            raise ValueError(f"the placement is not one of {self.M} transcripts")
+        E = int(placement.exon_off[-1])
+        if model[4].numel() != E or model[5].numel() != E:
+            raise ValueError(f"the placement's offsets end at {E} but it holds {model[4].numel()} block starts and {model[5].numel()} lengths")
+        self.stats = dict.fromkeys(GENOME_ALN_STATS, 0)
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()
+            _lib.check(self._L.sfgpu_galn_open(C.byref(h), *(_lib.ptr(t) if t.numel() else None for t in model[:3]), _lib.ptr(model[3]),
+                                               *(_lib.ptr(t) if t.numel() else None for t in model[4:]), self.M, self.n_chrom, _lib.current_stream_ptr()))
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            with torch.cuda.device(self.device):
+                self._L.sfgpu_galn_close(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+
+def project_alignments(hits, offsets, placement, alignments=None, tags=None, *, device="cuda", _room=None):
+    """project_alignments_host on the device (sfgpu_galn_project; csrc/genomealn.hip).  hits / offsets: a batch as map_reads returns it
+    (device tensors) or numpy arrays; placement: genes.ExonModel.for_names' result, or a GenomeAlignments made of one (a run opens the
+    model once); alignments / tags: what align_hits / md_tags returned for the same records, or None.  The words' room is sized at the
+    words given plus two a slot (an ungapped line has at most two words), the MD's at the bytes given, and the call repeated once with the counts the library
+    reports where they do not fit (_room = (words, MD bytes) overrides the first sizes: for tests).
+    -> (hits uint8 tensor of HIT_DTYPE records, offsets int32[R + 1], alignments = (pos int32[2 n'], nm int32[2 n'], op_off int64[2 n' + 1],
+        ops int32[]), tags = (nm int32[2 n'], md_off int64[2 n' + 1], md uint8[]) or None, src_record int32[n'], stats dict of
+        GENOME_ALN_STATS): device tensors, the bits of the unsigned values."""
+    own = not isinstance(placement, GenomeAlignments)
+    g = GenomeAlignments(placement, device) if own else placement
+    try:
+        dev = g.device
+        d_hits, d_off = _device_hits(hits, offsets, dev)
+        R, n = int(d_off.numel()) - 1, d_hits.numel() // 24
+        signed = {1: np.uint8, 4: np.int32, 8: np.int64}
+        up = lambda v: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v).view(signed[v.dtype.itemsize]).copy())).to(dev).contiguous()      # noqa: E731
+        some = lambda t, dt: t if t.numel() else torch.zeros(1, dtype=dt, device=dev)      # noqa: E731  (nothing at all: still "given")
+        b = _lib.GalnBatch(_lib.ptr(d_hits) if n else None, _lib.ptr(d_off), max(R, 0), 0)
+        keep, words_in, md_in = [d_hits, d_off], 0, 0
+        if alignments is not None:
+            a_pos, a_nm, a_off, a_ops = (up(alignments[i]) for i in range(4))
+            if int(a_pos.numel()) != 2 * n or int(a_off.numel()) != 2 * n + 1 or int(a_nm.numel()) != 2 * n:
+                raise ValueError(f"an alignment of {int(a_pos.numel())} slots for {n} records (two slots a record)")
+            words_in = int(a_ops.numel())
+            a_pos, a_nm, a_ops = some(a_pos, torch.int32), some(a_nm, torch.int32), some(a_ops, torch.int32)
+            b.aln_pos, b.aln_op_off, b.aln_ops, b.aln_nm = _lib.ptr(a_pos), _lib.ptr(a_off), _lib.ptr(a_ops), _lib.ptr(a_nm)
+            keep += [a_pos, a_nm, a_off, a_ops]
+        if tags is not None:
+            t_nm, t_off, t_md = (up(tags[i]) for i in range(3))
+            if int(t_nm.numel()) != 2 * n or int(t_off.numel()) != 2 * n + 1:
+                raise ValueError(f"tags of {int(t_nm.numel())} slots for {n} records (two slots a record)")
+            md_in = int(t_md.numel())
+            t_nm, t_md = some(t_nm, torch.int32), some(t_md, torch.uint8)
+            b.tag_nm, b.tag_md_off, b.tag_md = _lib.ptr(t_nm), _lib.ptr(t_off), _lib.ptr(t_md)
+            keep += [t_nm, t_off, t_md]
+        o_hits = torch.zeros(max(n, 1) * 24, dtype=torch.uint8, device=dev)
+        o_off = torch.zeros(R + 1, dtype=torch.int32, device=dev)
+        o_pos, o_nm, o_tnm = (torch.zeros(max(2 * n, 1), dtype=torch.int32, device=dev) for _ in range(3))
+        o_aoff, o_moff = (torch.zeros(2 * n + 1, dtype=torch.int64, device=dev) for _ in range(2))
+        src = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        st, need_ops, need_md = _lib.GalnStats(), C.c_uint64(0), C.c_uint64(0)
+        cap_ops, cap_md = (words_in + 4 * n, md_in) if _room is None else (int(_room[0]), int(_room[1]))
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream().synchronize()
+            for attempt in range(2):
+                ops = torch.zeros(max(cap_ops, 1), dtype=torch.int32, device=dev)
+                md = torch.zeros(max(cap_md, 1), dtype=torch.uint8, device=dev)
+                o = _lib.GalnOut(_lib.ptr(o_hits), _lib.ptr(o_off), _lib.ptr(o_pos), _lib.ptr(o_nm), _lib.ptr(o_aoff), _lib.ptr(ops), cap_ops,
+                                 _lib.ptr(o_tnm), _lib.ptr(o_moff), _lib.ptr(md), cap_md, _lib.ptr(src))
+                rc = g._L.sfgpu_galn_project(g._h, C.byref(b), C.byref(o), C.byref(need_ops), C.byref(need_md), C.byref(st), _lib.current_stream_ptr())
+                if rc != _lib.ERR_RANGE or attempt or (need_ops.value <= cap_ops and need_md.value <= cap_md):
+                    break
+                cap_ops, cap_md = max(cap_ops, int(need_ops.value)), max(cap_md, int(need_md.value))
+            _lib.check(rc)
+        del keep
+        stats = {k: int(getattr(st, k)) for k in GENOME_ALN_STATS}
+        for k, v in stats.items():
+            g.stats[k] += v
+        m = stats["records_out"]
+        out_tags = (o_tnm[:2 * m], o_moff[:2 * m + 1], md[:int(need_md.value)]) if tags is not None else None
+        return o_hits[:24 * m], o_off, (o_pos[:2 * m], o_nm[:2 * m], o_aoff[:2 * m + 1], ops[:int(need_ops.value)]), out_tags, src[:m], dict(stats, project_ms=st.project_ms)
+    finally:
+        if own:
+            g.close()

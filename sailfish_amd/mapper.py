@@ -232,6 +232,14 @@ class _UnmappedWriters:
         return dict(reads=self.reads, unmapped=self.unmapped, bytes=[w.stats["bytes"] for w in self.writers])
 
 
+def _host_names(names):
+    """the transcripts' names as a host list; names on the device give their bytes, never decoded"""
+    if isinstance(names, tuple) and isinstance(names[0], torch.Tensor):
+        blob, off = (x.cpu().numpy() for x in names)
+        return [blob[a:b].tobytes() for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+    return names
+
+
 class _MappingsRun:
     """What quantify_reads and quantify_files share from the mapper's call to the files beside the estimates: the
     options' checks, the two kinds of writers, a batch's map -> rescue -> validate -> align -> tag -> write, the counters added up over the
@@ -240,15 +248,27 @@ class _MappingsRun:
     def __init__(self, paired, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                  mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates=False, rescue_window=None, lib_format=None, sopt=None,
                  mappings_posteriors=False, write_coverage=None, coverage_weights="posterior", coverage_compress=False, out_dir=None,
-                 write_genome_coverage=None, coverage_annotation=None):
+                 write_genome_coverage=None, coverage_annotation=None, write_genome_mappings=None, genome_annotation=None, genome_sizes=None):
         from .hits import ALIGNG_STATS, MDTAG_STATS, POSTERIOR_STATS
+        if write_genome_mappings is None and (genome_annotation is not None or genome_sizes is not None):
+            raise ValueError("genome_annotation and genome_sizes need write_genome_mappings")
+        if write_genome_mappings is not None:
+            if not _is_sink(write_genome_mappings):
+                raise ValueError("write_genome_mappings: one path or binary file object")
+            if genome_annotation is None and coverage_annotation is None:
+                raise ValueError("write_genome_mappings needs genome_annotation (the GTF with the exons), or coverage_annotation to serve as it")
+            if genome_annotation is not None and coverage_annotation is not None and os.fspath(genome_annotation) != os.fspath(coverage_annotation):
+                raise ValueError(f"one run reads one annotation: genome_annotation is {genome_annotation!r}, coverage_annotation {coverage_annotation!r}")
+            if genome_annotation is None:
+                genome_annotation = coverage_annotation
+        any_mappings = write_mappings is not None or write_genome_mappings is not None
         if coverage_weights not in ("posterior", "uniform"):
             raise ValueError(f'coverage_weights is "posterior" or "uniform", not {coverage_weights!r}')
         if write_coverage is None and write_genome_coverage is None and coverage_compress:
             raise ValueError("coverage_compress=True needs write_coverage or write_genome_coverage")
         if write_coverage is not None and not _is_sink(write_coverage):
             raise ValueError("write_coverage: one path or binary file object")
-        if (write_genome_coverage is None) != (coverage_annotation is None):
+        if (write_genome_coverage is None) != (coverage_annotation is None) and not (write_genome_coverage is None and write_genome_mappings is not None):
             raise ValueError("write_genome_coverage and coverage_annotation (the GTF with the exons) come together")
         if write_genome_coverage is not None and not _is_sink(write_genome_coverage):
             raise ValueError("write_genome_coverage: one path or binary file object")
@@ -258,15 +278,15 @@ class _MappingsRun:
         self.validate, vstats = _validation(validate_mappings, min_identity, keep_best, max_indel)
         astats = tstats = None
         if mappings_gapped:
-            if write_mappings is None or not validate_mappings or not (self.validate or {}).get("max_indel"):
-                raise ValueError("mappings_gapped=True needs write_mappings, validate_mappings=True and a max_indel of 1 .. 15")
+            if not any_mappings or not validate_mappings or not (self.validate or {}).get("max_indel"):
+                raise ValueError("mappings_gapped=True needs write_mappings or write_genome_mappings, validate_mappings=True and a max_indel of 1 .. 15")
             self.validate, astats = dict(self.validate, align=True), dict.fromkeys(ALIGNG_STATS, 0)
         if mappings_tags:
-            if write_mappings is None or not mappings_oriented:
-                raise ValueError("mappings_tags=True needs write_mappings and mappings_oriented=True")
+            if not any_mappings or not mappings_oriented:
+                raise ValueError("mappings_tags=True needs write_mappings or write_genome_mappings, and mappings_oriented=True")
             tstats = dict.fromkeys(MDTAG_STATS, 0)
-        if mappings_posteriors and write_mappings is None:
-            raise ValueError("mappings_posteriors=True needs write_mappings")
+        if mappings_posteriors and not any_mappings:
+            raise ValueError("mappings_posteriors=True needs write_mappings or write_genome_mappings")
         # With posteriors the reads pass twice: the first pass decides the records and quantifies them without a mappings
         # file, the second maps them again and writes the file with the estimates' weights.  `second`: which pass batch() serves;
         # `again`: the second pass's rescue / verify counters, which must reproduce the first's.
@@ -277,9 +297,15 @@ class _MappingsRun:
         # CoverageDevice; the annotation is read here, before anything is indexed: a bad line fails early.
         self.cov_sink, self.cov_compress, self.cov_dir = write_coverage, bool(coverage_compress), out_dir
         self.covg_sink, self.covg_model, self.covg_stats = write_genome_coverage, None, None
-        if write_genome_coverage is not None:
+        # The genome mappings file is the mappings file's batch projected through the same kind of model and written by a
+        # second SamDeviceWriter over the chromosomes; where both genome files are asked for, the GTF is read once.
+        self.gsink, self.gmodel, self.gsizes, self.galn, self.gsam, self.galn_stats = write_genome_mappings, None, None, None, None, None
+        if write_genome_coverage is not None or write_genome_mappings is not None:
             from .genes import ExonModel
-            self.covg_model = ExonModel.from_gtf(coverage_annotation)
+            model = ExonModel.from_gtf(coverage_annotation if write_genome_coverage is not None else genome_annotation)
+            self.covg_model = model if write_genome_coverage is not None else None
+            if write_genome_mappings is not None:
+                self.gmodel, self.gsizes = model, model.chrom_lengths(genome_sizes)
         self.cov_wanted = write_coverage is not None or write_genome_coverage is not None
         self.cov_posterior = self.cov_wanted and coverage_weights == "posterior"
         self.gapped = bool(mappings_gapped)
@@ -290,7 +316,7 @@ class _MappingsRun:
         self.targets, self.compress = _UnmappedWriters.targets(write_unmapped, unmapped_compress, paired), unmapped_compress
         self.paired, self.sink = paired, write_mappings
         self.sam_kw = dict(format=mappings_format, oriented=mappings_oriented, sort="coordinate" if mappings_sorted else None)
-        self.mapped, self.unmapped = write_mappings is not None, self.targets is not None       # which files the run writes
+        self.mapped, self.unmapped = any_mappings, self.targets is not None       # which files the run writes
         self.sam = self.unm = None
 
     def open(self, names, idx):
@@ -305,18 +331,26 @@ class _MappingsRun:
 
     def _open_sam(self, names, idx):
         from .samfile import SamDeviceWriter
-        self.sam = SamDeviceWriter(self.sink, names, idx.ref_len.cpu().numpy().view(np.uint32), self.paired, **self.sam_kw)
+        if self.sink is not None:
+            self.sam = SamDeviceWriter(self.sink, names, idx.ref_len.cpu().numpy().view(np.uint32), self.paired, **self.sam_kw)
+        if self.gsink is not None:
+            from .hits import GENOME_ALN_STATS, GenomeAlignments
+            placement = self.gmodel.for_names(_host_names(names))
+            self.galn = GenomeAlignments(placement, idx.device)
+            self.gsam = SamDeviceWriter(self.gsink, placement.chrom_names, self.gsizes, self.paired, **self.sam_kw)
+            self.galn_stats = dict(dict.fromkeys(GENOME_ALN_STATS, 0), transcripts=len(placement.status), transcripts_placed=int((placement.status == 0).sum()))
 
     def batch(self, idx, r1, r2, *, quals=(None, None), sam_quals=True, read_names=None, mate_names=(None, None)):
         """One batch: mapped (validated, aligned, tagged, as the options say), its counters added, and written to the run's files.
         r1 / r2: what map_reads takes (packed pairs on the device where the run writes a file); quals / mate_names: one entry per mate
         file; sam_quals: whether the mappings file takes the qualities too; read_names: its QNAMEs.  -> (hits, offsets)"""
         opt = {} if self.rescue is None else dict(rescue=self.rescue)              # (without the option the call is the one it was)
-        sam_now = self.sam is not None and self.second == self.posteriors       # the pass that writes the mappings file: the second with posteriors
+        writing = self.sam is not None or self.gsam is not None
+        sam_now = writing and self.second == self.posteriors       # the pass that writes the mappings files: the second with posteriors
         cov_now = self.cov is not None and self.second == self.cov_posterior    # ... that adds to the coverage: the second with posterior weights
         first = self.two_pass and not self.second
         validate = self.validate
-        if validate is not None and not (sam_now or (cov_now and self.gapped)) and (self.two_pass or self.sam is None):
+        if validate is not None and not (sam_now or (cov_now and self.gapped)) and (self.two_pass or not writing):
             validate = {key: v for key, v in validate.items() if key != "align"}      # only what decides the records runs: map -> rescue -> validate
         aligned = validate is not None and bool(validate.get("align"))
         tagged = self.stats["tag"] is not None and (sam_now or not self.two_pass)
@@ -344,9 +378,17 @@ class _MappingsRun:
             self.cov.add(h, o, posteriors=values[0] if self.cov_posterior else None, alignments=aln)
         if sam_now:
             q1, q2 = quals if sam_quals else (None, None)
-            self.sam.write(h, o, read_names=read_names, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2),
-                           alignments=idx.last_alignments if self.stats["align"] is not None else None, tags=idx.last_tags if self.stats["tag"] is not None else None,
-                           **post)
+            reads = dict(read_names=read_names, seqs=r1 if r2 is None else (r1, r2), quals=None if q1 is None and q2 is None else q1 if r2 is None else (q1, q2))
+            aln, tags = idx.last_alignments if self.stats["align"] is not None else None, idx.last_tags if self.stats["tag"] is not None else None
+            if self.sam is not None:
+                self.sam.write(h, o, **reads, alignments=aln, tags=tags, **post)
+            if self.gsam is not None:                     # the same batch in genome terms: projected, its per-record values gathered, written
+                from .hits import GENOME_ALN_STATS, project_alignments
+                g_h, g_o, g_aln, g_tags, src, st = project_alignments(h, o, self.galn, aln, tags)
+                for key in GENOME_ALN_STATS:
+                    self.galn_stats[key] += st[key]
+                g_post = dict(posteriors=tuple(v[src.long()] for v in post["posteriors"])) if post else {}
+                self.gsam.write(g_h, g_o, **reads, alignments=g_aln, tags=g_tags, **g_post)
         if self.unm is not None and not self.second:
             self.unm.write(o, (r1,) if r2 is None else (r1, r2), quals, mate_names)
         return h, o
@@ -394,11 +436,7 @@ class _MappingsRun:
         res = self.cov.finish()
         wrote = self.cov.write(self.cov_sink, names, compress=self.cov_compress) if self.cov_sink is not None else dict(n_bytes=0)
         if self.covg_sink is not None:
-            host = names
-            if isinstance(names, tuple) and isinstance(names[0], torch.Tensor):      # names on the device: their bytes, never decoded
-                blob, off = (x.cpu().numpy() for x in names)
-                host = [blob[a:b].tobytes() for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
-            placement = self.covg_model.for_names(host)
+            placement = self.covg_model.for_names(_host_names(names))
             with self.cov.project(placement) as g:
                 gw = g.write(self.covg_sink, placement.chrom_names, compress=self.cov_compress)
                 self.covg_stats = dict(g.result, transcripts=self.cov.M, bytes=int(gw["n_bytes"]))
@@ -410,7 +448,7 @@ class _MappingsRun:
                               state_bytes=res["state_bytes"], bytes=int(wrote["n_bytes"]), weights="posterior" if self.cov_posterior else "uniform")
 
     def close(self):
-        for w in (self.sam, self.unm, self.cov):
+        for w in (self.sam, self.gsam, self.galn, self.unm, self.cov):
             if w is not None:
                 w.close()
 
@@ -425,6 +463,7 @@ class _MappingsRun:
             exp.posterior_stats = ps
             exp.coverage_stats = self.cov_stats
             exp.genome_coverage_stats = self.covg_stats
+            exp.genome_mappings_stats = self.galn_stats
             if u is not None:
                 exp.unmapped_stats = u
         log = getattr(sopt, "jointLog", None) if sopt is not None else None
@@ -470,6 +509,15 @@ class _MappingsRun:
             if c["transcripts_length_mismatch"] > 0:
                 log(1, "write_genome_coverage: the exons of {} placed transcripts do not sum to the transcript's length; bases beyond the exons "
                        "are dropped".format(c["transcripts_length_mismatch"]))
+        if self.galn_stats is not None:
+            c = self.galn_stats
+            log(0, "genome mappings: {} of {} transcripts placed; {} of {} records written ({} on transcripts that are not placed, {} unalignable, {} off "
+                   "the chromosome's range); {} reads lost every record; {} lines, {} of them spliced by {} N operations, {} reversed; {} columns beyond "
+                   "the exons; {} words in, {} out".format(c["transcripts_placed"], c["transcripts"], c["records_out"], c["records_in"], c["records_unplaced"],
+                                                           c["records_unalignable"], c["records_off_range"], c["reads_emptied"], c["lines"], c["lines_spliced"],
+                                                           c["n_operations"], c["lines_reversed"], c["columns_beyond_model"], c["words_in"], c["words_out"]))
+            if c["transcripts_placed"] == 0:
+                log(1, "write_genome_mappings: the annotation places none of the {} transcripts (the names are matched byte for byte)".format(c["transcripts"]))
         if u is not None:
             log(0, "unmapped reads: {} of {} reads have no record and were written, {} bytes of {}".format(
                 u["unmapped"], u["reads"], " + ".join(str(b) for b in u["bytes"]), "FASTQ" if self.unm.writers[0].format == 2 else "FASTA"))
@@ -480,7 +528,7 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
                    write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
                    write_coverage=None, coverage_weights="posterior", coverage_compress=False, write_genome_coverage=None, coverage_annotation=None,
-                   **kw):
+                   write_genome_mappings=None, genome_annotation=None, genome_sizes=None, **kw):
     """`sailfish quant` from the reads on: index the transcriptome, map the reads in batches (the reference's parser jobs),
     and hand the hit records to quant.quantify (filtering, classes, effective lengths, EM, writers).  write_mappings: a path (or a
     binary file object) that receives every mapped batch as SAM, formatted on the device (samfile.SamDeviceWriter) before the batch
@@ -563,11 +611,27 @@ def quantify_reads(names, sequences, reads1, reads2, lib_format, out_dir, sopt=N
     annotation does not place (genes.EXON_STATUS) and bases beyond a transcript's exons are dropped and counted; the counters are left
     on the experiment as `genome_coverage_stats` (None without the option) and go to sopt.jointLog as one line, with a warning where
     no transcript is placed or where exons do not sum to a transcript's length.
+    write_genome_mappings: a path (or a binary file object) that receives the mappings in GENOME coordinates -- what `rsem
+    --output-genome-bam` is for: RNAME a chromosome, POS on it, introns as N in the CIGAR, reverse-strand transcripts turned round
+    (FLAG 0x10 / 0x20, SEQ, QUAL, the CIGAR's order and the MD all follow) -- with genome_annotation, the GTF whose `exon` records place
+    the transcripts (read once, on the host, before anything is indexed; where only coverage_annotation is given it serves; two
+    different annotations in one run are a ValueError), and optionally genome_sizes, a chrom.sizes / .fai-style file for the @SQ
+    lengths (genes.ExonModel.chrom_lengths: without it LN is the furthest exon end, a lower bound).  Every batch of the mappings
+    file is projected on the device (hits.project_alignments, csrc/galnfmt.h) behind map, rescue, validate, align, tag and the
+    posteriors, and written by a second SamDeviceWriter over the chromosomes: the file obeys mappings_format, mappings_oriented,
+    mappings_sorted (with its .bai), mappings_gapped, mappings_tags and mappings_posteriors as the transcript file does, and is
+    written in the same pass.  write_mappings is not required: the options that need a mappings file take either.  Records on
+    transcripts the annotation does not place, lines without a reference column and lines that leave [0, 2^31 - 1] are dropped and
+    counted; a read that keeps none is written unmapped; NH is the number of records the genome file shows for the read, and ZW
+    the transcript file's value, gathered and not renormalised over the kept records.  The estimates, the
+    transcript file and every other output never depend on it; the counters are left on the experiment as `genome_mappings_stats`
+    (None without the option) and go to sopt.jointLog as one line, with a warning where no transcript is placed.
     -> (rc, experiment)"""
     from . import quant
     run = _MappingsRun(reads2 is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                        mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
-                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation)
+                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation, write_genome_mappings,
+                       genome_annotation, genome_sizes)
     if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()
@@ -616,7 +680,7 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
                    validate_mappings=False, min_identity=0.9, keep_best=False, max_indel=0, mappings_gapped=False, mappings_tags=False,
                    write_unmapped=None, unmapped_compress=False, rescue_mates=False, rescue_window=None, mappings_posteriors=False,
                    write_coverage=None, coverage_weights="posterior", coverage_compress=False, write_genome_coverage=None, coverage_annotation=None,
-                   **kw):
+                   write_genome_mappings=None, genome_annotation=None, genome_sizes=None, **kw):
     """`sailfish quant` from the files on: the transcript FASTA and the read files (FASTA or FASTQ, plain or gzip; reads2_path =
     None: single end) are parsed on the device (readfile.ReadFile), the mate files in lockstep, batch_reads records each; the
     batches are mapped and handed to quant.quantify as in quantify_reads.  `inflate` is ReadFile's: where gzip files are inflated.
@@ -633,13 +697,14 @@ def quantify_files(transcripts_path, reads1_path, reads2_path, lib_format, out_d
     (quals=True on both, also when mappings_oriented is off: QUAL of the mappings file is then still '*'); a FASTA read file gives a
     FASTA unmapped file.  No name, base or offset visits the host.  write_coverage, coverage_weights, coverage_compress,
     write_genome_coverage and coverage_annotation as in quantify_reads (the transcripts' names are matched to the annotation by
-    their bytes as the FASTA has them).
+    their bytes as the FASTA has them).  write_genome_mappings, genome_annotation and genome_sizes as in quantify_reads.
     -> (rc, experiment)"""
     from . import quant
     from .readfile import ReadFile, mate_names_match, read_transcripts
     run = _MappingsRun(reads2_path is not None, write_mappings, mappings_format, mappings_oriented, mappings_sorted, validate_mappings, min_identity, keep_best, max_indel,
                        mappings_gapped, mappings_tags, write_unmapped, unmapped_compress, rescue_mates, rescue_window, lib_format, sopt, mappings_posteriors,
-                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation)
+                       write_coverage, coverage_weights, coverage_compress, out_dir, write_genome_coverage, coverage_annotation, write_genome_mappings,
+                       genome_annotation, genome_sizes)
     if run.two_pass and sopt is None:                      # (the second pass reads the columns under the options the run had)
         from .experiment import SailfishOpts
         sopt = SailfishOpts()
